@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — headline metric of BASELINE.json: jac_coord!+hess_coord! evaluation pairs
-per second on the quadrotor transcription (examples/quadrotor.jl) at 10^6 supports,
-with the achieved fraction of the gfx950 HBM roofline and a CPU baseline timed in the
-same run.
+per second on the quadrotor transcription (examples/quadrotor.jl) at 10^6 supports;
+with `--full`, also the achieved fraction of the gfx950 HBM roofline and a CPU baseline
+timed in the same run.
 
-  python bench.py --gpus N --steps K --warmup W [--supports S] [--scaling strong|weak]
+  python bench.py --gpus N --steps K --warmup W [--supports S] [--scaling strong|weak] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints the headline line (`value`, `ms_per_step` = milliseconds
+of one timed step).  Everything else — the other launch form of the pair, the per-step distribution, per-kernel and
+roofline figures, the live PMC traffic, cold inputs, the ESCAPE34 variant, the CPU baseline — runs only with `--full`
+(N > 1: the child-process check of the exchange below stays in a plain run, since it decides what the timed step contains).
+`--dump-outputs DIR` writes what the last timed step left in the jac / hess buffers as DIR/<name>.npy (see dump_outputs).
 
 A "step" is one jac_coord! + one hess_coord! over the resident model (inputs already in HBM): the metric's own call pair,
 iem_jac_coord + iem_hess_coord — what an NLPModels solver makes (ext/InfiniteExaModelsIpopt.jl:48-49,
 ext/InfiniteExaModelsMadNLP.jl:49-50).  The C-ABI's one-launch form of the pair (iem_jac_hess_coord, identical bytes) is
-reported beside it as "fused_pair" (`--fused` makes IT the timed step; then "separate_calls" is the one beside).  N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); the time
+reported beside it by `--full` as "fused_pair" (`--fused` makes IT the timed step; then "separate_calls" is the one beside).  N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); the time
 axis is sharded into contiguous support blocks (halo of one support for the
 finite-difference rows); jac_coord!/hess_coord! need no collective, so ranks only meet
 at the barriers that bracket the timed region.
@@ -27,7 +33,7 @@ the shard boundary before the rows that read them are evaluated.  The timed step
 `iem_halo_exchange_async(x); jac_coord!; hess_coord!` — the exchange INSIDE the timed region (key "halo_in_timed_loop").
 The library launches nothing for it: the exchange rides on the step's first launch as one extra leading workgroup, because
 that kernel's loads cannot touch a halo entry (csrc/iem_api.cpp: halo_plan; a call that can gets the stand-alone exchange
-kernel in front of it); the communication-free pair is reported beside it ("pair_no_halo").
+kernel in front of it); `--full` reports the communication-free pair beside it ("pair_no_halo").
 Before the ranks wire their mailboxes in-process, the same wiring + one checked exchange + one checked all-reduce
 run in CHILD processes (key "comm": peer-mapped memory is the one part that the one-GPU box can only rehearse with all
 ranks on one device — whatever it does on a real xGMI node must end in an entry of the line, never in a lost line).  If
@@ -116,6 +122,25 @@ def cpu_baseline(sample_supports: int, seconds: float = 12.0):
         "interpreter_value": interp, "interpreter": "oracle/iem_oracle.c (generic tree interpreter), 1 thread",
         "max_abs_diff_vs_oracle": agree,
     }
+
+
+DUMP_MAX_BYTES = 48_000_000   # --dump-outputs: the values of all files together, well under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: what the last timed step left in its output buffers, as DIR/<name>.npy in float64 (N > 1: every rank
+    its own shard's buffers, as DIR/<name>.rank<R>.npy).  An array over its share of DUMP_MAX_BYTES is written as a fixed
+    sample: the entries at the sorted distinct indices of a seed-0 draw that depends on the array's length alone, so two
+    builds of the project run with the same arguments write the same entries."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * len(arrays) * world)
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, n, cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.rank{rank}.npy" if world > 1 else f"{name}.npy"), t.to(torch.float64).cpu().numpy())
 
 
 def live_traffic(args):
@@ -362,13 +387,17 @@ def main():
     ap.add_argument("--force-rccl", action="store_true", help="N > 1: take the torch.distributed fallback of the halo exchange even when the mailboxes work")
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="no GPU, no evaluation, NOT a measurement: spawn / rendezvous / reduce only (CPU test of the N>1 launch path)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check beside the headline (other "
+                    "launch form, per-step distribution, roofline and per-kernel figures, live PMC traffic, cold inputs, ESCAPE34 "
+                    "variant, CPU baseline); the --no-* options above switch single ones off again — off by default")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the jac / hess values of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
     live, live_note = None, None
-    if (args.gpus == 1 and "RANK" not in os.environ and not args.no_live_traffic and not args.pmc_child and not args.emulate_shard and not args.rehearse_launch
+    if (args.full and args.gpus == 1 and "RANK" not in os.environ and not args.no_live_traffic and not args.pmc_child and not args.emulate_shard and not args.rehearse_launch
             and not os.environ.get("IEM_PMC_CHILD") and not any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)
             and "rocprof" not in os.environ.get("LD_PRELOAD", "")):
         live, live_note = live_traffic(args)     # before this process touches the GPU: one process on the card at a time
@@ -612,6 +641,8 @@ def main():
         barrier()
         dist.destroy_process_group()
         return
+    if args.dump_outputs:    # before anything else writes to jac / hess
+        dump_outputs(args.dump_outputs, {"jac_coord": jac, "hess_coord": hess}, rank, world)
 
     def timed_loop(fn, n):
         """max-over-ranks seconds of n calls of fn between barriers (secondary measurements, outside the headline region)"""
@@ -630,23 +661,24 @@ def main():
         return d
 
     n2 = min(args.steps, 200)
-    secondary = {}
-    # the other launch form of the same pair, and (N > 1) the same step without the exchange
-    other = gm.raw_pair(xd, yd, jac, hess, obj_weight=1.0, fused=not args.fused, halo=halo_state["path"] == "own")
-    secondary["fused_pair" if not args.fused else "separate_calls"] = {"ms_per_step": timed_loop(other, n2) / n2 * 1e3}
-    if halo_state["in_loop"]:
-        nohalo = gm.raw_pair(xd, yd, jac, hess, obj_weight=1.0, fused=args.fused, halo=False)
-        secondary["pair_no_halo"] = {"ms_per_step": timed_loop(nohalo, n2) / n2 * 1e3}
+    secondary, other = {}, None
+    if args.full:
+        # the other launch form of the same pair, and (N > 1) the same step without the exchange
+        other = gm.raw_pair(xd, yd, jac, hess, obj_weight=1.0, fused=not args.fused, halo=halo_state["path"] == "own")
+        secondary["fused_pair" if not args.fused else "separate_calls"] = {"ms_per_step": timed_loop(other, n2) / n2 * 1e3}
+        if halo_state["in_loop"]:
+            nohalo = gm.raw_pair(xd, yd, jac, hess, obj_weight=1.0, fused=args.fused, halo=False)
+            secondary["pair_no_halo"] = {"ms_per_step": timed_loop(nohalo, n2) / n2 * 1e3}
 
-    # distribution of single steps (median, p10/p90), HIP events on the
-    # launch stream, outside the timed region
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n2 + 1)]
-    ev[0].record()
-    for e in ev[1:]:
-        step()
-        e.record()
-    torch.cuda.synchronize()
-    pair_ms = np.array([a.elapsed_time(b) for a, b in zip(ev[:-1], ev[1:])])
+        # distribution of single steps (median, p10/p90), HIP events on the
+        # launch stream, outside the timed region
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(n2 + 1)]
+        ev[0].record()
+        for e in ev[1:]:
+            step()
+            e.record()
+        torch.cuda.synchronize()
+        pair_ms = np.array([a.elapsed_time(b) for a, b in zip(ev[:-1], ev[1:])])
 
     has_pair = any(k["kind"] == "pair" for k in gm.kernels())
 
@@ -662,12 +694,13 @@ def main():
         b.record()
         torch.cuda.synchronize()
         return a.elapsed_time(b) / n
-    ms_jac_blk = block_ms(lambda: gm.jac_coord(xd, jac))
-    ms_hess_blk = block_ms(lambda: gm.hess_coord(xd, yd, hess, obj_weight=1.0))
-    pair_kernel_ms = block_ms(lambda: gm.jac_hess_coord(xd, yd, jac, hess, obj_weight=1.0)) if has_pair else None
+    if args.full:
+        ms_jac_blk = block_ms(lambda: gm.jac_coord(xd, jac))
+        ms_hess_blk = block_ms(lambda: gm.hess_coord(xd, yd, hess, obj_weight=1.0))
+        pair_kernel_ms = block_ms(lambda: gm.jac_hess_coord(xd, yd, jac, hess, obj_weight=1.0)) if has_pair else None
     # the same pair with COLD inputs: K distinct (x, y) sets, > 256 MiB in total, cycled per call — per-kernel events
     cold = None
-    if world == 1 and not args.no_cold and not args.graph:
+    if args.full and world == 1 and not args.no_cold and not args.graph:
         K = max(4, int(np.ceil(300e6 / (8.0 * (gm.meta.nvar + gm.meta.ncon)))))
         K = max(2, args.rotate_inputs) if args.rotate_inputs else min(K, 64)
         xs = [xd] + [xd + 1e-3 * (i + 1) for i in range(K - 1)]
@@ -700,68 +733,69 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = supports_total / 1e6 * args.steps / dt
-        # roofline of the dominant kernel: its algorithmic bytes / its average launch duration, the latter from blocks of
-        # back-to-back launches between ONE pair of HIP events on the launch stream (block_ms) — never per-launch event pairs
-        ms_jac, ms_hess = ms_jac_blk, ms_hess_blk
         ks = {k["kind"]: k for k in gm.kernels() if k["kind"] in ("jac", "hess") and k["grid"][0] > 1}
-        pair_alg = sum(k["alg_bytes_read"] + k["alg_bytes_written"] for k in ks.values())     # two calls: each reads its own inputs
-        fused_kd = dict([k for k in gm.kernels() if k["kind"] == "pair"][0]) if has_pair else None
-        fused_alg = (fused_kd["alg_bytes_read"] + fused_kd["alg_bytes_written"]) if has_pair else None   # ONE launch: inputs both bodies load counted once
-        if args.fused and has_pair:
-            # the timed step is ONE kernel (both calls' workgroups behind one dispatcher): it is the dominant kernel
-            dom = "pair"
-            kd = fused_kd
-            alg, ms_dom = fused_alg, pair_kernel_ms
-        else:
-            dom = "hess" if ms_hess >= ms_jac else "jac"
-            kd = dict(ks[dom])
-            if gm._tuned.get(dom, -1) == 1:     # the tuner chose the handle's second code object for this buffer: its kernels carry a tag
-                kd["name"] += "_b48"
-            alg = kd["alg_bytes_read"] + kd["alg_bytes_written"]
-            ms_dom = ms_hess if dom == "hess" else ms_jac
-        achieved = alg / (ms_dom * 1e-3) / 1e9
-        # HBM bytes per launch from the PMC counters cannot be collected inside this process (they need rocprofv3
-        # passes of their own): read from the committed profile of the same command and size (tools/profile_gpu.sh →
-        # profiles/), which records the fingerprint of the csrc tree it was taken from — `traffic_stale` says whether
-        # that is THIS tree.
-        traffic, traffic_src, stale, traffic_static = None, None, None, True
-        prof = os.path.join(ROOT, "profiles", PMC_PROFILE)
-        if live and kd["name"] in live:
-            traffic, traffic_src, stale, traffic_static = live[kd["name"]], live_note, False, False
-        elif os.path.exists(prof) and S_local == 1_000_000 and world == 1:
-            try:
-                pj = json.load(open(prof))
-                traffic = pj["pmc"][kd["name"]]["hbm_bytes_per_launch"]
-                stale = pj.get("csrc_fingerprint") != csrc_fingerprint()
-                traffic_src = (f"profiles/{PMC_PROFILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; "
-                               f"csrc fingerprint {pj.get('csrc_fingerprint', 'n/a')}, commit {pj.get('commit', 'n/a')})")
-            except Exception:
-                traffic = None
         par = f"support-sharded x{world}, {args.scaling} scaling" + (f", shard {args.emulate_shard} emulated on one GPU" if args.emulate_shard else "")
         step_txt = ("iem_jac_hess_coord (one launch)" if args.fused else "iem_jac_coord + iem_hess_coord") + \
                    (" behind iem_halo_exchange_async(x)" if halo_state["path"] == "own" else
                     " behind a torch.distributed send/recv of the halo doubles (shard.ShardComm fallback)" if halo_state["path"] == "rccl" else "")
-        roof = {"bound": "hbm", "kernel": kd["name"], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_static": traffic_static,
-                "traffic_all_kernels": live, "traffic_note": None if live else live_note,
-                "traffic_stale": stale, "traffic_source": traffic_src, "csrc_fingerprint": csrc_fingerprint(),
-                "alg_bytes": alg, "kernel_ms": ms_dom, "kernel_ms_from": "100 back-to-back launches between one pair of HIP events on the launch stream",
-                "jac_ms": ms_jac, "hess_ms": ms_hess,
-                "jac_frac": (ks["jac"]["alg_bytes_read"] + ks["jac"]["alg_bytes_written"]) / (ms_jac * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "hess_frac": (ks["hess"]["alg_bytes_read"] + ks["hess"]["alg_bytes_written"]) / (ms_hess * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "pair_alg_bytes": fused_alg if (args.fused and has_pair) else pair_alg,
-                # the step's own fraction, from the HIP events that bracket the TIMED loop (all K steps between one event pair)
-                "step_event_ms": halo_state.get("loop_event_ms"),
-                "pair_frac": (fused_alg if (args.fused and has_pair) else pair_alg) / (halo_state["loop_event_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if pair_kernel_ms is not None:
-            roof["pair_kernel_ms"] = pair_kernel_ms
-            roof["pair_kernel_alg_bytes"] = fused_alg
-            roof["pair_kernel_frac"] = fused_alg / (pair_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        if cold:
-            cms = cold.get("pair_kernel_ms") if dom == "pair" else cold["hess_ms"] if dom == "hess" else cold["jac_ms"]
-            roof["frac_cold_inputs"] = alg / (cms * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof["pair_frac_cold_inputs"] = pair_alg / (cold["two_calls_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-            roof["cold_inputs"] = cold
+        if args.full:
+            # roofline of the dominant kernel: its algorithmic bytes / its average launch duration, the latter from blocks of
+            # back-to-back launches between ONE pair of HIP events on the launch stream (block_ms) — never per-launch event pairs
+            ms_jac, ms_hess = ms_jac_blk, ms_hess_blk
+            pair_alg = sum(k["alg_bytes_read"] + k["alg_bytes_written"] for k in ks.values())     # two calls: each reads its own inputs
+            fused_kd = dict([k for k in gm.kernels() if k["kind"] == "pair"][0]) if has_pair else None
+            fused_alg = (fused_kd["alg_bytes_read"] + fused_kd["alg_bytes_written"]) if has_pair else None   # ONE launch: inputs both bodies load counted once
+            if args.fused and has_pair:
+                # the timed step is ONE kernel (both calls' workgroups behind one dispatcher): it is the dominant kernel
+                dom = "pair"
+                kd = fused_kd
+                alg, ms_dom = fused_alg, pair_kernel_ms
+            else:
+                dom = "hess" if ms_hess >= ms_jac else "jac"
+                kd = dict(ks[dom])
+                if gm._tuned.get(dom, -1) == 1:     # the tuner chose the handle's second code object for this buffer: its kernels carry a tag
+                    kd["name"] += "_b48"
+                alg = kd["alg_bytes_read"] + kd["alg_bytes_written"]
+                ms_dom = ms_hess if dom == "hess" else ms_jac
+            achieved = alg / (ms_dom * 1e-3) / 1e9
+            # HBM bytes per launch from the PMC counters cannot be collected inside this process (they need rocprofv3
+            # passes of their own): read from the committed profile of the same command and size (tools/profile_gpu.sh →
+            # profiles/), which records the fingerprint of the csrc tree it was taken from — `traffic_stale` says whether
+            # that is THIS tree.
+            traffic, traffic_src, stale, traffic_static = None, None, None, True
+            prof = os.path.join(ROOT, "profiles", PMC_PROFILE)
+            if live and kd["name"] in live:
+                traffic, traffic_src, stale, traffic_static = live[kd["name"]], live_note, False, False
+            elif os.path.exists(prof) and S_local == 1_000_000 and world == 1:
+                try:
+                    pj = json.load(open(prof))
+                    traffic = pj["pmc"][kd["name"]]["hbm_bytes_per_launch"]
+                    stale = pj.get("csrc_fingerprint") != csrc_fingerprint()
+                    traffic_src = (f"profiles/{PMC_PROFILE} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; "
+                                   f"csrc fingerprint {pj.get('csrc_fingerprint', 'n/a')}, commit {pj.get('commit', 'n/a')})")
+                except Exception:
+                    traffic = None
+            roof = {"bound": "hbm", "kernel": kd["name"], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_static": traffic_static,
+                    "traffic_all_kernels": live, "traffic_note": None if live else live_note,
+                    "traffic_stale": stale, "traffic_source": traffic_src, "csrc_fingerprint": csrc_fingerprint(),
+                    "alg_bytes": alg, "kernel_ms": ms_dom, "kernel_ms_from": "100 back-to-back launches between one pair of HIP events on the launch stream",
+                    "jac_ms": ms_jac, "hess_ms": ms_hess,
+                    "jac_frac": (ks["jac"]["alg_bytes_read"] + ks["jac"]["alg_bytes_written"]) / (ms_jac * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "hess_frac": (ks["hess"]["alg_bytes_read"] + ks["hess"]["alg_bytes_written"]) / (ms_hess * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "pair_alg_bytes": fused_alg if (args.fused and has_pair) else pair_alg,
+                    # the step's own fraction, from the HIP events that bracket the TIMED loop (all K steps between one event pair)
+                    "step_event_ms": halo_state.get("loop_event_ms"),
+                    "pair_frac": (fused_alg if (args.fused and has_pair) else pair_alg) / (halo_state["loop_event_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            if pair_kernel_ms is not None:
+                roof["pair_kernel_ms"] = pair_kernel_ms
+                roof["pair_kernel_alg_bytes"] = fused_alg
+                roof["pair_kernel_frac"] = fused_alg / (pair_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            if cold:
+                cms = cold.get("pair_kernel_ms") if dom == "pair" else cold["hess_ms"] if dom == "hess" else cold["jac_ms"]
+                roof["frac_cold_inputs"] = alg / (cms * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof["pair_frac_cold_inputs"] = pair_alg / (cold["two_calls_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                roof["cold_inputs"] = cold
         line = {
             "metric": "jac_coord!+hess_coord! evals/sec, quadrotor 1e6 supports; % HBM roofline",
             "value": value, "unit": "jac+hess pairs/s (1e6-support quadrotor equivalent)",
@@ -777,12 +811,14 @@ def main():
                        "lds_bytes": {k: v["lds_bytes"] for k, v in ks.items()},
                        "store_batch_tuner": {**gm._tuned, "meaning": "-1 tuner off (default: the staging batch is a function of kind and grid size)"},
                        "kernels_from": "hiprtc at run time (code-object cache miss)" if any(k["jit"] for k in gm.kernels()) else "in-tree code-object cache"},
-            "roofline": roof,
         }
+        if args.full:
+            line["roofline"] = roof
         line["launch"] = {"world_size": dist.get_world_size() if use_dist else 1, "device_count": torch.cuda.device_count(), "process_group": bool(use_dist),
                           "rank_ms_per_step": halo_state.get("rank_ms_per_step")}
-        line["pair_ms"] = {"median": float(np.median(pair_ms)), "p10": float(np.percentile(pair_ms, 10)),
-                           "p90": float(np.percentile(pair_ms, 90)), "n": int(pair_ms.size)}
+        if args.full:
+            line["pair_ms"] = {"median": float(np.median(pair_ms)), "p10": float(np.percentile(pair_ms, 10)),
+                               "p90": float(np.percentile(pair_ms, 90)), "n": int(pair_ms.size)}
         for k, v in secondary.items():
             v["value"] = supports_total / 1e6 / (v["ms_per_step"] * 1e-3)
             line[k] = v
@@ -802,7 +838,7 @@ def main():
                 line["comm"] = comm
     # one-GPU rehearsal with many ranks: parents + children would exceed the box's per-GPU process limit — the checked
     # comm section runs in-process there
-    if world > 1 and use_dist and not args.no_comm and not args.no_comm_check and not args.emulate_shard and args.same_device and 2 * world > 6:
+    if args.full and world > 1 and use_dist and not args.no_comm and not args.no_comm_check and not args.emulate_shard and args.same_device and 2 * world > 6:
         ccomm = comm_section(gm, step, torch, dist, dev, red_dev, barrier, rank, world, n2, connect=halo_state["path"] != "own")
         if rank == 0:
             line["comm"] = ccomm
@@ -822,7 +858,7 @@ def main():
     # secondary measurement, outside the headline timed region: the reference's own benchmark VARIANT of the same model
     # (ESCAPE34/quadrotor.jl:13-14,73 — OrthogonalCollocation(3), controls constant over each element) at the same total
     # number of supports (S / 2 public ones + one collocation node per element), same step, same roofline arithmetic
-    if world == 1 and not args.emulate_shard and not args.no_variants and not args.graph:
+    if args.full and world == 1 and not args.emulate_shard and not args.no_variants and not args.graph:
         del gm, xd, yd, jac, hess, step, other
         torch.cuda.empty_cache()
         vcore = transcribe.exa_core(workloads.quadrotor(max(2, args.supports // 2), collocation=3))
@@ -848,7 +884,7 @@ def main():
         vm.close()
         del vm, vxd, vyd, vj, vh, vstep
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args.cpu_sample)
         print(json.dumps(line), flush=True)
     if use_dist:

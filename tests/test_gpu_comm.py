@@ -55,7 +55,7 @@ def test_bench_line_carries_a_checked_comm_section(built):
     halo exchange and objective all-reduce of the C-ABI's own mailboxes — exact, timed — next to the headline value."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--same-device",
-                        "--supports", "40000", "--steps", "5", "--warmup", "2", "--no-weak"],
+                        "--supports", "40000", "--steps", "5", "--warmup", "2", "--no-weak", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -81,7 +81,7 @@ def test_bench_line_with_the_torch_distributed_fallback_in_the_timed_step(built)
     N > 1 line never times a communication-free step silently."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--same-device", "--force-rccl",
-                        "--supports", "40000", "--steps", "5", "--warmup", "2", "--no-comm-check"],
+                        "--supports", "40000", "--steps", "5", "--warmup", "2", "--no-comm-check", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

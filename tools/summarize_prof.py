@@ -52,7 +52,7 @@ def main():
     import bench
     commit = os.environ.get("IEM_COMMIT", "n/a")      # no .git on the GPU box: pass `IEM_COMMIT=$(git rev-parse --short HEAD)` through the runner
     json.dump({"csrc_fingerprint": bench.csrc_fingerprint(), "commit": commit, "command": "tools/profile_gpu.sh (rocprofv3 --kernel-trace --stats; each --pmc group in its own pass) on "
-                          "python3 bench.py --no-cpu-baseline", "kernel_stats": stats, "pmc": pmc}, open(dst, "w"), indent=1)
+                          "python3 bench.py --full --no-cpu-baseline", "kernel_stats": stats, "pmc": pmc}, open(dst, "w"), indent=1)
     print(json.dumps({"kernel_stats": stats, "pmc": {k: {n: v for n, v in c.items() if n in ("hbm_bytes_per_launch", "compute_guard")}
                                                      for k, c in pmc.items()}}, indent=1))
 
