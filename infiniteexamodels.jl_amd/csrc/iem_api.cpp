@@ -138,20 +138,30 @@ bool read_file(const std::string &path, std::vector<char> &out) {
 
 }  // namespace
 
+// A generated program as loaded for launching: its module and kernel functions and, per kernel, the argument block
+// (LaunchHead, then the tables) with the device copy of the tables that do not fit it.  launchable[kind]: the kernels of
+// the kind that have work (n_blocks > 0), in program order — what launch_kind launches.
+struct CodeObject {
+  iem::Program prog;
+  hipModule_t mod = nullptr;
+  std::vector<hipFunction_t> fns;
+  std::vector<std::vector<uint64_t>> argbuf;
+  std::vector<void *> d_tables;
+  std::vector<int> launchable[iem::KK_LAST + 1];
+};
+
 struct iem_model {
   iem::Model model;
-  iem::Program prog;
+  CodeObject code;      // the model's program
   iem::Options opt;     // this handle's generator options (process defaults + iem_create_opts overrides)
   int poll_obj = 1;
   int device = 0;
   hipStream_t stream = nullptr;
-  hipModule_t mod = nullptr;
-  std::vector<hipFunction_t> fns;
   hipFunction_t fn_struct = nullptr, fn_csr = nullptr, fn_csr32 = nullptr, fn_axis = nullptr, fn_spmv = nullptr, fn_spmv_long = nullptr;
   long long *d_axis[iem::KK_COUNT] = {};
   long long *d_gather[iem::KK_COUNT] = {};   // per scatter kind: dest | seg | perm of its plan-driven gather (iem_gather_sum_kernel)
   hipFunction_t fn_gather = nullptr;   // per scatter kind: table of its axis sums (iem_axis_sum_kernel)
-  double *d_theta = nullptr, *d_partials = nullptr, *d_obj = nullptr;
+  double *d_theta = nullptr, *d_partials = nullptr;
   double *d_red[iem::KK_COUNT] = {};   // per scatter kind: parked shared-entry values + tickets (iem_shared_*)
   // Second code object of jac_coord!/hess_coord! with a larger LDS staging batch (lds_slots = 48: one 96-KB
   // workgroup per CU, a third of the concurrently open store streams) and the tuner that picks, per kind and
@@ -159,14 +169,7 @@ struct iem_model {
   // channels decides that, and both variants write identical bytes, so the first twenty calls into a
   // buffer run ten with one, ten with the other, under HIP events, and every call is a valid evaluation.
 #define IEM_TUNE_CALLS 20   // measured calls per output buffer: a block of ten per variant
-  struct Alt {
-    bool on = false;
-    iem::Program prog;
-    hipModule_t mod = nullptr;
-    std::vector<hipFunction_t> fns;
-    std::vector<std::vector<uint64_t>> argbuf;
-    std::vector<void *> d_tables;
-  } alt;
+  CodeObject alt;      // loaded (alt.mod set) only where the tuner runs
   struct Tune {
     const void *out = nullptr;   // the buffer the decision belongs to
     int calls = 0, choice = -1;  // choice: -1 undecided, 0 default, 1 alt
@@ -212,13 +215,9 @@ struct iem_model {
   struct KktMod { unsigned elim_wg = 64; int elim_bpw = 1; hipModule_t mod = nullptr; hipFunction_t elim = nullptr, upd = nullptr, fwd = nullptr, bwd = nullptr, gather = nullptr, move = nullptr, colsum = nullptr, hub_z = nullptr, hub_widen = nullptr, hub_mask = nullptr, hub_ety = nullptr, hub_ex = nullptr, hub_leaf = nullptr, hub_diagmax = nullptr, fz = nullptr, fs = nullptr, bw = nullptr; int solve_bpw = 0; };
   std::map<std::pair<int, int>, KktMod> kkt_mods;
   std::map<int, void *> d_arrays;  // model array id -> device copy
-  std::vector<std::vector<uint64_t>> argbuf;  // per kernel: launch argument block; only the six head words change per call
-  std::vector<void *> d_tables;    // per kernel: device copy of {ip, dp, fa, ia} when they do not fit the argument block
   std::vector<double> theta_host;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool jit = false;
-  std::vector<std::pair<int64_t, int64_t>> grad_zero;  // [lo, hi) ranges of g the kernels do not overwrite
-  std::vector<std::pair<int64_t, int64_t>> zero_ranges[iem::KK_COUNT];
+  std::vector<std::pair<int64_t, int64_t>> zero_ranges[iem::KK_COUNT];  // per scatter kind: [lo, hi) of the output its kernels do not overwrite
 };
 
 namespace {
@@ -229,26 +228,14 @@ int upload_array(iem_model *m, int id, bool as_int) {
   void *d = nullptr;
   size_t bytes = (size_t)std::max<int64_t>(a.n, 1) * 8;
   HIP_TRY(hipMalloc(&d, bytes));
-  if (a.kind == IEM_A_F64_DATA || a.kind == IEM_A_I64_DATA) {
-    bool src_int = a.kind == IEM_A_I64_DATA;
-    if (src_int == as_int) {
-      HIP_TRY(hipMemcpy(d, a.data, (size_t)a.n * 8, hipMemcpyHostToDevice));
-    } else if (as_int) {
-      std::vector<int64_t> tmp(a.n);
-      for (int64_t j = 0; j < a.n; ++j) tmp[j] = a.i(j);
-      HIP_TRY(hipMemcpy(d, tmp.data(), (size_t)a.n * 8, hipMemcpyHostToDevice));
-    } else {
-      std::vector<double> tmp(a.n);
-      for (int64_t j = 0; j < a.n; ++j) tmp[j] = a.f(j);
-      HIP_TRY(hipMemcpy(d, tmp.data(), (size_t)a.n * 8, hipMemcpyHostToDevice));
+  if ((a.kind == IEM_A_F64_DATA && !as_int) || (a.kind == IEM_A_I64_DATA && as_int)) {   // stored as requested: as is
+    HIP_TRY(hipMemcpy(d, a.data, (size_t)a.n * 8, hipMemcpyHostToDevice));
+  } else {   // the other stored type, or a fill / range array: converted element by element
+    std::vector<uint64_t> tmp((size_t)a.n);
+    for (int64_t j = 0; j < a.n; ++j) {
+      if (as_int) tmp[j] = (uint64_t)a.i(j);
+      else { const double v = a.f(j); std::memcpy(&tmp[j], &v, 8); }
     }
-  } else if (as_int) {
-    std::vector<int64_t> tmp(a.n);
-    for (int64_t j = 0; j < a.n; ++j) tmp[j] = a.i(j);
-    HIP_TRY(hipMemcpy(d, tmp.data(), (size_t)a.n * 8, hipMemcpyHostToDevice));
-  } else {
-    std::vector<double> tmp(a.n);
-    for (int64_t j = 0; j < a.n; ++j) tmp[j] = a.f(j);
     HIP_TRY(hipMemcpy(d, tmp.data(), (size_t)a.n * 8, hipMemcpyHostToDevice));
   }
   m->d_arrays[id] = d;
@@ -307,26 +294,6 @@ int load_source(iem_model *m, const std::string &src, hipModule_t *mod) {
   std::vector<char> code;
   bool loaded = false;
   if (read_file(path, code)) {
-    loaded = hipModuleLoadData(mod, code.data()) == hipSuccess;
-    if (!loaded) { *mod = nullptr; (void)hipGetLastError(); }
-  }
-  if (!loaded) {
-    int rc = jit_compile(m, src, dir, path, code);
-    if (rc) return rc;
-    HIP_TRY(hipModuleLoadData(mod, code.data()));
-  }
-  return IEM_OK;
-}
-
-// code object of `prog` (cache -> hiprtc on a miss) and its kernel functions
-int load_program(iem_model *m, const iem::Program &prog, const iem::Options &opt, hipModule_t *mod, std::vector<hipFunction_t> *fns) {
-  const std::string src = full_source(prog, opt);
-  const uint64_t key = iem::fnv1a64(src);
-  const std::string dir = cache_dir();
-  const std::string path = dir + "/iem_" + key_hex(key) + ".hsaco";
-  std::vector<char> code;
-  bool loaded = false;
-  if (read_file(path, code)) {
     // a cached object that does not load (truncated file, built for another architecture) is rebuilt
     loaded = hipModuleLoadData(mod, code.data()) == hipSuccess;
     if (!loaded) { *mod = nullptr; (void)hipGetLastError(); }
@@ -336,98 +303,100 @@ int load_program(iem_model *m, const iem::Program &prog, const iem::Options &opt
     if (rc) return rc;
     HIP_TRY(hipModuleLoadData(mod, code.data()));
   }
-  fns->resize(prog.kernels.size());
-  for (size_t k = 0; k < prog.kernels.size(); ++k)
-    HIP_TRY(hipModuleGetFunction(&(*fns)[k], *mod, prog.kernels[k].name.c_str()));
   return IEM_OK;
+}
+
+// code object of `co.prog` (generated with `opt`) and its kernel functions
+int load_program(iem_model *m, CodeObject &co, const iem::Options &opt) {
+  int rc = load_source(m, full_source(co.prog, opt), &co.mod);
+  if (rc) return rc;
+  co.fns.resize(co.prog.kernels.size());
+  for (size_t k = 0; k < co.prog.kernels.size(); ++k)
+    HIP_TRY(hipModuleGetFunction(&co.fns[k], co.mod, co.prog.kernels[k].name.c_str()));
+  return IEM_OK;
+}
+
+void free_program(CodeObject &co) {
+  for (void *t : co.d_tables) if (t) hipFree(t);
+  if (co.mod) hipModuleUnload(co.mod);
 }
 
 int compile_or_load(iem_model *m) {
-  int rc = load_program(m, m->prog, m->opt, &m->mod, &m->fns);
+  int rc = load_program(m, m->code, m->opt);
   if (rc) return rc;
-  HIP_TRY(hipModuleGetFunction(&m->fn_struct, m->mod, "iem_structure_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_csr, m->mod, "iem_csr_gather_sum"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_csr32, m->mod, "iem_csr_gather_sum32"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_spmv, m->mod, "iem_csr_spmv_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_spmv_long, m->mod, "iem_csr_spmv_long_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_axis, m->mod, "iem_axis_sum_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_gather, m->mod, "iem_gather_sum_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_halo, m->mod, "iem_halo_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_fold, m->mod, "iem_halo_fold_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_reduce, m->mod, "iem_allreduce_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_struct, m->code.mod, "iem_structure_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_csr, m->code.mod, "iem_csr_gather_sum"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_csr32, m->code.mod, "iem_csr_gather_sum32"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_spmv, m->code.mod, "iem_csr_spmv_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_spmv_long, m->code.mod, "iem_csr_spmv_long_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_axis, m->code.mod, "iem_axis_sum_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_gather, m->code.mod, "iem_gather_sum_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_halo, m->code.mod, "iem_halo_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_fold, m->code.mod, "iem_halo_fold_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_reduce, m->code.mod, "iem_allreduce_kernel"));
   return IEM_OK;
 }
 
-// Builds the static part of a kernel's argument block once (iem_create); launching only rewrites
-// the head {x, theta, y, v, out, w, aux, comm}.
-void build_argbuf(iem_model *m, const iem::KernelDesc &kd, const void *d_table, std::vector<uint64_t> &buf) {
-  buf.assign(13, 0);   // head: x, theta, y, v, out, w, aux, comm, p2 .. p6
-  auto push_ptr = [&](const void *p) { buf.push_back((uint64_t)(uintptr_t)p); };
-  if (kd.tables_in_memory) {
-    const uint64_t *tb = (const uint64_t *)d_table;
-    size_t nip = std::max<size_t>(1, kd.ip.size()), ndp = std::max<size_t>(1, kd.dp.size()), nfa = std::max<size_t>(1, kd.fa.size());
-    push_ptr(tb); push_ptr(tb + nip); push_ptr(tb + nip + ndp); push_ptr(tb + nip + ndp + nfa);
-  } else {
-    for (int64_t v : kd.ip) buf.push_back((uint64_t)v);
-    if (kd.ip.empty()) buf.push_back(0);
-    for (double v : kd.dp) { uint64_t b; std::memcpy(&b, &v, 8); buf.push_back(b); }
-    if (kd.dp.empty()) buf.push_back(0);
-    for (int id : kd.fa) push_ptr(m->d_arrays[id]);
-    if (kd.fa.empty()) buf.push_back(0);
-    for (int id : kd.ia) push_ptr(m->d_arrays[id]);
-    if (kd.ia.empty()) buf.push_back(0);
-  }
+// The head of every generated kernel's argument block (iem_codegen.cpp: emit_kernel_head), the only part rewritten per
+// launch.  The last five words carry the further outputs of the one-launch kinds (iem_codegen.hpp: KernelKind).
+struct LaunchHead {
+  const double *x = nullptr, *th = nullptr, *y = nullptr, *v = nullptr;
+  double *out = nullptr;
+  double w = 0.0;
+  double *aux = nullptr;
+  const void *comm = nullptr;   // set by launch_kind: the deferred halo exchange this launch carries (IemHaloArgs)
+  union {
+    double *g = nullptr;        // KK_ACCEPTED / KK_ALL: grad!'s output
+    double *trial_partials;     // KK_TRIAL: the objective's partials
+  };
+  double *g_red = nullptr;      // KK_ACCEPTED / KK_ALL: grad!'s reduction buffer
+  double *c = nullptr;          // KK_ALL: cons!'s output
+  double *partials = nullptr;   // KK_ALL: the objective's partials
+  double *obj = nullptr;        // KK_ALL: the objective scalar
+};
+static_assert(sizeof(LaunchHead) == 13 * 8, "the generated Args_* head is 13 words");
+
+// a kernel's tables {ip, dp, fa, ia} as words (an empty table still takes one): inline in its argument block, or in a
+// device copy the block points to when they do not fit (KernelDesc::tables_in_memory)
+void pack_tables(iem_model *m, const iem::KernelDesc &kd, std::vector<uint64_t> &out) {
+  for (int64_t v : kd.ip) out.push_back((uint64_t)v);
+  if (kd.ip.empty()) out.push_back(0);
+  for (double v : kd.dp) { uint64_t b; std::memcpy(&b, &v, 8); out.push_back(b); }
+  if (kd.dp.empty()) out.push_back(0);
+  for (int id : kd.fa) out.push_back((uint64_t)(uintptr_t)m->d_arrays[id]);
+  if (kd.fa.empty()) out.push_back(0);
+  for (int id : kd.ia) out.push_back((uint64_t)(uintptr_t)m->d_arrays[id]);
+  if (kd.ia.empty()) out.push_back(0);
 }
 
-// uploads what the program's kernels read and builds their argument blocks
-int prepare_program(iem_model *m, const iem::Program &prog, std::vector<void *> &d_tables, std::vector<std::vector<uint64_t>> &argbuf) {
+// uploads what the program's kernels read and builds, once, their argument blocks and lists of launchable kernels
+int prepare_program(iem_model *m, CodeObject &co) {
   int rc;
-  for (const iem::KernelDesc &kd : prog.kernels) {
+  for (const iem::KernelDesc &kd : co.prog.kernels) {
     for (int id : kd.fa) if ((rc = upload_array(m, id, false)) != IEM_OK) return rc;
     for (int id : kd.ia) if ((rc = upload_array(m, id, true)) != IEM_OK) return rc;
   }
-  d_tables.assign(prog.kernels.size(), nullptr);
-  for (size_t k = 0; k < prog.kernels.size(); ++k) {
-    const iem::KernelDesc &kd = prog.kernels[k];
-    if (!kd.tables_in_memory) continue;
-    std::vector<uint64_t> tb;
-    for (int64_t v : kd.ip) tb.push_back((uint64_t)v);
-    if (kd.ip.empty()) tb.push_back(0);
-    for (double v : kd.dp) { uint64_t b; std::memcpy(&b, &v, 8); tb.push_back(b); }
-    if (kd.dp.empty()) tb.push_back(0);
-    for (int id : kd.fa) tb.push_back((uint64_t)(uintptr_t)m->d_arrays[id]);
-    if (kd.fa.empty()) tb.push_back(0);
-    for (int id : kd.ia) tb.push_back((uint64_t)(uintptr_t)m->d_arrays[id]);
-    if (kd.ia.empty()) tb.push_back(0);
-    HIP_TRY(hipMalloc(&d_tables[k], tb.size() * 8));
-    HIP_TRY(hipMemcpy(d_tables[k], tb.data(), tb.size() * 8, hipMemcpyHostToDevice));
+  const size_t n = co.prog.kernels.size();
+  co.d_tables.assign(n, nullptr);
+  co.argbuf.resize(n);
+  for (size_t k = 0; k < n; ++k) {
+    const iem::KernelDesc &kd = co.prog.kernels[k];
+    std::vector<uint64_t> &buf = co.argbuf[k];
+    buf.assign(sizeof(LaunchHead) / 8, 0);
+    if (kd.tables_in_memory) {
+      std::vector<uint64_t> tb;
+      pack_tables(m, kd, tb);
+      HIP_TRY(hipMalloc(&co.d_tables[k], tb.size() * 8));
+      HIP_TRY(hipMemcpy(co.d_tables[k], tb.data(), tb.size() * 8, hipMemcpyHostToDevice));
+      const uint64_t *t = (const uint64_t *)co.d_tables[k];
+      const size_t nip = std::max<size_t>(1, kd.ip.size()), ndp = std::max<size_t>(1, kd.dp.size()), nfa = std::max<size_t>(1, kd.fa.size());
+      for (const uint64_t *p : {t, t + nip, t + nip + ndp, t + nip + ndp + nfa}) buf.push_back((uint64_t)(uintptr_t)p);
+    } else {
+      pack_tables(m, kd, buf);
+    }
+    if (kd.kind >= 0 && kd.kind <= iem::KK_LAST && kd.n_blocks > 0) co.launchable[kd.kind].push_back((int)k);   // (a grid none of whose templates has an item: nothing to launch)
   }
-  argbuf.resize(prog.kernels.size());
-  for (size_t k = 0; k < prog.kernels.size(); ++k) build_argbuf(m, prog.kernels[k], d_tables[k], argbuf[k]);
   return IEM_OK;
-}
-
-// `carry`: the launch also carries the deferred halo exchange of x — one extra leading workgroup column (iem_halo_wg)
-int launch_one(iem_model *m, const iem::KernelDesc &kd, hipFunction_t fn, std::vector<uint64_t> &buf, const double *x, const double *y,
-               double *out, double w, const double *v, double *aux, bool carry = false, double *p2 = nullptr, double *p3 = nullptr,
-               double *p4 = nullptr, double *p5 = nullptr, double *p6 = nullptr) {
-  if (kd.n_blocks <= 0) return IEM_OK;   // a support grid none of whose templates has an item
-  buf[0] = (uint64_t)(uintptr_t)x; buf[1] = (uint64_t)(uintptr_t)m->d_theta; buf[2] = (uint64_t)(uintptr_t)y;
-  buf[3] = (uint64_t)(uintptr_t)v; buf[4] = (uint64_t)(uintptr_t)out;
-  std::memcpy(&buf[5], &w, 8);
-  buf[6] = (uint64_t)(uintptr_t)aux;
-  buf[7] = carry ? (uint64_t)(uintptr_t)m->d_comm : 0;
-  buf[8] = (uint64_t)(uintptr_t)p2; buf[9] = (uint64_t)(uintptr_t)p3;
-  buf[10] = (uint64_t)(uintptr_t)p4; buf[11] = (uint64_t)(uintptr_t)p5; buf[12] = (uint64_t)(uintptr_t)p6;
-  size_t sz = buf.size() * 8;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, buf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)kd.grid[0] + (carry ? 1u : 0u), (unsigned)kd.grid[1], (unsigned)kd.grid[2], (unsigned)kd.block, 1, 1, 0,
-                                m->stream, nullptr, cfg));
-  return IEM_OK;
-}
-
-int launch(iem_model *m, size_t k, const double *x, const double *y, double *out, double w, const double *v = nullptr, double *aux = nullptr) {
-  return launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], x, y, out, w, v, aux);
 }
 
 // A mailbox wait timed out since the last check: the kernels poisoned what they delivered (NaN) and recorded it in
@@ -475,18 +444,16 @@ int halo_plan(iem_model *m, int kind, const void *x, const void *v, bool *carry)
   return IEM_OK;
 }
 
-int launch_kind_raw(iem_model *m, int kind, const double *x, const double *y, double *out, double w, const double *v, double *aux);
-
-// what runs BEHIND the kernels of a scatter kind (also behind the one-launch accepted-point kernel, for grad!)
+// what runs BEHIND the kernels of a scatter kind (also behind the one-launch phases that contain grad!)
 int kind_followups(iem_model *m, int kind, double *out, double *aux) {
-  if (!m->prog.axis[kind].empty()) {   // sums over a non-lane axis: the rows the kernels parked -> one write per entry (iem_axis_sum_kernel)
+  if (!m->code.prog.axis[kind].empty()) {   // sums over a non-lane axis: the rows the kernels parked -> one write per entry (iem_axis_sum_kernel)
     int64_t n0 = 1;
-    for (auto &a : m->prog.axis[kind]) n0 = std::max(n0, a.n0);
+    for (auto &a : m->code.prog.axis[kind]) n0 = std::max(n0, a.n0);
     void *args[] = {(void *)&out, (void *)&aux, (void *)&m->d_axis[kind]};
-    HIP_TRY(hipModuleLaunchKernel(m->fn_axis, (unsigned)((n0 + 63) / 64), (unsigned)m->prog.axis[kind].size(), 1, 256, 1, 1, 0, m->stream, args, nullptr));   // 64 lanes x 4 row groups per workgroup
+    HIP_TRY(hipModuleLaunchKernel(m->fn_axis, (unsigned)((n0 + 63) / 64), (unsigned)m->code.prog.axis[kind].size(), 1, 256, 1, 1, 0, m->stream, args, nullptr));   // 64 lanes x 4 row groups per workgroup
   }
-  if (!m->prog.gather[kind].dest.empty()) {   // what would have been float atomics: parked addends summed per entry in plan order
-    const iem::Program::Gather &G = m->prog.gather[kind];
+  if (!m->code.prog.gather[kind].dest.empty()) {   // what would have been float atomics: parked addends summed per entry in plan order
+    const iem::Program::Gather &G = m->code.prog.gather[kind];
     long long n = (long long)G.dest.size();
     const double *parked = aux + G.aux_off;
     const long long *dest = m->d_gather[kind], *seg = dest + n;
@@ -498,59 +465,73 @@ int kind_followups(iem_model *m, int kind, double *out, double *aux) {
   return IEM_OK;
 }
 
-int launch_kind(iem_model *m, int kind, const double *x, const double *y, double *out, double w, const double *v = nullptr, double *aux = nullptr) {
-  return launch_kind_raw(m, kind, x, y, out, w, v, aux);
-}
-
-int launch_kind_raw(iem_model *m, int kind, const double *x, const double *y, double *out, double w, const double *v, double *aux) {
-  bool carry = false;
-  int rc0 = halo_plan(m, kind, x, v, &carry);
-  if (rc0) return rc0;
-  for (size_t k = 0; k < m->prog.kernels.size(); ++k)
-    if (m->prog.kernels[k].kind == kind) {
-      if (m->prog.kernels[k].n_blocks <= 0) continue;
-      int rc = launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], x, y, out, w, v, aux, carry);
-      if (rc) return rc;
-      carry = false;   // the first kernel of the call carries it
-    }
-  if (carry) { m->halo_deferred = true; }   // (no kernel of the kind was launched: still pending)
-  return kind_followups(m, kind, out, aux);
-}
-
-int launch_kind_alt(iem_model *m, int kind, const double *x, const double *y, double *out, double w) {
-  bool carry = false;
-  int rc = halo_plan(m, kind, x, nullptr, &carry);
-  if (rc) return rc;
-  for (size_t k = 0; k < m->alt.prog.kernels.size(); ++k)
-    if (m->alt.prog.kernels[k].kind == kind) {
-      if (m->alt.prog.kernels[k].n_blocks <= 0) continue;
-      rc = launch_one(m, m->alt.prog.kernels[k], m->alt.fns[k], m->alt.argbuf[k], x, y, out, w, nullptr, nullptr, carry);
-      if (rc) return rc;
-      carry = false;
-    }
-  if (carry) m->halo_deferred = true;
+// kernel k of `co` with the head `h` (h.comm set: the launch carries the deferred halo exchange — one extra leading workgroup column, iem_halo_wg)
+int launch_one(iem_model *m, CodeObject &co, int k, const LaunchHead &h) {
+  const iem::KernelDesc &kd = co.prog.kernels[k];
+  const hipFunction_t fn = co.fns[k];
+  const bool carry = h.comm != nullptr;
+  std::vector<uint64_t> &buf = co.argbuf[k];
+  std::memcpy(buf.data(), &h, sizeof h);
+  size_t sz = buf.size() * 8;
+  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, buf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)kd.grid[0] + (carry ? 1u : 0u), (unsigned)kd.grid[1], (unsigned)kd.grid[2], (unsigned)kd.block, 1, 1, 0,
+                                m->stream, nullptr, cfg));
   return IEM_OK;
 }
 
-// jac_coord! / hess_coord! through the tuner (struct Alt): the first IEM_TUNE_CALLS calls into an output buffer
-// run ten with the default, then ten with the alt object, under events; then the faster variant (medians of the last
-// eight of each block; alt only if > 2 % faster) is kept.
-int launch_tuned(iem_model *m, int which, int kind, const double *x, const double *y, double *out, double w) {
-  if (!m->alt.on) return launch_kind(m, kind, x, y, out, w);
+// One evaluation call: the launchable kernels of `kind` in `co` with the head `h` (th and comm filled in here), ordered
+// against a deferred halo exchange (halo_plan) — the first kernel launched carries it, and it stays deferred when the kind
+// launches nothing — then what runs behind them: a scatter kind's own follow-ups, grad!'s behind the phases that contain
+// it; none behind the pair and trial kinds, nor behind the tuner's second object (jac_coord! / hess_coord! only).
+int launch_kind(iem_model *m, CodeObject &co, int kind, const LaunchHead &h) {
+  bool carry = false;
+  int rc = halo_plan(m, kind, h.x, h.v, &carry);
+  if (rc) return rc;
+  LaunchHead a = h;
+  a.th = m->d_theta;
+  for (int k : co.launchable[kind]) {
+    a.comm = carry ? m->d_comm : nullptr;
+    if ((rc = launch_one(m, co, k, a))) return rc;
+    carry = false;
+  }
+  if (carry) m->halo_deferred = true;
+  if (&co != &m->code) return IEM_OK;
+  if (kind < iem::KK_COUNT) return kind_followups(m, kind, h.out, h.aux);
+  if (kind == iem::KK_ACCEPTED || kind == iem::KK_ALL) return kind_followups(m, iem::KK_GRAD, h.g, h.g_red);
+  return IEM_OK;
+}
+
+// memsets what the kernels of a scatter kind do not overwrite completely, in front of them
+int zero_uncovered(iem_model *m, int kind, double *out) {
+  for (auto &z : m->zero_ranges[kind])
+    HIP_TRY(hipMemsetAsync(out + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
+  return IEM_OK;
+}
+
+// the tuner's record of jac_coord! (which = 0) / hess_coord! (1) into the buffer `out`; a buffer not seen lately takes the oldest slot, undecided
+iem_model::Tune &tune_slot(iem_model *m, int which, const void *out) {
   iem_model::TuneSet &S = m->tune[which];
   iem_model::Tune *hit = nullptr;
   for (auto &t : S.slot)
     if (t.out == out) hit = &t;
-  if (!hit) {                    // a buffer not seen lately: its own measurement, in the oldest slot
+  if (!hit) {
     hit = &S.slot[S.next];
     S.next = (S.next + 1) % 4;
     hit->out = out; hit->calls = 0; hit->choice = -1;
   }
-  iem_model::Tune &T = *hit;
-  if (T.choice >= 0) return T.choice ? launch_kind_alt(m, kind, x, y, out, w) : launch_kind(m, kind, x, y, out, w);
+  return *hit;
+}
+
+// jac_coord! / hess_coord! through the tuner (iem_model::alt): the first IEM_TUNE_CALLS calls into an output buffer
+// run ten with the default, then ten with the alt object, under events; then the faster variant (medians of the last
+// eight of each block; alt only if > 2 % faster) is kept.
+int launch_tuned(iem_model *m, int which, int kind, const LaunchHead &h) {
+  if (!m->alt.mod) return launch_kind(m, m->code, kind, h);
+  iem_model::Tune &T = tune_slot(m, which, h.out);
+  if (T.choice >= 0) return launch_kind(m, T.choice ? m->alt : m->code, kind, h);
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(m->stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-  if (cap != hipStreamCaptureStatusNone) return launch_kind(m, kind, x, y, out, w);   // no timing inside a graph capture
+  if (cap != hipStreamCaptureStatusNone) return launch_kind(m, m->code, kind, h);   // no timing inside a graph capture
   if (T.calls < IEM_TUNE_CALLS) {
     if (!T.have_events) {
       for (auto &e : T.ev) for (auto &q : e) HIP_TRY(hipEventCreate(&q));
@@ -558,7 +539,7 @@ int launch_tuned(iem_model *m, int which, int kind, const double *x, const doubl
     }
     const int v = T.calls >= IEM_TUNE_CALLS / 2 ? 1 : 0;   // a block of each: alternating single launches measures the switch, not the variant
     HIP_TRY(hipEventRecord(T.ev[T.calls][0], m->stream));
-    int rc = v ? launch_kind_alt(m, kind, x, y, out, w) : launch_kind(m, kind, x, y, out, w);
+    int rc = launch_kind(m, v ? m->alt : m->code, kind, h);
     HIP_TRY(hipEventRecord(T.ev[T.calls][1], m->stream));
     ++T.calls;
     return rc;
@@ -578,14 +559,14 @@ int launch_tuned(iem_model *m, int which, int kind, const double *x, const doubl
       if (!s[v].empty()) { std::sort(s[v].begin(), s[v].end()); med[v] = s[v][s[v].size() / 2]; }
     T.choice = med[1] < 0.98f * med[0] ? 1 : 0;
     if (getenv("IEM_TUNER_LOG")) {
-      fprintf(stderr, "iem tuner: kind %d buffer %p:", kind, (const void *)out);
+      fprintf(stderr, "iem tuner: kind %d buffer %p:", kind, (const void *)h.out);
       for (int c = 0; c < IEM_TUNE_CALLS; ++c) { float ms = -1.f; (void)hipEventElapsedTime(&ms, T.ev[c][0], T.ev[c][1]); fprintf(stderr, " %s%.4f", c >= IEM_TUNE_CALLS / 2 ? "a" : "d", ms); }
       fprintf(stderr, " medians %.4f / %.4f -> %s\n", med[0], med[1], T.choice ? "alt" : "default");
     }
-    return T.choice ? launch_kind_alt(m, kind, x, y, out, w) : launch_kind(m, kind, x, y, out, w);
+    return launch_kind(m, T.choice ? m->alt : m->code, kind, h);
   }
   (void)hipGetLastError();
-  return launch_kind(m, kind, x, y, out, w);
+  return launch_kind(m, m->code, kind, h);
 }
 
 // host-side item index evaluation for the structure calls
@@ -668,8 +649,8 @@ int structure_device(iem_model *m, int64_t *d_rows, int64_t *d_cols, int base, b
   to_free.push_back((void *)d_ptrs);
   if (!ptrs.empty()) HIP_TRY(hipMemcpy(d_ptrs, ptrs.data(), ptrs.size() * 8, hipMemcpyHostToDevice));
   int rc = IEM_OK;
-  if (hess && !m->prog.hess_classes.empty()) {
-    for (const iem::HessClass &hc : m->prog.hess_classes) {
+  if (hess && !m->code.prog.hess_classes.empty()) {
+    for (const iem::HessClass &hc : m->code.prog.hess_classes) {
       const int ns = (int)hc.idx_i.size();
       if (ns == 0) continue;
       std::vector<IdxDescH> a(ns), b(ns);
@@ -997,7 +978,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
       m->model = iem::Model();
       iem::parse_blob(local.data(), local.size() * 8, m->model);
     }
-    m->prog = iem::generate(m->model, m->opt);
+    m->code.prog = iem::generate(m->model, m->opt);
   } catch (const std::exception &e) {
     delete m;
     return fail(IEM_E_BLOB, e.what());
@@ -1015,19 +996,19 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   // partials + the ticket counters behind them (iem_block_partial: 1 top + one per 32 workgroups),
   // zeroed once — the workgroups that complete a count reset it
   {
-    const size_t np = (size_t)std::max<int64_t>(m->prog.n_partials, 1);
+    const size_t np = (size_t)std::max<int64_t>(m->code.prog.n_partials, 1);
     const size_t words = np + 1 + (np + 31) / 32;
     if (hipMalloc((void **)&m->d_partials, words * 8) != hipSuccess || hipMemset(m->d_partials, 0, words * 8) != hipSuccess)
       return bail(fail(IEM_E_HIP, "hipMalloc partials"));
   }
   for (int kind = 0; kind < iem::KK_COUNT; ++kind) {
     // aux buffer of a scatter kind: shared-entry values x workgroups + ticket words (zeroed once), then the rows of its axis sums
-    const size_t words = (size_t)m->prog.aux_doubles[kind];
+    const size_t words = (size_t)m->code.prog.aux_doubles[kind];
     if (words == 0) continue;
     if (hipMalloc((void **)&m->d_red[kind], words * 8) != hipSuccess || hipMemset(m->d_red[kind], 0, words * 8) != hipSuccess)
       return bail(fail(IEM_E_HIP, "hipMalloc reduction buffer"));
-    if (!m->prog.gather[kind].dest.empty()) {
-      const iem::Program::Gather &G = m->prog.gather[kind];
+    if (!m->code.prog.gather[kind].dest.empty()) {
+      const iem::Program::Gather &G = m->code.prog.gather[kind];
       const size_t nd = G.dest.size(), np = G.perm.size();
       const bool wide = G.park_doubles >= (1LL << 32);   // parked positions fit 32 bits otherwise: half the plan traffic
       std::vector<uint32_t> p32;
@@ -1038,15 +1019,14 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
           hipMemcpy(m->d_gather[kind] + 2 * nd + 1, wide ? (const void *)G.perm.data() : (const void *)p32.data(), np * (wide ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess)
         return bail(fail(IEM_E_HIP, "hipMalloc gather plan"));
     }
-    if (!m->prog.axis[kind].empty()) {
+    if (!m->code.prog.axis[kind].empty()) {
       std::vector<long long> tab;
-      for (auto &a : m->prog.axis[kind]) { tab.push_back(a.c); tab.push_back(a.k0); tab.push_back(a.n0); tab.push_back(a.rows); tab.push_back(a.off); }
+      for (auto &a : m->code.prog.axis[kind]) { tab.push_back(a.c); tab.push_back(a.k0); tab.push_back(a.n0); tab.push_back(a.rows); tab.push_back(a.off); }
       if (hipMalloc((void **)&m->d_axis[kind], tab.size() * 8) != hipSuccess ||
           hipMemcpy(m->d_axis[kind], tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
         return bail(fail(IEM_E_HIP, "hipMalloc axis-sum table"));
     }
   }
-  if (hipMalloc((void **)&m->d_obj, 8) != hipSuccess) return bail(fail(IEM_E_HIP, "hipMalloc obj"));
   if (hipHostMalloc((void **)&m->h_obj, 16, hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer((void **)&m->d_hobj, m->h_obj, 0) != hipSuccess) return bail(fail(IEM_E_HIP, "hipHostMalloc"));
   m->h_status = reinterpret_cast<volatile unsigned long long *>(m->h_obj + 1);   // second word: comm time-outs (IemCommErr::hstatus)
@@ -1064,7 +1044,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
       }
       return false;
     };
-    for (const iem::KernelDesc &kd : m->prog.kernels) {
+    for (const iem::KernelDesc &kd : m->code.prog.kernels) {
       if (kd.kind < 0 || kd.kind > iem::KK_LAST) continue;
       m->reads_halo_x[kd.kind] = m->reads_halo_x[kd.kind] || hits(kd.x_ranges);
       m->reads_halo_v[kd.kind] = m->reads_halo_v[kd.kind] || hits(kd.v_ranges);
@@ -1073,18 +1053,18 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
     // reduces shared entries has none: one extra workgroup there would shift every tile)
     bool any[iem::KK_LAST + 1] = {}, all[iem::KK_LAST + 1];
     for (bool &a : all) a = true;
-    for (const iem::KernelDesc &kd : m->prog.kernels) {
+    for (const iem::KernelDesc &kd : m->code.prog.kernels) {
       if (kd.kind < 0 || kd.kind > iem::KK_LAST) continue;
       any[kd.kind] = true; all[kd.kind] = all[kd.kind] && kd.carries;
     }
     for (int k = 0; k <= iem::KK_LAST; ++k) m->carrier[k] = any[k] && all[k];
   }
-  if ((rc = prepare_program(m, m->prog, m->d_tables, m->argbuf)) != IEM_OK) return bail(rc);
+  if ((rc = prepare_program(m, m->code)) != IEM_OK) return bail(rc);
   // second code object for the tuner: only for block-store models with a large jac/hess grid (below ~2e5 supports
   // the larger batch loses), never for the experiment knobs
   if (m->opt.autotune && m->opt.store_mode == 2 && m->opt.lds_slots < 48 && !m->opt.no_fuse && !m->opt.ablate) {
     int64_t big = 0;
-    for (const iem::KernelDesc &kd : m->prog.kernels)
+    for (const iem::KernelDesc &kd : m->code.prog.kernels)
       if (kd.kind == iem::KK_JAC || kd.kind == iem::KK_HESS) big = std::max(big, kd.n_blocks);
     if (big >= m->opt.autotune_min_blocks) {
       iem::Options ob = m->opt;
@@ -1095,9 +1075,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
       } catch (const std::exception &e) {
         return bail(fail(IEM_E_BLOB, e.what()));
       }
-      if ((rc = load_program(m, m->alt.prog, ob, &m->alt.mod, &m->alt.fns)) != IEM_OK) return bail(rc);
-      if ((rc = prepare_program(m, m->alt.prog, m->alt.d_tables, m->alt.argbuf)) != IEM_OK) return bail(rc);
-      m->alt.on = true;
+      if ((rc = load_program(m, m->alt, ob)) != IEM_OK || (rc = prepare_program(m, m->alt)) != IEM_OK) return bail(rc);
     }
   }
   for (int kind : {(int)iem::KK_GRAD, (int)iem::KK_JTPROD, (int)iem::KK_HPROD}) {
@@ -1105,7 +1083,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
     // fully-overwritten stretch are zeroed as one (what lies between is written afterwards, on the same
     // stream): one memset launch instead of two around pandemic's u(t) slab (grad! 11.5 -> 6 us of memsets)
     auto &zr = m->zero_ranges[kind];
-    for (auto &z : m->prog.zero_ranges[kind]) {
+    for (auto &z : m->code.prog.zero_ranges[kind]) {
       // the gap is measured against the two NEIGHBOURING ranges (never the whole span so far) and capped: a memset
       // never swallows more than 64 K doubles that a kernel is about to overwrite anyway
       const int64_t near = zr.empty() ? 0 : std::min<int64_t>(65536, std::max<int64_t>(8192, ((zr.back().second - zr.back().first) + (z.second - z.first)) / 16));
@@ -1113,8 +1091,6 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
       else zr.push_back(z);
     }
   }
-  m->grad_zero = m->zero_ranges[iem::KK_GRAD];
-  if (hipEventCreate(&m->ev0) != hipSuccess || hipEventCreate(&m->ev1) != hipSuccess) return bail(fail(IEM_E_HIP, "hipEventCreate"));
   *out = m;
   return IEM_OK;
 }
@@ -1124,7 +1100,6 @@ int iem_destroy(iem_model *m) {
   DevGuard dg_(m->device);
   if (m->d_theta) hipFree(m->d_theta);
   if (m->d_partials) hipFree(m->d_partials);
-  if (m->d_obj) hipFree(m->d_obj);
   for (double *r : m->d_red) if (r) hipFree(r);
   for (long long *r : m->d_axis) if (r) hipFree(r);
   for (long long *r : m->d_gather) if (r) hipFree(r);
@@ -1138,13 +1113,9 @@ int iem_destroy(iem_model *m) {
   if (m->d_comm) hipFree(m->d_comm);
   for (auto &kv : m->kkt_mods) if (kv.second.mod) hipModuleUnload(kv.second.mod);
   for (auto &kv : m->d_arrays) hipFree(kv.second);
-  for (void *t : m->d_tables) if (t) hipFree(t);
-  for (void *t : m->alt.d_tables) if (t) hipFree(t);
-  if (m->alt.mod) hipModuleUnload(m->alt.mod);
+  free_program(m->alt);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
-  if (m->ev0) hipEventDestroy(m->ev0);
-  if (m->ev1) hipEventDestroy(m->ev1);
-  if (m->mod) hipModuleUnload(m->mod);
+  free_program(m->code);
   delete m;
   return IEM_OK;
 }
@@ -1153,10 +1124,10 @@ int iem_meta(const iem_model *m, iem_meta_t *out) {
   if (!m || !out) return fail(IEM_E_ARG, "null argument");
   out->nvar = m->model.nvar; out->ncon = m->model.ncon; out->npar = m->model.npar;
   out->nnzj = m->model.nnzj;
-  out->nnzh = m->prog.hess_classes.empty() ? m->model.nnzh : m->prog.nnzh_merged;
+  out->nnzh = m->code.prog.hess_classes.empty() ? m->model.nnzh : m->code.prog.nnzh_merged;
   out->n_templates = (int64_t)m->model.tpl.size();
   out->minimize = m->model.minimize;
-  out->n_kernels = (int32_t)m->prog.kernels.size();
+  out->n_kernels = (int32_t)m->code.prog.kernels.size();
   return IEM_OK;
 }
 
@@ -1169,8 +1140,8 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 }
 
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
-  if (!m || !out || k < 0 || k >= (int)m->prog.kernels.size()) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = m->prog.kernels[k];
+  if (!m || !out || k < 0 || k >= (int)m->code.prog.kernels.size()) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = m->code.prog.kernels[k];
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
   out->kind = kd.kind;
@@ -1236,12 +1207,13 @@ int iem_set_parameter(iem_model *m, int64_t off, int64_t len, const double *h_va
 int iem_obj_device(iem_model *m, const double *d_x, double *d_out) {
   if (!m || !d_x || !d_out) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  if (m->prog.n_partials == 0) {   // no objective template: f = 0
+  if (m->code.prog.n_partials == 0) {   // no objective template: f = 0
     HIP_TRY(hipMemsetAsync(d_out, 0, 8, m->stream));
     return IEM_OK;
   }
-  // the last workgroup of the objective kernel(s) to finish writes the scalar to d_out
-  return launch_kind(m, iem::KK_OBJ, d_x, nullptr, m->d_partials, 0.0, nullptr, d_out);
+  LaunchHead h;   // the last workgroup of the objective kernel(s) to finish writes the scalar to aux
+  h.x = d_x; h.out = m->d_partials; h.aux = d_out;
+  return launch_kind(m, m->code, iem::KK_OBJ, h);
 }
 
 // The objective as a host scalar, in two halves (a solver that evaluates obj, grad!, cons!, jac_coord!, hess_coord! at one
@@ -1250,24 +1222,29 @@ int iem_obj_device(iem_model *m, const double *d_x, double *d_out) {
 //   iem_obj_end     waits for the slot (polling, ~200 us, then a stream synchronise) and returns the value
 // The last workgroup writes the scalar straight into mapped pinned host memory; the 8-byte store is atomic, so the first
 // value that is not the sentinel is the result.  iem_obj = begin + end (the host round trip of one launch: ~14 us).
+// Whatever fails after obj_arm disarms again, so that the next begin is not refused.
 static const uint64_t kObjSentinel = 0x7ff8dead0bad0b1eULL;
+
+static void obj_arm(iem_model *m) {
+  *reinterpret_cast<volatile uint64_t *>(m->h_obj) = kObjSentinel;
+  m->obj_armed = true;
+}
 
 int iem_obj_begin(iem_model *m, const double *d_x) {
   if (!m || !d_x) return fail(IEM_E_ARG, "null argument");
   if (m->obj_armed) return fail(IEM_E_ARG, "iem_obj_begin: the previous iem_obj_begin has not been collected (iem_obj_end)");
-  if (m->prog.n_partials == 0) { m->obj_armed = true; return IEM_OK; }
-  *reinterpret_cast<volatile uint64_t *>(m->h_obj) = kObjSentinel;
+  obj_arm(m);
+  if (m->code.prog.n_partials == 0) return IEM_OK;
   int rc = iem_obj_device(m, d_x, m->d_hobj);
-  if (rc) return rc;
-  m->obj_armed = true;
-  return IEM_OK;
+  if (rc) m->obj_armed = false;
+  return rc;
 }
 
 int iem_obj_end(iem_model *m, double *h_out) {
   if (!m || !h_out) return fail(IEM_E_ARG, "null argument");
   if (!m->obj_armed) return fail(IEM_E_ARG, "iem_obj_end without iem_obj_begin");
   m->obj_armed = false;
-  if (m->prog.n_partials == 0) { *h_out = 0.0; return comm_check(m); }
+  if (m->code.prog.n_partials == 0) { *h_out = 0.0; return comm_check(m); }
   DevGuard dg_(m->device);
   volatile uint64_t *slot = reinterpret_cast<volatile uint64_t *>(m->h_obj);
   bool got = false;
@@ -1294,68 +1271,80 @@ int iem_obj(iem_model *m, const double *d_x, double *h_out) {
 int iem_grad(iem_model *m, const double *d_x, double *d_g) {
   if (!m || !d_x || !d_g) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (auto &z : m->grad_zero)   // zero only what the kernels do not overwrite completely
-    HIP_TRY(hipMemsetAsync(d_g + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  return launch_kind(m, iem::KK_GRAD, d_x, nullptr, d_g, 0.0, nullptr, m->d_red[iem::KK_GRAD]);
+  int rc = zero_uncovered(m, iem::KK_GRAD, d_g);
+  if (rc) return rc;
+  LaunchHead h;
+  h.x = d_x; h.out = d_g; h.aux = m->d_red[iem::KK_GRAD];
+  return launch_kind(m, m->code, iem::KK_GRAD, h);
 }
 
 /* NLPModels.jprod!(m, x, v, Jv) */
 int iem_jprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jv) {
   if (!m || !d_x || !d_v || (!d_Jv && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  return launch_kind(m, iem::KK_JPROD, d_x, nullptr, d_Jv, 0.0, d_v);
+  LaunchHead h;
+  h.x = d_x; h.v = d_v; h.out = d_Jv;
+  return launch_kind(m, m->code, iem::KK_JPROD, h);
 }
 
 /* NLPModels.jtprod!(m, x, v, Jtv) */
 int iem_jtprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jtv) {
   if (!m || !d_x || (!d_v && m->model.ncon) || !d_Jtv) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (auto &z : m->zero_ranges[iem::KK_JTPROD])
-    HIP_TRY(hipMemsetAsync(d_Jtv + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  return launch_kind(m, iem::KK_JTPROD, d_x, nullptr, d_Jtv, 0.0, d_v, m->d_red[iem::KK_JTPROD]);
+  int rc = zero_uncovered(m, iem::KK_JTPROD, d_Jtv);
+  if (rc) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_v; h.out = d_Jtv; h.aux = m->d_red[iem::KK_JTPROD];
+  return launch_kind(m, m->code, iem::KK_JTPROD, h);
 }
 
 /* NLPModels.hprod!(m, x, y, v, Hv; obj_weight) */
 int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *d_v, double obj_weight, double *d_Hv) {
   if (!m || !d_x || (!d_y && m->model.ncon) || !d_v || !d_Hv) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (auto &z : m->zero_ranges[iem::KK_HPROD])
-    HIP_TRY(hipMemsetAsync(d_Hv + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  return launch_kind(m, iem::KK_HPROD, d_x, d_y, d_Hv, obj_weight, d_v, m->d_red[iem::KK_HPROD]);
+  int rc = zero_uncovered(m, iem::KK_HPROD, d_Hv);
+  if (rc) return rc;
+  LaunchHead h;
+  h.x = d_x; h.y = d_y; h.v = d_v; h.out = d_Hv; h.w = obj_weight; h.aux = m->d_red[iem::KK_HPROD];
+  return launch_kind(m, m->code, iem::KK_HPROD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {
   if (!m || !d_x || (!d_c && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  return launch_kind(m, iem::KK_CONS, d_x, nullptr, d_c, 0.0);
+  LaunchHead h;
+  h.x = d_x; h.out = d_c;
+  return launch_kind(m, m->code, iem::KK_CONS, h);
 }
 
 int iem_jac_coord(iem_model *m, const double *d_x, double *d_vals) {
   if (!m || !d_x || (!d_vals && m->model.nnzj)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  return launch_tuned(m, 0, iem::KK_JAC, d_x, nullptr, d_vals, 0.0);
+  LaunchHead h;
+  h.x = d_x; h.out = d_vals;
+  return launch_tuned(m, 0, iem::KK_JAC, h);
 }
 
 int iem_hess_coord(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_vals) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_vals && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  return launch_tuned(m, 1, iem::KK_HESS, d_x, d_y, d_vals, obj_weight);
+  LaunchHead h;
+  h.x = d_x; h.y = d_y; h.out = d_vals; h.w = obj_weight;
+  return launch_tuned(m, 1, iem::KK_HESS, h);
 }
 
 /* jac_coord!(m, x, jac) and hess_coord!(m, x, y, hess; obj_weight) in ONE launch (kernel kind KK_PAIR): the two calls are
  * independent given x and y, so their workgroups share a launch — one ramp and one drain, and on a shard-sized grid both
- * kinds are resident together.  Identical bytes to the two separate calls.  Handles without a fused kernel (option
- * "pair_kernel" = 0, or only one of the two kinds exists) make the two calls. */
+ * kinds are resident together.  Identical bytes to the two separate calls.  Handles without a launchable fused kernel
+ * (option "pair_kernel" = 0, or only one of the two kinds exists) make the two calls. */
 int iem_jac_hess_coord(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_jac, double *d_hess) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (size_t k = 0; k < m->prog.kernels.size(); ++k)
-    if (m->prog.kernels[k].kind == iem::KK_PAIR) {
-      bool carry = false;
-      int rc = halo_plan(m, iem::KK_PAIR, d_x, nullptr, &carry);
-      if (rc == IEM_OK) rc = launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], d_x, d_y, d_jac, obj_weight, nullptr, d_hess, carry);
-      return rc;
-    }
+  if (!m->code.launchable[iem::KK_PAIR].empty()) {
+    LaunchHead h;
+    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess;
+    return launch_kind(m, m->code, iem::KK_PAIR, h);
+  }
   int rc = iem_jac_coord(m, d_x, d_jac);
   if (rc == IEM_OK) rc = iem_hess_coord(m, d_x, d_y, obj_weight, d_hess);
   return rc;
@@ -1365,44 +1354,38 @@ int iem_jac_hess_coord(iem_model *m, const double *d_x, const double *d_y, doubl
  * TRIAL point of its line search and grad! + jac_coord! + hess_coord! once per ACCEPTED point (the reference's solvers:
  * ext/InfiniteExaModelsMadNLP.jl:49-50,64, ext/InfiniteExaModelsIpopt.jl:48-49).  The member kinds' bodies — the very
  * functions the separate calls run — sit behind one workgroup-id dispatcher: identical bytes, one launch instead of two /
- * three (5-7 us each on the grids the reference benchmarks, ESCAPE34/run_cases_gpu.jl:89-102).  Handles without the kernel
- * (option "phase_kernels" = 0, a model without objective or without constraints, kinds of different workgroup sizes) make
- * the separate calls. */
+ * three (5-7 us each on the grids the reference benchmarks, ESCAPE34/run_cases_gpu.jl:89-102).  Handles without a launchable
+ * kernel (option "phase_kernels" = 0, a model without objective or without constraints, kinds of different workgroup sizes)
+ * make the separate calls. */
 int iem_eval_trial(iem_model *m, const double *d_x, double *d_c, double *h_obj) {
   if (!m || !d_x || (!d_c && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (size_t k = 0; k < m->prog.kernels.size(); ++k)
-    if (m->prog.kernels[k].kind == iem::KK_TRIAL && m->prog.n_partials > 0) {
-      if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_trial: the previous iem_obj_begin / iem_eval_trial has not been collected (iem_obj_end)");
-      *reinterpret_cast<volatile uint64_t *>(m->h_obj) = kObjSentinel;
-      bool carry = false;
-      int rc = halo_plan(m, iem::KK_TRIAL, d_x, nullptr, &carry);
-      // out = c, aux = the objective scalar (mapped host memory), p2 = the objective's partials
-      if (rc == IEM_OK) rc = launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], d_x, nullptr, d_c, 0.0, nullptr, m->d_hobj, carry, m->d_partials);
-      if (rc) return rc;
-      m->obj_armed = true;
-      return h_obj ? iem_obj_end(m, h_obj) : IEM_OK;
-    }
-  int rc = iem_obj_begin(m, d_x);
-  if (rc == IEM_OK) rc = iem_cons(m, d_x, d_c);
-  if (rc == IEM_OK && h_obj) rc = iem_obj_end(m, h_obj);
-  return rc;
+  int rc;
+  if (!m->code.launchable[iem::KK_TRIAL].empty() && m->code.prog.n_partials > 0) {
+    if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_trial: the previous iem_obj_begin / iem_eval_trial has not been collected (iem_obj_end)");
+    obj_arm(m);
+    LaunchHead h;
+    h.x = d_x; h.out = d_c; h.aux = m->d_hobj; h.trial_partials = m->d_partials;
+    rc = launch_kind(m, m->code, iem::KK_TRIAL, h);
+  } else if ((rc = iem_obj_begin(m, d_x)) == IEM_OK) {
+    rc = iem_cons(m, d_x, d_c);
+  } else {
+    return rc;   // (not armed)
+  }
+  if (rc) { m->obj_armed = false; return rc; }
+  return h_obj ? iem_obj_end(m, h_obj) : IEM_OK;
 }
 
 int iem_eval_accepted(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_g, double *d_jac, double *d_hess) {
   if (!m || !d_x || !d_g || (!d_y && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (size_t k = 0; k < m->prog.kernels.size(); ++k)
-    if (m->prog.kernels[k].kind == iem::KK_ACCEPTED) {
-      for (auto &z : m->grad_zero)   // zero only what grad!'s bodies do not overwrite completely
-        HIP_TRY(hipMemsetAsync(d_g + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-      bool carry = false;
-      int rc = halo_plan(m, iem::KK_ACCEPTED, d_x, nullptr, &carry);
-      // out = jac values, aux = hess values, p2 = g, p3 = grad!'s reduction buffer
-      if (rc == IEM_OK) rc = launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], d_x, d_y, d_jac, obj_weight, nullptr, d_hess, carry, d_g, m->d_red[iem::KK_GRAD]);
-      if (rc == IEM_OK) rc = kind_followups(m, iem::KK_GRAD, d_g, m->d_red[iem::KK_GRAD]);
-      return rc;
-    }
+  if (!m->code.launchable[iem::KK_ACCEPTED].empty()) {
+    int rc = zero_uncovered(m, iem::KK_GRAD, d_g);
+    if (rc) return rc;
+    LaunchHead h;
+    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->d_red[iem::KK_GRAD];
+    return launch_kind(m, m->code, iem::KK_ACCEPTED, h);
+  }
   int rc = iem_grad(m, d_x, d_g);
   if (rc == IEM_OK) rc = iem_jac_hess_coord(m, d_x, d_y, obj_weight, d_jac, d_hess);
   return rc;
@@ -1415,25 +1398,22 @@ int iem_eval_all(iem_model *m, const double *d_x, const double *d_y, double obj_
   if (!m || !d_x || !d_g || (!d_c && m->model.ncon) || (!d_y && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh))
     return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  for (size_t k = 0; k < m->prog.kernels.size(); ++k)
-    if (m->prog.kernels[k].kind == iem::KK_ALL && m->prog.n_partials > 0) {
-      if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_all: the previous iem_obj_begin / iem_eval_trial / iem_eval_all has not been collected (iem_obj_end)");
-      for (auto &z : m->grad_zero)
-        HIP_TRY(hipMemsetAsync(d_g + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-      *reinterpret_cast<volatile uint64_t *>(m->h_obj) = kObjSentinel;
-      bool carry = false;
-      int rc = halo_plan(m, iem::KK_ALL, d_x, nullptr, &carry);
-      if (rc == IEM_OK) rc = launch_one(m, m->prog.kernels[k], m->fns[k], m->argbuf[k], d_x, d_y, d_jac, obj_weight, nullptr, d_hess, carry, d_g, m->d_red[iem::KK_GRAD],
-                                        d_c, m->d_partials, m->d_hobj);
-      if (rc == IEM_OK) rc = kind_followups(m, iem::KK_GRAD, d_g, m->d_red[iem::KK_GRAD]);
-      if (rc) return rc;
-      m->obj_armed = true;
-      return h_obj ? iem_obj_end(m, h_obj) : IEM_OK;
-    }
-  int rc = iem_eval_trial(m, d_x, d_c, nullptr);
-  if (rc == IEM_OK) rc = iem_eval_accepted(m, d_x, d_y, obj_weight, d_g, d_jac, d_hess);
-  if (rc == IEM_OK && h_obj) rc = iem_obj_end(m, h_obj);
-  return rc;
+  int rc;
+  if (!m->code.launchable[iem::KK_ALL].empty() && m->code.prog.n_partials > 0) {
+    if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_all: the previous iem_obj_begin / iem_eval_trial / iem_eval_all has not been collected (iem_obj_end)");
+    if ((rc = zero_uncovered(m, iem::KK_GRAD, d_g))) return rc;
+    obj_arm(m);
+    LaunchHead h;
+    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->d_red[iem::KK_GRAD];
+    h.c = d_c; h.partials = m->d_partials; h.obj = m->d_hobj;
+    rc = launch_kind(m, m->code, iem::KK_ALL, h);
+  } else if ((rc = iem_eval_trial(m, d_x, d_c, nullptr)) == IEM_OK) {
+    rc = iem_eval_accepted(m, d_x, d_y, obj_weight, d_g, d_jac, d_hess);
+  } else {
+    return rc;   // (not armed)
+  }
+  if (rc) { m->obj_armed = false; return rc; }
+  return h_obj ? iem_obj_end(m, h_obj) : IEM_OK;
 }
 
 int iem_jac_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) {
@@ -1446,7 +1426,7 @@ int iem_jac_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) 
 int iem_hess_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) {
   if (!m || ((!h_rows || !h_cols) && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  if (!m->prog.hess_classes.empty()) hess_structure_merged_host(m->model, m->prog.hess_classes, h_rows, h_cols, base);
+  if (!m->code.prog.hess_classes.empty()) hess_structure_merged_host(m->model, m->code.prog.hess_classes, h_rows, h_cols, base);
   else hess_structure_host(m->model, h_rows, h_cols, base);
   return IEM_OK;
 }
@@ -2692,7 +2672,7 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
 int iem_tuner_choice(iem_model *m, int kind, const double *d_vals, int *out_choice) {
   if (!m || !out_choice || kind < 0 || kind > 1) return fail(IEM_E_ARG, "bad argument");
   *out_choice = -1;
-  if (m->alt.on)
+  if (m->alt.mod)
     for (auto &t : m->tune[kind].slot)
       if (t.out == d_vals) *out_choice = t.choice;
   return IEM_OK;
@@ -2700,7 +2680,7 @@ int iem_tuner_choice(iem_model *m, int kind, const double *d_vals, int *out_choi
 
 int iem_tune(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_jac, double *d_hess) {
   if (!m || !d_x || (d_hess && !d_y)) return fail(IEM_E_ARG, "bad argument");
-  if (!m->alt.on) return IEM_OK;
+  if (!m->alt.mod) return IEM_OK;
   DevGuard dg_(m->device);
   // Per kind and variant, twice: six warm launches, then ten launches between ONE pair of events (the faster block counts) — the steady state of that
   // kernel into that buffer.  (Events around every single launch, as the implicit tuner of a running solve uses,
@@ -2717,7 +2697,9 @@ int iem_tune(iem_model *m, const double *d_x, const double *d_y, double obj_weig
     float ms[2] = {1e30f, 1e30f};
     for (int round = 0; round < 2 && rc == IEM_OK; ++round)   // default, large batch, default, large batch: the first blocks of a process run on a GPU that is still ramping up
     for (int v = 0; v < 2 && rc == IEM_OK; ++v) {
-      auto go = [&]() { return v ? launch_kind_alt(m, kind, d_x, d_y, out, obj_weight) : launch_kind(m, kind, d_x, d_y, out, obj_weight); };
+      LaunchHead h;
+      h.x = d_x; h.y = d_y; h.out = out; h.w = obj_weight;
+      auto go = [&]() { return launch_kind(m, v ? m->alt : m->code, kind, h); };
       for (int i = 0; i < 6 && rc == IEM_OK; ++i) rc = go();   // warm: the first launches of a code object run cold
       if (rc == IEM_OK && hipEventRecord(e0, m->stream) != hipSuccess) rc = fail(IEM_E_HIP, "hipEventRecord");
       for (int i = 0; i < 10 && rc == IEM_OK; ++i) rc = go();
@@ -2728,15 +2710,12 @@ int iem_tune(iem_model *m, const double *d_x, const double *d_y, double obj_weig
       if (getenv("IEM_TUNER_LOG")) fprintf(stderr, "iem tuner (iem_tune): kind %d round %d variant %d block %.4f ms per launch\n", kind, round, v, t / 10);
     }
     if (rc != IEM_OK) break;
-    iem_model::TuneSet &S = m->tune[which];
-    iem_model::Tune *hit = nullptr;
-    for (auto &t : S.slot) if (t.out == out) hit = &t;
-    if (!hit) { hit = &S.slot[S.next]; S.next = (S.next + 1) % 4; hit->out = out; }
-    hit->calls = IEM_TUNE_CALLS;
-    hit->choice = ms[1] < 0.98f * ms[0] ? 1 : 0;
+    iem_model::Tune &T = tune_slot(m, which, out);
+    T.calls = IEM_TUNE_CALLS;
+    T.choice = ms[1] < 0.98f * ms[0] ? 1 : 0;
     if (getenv("IEM_TUNER_LOG"))
       fprintf(stderr, "iem tuner (iem_tune): kind %d buffer %p: default %.4f ms, large batch %.4f ms -> %s\n", kind, (const void *)out,
-              ms[0] / 10, ms[1] / 10, hit->choice ? "large batch" : "default");
+              ms[0] / 10, ms[1] / 10, T.choice ? "large batch" : "default");
   }
   hipEventDestroy(e0); hipEventDestroy(e1);
   if (rc == IEM_OK) HIP_TRY(hipStreamSynchronize(m->stream));

@@ -91,6 +91,22 @@ std::string hexf(double v) {
   return s;
 }
 
+// A generated kernel's argument struct and signature.  The 13-word head {x, th, y, v, out, w, aux, comm, p2 .. p6} is what
+// the runtime rewrites before every launch (iem_api.cpp: LaunchHead); the kernel's tables {ip, dp, fa, ia} follow it, inline
+// or, when they do not fit the argument segment, as pointers to a device copy.
+void emit_kernel_head(std::ostream &os, const std::string &name, bool tables_in_memory, size_t nip, size_t ndp, size_t nfa, size_t nia,
+                      int min_waves) {
+  os << "struct Args_" << name << " {\n  const double* x; const double* th; const double* y; const double* v; double* out; double w; double* aux; const IemHaloArgs* comm;\n"
+     << "  double* p2; double* p3; double* p4; double* p5; double* p6;\n";
+  if (tables_in_memory)
+    os << "  const long long* ip; const double* dp; const double* const* fa; const long long* const* ia;\n};\n";
+  else
+    os << "  long long ip[" << std::max<size_t>(1, nip) << "]; double dp[" << std::max<size_t>(1, ndp) << "]; const double* fa[" << std::max<size_t>(1, nfa)
+       << "]; const long long* ia[" << std::max<size_t>(1, nia) << "];\n};\n";
+  os << "extern \"C\" __global__ __launch_bounds__(IEM_TILE" << (min_waves > 0 ? ", " + std::to_string(min_waves) : std::string()) << ") void " << name
+     << "(const Args_" << name << " A) {\n";
+}
+
 // pseudo unary ops beyond the blob vocabulary
 enum { U_SGN = 1000 };
 
@@ -1816,14 +1832,7 @@ class KernelBuilder {
       os << "  (void)X; (void)TH; (void)Y; (void)V; (void)FA; (void)IA; (void)A; (void)AUX; (void)lds_blk; (void)lds4; (void)BY_; (void)BZ_; (void)GX_; (void)GY_; (void)GZ_;\n";
       kd.tables_in_memory = false;
     } else {
-    os << "struct Args_" << name_ << " {\n  const double* x; const double* th; const double* y; const double* v; double* out; double w; double* aux; const IemHaloArgs* comm;\n"
-       << "  double* p2; double* p3; double* p4; double* p5; double* p6;\n";
-    if (kd.tables_in_memory)
-      os << "  const long long* ip; const double* dp; const double* const* fa; const long long* const* ia;\n};\n";
-    else
-      os << "  long long ip[" << nip << "]; double dp[" << ndp << "]; const double* fa[" << nfa << "]; const long long* ia[" << nia << "];\n};\n";
-    os << "extern \"C\" __global__ __launch_bounds__(IEM_TILE" << (opt_.min_waves > 0 ? ", " + std::to_string(opt_.min_waves) : std::string())
-       << ") void " << name_ << "(const Args_" << name_ << " A) {\n";
+    emit_kernel_head(os, name_, kd.tables_in_memory, nip, ndp, nfa, nia, opt_.min_waves);
     os << "  const double* __restrict__ X = A.x; const double* __restrict__ TH = A.th; const double* __restrict__ Y = A.y;\n";
     os << "  const double* __restrict__ V = A.v; (void)V;\n";
     os << "  double* __restrict__ OUT = A.out; double* __restrict__ AUX = A.aux; (void)AUX;\n";
@@ -2913,16 +2922,7 @@ Program generate(const Model &m, const Options &opt_in) {
     return c.str();
   };
   auto args_struct = [&](const KernelDesc &F) {
-    const size_t nip = std::max<size_t>(1, F.ip.size()), ndp = std::max<size_t>(1, F.dp.size());
-    const size_t nfa = std::max<size_t>(1, F.fa.size()), nia = std::max<size_t>(1, F.ia.size());
-    src << "struct Args_" << F.name << " {\n  const double* x; const double* th; const double* y; const double* v; double* out; double w; double* aux; const IemHaloArgs* comm;\n"
-        << "  double* p2; double* p3; double* p4; double* p5; double* p6;\n";
-    if (F.tables_in_memory)
-      src << "  const long long* ip; const double* dp; const double* const* fa; const long long* const* ia;\n};\n";
-    else
-      src << "  long long ip[" << nip << "]; double dp[" << ndp << "]; const double* fa[" << nfa << "]; const long long* ia[" << nia << "];\n};\n";
-    src << "extern \"C\" __global__ __launch_bounds__(IEM_TILE" << (opt.min_waves > 0 ? ", " + std::to_string(opt.min_waves) : std::string())
-        << ") void " << F.name << "(const Args_" << F.name << " A) {\n";
+    emit_kernel_head(src, F.name, F.tables_in_memory, F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), opt.min_waves);
   };
   for (int kind = 0; kind < KK_COUNT; ++kind) {
     std::vector<size_t> ks;
@@ -3216,14 +3216,7 @@ Program generate(const Model &m, const Options &opt_in) {
         const size_t nip = std::max<size_t>(1, F.ip.size()), ndp = std::max<size_t>(1, F.dp.size());
         const size_t nfa = std::max<size_t>(1, F.fa.size()), nia = std::max<size_t>(1, F.ia.size());
         F.tables_in_memory = (nip + ndp + nfa + nia) > 320 || F.ip.size() > tbl;
-        src << "struct Args_" << F.name << " {\n  const double* x; const double* th; const double* y; const double* v; double* out; double w; double* aux; const IemHaloArgs* comm;\n"
-            << "  double* p2; double* p3; double* p4; double* p5; double* p6;\n";
-        if (F.tables_in_memory)
-          src << "  const long long* ip; const double* dp; const double* const* fa; const long long* const* ia;\n};\n";
-        else
-          src << "  long long ip[" << nip << "]; double dp[" << ndp << "]; const double* fa[" << nfa << "]; const long long* ia[" << nia << "];\n};\n";
-        src << "extern \"C\" __global__ __launch_bounds__(IEM_TILE" << (opt.min_waves > 0 ? ", " + std::to_string(opt.min_waves) : std::string())
-            << ") void " << F.name << "(const Args_" << F.name << " A) {\n";
+        args_struct(F);
         if (F.lds_bytes > 0) src << "  __shared__ double lds_blk[" << (F.lds_bytes / 8) << "];\n";
         else src << "  double* lds_blk = nullptr;\n";
         src << "  double* lds4 = nullptr;\n";
