@@ -44,6 +44,16 @@
  *
  * Item coordinates: item ordinal k = k_0 + dims[0]*(k_1 + dims[1]*k_2), first
  * coordinate fastest — the order Iterators.product gives at transform.jl:445.
+ *
+ * A product of more than three groups is written in this same format: the producer merges
+ * ADJACENT factors into runs, each run one box axis of extent prod n_i in mixed-radix order
+ * (first factor fastest), so the item order is the product's.  An axis restricted by the
+ * template (a derivative's parameter, a sub-range) is alone in its run or its slowest digit.
+ * Per run an index expression has one term: on the run coordinate when its strides match the
+ * slab's, else on an int64 column of n_run values (step 1 on that run's axis, 0 elsewhere)
+ * holding one digit or the run's whole contribution; float fields of one digit read a column of
+ * n_run values the same way.  A merged run's grid hint is a virtual grid id in 3500..4093, its
+ * slab-table axis has group 0; a model with such a template cannot be sharded or chained.
  */
 #ifndef IEM_BLOB_H
 #define IEM_BLOB_H

@@ -21,7 +21,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .items import Items, as_items, Field
+from .items import Fold, Items, as_items, Field, fold_runs, MAX_DIMS, RUN_GRID_LO, RUN_GRID_HI
 from .nodes import (OP, Binary, Const, DataField, Node, Null, ParameterNode, Unary, Var,
                     affine_index)
 
@@ -138,6 +138,9 @@ class ExaCore:
         # (offset, dims, infinite-parameter group of each axis; 0 = none) of every add_var slab — the
         # blob's slab table, from which iem_create_sharded cuts a rank's window (include/iem_blob.h)
         self.slabs: List[Tuple[int, Tuple[int, ...], Tuple[int, ...]]] = []
+        # a slab or template over more than three groups was folded (items.fold_runs): sharding and the
+        # chain KKT solver refuse such a model
+        self.folded = False
 
     # the core buffers (views into the growable storage; element writes go through)
     x0 = property(lambda self: self._bufs["x0"].view)
@@ -170,6 +173,10 @@ class ExaCore:
         assert len(groups) == len(dims)
         if len(dims) <= 3:
             self.slabs.append((var.offset, dims, groups))
+        else:   # folded like an item box over the same groups; a merged axis belongs to no group
+            F = Fold(dims, fold_runs(dims, (True,) * len(dims)))
+            self.slabs.append((var.offset, tuple(F.ext), tuple(groups[lo] if hi - lo == 1 else 0 for lo, hi in F.runs)))
+            self.folded = True
 
         def expand(v):
             a = np.asarray(v, dtype=np.float64)
@@ -234,6 +241,8 @@ class ExaCore:
     def _compile(self, kind: int, expr, items: Items) -> _Template:
         if isinstance(expr, numbers.Real):
             expr = Null(expr)
+        if len(items.dims) > MAX_DIMS:
+            return self._compile_folded(kind, expr, items)
         t = _Template()
         t.kind, t.items, t.expr = kind, items, expr
         t.tag = ("tpl", len(self.templates))   # the transcriber overwrites it with a model-level tag
@@ -274,6 +283,124 @@ class ExaCore:
             if len(terms) > MAX_IDX_TERMS:
                 raise ValueError("index expression uses too many item fields")
             key = (c0, tuple((ifield(k), v) for k, v in terms.items()))
+            if key not in idx_ids:
+                idx_ids[key] = len(t.idx)
+                t.idx.append(key)
+            return idx_ids[key]
+
+        def emit(node) -> int:
+            if isinstance(node, Const):
+                t.nodes.append((OP["const"], 0, 0, node.value))
+            elif isinstance(node, DataField):
+                t.nodes.append((OP["data"], ffield(node.name), 0, 0.0))
+            elif isinstance(node, ParameterNode):
+                t.nodes.append((OP["par"], index(node.i), 0, 0.0))
+            elif isinstance(node, Var):
+                t.nodes.append((OP["var"], index(node.i), 0, 0.0))
+            elif isinstance(node, Unary):
+                a = emit(node.inner)
+                t.nodes.append((OP[node.op], a, 0, 0.0))
+            elif isinstance(node, Binary):
+                a = emit(node.inner1)
+                b = emit(node.inner2)
+                t.nodes.append((OP[node.op], a, b, 0.0))
+            else:
+                raise TypeError(f"not a template expression: {node!r}")
+            return len(t.nodes) - 1
+
+        if isinstance(expr, Null):
+            t.nodes.append((OP["const"], 0, 0, expr.value))
+            t.root = 0
+        else:
+            t.root = emit(expr)
+        return t
+
+    def _compile_folded(self, kind: int, expr, logical: Items) -> _Template:
+        """:meth:`_compile` of a template over more than three item axes: the items fold into a box of
+        at most three runs (``items.fold_runs``); fields and index expressions are rewritten over it.
+        An index ``c0 + Σ coef·field`` is first made affine in the logical coordinates, then per run
+        either one term on the run coordinate (slab-consistent strides), one term on a short digit
+        column (a single digit of the run), or one term on a short column of the run's whole
+        contribution; a gathered field over several runs keeps a term of its own."""
+        F = Fold(logical.dims, fold_runs(logical.dims, logical.free))
+        items = logical.fold(F.runs)
+        self.folded = True
+        t = _Template()
+        t.kind, t.items, t.expr = kind, items, expr
+        t.tag = ("tpl", len(self.templates))
+        t.nodes, t.ifields, t.ffields, t.idx = [], [], [], []
+        if_ids: Dict[tuple, int] = {}
+        ff_ids: Dict[str, int] = {}
+        idx_ids: Dict[tuple, int] = {}
+
+        def lfield(name: str) -> Field:
+            f = logical.fields.get(name)
+            if f is None:
+                raise KeyError(f"item iterator has no field `{name}`")
+            return f
+
+        def ifield(key: tuple, make) -> int:
+            if key not in if_ids:
+                if_ids[key] = len(t.ifields)
+                t.ifields.append(make())
+            return if_ids[key]
+
+        def ffield(name: str) -> int:
+            if name not in ff_ids:
+                f = lfield(name)
+                if f.kind == "int":  # integer item data used as a Float64 leaf
+                    f = Field("float", "gather", 0, tuple(F.stride[d] * int(np.prod(
+                        [F.ext[r] for r in range(F.run_of[d])], dtype=np.int64)) for d in range(len(F.dims))),
+                        np.ascontiguousarray(f.values(logical.dims).astype(np.float64)))
+                ff_ids[name] = len(t.ffields)
+                t.ffields.append(F.field(f))
+            return ff_ids[name]
+
+        def unit(r: int) -> Tuple[int, ...]:
+            return tuple(1 if q == r else 0 for q in range(len(F.runs)))
+
+        def index(i) -> int:
+            c0, terms = affine_index(i)
+            a = np.zeros(len(F.dims), dtype=np.int64)   # logical coefficients of the affine part
+            cols: Dict[int, np.ndarray] = {}             # run -> gathered contributions over it
+            extra = []
+            for name, coef in terms.items():
+                f = lfield(name)
+                if f.kind != "int":
+                    raise TypeError(f"item field `{name}` is not an integer; cannot index with it")
+                if f.mode == "affine":
+                    c0 += coef * f.base
+                    a += coef * np.asarray(f.steps, dtype=np.int64)
+                    continue
+                touched = F.touched(f.steps)
+                if len(touched) == 1:
+                    r = touched[0]
+                    col, _ = F.over_runs([r], lambda k: f.arr[f.base + sum(int(f.steps[d]) * k[d] for d in range(len(F.dims)))])
+                    cols[r] = cols.get(r, 0) + coef * col.astype(np.int64)
+                else:
+                    g = F.field(f)
+                    extra.append((ifield(("field", name), lambda: g), coef))
+            out = []
+            for r, (lo, hi) in enumerate(F.runs):
+                digits = [d for d in range(lo, hi) if a[d] != 0 and F.dims[d] > 1]
+                if not digits and r not in cols:
+                    continue
+                c = F.collapse([int(a[d]) if lo <= d < hi else 0 for d in range(len(F.dims))])
+                if r not in cols and c is not None:
+                    out.append((ifield(("run", r), lambda: Field("int", "affine", 0, unit(r))), c[r]))
+                elif r not in cols and len(digits) == 1:
+                    d = digits[0]
+                    out.append((ifield(("digit", d), lambda: Field("int", "gather", 0, unit(r), np.ascontiguousarray(F.digit(d)))),
+                                int(a[d])))
+                else:
+                    col = cols.get(r, 0) + sum(int(a[d]) * F.digit(d) for d in digits)
+                    col = np.ascontiguousarray(np.broadcast_to(col, (F.ext[r],)).astype(np.int64))
+                    out.append((ifield(("col", r, col.tobytes()), lambda: Field("int", "gather", 0, unit(r), col)), 1))
+            out += extra
+            if len(out) > MAX_IDX_TERMS:
+                raise ValueError(f"index expression over {len(F.dims)} item axes folded into runs {F.runs} needs "
+                                 f"{len(out)} item fields; the blob allows {MAX_IDX_TERMS}")
+            key = (int(c0), tuple(out))
             if key not in idx_ids:
                 idx_ids[key] = len(t.idx)
                 t.idx.append(key)

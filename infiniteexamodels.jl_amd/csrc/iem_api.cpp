@@ -830,6 +830,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "pair_inter") == 0) { o.pair_inter = value != 0; return IEM_OK; }
   if (std::strcmp(name, "split_shift") == 0) { o.split_shift = value != 0; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
+  if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;

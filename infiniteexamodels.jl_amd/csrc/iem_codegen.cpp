@@ -146,6 +146,8 @@ struct ILoad {
   int ia_slot;
   AffQ pos;
   std::set<int> guards;
+  // digit decode (FieldDesc digit form): no load — v0 + a * ((pos / r) mod q), 32-bit unsigned with literal r, q
+  int64_t r = 0, q = 0, v0 = 0, a = 0;
 };
 
 struct Load {
@@ -298,6 +300,17 @@ class KernelBuilder {
     iloads_.push_back(ILoad{ia, pos, {guard}});
     return (int)iloads_.size() - 1;
   }
+  int dload(const AffQ &pos, int64_t r, int64_t q, int64_t v0, int64_t a, int guard) {
+    for (size_t i = 0; i < iloads_.size(); ++i) {
+      ILoad &l = iloads_[i];
+      if (l.ia_slot == -1 && l.pos == pos && l.r == r && l.q == q && l.v0 == v0 && l.a == a) { l.guards.insert(guard); return (int)i; }
+    }
+    ILoad l{-1, pos, {guard}};
+    l.r = r; l.q = q; l.v0 = v0; l.a = a;
+    iloads_.push_back(l);
+    return (int)iloads_.size() - 1;
+  }
+  bool digit(const FieldDesc &f) const { return opt_.digit_fields && f.dr > 0; }
   int load(int arr, int slot, int idxv, int guard) {
     auto key = std::make_tuple(arr, slot, idxv);
     auto it = load_ids_.find(key);
@@ -436,6 +449,9 @@ class KernelBuilder {
       if (f.mode == IEM_F_AFFINE) {
         iv.aff.c += ix.coef[j] * fa.c;
         for (int d = 0; d < 3; ++d) iv.aff.k[d] += ix.coef[j] * fa.k[d];
+      } else if (digit(f)) {
+        fa.space = 300;
+        iv.ind.emplace_back(ix.coef[j], dload(fa, f.dr, f.dq, f.dv0, f.da, G.guard));
       } else {
         fa.space = 200 + ia_slot(f.arr);
         int il = iload(ia_slot(f.arr), fa, G.guard);
@@ -499,6 +515,13 @@ class KernelBuilder {
             const ArrayDesc &ad = K.m_.arrs[f.arr];
             if (ad.kind == IEM_A_F64_FILL) {
               val[n] = K.mk(VDP, K.dp(ad.fill), -1, -1, -1, 0);
+            } else if (K.digit(f)) {   // the shrunk column indexed by the decoded digit
+              AffQ pa = K.field_aff(t, f, G);
+              pa.space = 300;
+              IdxVal iv;
+              iv.aff.space = 100 + K.fa_slot(f.darr);
+              iv.ind.emplace_back(1, K.dload(pa, f.dr, f.dq, 0, 1, G.guard));
+              val[n] = K.load(3, K.fa_slot(f.darr), K.idxval(iv), G.guard);
             } else {
               IdxVal iv;
               iv.aff = K.field_aff(t, f, G);
@@ -1750,8 +1773,14 @@ class KernelBuilder {
     }
     for (size_t gi = 0; gi < guards_.size(); ++gi) head << "  const bool g" << gi << " = " << guards_[gi] << ";\n";
     for (size_t i = 0; i < iloads_.size(); ++i) {
-      head << "  const long long il" << i << " = " << guard_or(iloads_[i].guards) << " ? IA" << "[" << iloads_[i].ia_slot << "]["
-           << aff_str(iloads_[i].pos) << "] : 0LL;\n";
+      const ILoad &l = iloads_[i];
+      if (l.ia_slot < 0) {   // decoded digit: 32-bit unsigned division by literals (multiply-high + shift)
+        head << "  const long long il" << i << " = " << guard_or(l.guards) << " ? " << coefstr(l.v0) << " + " << coefstr(l.a)
+             << " * (long long)((unsigned)(" << aff_str(l.pos) << ") / " << l.r << "u % " << l.q << "u) : 0LL;\n";
+        continue;
+      }
+      head << "  const long long il" << i << " = " << guard_or(l.guards) << " ? IA" << "[" << l.ia_slot << "]["
+           << aff_str(l.pos) << "] : 0LL;\n";
     }
     for (int id : need_idx) {
       const IdxVal &iv = idx_[id];
@@ -1798,7 +1827,9 @@ class KernelBuilder {
         }
         elems += cur_hi - cur_lo + 1;
       }
-      iload_elems_ = (int64_t)iloads_.size() * g_.ext[0] * g_.ext[1] * g_.ext[2];
+      int64_t n_il = 0;
+      for (const ILoad &l : iloads_) n_il += l.ia_slot >= 0;   // decoded digits read nothing
+      iload_elems_ = n_il * g_.ext[0] * g_.ext[1] * g_.ext[2];
       kd.alg_bytes_read = 8 * (elems + iload_elems_);
       if (kind_ == KK_GRAD || kind_ == KK_JTPROD || kind_ == KK_HPROD) {
         // scatter kinds: one write per item of every slot that is still its own (merge_scatter sums a lane's
@@ -2670,6 +2701,11 @@ Program generate(const Model &m, const Options &opt_in) {
             for (auto &t : iv.ind) {
               const ILoad &il = kb.iloads()[t.second];
               const int64_t p = il.pos.c + il.pos.k[0] * q[0] + il.pos.k[1] * c1 + il.pos.k[2] * c2;
+              if (il.ia_slot < 0) {   // decoded digit (the same value the kernel computes)
+                if (p < 0 || p >= ((int64_t)1 << 31)) throw std::runtime_error("digit position out of range");
+                d += t.first * (il.v0 + il.a * ((p / il.r) % il.q));
+                continue;
+              }
               const ArrayDesc &arr = m.arrs[kb.ia_arrays()[il.ia_slot]];
               if (p < 0 || p >= arr.n) throw std::runtime_error("index array position out of range");
               d += t.first * arr.i(p);

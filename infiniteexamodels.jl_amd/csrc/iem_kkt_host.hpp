@@ -69,6 +69,9 @@ inline KktLayout kkt_layout(const Model &m, const std::vector<int64_t> &jr, cons
   KktLayout L;
   L.nvar = m.nvar; L.ncon = m.ncon;
   const int64_t nvar = m.nvar, ncon = m.ncon, n = nvar + ncon, nj = (int64_t)jr.size();
+  if (const int ft = folded_run_template(m); ft >= 0)
+    throw std::runtime_error("chain KKT: template " + std::to_string(ft) + " folds several parameter groups into one item axis "
+                             "(a product of more than three groups); the chain solver does not support such a model");
   std::set<int> groups;
   for (const Slab &s : m.slabs) for (int a = 0; a < s.nd; ++a) if (s.group[a] > 0) groups.insert(s.group[a]);
   if (groups.empty()) throw std::runtime_error("chain KKT: the model has no infinite-parameter slab table (nothing to chain along)");

@@ -37,6 +37,11 @@ struct FieldDesc {
   int mode = 0;
   int64_t base = 0, step[3] = {0, 0, 0};
   int arr = -1;
+  // digit form (library-internal, never on the wire; set by recover_digits): this GATHER field's column position p
+  // (= base + step.k, base 0 and unit step on one axis) holds  dv0 + da * ((p / dr) mod dq)  — an integer field — or, for a
+  // float field, darr[(p / dr) mod dq] with darr the column shrunk to dq values.  dr == 0: no digit form.
+  int64_t dr = 0, dq = 0, dv0 = 0, da = 0;
+  int darr = -1;
 };
 
 struct IdxExpr {
@@ -108,6 +113,25 @@ struct Model {
   std::deque<std::vector<double>> synth;  // arrays created by recover_lattice / the shard cut (ArrayDesc::data points here)
   std::deque<std::vector<int64_t>> synth_i;   // ... integer columns (shard cut of explicit item lists)
 };
+
+// Grid hints of box axes that fold several infinite-parameter groups into one run (a product of more than
+// three groups, include/iem_blob.h): the producer gives such an axis a virtual grid id in this range.
+constexpr int IEM_RUN_GRID_LO = 3500, IEM_RUN_GRID_HI = 4094;
+
+// Does any template of `m` carry a folded run (a box axis over several groups)?  Sharding along a group and
+// chaining the KKT system along one need every group on an axis of its own: both refuse such a model.
+inline int folded_run_template(const Model &m) {
+  for (size_t i = 0; i < m.tpl.size(); ++i) {
+    const auto &t = m.tpl[i];
+    if (t.grid_id <= 0 || t.lattice_recovered) continue;
+    int64_t g = t.grid_id;
+    for (int d = 0; d < t.nd; ++d, g /= 4096) {
+      const int64_t v = g % 4096 - 1;
+      if (v >= IEM_RUN_GRID_LO && v < IEM_RUN_GRID_HI) return (int)i;
+    }
+  }
+  return -1;
+}
 
 inline double w2d(int64_t w) {
   double d;
@@ -285,6 +309,79 @@ inline void recover_lattice(Model &m, Template &t) {
   }
 }
 
+// A product of more than three groups folds adjacent groups into one box axis (a run, grid hint in the run range); a
+// factor inside a run reaches the template as a short integer column of one mixed-radix digit, k_d = (k / r) mod q.
+// This pass recognises such columns — v0 + a·((k / r) mod q) over exactly one run axis, unit step, constant along the
+// other axes — and gives them the digit form, so that the generator decodes them from the item coordinate instead of
+// reading them (Options::digit_fields).  Float columns that depend on one recognised digit only are shrunk to its q
+// values.  Only templates carrying a run grid id are touched; everything else keeps its gathers.
+inline void recover_digits(Model &m, Template &t) {
+  if (t.grid_id <= 0 || t.lattice_recovered || t.n_items < 2) return;
+  bool run[3] = {false, false, false};
+  bool any = false;
+  int64_t g = t.grid_id;
+  for (int d = t.nd - 1; d >= 0; --d, g /= 4096) {
+    const int64_t v = g % 4096 - 1;
+    run[d] = v >= IEM_RUN_GRID_LO && v < IEM_RUN_GRID_HI && t.dims[d] >= 2;
+    any = any || run[d];
+  }
+  if (!any) return;
+  auto one_axis = [&](const FieldDesc &f) {   // the run axis the column runs along with base 0 and unit step, else -1
+    if (f.mode != IEM_F_GATHER || f.base != 0) return -1;
+    int ax = -1;
+    for (int d = 0; d < t.nd; ++d) {
+      if (t.dims[d] <= 1 || f.step[d] == 0) continue;
+      if (ax >= 0 || f.step[d] != 1) return -1;
+      ax = d;
+    }
+    return ax >= 0 && run[ax] && t.dims[ax] < ((int64_t)1 << 31) ? ax : -1;
+  };
+  std::vector<std::pair<int, std::pair<int64_t, int64_t>>> digits;   // (axis, (r, q)) recognised
+  for (FieldDesc &f : t.ifields) {
+    const int ax = one_axis(f);
+    if (ax < 0) continue;
+    const ArrayDesc &A = m.arrs[f.arr];
+    const int64_t n = t.dims[ax], v0 = A.i(0);
+    int64_t r = 0;
+    for (int64_t j = 1; j < n && !r; ++j) if (A.i(j) != v0) r = j;
+    if (!r) continue;
+    const int64_t a = A.i(r) - v0;
+    int64_t q = (n + r - 1) / r;
+    for (int64_t mq = 1; mq * r < n; ++mq) if (A.i(mq * r) == v0) { q = mq; break; }
+    bool ok = true;
+    for (int64_t j = 0; j < n && ok; ++j) ok = A.i(j) == v0 + a * ((j / r) % q);
+    if (!ok) continue;
+    f.dr = r; f.dq = q; f.dv0 = v0; f.da = a;
+    digits.push_back({ax, {r, q}});
+  }
+  for (FieldDesc &f : t.ffields) {
+    const int ax = one_axis(f);
+    if (ax < 0) continue;
+    const ArrayDesc &A = m.arrs[f.arr];
+    if (A.kind != IEM_A_F64_DATA) continue;
+    const int64_t n = t.dims[ax];
+    for (const auto &dg : digits) {
+      if (dg.first != ax) continue;
+      const int64_t r = dg.second.first, q = dg.second.second;
+      bool ok = true;
+      for (int64_t j = 0; j < n && ok; ++j) {
+        const double u = A.f(j), w = A.f(((j / r) % q) * r);
+        ok = std::memcmp(&u, &w, 8) == 0;
+      }
+      if (!ok) continue;
+      std::vector<double> col((size_t)q);
+      for (int64_t k = 0; k < q; ++k) col[(size_t)k] = A.f(k * r);
+      m.synth.push_back(std::move(col));
+      ArrayDesc s;
+      s.kind = IEM_A_F64_DATA; s.n = q; s.data = m.synth.back().data();
+      f.darr = (int)m.arrs.size();
+      m.arrs.push_back(s);
+      f.dr = r; f.dq = q; f.dv0 = 0; f.da = 1;
+      break;
+    }
+  }
+}
+
 inline void parse_blob(const void *blob, size_t nbytes, Model &m) {
   if (nbytes < 8 * IEM_HDR_WORDS || nbytes % 8) throw std::runtime_error("blob too small / not word aligned");
   const int64_t *w0 = static_cast<const int64_t *>(blob);
@@ -398,6 +495,7 @@ inline void parse_blob(const void *blob, size_t nbytes, Model &m) {
     }
     if (t.root < 0 || t.root >= n_nodes) throw std::runtime_error("bad root");
     recover_lattice(m, t);
+    recover_digits(m, t);
     analyse_template(t);
     t.o2 = o2; o2 += t.n_items * t.o2step;
     if (o2 > IEM_MAX_COUNT * 64 || o1 > IEM_MAX_COUNT * 64) throw std::runtime_error("nnz out of range");

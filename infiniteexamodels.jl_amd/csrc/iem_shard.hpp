@@ -170,6 +170,9 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
   if (world < 1 || rank < 0 || rank >= world) throw std::runtime_error("bad rank / world");
   if (group < 1 || group > 4094) throw std::runtime_error("bad sharded group id");
   if (m.slabs.empty()) throw std::runtime_error("sharding needs the blob's slab table (header word 9)");
+  if (const int ft = folded_run_template(m); ft >= 0)
+    throw std::runtime_error("sharding: template " + std::to_string(ft) + " folds several parameter groups into one item axis "
+                             "(a product of more than three groups); such a model cannot be sharded");
   info = ShardInfo();
   info.group = group; info.rank = rank; info.world = world;
   info.nvar_global = m.nvar; info.ncon_global = m.ncon; info.nnzj_global = m.nnzj; info.nnzh_global = m.nnzh;

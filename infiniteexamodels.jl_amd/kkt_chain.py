@@ -312,6 +312,9 @@ class ChainKKT:
         m = self.model = kkt.model
         if m.core is None:
             raise _lib.IemError("chain KKT needs the model's core (slab table)")
+        if getattr(m.core, "folded", False):
+            raise NotImplementedError("chain KKT: a model whose item boxes fold more than three parameter groups into runs "
+                                      "is not supported")
         jr, jc = m.jac_structure(0)
         self.layout = L = ChainLayout(m.core.slabs, m.meta.nvar, m.meta.ncon, jr, jc, group=group)
         dev = m.device
@@ -454,6 +457,9 @@ class HubChainKKT:
         self._torch = t = torch
         self.kkt = kkt
         m = self.model = kkt.model
+        if getattr(m.core, "folded", False):
+            raise NotImplementedError("chain KKT: a model whose item boxes fold more than three parameter groups into runs "
+                                      "is not supported")
         jr, jc = m.jac_structure(0)
         self.layout = L = ChainLayout(m.core.slabs, m.meta.nvar, m.meta.ncon, jr, jc, group=group, hubs=True)
         if L.reach != 1 or L.supports_per_block != 1:

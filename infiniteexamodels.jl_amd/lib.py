@@ -204,7 +204,7 @@ def set_option(name: str, value: int):
 OPTION_DEFAULTS = dict(store_mode=2, nt_stores=1, block=0, lds_slots=24, reorder=1, no_fuse=0, hess_merge=0, ablate=0,
                        min_waves=0, fp_contract=0, fuse_zero=1, fuse_groups=1, split_small=64, poll_obj=1, xcd_remap=0, overlap=1, wide_stores=1, obj_wgs=1024, det_shared=1, obj_unroll=1, flat2d=0, flush32=2, autotune=0, autotune_min_blocks=400, pull_scatter=1, fold_colloc=2, fold_max_n=6, det_axis=1, det_scatter=1, det_scatter_max=1 << 28, lazy_loads=2, lazy_min_loads=48, lazy_all_kinds=0, name_tag=0,
                        big_batch_slots=48, big_batch_jac=4000, big_batch_hess=4000, big_xcd=1, big_tile=1024, pair_kernel=1, store_wait=0, comm_timeout_ms=5000,
-                       carrier=0, phase_kernels=1, jac_split=1, jac_split_min=0, pair_inter=0, split_shift=0, cons_direct_2d=1)
+                       carrier=0, phase_kernels=1, jac_split=1, jac_split_min=0, pair_inter=0, split_shift=0, cons_direct_2d=1, digit_fields=1)
 
 
 def option_array(opts: dict):
@@ -349,6 +349,22 @@ def blob_hess_structure(blob: bytes, base: int = 0):
         L.iem_free(r)
         L.iem_free(c)
     return rows, cols
+
+
+def blob_has_folded_runs(blob: bytes) -> bool:
+    """Does a template of ``blob`` fold several parameter groups into one box axis (its grid hint holds a
+    virtual run id, ``items.RUN_GRID_LO`` ..)?  Such a model cannot be sharded or chained."""
+    import numpy as np
+    from .items import RUN_GRID_LO, RUN_GRID_HI
+    w = np.frombuffer(blob, dtype=np.int64)
+    n_tpl, n_arr = int(w[5]), int(w[6])
+    for off in w[14 + 6 * n_arr:14 + 6 * n_arr + n_tpl]:
+        nd, g = int(w[off + 2]), int(w[off + 6])
+        for _ in range(nd if g > 0 else 0):
+            if RUN_GRID_LO <= g % 4096 - 1 < RUN_GRID_HI:
+                return True
+            g //= 4096
+    return False
 
 
 def shard_blob(blob: bytes, group: int, rank: int, world: int):

@@ -75,6 +75,9 @@ class ExaModel:
 
         if device is None:
             device = core.backend.device if core is not None and isinstance(core.backend, MI355XBackend) else 0
+        if _shard is not None and (getattr(core, "folded", False) or (blob is not None and _lib.blob_has_folded_runs(blob))):
+            raise NotImplementedError("sharding a model whose item boxes fold more than three parameter groups "
+                                      "into runs is not supported")
         if not torch.cuda.is_available():
             raise _lib.IemError("no GPU visible: the evaluation path has no CPU fallback")
         self._torch = torch
