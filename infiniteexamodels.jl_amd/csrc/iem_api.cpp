@@ -797,7 +797,6 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
     return IEM_OK;
   }
   if (std::strcmp(name, "det_shared") == 0) { o.det_shared = (int)value; return IEM_OK; }
-  if (std::strcmp(name, "obj_unroll") == 0) { o.obj_unroll = (int)value; return IEM_OK; }
   if (std::strcmp(name, "flat2d") == 0) { o.flat2d = (int)value; return IEM_OK; }
   if (std::strcmp(name, "flush32") == 0) { o.flush32 = (int)value; return IEM_OK; }
   if (std::strcmp(name, "autotune") == 0) { o.autotune = (int)value; return IEM_OK; }
@@ -825,10 +824,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "store_wait") == 0) { o.store_wait = (int)value; return IEM_OK; }
   if (std::strcmp(name, "carrier") == 0) { o.carrier = value != 0; return IEM_OK; }
   if (std::strcmp(name, "phase_kernels") == 0) { o.phase_kernels = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 2) return fail(IEM_E_ARG, "jac_split must be 0, 1 or 2"); o.jac_split = (int)value; return IEM_OK; }
-  if (std::strcmp(name, "jac_split_min") == 0) { if (value < 0) return fail(IEM_E_ARG, "jac_split_min must be >= 0"); o.jac_split_min = value; return IEM_OK; }
-  if (std::strcmp(name, "pair_inter") == 0) { o.pair_inter = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "split_shift") == 0) { o.split_shift = value != 0; return IEM_OK; }
+  if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {

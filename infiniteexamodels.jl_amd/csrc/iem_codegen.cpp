@@ -107,6 +107,25 @@ void emit_kernel_head(std::ostream &os, const std::string &name, bool tables_in_
      << "(const Args_" << name << " A) {\n";
 }
 
+// The kernel-argument segment is limited (4 KB): big tables move to device memory and the struct carries pointers
+// instead — `A.ip[i]` reads the same either way (uniform scalar loads).
+static bool tables_fit_arguments(size_t nip, size_t ndp, size_t nfa, size_t nia) {
+  return std::max<size_t>(1, nip) + std::max<size_t>(1, ndp) + std::max<size_t>(1, nfa) + std::max<size_t>(1, nia) <= 320;
+}
+
+// The halo-carrier prologue (Options::carrier): a pending asynchronous halo exchange rides on a launch as one EXTRA leading
+// workgroup (column 0 of the grid; `rows`: one per row of a 2-D / 3-D grid, only the first works) that runs it while the
+// others evaluate — they work with the workgroup column `wg` = blockIdx.x - 1 (the objective's walkers: and with their
+// number `nw`).  A.comm is null on every other launch (and on handles that are not sharded).
+static void emit_carrier_prologue(std::ostream &os, const std::string &wg, const std::string &nw = std::string(), bool rows = false) {
+  os << "  const long long cb_ = A.comm != nullptr ? 1 : 0;"
+     << (nw.empty() && !rows ? "   // a pending halo exchange rides on this launch: one extra leading workgroup" : "") << "\n"   // (the dispatchers' text says so)
+     << "  if (cb_ && blockIdx.x == 0) { " << (rows ? "if (blockIdx.y == 0 && blockIdx.z == 0) " : "") << "iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
+     << "  const long long " << wg << " = (long long)blockIdx.x - cb_";
+  if (!nw.empty()) os << ", " << nw << " = (long long)gridDim.x - cb_";
+  os << ";\n";
+}
+
 // pseudo unary ops beyond the blob vocabulary
 enum { U_SGN = 1000 };
 
@@ -1849,11 +1868,7 @@ class KernelBuilder {
 
     // assemble
     std::ostringstream os;
-    size_t nip = std::max<size_t>(1, ipv_.size()), ndp = std::max<size_t>(1, dpv_.size());
-    size_t nfa = std::max<size_t>(1, fav_.size()), nia = std::max<size_t>(1, iav_.size());
-    // the kernel-argument segment is limited (4 KB): big tables move to device memory and the
-    // struct carries pointers instead — `A.ip[i]` reads the same either way (uniform scalar loads)
-    kd.tables_in_memory = (nip + ndp + nfa + nia) > 320;
+    kd.tables_in_memory = !tables_fit_arguments(ipv_.size(), dpv_.size(), fav_.size(), iav_.size());
     if (as_body) {
       os << "__device__ __forceinline__ " << (kind_ == KK_OBJ ? "double " : "void ") << name_ << "_body(const double* __restrict__ X, const double* __restrict__ TH, "
          << "const double* __restrict__ Y, const double* __restrict__ V, double* __restrict__ OUT, const double w_, double* __restrict__ AUX,\n"
@@ -1863,21 +1878,14 @@ class KernelBuilder {
       os << "  (void)X; (void)TH; (void)Y; (void)V; (void)FA; (void)IA; (void)A; (void)AUX; (void)lds_blk; (void)lds4; (void)BY_; (void)BZ_; (void)GX_; (void)GY_; (void)GZ_;\n";
       kd.tables_in_memory = false;
     } else {
-    emit_kernel_head(os, name_, kd.tables_in_memory, nip, ndp, nfa, nia, opt_.min_waves);
+    emit_kernel_head(os, name_, kd.tables_in_memory, ipv_.size(), dpv_.size(), fav_.size(), iav_.size(), opt_.min_waves);
     os << "  const double* __restrict__ X = A.x; const double* __restrict__ TH = A.th; const double* __restrict__ Y = A.y;\n";
     os << "  const double* __restrict__ V = A.v; (void)V;\n";
     os << "  double* __restrict__ OUT = A.out; double* __restrict__ AUX = A.aux; (void)AUX;\n";
     os << "  const double* const* FA = A.fa; const long long* const* IA = A.ia;\n";
     os << "  (void)X; (void)TH; (void)Y; (void)FA; (void)IA;\n";
     kd.carries = carrier();
-    if (carrier()) {
-      // a pending asynchronous halo exchange rides on this launch: one EXTRA leading workgroup (column 0 of the grid;
-      // one per row on 2-D / 3-D grids, only the first works) runs it while the others evaluate — they see workgroup
-      // column blockIdx.x - 1.  A.comm is null on every other launch (and on handles that are not sharded).
-      os << "  const long long cb_ = A.comm != nullptr ? 1 : 0;\n"
-         << "  if (cb_ && blockIdx.x == 0) { if (blockIdx.y == 0 && blockIdx.z == 0) iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
-         << "  const long long BX_ = (long long)blockIdx.x - cb_;\n";
-    }
+    if (carrier()) emit_carrier_prologue(os, "BX_", std::string(), true);
     if (opt_.xcd_remap) {
       // (with a carried halo exchange the evaluating workgroups are columns 1 .. of the launch: workgroups that share
       // b & 7 still share an XCD on a 1-D grid — the labels rotate by one)
@@ -2386,12 +2394,11 @@ static int64_t union_read_bytes(const Builders &bs) {
 
 // Workgroup-id dispatch over a few bodies (<= 4) of one launch: body j owns the workgroups [first_j, first_j + n_j) —
 // except a LEADING RUN of `run` bodies with one common grid, whose workgroups are interleaved so that all of them are
-// resident together (Options::jac_split / pair_inter).  mode 1: workgroup r of the run -> body r % run, tile r / run;
-// mode 2: in runs of 8 consecutive workgroups (hardware deals workgroups round-robin over the 8 XCDs: every XCD then
-// works on every body), the last n % 8 tiles of each body behind them.  `dec`: decode table {first, gx, gy, gz} per body.
-static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t run, int mode, const std::vector<bool> &remap, const std::string &b,
+// resident together (Options::jac_split): workgroup r of the run -> body r % run, tile r / run.  `dec`: decode table
+// {first, gx, gy, gz} per body.
+static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t run, const std::vector<bool> &remap, const std::string &b,
                                 const std::function<std::string(size_t, const std::string &)> &call,
-                                const std::function<std::string(size_t)> &extra, bool shift_first = false) {
+                                const std::function<std::string(size_t)> &extra) {
   size_t j0 = 0;
   if (run >= 2) {
     const size_t e = dec;
@@ -2399,13 +2406,7 @@ static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t
     if (run < nb) src << "if (" << b << " < A.ip[" << (dec + 4 * run) << "]) ";
     src << "{\n    const long long gx = A.ip[" << (e + 1) << "], gy = A.ip[" << (e + 2) << "], gz = A.ip[" << (e + 3) << "];\n"
         << "    const long long n_ = gx * gy * gz, r_ = " << b << " - A.ip[" << e << "];\n    long long j_, lq_;\n";
-    if (mode == 1)
-      src << "    j_ = r_ % " << run << "; lq_ = r_ / " << run << ";\n";
-    else
-      src << "    { const long long f_ = (n_ >> 3) * " << (8 * run) << ";\n"
-          << "      if (r_ < f_) { j_ = (r_ >> 3) % " << run << "; lq_ = (r_ / " << (8 * run) << ") * 8 + (r_ & 7); }\n"
-          << "      else { const long long t_ = n_ & 7, q_ = r_ - f_; j_ = q_ / t_; lq_ = (n_ & ~7LL) + q_ % t_; } }\n";
-    if (shift_first) src << "    if (j_ == 0) { lq_ += n_ >> 1; if (lq_ >= n_) lq_ -= n_; }\n";
+    src << "    j_ = r_ % " << run << "; lq_ = r_ / " << run << ";\n";
     src << "    const long long lb = " << (remap[0] ? "iem_xcd_remap(lq_, n_)" : "lq_") << ";\n";
     for (size_t j = 0; j < run; ++j) {
       src << "    " << (j ? "else " : "");
@@ -2423,6 +2424,388 @@ static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t
         << "    const long long lb = " << (remap[j] ? "iem_xcd_remap(" + b + " - A.ip[" + std::to_string(e) + "], gx * gy * gz)" : b + " - A.ip[" + std::to_string(e) + "]") << ";\n"
         << extra(j) << call(j, "    ") << "  }\n";
   }
+}
+
+static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"};
+static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
+
+// ---- launches of several bodies ------------------------------------------------------------------------------------------
+// One launch per NLPModels call: when the templates of a call live on several support grids (pandemic: t x xi and t;
+// collocation: the node grids), the per-grid bodies become __device__ functions and ONE kernel dispatches on the
+// workgroup id (block-uniform branch, shared LDS, largest grid first so that its workgroups start first).  The objective
+// always takes this form: at most `obj_wgs` workgroups WALK the tiles of every body, so there is one partial (and one
+// ticket) per workgroup.  The fused jac_coord! + hess_coord! launch is the same thing over the bodies of two kinds.
+struct Body {
+  KernelBuilder *kb;
+  KernelDesc *d;
+  std::string out, aux;   // the pointer expressions the body gets as its output and aux buffers
+  bool remap;             // its workgroups walk their tiles XCD-aware (Options::xcd_remap)
+};
+
+// The bodies are emitted ONCE together with the launch's tables; the dispatch code that routes a workgroup id to a body is
+// generated from a Launch at a TABLE BASE (Place), so that the launch's own kernel (base 0) and the one-launch-per-solver-
+// phase kernels (each member kind at its own base behind one workgroup-id dispatcher) run the very same bodies.
+struct Launch {
+  int kind = -1, tile = 0;
+  std::vector<Body> bodies;                    // largest grid first
+  std::vector<size_t> oip, odp, ofa, oia;      // table offsets of each body
+  KernelDesc F;                                // the launch; F.ip / dp / fa / ia = its tables at base 0
+  size_t dec = 0, tbl = 0, sh_tbl = 0, sh_off = 0, nt_slot = 0;
+  bool table = false;                          // workgroup -> body table behind the decode table
+  const KernelBuilder::SharedInfo *si = nullptr;
+  int sh_lds = 0;
+  bool any_remap = false;
+  size_t run = 1;                              // leading bodies whose workgroups are interleaved (Options::jac_split)
+};
+
+// where a Launch's tables start in the tables of the kernel that dispatches to its bodies, and the index of its workgroup ->
+// body table; out / aux (a member kind of a phase kernel): the phase's buffers for the kind, instead of the bodies' own
+struct Place {
+  size_t ip = 0, dp = 0, fa = 0, ia = 0;
+  std::string tbl;
+  const char *out = nullptr, *aux = nullptr;
+};
+
+static bool fits_one_launch(int64_t workgroups) { return workgroups <= 2147483647LL; }
+
+// F of a Launch from its bodies (emitted already: their descs hold their tables).  false: too many workgroups for one launch.
+static bool assemble_launch(Launch &L, const std::string &name, int obj_wgs) {
+  const bool is_obj = L.kind == KK_OBJ;
+  const size_t nb = L.bodies.size();
+  KernelDesc &F = L.F;
+  F.name = name;
+  F.kind = L.kind; F.block = L.tile;
+  F.grid[0] = 0; F.grid[1] = F.grid[2] = 1;
+  std::vector<const KernelBuilder *> bs;
+  for (const Body &b : L.bodies) {
+    const KernelDesc &d = *b.d;
+    L.oip.push_back(F.ip.size()); L.odp.push_back(F.dp.size()); L.ofa.push_back(F.fa.size()); L.oia.push_back(F.ia.size());
+    F.ip.insert(F.ip.end(), d.ip.begin(), d.ip.end());
+    F.dp.insert(F.dp.end(), d.dp.begin(), d.dp.end());
+    F.fa.insert(F.fa.end(), d.fa.begin(), d.fa.end());
+    F.ia.insert(F.ia.end(), d.ia.begin(), d.ia.end());
+    F.grid[0] += d.n_blocks;
+    F.lds_bytes = std::max(F.lds_bytes, d.lds_bytes);
+    F.alg_bytes_written += d.alg_bytes_written;
+    F.x_ranges.insert(F.x_ranges.end(), d.x_ranges.begin(), d.x_ranges.end());
+    F.v_ranges.insert(F.v_ranges.end(), d.v_ranges.begin(), d.v_ranges.end());
+    F.lds_slots = std::max(F.lds_slots, d.lds_slots);
+    L.any_remap = L.any_remap || b.remap;
+    bs.push_back(b.kb);
+  }
+  if (!fits_one_launch(F.grid[0])) return false;
+  F.alg_bytes_read = union_read_bytes(bs);   // what several bodies load (the pair: x7..x9, u1..u3, h) is counted once
+  const int64_t n_tiles = F.grid[0];
+  // workgroup decode table: per body {first workgroup, gx, gy, gz} (launch-size dependent -> arguments)
+  L.dec = F.ip.size();
+  int64_t first = 0;
+  for (const Body &b : L.bodies) {
+    F.ip.push_back(first); F.ip.push_back(b.d->grid[0]); F.ip.push_back(b.d->grid[1]); F.ip.push_back(b.d->grid[2]);
+    first += b.d->n_blocks;
+  }
+  // scatter kinds with shared entries: the last workgroup's tables, and each body's first workgroup of
+  // the call in the numbering the bodies park under (descs order, not the sorted one)
+  for (const Body &b : L.bodies) if (b.kb->shared().on) L.si = &b.kb->shared();
+  if (L.si) {
+    L.sh_tbl = F.ip.size();
+    const std::vector<int64_t> t = KernelBuilder::shared_final_table(*L.si);
+    F.ip.insert(F.ip.end(), t.begin(), t.end());
+    L.sh_off = F.ip.size();
+    for (const Body &b : L.bodies) { F.ip.push_back(b.kb->shared().red_off); L.sh_lds = std::max(L.sh_lds, b.kb->shared_lds_doubles()); }
+    F.lds_bytes = std::max(F.lds_bytes, L.sh_lds * 8);
+  }
+  if (is_obj) {
+    L.nt_slot = F.ip.size();
+    F.ip.push_back(n_tiles);
+    F.grid[0] = std::min<int64_t>(n_tiles, std::max(1, obj_wgs));
+    F.alg_bytes_written = 8 * F.grid[0];
+  }
+  F.n_blocks = F.grid[0];
+  L.tbl = F.ip.size();
+  // many bodies (one per template on a small grid): workgroup -> body table, one scalar load
+  if (!is_obj && nb > 4 && F.grid[0] <= (1 << 18)) {
+    L.table = true;
+    for (size_t j = 0; j < nb; ++j) F.ip.insert(F.ip.end(), (size_t)L.bodies[j].d->n_blocks, (int64_t)j);
+  }
+  // leading bodies that share an interleave class and a grid (the two halves of a split jac_coord!) take turns
+  const KernelDesc &d0 = *L.bodies[0].d;
+  while (!is_obj && L.run < nb && d0.inter >= 0 && L.bodies[L.run].d->inter == d0.inter && L.bodies[L.run].d->n_blocks == d0.n_blocks &&
+         L.bodies[L.run].d->grid[0] == d0.grid[0] && L.bodies[L.run].d->grid[1] == d0.grid[1]) ++L.run;
+  // the workgroup->body table has one entry per workgroup: in device memory always, so that the
+  // argument struct (hence the source) does not depend on the launch size
+  F.tables_in_memory = !tables_fit_arguments(F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size()) || F.ip.size() > L.tbl;
+  return true;
+}
+
+// The code that takes local workgroup id `b` (of the Launch) to its body, tables at `at`.  Objective: `b` = walker index,
+// `nw` = walkers.
+static std::string dispatch_code(const Launch &E, const Place &at, const std::string &b, const std::string &nw, const std::string &ind0) {
+  std::ostringstream c;
+  const bool is_obj = E.kind == KK_OBJ;
+  const size_t nb = E.bodies.size(), ipb = at.ip, dec = E.dec;
+  auto out = [&](size_t j) { return at.out ? std::string(at.out) : E.bodies[j].out; };
+  auto aux = [&](size_t j) { return at.aux ? std::string(at.aux) : E.bodies[j].aux; };
+  auto ipx = [&](size_t i) { return "A.ip[" + std::to_string(ipb + i) + "]"; };
+  auto call = [&](size_t j, const std::string &ind) {
+    std::ostringstream s;
+    s << ind << (is_obj ? "acc += " : "") << E.bodies[j].d->name << "_body(A.x, A.th, A.y, A.v, " << out(j) << ", A.w, " << aux(j) << ", A.ip + " << (ipb + E.oip[j])
+      << ", A.dp + " << (at.dp + E.odp[j]) << ", A.fa + " << (at.fa + E.ofa[j]) << ", A.ia + " << (at.ia + E.oia[j])
+      << ", lds_blk, lds4, lb % gx, (lb / gx) % gy, lb / (gx * gy), gx, gy, gz);\n";
+    return s.str();
+  };
+  if (is_obj) {
+    // every lane adds the terms of its tiles b, b + nw, ... in that order; the body index only grows
+    c << ind0 << "double acc = 0.0;\n" << ind0 << "int j_ = 0;\n"
+      << ind0 << "for (long long t_ = " << b << "; t_ < " << ipx(E.nt_slot) << "; t_ += " << nw << ") {\n";
+    if (nb > 1)
+      c << ind0 << "  while (j_ + 1 < " << nb << " && t_ >= A.ip[" << (ipb + dec) << " + 4 * (j_ + 1)]) ++j_;\n";
+    c << ind0 << "  const long long gx = A.ip[" << (ipb + dec) << " + 4 * j_ + 1], gy = A.ip[" << (ipb + dec) << " + 4 * j_ + 2], gz = A.ip[" << (ipb + dec) << " + 4 * j_ + 3];\n"
+      << ind0 << "  const long long lb = t_ - A.ip[" << (ipb + dec) << " + 4 * j_];\n";
+    if (nb == 1) c << call(0, ind0 + "  ");
+    else {
+      c << ind0 << "  switch (j_) {\n";
+      for (size_t j = 0; j < nb; ++j) c << ind0 << "    case " << j << ":\n" << call(j, ind0 + "      ") << ind0 << "      break;\n";
+      c << ind0 << "  }\n";
+    }
+    c << ind0 << "}\n"
+      << ind0 << "iem_block_partial(acc, " << out(0) << ", " << b << ", lds4, " << nw << ", " << aux(0) << ");\n";
+    return c.str();
+  }
+  if (E.si) c << ind0 << "double* __restrict__ OUT = " << out(0) << "; double* __restrict__ AUX = " << aux(0) << ";\n"   // (the epilogue's names)
+              << ind0 << "long long wg_ = 0;\n";
+  if (nb > 4) {
+    // many bodies: workgroup -> body table, or a binary search of the table of first workgroups, then a jump table — a
+    // chain of 80 compares costs microseconds
+    if (E.table) c << ind0 << "const int lo_ = (int)A.ip[" << at.tbl << " + " << b << "];\n";
+    else c << ind0 << "int lo_ = 0, hi_ = " << nb << ";\n"
+           << ind0 << "while (hi_ - lo_ > 1) { const int mid_ = (lo_ + hi_) >> 1; if (" << b << " >= A.ip[" << (ipb + dec) << " + 4 * mid_]) lo_ = mid_; else hi_ = mid_; }\n";
+    c << ind0 << "const long long gx = A.ip[" << (ipb + dec) << " + 4 * lo_ + 1], gy = A.ip[" << (ipb + dec) << " + 4 * lo_ + 2], gz = A.ip[" << (ipb + dec) << " + 4 * lo_ + 3];\n"
+      << ind0 << "const long long lb = " << (E.any_remap ? "iem_xcd_remap(" + b + " - A.ip[" + std::to_string(ipb + dec) + " + 4 * lo_], gx * gy * gz)"
+                                                          : b + " - A.ip[" + std::to_string(ipb + dec) + " + 4 * lo_]") << ";\n";
+    if (E.si) c << ind0 << "wg_ = A.ip[" << (ipb + E.sh_off) << " + lo_] + lb;\n";
+    c << ind0 << "switch (lo_) {\n";
+    for (size_t j = 0; j < nb; ++j) c << ind0 << "  case " << j << ":\n" << call(j, ind0 + "    ") << ind0 << "    break;\n";
+    c << ind0 << "}\n";
+  } else {
+    std::vector<bool> remap;
+    for (const Body &bd : E.bodies) remap.push_back(bd.remap);
+    emit_dispatch_chain(c, nb, ipb + dec, E.si ? 1 : E.run, remap, b, call,
+                        [&](size_t j) { return E.si ? "    wg_ = A.ip[" + std::to_string(ipb + E.sh_off + j) + "] + lb;\n" : std::string(); });
+  }
+  if (E.si) c << KernelBuilder::shared_epilogue(*E.si, "A.ip + " + std::to_string(ipb + E.sh_tbl), "wg_", "lds_blk", E.sh_lds);
+  return c.str();
+}
+
+// what the tail of generate() works on
+struct Emitter {
+  std::ostringstream &src;
+  std::vector<KernelDesc> &descs;
+  const std::vector<std::unique_ptr<KernelBuilder>> &builders;
+  const std::vector<Options> &kopts;   // the options each builder was made with (kind_options)
+  const Options &opt;
+  Program &P;
+  // Kernels of more than one workgroup size in one program (the large-grid shape of jac_coord! / hess_coord!): every kernel
+  // then sits in the namespace iem_t<size> that holds the tile-dependent device primitives compiled for its size, with
+  // IEM_TILE redefined in front of it (csrc/iem_api.cpp: full_source).  A program of one size is emitted as it always was.
+  bool mixed = false;
+  // a handle's second code object (the tuner's large store batch) carries a tag in its kernel names, so that a
+  // profile of a run that used both tells them apart
+  std::string name_tag;
+  std::map<int, Launch> emitted;   // the launches of the kinds, for the phase kernels
+
+  void ns_begin(int tile) {
+    if (mixed) src << "#undef IEM_TILE\n#define IEM_TILE " << tile << "\nnamespace iem_t" << tile << " {\n";
+  }
+  void ns_end(int tile) {
+    if (mixed) src << "}  // namespace iem_t" << tile << "\n#undef IEM_TILE\n#define IEM_TILE " << opt.block << "\n\n";
+  }
+  bool phases_on() const { return opt.phase_kernels && !opt.no_fuse && opt.fuse_groups && !opt.hess_merge; }
+};
+
+// The head of a dispatcher kernel: argument struct and signature, the LDS its bodies share (`lds4`: the objective's wave
+// sums) and the workgroup id `wg` its dispatch code works with (objective: and the walker count `nw`) — behind the halo
+// carrier's workgroup, when the launch can bring one (F.carries).
+static void emit_launch_prologue(Emitter &E, const KernelDesc &F, bool lds4, const std::string &wg, const std::string &nw = std::string()) {
+  emit_kernel_head(E.src, F.name, F.tables_in_memory, F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), E.opt.min_waves);
+  if (F.lds_bytes > 0) E.src << "  __shared__ double lds_blk[" << (F.lds_bytes / 8) << "];\n";
+  else E.src << "  double* lds_blk = nullptr;\n";
+  if (lds4) E.src << "  __shared__ double lds4[IEM_TILE / 64 + 1];\n";
+  else E.src << "  double* lds4 = nullptr;\n";
+  if (F.carries) emit_carrier_prologue(E.src, wg, nw);
+  else if (nw.empty()) E.src << "  const long long " << wg << " = blockIdx.x;\n";
+  else E.src << "  const long long " << wg << " = (long long)blockIdx.x, " << nw << " = (long long)gridDim.x;\n";
+}
+
+// bodies, tables and kernel of one Launch.  false (after the bodies): more workgroups than one launch can have, no kernel.
+static bool emit_launch(Emitter &E, Launch &L, const std::string &name) {
+  const bool is_obj = L.kind == KK_OBJ;
+  E.ns_begin(L.tile);
+  for (Body &b : L.bodies) E.src << b.kb->emit(*b.d, true);
+  const bool ok = assemble_launch(L, name, E.opt.obj_wgs);
+  if (ok) {
+    // (the scatter kinds' outputs are not complete before their follow-ups: nothing to overlap an exchange with)
+    L.F.carries = E.opt.carrier && !is_scatter(L.kind);
+    emit_launch_prologue(E, L.F, is_obj, is_obj ? "bx_" : "b", is_obj ? "gx_" : "");
+    Place at;
+    at.tbl = std::to_string(L.tbl);
+    E.src << dispatch_code(L, at, is_obj ? "bx_" : "b", is_obj ? "gx_" : "", "  ") << "}\n\n";
+    E.P.kernels.push_back(L.F);
+  }
+  E.ns_end(L.tile);
+  return ok;
+}
+
+// ---- per-kind launches: iem_<kind>_all, or the kind's kernels one by one
+static void emit_kinds(Emitter &E) {
+  const Options &opt = E.opt;
+  for (int kind = 0; kind < KK_COUNT; ++kind) {
+    std::vector<size_t> ks;
+    for (size_t k = 0; k < E.descs.size(); ++k) if (E.descs[k].kind == kind) ks.push_back(k);
+    if (ks.empty()) continue;
+    const int ktile = E.descs[ks[0]].block;   // one workgroup size per kind (kind_options)
+    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS);
+    const bool unfused = !opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2);   // fuse_groups = 2: experiments (one launch of per-template bodies)
+    if (kind != KK_OBJ && (unfused || (ks.size() == 1 && !in_a_phase))) {
+      for (size_t k : ks) { E.ns_begin(ktile); E.src << E.builders[k]->emit(E.descs[k]); E.ns_end(ktile); E.P.kernels.push_back(E.descs[k]); }
+      continue;
+    }
+    std::stable_sort(ks.begin(), ks.end(), [&](size_t a, size_t b) { return E.descs[a].n_blocks > E.descs[b].n_blocks; });
+    Launch &L = E.emitted[kind];
+    L.kind = kind; L.tile = ktile;
+    for (size_t k : ks) L.bodies.push_back(Body{E.builders[k].get(), &E.descs[k], "A.out", "A.aux", E.kopts[k].xcd_remap != 0});
+    if (!emit_launch(E, L, std::string("iem_") + kname[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
+    if (kind == KK_OBJ) E.P.n_partials = L.F.grid[0];
+  }
+}
+
+// ---- one launch per solver phase (KK_TRIAL: obj + cons! at a trial point; KK_ACCEPTED: grad! + jac_coord! + hess_coord!
+// at an accepted point — the call pattern of ext/InfiniteExaModelsMadNLP.jl:49-50,64 and ext/InfiniteExaModelsIpopt.jl:48-49
+// of the reference).  Member kinds keep their workgroup ranges (largest member first), each decoded by its own dispatch
+// code at its own table base; bytes identical to the separate calls (same bodies).  Pointers: trial  out = c, aux = the
+// objective scalar, p2 = the objective's partials;  accepted  out = jac values, aux = hess values, p2 = g, p3 = grad!'s
+// reduction buffer.  Follow-ups of grad! (axis sums, plan-driven gather, runtime memsets) stay with the runtime.
+static void emit_phases(Emitter &E) {
+  if (!E.phases_on()) return;
+  std::ostringstream &src = E.src;
+  struct Member { int kind; const char *out, *aux; };
+  struct Phase { int id; const char *name; std::vector<Member> mem; };
+  const Phase phases[] = {
+    {KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
+    {KK_ACCEPTED, "iem_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}}},
+    // all five evaluations of one point in ONE launch (iem_eval_all: the solver's first trial point is usually accepted —
+    // obj, cons!, grad!, jac_coord!, hess_coord! at the same x): p4 = c, p5 = the objective's partials, p6 = its scalar
+    {KK_ALL, "iem_point_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_CONS, "A.p4", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}, {KK_OBJ, "A.p5", "A.p6"}}},
+  };
+  for (const Phase &ph : phases) {
+    bool ok = true;
+    int tile = 0;
+    std::vector<Member> present;   // (a linear program has no hess_coord! kernel: the accepted point is grad! + jac_coord!)
+    for (const Member &mb : ph.mem) {
+      auto it = E.emitted.find(mb.kind);
+      if (it == E.emitted.end()) { if (ph.id == KK_TRIAL || mb.kind == KK_OBJ || mb.kind == KK_CONS) ok = false; continue; }
+      if (!tile) tile = it->second.tile;
+      ok = ok && it->second.tile == tile;   // (kinds of different workgroup sizes cannot share a launch)
+      present.push_back(mb);
+    }
+    if (!ok || present.size() < 2 || (ph.id == KK_ALL && present.size() < 3)) continue;
+    KernelDesc F;
+    F.name = std::string(ph.name) + E.name_tag;
+    F.kind = ph.id; F.block = tile;
+    F.grid[0] = 0; F.grid[1] = F.grid[2] = 1;
+    std::vector<Place> base;
+    std::vector<int64_t> first;
+    std::vector<const KernelBuilder *> bs;
+    bool has_obj = false, has_si = false;
+    for (const Member &mb : present) {
+      const Launch &L = E.emitted[mb.kind];
+      // the member's tables WITHOUT its per-workgroup table (the only part whose length depends on the launch size:
+      // those go behind everything else, so that every index the source names is size-independent)
+      base.push_back(Place{F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), std::string(), mb.out, mb.aux});
+      first.push_back(F.grid[0]);
+      F.ip.insert(F.ip.end(), L.F.ip.begin(), L.F.ip.begin() + (long)L.tbl);
+      F.dp.insert(F.dp.end(), L.F.dp.begin(), L.F.dp.end());
+      F.fa.insert(F.fa.end(), L.F.fa.begin(), L.F.fa.end());
+      F.ia.insert(F.ia.end(), L.F.ia.begin(), L.F.ia.end());
+      F.grid[0] += L.F.grid[0];
+      F.lds_bytes = std::max(F.lds_bytes, L.F.lds_bytes);
+      F.alg_bytes_written += L.F.alg_bytes_written;
+      F.x_ranges.insert(F.x_ranges.end(), L.F.x_ranges.begin(), L.F.x_ranges.end());
+      F.lds_slots = std::max(F.lds_slots, L.F.lds_slots);
+      for (const Body &b : L.bodies) bs.push_back(b.kb);
+      has_obj = has_obj || mb.kind == KK_OBJ;
+      has_si = has_si || L.si != nullptr;
+    }
+    if (!fits_one_launch(F.grid[0])) continue;
+    F.n_blocks = F.grid[0];
+    F.alg_bytes_read = union_read_bytes(bs);
+    const size_t mdec = F.ip.size();            // per member {first workgroup, workgroups, start of its workgroup -> body table}: launch-size dependent -> arguments
+    F.ip.resize(mdec + 3 * base.size());
+    for (size_t i = 0; i < base.size(); ++i) {
+      const Launch &L = E.emitted[present[i].kind];
+      F.ip[mdec + 3 * i] = first[i]; F.ip[mdec + 3 * i + 1] = L.F.grid[0]; F.ip[mdec + 3 * i + 2] = (int64_t)F.ip.size();
+      F.ip.insert(F.ip.end(), L.F.ip.begin() + (long)L.tbl, L.F.ip.end());
+      base[i].tbl = "A.ip[" + std::to_string(mdec + 3 * i + 2) + "]";
+    }
+    F.tables_in_memory = true;                  // (member tables may hold per-workgroup entries; one form for every size)
+    F.carries = E.opt.carrier && !has_si;
+    E.ns_begin(tile);
+    emit_launch_prologue(E, F, has_obj, "pb_");
+    for (size_t i = 0; i < present.size(); ++i) {
+      src << "  " << (i ? "else " : "");
+      if (i + 1 < present.size()) src << "if (pb_ < A.ip[" << (mdec + 3 * (i + 1)) << "]) ";
+      src << "{\n    const long long b = pb_ - A.ip[" << (mdec + 3 * i) << "];\n"
+          << dispatch_code(E.emitted[present[i].kind], base[i], "b", "A.ip[" + std::to_string(mdec + 3 * i + 1) + "]", "    ")
+          << "  }\n";
+    }
+    src << "}\n\n";
+    E.ns_end(tile);
+    E.P.kernels.push_back(F);
+  }
+}
+
+// jac_coord! + hess_coord! in ONE launch (KK_PAIR; iem_jac_hess_coord).  The two calls are independent given x (and y):
+// behind one workgroup-id dispatcher their bodies share a launch — one ramp and one drain instead of two, and on a grid
+// of about one workgroup per CU (a 1/8 shard of the headline problem: 252 + 252 workgroups) both kinds are resident
+// together, 16 waves per CU instead of 8.  `out` = Jacobian values, `aux` = Hessian values; every body is generated
+// again by a builder of its own (a builder emits once), with the options its stand-alone twin got.
+// `whole_of` / `second_half`: jac_coord!'s two halves (Options::jac_split) are ONE body again here — measured, the pair is
+// fastest as jac_coord!'s workgroups followed by hess_coord!'s: 0.155 ms against 0.159 - 0.165 for any interleaving at 1e6
+// quadrotor supports, profiles/r04_ab_jac_split.txt.
+static void emit_pair(Emitter &E, const Model &m, const std::map<size_t, std::pair<const Group *, std::string>> &whole_of, const std::set<size_t> &second_half) {
+  const Options &opt = E.opt;
+  if (!opt.pair_kernel || opt.no_fuse) return;
+  std::vector<size_t> ks;
+  bool have[2] = {false, false};
+  for (size_t k = 0; k < E.descs.size(); ++k)
+    if (E.descs[k].kind == KK_JAC || E.descs[k].kind == KK_HESS) { ks.push_back(k); have[E.descs[k].kind == KK_HESS] = true; }
+  int ptile = 0;
+  bool one_tile = true;
+  for (size_t k : ks) { if (!ptile) ptile = E.descs[k].block; one_tile = one_tile && E.descs[k].block == ptile; }
+  if (!have[0] || !have[1] || !one_tile) return;   // (kinds of different workgroup sizes cannot share a launch: the two calls stay)
+  std::vector<std::unique_ptr<KernelBuilder>> pb;
+  std::deque<KernelDesc> pd;   // (the bodies keep pointers)
+  Launch L;
+  L.kind = KK_PAIR; L.tile = ptile;
+  int64_t nnz_again = 0;
+  std::vector<HessClass> classes_again;
+  for (size_t k : ks) {   // in the order of the first pass: the merged Hessian layout's offsets are running counters
+    if (second_half.count(k)) continue;
+    const KernelDesc &d = E.descs[k];
+    const auto whole = whole_of.find(k);
+    const bool rejoin = whole != whole_of.end();
+    pd.emplace_back();
+    KernelDesc &kd = pd.back();
+    kd.name = (rejoin ? whole->second.second : d.name) + "_p"; kd.kind = d.kind; kd.block = d.block; kd.lds_slots = d.lds_slots; kd.inter = rejoin ? -1 : d.inter;
+    for (int a = 0; a < 3; ++a) kd.grid[a] = d.grid[a];
+    kd.n_blocks = d.n_blocks;
+    auto kb = std::make_unique<KernelBuilder>(m, rejoin ? *whole->second.first : E.builders[k]->group(), kd.kind, E.kopts[k], kd.name);
+    if (!kb->build(nullptr)) throw std::runtime_error("internal: pair body without outputs");
+    if (kd.kind == KK_HESS && opt.hess_merge) kb->merge_hess(nnz_again, classes_again);
+    L.bodies.push_back(Body{kb.get(), &kd, kd.kind == KK_JAC ? "A.out" : "A.aux", "nullptr", E.kopts[k].xcd_remap != 0});
+    pb.push_back(std::move(kb));
+  }
+  std::stable_sort(L.bodies.begin(), L.bodies.end(), [](const Body &a, const Body &b) { return a.d->n_blocks > b.d->n_blocks; });
+  emit_launch(E, L, std::string("iem_pair_all") + E.name_tag);   // (too large for one launch: the two calls stay separate launches)
 }
 
 Program generate(const Model &m, const Options &opt_in) {
@@ -2462,7 +2845,6 @@ Program generate(const Model &m, const Options &opt_in) {
   }
   std::ostringstream src;
   src << "// generated by libiem_hip (iem_codegen.cpp) — do not edit\n";
-  static const char *kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"};
 
   // gradient slot classification needs a global view of every objective slot's index range
   struct GSlot { int kind; int kernel; int out; int slot; int64_t lo, hi; bool injective, uniform0; AffQ aff; bool pure; int64_t count = 0;
@@ -2475,7 +2857,6 @@ Program generate(const Model &m, const Options &opt_in) {
   std::map<size_t, std::pair<const Group *, std::string>> whole_of;   // desc index of a split body's FIRST half -> (the whole grid, its kernel name)
   std::set<size_t> second_half;
 
-  auto is_scatter = [](int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; };
   // a handle's second code object (the tuner's large store batch) carries a tag in its kernel names, so that a
   // profile of a run that used both tells them apart
   const std::string name_tag = opt.name_tag > 0 ? "_b" + std::to_string(opt.name_tag) : std::string();
@@ -2492,12 +2873,10 @@ Program generate(const Model &m, const Options &opt_in) {
       if (!kb->build(nullptr)) continue;
       if (kind == KK_JAC && opt.jac_split > 0 && !opt.no_fuse && ko.store_mode == 2 && g.grid_id > 0) {
         // a large grid: the templates whose partials are item data get a body of their own (Options::jac_split)
-        KernelDesc probe;
-        launch_grid(g, kb->qstep(), probe);
         const std::set<int> data = kb->data_only_templates();
         int n_data = 0, n_comp = 0;   // lane templates on either side (scalars follow their class, but never make a body)
         for (int ti : g.tpls) if (kb->relevant(m.tpl[ti])) (data.count(ti) ? n_data : n_comp)++;
-        if (probe.n_blocks > opt.jac_split_min && n_data > 0 && n_comp > 0) {
+        if (g.ext[0] * g.ext[1] * g.ext[2] > 0 && n_data > 0 && n_comp > 0) {   // (every lane-fused grid: the source stays size-independent)
           for (int half = 0; half < 2; ++half) {
             sub_groups.push_back(g);
             Group &sg = sub_groups.back();
@@ -2852,452 +3231,13 @@ Program generate(const Model &m, const Options &opt_in) {
     }
     P.aux_doubles[kind] = base;
   }
-  // One launch per NLPModels call: when the templates of a call live on several support grids
-  // (pandemic: t x xi and t; collocation: the node grids), the per-grid bodies become
-  // __device__ functions and ONE kernel dispatches on the workgroup id (block-uniform branch,
-  // shared LDS, largest grid first so that its workgroups start first).
-  // The objective always takes this form, with a wrapper of its own: at most `obj_wgs` workgroups
-  // WALK the tiles of every body, so there is one partial (and one ticket) per workgroup.
-  // Kernels of more than one workgroup size in one program (the large-grid shape of jac_coord! / hess_coord!): every kernel
-  // then sits in the namespace iem_t<size> that holds the tile-dependent device primitives compiled for its size, with
-  // IEM_TILE redefined in front of it (csrc/iem_api.cpp: full_source).  A program of one size is emitted as it always was.
-  bool mixed = false;
-  for (const KernelDesc &d : descs) mixed = mixed || d.block != opt.block;
-  auto ns_begin = [&](int tile) {
-    if (mixed) src << "#undef IEM_TILE\n#define IEM_TILE " << tile << "\nnamespace iem_t" << tile << " {\n";
-  };
-  auto ns_end = [&](int tile) {
-    if (mixed) src << "}  // namespace iem_t" << tile << "\n#undef IEM_TILE\n#define IEM_TILE " << opt.block << "\n\n";
-  };
-  // ---- per-kind launches ------------------------------------------------------------------------------------------------
-  // A kind's bodies are emitted ONCE (__device__ functions) together with its tables; the dispatch code that routes a
-  // workgroup id to a body is generated from a KindEmit at a TABLE BASE, so that the kind's own kernel (base 0) and the
-  // one-launch-per-solver-phase kernels below (iem_eval_trial: obj + cons!; iem_eval_accepted: grad! + jac_coord! +
-  // hess_coord! — each member kind at its own base behind one workgroup-id dispatcher) run the very same bodies.
-  struct KindEmit {
-    int kind = -1, tile = 0;
-    std::vector<size_t> ks;                      // descs of the kind, largest grid first
-    std::vector<size_t> oip, odp, ofa, oia;      // table offsets of each body
-    KernelDesc F;                                // the kind's own launch; F.ip / dp / fa / ia = its tables at base 0
-    size_t dec = 0, tbl = 0, sh_tbl = 0, sh_off = 0, nt_slot = 0;
-    bool table = false;                          // workgroup -> body table behind the decode table
-    const KernelBuilder::SharedInfo *si = nullptr;
-    int sh_lds = 0;
-    bool any_remap = false;
-    std::vector<bool> remap;
-    size_t run = 1;                              // leading bodies whose workgroups are interleaved (Options::jac_split)
-  };
-  std::map<int, KindEmit> emitted;
-  const bool phases_on = opt.phase_kernels && !opt.no_fuse && opt.fuse_groups && !opt.hess_merge;
-  auto in_a_phase = [&](int kind) { return phases_on && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS); };
-  // the code that takes local workgroup id `b` (of the kind's launch) to its body, tables at the given bases; OUT / AUX: the
-  // pointer expressions the bodies get as their output and aux buffers.  Objective: `b` = walker index, `nw` = walkers.
-  auto dispatch_code = [&](const KindEmit &E, size_t ipb, size_t dpb, size_t fab, size_t iab, const std::string &tblx, const std::string &b, const std::string &nw,
-                           const std::string &OUT, const std::string &AUX, const std::string &ind0) {
-    std::ostringstream c;
-    const bool is_obj = E.kind == KK_OBJ;
-    const auto &ks = E.ks;
-    auto ipx = [&](size_t i) { return "A.ip[" + std::to_string(ipb + i) + "]"; };
-    auto call = [&](size_t j, const std::string &ind) {
-      std::ostringstream s;
-      s << ind << (is_obj ? "acc += " : "") << descs[ks[j]].name << "_body(A.x, A.th, A.y, A.v, " << OUT << ", A.w, " << AUX << ", A.ip + " << (ipb + E.oip[j])
-        << ", A.dp + " << (dpb + E.odp[j]) << ", A.fa + " << (fab + E.ofa[j]) << ", A.ia + " << (iab + E.oia[j])
-        << ", lds_blk, lds4, lb % gx, (lb / gx) % gy, lb / (gx * gy), gx, gy, gz);\n";
-      return s.str();
-    };
-    const size_t dec = E.dec;
-    if (is_obj) {
-      // every lane adds the terms of its tiles b, b + nw, ... in that order; the body index only grows
-      c << ind0 << "double acc = 0.0;\n" << ind0 << "int j_ = 0;\n"
-        << ind0 << "for (long long t_ = " << b << "; t_ < " << ipx(E.nt_slot) << "; t_ += " << nw << ") {\n";
-      if (ks.size() > 1)
-        c << ind0 << "  while (j_ + 1 < " << ks.size() << " && t_ >= A.ip[" << (ipb + dec) << " + 4 * (j_ + 1)]) ++j_;\n";
-      c << ind0 << "  const long long gx = A.ip[" << (ipb + dec) << " + 4 * j_ + 1], gy = A.ip[" << (ipb + dec) << " + 4 * j_ + 2], gz = A.ip[" << (ipb + dec) << " + 4 * j_ + 3];\n"
-        << ind0 << "  const long long lb = t_ - A.ip[" << (ipb + dec) << " + 4 * j_];\n";
-      if (ks.size() == 1 && opt.obj_unroll > 1) {
-        // one body: two tiles per trip (t_ and t_ + nw) so that the second tile's loads are in flight while the first is
-        // summed; a tile index past the end decodes to a workgroup column outside the grid, where every lane's guard is
-        // false and the body adds 0
-        c << call(0, ind0 + "  ")
-          << ind0 << "  { const long long b2 = t_ + " << nw << "; const bool in2 = b2 < " << ipx(E.nt_slot) << ";\n"
-          << ind0 << "    const long long lb2 = b2 - A.ip[" << (ipb + dec) << " + 4 * j_];\n"
-          << ind0 << "    acc += " << descs[ks[0]].name << "_body(A.x, A.th, A.y, A.v, " << OUT << ", A.w, " << AUX << ", A.ip + " << (ipb + E.oip[0]) << ", A.dp + " << (dpb + E.odp[0])
-          << ", A.fa + " << (fab + E.ofa[0]) << ", A.ia + " << (iab + E.oia[0]) << ", lds_blk, lds4, in2 ? lb2 % gx : gx, in2 ? (lb2 / gx) % gy : 0, in2 ? lb2 / (gx * gy) : 0, gx, gy, gz);\n"
-          << ind0 << "    t_ += " << nw << "; }\n";
-      } else if (ks.size() == 1) c << call(0, ind0 + "  ");
-      else {
-        c << ind0 << "  switch (j_) {\n";
-        for (size_t j = 0; j < ks.size(); ++j) c << ind0 << "    case " << j << ":\n" << call(j, ind0 + "      ") << ind0 << "      break;\n";
-        c << ind0 << "  }\n";
-      }
-      c << ind0 << "}\n"
-        << ind0 << "iem_block_partial(acc, " << OUT << ", " << b << ", lds4, " << nw << ", " << AUX << ");\n";
-      return c.str();
-    }
-    if (E.si) c << ind0 << "long long wg_ = 0;\n";
-    if (ks.size() > 4) {
-      // many bodies (one per template on a small grid): workgroup -> body table (one scalar load), or a binary search of
-      // the table of first workgroups, then a jump table — a chain of 80 compares costs microseconds
-      if (E.table) c << ind0 << "const int lo_ = (int)A.ip[" << tblx << " + " << b << "];\n";
-      else c << ind0 << "int lo_ = 0, hi_ = " << ks.size() << ";\n"
-             << ind0 << "while (hi_ - lo_ > 1) { const int mid_ = (lo_ + hi_) >> 1; if (" << b << " >= A.ip[" << (ipb + dec) << " + 4 * mid_]) lo_ = mid_; else hi_ = mid_; }\n";
-      c << ind0 << "const long long gx = A.ip[" << (ipb + dec) << " + 4 * lo_ + 1], gy = A.ip[" << (ipb + dec) << " + 4 * lo_ + 2], gz = A.ip[" << (ipb + dec) << " + 4 * lo_ + 3];\n"
-        << ind0 << "const long long lb = " << (E.any_remap ? "iem_xcd_remap(" + b + " - A.ip[" + std::to_string(ipb + dec) + " + 4 * lo_], gx * gy * gz)"
-                                                            : b + " - A.ip[" + std::to_string(ipb + dec) + " + 4 * lo_]") << ";\n";
-      if (E.si) c << ind0 << "wg_ = A.ip[" << (ipb + E.sh_off) << " + lo_] + lb;\n";
-      c << ind0 << "switch (lo_) {\n";
-      for (size_t j = 0; j < ks.size(); ++j) c << ind0 << "  case " << j << ":\n" << call(j, ind0 + "    ") << ind0 << "    break;\n";
-      c << ind0 << "}\n";
-    } else {
-      std::ostringstream ch;
-      emit_dispatch_chain(ch, ks.size(), ipb + dec, E.si ? 1 : E.run, opt.jac_split == 1 ? 1 : 2, E.remap, b, call,
-                          [&](size_t j) { return E.si ? "    wg_ = A.ip[" + std::to_string(ipb + E.sh_off + j) + "] + lb;\n" : std::string(); }, opt.split_shift != 0);
-      c << ch.str();
-    }
-    if (E.si) c << KernelBuilder::shared_epilogue(*E.si, "A.ip + " + std::to_string(ipb + E.sh_tbl), "wg_", "lds_blk", E.sh_lds);
-    return c.str();
-  };
-  auto args_struct = [&](const KernelDesc &F) {
-    emit_kernel_head(src, F.name, F.tables_in_memory, F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), opt.min_waves);
-  };
-  for (int kind = 0; kind < KK_COUNT; ++kind) {
-    std::vector<size_t> ks;
-    for (size_t k = 0; k < descs.size(); ++k) if (descs[k].kind == kind) ks.push_back(k);
-    if (ks.empty()) continue;
-    const bool is_obj = kind == KK_OBJ;
-    const int ktile = descs[ks[0]].block;   // one workgroup size per kind (kind_options)
-    if (!is_obj && !in_a_phase(kind) && (ks.size() == 1 || !opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2))) {   // fuse_groups = 2: experiments (one launch of per-template bodies)
-      for (size_t k : ks) { ns_begin(ktile); src << builders[k]->emit(descs[k]); ns_end(ktile); P.kernels.push_back(descs[k]); }
-      continue;
-    }
-    if (!is_obj && (!opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2))) {
-      for (size_t k : ks) { ns_begin(ktile); src << builders[k]->emit(descs[k]); ns_end(ktile); P.kernels.push_back(descs[k]); }
-      continue;
-    }
-    ns_begin(ktile);
-    std::stable_sort(ks.begin(), ks.end(), [&](size_t a, size_t b) { return descs[a].n_blocks > descs[b].n_blocks; });
-    KindEmit &E = emitted[kind];
-    E.kind = kind; E.tile = ktile; E.ks = ks;
-    KernelDesc &F = E.F;
-    F.name = std::string("iem_") + kname[kind] + "_all" + name_tag;
-    F.kind = kind; F.block = ktile;
-    F.grid[0] = 0; F.grid[1] = F.grid[2] = 1;
-    for (size_t k : ks) {
-      src << builders[k]->emit(descs[k], true);
-      const KernelDesc &d = descs[k];
-      E.oip.push_back(F.ip.size()); E.odp.push_back(F.dp.size()); E.ofa.push_back(F.fa.size()); E.oia.push_back(F.ia.size());
-      F.ip.insert(F.ip.end(), d.ip.begin(), d.ip.end());
-      F.dp.insert(F.dp.end(), d.dp.begin(), d.dp.end());
-      F.fa.insert(F.fa.end(), d.fa.begin(), d.fa.end());
-      F.ia.insert(F.ia.end(), d.ia.begin(), d.ia.end());
-      F.grid[0] += d.n_blocks;
-      F.lds_bytes = std::max(F.lds_bytes, d.lds_bytes);
-      F.alg_bytes_read += d.alg_bytes_read; F.alg_bytes_written += d.alg_bytes_written;
-      F.x_ranges.insert(F.x_ranges.end(), d.x_ranges.begin(), d.x_ranges.end());
-      F.v_ranges.insert(F.v_ranges.end(), d.v_ranges.begin(), d.v_ranges.end());
-      F.lds_slots = std::max(F.lds_slots, d.lds_slots);
-      E.remap.push_back(kopts[k].xcd_remap != 0);
-      E.any_remap = E.any_remap || kopts[k].xcd_remap;
-    }
-    if (F.grid[0] > 2147483647LL) throw std::runtime_error("support grids too large for one launch");
-    {
-      std::vector<const KernelBuilder *> bs;
-      for (size_t k : ks) bs.push_back(builders[k].get());
-      F.alg_bytes_read = union_read_bytes(bs);
-    }
-    const int64_t n_tiles = F.grid[0];
-    // workgroup decode table: per body {first workgroup, gx, gy, gz} (launch-size dependent -> arguments)
-    E.dec = F.ip.size();
-    int64_t first = 0;
-    for (size_t k : ks) {
-      const KernelDesc &d = descs[k];
-      F.ip.push_back(first); F.ip.push_back(d.grid[0]); F.ip.push_back(d.grid[1]); F.ip.push_back(d.grid[2]);
-      first += d.n_blocks;
-    }
-    // scatter kinds with shared entries: the last workgroup's tables, and each body's first workgroup of
-    // the call in the numbering the bodies park under (descs order, not the sorted one)
-    for (size_t k : ks) if (builders[k]->shared().on) E.si = &builders[k]->shared();
-    if (E.si) {
-      E.sh_tbl = F.ip.size();
-      const std::vector<int64_t> t = KernelBuilder::shared_final_table(*E.si);
-      F.ip.insert(F.ip.end(), t.begin(), t.end());
-      E.sh_off = F.ip.size();
-      for (size_t k : ks) { F.ip.push_back(builders[k]->shared().red_off); E.sh_lds = std::max(E.sh_lds, builders[k]->shared_lds_doubles()); }
-      F.lds_bytes = std::max(F.lds_bytes, E.sh_lds * 8);
-    }
-    if (is_obj) {
-      E.nt_slot = F.ip.size();
-      F.ip.push_back(n_tiles);
-      F.grid[0] = std::min<int64_t>(n_tiles, std::max(1, opt.obj_wgs));
-      F.alg_bytes_written = 8 * F.grid[0];
-      P.n_partials = F.grid[0];
-    }
-    F.n_blocks = F.grid[0];
-    E.tbl = F.ip.size();
-    if (!is_obj && ks.size() > 4 && F.grid[0] <= (1 << 18)) {
-      E.table = true;
-      for (size_t j = 0; j < ks.size(); ++j) F.ip.insert(F.ip.end(), (size_t)descs[ks[j]].n_blocks, (int64_t)j);
-    }
-    // leading bodies that share an interleave class and a grid (the two halves of a split jac_coord!) take turns
-    while (!is_obj && E.run < ks.size() && descs[ks[0]].inter >= 0 && descs[ks[E.run]].inter == descs[ks[0]].inter && descs[ks[E.run]].n_blocks == descs[ks[0]].n_blocks &&
-           descs[ks[E.run]].grid[0] == descs[ks[0]].grid[0] && descs[ks[E.run]].grid[1] == descs[ks[0]].grid[1]) ++E.run;
-    {
-      const size_t nip = std::max<size_t>(1, F.ip.size()), ndp = std::max<size_t>(1, F.dp.size());
-      const size_t nfa = std::max<size_t>(1, F.fa.size()), nia = std::max<size_t>(1, F.ia.size());
-      // the workgroup->body table has one entry per workgroup: in device memory always, so that the
-      // argument struct (hence the source) does not depend on the launch size
-      F.tables_in_memory = (nip + ndp + nfa + nia) > 320 || F.ip.size() > E.tbl;
-    }
-    args_struct(F);
-    if (F.lds_bytes > 0) src << "  __shared__ double lds_blk[" << (F.lds_bytes / 8) << "];\n";
-    else src << "  double* lds_blk = nullptr;\n";
-    if (is_obj) src << "  __shared__ double lds4[IEM_TILE / 64 + 1];\n";
-    else src << "  double* lds4 = nullptr;\n";
-    if (is_obj) {
-      // (a pending halo exchange rides on this launch as one extra leading workgroup; the walkers are the others)
-      F.carries = opt.carrier != 0;
-      if (opt.carrier)
-      src << "  const long long cb_ = A.comm != nullptr ? 1 : 0;\n"
-          << "  if (cb_ && blockIdx.x == 0) { iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
-          << "  const long long bx_ = (long long)blockIdx.x - cb_, gx_ = (long long)gridDim.x - cb_;\n";
-      else src << "  const long long bx_ = (long long)blockIdx.x, gx_ = (long long)gridDim.x;\n";
-      src << dispatch_code(E, 0, 0, 0, 0, std::to_string(E.tbl), "bx_", "gx_", "A.out", "A.aux", "  ");
-      src << "}\n\n";
-      ns_end(ktile);
-      P.kernels.push_back(F);
-      continue;
-    }
-    F.carries = opt.carrier && !E.si && (kind == KK_CONS || kind == KK_JAC || kind == KK_HESS || kind == KK_JPROD);
-    if (F.carries)
-      src << "  const long long cb_ = A.comm != nullptr ? 1 : 0;   // a pending halo exchange rides on this launch: one extra leading workgroup\n"
-          << "  if (cb_ && blockIdx.x == 0) { iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
-          << "  const long long b = (long long)blockIdx.x - cb_;\n";
-    else
-    src << "  const long long b = blockIdx.x;\n";
-    if (E.si) src << "  double* __restrict__ OUT = A.out; double* __restrict__ AUX = A.aux;\n";
-    src << dispatch_code(E, 0, 0, 0, 0, std::to_string(E.tbl), "b", "", "A.out", "A.aux", "  ");
-    src << "}\n\n";
-    ns_end(ktile);
-    P.kernels.push_back(F);
-  }
-  // ---- one launch per solver phase (KK_TRIAL: obj + cons! at a trial point; KK_ACCEPTED: grad! + jac_coord! + hess_coord!
-  // at an accepted point — the call pattern of ext/InfiniteExaModelsMadNLP.jl:49-50,64 and ext/InfiniteExaModelsIpopt.jl:48-49
-  // of the reference).  Member kinds keep their workgroup ranges (largest member first), each decoded by its own dispatch
-  // code at its own table base; bytes identical to the separate calls (same bodies).  Pointers: trial  out = c, aux = the
-  // objective scalar, p2 = the objective's partials;  accepted  out = jac values, aux = hess values, p2 = g, p3 = grad!'s
-  // reduction buffer.  Follow-ups of grad! (axis sums, plan-driven gather, runtime memsets) stay with the runtime.
-  if (phases_on) {
-    struct Member { int kind; std::string out, aux; };
-    struct Phase { int id; const char *name; std::vector<Member> mem; };
-    const Phase phases[] = {
-      {KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
-      {KK_ACCEPTED, "iem_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}}},
-      // all five evaluations of one point in ONE launch (iem_eval_all: the solver's first trial point is usually accepted —
-      // obj, cons!, grad!, jac_coord!, hess_coord! at the same x): p4 = c, p5 = the objective's partials, p6 = its scalar
-      {KK_ALL, "iem_point_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_CONS, "A.p4", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}, {KK_OBJ, "A.p5", "A.p6"}}},
-    };
-    for (const Phase &ph : phases) {
-      bool ok = true;
-      int tile = 0;
-      std::vector<Member> present;   // (a linear program has no hess_coord! kernel: the accepted point is grad! + jac_coord!)
-      for (const Member &mb : ph.mem) {
-        auto it = emitted.find(mb.kind);
-        if (it == emitted.end()) { if (ph.id == KK_TRIAL || mb.kind == KK_OBJ || mb.kind == KK_CONS) ok = false; continue; }
-        if (!tile) tile = it->second.tile;
-        ok = ok && it->second.tile == tile;   // (kinds of different workgroup sizes cannot share a launch)
-        present.push_back(mb);
-      }
-      if (!ok || present.size() < 2 || (ph.id == KK_ALL && present.size() < 3)) continue;
-      KernelDesc F;
-      F.name = std::string(ph.name) + name_tag;
-      F.kind = ph.id; F.block = tile;
-      F.grid[0] = 0; F.grid[1] = F.grid[2] = 1;
-      struct Base { size_t ip, dp, fa, ia; int64_t first, n; size_t tbl; };
-      std::vector<Base> base;
-      std::vector<const KernelBuilder *> bs;
-      bool has_obj = false, has_si = false;
-      for (const Member &mb : present) {
-        const KindEmit &E = emitted[mb.kind];
-        // the member's tables WITHOUT its per-workgroup table (the only part whose length depends on the launch size:
-        // those go behind everything else, so that every index the source names is size-independent)
-        base.push_back(Base{F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), F.grid[0], E.F.grid[0], 0});
-        F.ip.insert(F.ip.end(), E.F.ip.begin(), E.F.ip.begin() + (long)E.tbl);
-        F.dp.insert(F.dp.end(), E.F.dp.begin(), E.F.dp.end());
-        F.fa.insert(F.fa.end(), E.F.fa.begin(), E.F.fa.end());
-        F.ia.insert(F.ia.end(), E.F.ia.begin(), E.F.ia.end());
-        F.grid[0] += E.F.grid[0];
-        F.lds_bytes = std::max(F.lds_bytes, E.F.lds_bytes);
-        F.alg_bytes_written += E.F.alg_bytes_written;
-        F.x_ranges.insert(F.x_ranges.end(), E.F.x_ranges.begin(), E.F.x_ranges.end());
-        F.lds_slots = std::max(F.lds_slots, E.F.lds_slots);
-        for (size_t k : E.ks) bs.push_back(builders[k].get());
-        has_obj = has_obj || mb.kind == KK_OBJ;
-        has_si = has_si || E.si != nullptr;
-      }
-      if (F.grid[0] > 2147483647LL) continue;
-      F.n_blocks = F.grid[0];
-      F.alg_bytes_read = union_read_bytes(bs);
-      const size_t mdec = F.ip.size();            // per member {first workgroup, workgroups, start of its workgroup -> body table}: launch-size dependent -> arguments
-      F.ip.resize(mdec + 3 * base.size());
-      for (size_t i = 0; i < base.size(); ++i) {
-        const KindEmit &E = emitted[present[i].kind];
-        base[i].tbl = F.ip.size();
-        F.ip.insert(F.ip.end(), E.F.ip.begin() + (long)E.tbl, E.F.ip.end());
-        F.ip[mdec + 3 * i] = base[i].first; F.ip[mdec + 3 * i + 1] = base[i].n; F.ip[mdec + 3 * i + 2] = (int64_t)base[i].tbl;
-      }
-      F.tables_in_memory = true;                  // (member tables may hold per-workgroup entries; one form for every size)
-      ns_begin(tile);
-      args_struct(F);
-      if (F.lds_bytes > 0) src << "  __shared__ double lds_blk[" << (F.lds_bytes / 8) << "];\n";
-      else src << "  double* lds_blk = nullptr;\n";
-      if (has_obj) src << "  __shared__ double lds4[IEM_TILE / 64 + 1];\n";
-      else src << "  double* lds4 = nullptr;\n";
-      F.carries = opt.carrier && !has_si;
-      if (F.carries)
-        src << "  const long long cb_ = A.comm != nullptr ? 1 : 0;   // a pending halo exchange rides on this launch: one extra leading workgroup\n"
-            << "  if (cb_ && blockIdx.x == 0) { iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
-            << "  const long long pb_ = (long long)blockIdx.x - cb_;\n";
-      else src << "  const long long pb_ = blockIdx.x;\n";
-      for (size_t i = 0; i < present.size(); ++i) {
-        const KindEmit &E = emitted[present[i].kind];
-        src << "  " << (i ? "else " : "");
-        if (i + 1 < present.size()) src << "if (pb_ < A.ip[" << (mdec + 3 * (i + 1)) << "]) ";
-        src << "{\n    const long long b = pb_ - A.ip[" << (mdec + 3 * i) << "];\n";
-        if (E.si) src << "    double* __restrict__ OUT = " << present[i].out << "; double* __restrict__ AUX = " << present[i].aux << ";\n";
-        src << dispatch_code(E, base[i].ip, base[i].dp, base[i].fa, base[i].ia, "A.ip[" + std::to_string(mdec + 3 * i + 2) + "]", "b", "A.ip[" + std::to_string(mdec + 3 * i + 1) + "]",
-                             present[i].out, present[i].aux, "    ");
-        src << "  }\n";
-      }
-      src << "}\n\n";
-      ns_end(tile);
-      P.kernels.push_back(F);
-    }
-  }
-  // jac_coord! + hess_coord! in ONE launch (KK_PAIR; iem_jac_hess_coord).  The two calls are independent given x (and y):
-  // behind one workgroup-id dispatcher their bodies share a launch — one ramp and one drain instead of two, and on a grid
-  // of about one workgroup per CU (a 1/8 shard of the headline problem: 252 + 252 workgroups) both kinds are resident
-  // together, 16 waves per CU instead of 8.  `out` = Jacobian values, `aux` = Hessian values; every body is generated
-  // again by a builder of its own (a builder emits once), with the options its stand-alone twin got.
-  if (opt.pair_kernel && !opt.no_fuse) {
-    std::vector<size_t> ks;
-    bool have[2] = {false, false};
-    for (size_t k = 0; k < descs.size(); ++k)
-      if (descs[k].kind == KK_JAC || descs[k].kind == KK_HESS) { ks.push_back(k); have[descs[k].kind == KK_HESS] = true; }
-    int ptile = 0;
-    bool one_tile = true;
-    for (size_t k : ks) { if (!ptile) ptile = descs[k].block; one_tile = one_tile && descs[k].block == ptile; }
-    if (have[0] && have[1] && one_tile) {   // (kinds of different workgroup sizes cannot share a launch: the two calls stay)
-      ns_begin(ptile);
-      std::vector<std::unique_ptr<KernelBuilder>> pb;
-      std::vector<KernelDesc> pd;
-      std::vector<bool> pxcd;
-      int64_t nnz_again = 0;
-      std::vector<HessClass> classes_again;
-      for (size_t k : ks) {   // in the order of the first pass: the merged Hessian layout's offsets are running counters
-        // (jac_coord!'s two halves, Options::jac_split, are ONE body again here unless pair_inter asks for interleaved bodies:
-        // measured, the pair is fastest as jac_coord!'s workgroups followed by hess_coord!'s — 0.155 ms against 0.159 - 0.165
-        // for any interleaving at 1e6 quadrotor supports, profiles/r04_ab_jac_split.txt)
-        const bool rejoin = !opt.pair_inter && whole_of.count(k);
-        if (!opt.pair_inter && second_half.count(k)) continue;
-        KernelDesc kd;
-        kd.name = (rejoin ? whole_of[k].second : descs[k].name) + "_p"; kd.kind = descs[k].kind; kd.block = descs[k].block; kd.lds_slots = descs[k].lds_slots; kd.inter = rejoin ? -1 : descs[k].inter;
-        for (int d = 0; d < 3; ++d) kd.grid[d] = descs[k].grid[d];
-        kd.n_blocks = descs[k].n_blocks;
-        auto kb = std::make_unique<KernelBuilder>(m, rejoin ? *whole_of[k].first : builders[k]->group(), kd.kind, kopts[k], kd.name);
-        if (!kb->build(nullptr)) throw std::runtime_error("internal: pair body without outputs");
-        if (kd.kind == KK_HESS && opt.hess_merge) kb->merge_hess(nnz_again, classes_again);
-        pb.push_back(std::move(kb));
-        pd.push_back(kd);
-        pxcd.push_back(kopts[k].xcd_remap != 0);
-      }
-      std::vector<size_t> ord(pd.size());
-      for (size_t j = 0; j < ord.size(); ++j) ord[j] = j;
-      std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return pd[a].n_blocks > pd[b].n_blocks; });
-      KernelDesc F;
-      F.name = std::string("iem_pair_all") + name_tag;
-      F.kind = KK_PAIR; F.block = ptile;
-      F.grid[0] = 0; F.grid[1] = F.grid[2] = 1;
-      std::vector<size_t> oip, odp, ofa, oia;
-      for (size_t j : ord) {
-        src << pb[j]->emit(pd[j], true);
-        const KernelDesc &d = pd[j];
-        oip.push_back(F.ip.size()); odp.push_back(F.dp.size()); ofa.push_back(F.fa.size()); oia.push_back(F.ia.size());
-        F.ip.insert(F.ip.end(), d.ip.begin(), d.ip.end());
-        F.dp.insert(F.dp.end(), d.dp.begin(), d.dp.end());
-        F.fa.insert(F.fa.end(), d.fa.begin(), d.fa.end());
-        F.ia.insert(F.ia.end(), d.ia.begin(), d.ia.end());
-        F.grid[0] += d.n_blocks;
-        F.lds_bytes = std::max(F.lds_bytes, d.lds_bytes);
-        F.alg_bytes_read += d.alg_bytes_read; F.alg_bytes_written += d.alg_bytes_written;
-        F.x_ranges.insert(F.x_ranges.end(), d.x_ranges.begin(), d.x_ranges.end());
-        F.lds_slots = std::max(F.lds_slots, d.lds_slots);
-      }
-      {
-        std::vector<const KernelBuilder *> bs;
-        for (auto &b : pb) bs.push_back(b.get());
-        F.alg_bytes_read = union_read_bytes(bs);   // x7..x9, u1..u3, h are loaded by both kinds' bodies: counted once
-      }
-      if (F.grid[0] <= 2147483647LL) {   // (larger: the two calls stay separate launches)
-        F.n_blocks = F.grid[0];
-        const size_t dec = F.ip.size();
-        int64_t first = 0;
-        for (size_t j : ord) {
-          F.ip.push_back(first); F.ip.push_back(pd[j].grid[0]); F.ip.push_back(pd[j].grid[1]); F.ip.push_back(pd[j].grid[2]);
-          first += pd[j].n_blocks;
-        }
-        const size_t tbl = F.ip.size();
-        const bool table = ord.size() > 4 && F.grid[0] <= (1 << 18);   // many bodies (templates side by side): workgroup -> body table, one scalar load
-        if (table)
-          for (size_t jj = 0; jj < ord.size(); ++jj) F.ip.insert(F.ip.end(), (size_t)pd[ord[jj]].n_blocks, (int64_t)jj);
-        const size_t nip = std::max<size_t>(1, F.ip.size()), ndp = std::max<size_t>(1, F.dp.size());
-        const size_t nfa = std::max<size_t>(1, F.fa.size()), nia = std::max<size_t>(1, F.ia.size());
-        F.tables_in_memory = (nip + ndp + nfa + nia) > 320 || F.ip.size() > tbl;
-        args_struct(F);
-        if (F.lds_bytes > 0) src << "  __shared__ double lds_blk[" << (F.lds_bytes / 8) << "];\n";
-        else src << "  double* lds_blk = nullptr;\n";
-        src << "  double* lds4 = nullptr;\n";
-        F.carries = opt.carrier != 0;
-        if (opt.carrier)
-        src << "  const long long cb_ = A.comm != nullptr ? 1 : 0;   // a pending halo exchange rides on this launch: one extra leading workgroup\n"
-            << "  if (cb_ && blockIdx.x == 0) { iem_halo_wg(*A.comm, const_cast<double*>(A.x)); return; }\n"
-            << "  const long long b = (long long)blockIdx.x - cb_;\n";
-        else src << "  const long long b = blockIdx.x;\n";
-        auto call = [&](size_t jj, const std::string &ind) {
-          const KernelDesc &d = pd[ord[jj]];
-          std::ostringstream c;
-          c << ind << d.name << "_body(A.x, A.th, A.y, A.v, " << (d.kind == KK_JAC ? "A.out" : "A.aux") << ", A.w, nullptr, A.ip + " << oip[jj] << ", A.dp + " << odp[jj]
-            << ", A.fa + " << ofa[jj] << ", A.ia + " << oia[jj] << ", lds_blk, lds4, lb % gx, (lb / gx) % gy, lb / (gx * gy), gx, gy, gz);\n";
-          return c.str();
-        };
-        bool pair_remap = false;
-        for (bool f : pxcd) pair_remap = pair_remap || f;
-        if (ord.size() > 4) {
-          if (table) src << "  const int lo_ = (int)A.ip[" << tbl << " + b];\n";
-          else src << "  int lo_ = 0, hi_ = " << ord.size() << ";\n"
-                   << "  while (hi_ - lo_ > 1) { const int mid_ = (lo_ + hi_) >> 1; if (b >= A.ip[" << dec << " + 4 * mid_]) lo_ = mid_; else hi_ = mid_; }\n";
-          src << "  const long long gx = A.ip[" << dec << " + 4 * lo_ + 1], gy = A.ip[" << dec << " + 4 * lo_ + 2], gz = A.ip[" << dec << " + 4 * lo_ + 3];\n"
-              << "  const long long lb = " << (pair_remap ? "iem_xcd_remap(b - A.ip[" + std::to_string(dec) + " + 4 * lo_], gx * gy * gz)" : "b - A.ip[" + std::to_string(dec) + " + 4 * lo_]")
-              << ";\n  switch (lo_) {\n";
-          for (size_t jj = 0; jj < ord.size(); ++jj) src << "    case " << jj << ":\n" << call(jj, "      ") << "      break;\n";
-          src << "  }\n";
-        } else {
-          // bodies of one grid (jac_coord!'s halves and hess_coord! of the same support grid) take turns: all resident together
-          size_t run = 1;
-          auto same = [&](size_t a, size_t b2) {
-            return pd[ord[a]].n_blocks == pd[ord[b2]].n_blocks && pd[ord[a]].grid[0] == pd[ord[b2]].grid[0] && pd[ord[a]].grid[1] == pd[ord[b2]].grid[1] &&
-                   pxcd[ord[a]] == pxcd[ord[b2]] && (opt.pair_inter || (pd[ord[a]].inter >= 0 && pd[ord[a]].inter == pd[ord[b2]].inter));
-          };
-          while (run < ord.size() && same(0, run)) ++run;
-          std::vector<bool> rm;
-          for (size_t jj = 0; jj < ord.size(); ++jj) rm.push_back(pxcd[ord[jj]]);
-          emit_dispatch_chain(src, ord.size(), dec, run, opt.jac_split == 1 ? 1 : 2, rm, "b", call, [](size_t) { return std::string(); }, opt.split_shift != 0);
-        }
-        src << "}\n\n";
-        P.kernels.push_back(F);
-      }
-      ns_end(ptile);
-    }
-  }
+  // the launches: one per NLPModels call, one per solver phase, and jac_coord! + hess_coord! in one
+  Emitter E{src, descs, builders, kopts, opt, P};
+  for (const KernelDesc &d : descs) E.mixed = E.mixed || d.block != opt.block;
+  E.name_tag = name_tag;
+  emit_kinds(E);
+  emit_phases(E);
+  emit_pair(E, m, whole_of, second_half);
   P.source = src.str();
   P.key = fnv1a64(P.source);
   return P;

@@ -85,7 +85,6 @@ struct Options {
   int autotune = 0;    // opt-in (measured gains depend on the process).  1: jac_coord!/hess_coord! of large grids keep a second code object (lds_slots = 48) and pick, per output
                        // buffer, the faster of the two from their first twenty calls (runtime only; the generator ignores it)
   int autotune_min_blocks = 400;   // ... grids of at least this many workgroups (about 2e5 supports)
-  int obj_unroll = 1;  // 2: the objective's tile walk takes two tiles per trip (single-body kernels)
   int det_shared = 1;  // 1: scatter entries shared by many items are reduced deterministically (iem_shared_*), 0: one f64 atomic per wave
   // LARGE grids — outputs far beyond the 256-MiB Infinity Cache, everything goes to DRAM — get another kernel shape for
   // jac_coord! / hess_coord!, chosen from the GRID SIZE per kind (never from a timer): when a kind has a grid of at least
@@ -120,16 +119,11 @@ struct Options {
   // workgroups interleaved so that both are resident: body a = the templates whose partials are item data or constants
   // (linear rows: difference rows h, -1, +1 of src/transform.jl:511-562, affine dynamics) — no x load, no arithmetic, a
   // fill-shaped body; body b = the rest (loads, trigonometry).  Halves the store fronts a workgroup keeps open; same bytes.
-  // 1: bodies alternate workgroup by workgroup; 2: in runs of 8 workgroups (one per XCD), so every XCD sees both; 0: off
+  // 1: bodies alternate workgroup by workgroup, on every lane-fused grid (the source stays size-independent); 0: off
   int jac_split = 1;
-  int64_t jac_split_min = 0;    // ... only grids of more workgroups than this (0: every lane-fused grid — the source stays size-independent)
   int digit_fields = 1;    // fields the parse-time digit pass recognised (iem_model.hpp: recover_digits, folded runs only) are decoded
                            // from the item coordinate in registers; 0: they stay gathers from their short columns
   int cons_direct_2d = 1;  // cons! of a model whose largest grid is 2-D: plain coalesced stores instead of the LDS re-cut (kind_options)
-  int split_shift = 0;     // jac_split's bodies: 1 = the FIRST body of an interleaved run (the data rows) takes its tiles half a grid away from the
-                           // others' — its store fronts then sit in another part of the output while the computed rows' fronts pass
-  int pair_inter = 0;      // the fused pair: 1 = bodies of equal grids (jac_coord!'s halves, hess_coord!) interleaved the same way; 0 (default,
-                           // measured faster) = jac_coord! as ONE body, its workgroups first, hess_coord!'s behind them
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };

@@ -319,6 +319,39 @@ def test_existing_emit_keys_unchanged(name, built):
     assert f"{key:016x}" == want["emit_key"]
 
 
+def _emit_keys_tool():
+    import sys
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import record_emit_keys
+    return record_emit_keys
+
+
+@pytest.mark.parametrize("name", list(cases.small_cases()) + NAMES)
+def test_emit_keys_under_options(name, built):
+    """Source key and launch plan of every small model under the option sets of tools/record_emit_keys.py, against what
+    the generator emitted BEFORE its multi-body launches were given one path (tests/golden/emit_keys_options.json, recorded
+    at that commit's parent): the generated code and the launch descriptors are byte-identical."""
+    rk = _emit_keys_tool()
+    want = json.load(open(rk.GOLDEN))[name]
+    blob = cases.build_core(name).to_blob() if name in cases.small_cases() else _core(name)[0].to_blob()
+    assert hashlib.sha256(blob).hexdigest()[:16] == want["blob_sha256_16"]
+    assert list(want["sets"]) == sorted(rk.set_name(o) for o in rk.OPTION_SETS)
+    for opts in rk.OPTION_SETS:
+        assert rk.emit_record(blob, opts) == want["sets"][rk.set_name(opts)], (name, opts)
+
+
+def test_option_names_and_ranges(built):
+    """Every knob of lib.OPTION_DEFAULTS is one the library knows; any other name, and jac_split's retired value 2, fail."""
+    for k, v in iemlib.OPTION_DEFAULTS.items():
+        iemlib.set_option(k, v)
+    with pytest.raises(iemlib.IemError, match="unknown option no_such_knob"):
+        iemlib.set_option("no_such_knob", 0)
+    with pytest.raises(iemlib.IemError, match="jac_split must be 0 or 1"):
+        iemlib.set_option("jac_split", 2)
+
+
 # 7 -- sharding and the chain KKT solver refuse ------------------------------------------------------
 @pytest.mark.parametrize("group", [1, 3, 4])
 def test_sharding_refuses(group, built):
