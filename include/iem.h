@@ -138,8 +138,15 @@ int iem_create_sharded(const void *blob, size_t nbytes, int device, int group, i
                        const iem_option_t *opts, int n_opts, iem_model **out);
 int iem_shard_info(const iem_model *m, iem_shard_t *out);
 /* local variable -> global variable (0-based), and per local variable: bit 0 owned by this rank,
- * bit 1 replicated on every rank, bit 2 halo copy of the left neighbour's variable (either may be NULL) */
+ * bit 1 replicated on every rank, bit 2 halo copy of the LEFT neighbour's variable (in front of the owned block),
+ * bit 3 halo copy of the RIGHT neighbour's variable (behind it: forward / central differences) (either may be NULL) */
 int iem_shard_var_map(const iem_model *m, int64_t *h_map, uint8_t *h_flag);
+/* Both directions of the halo (iem_shard_t keeps its layout: its halo / halo_reach / halo_doubles are the FRONT halo):
+ * out = {halo_left, halo_right, reach_left, reach_right, doubles_to_right, doubles_to_left} — the halo supports this rank
+ * carries in front of / behind its owned block, the model's stencil reach to the left / right (backward differences:
+ * 1 / 0, forward: 0 / 1, central: 1 / 1; transform.jl:535), and the doubles one rank sends its right / left neighbour
+ * per exchange.  A shard with reach_right > 0 exchanges (and folds) both ways in ONE kernel: all sends before all waits. */
+int iem_shard_halo(const iem_model *m, int64_t out[6]);
 int iem_shard_template_info(const iem_model *m, int64_t i, iem_shard_template_t *out);
 /* global item ordinals of every explicit-list template, concatenated (see items_offset); h_items may be NULL to
  * query the length */
@@ -178,12 +185,15 @@ int iem_halo_reads(const iem_model *m, int kind, int *out_x, int *out_v, int *ou
  * (iem_jtprod): the entries of the halo copies hold what this rank's rows owe to variables the LEFT neighbour owns
  * (the x_k[a_r - 1] column of the first difference row, src/transform.jl:535-557).  They are sent to the left
  * neighbour, which ADDS them to its owned entries (one addend per entry: order-independent), and zeroed here.
+ * A two-sided shard (iem_shard_halo: reach_right > 0) also sends its BACK halo copies to the right neighbour; an owned
+ * entry then takes the left neighbour's addend first, the right neighbour's second — a fixed order, reproducible bits.
  * Entries of replicated variables are summed with iem_allreduce_obj_grad (d_obj may be NULL).  Asynchronous on the
  * handle's stream, graph-capturable, bounded waits like iem_halo_exchange. */
 int iem_halo_fold(iem_model *m, double *d_vec);
 int iem_allreduce_obj_grad(iem_model *m, double *d_obj /* device scalar, may be NULL */, double *d_g);
 /* synchronises the handle's stream; 0 = every exchange so far completed, else a bit mask of time-outs (1 / 2 halo ack / data,
- * 4 all-reduce, 8 / 16 fold ack / data).  A time-out never hangs and never goes unnoticed: the kernel that ran into it writes
+ * 4 all-reduce, 8 / 16 fold ack / data; the second direction of a two-way exchange: 32 / 64 halo ack / data, 128 / 256 fold
+ * ack / data).  A time-out never hangs and never goes unnoticed: the kernel that ran into it writes
  * NaN instead of the data that did not arrive, and the next iem_obj / iem_obj_end / iem_synchronize returns IEM_E_COMM (and
  * clears the mask).  The bound is the per-handle option "comm_timeout_ms" (default 5000). */
 int iem_comm_status(iem_model *m, int64_t *out_status);

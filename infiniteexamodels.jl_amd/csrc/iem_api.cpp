@@ -32,6 +32,9 @@
 static const char *kDeviceHeader =
 #include "iem_device_h.inc"
     ;
+static const char *kHalo2Header =   // the two-way halo exchange: only in the source of a two-sided shard (Options::two_sided)
+#include "iem_halo2_device_h.inc"
+    ;
 static const char *kKktSource =
 #include "iem_kkt_device_h.inc"
     ;
@@ -98,6 +101,7 @@ std::string full_source(const iem::Program &p, const iem::Options &o) {
     s += "#undef IEM_TILE\n#define IEM_TILE " + std::to_string(p.block) + "\n";
     s += hdr.substr(b);
   }
+  if (o.two_sided) s += std::string("\n") + kHalo2Header;
   s += "\n";
   s += p.source;
   return s;
@@ -183,7 +187,7 @@ struct iem_model {
   // multi-GPU (iem_create_sharded): what was cut, and the mailbox the peers push into
   bool sharded = false;
   iem::ShardInfo shard;
-  hipFunction_t fn_halo = nullptr, fn_reduce = nullptr, fn_fold = nullptr;
+  hipFunction_t fn_halo = nullptr, fn_reduce = nullptr, fn_fold = nullptr;   // (a two-sided shard: the two-way kernels of iem_halo2_device.h)
   unsigned long long *mailbox = nullptr;   // device memory, exported through HIP IPC
   size_t mailbox_words = 0;
   int mailbox_kind = 0;   // 0 none yet, 1 uncached (fine-grained) device memory, 2 plain hipMalloc
@@ -192,6 +196,7 @@ struct iem_model {
   std::vector<void *> ipc_opened;          // what hipIpcCloseMemHandle must release
   unsigned long long **d_peers = nullptr;
   long long *d_halo_src = nullptr, *d_halo_dst = nullptr, *d_shared = nullptr;
+  long long *d_halo_src_l = nullptr, *d_halo_dst_r = nullptr;   // second direction: my first owned supports (go left), my back halo entries
   int64_t n_shared = 0;
   double *h_obj = nullptr;   // pinned + mapped host scalar
   double *d_hobj = nullptr;  // its device address
@@ -331,8 +336,8 @@ int compile_or_load(iem_model *m) {
   HIP_TRY(hipModuleGetFunction(&m->fn_spmv_long, m->code.mod, "iem_csr_spmv_long_kernel"));
   HIP_TRY(hipModuleGetFunction(&m->fn_axis, m->code.mod, "iem_axis_sum_kernel"));
   HIP_TRY(hipModuleGetFunction(&m->fn_gather, m->code.mod, "iem_gather_sum_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_halo, m->code.mod, "iem_halo_kernel"));
-  HIP_TRY(hipModuleGetFunction(&m->fn_fold, m->code.mod, "iem_halo_fold_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_halo, m->code.mod, m->opt.two_sided ? "iem_halo2_kernel" : "iem_halo_kernel"));
+  HIP_TRY(hipModuleGetFunction(&m->fn_fold, m->code.mod, m->opt.two_sided ? "iem_halo2_fold_kernel" : "iem_halo_fold_kernel"));
   HIP_TRY(hipModuleGetFunction(&m->fn_reduce, m->code.mod, "iem_allreduce_kernel"));
   return IEM_OK;
 }
@@ -406,22 +411,31 @@ int comm_check(iem_model *m) {
   const unsigned long long bits = *m->h_status;
   *m->h_status = 0;
   if (m->mailbox) { const unsigned long long z = 0; (void)hipMemcpy(m->mailbox, &z, 8, hipMemcpyHostToDevice); (void)hipGetLastError(); }
-  return fail(IEM_E_COMM, "a mailbox wait timed out (status bits " + std::to_string(bits) + ": 1/2 halo ack/data, 4 all-reduce, 8/16 fold ack/data): "
+  return fail(IEM_E_COMM, "a mailbox wait timed out (status bits " + std::to_string(bits) + ": 1/2 halo ack/data, 4 all-reduce, 8/16 fold ack/data; 32/64 and 128/256: the same of the second direction): "
                           "a peer did not take part in the exchange; the halo entries / reduced values it should have delivered were set to NaN");
 }
 
 // the all-reduce runs on G workgroups, each on its own chunk of the NR doubles (one per 1 024, at most 64)
 int64_t reduce_chunks(int64_t NR) { return std::min<int64_t>(64, std::max<int64_t>(1, (NR + 1023) / 1024)); }
-struct HaloArgsH { double *x; unsigned long long *mine, *left, *right; const long long *src, *dst; long long NH, W, G; unsigned long long *hstatus; long long ticks; };
+// IemHaloArgs, and behind it what IemHalo2Args adds (iem_halo2_device.h); a one-way shard's kernels take the first 11 words only
+struct HaloArgsH { double *x; unsigned long long *mine, *left, *right; const long long *src, *dst; long long NH, W, G; unsigned long long *hstatus; long long ticks;
+                   const long long *src_l, *dst_r; long long NL, B2; };
+constexpr size_t kHaloArgs1 = 11 * 8;
+// word offset of the second direction's block in a mailbox: behind the fold data of the one-way layout
+int64_t mailbox_b2(int64_t W, int64_t NH, int64_t NR) {
+  const int64_t G = reduce_chunks(NR);
+  return 12 + G + 2 * W * G + 2 * NH + 2 * W * NR + 2 * NH;
+}
 HaloArgsH halo_args(iem_model *m, double *d_x) {
   const iem::ShardInfo &si = m->shard;
   return HaloArgsH{d_x, m->mailbox, si.rank > 0 ? m->peers[si.rank - 1] : nullptr, si.rank + 1 < si.world ? m->peers[si.rank + 1] : nullptr,
                    m->d_halo_src, m->d_halo_dst, (long long)si.halo_doubles, (long long)si.world, (long long)reduce_chunks(1 + m->n_shared),
-                   m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL};
+                   m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL,
+                   m->d_halo_src_l, m->d_halo_dst_r, (long long)si.halo_doubles_right, (long long)mailbox_b2(si.world, si.halo_doubles, 1 + m->n_shared)};
 }
 int halo_launch(iem_model *m, double *d_x, hipStream_t stream) {
   HaloArgsH A = halo_args(m, d_x);
-  size_t sz = sizeof A;
+  size_t sz = m->opt.two_sided ? sizeof A : kHaloArgs1;
   void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   HIP_TRY(hipModuleLaunchKernel(m->fn_halo, 1, 1, 1, 256, 1, 1, 0, stream, nullptr, cfg));
   return IEM_OK;
@@ -823,6 +837,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "pair_kernel") == 0) { o.pair_kernel = (int)value; return IEM_OK; }
   if (std::strcmp(name, "store_wait") == 0) { o.store_wait = (int)value; return IEM_OK; }
   if (std::strcmp(name, "carrier") == 0) { o.carrier = value != 0; return IEM_OK; }
+  if (std::strcmp(name, "two_sided") == 0) { o.two_sided = value != 0; return IEM_OK; }
   if (std::strcmp(name, "phase_kernels") == 0) { o.phase_kernels = value != 0; return IEM_OK; }
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
@@ -968,6 +983,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
       iem::shard_model(m->model, shard_group, rank, world, m->shard);
       m->sharded = true;
       m->opt.carrier = 1;    // only a sharded handle's kernels carry the halo-exchange prologue (iem_halo_exchange_async)
+      m->opt.two_sided = m->shard.reach_right > 0 ? 1 : 0;   // a stencil reaches to the right: the two-way exchange kernels join the source
       // continue from the shard's own blob — byte for byte what iem_shard_blob hands out — so that the
       // generated source (hence the code-object cache key) is the one an offline build of that blob gets,
       // and the global arrays nothing references any more (x0/lvar/uvar of the whole model) are released
@@ -1033,7 +1049,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
     // which kinds can touch a halo entry of x / of a variable-space v: from the live loads of the generated kernels
     const auto &flag = m->shard.var_flag;
     std::vector<int64_t> pre(flag.size() + 1, 0);
-    for (size_t i = 0; i < flag.size(); ++i) pre[i + 1] = pre[i] + ((flag[i] & 4) ? 1 : 0);
+    for (size_t i = 0; i < flag.size(); ++i) pre[i + 1] = pre[i] + ((flag[i] & 12) ? 1 : 0);   // front and back halo copies alike
     auto hits = [&](const std::vector<std::pair<int64_t, int64_t>> &rs) {
       for (auto &r : rs) {
         const int64_t lo = std::max<int64_t>(0, r.first), hi = std::min<int64_t>((int64_t)flag.size() - 1, r.second);
@@ -1105,6 +1121,8 @@ int iem_destroy(iem_model *m) {
   if (m->d_peers) hipFree(m->d_peers);
   if (m->d_halo_src) hipFree(m->d_halo_src);
   if (m->d_halo_dst) hipFree(m->d_halo_dst);
+  if (m->d_halo_src_l) hipFree(m->d_halo_src_l);
+  if (m->d_halo_dst_r) hipFree(m->d_halo_dst_r);
   if (m->d_shared) hipFree(m->d_shared);
   if (m->h_obj) hipHostFree(m->h_obj);
   if (m->d_comm) hipFree(m->d_comm);
@@ -1516,9 +1534,9 @@ std::vector<int64_t> shard_items(const iem::ShardInfo &si) {
 
 // mailbox words: see iem_device.h
 // the all-reduce runs on G workgroups, each on its own chunk of the NR doubles (one per 1 024, at most 64)
-size_t mailbox_words(int64_t W, int64_t NH, int64_t NR) {
-  const int64_t G = reduce_chunks(NR);
-  return (size_t)(12 + G + 2 * W * G + 2 * NH + 2 * W * NR + 2 * NH);   // header, reduce flags, halo data, reduce data, fold data
+size_t mailbox_words(int64_t W, int64_t NH, int64_t NR, int64_t NL) {
+  // header, reduce flags, halo data, reduce data, fold data; a two-sided shard: the second direction's block (8 words, halo data, fold data)
+  return (size_t)(mailbox_b2(W, NH, NR) + (NL > 0 ? 8 + 4 * NL : 0));
 }
 
 struct CommHandle {   // what iem_comm_export writes (IEM_COMM_HANDLE_BYTES)
@@ -1589,6 +1607,15 @@ int iem_shard_info(const iem_model *m, iem_shard_t *out) {
   return IEM_OK;
 }
 
+int iem_shard_halo(const iem_model *m, int64_t out[6]) {
+  if (!m || !out) return fail(IEM_E_ARG, "null argument");
+  if (!m->sharded) return fail(IEM_E_ARG, "not a sharded handle (iem_create_sharded)");
+  const iem::ShardInfo &si = m->shard;
+  out[0] = si.halo; out[1] = si.halo_right; out[2] = si.halo_reach; out[3] = si.reach_right;
+  out[4] = si.halo_doubles; out[5] = si.halo_doubles_right;
+  return IEM_OK;
+}
+
 int iem_shard_var_map(const iem_model *m, int64_t *h_map, uint8_t *h_flag) {
   if (!m) return fail(IEM_E_ARG, "null argument");
   if (!m->sharded) return fail(IEM_E_ARG, "not a sharded handle (iem_create_sharded)");
@@ -1620,16 +1647,16 @@ int iem_comm_export(iem_model *m, void *out_handle) {
   if (!m->sharded) return fail(IEM_E_ARG, "not a sharded handle (iem_create_sharded)");
   DevGuard dg_(m->device);
   const iem::ShardInfo &si = m->shard;
-  if (si.halo_reach > 0)
-    for (int r = 0; r < si.world; ++r) {   // a stencil must not reach past the neighbouring rank
+  if (si.halo_reach > 0 || si.reach_right > 0)
+    for (int r = 0; r < si.world; ++r) {   // a stencil must not reach past the neighbouring rank (either way)
       int64_t a, b;
       iem::partition_block(si.n_global, si.world, r, a, b);
-      if (b - a < si.halo_reach) return fail(IEM_E_ARG, "a rank owns fewer supports than the stencil reaches");
+      if (b - a < std::max(si.halo_reach, si.reach_right)) return fail(IEM_E_ARG, "a rank owns fewer supports than the stencil reaches");
     }
   int64_t ns = 0;
   for (unsigned char f : si.var_flag) ns += (f & 2) ? 1 : 0;
   m->n_shared = ns;
-  m->mailbox_words = mailbox_words(si.world, si.halo_doubles, 1 + ns);
+  m->mailbox_words = mailbox_words(si.world, si.halo_doubles, 1 + ns, si.halo_doubles_right);
   CommHandle h;
   std::memset(&h, 0, sizeof h);
   if (!m->mailbox) {
@@ -1718,14 +1745,29 @@ int iem_comm_connect(iem_model *m, const void *all_handles) {
   HIP_TRY(hipMemcpy(m->d_peers, m->peers.data(), sizeof(void *) * (size_t)si.world, hipMemcpyHostToDevice));
   // halo positions: what goes to the right neighbour (my last `reach` owned supports of every sharded
   // slab), where the left neighbour's arrive (my first `reach` window entries) — one canonical order
-  std::vector<long long> src, dst;
+  // The second direction likewise: my FIRST `reach_right` owned supports go left, the right neighbour's arrive in my back
+  // halo entries.  A rank at an end of the chain has no such entries: its positions are never used and stay 0.
+  std::vector<long long> src, dst, src_l, dst_r;
+  const int64_t own_end = si.halo + si.own_n;   // window coordinate behind the last owned support
   for (const iem::HaloSeg &sg : si.segs)
-    for (int64_t o = 0; o < sg.outer; ++o)
+    for (int64_t o = 0; o < sg.outer; ++o) {
+      const int64_t base = sg.loff + o * sg.wn * sg.inner;
       for (int64_t j = 0; j < si.halo_reach * sg.inner; ++j) {
-        src.push_back(sg.loff + o * sg.wn * sg.inner + (sg.wn - si.halo_reach) * sg.inner + j);
-        dst.push_back(sg.loff + o * sg.wn * sg.inner + j);
+        src.push_back(base + (own_end - si.halo_reach) * sg.inner + j);
+        dst.push_back(base + j);
       }
-  if ((int64_t)src.size() != si.halo_doubles) return fail(IEM_E_ARG, "internal: halo size mismatch");
+      for (int64_t j = 0; j < si.reach_right * sg.inner; ++j) {
+        src_l.push_back(base + si.halo * sg.inner + j);
+        dst_r.push_back(si.halo_right == si.reach_right ? base + own_end * sg.inner + j : 0);
+      }
+    }
+  if ((int64_t)src.size() != si.halo_doubles || (int64_t)src_l.size() != si.halo_doubles_right) return fail(IEM_E_ARG, "internal: halo size mismatch");
+  if (!src_l.empty()) {
+    HIP_TRY(hipMalloc((void **)&m->d_halo_src_l, src_l.size() * 8));
+    HIP_TRY(hipMalloc((void **)&m->d_halo_dst_r, dst_r.size() * 8));
+    HIP_TRY(hipMemcpy(m->d_halo_src_l, src_l.data(), src_l.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_halo_dst_r, dst_r.data(), dst_r.size() * 8, hipMemcpyHostToDevice));
+  }
   if (!src.empty()) {
     HIP_TRY(hipMalloc((void **)&m->d_halo_src, src.size() * 8));
     HIP_TRY(hipMalloc((void **)&m->d_halo_dst, dst.size() * 8));
@@ -1751,7 +1793,7 @@ int iem_halo_exchange(iem_model *m, double *d_x) {
   if (!m || !d_x) return fail(IEM_E_ARG, "null argument");
   if (!m->connected) return fail(IEM_E_ARG, "iem_halo_exchange: not connected (iem_comm_connect)");
   const iem::ShardInfo &si = m->shard;
-  if (si.halo_doubles == 0 || si.world == 1) return IEM_OK;   // no stencil crosses the shard boundary
+  if ((si.halo_doubles == 0 && si.halo_doubles_right == 0) || si.world == 1) return IEM_OK;   // no stencil crosses the shard boundary
   DevGuard dg_(m->device);
   int rc = halo_flush(m);   // one exchange at a time (the mailbox has two parity slots)
   if (rc) return rc;
@@ -1762,7 +1804,7 @@ int iem_halo_exchange_async(iem_model *m, double *d_x) {
   if (!m || !d_x) return fail(IEM_E_ARG, "null argument");
   if (!m->connected) return fail(IEM_E_ARG, "iem_halo_exchange_async: not connected (iem_comm_connect)");
   const iem::ShardInfo &si = m->shard;
-  if (si.halo_doubles == 0 || si.world == 1) return IEM_OK;
+  if ((si.halo_doubles == 0 && si.halo_doubles_right == 0) || si.world == 1) return IEM_OK;
   DevGuard dg_(m->device);
   int rc = halo_flush(m);   // an earlier exchange nobody carried: it goes first, in order
   if (rc) return rc;
@@ -1789,14 +1831,17 @@ int iem_halo_fold(iem_model *m, double *d_vec) {
   if (!m || !d_vec) return fail(IEM_E_ARG, "null argument");
   if (!m->connected) return fail(IEM_E_ARG, "iem_halo_fold: not connected (iem_comm_connect)");
   const iem::ShardInfo &si = m->shard;
-  if (si.halo_doubles == 0 || si.world == 1) return IEM_OK;
+  if ((si.halo_doubles == 0 && si.halo_doubles_right == 0) || si.world == 1) return IEM_OK;
   DevGuard dg_(m->device);
   { int rc = halo_flush(m); if (rc) return rc; }
-  struct { double *vec; unsigned long long *mine, *left, *right; const long long *src, *dst; long long NH, W, G, NR; unsigned long long *hstatus; long long ticks; } A = {
+  // IemFoldArgs, and behind it what IemFold2Args adds (iem_halo2_device.h)
+  struct { double *vec; unsigned long long *mine, *left, *right; const long long *src, *dst; long long NH, W, G, NR; unsigned long long *hstatus; long long ticks;
+           const long long *src_l, *dst_r; long long NL, B2; } A = {
       d_vec, m->mailbox, si.rank > 0 ? m->peers[si.rank - 1] : nullptr, si.rank + 1 < si.world ? m->peers[si.rank + 1] : nullptr,
       m->d_halo_src, m->d_halo_dst, (long long)si.halo_doubles, (long long)si.world, (long long)reduce_chunks(1 + m->n_shared),
-      (long long)(1 + m->n_shared), m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL};
-  size_t sz = sizeof A;
+      (long long)(1 + m->n_shared), m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL,
+      m->d_halo_src_l, m->d_halo_dst_r, (long long)si.halo_doubles_right, (long long)mailbox_b2(si.world, si.halo_doubles, 1 + m->n_shared)};
+  size_t sz = m->opt.two_sided ? sizeof A : 12 * 8;
   void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   HIP_TRY(hipModuleLaunchKernel(m->fn_fold, 1, 1, 1, 256, 1, 1, 0, m->stream, nullptr, cfg));
   return IEM_OK;

@@ -113,6 +113,9 @@ struct Options {
   // exchange as one extra leading workgroup (iem_halo_wg).  Set by iem_create_sharded; an unsharded handle's kernels have no
   // such prologue (and no LDS word for it) at all.
   int carrier = 0;
+  // 1: the source carries the two-way halo exchange (iem_halo2_device.h) behind the device header, and the carrier prologue
+  // runs it.  Set by iem_create_sharded for a shard whose stencils reach to the right; the generator itself does not read it.
+  int two_sided = 0;
   int phase_kernels = 1;   // 1: also emit the one-launch-per-solver-phase kernels (KK_TRIAL, KK_ACCEPTED); their member kinds then
                            // always take the bodies-behind-a-dispatcher form, which the phase kernels share
   // jac_coord! of a lane-fused support grid runs as TWO bodies behind the dispatcher, their

@@ -10,8 +10,9 @@
 // stencil, whose index expressions are `group_idx ± const` (transform.jl:471-506, 535-557).
 //
 // Rank r of `world` owns the contiguous block [a, b) of the sharded parameter group's supports.
-//   * x: every slab that runs over the group keeps the WINDOW [a - h, b) of that axis (h = the
-//     stencil's reach to the left, at most `a`); other slabs (finite / first-stage variables,
+//   * x: every slab that runs over the group keeps the WINDOW [a - h, b + hr) of that axis (h = the
+//     stencil's reach to the left, at most `a`; hr = its reach to the right, at most n - b: forward
+//     and central differences); other slabs (finite / first-stage variables,
 //     variables over other parameters) are replicated.  The local x is the concatenation of the
 //     local slabs in the global order; `var_map` gives local -> global.
 //   * theta and every item-data column stay GLOBAL and resident on every rank (read-only,
@@ -27,8 +28,9 @@
 //     cut along the dimension with the largest stride, whole elements at a time; an item belongs to
 //     the rank owning the LAST support it references, the halo covers the first.
 // Supported: templates on support grids (grid hint present) with affine integer fields, stencils
-// that reach to the LEFT only (backward differences, orthogonal collocation) — what the reference's
-// derivative methods emit; and explicit item lists (a domain restriction filters the iterator,
+// that reach to the left (backward differences, orthogonal collocation), to the right (forward
+// differences) or both ways (central differences) — what the reference's
+// derivative methods emit (transform.jl:535: any finite-difference method); and explicit item lists (a domain restriction filters the iterator,
 // transform.jl:448-451) whose variable indices all sit at the item's own support: the list is
 // filtered to the owned supports and every column re-gathered.  Anything else throws with a message
 // (IEM_E_BLOB at the ABI).
@@ -60,13 +62,15 @@ struct ShardInfo {
   int group = 0, rank = 0, world = 1;
   int64_t n_global = 0;     // supports of the sharded group
   int64_t own_lo = 0, own_n = 0, halo = 0;   // global index of the first OWNED support, count, halo supports in front
-  int64_t halo_reach = 0;   // the model's stencil reach (what ranks > 0 carry)
+  int64_t halo_reach = 0;   // the model's stencil reach to the LEFT (what ranks > 0 carry in front)
+  int64_t halo_right = 0, reach_right = 0;   // halo supports BEHIND the owned block, and the model's stencil reach to the right
   int64_t nvar_global = 0, ncon_global = 0, nnzj_global = 0, nnzh_global = 0;
   std::vector<int64_t> var_map;        // local variable -> global variable (0-based)
-  std::vector<unsigned char> var_flag; // bit 0: owned by this rank, bit 1: replicated on every rank, bit 2: halo copy
+  std::vector<unsigned char> var_flag; // bit 0: owned by this rank, bit 1: replicated on every rank, bit 2: halo copy of the LEFT neighbour's (front), bit 3: of the RIGHT neighbour's (back)
   std::vector<ShardTpl> tpl;
   std::vector<HaloSeg> segs;           // sharded slabs, in local order
   int64_t halo_doubles = 0;            // doubles one neighbour sends the next: sum over segs of outer * halo_reach * inner
+  int64_t halo_doubles_right = 0;      // doubles one neighbour sends the PREVIOUS one: sum over segs of outer * reach_right * inner
 };
 
 inline void partition_block(int64_t n, int world, int rank, int64_t &a, int64_t &b) {
@@ -213,7 +217,7 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
   std::vector<int64_t> gm(nt, 0), ganchor(nt, 0);   // its stride in supports, and the last referenced support at item 0
   std::vector<char> explicit_tpl(nt, 0);
   std::vector<std::vector<Walk>> walks(nt);
-  int64_t reach = 0;
+  int64_t reach = 0, reach_r = 0;
   for (size_t ti = 0; ti < nt; ++ti) {
     const Template &t = m.tpl[ti];
     std::vector<char> is_var(t.idx.size(), 0);
@@ -245,8 +249,8 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
         }
         if (w.m[sdim[ti]][ax] == 1) {
           const int64_t shift = w.i0[ax] - t.origin[sdim[ti]];   // slab coordinate minus the item's own support
-          if (shift > 0) throw std::runtime_error("template " + std::to_string(ti) + ": stencils that reach to the right of their support are not supported (backward differences only)");
           reach = std::max(reach, -shift);
+          reach_r = std::max(reach_r, shift);
         }
         continue;
       }
@@ -282,10 +286,10 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
       reach = std::max(reach, a_max - c_min);
     }
   }
-  info.halo_reach = reach;
-  const int64_t h = std::min(reach, a0);
-  info.halo = h;
-  const int64_t wlo = a0 - h, wn = b0 - a0 + h;
+  info.halo_reach = reach; info.reach_right = reach_r;
+  const int64_t h = std::min(reach, a0), hr = std::min(reach_r, ng - b0);
+  info.halo = h; info.halo_right = hr;
+  const int64_t wlo = a0 - h, wn = b0 - a0 + h + hr;
 
   // local slabs, variable map
   std::vector<Slab> ls(m.slabs.size());
@@ -309,7 +313,7 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
           if (ax >= 0) gi[ax] += wlo;
           const int64_t lv = l.off + i0 + l.dims[0] * (i1 + l.dims[1] * i2);
           info.var_map[(size_t)lv] = g.off + gi[0] + g.dims[0] * (gi[1] + g.dims[1] * gi[2]);
-          info.var_flag[(size_t)lv] = ax < 0 ? (unsigned char)(2 | (rank == 0 ? 1 : 0)) : (li[ax] >= h ? 1 : 4);
+          info.var_flag[(size_t)lv] = ax < 0 ? (unsigned char)(2 | (rank == 0 ? 1 : 0)) : (li[ax] < h ? 4 : li[ax] < h + (b0 - a0) ? 1 : 8);
         }
     if (ax >= 0) {
       HaloSeg sg;
@@ -318,6 +322,7 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
       for (int e = ax + 1; e < 3; ++e) sg.outer *= l.dims[e];
       info.segs.push_back(sg);
       info.halo_doubles += sg.outer * reach * sg.inner;
+      info.halo_doubles_right += sg.outer * reach_r * sg.inner;
     }
   }
 
@@ -480,6 +485,9 @@ inline void shard_model(Model &m, int group, int rank, int world, ShardInfo &inf
       for (FieldDesc &f : t.ffields) f.base += f.step[d] * lo;
       t.dims[d] = std::max<int64_t>(hi - lo, 0);
       if (sdim[ti] >= 0) t.origin[d] = t.origin[d] + lo - wlo;   // grid coordinate inside the local window
+      // a box recovered from a foreign producer's / a domain restriction's flat list (recover_lattice) goes out WITHOUT its
+      // synthesised grid hint (serialize_model): its origin on that grid must go too — a hint-less box starts at its corner
+      else if (t.lattice_recovered) t.origin[0] = t.origin[1] = t.origin[2] = 0;
       t.n_items = t.dims[0] * t.dims[1] * t.dims[2];
     } else {
       // not over the sharded group: the rank that owns the supports of its point variables, else rank 0

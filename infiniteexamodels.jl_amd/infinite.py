@@ -355,15 +355,21 @@ class InfiniteModel:
         self._ready = False
         return v
 
-    def deriv(self, arg, pref: InfiniteParameterRef) -> DerivativeRef:
-        """``∂(y, t)`` (first order; repeated calls return the same derivative)."""
-        for d in self.derivatives:
-            if d.arg is arg and d.pref is pref:
-                return d
-        d = DerivativeRef(self, f"∂({arg!r},{pref!r})", arg, pref, VarInfo())
-        self.derivatives.append(d)
-        self._ready = False
-        return d
+    def deriv(self, arg, pref: InfiniteParameterRef, *more_prefs: InfiniteParameterRef) -> DerivativeRef:
+        """``∂(y, t)``; ``deriv(y, x, x)`` is ``deriv(deriv(y, x), x)``: every further parameter nests one more
+        first-order derivative with a variable slab and approximation rows of its own — what
+        ``reformulate_high_order_derivatives!`` leaves behind (transform.jl:141-142).  Repeated calls return the
+        same objects."""
+        d = None
+        for e in self.derivatives:
+            if e.arg is arg and e.pref is pref:
+                d = e
+                break
+        if d is None:
+            d = DerivativeRef(self, f"∂({arg!r},{pref!r})", arg, pref, VarInfo())
+            self.derivatives.append(d)
+            self._ready = False
+        return self.deriv(d, *more_prefs) if more_prefs else d
 
     def _semi(self, ivref, args) -> SemiInfiniteVariableRef:
         for s in self.semi_infinite_variables:

@@ -192,6 +192,13 @@ function MI355XShardedModel(core, backend::MI355XBackend, group::Int, rank::Int,
     check(ccall((:iem_comm_connect, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{UInt8}), h[], allgather(mine)))
     return h[]                                             # wrap like MI355XModel(core, backend) (meta from iem_meta)
 end
+# both directions of the halo: (halo_left, halo_right, reach_left, reach_right, doubles_to_right, doubles_to_left); a model with
+# forward / central differences (transform.jl:535: any finite-difference method) has reach_right > 0 and exchanges both ways
+function shard_halo(m::MI355XModel)
+    out = Vector{Int64}(undef, 6)
+    check(ccall((:iem_shard_halo, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int64}), m.handle, out))
+    return (halo_left = out[1], halo_right = out[2], reach_left = out[3], reach_right = out[4], doubles_to_right = out[5], doubles_to_left = out[6])
+end
 # before cons!/jac_coord!/hess_coord!: the stencil neighbours x_k[a_r - 1] from the left rank (transform.jl:535-557)
 halo_exchange!(m::MI355XModel, x::ROCVector{Float64}) =
     (check(ccall((:iem_halo_exchange, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}), m.handle, dptr(x))); x)

@@ -81,7 +81,7 @@ class KernelInfo(C.Structure):
 
 
 # every symbol include/iem.h declares (tests check the export list against the header)
-SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_info", "iem_shard_var_map", "iem_shard_template_info",
+SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_info", "iem_shard_halo", "iem_shard_var_map", "iem_shard_template_info",
            "iem_shard_template_items", "iem_shard_blob", "iem_comm_export", "iem_comm_connect", "iem_halo_exchange", "iem_halo_exchange_async", "iem_halo_wait", "iem_halo_reads", "iem_halo_fold", "iem_allreduce_obj_grad", "iem_comm_status",
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
@@ -94,7 +94,7 @@ def build_library(force: bool = False) -> str:
     """Compile ``libiem_hip.so`` in-tree (host C++; links libamdhip64 + libhiprtc)."""
     src_dir = os.path.join(_HERE, "csrc")
     newest = max(os.path.getmtime(os.path.join(src_dir, f)) for f in os.listdir(src_dir)
-                 if f.endswith((".cpp", ".hpp", ".h")) and f != "iem_device_h.inc")
+                 if f.endswith((".cpp", ".hpp", ".h", "Makefile")))
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < newest:
         subprocess.check_call(["make", "-C", src_dir, "-s"])
     return LIB_PATH
@@ -125,6 +125,7 @@ def lib():
     L.iem_create_sharded.argtypes = [C.c_char_p, C.c_size_t, i32, i32, i32, i32, C.POINTER(Option), i32, C.POINTER(vp)]
     L.iem_shard_info.argtypes = [vp, C.POINTER(ShardT)]
     L.iem_shard_var_map.argtypes = [vp, vp, vp]
+    L.iem_shard_halo.argtypes = [vp, C.POINTER(C.c_int64 * 6)]
     L.iem_shard_template_info.argtypes = [vp, i64, C.POINTER(ShardTemplate)]
     L.iem_shard_blob.argtypes = [C.c_char_p, C.c_size_t, i32, i32, i32, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(ShardT),
                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
@@ -204,7 +205,7 @@ def set_option(name: str, value: int):
 OPTION_DEFAULTS = dict(store_mode=2, nt_stores=1, block=0, lds_slots=24, reorder=1, no_fuse=0, hess_merge=0, ablate=0,
                        min_waves=0, fp_contract=0, fuse_zero=1, fuse_groups=1, split_small=64, poll_obj=1, xcd_remap=0, overlap=1, wide_stores=1, obj_wgs=1024, det_shared=1, flat2d=0, flush32=2, autotune=0, autotune_min_blocks=400, pull_scatter=1, fold_colloc=2, fold_max_n=6, det_axis=1, det_scatter=1, det_scatter_max=1 << 28, lazy_loads=2, lazy_min_loads=48, lazy_all_kinds=0, name_tag=0,
                        big_batch_slots=48, big_batch_jac=4000, big_batch_hess=4000, big_xcd=1, big_tile=1024, pair_kernel=1, store_wait=0, comm_timeout_ms=5000,
-                       carrier=0, phase_kernels=1, jac_split=1, cons_direct_2d=1, digit_fields=1)
+                       carrier=0, two_sided=0, phase_kernels=1, jac_split=1, cons_direct_2d=1, digit_fields=1)
 
 
 def option_array(opts: dict):
@@ -388,7 +389,10 @@ def shard_blob(blob: bytes, group: int, rank: int, world: int):
     finally:
         for p in (ob, vm, vf, tp, it):
             L.iem_free(p)
-    return local, info.asdict(), var_map, var_flag, tpl
+    d = info.asdict()
+    # the back halo, as the flags tell it (iem_shard_t keeps its layout: halo / halo_reach / halo_doubles are the front one)
+    d["halo_right_vars"] = int(((var_flag & 8) != 0).sum())
+    return local, d, var_map, var_flag, tpl
 
 
 def precompile(blob: bytes, arch: str = "gfx950", force: bool = False, defer: list = None) -> str:

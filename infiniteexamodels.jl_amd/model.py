@@ -439,8 +439,16 @@ class ExaModel:
         _lib.check(self._L.iem_shard_info(self._h, C.byref(t)))
         return t.asdict()
 
+    def shard_halo(self) -> dict:
+        """Both directions of the halo (``iem_shard_halo``): halo supports in front of / behind the owned block, the
+        model's stencil reach to the left / right, the doubles one rank sends its right / left neighbour per exchange."""
+        out = (C.c_int64 * 6)()
+        _lib.check(self._L.iem_shard_halo(self._h, C.byref(out)))
+        return dict(zip(("halo_left", "halo_right", "reach_left", "reach_right", "doubles_to_right", "doubles_to_left"), map(int, out)))
+
     def shard_var_map(self):
-        """``(local -> global variable, flags)``; flag bit 0 owned here, bit 1 replicated, bit 2 halo copy."""
+        """``(local -> global variable, flags)``; flag bit 0 owned here, bit 1 replicated, bit 2 halo copy of the left
+        neighbour's variable (front), bit 3 of the right neighbour's (back)."""
         vm = np.zeros(max(self.meta.nvar, 1), dtype=np.int64)
         vf = np.zeros(max(self.meta.nvar, 1), dtype=np.uint8)
         _lib.check(self._L.iem_shard_var_map(self._h, vm.ctypes.data, vf.ctypes.data))
@@ -470,7 +478,8 @@ class ExaModel:
         _lib.check(self._L.iem_comm_connect(self._h, handles))
 
     def halo_exchange(self, x):
-        """Fill the halo entries of the local ``x`` from the left neighbour (and send mine right);
+        """Fill the halo entries of the local ``x`` from the left neighbour (and send mine right) — and, for a model
+        whose stencils reach to the right, the back halo entries from the right neighbour in the same kernel;
         asynchronous on the current stream."""
         self._chk(x, self.meta.nvar, "x")
         self._sync_stream()
@@ -502,7 +511,8 @@ class ExaModel:
 
     def halo_fold(self, vec):
         """Transposed halo exchange for a variable-space vector (``jtprod`` of this rank's rows): halo-copy
-        entries are added to the left neighbour's owned entries and zeroed here; asynchronous."""
+        entries are added to the owning neighbour's entries (front copies: the left one's, back copies: the right
+        one's; an entry takes the left neighbour's addend first) and zeroed here; asynchronous."""
         self._chk(vec, self.meta.nvar, "vec")
         self._sync_stream()
         _lib.check(self._L.iem_halo_fold(self._h, _ptr(vec)))

@@ -41,7 +41,7 @@ class ShardSpec:
     rank: int
     world: int
     own_lo: int                 # local index of the first owned support (= halo actually present)
-    own_n: int                  # number of owned supports
+    own_n: int                  # number of owned supports (local supports behind them: the back halo)
     global_lo: int              # global index of the first LOCAL support (window start)
     n_global: int
     coeffs: Optional[np.ndarray] = None   # measure coefficients of the LOCAL supports from the global grid
@@ -66,16 +66,17 @@ def trapezoid_weights(s: np.ndarray) -> np.ndarray:
     return c
 
 
-def window(supports: np.ndarray, rank: int, world: int, halo: int, measure: str = "trapezoid"):
-    """Local support window of ``rank`` and its :class:`ShardSpec` fields."""
+def window(supports: np.ndarray, rank: int, world: int, halo: int, measure: str = "trapezoid", halo_right: int = 0):
+    """Local support window of ``rank`` and its :class:`ShardSpec` fields (``halo_right``: supports kept BEHIND the
+    owned block, for stencils that reach to the right — forward and central differences)."""
     n = len(supports)
     a, b = partition(n, world)[rank]
-    h = min(halo, a)
+    h, hr = min(halo, a), min(halo_right, n - b)
     if measure == "trapezoid":
         cg = trapezoid_weights(supports)
     else:
         cg = np.full(n, 1.0 / n)
-    return supports[a - h:b], dict(own_lo=h, own_n=b - a, global_lo=a - h, n_global=n, coeffs=cg[a - h:b].copy())
+    return supports[a - h:b + hr], dict(own_lo=h, own_n=b - a, global_lo=a - h, n_global=n, coeffs=cg[a - h:b + hr].copy())
 
 
 def quadrotor_shard(S_global: int, rank: int, world: int, backend=None):
@@ -174,7 +175,7 @@ class ShardMaps:
             lflat = np.ravel_multi_index(tuple(lidx), lshape, order="F")
             gflat = np.ravel_multi_index(tuple(gidx), gshape, order="F")
             self.var_map[lvar.offset + lflat] = gvar.offset + gflat
-            self.var_owned[lvar.offset + lflat] = lidx[ax] >= spec.own_lo
+            self.var_owned[lvar.offset + lflat] = (lidx[ax] >= spec.own_lo) & (lidx[ax] < spec.own_lo + spec.own_n)
         assert (self.var_map >= 0).all()
         # templates -------------------------------------------------------------------
         gt = {t.tag: t for t in glob.templates}
@@ -251,7 +252,8 @@ class ShardLayout:
     def __init__(self, var_map, var_flag, templates, ncon: int, nnzj: int, nnzh: int):
         self.var_map = np.asarray(var_map)
         f = np.asarray(var_flag)
-        self.owned, self.replicated, self.halo = (f & 1) != 0, (f & 2) != 0, (f & 4) != 0
+        self.owned, self.replicated, self.halo = (f & 1) != 0, (f & 2) != 0, (f & 12) != 0   # halo: either side
+        self.halo_left, self.halo_right = (f & 4) != 0, (f & 8) != 0
         self.row_map = np.full(ncon, -1, dtype=np.int64)
         self.jac_pos = np.full(nnzj, -1, dtype=np.int64)
         self.hess_pos = np.full(nnzh, -1, dtype=np.int64)
@@ -333,22 +335,32 @@ class ShardComm:
         self.why = errs[0] if errs else ""
         if self.kind == "own":
             return
-        # fallback plan: who sends what to whom (halo copies are the left neighbour's LAST owned supports)
+        # fallback plan: who sends what to whom (front halo copies are the left neighbour's LAST owned supports, back
+        # halo copies — stencils that reach to the right — the right neighbour's FIRST)
         vm, vf = gm.shard_var_map()
         info = gm.shard_info()
-        halo = (vf & 4) != 0
+        halo, back = (vf & 4) != 0, (vf & 8) != 0
         self._dst = np.nonzero(halo)[0].astype(np.int64)
+        self._dst_r = np.nonzero(back)[0].astype(np.int64)
         wanted = [None] * self.world
-        dist.all_gather_object(wanted, vm[halo].astype(np.int64))
+        dist.all_gather_object(wanted, (vm[halo].astype(np.int64), vm[back].astype(np.int64)))
         self._left = self.rank - 1 if self.rank > 0 and self._dst.size else None
         self._right, self._src = None, np.zeros(0, np.int64)
-        if self.rank + 1 < self.world and wanted[self.rank + 1].size:
-            order = np.argsort(vm, kind="stable")
-            pos = np.searchsorted(vm[order], wanted[self.rank + 1])
+        self._from_right = self.rank + 1 if self.rank + 1 < self.world and self._dst_r.size else None
+        self._to_left, self._src_l = None, np.zeros(0, np.int64)
+        order = np.argsort(vm, kind="stable")
+
+        def owned_positions(want, who):
+            pos = np.searchsorted(vm[order], want)
             src = order[np.minimum(pos, vm.size - 1)]
-            if not (np.array_equal(vm[src], wanted[self.rank + 1]) and ((vf[src] & 1) != 0).all()):
-                raise RuntimeError("ShardComm: the right neighbour's halo copies are not all owned by this rank")
-            self._right, self._src = self.rank + 1, src.astype(np.int64)
+            if not (np.array_equal(vm[src], want) and ((vf[src] & 1) != 0).all()):
+                raise RuntimeError(f"ShardComm: the {who} neighbour's halo copies are not all owned by this rank")
+            return src.astype(np.int64)
+
+        if self.rank + 1 < self.world and wanted[self.rank + 1][0].size:
+            self._right, self._src = self.rank + 1, owned_positions(wanted[self.rank + 1][0], "right")
+        if self.rank > 0 and wanted[self.rank - 1][1].size:
+            self._to_left, self._src_l = self.rank - 1, owned_positions(wanted[self.rank - 1][1], "left")
         self._shared = np.nonzero((vf & 2) != 0)[0].astype(np.int64)
         self._n_shared = int(info["n_shared"])
         self._bufs = {}
@@ -360,6 +372,7 @@ class ShardComm:
             t = self._torch
             mk = lambda a: t.as_tensor(a, device=ref.device)
             self._bufs[key] = dict(src=mk(self._src), dst=mk(self._dst), shared=mk(self._shared),
+                                   src_l=mk(self._src_l), dst_r=mk(self._dst_r),
                                    send=t.empty(self._src.size, dtype=t.float64, device=ref.device),
                                    recv=t.empty(self._dst.size, dtype=t.float64, device=ref.device),
                                    red=t.empty(1 + self._shared.size, dtype=t.float64, device=ref.device))
@@ -381,12 +394,54 @@ class ShardComm:
         if self._left is not None:
             recv = self._torch.empty(b["recv"].shape, dtype=b["recv"].dtype) if stage else b["recv"]
             ops.append(dist.P2POp(dist.irecv, recv, self._left))
+        # the second direction (stencils that reach to the right): my first owned supports go left
+        send_l = recv_r = None
+        if self._to_left is not None:
+            send_l = x[b["src_l"]].cpu() if stage else x[b["src_l"]].contiguous()
+            ops.append(dist.P2POp(dist.isend, send_l, self._to_left))
+        if self._from_right is not None:
+            recv_r = self._torch.empty(self._dst_r.size, dtype=x.dtype, device="cpu" if stage else x.device)
+            ops.append(dist.P2POp(dist.irecv, recv_r, self._from_right))
         if ops:
             for r in dist.batch_isend_irecv(ops):
                 r.wait()
         if self._left is not None:
             x[b["dst"]] = recv.to(x.device) if stage else recv
+        if self._from_right is not None:
+            x[b["dst_r"]] = recv_r.to(x.device)
         return x
+
+    def halo_fold(self, vec):
+        """The transposed exchange (``iem_halo_fold``) for a variable-space vector of this rank's rows (``jtprod!``): front
+        halo copies are added to the left neighbour's owned entries, back halo copies to the right neighbour's, both are
+        zeroed here; an owned entry takes the left neighbour's addend first, then the right neighbour's."""
+        if self.kind == "own":
+            return self.gm.halo_fold(vec)
+        b, dist, ops = self._dev(vec), self.dist, []
+        stage = vec.is_cuda and dist.get_backend() == "gloo"
+        host = (lambda t: t.cpu()) if stage else (lambda t: t.contiguous())
+        empty = lambda n: self._torch.empty(n, dtype=vec.dtype, device="cpu" if stage else vec.device)
+        from_l = from_r = None
+        if self._left is not None:            # my front copies -> the left neighbour
+            ops.append(dist.P2POp(dist.isend, host(vec[b["dst"]]), self._left))
+        if self._from_right is not None:      # my back copies -> the right neighbour
+            ops.append(dist.P2POp(dist.isend, host(vec[b["dst_r"]]), self._from_right))
+        if self._to_left is not None:
+            from_l = empty(self._src_l.size)
+            ops.append(dist.P2POp(dist.irecv, from_l, self._to_left))
+        if self._right is not None:
+            from_r = empty(self._src.size)
+            ops.append(dist.P2POp(dist.irecv, from_r, self._right))
+        if ops:
+            for r in dist.batch_isend_irecv(ops):
+                r.wait()
+        vec[b["dst"]] = 0.0
+        vec[b["dst_r"]] = 0.0
+        if from_l is not None:
+            vec[b["src_l"]] += from_l.to(vec.device)
+        if from_r is not None:
+            vec[b["src"]] += from_r.to(vec.device)
+        return vec
 
     def allreduce_obj_grad(self, obj_dev, g):
         """Sum of the scalar objective (1-element tensor, may be ``None``) and of the replicated entries of ``g`` over

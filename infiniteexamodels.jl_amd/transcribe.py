@@ -586,11 +586,11 @@ def _add_derivative_approximations(core: ExaCore, data: ExaMappingData, m: Infin
                 pref_itr = pref_itr.with_float(a, col)
         sp = _shard(m)
         if sp is not None and sp.group_index == pref_group:
-            # the window carries the stencil halo, so every local row of a backward difference
-            # belongs to an owned support
-            if method[0] != "fd_backward":
-                raise NotImplementedError("sharding along a parameter supports backward differences only")
-            keep = idxs >= sp.own_lo
+            # the window carries the stencil halo on the side(s) the method reaches to (shard.window: halo in front for
+            # backward, behind for forward, both for central differences), so every local row belongs to an owned support
+            if method[0] not in ("fd_backward", "fd_forward", "fd_central"):
+                raise NotImplementedError("sharding along a parameter supports finite differences only")
+            keep = (idxs >= sp.own_lo) & (idxs < sp.own_lo + sp.own_n)
             assert keep.all(), "halo does not cover the stencil"
         if _rank0_only(group_idxs, m):
             continue

@@ -326,3 +326,25 @@ def kinetic_control(num_supports: int = 100, backend=None) -> InfiniteModel:
     im.constraint(im.deriv(c[2], t) == r2)
     im.constant_over_collocation(T, t)
     return im
+
+
+def heat(nt: int = 12, nx: int = 9, method_x: str = "central", kappa: float = 0.1, backend=None) -> InfiniteModel:
+    """Distributed control of the 1-D heat equation ``∂y/∂t = κ ∂²y/∂x² + u`` on ``(t, x) ∈ [0, 1]²`` — the PDE form of
+    what ``/root/reference/src/transform.jl:141`` (``reformulate_high_order_derivatives!``) and ``:535``
+    (``derivative_expr_data`` with any finite-difference method) transcribe; the reference's own structural test builds
+    the second derivative the same way (``test/transcription.jl:20``).  ``t`` uses backward differences, ``x`` the
+    method ``method_x`` ("central", "forward" or "backward"); the second derivative is the nested first-order form."""
+    im = InfiniteModel(backend)
+    t = im.infinite_parameter("t", 0.0, 1.0, num_supports=nt)
+    x = im.infinite_parameter("x", 0.0, 1.0, num_supports=nx, derivative_method=io.FiniteDifference(method_x))
+    y = im.variable("y", t, x)
+    u = im.variable("u", t, x, lb=-5.0, ub=5.0, start=0.0)
+    target = im.parameter_function("target", lambda t, x: np.sin(np.pi * x) * t, t, x)
+    # the PDE on the interior of x (the boundary values of ∂²y/∂x² have no approximation row)
+    interior = io.DomainRestriction(lambda s: (s > 0.0) & (s < 1.0), x)
+    im.constraint(im.deriv(y, t) == kappa * im.deriv(y, x, x) + u, restriction=interior, name="pde")
+    im.constraint(y(t, 0) == 0, name="left")                     # Dirichlet boundaries: semi-infinite constraints
+    im.constraint(y(t, 1) == 0, name="right")
+    im.constraint(y(0, x) == 0, name="initial")
+    im.objective("min", im.integral(im.integral((y - target) ** 2 + 0.01 * u ** 2, t), x))   # (t innermost: the item box runs like the slabs)
+    return im
