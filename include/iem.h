@@ -253,6 +253,30 @@ int iem_jprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jv);
 int iem_jtprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jtv);
 int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *d_v, double obj_weight, double *d_Hv);
 
+/* parameter sensitivities: the same three products with d/dθ in place of d/dx, at (x, the handle's current θ — after any
+ * iem_set_parameter), L = obj_weight*f + y'c:
+ *   iem_jpprod    (dc/dθ) w                        w: npar, out: ncon
+ *   iem_jptprod   obj_weight df/dθ + (dc/dθ)' y    y: ncon, out: npar
+ *   iem_hpprod    (d2L/dx dθ) w                    w: npar, out: nvar
+ * The right-hand side of the first-order parameter step  K [dx; dy] = -[hpprod(δθ); jpprod(δθ)].  One fused kernel per
+ * call (plus the deterministic follow-ups of the scatter kinds: no float atomics, bitwise reproducible), the caller's
+ * device pointers, outputs fully overwritten, asynchronous on the handle's stream.  Their kernels are a program of their
+ * own, generated and loaded by the first such call (iem_kernel_info lists them behind the model's own kernels from then
+ * on, kinds 5 / 6 / 7 with names iem_jpprod* / iem_jptprod* / iem_hpprod*).  npar == 0: jpprod and hpprod write zeros,
+ * jptprod (a zero-length output) launches nothing.  A sharded handle refuses all three with IEM_E_ARG: θ is replicated on
+ * every rank, the products would need an all-reduce.
+ * THE FIRST CALL of any of them on a handle sets the program up: it generates the kernels, loads their code object (the
+ * cache, else a hiprtc build that can take seconds), allocates and uploads their tables.  That call is therefore
+ * synchronous and must not run inside a stream capture; every later call is asynchronous and capturable like the x-kinds.
+ * iem_param_prepare does that set-up explicitly (warm up with it before a capture or a timed loop; idempotent) and returns
+ * the number of the program's kernels: iem_kernel_info answers for the indices meta.n_kernels .. meta.n_kernels + that
+ * number - 1 from then on.  A model the generator refuses stays refused; a runtime failure of the set-up (out of memory, a
+ * failed build) is not remembered, the next call tries again. */
+int iem_param_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_jpprod(iem_model *m, const double *d_x, const double *d_w, double *d_out);
+int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out);
+int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out);
+
 /* jac_structure! / hess_structure! — one-off; `base` = 1 for Julia, 0 for C/Python.
  * Hessian pairs are lower-triangular (row >= col); COO may repeat positions. */
 int iem_jac_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base);

@@ -112,6 +112,23 @@ class ExaTranscriptionBackend:
             return False
         return True
 
+    def parameter_direction(self, pref, value) -> np.ndarray:
+        """δθ of length ``npar``: by how much ``update_parameter_value(pref, value)`` WOULD change θ — a finite parameter
+        takes a scalar, a parameter function is evaluated over its supports; the entries of every other parameter are
+        zero.  θ, the model and ``pref`` stay as they are.  The direction ``sensitivity.parameter_step`` takes."""
+        if self.core is None or pref not in self.data.param_mappings:
+            raise KeyError("parameter_direction: not a transcribed finite parameter or parameter function")
+        par = self.data.param_mappings[pref]
+        out = np.zeros(self.core.npar)
+        if isinstance(pref, FiniteParameterRef):
+            vals = np.array([float(value)])
+        elif isinstance(pref, ParameterFunctionRef):
+            vals = np.asarray(transcribe._eval_over_supports(value, self._inf_model, pref.group_idxs, par.size), dtype=np.float64).reshape(-1, order="F")
+        else:
+            raise KeyError("parameter_direction: not a finite parameter or parameter function")
+        out[par.offset:par.offset + par.length] = vals - self.core.theta[par.offset:par.offset + par.length]
+        return out
+
     def update_start_value(self, vref, value) -> bool:
         """``InfiniteOpt.update_variable_info`` start-value branch (:553-592): writes ``core.x0``."""
         if self.core is None:

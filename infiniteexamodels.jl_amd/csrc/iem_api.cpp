@@ -223,6 +223,16 @@ struct iem_model {
   std::vector<double> theta_host;
   bool jit = false;
   std::vector<std::pair<int64_t, int64_t>> zero_ranges[iem::KK_COUNT];  // per scatter kind: [lo, hi) of the output its kernels do not overwrite
+  // The parameter kinds (iem_jpprod / iem_jptprod / iem_hpprod; Options::param_kinds): a program of their own with its own
+  // scatter buffers, generated and loaded by the first such call — the model's program and its cache key do not know of it.
+  struct ParamKinds {
+    bool tried = false;
+    int rc = IEM_OK;
+    std::string err;
+    CodeObject code;
+    double *d_red[iem::KK_COUNT] = {};
+    long long *d_axis[iem::KK_COUNT] = {}, *d_gather[iem::KK_COUNT] = {};
+  } par;
 };
 
 namespace {
@@ -459,22 +469,59 @@ int halo_plan(iem_model *m, int kind, const void *x, const void *v, bool *carry)
 }
 
 // what runs BEHIND the kernels of a scatter kind (also behind the one-launch phases that contain grad!)
-int kind_followups(iem_model *m, int kind, double *out, double *aux) {
-  if (!m->code.prog.axis[kind].empty()) {   // sums over a non-lane axis: the rows the kernels parked -> one write per entry (iem_axis_sum_kernel)
+int kind_followups(iem_model *m, const iem::Program &prog, long long *const *d_axis, long long *const *d_gather, int kind, double *out, double *aux) {
+  if (!prog.axis[kind].empty()) {   // sums over a non-lane axis: the rows the kernels parked -> one write per entry (iem_axis_sum_kernel)
     int64_t n0 = 1;
-    for (auto &a : m->code.prog.axis[kind]) n0 = std::max(n0, a.n0);
-    void *args[] = {(void *)&out, (void *)&aux, (void *)&m->d_axis[kind]};
-    HIP_TRY(hipModuleLaunchKernel(m->fn_axis, (unsigned)((n0 + 63) / 64), (unsigned)m->code.prog.axis[kind].size(), 1, 256, 1, 1, 0, m->stream, args, nullptr));   // 64 lanes x 4 row groups per workgroup
+    for (auto &a : prog.axis[kind]) n0 = std::max(n0, a.n0);
+    void *args[] = {(void *)&out, (void *)&aux, (void *)&d_axis[kind]};
+    HIP_TRY(hipModuleLaunchKernel(m->fn_axis, (unsigned)((n0 + 63) / 64), (unsigned)prog.axis[kind].size(), 1, 256, 1, 1, 0, m->stream, args, nullptr));   // 64 lanes x 4 row groups per workgroup
   }
-  if (!m->code.prog.gather[kind].dest.empty()) {   // what would have been float atomics: parked addends summed per entry in plan order
-    const iem::Program::Gather &G = m->code.prog.gather[kind];
+  if (!prog.gather[kind].dest.empty()) {   // what would have been float atomics: parked addends summed per entry in plan order
+    const iem::Program::Gather &G = prog.gather[kind];
     long long n = (long long)G.dest.size();
     const double *parked = aux + G.aux_off;
-    const long long *dest = m->d_gather[kind], *seg = dest + n;
+    const long long *dest = d_gather[kind], *seg = dest + n;
     const void *perm = seg + n + 1;
     int wide = G.park_doubles >= (1LL << 32) ? 1 : 0;
     void *args[] = {(void *)&out, (void *)&parked, (void *)&dest, (void *)&seg, (void *)&perm, (void *)&n, (void *)&wide};
     HIP_TRY(hipModuleLaunchKernel(m->fn_gather, (unsigned)((n + 255) / 256), 1, 1, 256, 1, 1, 0, m->stream, args, nullptr));
+  }
+  return IEM_OK;
+}
+int kind_followups(iem_model *m, int kind, double *out, double *aux) {
+  return kind_followups(m, m->code.prog, m->d_axis, m->d_gather, kind, out, aux);
+}
+
+// device buffers of a program's scatter kinds: the aux buffer (shared-entry values x workgroups + ticket words, zeroed once,
+// then the rows of its axis sums and the parked addends), the plan of its gather, the table of its axis sums
+// `on_stream`: zero the aux buffers on that stream (a program set up between launches of a running handle) instead of
+// with a plain hipMemset (handle creation)
+int scatter_buffers(const iem::Program &prog, double **d_red, long long **d_gather, long long **d_axis, const hipStream_t *on_stream = nullptr) {
+  for (int kind = 0; kind < iem::KK_COUNT; ++kind) {
+    const size_t words = (size_t)prog.aux_doubles[kind];
+    if (words == 0) continue;
+    if (hipMalloc((void **)&d_red[kind], words * 8) != hipSuccess ||
+        (on_stream ? hipMemsetAsync(d_red[kind], 0, words * 8, *on_stream) : hipMemset(d_red[kind], 0, words * 8)) != hipSuccess)
+      return fail(IEM_E_HIP, "hipMalloc reduction buffer");
+    if (!prog.gather[kind].dest.empty()) {
+      const iem::Program::Gather &G = prog.gather[kind];
+      const size_t nd = G.dest.size(), np = G.perm.size();
+      const bool wide = G.park_doubles >= (1LL << 32);   // parked positions fit 32 bits otherwise: half the plan traffic
+      std::vector<uint32_t> p32;
+      if (!wide) { p32.resize(np); for (size_t k = 0; k < np; ++k) p32[k] = (uint32_t)G.perm[k]; }
+      if (hipMalloc((void **)&d_gather[kind], (2 * nd + 1) * 8 + np * (wide ? 8 : 4)) != hipSuccess ||
+          hipMemcpy(d_gather[kind], G.dest.data(), nd * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(d_gather[kind] + nd, G.seg.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(d_gather[kind] + 2 * nd + 1, wide ? (const void *)G.perm.data() : (const void *)p32.data(), np * (wide ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(IEM_E_HIP, "hipMalloc gather plan");
+    }
+    if (!prog.axis[kind].empty()) {
+      std::vector<long long> tab;
+      for (auto &a : prog.axis[kind]) { tab.push_back(a.c); tab.push_back(a.k0); tab.push_back(a.n0); tab.push_back(a.rows); tab.push_back(a.off); }
+      if (hipMalloc((void **)&d_axis[kind], tab.size() * 8) != hipSuccess ||
+          hipMemcpy(d_axis[kind], tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(IEM_E_HIP, "hipMalloc axis-sum table");
+    }
   }
   return IEM_OK;
 }
@@ -842,6 +889,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
+  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -975,6 +1023,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   if (device < 0 || device >= ndev) return fail(IEM_E_ARG, "device ordinal out of range");
   iem_model *m = new iem_model();
   m->device = device;
+  hopt.param_kinds = 0;   // (the handle's own program; the parameter kinds are a second one, iem_model::par)
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1014,32 +1063,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
     if (hipMalloc((void **)&m->d_partials, words * 8) != hipSuccess || hipMemset(m->d_partials, 0, words * 8) != hipSuccess)
       return bail(fail(IEM_E_HIP, "hipMalloc partials"));
   }
-  for (int kind = 0; kind < iem::KK_COUNT; ++kind) {
-    // aux buffer of a scatter kind: shared-entry values x workgroups + ticket words (zeroed once), then the rows of its axis sums
-    const size_t words = (size_t)m->code.prog.aux_doubles[kind];
-    if (words == 0) continue;
-    if (hipMalloc((void **)&m->d_red[kind], words * 8) != hipSuccess || hipMemset(m->d_red[kind], 0, words * 8) != hipSuccess)
-      return bail(fail(IEM_E_HIP, "hipMalloc reduction buffer"));
-    if (!m->code.prog.gather[kind].dest.empty()) {
-      const iem::Program::Gather &G = m->code.prog.gather[kind];
-      const size_t nd = G.dest.size(), np = G.perm.size();
-      const bool wide = G.park_doubles >= (1LL << 32);   // parked positions fit 32 bits otherwise: half the plan traffic
-      std::vector<uint32_t> p32;
-      if (!wide) { p32.resize(np); for (size_t k = 0; k < np; ++k) p32[k] = (uint32_t)G.perm[k]; }
-      if (hipMalloc((void **)&m->d_gather[kind], (2 * nd + 1) * 8 + np * (wide ? 8 : 4)) != hipSuccess ||
-          hipMemcpy(m->d_gather[kind], G.dest.data(), nd * 8, hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(m->d_gather[kind] + nd, G.seg.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(m->d_gather[kind] + 2 * nd + 1, wide ? (const void *)G.perm.data() : (const void *)p32.data(), np * (wide ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(IEM_E_HIP, "hipMalloc gather plan"));
-    }
-    if (!m->code.prog.axis[kind].empty()) {
-      std::vector<long long> tab;
-      for (auto &a : m->code.prog.axis[kind]) { tab.push_back(a.c); tab.push_back(a.k0); tab.push_back(a.n0); tab.push_back(a.rows); tab.push_back(a.off); }
-      if (hipMalloc((void **)&m->d_axis[kind], tab.size() * 8) != hipSuccess ||
-          hipMemcpy(m->d_axis[kind], tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-        return bail(fail(IEM_E_HIP, "hipMalloc axis-sum table"));
-    }
-  }
+  if ((rc = scatter_buffers(m->code.prog, m->d_red, m->d_gather, m->d_axis)) != IEM_OK) return bail(rc);
   if (hipHostMalloc((void **)&m->h_obj, 16, hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer((void **)&m->d_hobj, m->h_obj, 0) != hipSuccess) return bail(fail(IEM_E_HIP, "hipHostMalloc"));
   m->h_status = reinterpret_cast<volatile unsigned long long *>(m->h_obj + 1);   // second word: comm time-outs (IemCommErr::hstatus)
@@ -1129,6 +1153,10 @@ int iem_destroy(iem_model *m) {
   for (auto &kv : m->kkt_mods) if (kv.second.mod) hipModuleUnload(kv.second.mod);
   for (auto &kv : m->d_arrays) hipFree(kv.second);
   free_program(m->alt);
+  for (double *r : m->par.d_red) if (r) hipFree(r);
+  for (long long *r : m->par.d_axis) if (r) hipFree(r);
+  for (long long *r : m->par.d_gather) if (r) hipFree(r);
+  free_program(m->par.code);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
   delete m;
@@ -1155,8 +1183,11 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 }
 
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
-  if (!m || !out || k < 0 || k >= (int)m->code.prog.kernels.size()) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = m->code.prog.kernels[k];
+  if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
+  // behind the model's own kernels: those of the parameter kinds, once their program exists (after the first such call)
+  const int n_own = (int)m->code.prog.kernels.size(), n_par = m->par.tried && m->par.rc == IEM_OK ? (int)m->par.code.prog.kernels.size() : 0;
+  if (k >= n_own + n_par) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : m->par.code.prog.kernels[k - n_own];
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
   out->kind = kd.kind;
@@ -1322,6 +1353,111 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_v; h.out = d_Hv; h.w = obj_weight; h.aux = m->d_red[iem::KK_HPROD];
   return launch_kind(m, m->code, iem::KK_HPROD, h);
+}
+
+// ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
+// The program of the three kinds, generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the
+// model's own); a failure is remembered and reported by every later call.
+static int param_program(iem_model *m) {
+  iem_model::ParamKinds &P = m->par;
+  if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
+  P.tried = true;
+  // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
+  // not remembered: what was set up is released and the next call tries again
+  auto done = [&](int rc) {
+    P.rc = rc;
+    if (rc) P.err = g_err;
+    if (rc != IEM_OK && rc != IEM_E_BLOB) {
+      for (double *&r : P.d_red) { if (r) hipFree(r); r = nullptr; }
+      for (long long *&r : P.d_axis) { if (r) hipFree(r); r = nullptr; }
+      for (long long *&r : P.d_gather) { if (r) hipFree(r); r = nullptr; }
+      free_program(P.code);
+      P.code = CodeObject();
+      P.tried = false; P.rc = IEM_OK;
+    }
+    return rc;
+  };
+  iem::Options po = m->opt;
+  po.param_kinds = 1;
+  try {
+    P.code.prog = iem::generate(m->model, po);
+  } catch (const std::exception &e) {
+    return done(fail(IEM_E_BLOB, e.what()));
+  }
+  int rc;
+  if ((rc = load_program(m, P.code, po)) != IEM_OK) return done(rc);
+  if ((rc = scatter_buffers(P.code.prog, P.d_red, P.d_gather, P.d_axis, &m->stream)) != IEM_OK) return done(rc);
+  return done(prepare_program(m, P.code));
+}
+
+static int param_refuse_sharded(const iem_model *m, const char *what);
+
+int iem_param_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = param_refuse_sharded(m, "iem_param_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->par.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+static int param_refuse_sharded(const iem_model *m, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — θ is replicated on every rank, so the products with d/dθ "
+                         "would need an all-reduce over the ranks; sharded parameter products are out of scope");
+}
+
+// the launchable kernels of a parameter kind (table slot `kind`) and what runs behind them; out fully overwritten
+static int param_launch(iem_model *m, int kind, LaunchHead h) {
+  iem_model::ParamKinds &P = m->par;
+  h.th = m->d_theta;
+  int rc;
+  if (iem::KK_JTPROD == kind || iem::KK_HPROD == kind) {
+    h.aux = P.d_red[kind];
+    for (auto &z : P.code.prog.zero_ranges[kind])
+      HIP_TRY(hipMemsetAsync(h.out + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
+  }
+  for (int k : P.code.launchable[kind])
+    if ((rc = launch_one(m, P.code, k, h))) return rc;
+  if (kind == iem::KK_JPROD) return IEM_OK;
+  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, kind, h.out, h.aux);
+}
+
+int iem_jpprod(iem_model *m, const double *d_x, const double *d_w, double *d_out) {
+  if (!m || !d_x || (!d_w && m->model.npar) || (!d_out && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_jpprod");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if (m->model.ncon == 0) return IEM_OK;
+  if ((rc = param_program(m))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_w; h.out = d_out;
+  return param_launch(m, iem::KK_JPROD, h);
+}
+
+int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out) {
+  if (!m || !d_x || (!d_y && m->model.ncon) || (!d_out && m->model.npar)) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_jptprod");
+  if (rc) return rc;
+  if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_y; h.out = d_out; h.w = obj_weight;
+  return param_launch(m, iem::KK_JTPROD, h);
+}
+
+int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out) {
+  if (!m || !d_x || (!d_y && m->model.ncon) || (!d_w && m->model.npar) || (!d_out && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_hpprod");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if (m->model.nvar == 0) return IEM_OK;
+  if ((rc = param_program(m))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
+  return param_launch(m, iem::KK_HPROD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

@@ -518,11 +518,11 @@ class KernelBuilder {
       vidx.assign(t.idx.size(), -1);
     }
     int idx1(int id) {
-      if (vidx[id] < 0) vidx[id] = K.tpl_idx(ti, id, G, 0, 1);
+      if (vidx[id] < 0) vidx[id] = K.tpl_idx(ti, id, G, 0, t.is_theta_idx(id) ? 2 : 1);
       return vidx[id];
     }
     int pos0(int id, int space = 1) {  // 0-based position of a 1-based index (space 1: x / g, 2: theta)
-      return K.tpl_idx(ti, id, G, -1, space);
+      return K.tpl_idx(ti, id, G, -1, t.is_theta_idx(id) ? 2 : space);
     }
     void forward(int order) {
       for (size_t n = 0; n < t.nodes.size(); ++n) {
@@ -693,6 +693,7 @@ class KernelBuilder {
           const IdxVal &A = K.idx_[ia], &Bv = K.idx_[ib];
           bool never = A.ind.empty() && Bv.ind.empty() && A.aff.k[0] == Bv.aff.k[0] && A.aff.k[1] == Bv.aff.k[1] &&
                        A.aff.k[2] == Bv.aff.k[2] && A.aff.c != Bv.aff.c;
+          if (A.aff.space != Bv.aff.space) never = true;   // (parameter view: an entry of x and an entry of θ)
           v = never ? adj : K.mk(VSEL, K.sel_id(ia, ib), two, adj, -1, 0);
         }
         acc2(cnt, v);
@@ -764,7 +765,23 @@ class KernelBuilder {
   }
 
   // ---- build the kernel's outputs ---------------------------------------------
+  // parameter kinds (Options::param_kinds; m_ is the parameter view): slots of θ
+  bool theta_kinds() const { return opt_.param_kinds != 0; }
+  static bool has_theta_slot1(const Template &t) {
+    for (int id : t.slot1_idx) if (t.is_theta_idx(id)) return true;
+    return false;
+  }
+  static bool has_cross_slot2(const Template &t) {
+    for (size_t s = 0; s < t.slot2_i.size(); ++s) if (t.is_theta_idx(t.slot2_i[s]) != t.is_theta_idx(t.slot2_j[s])) return true;
+    return false;
+  }
   bool relevant(const Template &t) const {
+    if (theta_kinds()) switch (kind_) {
+      case KK_JPROD: return t.kind == IEM_T_CON;           // every row is written: zero where c does not depend on θ
+      case KK_JTPROD: return has_theta_slot1(t);           // constraints (seed y) and objective terms (seed σ)
+      case KK_HPROD: return has_cross_slot2(t);
+      default: return false;
+    }
     switch (kind_) {
       case KK_CONS: return t.kind == IEM_T_CON;
       case KK_JAC: return t.kind == IEM_T_CON && t.o1step > 0;
@@ -828,7 +845,21 @@ class KernelBuilder {
           }
           break;
         }
-        case KK_JPROD: {   // (J v)[row] = sum_slots dc/dx_slot * v[col(slot)]
+        case KK_JPROD: if (theta_kinds()) {   // ((dc/dθ) w)[row]: the slots of x have no tangent — their partials are never built into the row
+          tg.forward(1);
+          tg.slots1.assign(t.o1step, -1);
+          tg.gr(t.root, 0, C(1.0));
+          int acc = C(0.0);
+          for (int s = 0; s < t.o1step; ++s) {
+            if (!t.is_theta_idx(t.slot1_idx[s]) || tg.slots1[s] < 0) continue;
+            acc = add(acc, mul(tg.slots1[s], load(4, 0, tg.pos0(t.slot1_idx[s]), G.guard)));
+          }
+          IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0);
+          o.pos_idx = idxval(iv); o.pos_off = t.o0;
+          o.vals = {acc};
+          alg_w_ += t.n_items;
+          break;
+        } else {   // (J v)[row] = sum_slots dc/dx_slot * v[col(slot)]
           tg.forward(1);
           tg.slots1.assign(t.o1step, -1);
           tg.gr(t.root, 0, C(1.0));
@@ -843,7 +874,26 @@ class KernelBuilder {
           alg_w_ += t.n_items;
           break;
         }
-        case KK_JTPROD: {  // (J' v)[col] += dc/dx_slot * v[row]  == gradient of  v . c(x)
+        case KK_JTPROD: if (theta_kinds()) {   // σ df/dθ + (dc/dθ)' y: the θ slots of the gradient of  σ f + y . c
+          tg.forward(1);
+          tg.slots1.assign(t.o1step, -1);
+          int seed;
+          if (t.kind == IEM_T_OBJ) seed = mk(VW, 0, -1, -1, -1, 0);
+          else {
+            IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;
+            seed = load(4, 0, idxval(rv), G.guard);
+          }
+          tg.gr(t.root, 0, seed);
+          for (int s = 0; s < t.o1step; ++s) {
+            if (!t.is_theta_idx(t.slot1_idx[s])) continue;
+            o.vals.push_back(tg.slots1[s]);
+            o.grad_idx.push_back(tg.pos0(t.slot1_idx[s]));
+            o.grad_tidx.push_back(t.slot1_idx[s]);
+            o.grad_mode.push_back(2);
+            alg_w_ += t.n_items;
+          }
+          break;
+        } else {  // (J' v)[col] += dc/dx_slot * v[row]  == gradient of  v . c(x)
           tg.forward(1);
           tg.slots1.assign(t.o1step, -1);
           IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into v), not an output position
@@ -876,7 +926,13 @@ class KernelBuilder {
             if (it == dest.end()) { dest.emplace(pos_id, val); dest_tidx.emplace(pos_id, tidx); dest_order.push_back(pos_id); }
             else it->second = add(it->second, val);
           };
-          for (int s = 0; s < t.o2step; ++s) {
+          for (int s = 0; s < t.o2step && theta_kinds(); ++s) {   // (d2L/dx dθ) w: the mixed slots only, row = the entry of x
+            const bool ti_ = t.is_theta_idx(t.slot2_i[s]), tj_ = t.is_theta_idx(t.slot2_j[s]);
+            if (ti_ == tj_) continue;
+            const int xi = ti_ ? t.slot2_j[s] : t.slot2_i[s], pi = ti_ ? t.slot2_i[s] : t.slot2_j[s];
+            contribute(tg.pos0(xi), mul(tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s], load(4, 0, tg.pos0(pi), G.guard)), xi);
+          }
+          for (int s = 0; s < t.o2step && !theta_kinds(); ++s) {
             int h = tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s];
             int ia = tg.idx1(t.slot2_i[s]), ib = tg.idx1(t.slot2_j[s]);
             int pa = tg.pos0(t.slot2_i[s]), pb = tg.pos0(t.slot2_j[s]);
@@ -2427,6 +2483,8 @@ static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t
 }
 
 static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"};
+// the parameter kinds (Options::param_kinds) ride on the table slots of the kinds they are shaped like
+static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod", "hpprod"};
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2673,7 +2731,7 @@ static void emit_kinds(Emitter &E) {
     Launch &L = E.emitted[kind];
     L.kind = kind; L.tile = ktile;
     for (size_t k : ks) L.bodies.push_back(Body{E.builders[k].get(), &E.descs[k], "A.out", "A.aux", E.kopts[k].xcd_remap != 0});
-    if (!emit_launch(E, L, std::string("iem_") + kname[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
+    if (!emit_launch(E, L, std::string("iem_") + (opt.param_kinds ? kname_theta : kname)[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
     if (kind == KK_OBJ) E.P.n_partials = L.F.grid[0];
   }
 }
@@ -2808,9 +2866,22 @@ static void emit_pair(Emitter &E, const Model &m, const std::map<size_t, std::pa
   emit_launch(E, L, std::string("iem_pair_all") + E.name_tag);   // (too large for one launch: the two calls stay separate launches)
 }
 
+static Program generate_kinds(const Model &m, const Options &opt_in);
+
 Program generate(const Model &m, const Options &opt_in) {
   validate_indices(m);
+  if (!opt_in.param_kinds) return generate_kinds(m, opt_in);
+  // the kinds d/dθ: the same machinery over the parameter view of the model (θ nodes are variables of the extended
+  // vector [x; θ]); the builders keep the slots the kind asks for and drop the rest before anything is emitted
+  const Model view = parameter_view(m);
+  return generate_kinds(view, opt_in);
+}
+
+static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
+  const bool theta = opt.param_kinds != 0;
+  // length of a scatter kind's output vector: nvar, except the parameter kind jptprod (an entry per θ)
+  auto nout = [&](int kind) { return theta && kind == KK_JTPROD ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
   Program P;
   P.block = opt.block;
@@ -2867,7 +2938,8 @@ Program generate(const Model &m, const Options &opt_in) {
       throw std::runtime_error("support grid too large in dims 2/3 (limit 65535 per dimension for 3-D grids)");
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
-      std::string name = std::string("iem_") + kname[kind] + "_g" + std::to_string(gi) + name_tag;
+      if (theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
+      std::string name = std::string("iem_") + (theta ? kname_theta : kname)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
       if (!kb->build(nullptr)) continue;
@@ -3089,7 +3161,7 @@ Program generate(const Model &m, const Options &opt_in) {
               if (p < 0 || p >= arr.n) throw std::runtime_error("index array position out of range");
               d += t.first * arr.i(p);
             }
-            if (d < 0 || d >= m.nvar) throw std::runtime_error("scatter destination out of range");
+            if (d < 0 || d >= nout(kind)) throw std::runtime_error("scatter destination out of range");
             dest_of.push_back(d);
             if (pos_of) pos_of->push_back(park + (o.scalar ? 0 : q[0] + g.ext[0] * (q[1] + g.ext[1] * q[2])));
           }
@@ -3130,10 +3202,10 @@ Program generate(const Model &m, const Options &opt_in) {
     const size_t na = dest_of.size();
     std::vector<size_t> order(na);
     for (size_t e = 0; e < na; ++e) order[e] = e;
-    if (m.nvar <= 4 * (int64_t)na + (1 << 20)) {   // counting sort
-      std::vector<int64_t> start((size_t)m.nvar + 1, 0);
+    if (nout(kind) <= 4 * (int64_t)na + (1 << 20)) {   // counting sort
+      std::vector<int64_t> start((size_t)nout(kind) + 1, 0);
       for (int64_t d : dest_of) ++start[(size_t)d + 1];
-      for (int64_t d = 0; d < m.nvar; ++d) start[(size_t)d + 1] += start[(size_t)d];
+      for (int64_t d = 0; d < nout(kind); ++d) start[(size_t)d + 1] += start[(size_t)d];
       for (size_t e = 0; e < na; ++e) order[(size_t)start[(size_t)dest_of[e]]++] = e;
     } else {
       std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return dest_of[a] < dest_of[b]; });
@@ -3163,7 +3235,8 @@ Program generate(const Model &m, const Options &opt_in) {
       if (c.first > pos) holes.emplace_back(pos, c.first);
       pos = std::max(pos, c.second + 1);
     }
-    if (pos < m.nvar) holes.emplace_back(pos, m.nvar);
+    if (theta && kind == KK_GRAD) continue;
+    if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
       if (descs[k].kind == kind && (best < 0 || descs[k].n_blocks > descs[best].n_blocks)) best = (int)k;
@@ -3236,8 +3309,10 @@ Program generate(const Model &m, const Options &opt_in) {
   for (const KernelDesc &d : descs) E.mixed = E.mixed || d.block != opt.block;
   E.name_tag = name_tag;
   emit_kinds(E);
-  emit_phases(E);
-  emit_pair(E, m, whole_of, second_half);
+  if (!theta) {
+    emit_phases(E);
+    emit_pair(E, m, whole_of, second_half);
+  }
   P.source = src.str();
   P.key = fnv1a64(P.source);
   return P;

@@ -127,6 +127,11 @@ struct Options {
   int digit_fields = 1;    // fields the parse-time digit pass recognised (iem_model.hpp: recover_digits, folded runs only) are decoded
                            // from the item coordinate in registers; 0: they stay gathers from their short columns
   int cons_direct_2d = 1;  // cons! of a model whose largest grid is 2-D: plain coalesced stores instead of the LDS re-cut (kind_options)
+  // 1: generate() emits the PARAMETER kinds instead — a program of its own, the model's usual program is untouched:
+  // jpprod (dc/dθ) w, jptprod σ df/dθ + (dc/dθ)' y, hpprod (d2L/dx dθ) w.  They take the table slots, pointers and follow-ups
+  // of the kinds they are shaped like (KK_JPROD / KK_JTPROD / KK_HPROD; jptprod's output has npar entries, A.w = σ), differentiate
+  // over the extended vector [x; θ] (iem_model.hpp: parameter_view) and go through the same deterministic scatter machinery.
+  int param_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };

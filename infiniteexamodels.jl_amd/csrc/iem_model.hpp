@@ -92,6 +92,10 @@ struct Template {
   std::vector<int> comp1, comp2;          // visit -> slot
   std::vector<int> slot1_idx;             // slot -> idx id
   std::vector<int> slot2_i, slot2_j;      // slot -> idx ids (unswapped)
+  // >= 0 only in the parameter view of a model (parameter_view): index-expression ids from here on belong to θ —
+  // every θ node got a copy of its expression, so that a slot is either a variable's or a parameter's
+  int theta_idx0 = -1;
+  bool is_theta_idx(int id) const { return theta_idx0 >= 0 && id >= theta_idx0; }
 };
 
 // one add_var slab of x: `dims` (first index fastest) starting at 0-based `off`; `group[a]` = the
@@ -187,12 +191,13 @@ struct SymWalk {
 // upper bound on any count in a blob (items, array lengths, nvar …): 2^40 elements = 8 TiB of doubles
 constexpr int64_t IEM_MAX_COUNT = (int64_t)1 << 40;
 
-inline void analyse_template(Template &t) {
+// par_is_var: θ nodes count as variables too (the slots of the extended vector [x; θ]; parameter_view)
+inline void analyse_template(Template &t, bool par_is_var = false) {
   for (size_t n = 0; n < t.nodes.size(); ++n) {
     Node &nd = t.nodes[n];
     nd.fixed = FX_NONE;
     nd.inner = -1;
-    if (nd.op == IEM_OP_VAR) nd.kind = K_VAR;
+    if (nd.op == IEM_OP_VAR || (par_is_var && nd.op == IEM_OP_PAR)) nd.kind = K_VAR;
     else if (nd.op <= IEM_OP_PAR) nd.kind = K_REAL;
     else if (IEM_OP_IS_UNARY(nd.op)) {
       nd.kind = t.nodes[nd.a].kind == K_REAL ? K_REAL : K_N1;
@@ -228,6 +233,32 @@ inline void analyse_template(Template &t) {
     t.comp2.push_back(s);
   }
   t.o2step = (int)t.slot2_i.size();
+}
+
+// The parameter view of a parsed model: the same templates analysed over the extended vector [x; θ] — every θ node
+// is a variable with an index expression of its own (ids from Template::theta_idx0), and the first- and second-order
+// slots (comp1 / comp2) run over both.  What the generator differentiates for the kinds ∂/∂θ (jpprod / jptprod /
+// hpprod); the row offsets o0 stay, the COO offsets o1 / o2 mean nothing here.  The view shares the array payloads of
+// `m` (ArrayDesc::data points into m's blob and synthesised columns): it must not outlive it.
+inline Model parameter_view(const Model &m) {
+  Model v;
+  v.slabs = m.slabs;
+  v.nvar = m.nvar; v.npar = m.npar; v.ncon = m.ncon; v.nnzj = m.nnzj; v.nnzh = m.nnzh;
+  v.minimize = m.minimize;
+  v.arr_x0 = m.arr_x0; v.arr_lvar = m.arr_lvar; v.arr_uvar = m.arr_uvar; v.arr_theta = m.arr_theta;
+  v.arrs = m.arrs;
+  v.tpl = m.tpl;
+  for (Template &t : v.tpl) {
+    t.theta_idx0 = (int)t.idx.size();
+    std::vector<int> copy_of(t.idx.size(), -1);
+    for (Node &nd : t.nodes) {
+      if (nd.op != IEM_OP_PAR) continue;
+      if (copy_of[nd.a] < 0) { copy_of[nd.a] = (int)t.idx.size(); t.idx.push_back(t.idx[nd.a]); }
+      nd.a = copy_of[nd.a];
+    }
+    analyse_template(t, true);
+  }
+  return v;
 }
 
 // A foreign producer (the Julia writer) sees a template's iterator as a flat list of records and

@@ -168,6 +168,23 @@ function NLPModels.hprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Fl
     return Hv
 end
 
+# Parameter sensitivities (no NLPModels counterpart; unexecuted like the rest of this shim): the products with ∂/∂θ at
+# (x, the handle's current θ) — (∂c/∂θ)·w, obj_weight·∂f/∂θ + (∂c/∂θ)ᵀ·y, (∂²L/∂x∂θ)·w.  K·[dx; dy] = -[hpprod!; jpprod!] is
+# the first-order move of a solution under δθ = w.
+jpprod!(m::MI355XModel, x::ROCVector{Float64}, w::ROCVector{Float64}, out::ROCVector{Float64}) =
+    (check(ccall((:iem_jpprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(w), dptr(out))); out)
+function jptprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, out::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_jptprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(out)))
+    return out
+end
+function hpprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, w::ROCVector{Float64},
+                 out::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_hpprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(w), dptr(out)))
+    return out
+end
+
 # ExaModels.set_parameter!(core, param, vals)  (src/infiniteopt_backend.jl:522,546)
 function set_parameter!(m::MI355XModel, param, vals)
     v = collect(Float64, vec(vals))

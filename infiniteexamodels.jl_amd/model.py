@@ -323,6 +323,52 @@ class ExaModel:
         _lib.check(self._L.iem_hprod(self._h, _ptr(x), _ptr(y), _ptr(v), float(obj_weight), _ptr(Hv)))
         return Hv
 
+    # ---- parameter sensitivities: the same products with ∂/∂θ, at (x, the model's current θ) ----
+    def jpprod(self, x, w, out=None):
+        """``(∂c/∂θ)·w`` (ncon), ``w`` of length ``npar``."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(w, self.meta.npar, "w")
+        out = out if out is not None else self._new(self.meta.ncon)
+        self._chk(out, self.meta.ncon, "out")
+        self._sync_stream()
+        _lib.check(self._L.iem_jpprod(self._h, _ptr(x), _ptr(w), _ptr(out)))
+        return out
+
+    def jptprod(self, x, y, obj_weight: float = 1.0, out=None):
+        """``obj_weight·∂f/∂θ + (∂c/∂θ)ᵀ·y`` (npar)."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(y, self.meta.ncon, "y")
+        out = out if out is not None else self._new(self.meta.npar)
+        self._chk(out, self.meta.npar, "out")
+        self._sync_stream()
+        _lib.check(self._L.iem_jptprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(out)))
+        return out
+
+    def hpprod(self, x, y, w, obj_weight: float = 1.0, out=None):
+        """``(∂²L/∂x∂θ)·w`` (nvar) with ``L = obj_weight·f + yᵀc``, ``w`` of length ``npar``."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(y, self.meta.ncon, "y"); self._chk(w, self.meta.npar, "w")
+        out = out if out is not None else self._new(self.meta.nvar)
+        self._chk(out, self.meta.nvar, "out")
+        self._sync_stream()
+        _lib.check(self._L.iem_hpprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(w), _ptr(out)))
+        return out
+
+    def param_prepare(self) -> int:
+        """Set up the program of jpprod / jptprod / hpprod now (``iem_param_prepare``: otherwise the first such call does —
+        synchronously, and not inside a stream capture); the number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_param_prepare(self._h, C.byref(n)))
+        return int(n.value)
+
+    def param_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of jpprod / jptprod / hpprod (kinds jprod / jtprod / hprod
+        of a program of their own, listed behind the model's kernels)."""
+        out = []
+        for k in range(self.meta.n_kernels, self.meta.n_kernels + self.param_prepare()):
+            ki = _lib.KernelInfo()
+            _lib.check(self._L.iem_kernel_info(self._h, k, C.byref(ki)))
+            out.append(dict(name=ki.name.decode(), kind=KERNEL_KINDS[ki.kind], grid=tuple(ki.grid), lds_bytes=int(ki.lds_bytes),
+                            alg_bytes_read=int(ki.alg_bytes_read), alg_bytes_written=int(ki.alg_bytes_written)))
+        return out
+
     def jac_structure(self, base: int = 0):
         """``jac_structure!(m, rows, cols)`` → host int64 arrays (``base`` 1 = Julia)."""
         r = np.zeros(max(self.meta.nnzj, 1), dtype=np.int64)
