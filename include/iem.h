@@ -348,6 +348,13 @@ int iem_kkt_hub_level(iem_model *m, int64_t S, int64_t lane_len, int nb, int nc,
 int iem_kkt_chain_solve_lanes(iem_model *m, int64_t S, int64_t lane_len, int nb, int ne, int nc, const double *d_Dinv, const double *d_Bt,
                               const double *d_BR, const int32_t *d_rows, const int32_t *d_cols, const double *d_Z, double *d_r, double *d_z,
                               double *d_rBp, const double *d_xB, int phase);
+/* ... and for nrhs right-hand sides at once (csrc/iem_kkt_many_device.h): column u of d_r / d_z is the plane + u S nb, of d_rBp
+ * + u S ne, of d_xB + u ne (lane_len = S or 0: one chain).  The columns go through the levels in chunks of 4 (2 for lane-per-row
+ * shapes with nc > 16) that read every block of the factors ONCE per level; per column the arithmetic is that of
+ * iem_kkt_chain_solve_lanes, operation for operation: the same bits, however the columns are grouped. */
+int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, int ne, int nc, const double *d_Dinv, const double *d_Bt,
+                             const double *d_BR, const int32_t *d_rows, const int32_t *d_cols, const double *d_Z, double *d_r, double *d_z,
+                             double *d_rBp, const double *d_xB, int nrhs, int phase);
 /* The same solver as ONE object — what a host without the Python layer (a Julia MadNLP linear-solver wrapper) binds.
  * iem_kkt_create analyses the model once on the host: grouping of the unknowns (variable u, then the multiplier of row
  * u - nvar) into chain blocks + border from the slab table and the Jacobian / Hessian structure, the narrow coupling, and a
@@ -386,6 +393,16 @@ int iem_kkt_analyse_blob(const void *blob, size_t nbytes, int group, iem_kkt_inf
 int iem_kkt_assemble(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, double delta_w, double delta_c);
 int iem_kkt_factor(iem_kkt *k, int64_t *out_inertia);
 int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol);
+/* K sol_u = rhs_u for nrhs columns with ONE pass over the factors per chunk of columns (sensitivity matrices, several refinement
+ * residuals, predictor + corrector): column u is d_rhs + u ld_rhs / d_sol + u ld_sol, nvar + ncon doubles; ld >= nvar + ncon, the
+ * entries between are neither read nor written.  d_sol == d_rhs with ld_sol == ld_rhs solves in place; any other overlap is
+ * IEM_E_ARG — judged on the whole extents [d, d + (nrhs - 1) ld + n), so columns of d_sol interleaved with those of d_rhs
+ * (disjoint, but inside each other's extent) are refused as well.  Any nrhs: the columns are processed in chunks (see iem_kkt_chain_solve_many) through a workspace of ONE chunk that
+ * the first call allocates and iem_kkt_destroy frees — memory does not grow with nrhs.  Column u carries the bits
+ * iem_kkt_solve gives for it.  The border system is solved on the host once per column, with one read-back and one upload per
+ * chunk.  Hub mode (info.hubs != 0) is accepted as a loop of single solves: the hubs' side stays matrix-vector work per column
+ * (sharing its factors across columns — GEMM for GEMV — is not done). */
+int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol);
 
 /* HIP source of the solver's kernels for one (nb, ne, nc) and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key);

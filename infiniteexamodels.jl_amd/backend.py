@@ -129,6 +129,14 @@ class ExaTranscriptionBackend:
         out[par.offset:par.offset + par.length] = vals - self.core.theta[par.offset:par.offset + par.length]
         return out
 
+    def parameter_directions(self, pairs) -> np.ndarray:
+        """``(npar, K)``: ``parameter_direction(pref, value)`` of every ``(pref, value)`` in ``pairs`` as a column — what
+        ``sensitivity.parameter_steps`` takes.  θ stays as it is."""
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("parameter_directions: no (parameter, value) pair")
+        return np.stack([self.parameter_direction(pref, value) for pref, value in pairs], axis=1)
+
     def update_start_value(self, vref, value) -> bool:
         """``InfiniteOpt.update_variable_info`` start-value branch (:553-592): writes ``core.x0``."""
         if self.core is None:

@@ -38,6 +38,9 @@ static const char *kHalo2Header =   // the two-way halo exchange: only in the so
 static const char *kKktSource =
 #include "iem_kkt_device_h.inc"
     ;
+static const char *kKktManySource =   // the multi-column solve kernels, behind the single-column ones in every chain KKT code object
+#include "iem_kkt_many_device_h.inc"
+    ;
 
 namespace {
 
@@ -217,7 +220,9 @@ struct iem_model {
   bool reads_halo_x[iem::KK_LAST + 1] = {}, reads_halo_v[iem::KK_LAST + 1] = {}, carrier[iem::KK_LAST + 1] = {};
   uint64_t nonce = 0;
   // chain KKT solver (iem_kkt_chain_*): one code object per (block size, border size)
-  struct KktMod { unsigned elim_wg = 64; int elim_bpw = 1; hipModule_t mod = nullptr; hipFunction_t elim = nullptr, upd = nullptr, fwd = nullptr, bwd = nullptr, gather = nullptr, move = nullptr, colsum = nullptr, hub_z = nullptr, hub_widen = nullptr, hub_mask = nullptr, hub_ety = nullptr, hub_ex = nullptr, hub_leaf = nullptr, hub_diagmax = nullptr, fz = nullptr, fs = nullptr, bw = nullptr; int solve_bpw = 0; };
+  struct KktMod { unsigned elim_wg = 64; int elim_bpw = 1; hipModule_t mod = nullptr; hipFunction_t elim = nullptr, upd = nullptr, fwd = nullptr, bwd = nullptr, gather = nullptr, move = nullptr, colsum = nullptr, hub_z = nullptr, hub_widen = nullptr, hub_mask = nullptr, hub_ety = nullptr, hub_ex = nullptr, hub_leaf = nullptr, hub_diagmax = nullptr, fz = nullptr, fs = nullptr, bw = nullptr; int solve_bpw = 0;
+                  // the multi-column solves (csrc/iem_kkt_many_device.h): many_r columns per chunk (KKT_MR of the module's source)
+                  hipFunction_t fwd_m = nullptr, bwd_m = nullptr, fz_m = nullptr, fs_m = nullptr, bw_m = nullptr, move_m = nullptr, colsum_m = nullptr; int many_r = 1; };
   std::map<std::pair<int, int>, KktMod> kkt_mods;
   std::map<int, void *> d_arrays;  // model array id -> device copy
   std::vector<double> theta_host;
@@ -2078,6 +2083,12 @@ void kkt_shape(int nb, int ne, int *wmax, int *wpe) {
   if (knobs.wmax >= 1) *wmax = knobs.wmax;
   if (knobs.wpe >= 0) *wpe = knobs.wpe;
 }
+// Columns per chunk of the multi-column solves (KKT_MR of csrc/iem_kkt_many_device.h).  Four, from the measurement and the
+// register use together (profiles/kkt_solve_many.json): at four every multi-column kernel of the precompiled shapes stays
+// within 184 VGPRs (<= 138 up to 52 x 52 blocks: three to four waves per SIMD) and a column costs half a single solve; eight
+// takes kkt_forward_m / kkt_fs_m to 216 - 256 VGPRs (two waves) for another 3 - 15 % per column at nrhs >= 8 and LOSES 4 - 31 %
+// at nrhs = 4 (a half-empty chunk).  Two where kkt_fs_m's per-lane state (MR x nc doubles of z) would be wide.
+int kkt_many_width(int nb, int ne, int nc) { return (kkt_rowwise(nb, ne) && nb <= 32 && nc > 16) ? 2 : 4; }
 std::string kkt_source(int nb, int ne, int nc) {
   // (fused multiply-adds would be allowed here — nothing compares these kernels bit for bit — and take 1 000 of the 2 350 FP64
   // instructions out of a 40 x 40 kkt_eliminate, but the factorisation does not get faster for it: 2.52 against 2.45 ms at 1e5
@@ -2092,7 +2103,9 @@ std::string kkt_source(int nb, int ne, int nc) {
   if (wmax != 4) s += "#define KKT_WMAX " + std::to_string(wmax) + "\n";
   if (kkt_rowwise(nb, ne)) s += "#define KKT_ROWWISE " + std::to_string(kkt_rowwise(nb, ne)) + "\n#define KKT_ROW_WPG " + std::to_string(kkt_row_wpg(nb, ne)) + "\n";
   if (!knobs.defs.empty()) s += knobs.defs + "\n";     // (experiments, IEM_KKT_EXPERIMENTS=1 only: extra #define lines)
+  s += "#define KKT_MR " + std::to_string(kkt_many_width(nb, ne, nc)) + "\n";
   s += kKktSource;
+  s += kKktManySource;
   return s;
 }
 // LDS of kkt_eliminate: the panel buffers of the inverse, and with a border one NB x NB and two NB x NE tiles; of kkt_update:
@@ -2134,7 +2147,15 @@ int kkt_module(iem_model *m, int nb, int ne, int nc, iem_model::KktMod **out) {
       HIP_TRY(hipModuleGetFunction(&km.fs, km.mod, "kkt_fs"));
       HIP_TRY(hipModuleGetFunction(&km.bw, km.mod, "kkt_bw"));
       km.solve_bpw = 64 / nb;
+      HIP_TRY(hipModuleGetFunction(&km.fz_m, km.mod, "kkt_fz_m"));
+      HIP_TRY(hipModuleGetFunction(&km.fs_m, km.mod, "kkt_fs_m"));
+      HIP_TRY(hipModuleGetFunction(&km.bw_m, km.mod, "kkt_bw_m"));
     }
+    HIP_TRY(hipModuleGetFunction(&km.fwd_m, km.mod, "kkt_forward_m"));
+    HIP_TRY(hipModuleGetFunction(&km.bwd_m, km.mod, "kkt_backward_m"));
+    HIP_TRY(hipModuleGetFunction(&km.move_m, km.mod, "kkt_move_m"));
+    HIP_TRY(hipModuleGetFunction(&km.colsum_m, km.mod, "kkt_colsum_m"));
+    km.many_r = kkt_many_width(nb, ne, nc);
     it = m->kkt_mods.emplace(std::make_pair(nb, ne * 64 + nc), km).first;
   }
   *out = &it->second;
@@ -2150,6 +2171,16 @@ int kkt_launch_raw(iem_model *m, hipFunction_t fn, void *args, size_t sz, long l
 }
 int kkt_launch(iem_model *m, hipFunction_t fn, KktArgsH a, long long grid, unsigned block) { return kkt_launch_raw(m, fn, &a, sizeof a, grid, block); }
 int kkt_launch_solve(iem_model *m, hipFunction_t fn, KktSolveArgsH a, long long grid, unsigned block) { return kkt_launch_raw(m, fn, &a, sizeof a, grid, block); }
+struct KktSolveManyArgsH { KktSolveArgsH a; int nr; };      // KktSolveManyArgs of csrc/iem_kkt_many_device.h
+int kkt_launch_many(iem_model *m, hipFunction_t fn, const KktSolveArgsH &a, int nr, long long grid, unsigned block) {
+  KktSolveManyArgsH A{a, nr};
+  return kkt_launch_raw(m, fn, &A, sizeof A, grid, block);
+}
+// (experiments only: the 64-thread solves for every shape)
+bool kkt_old_solves() {
+  static const bool v = [] { const char *e = getenv("IEM_KKT_EXPERIMENTS"), *o = getenv("IEM_KKT_OLD_SOLVES"); return e && !std::strcmp(e, "1") && o && !std::strcmp(o, "1"); }();
+  return v;
+}
 // kkt_eliminate over `blocks` blocks of the level: a workgroup takes elim_bpw of them
 int kkt_launch_elim(iem_model *m, const iem_model::KktMod *km, KktArgsH a, long long blocks) {
   return kkt_launch_raw(m, km->elim, &a, sizeof a, (blocks + km->elim_bpw - 1) / km->elim_bpw, km->elim_wg);
@@ -2247,8 +2278,7 @@ int iem_kkt_chain_solve_lanes(iem_model *m, int64_t S, int64_t lane_len, int nb,
   if (rc) return rc;
   const long long lanes = S / T;
   KktSolveArgsH A{d_Dinv, d_Bt, d_BR, d_Z, d_rows, d_cols, d_r, d_z, d_rBp, d_xB, (long long)S, 1, 0, T};
-  static const bool old_solves = [] { const char *e = getenv("IEM_KKT_EXPERIMENTS"), *o = getenv("IEM_KKT_OLD_SOLVES"); return e && !std::strcmp(e, "1") && o && !std::strcmp(o, "1"); }();
-  const bool rowwise = km->fz && !old_solves;        // no border, blocks that fit a wave: a lane per row
+  const bool rowwise = km->fz && !kkt_old_solves();        // no border, blocks that fit a wave: a lane per row
   const long long bpw = rowwise ? km->solve_bpw : 1;
   if (!chained) {            // independent blocks: the border terms of all blocks (forward), every block's own solve (backward)
     if (phase != 0 && phase != 1) return fail(IEM_E_ARG, "phase must be 0 (forward) or 1 (backward)");
@@ -2289,6 +2319,68 @@ int iem_kkt_chain_solve_lanes(iem_model *m, int64_t S, int64_t lane_len, int nb,
   return IEM_OK;
 }
 
+/* The same levels for nrhs right-hand sides (csrc/iem_kkt_many_device.h): column u of r / z is the plane d_r + u S nb, of rBp
+ * d_rBp + u S ne, of xB d_xB + u ne.  Chunks of the shape's width (kkt_many_width) share every read of the factors; a chunk of
+ * ONE column goes through the single-column kernels — whose operations, per column, the multi-column kernels repeat in the
+ * same order: a column's bits do not depend on how the columns were chunked. */
+int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, int ne, int nc, const double *d_Dinv, const double *d_Bt, const double *d_BR,
+                             const int32_t *d_rows, const int32_t *d_cols, const double *d_Z, double *d_r, double *d_z, double *d_rBp,
+                             const double *d_xB, int nrhs, int phase) {
+  const bool chained = d_Bt != nullptr;
+  const long long T = lane_len > 0 ? lane_len : S;
+  if (!m || nrhs < 1 || S < 1 || S % T || (T != S && ne > 0) || !d_Dinv || (chained && (!d_BR || !d_rows || !d_cols || !d_z)) || !d_r || (ne > 0 && (!d_Z || (phase == 0 && !d_rBp) || (phase == 1 && !d_xB))))
+    return fail(IEM_E_ARG, "bad argument");
+  if (phase != 0 && phase != 1) return fail(IEM_E_ARG, "phase must be 0 (forward) or 1 (backward)");
+  DevGuard dg_(m->device);
+  iem_model::KktMod *km = nullptr;
+  int rc = kkt_module(m, nb, ne, nc, &km);
+  if (rc) return rc;
+  const long long lanes = S / T, nep = std::max(ne, 0);
+  const bool rowwise = km->fz_m && !kkt_old_solves();
+  const long long bpw = rowwise ? km->solve_bpw : 1;
+  for (int c0 = 0; c0 < nrhs; c0 += km->many_r) {
+    const int nr = std::min(km->many_r, nrhs - c0);
+    double *r = d_r + (long long)c0 * S * nb, *z = d_z ? d_z + (long long)c0 * S * nb : nullptr, *rBp = d_rBp ? d_rBp + (long long)c0 * S * nep : nullptr;
+    const double *xB = d_xB ? d_xB + (long long)c0 * nep : nullptr;
+    if (nr == 1) {
+      if ((rc = iem_kkt_chain_solve_lanes(m, S, lane_len, nb, ne, nc, d_Dinv, d_Bt, d_BR, d_rows, d_cols, d_Z, r, z, rBp, xB, phase))) return rc;
+      continue;
+    }
+    KktSolveArgsH A{d_Dinv, d_Bt, d_BR, d_Z, d_rows, d_cols, r, z, rBp, xB, (long long)S, 1, 0, T};
+    auto go = [&](hipFunction_t fn, long long grid) { return kkt_launch_many(m, fn, A, nr, grid, 64); };
+    if (!chained) {            // independent blocks: the border terms of all blocks (forward), every block's own solve (backward)
+      A.final_block = 2;
+      if (phase == 0) rc = ne > 0 ? go(km->fwd_m, S) : IEM_OK;
+      else rc = rowwise ? go(km->fz_m, (S + bpw - 1) / bpw) : go(km->bwd_m, S);
+      if (rc) return rc;
+      continue;
+    }
+    if (phase == 0) {
+      for (long long s = 1; s < T; s *= 2) {
+        A.s = s;
+        const long long n_elim = lanes * ((T - s + 2 * s - 1) / (2 * s)), n_surv = lanes * ((T + 2 * s - 1) / (2 * s));
+        if (rowwise) {
+          if ((rc = go(km->fz_m, (n_elim + bpw - 1) / bpw)) || (rc = go(km->fs_m, (n_surv + 63) / 64))) return rc;
+        } else if ((rc = go(km->fwd_m, n_surv + n_elim))) return rc;
+      }
+      if (!rowwise && ne > 0) { A.final_block = 1; if ((rc = go(km->fwd_m, lanes))) return rc; }
+      continue;
+    }
+    A.final_block = 1;
+    if ((rc = rowwise ? go(km->fz_m, (lanes + bpw - 1) / bpw) : go(km->bwd_m, lanes))) return rc;
+    A.final_block = 0;
+    long long top = 1;
+    while (top * 2 < T) top *= 2;
+    for (long long s = top; s >= 1; s /= 2) {
+      if (s >= T) continue;
+      A.s = s;
+      const long long n_elim = lanes * ((T - s + 2 * s - 1) / (2 * s));
+      if ((rc = rowwise ? go(km->bw_m, (n_elim + bpw - 1) / bpw) : go(km->bwd_m, n_elim))) return rc;
+    }
+  }
+  return IEM_OK;
+}
+
 /* ---- the chain KKT solver as ONE object behind the C-ABI (what a host without the Python layer binds) ---------------------- */
 struct iem_kkt {
   iem_model *m = nullptr;
@@ -2299,6 +2391,7 @@ struct iem_kkt {
   long long *d_dest = nullptr, *d_on = nullptr, *d_pos = nullptr, *d_border = nullptr, *d_bloc = nullptr, *d_info = nullptr;
   unsigned *d_seg = nullptr, *d_perm = nullptr;
   int64_t n_dest = 0, n_on = 0, n_h = 0, n_j = 0;
+  double *m_r = nullptr, *m_z = nullptr, *m_rBp = nullptr, *m_xB = nullptr, *m_part = nullptr;      // iem_kkt_solve_many: ONE chunk of columns, allocated by its first call
   std::vector<double> Gs;        // the border's Schur complement (host), set by iem_kkt_factor
   bool factored = false;
   struct KktHub *hub = nullptr;  // hub mode (L.hubs): the span-sparse border's buffers and the library handle of its GEMMs
@@ -2725,6 +2818,7 @@ int iem_kkt_destroy(iem_kkt *k) {
   DevGuard dg_(k->m->device);
   hub_free(k);
   for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_r, (void *)k->d_z, (void *)k->d_rBp, (void *)k->d_xB, (void *)k->d_part,
+                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part,
                   (void *)k->d_rows, (void *)k->d_cols, (void *)k->d_dest, (void *)k->d_on, (void *)k->d_pos, (void *)k->d_border, (void *)k->d_bloc, (void *)k->d_info,
                   (void *)k->d_seg, (void *)k->d_perm})
     if (p) hipFree(p);
@@ -2844,6 +2938,84 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
     return rc;
   { Mv A{d_sol, k->d_r, k->d_on, k->d_pos, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
   if (L.n_border) { Mv A{d_sol, k->d_xB, k->d_border, k->d_bloc, (long long)L.n_border}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc; }
+  return IEM_OK;
+}
+
+int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol) {
+  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
+  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_solve_many: nrhs must be at least 1");
+  const iem::KktLayout &L = k->L;
+  const int64_t n = L.nvar + L.ncon;
+  if (ld_rhs < n || ld_sol < n) return fail(IEM_E_ARG, "iem_kkt_solve_many: a leading dimension is shorter than nvar + ncon");
+  if (!(d_sol == d_rhs && ld_sol == ld_rhs)) {      // in place column for column, or apart
+    // (address ranges as integers: the two may be unrelated allocations.  Whole extents are compared — columns of one array
+    // interleaved with columns of the other are refused too)
+    const uintptr_t r0 = (uintptr_t)d_rhs, r1 = r0 + (uintptr_t)(((int64_t)(nrhs - 1) * ld_rhs + n) * 8), s0 = (uintptr_t)d_sol, s1 = s0 + (uintptr_t)(((int64_t)(nrhs - 1) * ld_sol + n) * 8);
+    if (r0 < s1 && s0 < r1) return fail(IEM_E_ARG, "iem_kkt_solve_many: d_rhs and d_sol overlap (allowed: the same array with the same leading dimension)");
+  }
+  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc;
+  if (L.hubs) {      // the hubs' side is GEMV work per column (hub_solve): a loop — sharing the hubs' factors across columns is not done here
+    for (int u = 0; u < nrhs; ++u)
+      if ((rc = hub_solve(k, d_rhs + (int64_t)u * ld_rhs, d_sol + (int64_t)u * ld_sol))) return rc;
+    return IEM_OK;
+  }
+  const int R = k->km->many_r;
+  const int64_t pl = L.S * L.nb, ne = L.ne, wp = 513 * std::max<int64_t>(ne, 1);
+  if (!k->m_r) {
+    HIP_TRY(hipMalloc((void **)&k->m_r, (size_t)(R * pl) * 8));
+    HIP_TRY(hipMalloc((void **)&k->m_z, (size_t)(R * pl) * 8));
+    HIP_TRY(hipMalloc((void **)&k->m_rBp, (size_t)std::max<int64_t>(R * L.S * ne, 1) * 8));
+    HIP_TRY(hipMalloc((void **)&k->m_xB, (size_t)std::max<int64_t>(R * ne, 1) * 8));
+    HIP_TRY(hipMalloc((void **)&k->m_part, (size_t)(R * wp) * 8));      // per column: 512 partial rows + the result (kkt_colsum_host)
+  }
+  const bool chained = L.reach > 0;
+  const double *Dinv = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB();
+  struct Mv { double *dst; const double *src; const long long *di, *si; long long n, ldd, lds; int nr; };
+  struct Sum { const double *in; double *out; long long rows, w, rows_per_wg, in_ld, out_ld, wgs; };
+  auto move = [&](Mv A, int64_t cnt) { A.n = (long long)cnt; return kkt_launch_raw(m, k->km->move_m, &A, sizeof A, (cnt + 255) / 256, 256); };
+  auto chain = [&](int nr, int phase) {
+    return iem_kkt_chain_solve_many(m, L.S, L.S, L.nb, L.ne, L.nc, Dinv, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
+                                    chained ? k->d_cols : nullptr, k->d_Z, k->m_r, chained ? k->m_z : nullptr, k->m_rBp, (phase && ne > 0) ? k->m_xB : nullptr, nr, phase);
+  };
+  std::vector<double> rB, col;
+  for (int c0 = 0; c0 < nrhs; c0 += R) {
+    const int nr = std::min(R, nrhs - c0);
+    const double *rhs = d_rhs + (int64_t)c0 * ld_rhs;
+    double *sol = d_sol + (int64_t)c0 * ld_sol;
+    HIP_TRY(hipMemsetAsync(k->m_r, 0, (size_t)(nr * pl) * 8, m->stream));
+    if ((rc = move(Mv{k->m_r, rhs, k->d_pos, k->d_on, 0, (long long)pl, (long long)ld_rhs, nr}, k->n_on))) return rc;
+    if ((rc = chain(nr, 0))) return rc;
+    if (ne > 0) {      // the border systems on the host: Gs xB = rB - sum_k rBp[k] per column — ONE read-back and ONE upload per chunk
+      const int64_t ncc = (ne + 255) / 256, per = (L.S + 511) / 512, nrc = (L.S + per - 1) / per;      // kkt_colsum_host's two launches, for every column
+      Sum A{k->m_rBp, k->m_part, (long long)L.S, (long long)ne, (long long)per, (long long)(L.S * ne), (long long)wp, (long long)(nrc * ncc)};
+      if ((rc = kkt_launch_raw(m, k->km->colsum_m, &A, sizeof A, nr * nrc * ncc, 256))) return rc;
+      Sum B{k->m_part, k->m_part + 512 * ne, (long long)nrc, (long long)ne, (long long)nrc, (long long)wp, (long long)wp, (long long)ncc};
+      if ((rc = kkt_launch_raw(m, k->km->colsum_m, &B, sizeof B, nr * ncc, 256))) return rc;
+      if (L.n_border) {
+        HIP_TRY(hipMemsetAsync(k->m_xB, 0, (size_t)(nr * ne) * 8, m->stream));
+        if ((rc = move(Mv{k->m_xB, rhs, k->d_bloc, k->d_border, 0, (long long)ne, (long long)ld_rhs, nr}, L.n_border))) return rc;
+      }
+      rB.assign((size_t)(nr * ne), 0.0);
+      std::vector<double> rbp((size_t)(nr * ne));
+      HIP_TRY(hipStreamSynchronize(m->stream));
+      HIP_TRY(hipMemcpy2D(rbp.data(), (size_t)ne * 8, k->m_part + 512 * ne, (size_t)wp * 8, (size_t)ne * 8, (size_t)nr, hipMemcpyDeviceToHost));
+      if (L.n_border) HIP_TRY(hipMemcpy(rB.data(), k->m_xB, (size_t)(nr * ne) * 8, hipMemcpyDeviceToHost));
+      for (int u = 0; u < nr; ++u) {
+        col.assign((size_t)ne, 0.0);
+        for (int i = 0; i < ne; ++i) col[(size_t)i] = (i < L.n_border ? rB[(size_t)(u * ne + i)] : 0.0) - rbp[(size_t)(u * ne + i)];
+        if (!iem::dense_solve(k->Gs, L.ne, col)) return fail(IEM_E_ARG, "iem_kkt_solve: the border's Schur complement is singular");
+        std::copy(col.begin(), col.end(), rB.begin() + (size_t)u * (size_t)ne);
+      }
+      HIP_TRY(hipMemcpyAsync(k->m_xB, rB.data(), (size_t)(nr * ne) * 8, hipMemcpyHostToDevice, m->stream));
+      HIP_TRY(hipStreamSynchronize(m->stream));      // (rB is a host temporary)
+    }
+    if ((rc = chain(nr, 1))) return rc;
+    if ((rc = move(Mv{sol, k->m_r, k->d_on, k->d_pos, 0, (long long)ld_sol, (long long)pl, nr}, k->n_on))) return rc;
+    if (L.n_border && (rc = move(Mv{sol, k->m_xB, k->d_border, k->d_bloc, 0, (long long)ld_sol, (long long)ne, nr}, L.n_border))) return rc;
+  }
   return IEM_OK;
 }
 

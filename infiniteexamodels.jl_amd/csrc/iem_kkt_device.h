@@ -648,6 +648,9 @@ __device__ __forceinline__ double kkt_tdot(const double *__restrict__ M, const d
 }
 // forward, level l:   eliminated  z_i = D_i^-1 r_i,  rBp_i = Z_i' r_i ;
 //                     survivors   r_j[R] -= BR_p (D_p^-1 r_p)[C] ,  r_j[C] -= Bt_q' (D_q^-1 r_q)[R]      (64 threads per block)
+// TWINS: kkt_forward_m / kkt_backward_m (and kkt_fz_m / kkt_fs_m / kkt_bw_m, kkt_move_m, kkt_colsum_m) in csrc/iem_kkt_many_device.h repeat
+// these kernels' operations per column IN THE SAME ORDER — a column of iem_kkt_solve_many is bit for bit iem_kkt_solve of it
+// (tests/test_gpu_kkt_solve_many.py).  Any change to the arithmetic or its order here has to be made there as well.
 extern "C" __global__ __launch_bounds__(64) void kkt_forward(const KktSolveArgs A) {
   __shared__ double v[KKT_NB], zc[KKT_NC], zr[KKT_NC];
   __shared__ int rr[KKT_NC], cc[KKT_NC];
@@ -775,6 +778,7 @@ extern "C" __global__ __launch_bounds__(64) void kkt_backward(const KktSolveArgs
 //   kkt_fs   the survivors: r_j[R] -= BR_p z_p[C],  r_j[C] -= Bt_q' z_q[R]  from the stored z — a thread per survivor, NC x NC each
 //   kkt_bw   x_i = z_i - D_i^-1[:, R] (Bt_i x_p[C]) - D_i^-1[:, C] (BR_i' x_q[R]): the two NC-vectors through LDS, then a lane per entry
 // Every block inverse is read once per solve on the way up (3.2 KB for 20 x 20) and on 2 NC of its columns on the way down.
+// (TWINS in csrc/iem_kkt_many_device.h — kkt_fz_m / kkt_fs_m / kkt_bw_m: same operations, same order, see kkt_forward)
 #define KKT_SBPW (64 / KKT_NB)
 extern "C" __global__ __launch_bounds__(64) void kkt_fz(const KktSolveArgs A) {
   __shared__ double rv[KKT_SBPW * KKT_NB];

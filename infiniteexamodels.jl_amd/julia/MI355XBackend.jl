@@ -253,6 +253,8 @@ function factorize!(s::ChainKKTSolver)
 end
 solve!(s::ChainKKTSolver, x::ROCVector{Float64}) =       # in place: the right-hand side is read before the solution is written
     (check(ccall((:iem_kkt_solve, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.k, dptr(x), dptr(x))); x)
+solve!(s::ChainKKTSolver, X::ROCMatrix{Float64}) =       # the columns of X in one pass over the factors (iem_kkt_solve_many), in place
+    (check(ccall((:iem_kkt_solve_many, LIBIEM), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64), s.k, size(X, 2), dptr(X), stride(X, 2), dptr(X), stride(X, 2))); X)
 is_inertia(::ChainKKTSolver) = true
 inertia(s::ChainKKTSolver) = (s.inertia[1], s.inertia[3], s.inertia[2])      # (positive, zero, negative)
 

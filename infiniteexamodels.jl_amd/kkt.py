@@ -154,6 +154,8 @@ class KKTSystem:
 
     def solve(self, rhs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """K·sol = rhs with the current factors; ``rhs`` of length nvar + ncon (device tensor)."""
+        if rhs.dim() == 2 and self._nrhs == 1:      # (n, K): column by column
+            return torch.stack([self.solve(rhs[:, j].contiguous()) for j in range(rhs.shape[1])], 1)
         _, sol = _rocsolver()
         if rhs.numel() != self.n * self._nrhs:
             raise ValueError("rhs length")

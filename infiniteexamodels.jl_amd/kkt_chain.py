@@ -380,7 +380,14 @@ class ChainKKT:
     def solve(self, rhs, refine=1, rtol: float = 1e-9):
         """``K x = rhs`` (device tensor of length ``nvar + ncon``) with the current factors; ``refine`` steps of iterative
         refinement against the CSR matrix — or ``refine = "auto"``: up to two steps, each only while the residual exceeds
-        ``rtol * max|rhs|`` (one product with the CSR matrix decides; a solve is eight times that)."""
+        ``rtol * max|rhs|`` (one product with the CSR matrix decides; a solve is eight times that).
+
+        ``rhs`` may also be 2-D, ``(nvar + ncon, K)`` with columns of any stride: the K columns go through the levels
+        together (``iem_kkt_chain_solve_many``: the factors are read once per chunk of columns, not once per column) and
+        the result has the same shape.  Refinement is per column — with ``"auto"`` a column stops when ITS residual is
+        under ITS bound — and column ``j`` carries the bits ``solve(rhs[:, j])`` gives."""
+        if rhs.dim() == 2:
+            return self._solve_many(rhs, refine, rtol)
         x = self._solve_once(rhs)
         if refine == "auto":
             bound = rtol * max(1.0, float(rhs.abs().max().item()))
@@ -394,6 +401,63 @@ class ChainKKT:
             res = rhs - self._matvec(x)
             x = x + self._solve_once(res)
         return x
+
+    def _solve_many(self, rhs, refine, rtol):
+        t = self._torch
+        K = rhs.shape[1]
+        B = rhs.t().contiguous()                       # (K, n): a column per row, contiguous whatever the strides of rhs were
+        X = self._solve_once_many(B)
+        live = list(range(K))
+        bounds = [rtol * max(1.0, float(B[j].abs().max().item())) for j in range(K)] if refine == "auto" else None
+        for _ in range(2 if refine == "auto" else int(refine)):
+            if not live:
+                break
+            res = t.stack([B[j] - self._matvec(X[j]) for j in live])
+            if bounds is not None:
+                keep = [i for i, j in enumerate(live) if float(res[i].abs().max().item()) > bounds[j]]
+                live, res = [live[i] for i in keep], res[keep]
+                if not live:
+                    break
+            dX = self._solve_once_many(res.contiguous())
+            for i, j in enumerate(live):
+                X[j] = X[j] + dX[i]
+        return X.t()
+
+    _MANY_SLAB = 8      # columns per pass of _solve_once_many (a multiple of every chunk width of the kernels)
+
+    def _solve_once_many(self, B):
+        """``_solve_once`` for the rows of ``B`` (K, n); row for row the same arithmetic.  The rows go through in slabs of
+        ``_MANY_SLAB``: the block-ordered workspace (r, z, rBp) is at most that many columns, however large K is."""
+        if B.shape[0] > self._MANY_SLAB:
+            return self._torch.cat([self._solve_once_many(B[c0:c0 + self._MANY_SLAB]) for c0 in range(0, B.shape[0], self._MANY_SLAB)])
+        t, L, m = self._torch, self.layout, self.model
+        K, f64 = B.shape[0], dict(dtype=t.float64, device=B.device)
+        plane = L.S * L.nb
+        if getattr(self, "_many", None) is None or self._many[0].shape[0] < K:      # workspace for up to _MANY_SLAB columns, kept for the next call
+            self._many = (t.zeros(K, plane, **f64), t.empty(K, plane if L.reach > 0 else 1, **f64), t.empty(K, max(L.S * L.ne, 1), **f64))
+        r, z, rBp = (a[:K] for a in self._many)
+        r.zero_()
+        r[:, self._pos] = B[:, self._on]
+        m._sync_stream()
+        p = lambda a: C.c_void_p(a.data_ptr())
+        chained = L.reach > 0
+        args = (m._h, L.S, L.S, L.nb, L.ne, L.nc, p(self.D), p(self.B) if chained else None, p(self.BR) if chained else None,
+                p(self._rows) if chained else None, p(self._cols) if chained else None, p(self.Z), p(r), p(z) if chained else None, p(rBp))
+        xB = None
+        _lib.check(m._L.iem_kkt_chain_solve_many(*args, None, K, 0))
+        if L.ne:
+            xB = t.empty(K, L.ne, **f64)
+            for j in range(K):                         # (the border system per column, with the expressions of _solve_once: the same bits)
+                rB = t.zeros(L.ne, **f64)
+                rB[:L.n_border] = B[j][self._border]
+                rB = rB - rBp[j][:L.S * L.ne].view(L.S, L.ne).sum(0)
+                xB[j] = t.linalg.lu_solve(*self._glu, rB.unsqueeze(1)).squeeze(1)
+        _lib.check(m._L.iem_kkt_chain_solve_many(*args, p(xB) if xB is not None else None, K, 1))
+        out = t.empty_like(B)
+        out[:, self._on] = r[:, self._pos]
+        if L.ne:
+            out[:, self._border] = xB[:, :L.n_border]
+        return out
 
     def _matvec(self, x):
         """``K x`` with the CSR matrix of the last ``kkt.assemble`` (``iem_csr_spmv``)."""
@@ -793,6 +857,8 @@ class HubChainKKT:
 
     def solve(self, rhs, profile: Optional[dict] = None):
         t = self._torch
+        if rhs.dim() == 2:      # column by column (the hubs' side is matrix-vector work per column)
+            return t.stack([self.solve(rhs[:, j].contiguous(), profile) for j in range(rhs.shape[1])], 1)
         if self._levels is None:
             self.model._sync_stream()
         import time as _time

@@ -86,7 +86,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -176,6 +176,7 @@ def lib():
     L.iem_kkt_hub_level.argtypes = [vp, i64, i64, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i64, vp, vp, vp, i32]
     L.iem_kkt_chain_solve.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
     L.iem_kkt_chain_solve_lanes.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+    L.iem_kkt_chain_solve_many.argtypes = [vp, i64, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]
     L.iem_kkt_source.argtypes = [i32, i32, i32, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_kkt_create.argtypes = [vp, i32, C.POINTER(vp)]
     L.iem_kkt_destroy.argtypes = [vp]
@@ -185,6 +186,7 @@ def lib():
     L.iem_kkt_assemble.argtypes = [vp, vp, vp, vp, dbl, dbl]
     L.iem_kkt_factor.argtypes = [vp, vp]
     L.iem_kkt_solve.argtypes = [vp, vp, vp]
+    L.iem_kkt_solve_many.argtypes = [vp, i32, vp, i64, vp, i64]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_free.argtypes = [vp]
@@ -292,6 +294,12 @@ def kkt_source(nb: int, ne: int, nc: int = 12):
     finally:
         L.iem_free(p)
     return src, int(key.value)
+
+
+def kkt_many_width(nb: int, ne: int, nc: int = 12) -> int:
+    """Columns per chunk of the multi-column solves for that shape (``KKT_MR`` of its source)."""
+    import re
+    return int(re.search(r"^#define KKT_MR (\d+)$", kkt_source(nb, ne, nc)[0], re.M).group(1))
 
 
 def precompile_source(src: str, key: int, arch: str = "gfx950", defer: list = None) -> str:
