@@ -276,6 +276,20 @@ int iem_param_prepare(iem_model *m, int32_t *out_n_kernels);
 int iem_jpprod(iem_model *m, const double *d_x, const double *d_w, double *d_out);
 int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out);
 int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out);
+/* the adjoint of iem_hpprod, at the same (x, current θ) and with the same L:
+ *   iem_hptprod   (d2L/dθ dx) u                    u: nvar, out: npar
+ * With iem_jptprod(obj_weight = 0) it is the product the ADJOINT sensitivity needs: for a quantity q(x, y, θ) of a solution,
+ * one solve  K [lx; ly] = [dq/dx; dq/dy]  with the factorised (symmetric) KKT matrix, then
+ *   dq/dθ (total) = dq/dθ (partial) - [ hptprod(x, y, lx) + jptprod(x, ly, 0) ]
+ * — every entry of θ at the price of one solve, where iem_hpprod / iem_jpprod cost a solve per direction.  One fused kernel
+ * (plus the deterministic follow-ups of jptprod's scatter: no float atomics, bitwise reproducible), the output fully
+ * overwritten — entries of θ no mixed term reaches get 0 —, asynchronous on the handle's stream.  Its kernels (kind 7, names
+ * iem_hptprod*) are one more program of their own, set up by the first iem_hptprod — synchronous, outside a stream capture,
+ * like the first call of the three above — or by iem_param_prepare, which prepares BOTH programs and returns the number of
+ * kernels of both; iem_kernel_info lists the adjoint kernels behind those of the three kinds above (behind the model's own
+ * while only this program exists).  A model without any mixed term has no such kernel: the call is a memset.  npar == 0:
+ * nothing is launched.  A sharded handle refuses the call like the three above. */
+int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u, double *d_out);
 
 /* jac_structure! / hess_structure! — one-off; `base` = 1 for Julia, 0 for C/Python.
  * Hessian pairs are lower-triangular (row >= col); COO may repeat positions. */

@@ -137,6 +137,24 @@ class ExaTranscriptionBackend:
             raise ValueError("parameter_directions: no (parameter, value) pair")
         return np.stack([self.parameter_direction(pref, value) for pref, value in pairs], axis=1)
 
+    def parameter_gradient_values(self, pref, grad) -> np.ndarray:
+        """The inverse of ``parameter_direction``: the entries of a gradient over θ (length ``npar`` — what
+        ``sensitivity.parameter_gradient`` returns, as a host array) that belong to ``pref``, shaped like its values: a
+        float for a finite parameter, an array over the supports (first parameter fastest, as the function is evaluated)
+        for a parameter function."""
+        if self.core is None or pref not in self.data.param_mappings:
+            raise KeyError("parameter_gradient_values: not a transcribed finite parameter or parameter function")
+        par = self.data.param_mappings[pref]
+        grad = np.asarray(grad, dtype=np.float64)
+        if grad.shape != (self.core.npar,):
+            raise ValueError(f"parameter_gradient_values: expected a gradient of length {self.core.npar}")
+        vals = grad[par.offset:par.offset + par.length]
+        if isinstance(pref, FiniteParameterRef):
+            return float(vals[0])
+        if isinstance(pref, ParameterFunctionRef):
+            return vals.reshape(par.size, order="F").copy()
+        raise KeyError("parameter_gradient_values: not a finite parameter or parameter function")
+
     def update_start_value(self, vref, value) -> bool:
         """``InfiniteOpt.update_variable_info`` start-value branch (:553-592): writes ``core.x0``."""
         if self.core is None:

@@ -238,6 +238,9 @@ struct iem_model {
     double *d_red[iem::KK_COUNT] = {};
     long long *d_axis[iem::KK_COUNT] = {}, *d_gather[iem::KK_COUNT] = {};
   } par;
+  // the adjoint parameter kind (iem_hptprod; param_kinds = 2): a third program, set up in the same way — the source and the
+  // key of `par` do not know of it either
+  ParamKinds adj;
 };
 
 namespace {
@@ -894,7 +897,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value != 0; return IEM_OK; }
+  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value == 2 ? 2 : value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1162,6 +1165,10 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->par.d_axis) if (r) hipFree(r);
   for (long long *r : m->par.d_gather) if (r) hipFree(r);
   free_program(m->par.code);
+  for (double *r : m->adj.d_red) if (r) hipFree(r);
+  for (long long *r : m->adj.d_axis) if (r) hipFree(r);
+  for (long long *r : m->adj.d_gather) if (r) hipFree(r);
+  free_program(m->adj.code);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
   delete m;
@@ -1189,10 +1196,12 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
-  // behind the model's own kernels: those of the parameter kinds, once their program exists (after the first such call)
+  // behind the model's own kernels: those of the parameter kinds, once their program exists (after the first such call),
+  // and behind those the adjoint kind's (iem_hptprod), once ITS program exists
   const int n_own = (int)m->code.prog.kernels.size(), n_par = m->par.tried && m->par.rc == IEM_OK ? (int)m->par.code.prog.kernels.size() : 0;
-  if (k >= n_own + n_par) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : m->par.code.prog.kernels[k - n_own];
+  const int n_adj = m->adj.tried && m->adj.rc == IEM_OK ? (int)m->adj.code.prog.kernels.size() : 0;
+  if (k >= n_own + n_par + n_adj) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own] : m->adj.code.prog.kernels[k - n_own - n_par];
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
   out->kind = kd.kind;
@@ -1361,10 +1370,10 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 }
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
-// The program of the three kinds, generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the
-// model's own); a failure is remembered and reported by every later call.
-static int param_program(iem_model *m) {
-  iem_model::ParamKinds &P = m->par;
+// The program of the three kinds (P = m->par, kinds = 1) or of the adjoint kind (P = m->adj, kinds = 2), generated and loaded by
+// the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
+// later call.
+static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
   P.tried = true;
   // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
@@ -1383,13 +1392,14 @@ static int param_program(iem_model *m) {
     return rc;
   };
   iem::Options po = m->opt;
-  po.param_kinds = 1;
+  po.param_kinds = kinds;
   try {
     P.code.prog = iem::generate(m->model, po);
   } catch (const std::exception &e) {
     return done(fail(IEM_E_BLOB, e.what()));
   }
   int rc;
+  if (P.code.prog.kernels.empty()) return done(IEM_OK);   // (no mixed term at all: hptprod is the runtime's memset, no code object)
   if ((rc = load_program(m, P.code, po)) != IEM_OK) return done(rc);
   if ((rc = scatter_buffers(P.code.prog, P.d_red, P.d_gather, P.d_axis, &m->stream)) != IEM_OK) return done(rc);
   return done(prepare_program(m, P.code));
@@ -1402,8 +1412,8 @@ int iem_param_prepare(iem_model *m, int32_t *out_n_kernels) {
   int rc = param_refuse_sharded(m, "iem_param_prepare");
   if (rc) return rc;
   DevGuard dg_(m->device);
-  if ((rc = param_program(m))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->par.code.prog.kernels.size();
+  if ((rc = param_program(m, m->par, 1)) || (rc = param_program(m, m->adj, 2))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)(m->par.code.prog.kernels.size() + m->adj.code.prog.kernels.size());
   return IEM_OK;
 }
 
@@ -1414,8 +1424,7 @@ static int param_refuse_sharded(const iem_model *m, const char *what) {
 }
 
 // the launchable kernels of a parameter kind (table slot `kind`) and what runs behind them; out fully overwritten
-static int param_launch(iem_model *m, int kind, LaunchHead h) {
-  iem_model::ParamKinds &P = m->par;
+static int param_launch(iem_model *m, iem_model::ParamKinds &P, int kind, LaunchHead h) {
   h.th = m->d_theta;
   int rc;
   if (iem::KK_JTPROD == kind || iem::KK_HPROD == kind) {
@@ -1435,10 +1444,10 @@ int iem_jpprod(iem_model *m, const double *d_x, const double *d_w, double *d_out
   if (rc) return rc;
   DevGuard dg_(m->device);
   if (m->model.ncon == 0) return IEM_OK;
-  if ((rc = param_program(m))) return rc;
+  if ((rc = param_program(m, m->par, 1))) return rc;
   LaunchHead h;
   h.x = d_x; h.v = d_w; h.out = d_out;
-  return param_launch(m, iem::KK_JPROD, h);
+  return param_launch(m, m->par, iem::KK_JPROD, h);
 }
 
 int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out) {
@@ -1447,10 +1456,10 @@ int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   if (rc) return rc;
   if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m))) return rc;
+  if ((rc = param_program(m, m->par, 1))) return rc;
   LaunchHead h;
   h.x = d_x; h.v = d_y; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, iem::KK_JTPROD, h);
+  return param_launch(m, m->par, iem::KK_JTPROD, h);
 }
 
 int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out) {
@@ -1459,10 +1468,22 @@ int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_we
   if (rc) return rc;
   DevGuard dg_(m->device);
   if (m->model.nvar == 0) return IEM_OK;
-  if ((rc = param_program(m))) return rc;
+  if ((rc = param_program(m, m->par, 1))) return rc;
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, iem::KK_HPROD, h);
+  return param_launch(m, m->par, iem::KK_HPROD, h);
+}
+
+int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u, double *d_out) {
+  if (!m || !d_x || (!d_y && m->model.ncon) || (!d_u && m->model.nvar) || (!d_out && m->model.npar)) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_hptprod");
+  if (rc) return rc;
+  if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->adj, 2))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.y = d_y; h.v = d_u; h.out = d_out; h.w = obj_weight;
+  return param_launch(m, m->adj, iem::KK_HPROD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

@@ -767,6 +767,8 @@ class KernelBuilder {
   // ---- build the kernel's outputs ---------------------------------------------
   // parameter kinds (Options::param_kinds; m_ is the parameter view): slots of θ
   bool theta_kinds() const { return opt_.param_kinds != 0; }
+  // param_kinds = 2: the adjoint program, hptprod alone on the table slot of hprod — tangents on the slots of x, outputs on the slots of θ
+  bool theta_adjoint() const { return opt_.param_kinds == 2; }
   static bool has_theta_slot1(const Template &t) {
     for (int id : t.slot1_idx) if (t.is_theta_idx(id)) return true;
     return false;
@@ -776,6 +778,7 @@ class KernelBuilder {
     return false;
   }
   bool relevant(const Template &t) const {
+    if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
     if (theta_kinds()) switch (kind_) {
       case KK_JPROD: return t.kind == IEM_T_CON;           // every row is written: zero where c does not depend on θ
       case KK_JTPROD: return has_theta_slot1(t);           // constraints (seed y) and objective terms (seed σ)
@@ -930,6 +933,10 @@ class KernelBuilder {
             const bool ti_ = t.is_theta_idx(t.slot2_i[s]), tj_ = t.is_theta_idx(t.slot2_j[s]);
             if (ti_ == tj_) continue;
             const int xi = ti_ ? t.slot2_j[s] : t.slot2_i[s], pi = ti_ ? t.slot2_i[s] : t.slot2_j[s];
+            if (theta_adjoint()) {   // (d2L/dθ dx) u, the transpose: row = the entry of θ, the tangent sits on the entry of x
+              contribute(tg.pos0(pi), mul(tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s], load(4, 0, tg.pos0(xi), G.guard)), pi);
+              continue;
+            }
             contribute(tg.pos0(xi), mul(tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s], load(4, 0, tg.pos0(pi), G.guard)), xi);
           }
           for (int s = 0; s < t.o2step && !theta_kinds(); ++s) {
@@ -2485,6 +2492,8 @@ static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t
 static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"};
 // the parameter kinds (Options::param_kinds) ride on the table slots of the kinds they are shaped like
 static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod", "hpprod"};
+static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"};   // param_kinds = 2: the adjoint program
+static const char *const *kind_names(const Options &o) { return o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2731,7 +2740,7 @@ static void emit_kinds(Emitter &E) {
     Launch &L = E.emitted[kind];
     L.kind = kind; L.tile = ktile;
     for (size_t k : ks) L.bodies.push_back(Body{E.builders[k].get(), &E.descs[k], "A.out", "A.aux", E.kopts[k].xcd_remap != 0});
-    if (!emit_launch(E, L, std::string("iem_") + (opt.param_kinds ? kname_theta : kname)[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
+    if (!emit_launch(E, L, std::string("iem_") + kind_names(opt)[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
     if (kind == KK_OBJ) E.P.n_partials = L.F.grid[0];
   }
 }
@@ -2880,8 +2889,8 @@ Program generate(const Model &m, const Options &opt_in) {
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
   const bool theta = opt.param_kinds != 0;
-  // length of a scatter kind's output vector: nvar, except the parameter kind jptprod (an entry per θ)
-  auto nout = [&](int kind) { return theta && kind == KK_JTPROD ? m.npar : m.nvar; };
+  // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod and hptprod (an entry per θ)
+  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (opt.param_kinds == 2 && kind == KK_HPROD) ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
   Program P;
   P.block = opt.block;
@@ -2939,7 +2948,8 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
       if (theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
-      std::string name = std::string("iem_") + (theta ? kname_theta : kname)[kind] + "_g" + std::to_string(gi) + name_tag;
+      if (opt.param_kinds == 2 && kind != KK_HPROD) continue;
+      std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
       if (!kb->build(nullptr)) continue;
@@ -3167,7 +3177,9 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
           }
       return o.scalar ? (int64_t)1 : g.ext[0] * g.ext[1] * g.ext[2];
     };
-    if (park_atomics && opt.det_scatter < 2) {
+    // (not the adjoint parameter kind: its output must be written without any float atomic — and the atomics would need a
+    //  memset launch in front of the kernel where the gather needs its launch behind it)
+    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds != 2) {
       // at most TWO addends per entry: a + b = b + a, those atomics are already order-independent — and cheaper than
       // a second launch
       std::vector<int64_t> d0;
@@ -3236,6 +3248,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       pos = std::max(pos, c.second + 1);
     }
     if (theta && kind == KK_GRAD) continue;
+    if (opt.param_kinds == 2 && kind != KK_HPROD) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)

@@ -131,6 +131,9 @@ struct Options {
   // jpprod (dc/dθ) w, jptprod σ df/dθ + (dc/dθ)' y, hpprod (d2L/dx dθ) w.  They take the table slots, pointers and follow-ups
   // of the kinds they are shaped like (KK_JPROD / KK_JTPROD / KK_HPROD; jptprod's output has npar entries, A.w = σ), differentiate
   // over the extended vector [x; θ] (iem_model.hpp: parameter_view) and go through the same deterministic scatter machinery.
+  // 2: the ADJOINT parameter program, again one of its own (the source of 1 does not move): hptprod (d2L/dθ dx) u alone, the
+  // transpose of hpprod — the same second-order sweep with the tangent u on the slots of x and the θ slots of the mixed entries
+  // kept; it takes KK_HPROD's table slot with an output of npar entries, scattered like jptprod's.
   int param_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)

@@ -184,6 +184,14 @@ function hpprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, w
                 m.handle, dptr(x), dptr(y), obj_weight, dptr(w), dptr(out)))
     return out
 end
+# ... and the transpose of hpprod!, (∂²L/∂θ∂x)·u (u over x, out over θ): with λ = K⁻¹·[∂q/∂x; ∂q/∂y] (K symmetric),
+# dq/dθ = ∂q/∂θ - (hptprod!(x, y, λ_x) + jptprod!(x, λ_y; obj_weight = 0)) — every entry of θ from one solve.
+function hptprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, u::ROCVector{Float64},
+                  out::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_hptprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(u), dptr(out)))
+    return out
+end
 
 # ExaModels.set_parameter!(core, param, vals)  (src/infiniteopt_backend.jl:522,546)
 function set_parameter!(m::MI355XModel, param, vals)

@@ -351,16 +351,27 @@ class ExaModel:
         _lib.check(self._L.iem_hpprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(w), _ptr(out)))
         return out
 
+    def hptprod(self, x, y, u, obj_weight: float = 1.0, out=None):
+        """``(∂²L/∂θ∂x)·u`` (npar) with ``L = obj_weight·f + yᵀc``, ``u`` of length ``nvar``: the transpose of ``hpprod`` —
+        what the adjoint sensitivity (``sensitivity.parameter_gradient``) multiplies the solved multipliers with."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(y, self.meta.ncon, "y"); self._chk(u, self.meta.nvar, "u")
+        out = out if out is not None else self._new(self.meta.npar)
+        self._chk(out, self.meta.npar, "out")
+        self._sync_stream()
+        _lib.check(self._L.iem_hptprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(u), _ptr(out)))
+        return out
+
     def param_prepare(self) -> int:
-        """Set up the program of jpprod / jptprod / hpprod now (``iem_param_prepare``: otherwise the first such call does —
-        synchronously, and not inside a stream capture); the number of its kernels."""
+        """Set up the programs of jpprod / jptprod / hpprod and of hptprod now (``iem_param_prepare``: otherwise the first
+        such call does — synchronously, and not inside a stream capture); the number of their kernels."""
         n = C.c_int32()
         _lib.check(self._L.iem_param_prepare(self._h, C.byref(n)))
         return int(n.value)
 
     def param_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of jpprod / jptprod / hpprod (kinds jprod / jtprod / hprod
-        of a program of their own, listed behind the model's kernels)."""
+        of a program of their own, listed behind the model's kernels) and, behind them, of hptprod (kind hprod of ITS
+        program, names ``iem_hptprod*``)."""
         out = []
         for k in range(self.meta.n_kernels, self.meta.n_kernels + self.param_prepare()):
             ki = _lib.KernelInfo()

@@ -5,7 +5,15 @@ At a solution the KKT conditions hold for every θ nearby, so
     K · [dx; dy] = −[∇²ₓθL · δθ ; ∂c/∂θ · δθ],      L = obj_weight·f + yᵀc,
 
 with K the KKT matrix the solver has already assembled and factorised on the device.  The right-hand side is two
-matrix-free products of the model (``ExaModel.hpprod`` / ``ExaModel.jpprod``); nothing here forms a matrix."""
+matrix-free products of the model (``ExaModel.hpprod`` / ``ExaModel.jpprod``); nothing here forms a matrix.
+
+That is FORWARD mode: one solve per direction δθ.  The ADJOINT mode (``parameter_gradient(s)``) answers "how does one
+quantity q of the solution react to every entry of θ" with one solve per quantity: with G = [∇²ₓθL ; ∂c/∂θ] the forward
+step is [dx; dy] = −K⁻¹·G·δθ, so for g = [∂q/∂x; ∂q/∂y]
+
+    dq/dθ = ∂q/∂θ + gᵀ·d[x; y]/dθ = ∂q/∂θ − Gᵀ·λ,      K·λ = g      (K symmetric),
+
+and Gᵀ·λ = ``hptprod(x, y, λ_x)`` + ``jptprod(x, λ_y, obj_weight=0)`` — two matrix-free products again."""
 from __future__ import annotations
 
 
@@ -49,3 +57,58 @@ def parameter_steps(model, kkt, x, y, dthetas, obj_weight: float = 1.0):
     buf.neg_()
     sol = kkt.solve(buf.t())
     return sol[:n], sol[n:]
+
+
+def parameter_gradient(model, kkt, x, y, gx, gy=None, obj_weight: float = 1.0, dq_dtheta=None):
+    """Total derivative ``dq/dθ`` (length ``npar``) of a quantity ``q(x, y, θ)`` of the solution at the primal-dual point
+    ``(x, y)``, from ONE solve: ``gx = ∂q/∂x`` (length ``nvar``), ``gy = ∂q/∂y`` (length ``ncon``, ``None`` = zeros) and
+    ``dq_dtheta = ∂q/∂θ`` at fixed ``(x, y)`` (``None`` = zeros).
+
+    Sign convention: the one of ``parameter_step`` — ``K·[dx; dy] = −G·δθ`` with ``G = [∇²ₓθL ; ∂c/∂θ]`` — so that
+    ``parameter_gradient(…)·δθ == ∂q/∂θ·δθ + gx·dx + gy·dy`` for the ``(dx, dy)`` of ``parameter_step(δθ)``:
+
+        λ = kkt.solve([gx; gy]),      result = dq_dtheta − (hptprod(x, y, λ_x) + jptprod(x, λ_y, obj_weight=0)).
+
+    ``kkt`` is an ASSEMBLED AND FACTORISED system at that point, as for ``parameter_step``; the formula solves with K where
+    the derivation has Kᵀ, so K MUST BE THE SYMMETRIC SYSTEM the solver factorised (``[H + Σ + δw·I, Jᵀ; J, −δc·I]`` — what
+    ``kkt.KKTSystem`` assembles and the chain solvers factorise), not an unsymmetric reduction of it."""
+    import torch
+    n, mc = model.meta.nvar, model.meta.ncon
+    g = torch.zeros(n + mc, dtype=x.dtype, device=x.device)
+    g[:n].copy_(torch.as_tensor(gx, dtype=x.dtype, device=x.device))
+    if gy is not None:
+        g[n:].copy_(torch.as_tensor(gy, dtype=x.dtype, device=x.device))
+    lam = kkt.solve(g)
+    out = model.hptprod(x, y, lam[:n].contiguous(), obj_weight=obj_weight)
+    out += model.jptprod(x, lam[n:].contiguous(), obj_weight=0.0)
+    out.neg_()
+    if dq_dtheta is not None:
+        out += torch.as_tensor(dq_dtheta, dtype=x.dtype, device=x.device)
+    return out
+
+
+def parameter_gradients(model, kkt, x, y, G, obj_weight: float = 1.0, dq_dtheta=None):
+    """``(npar, K)``: ``parameter_gradient`` of K quantities at once.  ``G`` has shape ``(nvar + ncon, K)``, column j =
+    ``[∂q_j/∂x; ∂q_j/∂y]``; ``dq_dtheta`` is ``None`` (zeros) or ``(npar, K)``.  The factorised system is solved ONCE with
+    the 2-D right-hand side (``ChainKKT.solve`` reads its factors once per chunk of columns), then K pairs of matrix-free
+    products write the rows of one buffer.  Sign convention and the symmetry K must have: see ``parameter_gradient``."""
+    import torch
+    n, mc, npar = model.meta.nvar, model.meta.ncon, model.meta.npar
+    G = torch.as_tensor(G, dtype=x.dtype, device=x.device)
+    if G.dim() != 2 or G.shape[0] != n + mc:
+        raise ValueError("parameter_gradients: G must be (nvar + ncon, K)")
+    K = G.shape[1]
+    if K < 1:
+        raise ValueError("parameter_gradients: no column")
+    lam = kkt.solve(G).t().contiguous()          # a quantity per ROW: the products read contiguous slices
+    buf = torch.empty(K, npar, dtype=x.dtype, device=x.device)
+    tmp = torch.empty(npar, dtype=x.dtype, device=x.device)
+    for j in range(K):
+        model.hptprod(x, y, lam[j, :n], obj_weight=obj_weight, out=buf[j])
+        model.jptprod(x, lam[j, n:], obj_weight=0.0, out=tmp)
+        buf[j] += tmp
+    buf.neg_()
+    out = buf.t()
+    if dq_dtheta is not None:
+        out = out + torch.as_tensor(dq_dtheta, dtype=x.dtype, device=x.device)
+    return out
