@@ -290,6 +290,23 @@ int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_we
  * while only this program exists).  A model without any mixed term has no such kernel: the call is a memset.  npar == 0:
  * nothing is launched.  A sharded handle refuses the call like the three above. */
 int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u, double *d_out);
+/* the θθ block of the same L, at the same (x, current θ):
+ *   iem_hppprod   (d2L/dθ2) w                      w: npar, out: npar          (d2L/dθ2)' = d2L/dθ2
+ * The term the Hessian of the VALUE FUNCTION  φ(θ) = L(x*(θ), y*(θ), θ)  needs beside the products above: with one solve
+ *   K [dx; dy] = -[ hpprod(δθ); jpprod(δθ) ]   (the parameter step),
+ *   φ''(θ) δθ = hppprod(x, y, δθ) + hptprod(x, y, dx) + jptprod(x, dy, obj_weight = 0)
+ * (φ'(θ) = jptprod(x*, y*, obj_weight) by the envelope theorem).  One fused kernel (plus the deterministic follow-ups of
+ * jptprod's scatter: no float atomics, bitwise reproducible), the output fully overwritten — entries of θ no θθ term reaches
+ * get 0 —, asynchronous on the handle's stream.  Its kernels (kind 7, names iem_hppprod*) are a FOURTH program of their own,
+ * set up by the first iem_hppprod — synchronous, outside a stream capture; every later call is asynchronous and capturable —
+ * or by iem_hppprod_prepare (idempotent; returns the number of this program's kernels; a runtime failure is not remembered).
+ * iem_param_prepare does NOT prepare it and its count does not include it.  iem_kernel_info index rule: the model's own
+ * kernels first, then those of every program that exists on the handle in the order  three kinds / adjoint / θθ  — the θθ
+ * kernels are always the LAST ones, at  total - n .. total - 1  with n the count iem_hppprod_prepare returns.  A model
+ * without a θθ slot (θ read by linear templates only) has no such kernel: the call is a memset.  npar == 0: nothing is
+ * launched.  A sharded handle refuses both calls like the four above. */
+int iem_hppprod_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out);
 
 /* jac_structure! / hess_structure! — one-off; `base` = 1 for Julia, 0 for C/Python.
  * Hessian pairs are lower-triangular (row >= col); COO may repeat positions. */

@@ -241,6 +241,9 @@ struct iem_model {
   // the adjoint parameter kind (iem_hptprod; param_kinds = 2): a third program, set up in the same way — the source and the
   // key of `par` do not know of it either
   ParamKinds adj;
+  // the θθ kind (iem_hppprod; param_kinds = 3): a fourth program, set up by its own first call or by iem_hppprod_prepare —
+  // iem_param_prepare does not know of it
+  ParamKinds th2;
 };
 
 namespace {
@@ -897,7 +900,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value == 2 ? 2 : value != 0; return IEM_OK; }
+  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value == 2 || value == 3 ? (int)value : value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1169,6 +1172,10 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->adj.d_axis) if (r) hipFree(r);
   for (long long *r : m->adj.d_gather) if (r) hipFree(r);
   free_program(m->adj.code);
+  for (double *r : m->th2.d_red) if (r) hipFree(r);
+  for (long long *r : m->th2.d_axis) if (r) hipFree(r);
+  for (long long *r : m->th2.d_gather) if (r) hipFree(r);
+  free_program(m->th2.code);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
   delete m;
@@ -1197,11 +1204,13 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
   // behind the model's own kernels: those of the parameter kinds, once their program exists (after the first such call),
-  // and behind those the adjoint kind's (iem_hptprod), once ITS program exists
+  // behind those the adjoint kind's (iem_hptprod), once ITS program exists, and last the θθ kind's (iem_hppprod)
   const int n_own = (int)m->code.prog.kernels.size(), n_par = m->par.tried && m->par.rc == IEM_OK ? (int)m->par.code.prog.kernels.size() : 0;
   const int n_adj = m->adj.tried && m->adj.rc == IEM_OK ? (int)m->adj.code.prog.kernels.size() : 0;
-  if (k >= n_own + n_par + n_adj) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own] : m->adj.code.prog.kernels[k - n_own - n_par];
+  const int n_th2 = m->th2.tried && m->th2.rc == IEM_OK ? (int)m->th2.code.prog.kernels.size() : 0;
+  if (k >= n_own + n_par + n_adj + n_th2) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own]
+                            : k < n_own + n_par + n_adj ? m->adj.code.prog.kernels[k - n_own - n_par] : m->th2.code.prog.kernels[k - n_own - n_par - n_adj];
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
   out->kind = kd.kind;
@@ -1370,8 +1379,8 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 }
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
-// The program of the three kinds (P = m->par, kinds = 1) or of the adjoint kind (P = m->adj, kinds = 2), generated and loaded by
-// the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
+// The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2) or of the θθ kind
+// (P = m->th2, kinds = 3), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
 // later call.
 static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
@@ -1399,7 +1408,7 @@ static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
     return done(fail(IEM_E_BLOB, e.what()));
   }
   int rc;
-  if (P.code.prog.kernels.empty()) return done(IEM_OK);   // (no mixed term at all: hptprod is the runtime's memset, no code object)
+  if (P.code.prog.kernels.empty()) return done(IEM_OK);   // (no mixed / no θθ term at all: hptprod / hppprod is the runtime's memset, no code object)
   if ((rc = load_program(m, P.code, po)) != IEM_OK) return done(rc);
   if ((rc = scatter_buffers(P.code.prog, P.d_red, P.d_gather, P.d_axis, &m->stream)) != IEM_OK) return done(rc);
   return done(prepare_program(m, P.code));
@@ -1414,6 +1423,16 @@ int iem_param_prepare(iem_model *m, int32_t *out_n_kernels) {
   DevGuard dg_(m->device);
   if ((rc = param_program(m, m->par, 1)) || (rc = param_program(m, m->adj, 2))) return rc;
   if (out_n_kernels) *out_n_kernels = (int32_t)(m->par.code.prog.kernels.size() + m->adj.code.prog.kernels.size());
+  return IEM_OK;
+}
+
+int iem_hppprod_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = param_refuse_sharded(m, "iem_hppprod_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->th2, 3))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->th2.code.prog.kernels.size();
   return IEM_OK;
 }
 
@@ -1484,6 +1503,18 @@ int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_u; h.out = d_out; h.w = obj_weight;
   return param_launch(m, m->adj, iem::KK_HPROD, h);
+}
+
+int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out) {
+  if (!m || !d_x || (!d_y && m->model.ncon) || ((!d_w || !d_out) && m->model.npar)) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_hppprod");
+  if (rc) return rc;
+  if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->th2, 3))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
+  return param_launch(m, m->th2, iem::KK_HPROD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

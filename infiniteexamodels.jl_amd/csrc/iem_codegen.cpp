@@ -769,6 +769,8 @@ class KernelBuilder {
   bool theta_kinds() const { return opt_.param_kinds != 0; }
   // param_kinds = 2: the adjoint program, hptprod alone on the table slot of hprod — tangents on the slots of x, outputs on the slots of θ
   bool theta_adjoint() const { return opt_.param_kinds == 2; }
+  // param_kinds = 3: the θθ program, hppprod alone on the same table slot — tangents AND outputs on the slots of θ
+  bool theta_second() const { return opt_.param_kinds == 3; }
   static bool has_theta_slot1(const Template &t) {
     for (int id : t.slot1_idx) if (t.is_theta_idx(id)) return true;
     return false;
@@ -777,7 +779,12 @@ class KernelBuilder {
     for (size_t s = 0; s < t.slot2_i.size(); ++s) if (t.is_theta_idx(t.slot2_i[s]) != t.is_theta_idx(t.slot2_j[s])) return true;
     return false;
   }
+  static bool has_theta_slot2(const Template &t) {
+    for (size_t s = 0; s < t.slot2_i.size(); ++s) if (t.is_theta_idx(t.slot2_i[s]) && t.is_theta_idx(t.slot2_j[s])) return true;
+    return false;
+  }
   bool relevant(const Template &t) const {
+    if (theta_second()) return kind_ == KK_HPROD && has_theta_slot2(t);
     if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
     if (theta_kinds()) switch (kind_) {
       case KK_JPROD: return t.kind == IEM_T_CON;           // every row is written: zero where c does not depend on θ
@@ -929,7 +936,7 @@ class KernelBuilder {
             if (it == dest.end()) { dest.emplace(pos_id, val); dest_tidx.emplace(pos_id, tidx); dest_order.push_back(pos_id); }
             else it->second = add(it->second, val);
           };
-          for (int s = 0; s < t.o2step && theta_kinds(); ++s) {   // (d2L/dx dθ) w: the mixed slots only, row = the entry of x
+          for (int s = 0; s < t.o2step && theta_kinds() && !theta_second(); ++s) {   // (d2L/dx dθ) w: the mixed slots only, row = the entry of x
             const bool ti_ = t.is_theta_idx(t.slot2_i[s]), tj_ = t.is_theta_idx(t.slot2_j[s]);
             if (ti_ == tj_) continue;
             const int xi = ti_ ? t.slot2_j[s] : t.slot2_i[s], pi = ti_ ? t.slot2_i[s] : t.slot2_j[s];
@@ -939,7 +946,9 @@ class KernelBuilder {
             }
             contribute(tg.pos0(xi), mul(tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s], load(4, 0, tg.pos0(pi), G.guard)), xi);
           }
-          for (int s = 0; s < t.o2step && !theta_kinds(); ++s) {
+          // the plain kind, and (d2L/dθ2) w: the same arithmetic on the slots with both entries in θ — tangent and row over θ
+          for (int s = 0; s < t.o2step && (!theta_kinds() || theta_second()); ++s) {
+            if (theta_second() && !(t.is_theta_idx(t.slot2_i[s]) && t.is_theta_idx(t.slot2_j[s]))) continue;
             int h = tg.slots2[s] < 0 ? C(0.0) : tg.slots2[s];
             int ia = tg.idx1(t.slot2_i[s]), ib = tg.idx1(t.slot2_j[s]);
             int pa = tg.pos0(t.slot2_i[s]), pb = tg.pos0(t.slot2_j[s]);
@@ -2493,7 +2502,8 @@ static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod
 // the parameter kinds (Options::param_kinds) ride on the table slots of the kinds they are shaped like
 static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod", "hpprod"};
 static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"};   // param_kinds = 2: the adjoint program
-static const char *const *kind_names(const Options &o) { return o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"};   // param_kinds = 3: the θθ program
+static const char *const *kind_names(const Options &o) { return o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2889,8 +2899,8 @@ Program generate(const Model &m, const Options &opt_in) {
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
   const bool theta = opt.param_kinds != 0;
-  // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod and hptprod (an entry per θ)
-  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (opt.param_kinds == 2 && kind == KK_HPROD) ? m.npar : m.nvar; };
+  // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod, hptprod and hppprod (an entry per θ)
+  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (opt.param_kinds >= 2 && kind == KK_HPROD) ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
   Program P;
   P.block = opt.block;
@@ -2948,7 +2958,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
       if (theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
-      if (opt.param_kinds == 2 && kind != KK_HPROD) continue;
+      if (opt.param_kinds >= 2 && kind != KK_HPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3177,9 +3187,9 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
           }
       return o.scalar ? (int64_t)1 : g.ext[0] * g.ext[1] * g.ext[2];
     };
-    // (not the adjoint parameter kind: its output must be written without any float atomic — and the atomics would need a
+    // (not the adjoint parameter kind, nor the θθ kind: its output must be written without any float atomic — and the atomics would need a
     //  memset launch in front of the kernel where the gather needs its launch behind it)
-    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds != 2) {
+    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2) {
       // at most TWO addends per entry: a + b = b + a, those atomics are already order-independent — and cheaper than
       // a second launch
       std::vector<int64_t> d0;
@@ -3248,7 +3258,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       pos = std::max(pos, c.second + 1);
     }
     if (theta && kind == KK_GRAD) continue;
-    if (opt.param_kinds == 2 && kind != KK_HPROD) continue;
+    if (opt.param_kinds >= 2 && kind != KK_HPROD) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)

@@ -134,6 +134,9 @@ struct Options {
   // 2: the ADJOINT parameter program, again one of its own (the source of 1 does not move): hptprod (d2L/dθ dx) u alone, the
   // transpose of hpprod — the same second-order sweep with the tangent u on the slots of x and the θ slots of the mixed entries
   // kept; it takes KK_HPROD's table slot with an output of npar entries, scattered like jptprod's.
+  // 3: the θθ program, one more of its own (the sources of 1 and 2 do not move): hppprod (d2L/dθ2) w alone — the second-order
+  // slots with BOTH entries in θ, hprod's arithmetic on them (the symmetric addend behind the same select), tangent and
+  // output over θ; KK_HPROD's table slot again, npar entries out, scattered like hptprod's (no float atomic).
   int param_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)

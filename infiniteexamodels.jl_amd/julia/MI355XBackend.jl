@@ -192,6 +192,14 @@ function hptprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, 
                 m.handle, dptr(x), dptr(y), obj_weight, dptr(u), dptr(out)))
     return out
 end
+# ... and the θθ block (∂²L/∂θ²)·w (w and out over θ; symmetric): with (dx, dy) the parameter step of δθ,
+# φ''(θ)·δθ = hppprod!(x, y, δθ) + hptprod!(x, y, dx) + jptprod!(x, dy; obj_weight = 0) for the value function φ(θ) = L(x*(θ), y*(θ), θ).
+function hppprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, w::ROCVector{Float64},
+                  out::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_hppprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(w), dptr(out)))
+    return out
+end
 
 # ExaModels.set_parameter!(core, param, vals)  (src/infiniteopt_backend.jl:522,546)
 function set_parameter!(m::MI355XModel, param, vals)

@@ -361,6 +361,29 @@ class ExaModel:
         _lib.check(self._L.iem_hptprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(u), _ptr(out)))
         return out
 
+    def hppprod(self, x, y, w, obj_weight: float = 1.0, out=None):
+        """``(∂²L/∂θ²)·w`` (npar) with ``L = obj_weight·f + yᵀc``, ``w`` of length ``npar``: the θθ block (symmetric) — the
+        direct term of the value function's Hessian-vector product (``sensitivity.value_hessian_product``)."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(y, self.meta.ncon, "y"); self._chk(w, self.meta.npar, "w")
+        out = out if out is not None else self._new(self.meta.npar)
+        self._chk(out, self.meta.npar, "out")
+        self._sync_stream()
+        _lib.check(self._L.iem_hppprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(w), _ptr(out)))
+        return out
+
+    def hppprod_prepare(self) -> int:
+        """Set up the program of hppprod now (``iem_hppprod_prepare``: otherwise the first ``hppprod`` does — synchronously,
+        and not inside a stream capture); the number of its kernels.  ``param_prepare`` does not include it."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_hppprod_prepare(self._h, C.byref(n)))
+        return int(n.value)
+
+    def hppprod_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of hppprod alone (kind hprod of its own program, names
+        ``iem_hppprod*``): they are listed behind the model's kernels and those ``param_kernels`` returns."""
+        first = self.meta.n_kernels + self.param_prepare()
+        return self._kernel_infos(first, first + self.hppprod_prepare())
+
     def param_prepare(self) -> int:
         """Set up the programs of jpprod / jptprod / hpprod and of hptprod now (``iem_param_prepare``: otherwise the first
         such call does — synchronously, and not inside a stream capture); the number of their kernels."""
@@ -372,11 +395,14 @@ class ExaModel:
         """Launch shape and algorithmic traffic of the kernels of jpprod / jptprod / hpprod (kinds jprod / jtprod / hprod
         of a program of their own, listed behind the model's kernels) and, behind them, of hptprod (kind hprod of ITS
         program, names ``iem_hptprod*``)."""
+        return self._kernel_infos(self.meta.n_kernels, self.meta.n_kernels + self.param_prepare())
+
+    def _kernel_infos(self, first: int, last: int):
         out = []
-        for k in range(self.meta.n_kernels, self.meta.n_kernels + self.param_prepare()):
+        for k in range(first, last):
             ki = _lib.KernelInfo()
             _lib.check(self._L.iem_kernel_info(self._h, k, C.byref(ki)))
-            out.append(dict(name=ki.name.decode(), kind=KERNEL_KINDS[ki.kind], grid=tuple(ki.grid), lds_bytes=int(ki.lds_bytes),
+            out.append(dict(name=ki.name.decode(), kind=KERNEL_KINDS[ki.kind], grid=tuple(ki.grid), lds_bytes=int(ki.lds_bytes), jit=bool(ki.jit),
                             alg_bytes_read=int(ki.alg_bytes_read), alg_bytes_written=int(ki.alg_bytes_written)))
         return out
 

@@ -13,7 +13,16 @@ step is [dx; dy] = −K⁻¹·G·δθ, so for g = [∂q/∂x; ∂q/∂y]
 
     dq/dθ = ∂q/∂θ + gᵀ·d[x; y]/dθ = ∂q/∂θ − Gᵀ·λ,      K·λ = g      (K symmetric),
 
-and Gᵀ·λ = ``hptprod(x, y, λ_x)`` + ``jptprod(x, λ_y, obj_weight=0)`` — two matrix-free products again."""
+and Gᵀ·λ = ``hptprod(x, y, λ_x)`` + ``jptprod(x, λ_y, obj_weight=0)`` — two matrix-free products again.
+
+SECOND ORDER: the value function φ(θ) = L(x*(θ), y*(θ), θ) an outer problem optimises (parameter estimation, MPC tuning,
+bilevel design).  At a KKT point its gradient is the partial one (envelope theorem): φ'(θ) = ``jptprod(x*, y*, σ)``
+(``value_gradient``).  Differentiating once more along δθ, with [dx; dy] = −K⁻¹·G·δθ the forward step,
+
+    φ''(θ)·δθ = L_θθ·δθ + Gᵀ·[dx; dy] = (L_θθ − Gᵀ·K⁻¹·G)·δθ
+              = ``hppprod(x, y, δθ)`` + ``hptprod(x, y, dx)`` + ``jptprod(x, dy, obj_weight=0)``
+
+(``value_hessian_product(s)``): one solve and three matrix-free products per direction."""
 from __future__ import annotations
 
 
@@ -112,3 +121,62 @@ def parameter_gradients(model, kkt, x, y, G, obj_weight: float = 1.0, dq_dtheta=
     if dq_dtheta is not None:
         out = out + torch.as_tensor(dq_dtheta, dtype=x.dtype, device=x.device)
     return out
+
+
+def value_gradient(model, x, y, obj_weight: float = 1.0):
+    """Gradient (length ``npar``) of the value function ``φ(θ) = L(x*(θ), y*(θ), θ)``, ``L = obj_weight·f + yᵀc``: an alias
+    for ``model.jptprod(x, y, obj_weight)``.  That is the envelope theorem — the terms through ``dx*/dθ`` and ``dy*/dθ``
+    vanish because ``∇ₓL = 0`` and ``c = 0`` — so it is the gradient of φ ONLY AT A KKT POINT ``(x*, y*)``; anywhere else
+    it is just the partial derivative ``∂L/∂θ``."""
+    return model.jptprod(x, y, obj_weight=obj_weight)
+
+
+def value_hessian_product(model, kkt, x, y, dtheta, obj_weight: float = 1.0):
+    """``φ''(θ)·dtheta`` (length ``npar``) for the value function ``φ(θ) = L(x*(θ), y*(θ), θ)`` at the KKT point ``(x, y)``:
+    one ``parameter_step`` (ONE solve), then
+
+        hppprod(x, y, dtheta) + hptprod(x, y, dx) + jptprod(x, dy, obj_weight=0).
+
+    Sign convention: the one of ``parameter_step`` — ``K·[dx; dy] = −G·δθ`` with ``G = [∇²ₓθL ; ∂c/∂θ]`` — so the result is
+    ``(L_θθ − Gᵀ·K⁻¹·G)·δθ``.  It is exactly that ONLY FOR THE K THAT WAS FACTORISED: the regularisation (δw, δc) and the
+    barrier term Σ the solver put into ``kkt`` are part of it.  With the unregularised K of the reduced problem it is the
+    Hessian of φ; with what an interior-point iteration left behind it is that of the barrier problem's regularised model.
+    K must be the symmetric system (see ``parameter_gradient``) for the result to be symmetric in δθ."""
+    dtheta = _as(dtheta, x)
+    dx, dy = parameter_step(model, kkt, x, y, dtheta, obj_weight=obj_weight)
+    out = model.hppprod(x, y, dtheta, obj_weight=obj_weight)
+    out += model.hptprod(x, y, dx.contiguous(), obj_weight=obj_weight)
+    out += model.jptprod(x, dy.contiguous(), obj_weight=0.0)
+    return out
+
+
+def value_hessian_products(model, kkt, x, y, dthetas, obj_weight: float = 1.0):
+    """``(npar, K)``: ``value_hessian_product`` for K directions at once.  ``dthetas`` is what ``parameter_steps`` takes
+    (``(npar, K)`` or a list of K directions); the factorised system is solved ONCE with the 2-D right-hand side, then K
+    triples of matrix-free products write the rows of one buffer.  Exact only for the K that was factorised — its
+    regularisation and Σ are part of the result; see ``value_hessian_product``."""
+    import torch
+    n, npar = model.meta.nvar, model.meta.npar
+    if isinstance(dthetas, (list, tuple)):
+        cols = [_as(d, x) for d in dthetas]
+    else:
+        D = _as(dthetas, x)
+        if D.dim() != 2:
+            raise ValueError("value_hessian_products: dthetas must be (npar, K) or a list of K directions")
+        cols = [D[:, j].contiguous() for j in range(D.shape[1])]
+    dX, dY = parameter_steps(model, kkt, x, y, cols, obj_weight=obj_weight)
+    dX, dY = dX.t().contiguous(), dY.t().contiguous()      # a direction per ROW: the products read contiguous slices
+    buf = torch.empty(len(cols), npar, dtype=x.dtype, device=x.device)
+    tmp = torch.empty(npar, dtype=x.dtype, device=x.device)
+    for j, d in enumerate(cols):
+        model.hppprod(x, y, d, obj_weight=obj_weight, out=buf[j])
+        model.hptprod(x, y, dX[j], obj_weight=obj_weight, out=tmp)
+        buf[j] += tmp
+        model.jptprod(x, dY[j], obj_weight=0.0, out=tmp)
+        buf[j] += tmp
+    return buf.t()
+
+
+def _as(v, like):
+    import torch
+    return torch.as_tensor(v, dtype=like.dtype, device=like.device)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Durations of the four parameter kinds (jpprod, jptprod, hpprod, hptprod) beside their algorithmic bytes.
+"""Durations of the five parameter kinds (jpprod, jptprod, hpprod, hptprod, hppprod) beside their algorithmic bytes.
 
 Per case one child process under its own `timeout` (the parent never opens the GPU and stops at the first child that
 fails): every kind is warmed, then timed in blocks of back-to-back launches between one event pair, alternating the kinds,
@@ -7,7 +7,7 @@ fails): every kind is warmed, then timed in blocks of back-to-back launches betw
 (iem_kernel_info: alg_bytes_read / alg_bytes_written summed over the kernels of the kind; follow-up launches — memsets,
 axis sums, the plan-driven gather — are not in them but are in the time).
 
-  python tools/param_kinds_bench.py --out profiles/param_kinds.json
+  python tools/param_kinds_bench.py --out profiles/hppprod.json          (profiles/param_kinds.json: the run before hppprod existed)
   python tools/param_kinds_bench.py --case quadrotor_100000          (one case, JSON on stdout)
 """
 import argparse
@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CASES = {"quadrotor_100000": ("quadrotor", 100_000), "quadrotor_1000000": ("quadrotor", 1_000_000), "heat_400x401": ("heat", (400, 401))}
-KINDS = ("jpprod", "jptprod", "hpprod", "hptprod")
+KINDS = ("jpprod", "jptprod", "hpprod", "hptprod", "hppprod")
 
 
 def one(case, launches, repeats):
@@ -37,14 +37,16 @@ def one(case, launches, repeats):
     rng = np.random.default_rng(0)
     xd = torch.tensor(gm.meta.x0 + 0.1 * rng.standard_normal(n), device="cuda")
     yd, wd, ud = (torch.tensor(rng.standard_normal(k), device="cuda") for k in (mc, npar, n))
-    outs = {"jpprod": mc, "jptprod": npar, "hpprod": n, "hptprod": npar}
+    outs = {"jpprod": mc, "jptprod": npar, "hpprod": n, "hptprod": npar, "hppprod": npar}
     bufs = {k: [torch.empty(max(v, 1), dtype=torch.float64, device="cuda") for _ in range(3)] for k, v in outs.items()}
     p = lambda a: C.c_void_p(a.data_ptr())
     L, h = gm._L, gm._h
     gm.param_prepare()
+    gm.hppprod_prepare()
     gm._sync_stream()
     call = {"jpprod": lambda o: L.iem_jpprod(h, p(xd), p(wd), p(o)), "jptprod": lambda o: L.iem_jptprod(h, p(xd), p(yd), 1.0, p(o)),
-            "hpprod": lambda o: L.iem_hpprod(h, p(xd), p(yd), 1.0, p(wd), p(o)), "hptprod": lambda o: L.iem_hptprod(h, p(xd), p(yd), 1.0, p(ud), p(o))}
+            "hpprod": lambda o: L.iem_hpprod(h, p(xd), p(yd), 1.0, p(wd), p(o)), "hptprod": lambda o: L.iem_hptprod(h, p(xd), p(yd), 1.0, p(ud), p(o)),
+            "hppprod": lambda o: L.iem_hppprod(h, p(xd), p(yd), 1.0, p(wd), p(o))}
     for k in KINDS:
         for o in bufs[k]:
             for _ in range(30):
@@ -60,7 +62,7 @@ def one(case, launches, repeats):
                 call[k](o)
             e1.record(); torch.cuda.synchronize()
             us[k].append(e0.elapsed_time(e1) / launches * 1e3)
-    kernels = gm.param_kernels()
+    kernels = gm.param_kernels() + gm.hppprod_kernels()
     res = {"case": case, "nvar": n, "ncon": mc, "npar": npar, "launches_per_block": launches, "repeats": repeats,
            "jit": bool(any(k["jit"] for k in gm.kernels())), "device": torch.cuda.get_device_name(0), "kinds": {}}
     for k in KINDS:
@@ -82,7 +84,7 @@ def main():
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--timeout", type=int, default=400, help="seconds per case (child process)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "param_kinds.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hppprod.json"))
     a = ap.parse_args()
     if a.case:
         print(json.dumps(one(a.case, a.launches, a.repeats)))
