@@ -307,6 +307,47 @@ int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
  * launched.  A sharded handle refuses both calls like the four above. */
 int iem_hppprod_prepare(iem_model *m, int32_t *out_n_kernels);
 int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out);
+/* the three blocks themselves, in COO, at the same (x, current θ) and with the same L:
+ *   Jθ  = dc/dθ        ncon x npar   iem_jacp_structure    iem_jacp_coord
+ *   Hxθ = d2L/dx dθ    nvar x npar   iem_hessxp_structure  iem_hessp_coord, d_hessxp
+ *   Hθθ = d2L/dθ2      npar x npar   iem_hesspp_structure  iem_hessp_coord, d_hesspp
+ * What a host with its own linear algebra assembles G = [Hxθ; Jθ] from (K dX = -G, the sensitivity matrix d(x, y)/dθ), and
+ * the sparse form of iem_hpprod's output: only the entries that exist are written.
+ * PATTERN: symbolic — every kept slot of the model's templates, whatever x, y and θ are; an entry may be numerically zero.
+ * iem_param_coord_nnz returns the three lengths {Jθ, Hxθ, Hθθ}; a model without θ, or whose θ no template of a block
+ * reads, has 0 there and the call launches nothing for it.
+ * SLOT ORDER (the structure calls are the authority): per block, the templates in the order they were added; within a
+ * template, item ordinal times the block's slots per item; within an item, the order in which the template's first-order
+ * (Jθ) or second-order (Hxθ, Hθθ) slots over the extended vector [x; θ] list the kept ones — a left-to-right, depth-first
+ * walk of the expression, first occurrence of an entry (of an ordered pair of entries) opens its slot.  Jθ keeps the θ slots
+ * of the constraint templates; Hxθ the second-order slots with exactly one entry in θ; Hθθ those with both; a slot whose
+ * entries both lie in x is not part of any block (it belongs to hess_coord!).
+ * Hxθ is rectangular: row = the entry of x, column = the entry of θ, whichever operand order the slot has.  Hθθ follows
+ * hess_coord!: ONE triangle (row >= col, as iem_hess_structure reports), a slot (a, b) with a != b carries the sum of both
+ * orders, a slot whose two θ entries can coincide is doubled where they do, exactly as the Hessian of x handles it; the
+ * consumer sums duplicate positions (all three blocks may repeat a position) and mirrors the strict triangle.
+ * iem_jacp_coord writes Jθ's values; iem_hessp_coord writes Hxθ's and Hθθ's from ONE second-order sweep (one launch, two
+ * output streams).  Either output of iem_hessp_coord may be NULL — required for nothing when its block is empty; for a
+ * block with entries the values then go to a spare buffer the handle allocates on the FIRST call that passes NULL for that
+ * block, which is therefore synchronous and must stay outside a stream capture like the set-up call — but not both
+ * (IEM_E_ARG).  One lane per item, every slot stored exactly once through the store path of jac_coord! / hess_coord!, no
+ * atomics, bitwise reproducible from call to call, asynchronous on the handle's stream.  Their kernels (kinds 1 and 2,
+ * names iem_jacp* / iem_hessp*) are a FIFTH program of their own, set up by the first iem_jacp_coord / iem_hessp_coord —
+ * synchronous, outside a stream capture; every later call is asynchronous and capturable — or by iem_param_coord_prepare
+ * (idempotent; returns the number of this program's kernels; a runtime failure of the set-up is not remembered).
+ * iem_param_prepare and iem_hppprod_prepare do not prepare it and keep their counts; iem_kernel_info lists these kernels
+ * LAST, behind every other program that exists on the handle, with their algorithmic bytes read and written.  The
+ * structure calls and iem_param_coord_nnz need no program and no device work: they evaluate the index expressions on the
+ * host, like iem_jac_structure.  A sharded handle refuses all of them with IEM_E_ARG like the products above. */
+int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels);
+/* how many kernels iem_kernel_info answers for right now: the model's own and those of every θ program set up so far */
+int iem_kernel_count(const iem_model *m, int32_t *out_total);
+int iem_param_coord_nnz(iem_model *m, int64_t out[3]);
+int iem_jacp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base);
+int iem_hessxp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base);
+int iem_hesspp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base);
+int iem_jacp_coord(iem_model *m, const double *d_x, double *d_vals);
+int iem_hessp_coord(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_hessxp, double *d_hesspp);
 
 /* jac_structure! / hess_structure! — one-off; `base` = 1 for Julia, 0 for C/Python.
  * Hessian pairs are lower-triangular (row >= col); COO may repeat positions. */
@@ -448,6 +489,9 @@ int iem_emit_launch_plan(const void *blob, size_t nbytes, char **out_txt);
 /* Hessian structure of a blob under the current options, computed on the host (tooling/tests;
  * arrays are malloc'ed, release with iem_free). */
 int iem_blob_hess_structure(const void *blob, size_t nbytes, int base, int64_t **out_rows, int64_t **out_cols, int64_t *out_nnz);
+/* structure of one explicit θ block (iem_jacp_structure / iem_hessxp_structure / iem_hesspp_structure) from a blob alone, no
+ * device: which = 0 dc/dθ, 1 d2L/dx dθ, 2 d2L/dθ2.  The arrays are released with iem_free. */
+int iem_blob_param_coord_structure(const void *blob, size_t nbytes, int which, int base, int64_t **out_rows, int64_t **out_cols, int64_t *out_nnz);
 /* values of model array `id` as the library sees it after parsing — including the float columns it
  * synthesises when it recovers a product lattice from a flat iterator (tooling/tests; malloc'ed) */
 int iem_blob_array(const void *blob, size_t nbytes, int id, double **out_vals, int64_t *out_n);

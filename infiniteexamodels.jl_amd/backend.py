@@ -137,6 +137,17 @@ class ExaTranscriptionBackend:
             raise ValueError("parameter_directions: no (parameter, value) pair")
         return np.stack([self.parameter_direction(pref, value) for pref, value in pairs], axis=1)
 
+    def parameter_columns(self, pref) -> np.ndarray:
+        """The indices into θ (0-based, ascending — first parameter fastest for a parameter function) of the finite
+        parameter or parameter function ``pref``: the index set ``parameter_gradient_values`` cuts by, and what
+        ``sensitivity.parameter_jacobian(model, kkt, x, y, backend.parameter_columns(pref))`` takes."""
+        if self.core is None or pref not in self.data.param_mappings:
+            raise KeyError("parameter_columns: not a transcribed finite parameter or parameter function")
+        if not isinstance(pref, (FiniteParameterRef, ParameterFunctionRef)):
+            raise KeyError("parameter_columns: not a finite parameter or parameter function")
+        par = self.data.param_mappings[pref]
+        return np.arange(par.offset, par.offset + par.length, dtype=np.int64)
+
     def parameter_gradient_values(self, pref, grad) -> np.ndarray:
         """The inverse of ``parameter_direction``: the entries of a gradient over θ (length ``npar`` — what
         ``sensitivity.parameter_gradient`` returns, as a host array) that belong to ``pref``, shaped like its values: a

@@ -244,6 +244,14 @@ struct iem_model {
   // the θθ kind (iem_hppprod; param_kinds = 3): a fourth program, set up by its own first call or by iem_hppprod_prepare —
   // iem_param_prepare does not know of it
   ParamKinds th2;
+  // the explicit blocks in COO (iem_jacp_coord / iem_hessp_coord; param_kinds = 4): a fifth program, set up by its own first
+  // call or by iem_param_coord_prepare — the other prepare calls do not know of it.  `pc_view`: the parameter view with the
+  // blocks' layout (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.
+  // `d_pc_spare`: where a block the caller passed NULL for is written when it is not empty (allocated by the first such call)
+  ParamKinds pc;
+  iem::Model pc_view;
+  bool pc_have_view = false;
+  double *d_pc_spare[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -828,6 +836,39 @@ void hess_structure_host(const iem::Model &m, int64_t *rows, int64_t *cols, int 
   }
 }
 
+// the explicit θ blocks on a parameter view with its layout (iem_model.hpp: param_coord_layout); which: 0 dc/dθ (row = the
+// constraint, column = the entry of θ), 1 d2L/dx dθ (row = the entry of x, column = the entry of θ, whichever operand
+// order the slot has), 2 d2L/dθ2 (the triangle hess_structure_host reports: row >= column)
+void param_coord_structure_host(const iem::Model &v, int which, int64_t *rows, int64_t *cols, int base) {
+  for (const iem::Template &t : v.tpl) {
+    const std::vector<int> &keep = which == 0 ? t.pc1 : which == 1 ? t.pcx : t.pcp;
+    if (keep.empty()) continue;
+    const int64_t o0 = which == 0 ? t.pc_o1 : which == 1 ? t.pc_ox : t.pc_op, ns = (int64_t)keep.size();
+    ItemIdx it(v, t);
+    for (int64_t k = 0; k < t.n_items; ++k) {
+      it.eval(k);
+      for (int64_t j = 0; j < ns; ++j) {
+        const int s = keep[(size_t)j];
+        const int64_t o = o0 + ns * k + j;
+        if (which == 0) {
+          rows[o] = t.o0 + k + base;
+          cols[o] = it.idx[t.slot1_idx[s]] - 1 + base;
+          continue;
+        }
+        const int64_t a = it.idx[t.slot2_i[s]], b = it.idx[t.slot2_j[s]];
+        if (which == 1) {
+          const bool a_theta = t.is_theta_idx(t.slot2_i[s]);
+          rows[o] = (a_theta ? b : a) - 1 + base;
+          cols[o] = (a_theta ? a : b) - 1 + base;
+        } else {
+          rows[o] = (a >= b ? a : b) - 1 + base;
+          cols[o] = (a >= b ? b : a) - 1 + base;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -900,7 +941,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value == 2 || value == 3 ? (int)value : value != 0; return IEM_OK; }
+  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 4 ? (int)value : value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -996,6 +1037,25 @@ int iem_blob_hess_structure(const void *blob, size_t nbytes, int base, int64_t *
     int64_t *c = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
     if (!p.hess_classes.empty()) hess_structure_merged_host(model, p.hess_classes, r, c, base);
     else hess_structure_host(model, r, c, base);
+    *out_rows = r; *out_cols = c; *out_nnz = n;
+    return IEM_OK;
+  } catch (const std::exception &e) {
+    return fail(IEM_E_BLOB, e.what());
+  }
+}
+
+/* structure of one explicit θ block from a blob alone (no device): which = 0 dc/dθ, 1 d2L/dx dθ, 2 d2L/dθ2 */
+int iem_blob_param_coord_structure(const void *blob, size_t nbytes, int which, int base, int64_t **out_rows, int64_t **out_cols, int64_t *out_nnz) {
+  if (!out_rows || !out_cols || !out_nnz || which < 0 || which > 2) return fail(IEM_E_ARG, "bad argument");
+  try {
+    iem::Model model;
+    iem::parse_blob(blob, nbytes, model);
+    iem::Model view = iem::parameter_view(model);
+    iem::param_coord_layout(view);
+    const int64_t n = which == 0 ? view.nnzjp : which == 1 ? view.nnzhxp : view.nnzhpp;
+    int64_t *r = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
+    int64_t *c = (int64_t *)std::malloc(sizeof(int64_t) * (size_t)std::max<int64_t>(n, 1));
+    param_coord_structure_host(view, which, r, c, base);
     *out_rows = r; *out_cols = c; *out_nnz = n;
     return IEM_OK;
   } catch (const std::exception &e) {
@@ -1176,6 +1236,8 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->th2.d_axis) if (r) hipFree(r);
   for (long long *r : m->th2.d_gather) if (r) hipFree(r);
   free_program(m->th2.code);
+  free_program(m->pc.code);
+  for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
   delete m;
@@ -1208,8 +1270,9 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   const int n_own = (int)m->code.prog.kernels.size(), n_par = m->par.tried && m->par.rc == IEM_OK ? (int)m->par.code.prog.kernels.size() : 0;
   const int n_adj = m->adj.tried && m->adj.rc == IEM_OK ? (int)m->adj.code.prog.kernels.size() : 0;
   const int n_th2 = m->th2.tried && m->th2.rc == IEM_OK ? (int)m->th2.code.prog.kernels.size() : 0;
-  if (k >= n_own + n_par + n_adj + n_th2) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own]
+  const int n_pc = m->pc.tried && m->pc.rc == IEM_OK ? (int)m->pc.code.prog.kernels.size() : 0;   // ... and behind all of them the explicit blocks' (iem_jacp_coord / iem_hessp_coord)
+  if (k >= n_own + n_par + n_adj + n_th2 + n_pc) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = k >= n_own + n_par + n_adj + n_th2 ? m->pc.code.prog.kernels[k - n_own - n_par - n_adj - n_th2] : k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own]
                             : k < n_own + n_par + n_adj ? m->adj.code.prog.kernels[k - n_own - n_par] : m->th2.code.prog.kernels[k - n_own - n_par - n_adj];
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
@@ -1219,6 +1282,15 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   out->alg_bytes_read = kd.alg_bytes_read;
   out->alg_bytes_written = kd.alg_bytes_written;
   out->jit = m->jit ? 1 : 0;
+  return IEM_OK;
+}
+
+int iem_kernel_count(const iem_model *m, int32_t *out_total) {
+  if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
+  size_t n = m->code.prog.kernels.size();
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc})
+    if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
+  *out_total = (int32_t)n;
   return IEM_OK;
 }
 
@@ -1515,6 +1587,91 @@ int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
   return param_launch(m, m->th2, iem::KK_HPROD, h);
+}
+
+// ---- the blocks themselves in COO: dc/dθ, d2L/dx dθ, d2L/dθ2 at (x, the handle's current θ) ------------------------------
+// Slot order (the structure calls are the authority): template order, within a template item ordinal times kept slots per
+// item, within an item the order of the parameter view's first- / second-order slot lists.  The pattern is symbolic.
+static const iem::Model &param_coord_view(iem_model *m) {
+  if (!m->pc_have_view) {
+    m->pc_view = iem::parameter_view(m->model);
+    iem::param_coord_layout(m->pc_view);
+    m->pc_have_view = true;
+  }
+  return m->pc_view;
+}
+
+int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = param_refuse_sharded(m, "iem_param_coord_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->pc, 4))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->pc.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+int iem_param_coord_nnz(iem_model *m, int64_t out[3]) {
+  if (!m || !out) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_param_coord_nnz");
+  if (rc) return rc;
+  const iem::Model &v = param_coord_view(m);
+  out[0] = v.nnzjp; out[1] = v.nnzhxp; out[2] = v.nnzhpp;
+  return IEM_OK;
+}
+
+static int param_coord_structure(iem_model *m, int which, int64_t *h_rows, int64_t *h_cols, int base, const char *what) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = param_refuse_sharded(m, what);
+  if (rc) return rc;
+  const iem::Model &v = param_coord_view(m);
+  const int64_t n = which == 0 ? v.nnzjp : which == 1 ? v.nnzhxp : v.nnzhpp;
+  if ((!h_rows || !h_cols) && n) return fail(IEM_E_ARG, "null argument");
+  param_coord_structure_host(v, which, h_rows, h_cols, base);
+  return IEM_OK;
+}
+
+int iem_jacp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) { return param_coord_structure(m, 0, h_rows, h_cols, base, "iem_jacp_structure"); }
+int iem_hessxp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) { return param_coord_structure(m, 1, h_rows, h_cols, base, "iem_hessxp_structure"); }
+int iem_hesspp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base) { return param_coord_structure(m, 2, h_rows, h_cols, base, "iem_hesspp_structure"); }
+
+int iem_jacp_coord(iem_model *m, const double *d_x, double *d_vals) {
+  if (!m || !d_x) return fail(IEM_E_ARG, "null argument");
+  int rc = param_refuse_sharded(m, "iem_jacp_coord");
+  if (rc) return rc;
+  if (param_coord_view(m).nnzjp == 0) return IEM_OK;   // no θ slot in any constraint: nothing to launch
+  if (!d_vals) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->pc, 4))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.out = d_vals;
+  for (int k : m->pc.code.launchable[iem::KK_JAC])
+    if ((rc = launch_one(m, m->pc.code, k, h))) return rc;
+  return IEM_OK;
+}
+
+int iem_hessp_coord(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_hessxp, double *d_hesspp) {
+  if (!m || !d_x || (!d_y && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
+  if (!d_hessxp && !d_hesspp) return fail(IEM_E_ARG, "iem_hessp_coord: both outputs are NULL");
+  int rc = param_refuse_sharded(m, "iem_hessp_coord");
+  if (rc) return rc;
+  const iem::Model &v = param_coord_view(m);
+  if (v.nnzhxp == 0 && v.nnzhpp == 0) return IEM_OK;   // no second-order slot touches θ: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->pc, 4))) return rc;
+  // both blocks come out of ONE sweep: a block the caller does not want (NULL) but that has entries goes to a spare buffer
+  double *outp[2] = {d_hessxp, d_hesspp};
+  const int64_t nn[2] = {v.nnzhxp, v.nnzhpp};
+  for (int b = 0; b < 2; ++b) {
+    if (outp[b] || nn[b] == 0) continue;
+    if (!m->d_pc_spare[b]) HIP_TRY(hipMalloc((void **)&m->d_pc_spare[b], (size_t)nn[b] * 8));
+    outp[b] = m->d_pc_spare[b];
+  }
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.w = obj_weight; h.out = outp[0]; h.aux = outp[1];
+  for (int k : m->pc.code.launchable[iem::KK_HESS])
+    if ((rc = launch_one(m, m->pc.code, k, h))) return rc;
+  return IEM_OK;
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

@@ -195,6 +195,7 @@ struct Output {
   int fold = 0;
   int64_t pin_J = 0, pin_K = -1, pin_de = 0;
   std::vector<int> grad_tidx;   // scatter kinds: template index-expression id behind each destination
+  bool to_aux = false;          // the explicit θ blocks (Options::param_kinds = 4): this COO stream goes to the kernel's second buffer
 };
 
 class KernelBuilder {
@@ -771,6 +772,8 @@ class KernelBuilder {
   bool theta_adjoint() const { return opt_.param_kinds == 2; }
   // param_kinds = 3: the θθ program, hppprod alone on the same table slot — tangents AND outputs on the slots of θ
   bool theta_second() const { return opt_.param_kinds == 3; }
+  // param_kinds = 4: the explicit blocks in COO — jacp on the table slot of jac_coord!, hessp (two streams) on that of hess_coord!
+  bool theta_coord() const { return opt_.param_kinds == 4; }
   static bool has_theta_slot1(const Template &t) {
     for (int id : t.slot1_idx) if (t.is_theta_idx(id)) return true;
     return false;
@@ -784,6 +787,7 @@ class KernelBuilder {
     return false;
   }
   bool relevant(const Template &t) const {
+    if (theta_coord()) return kind_ == KK_JAC ? !t.pc1.empty() : kind_ == KK_HESS && (!t.pcx.empty() || !t.pcp.empty());
     if (theta_second()) return kind_ == KK_HPROD && has_theta_slot2(t);
     if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
     if (theta_kinds()) switch (kind_) {
@@ -839,6 +843,13 @@ class KernelBuilder {
           tg.forward(1);
           tg.slots1.assign(t.o1step, -1);
           tg.gr(t.root, 0, C(1.0));
+          if (kind_ == KK_JAC && theta_coord()) {   // dc/dθ: the θ slots of the row, the partials of x are never built into it
+            for (int s : t.pc1) o.vals.push_back(tg.slots1[s]);
+            IdxVal iv; iv.aff = klin_aff(t, G, (int64_t)t.pc1.size(), t.pc_o1);
+            o.pos_idx = idxval(iv); o.pos_off = t.pc_o1;
+            alg_w_ += t.n_items * (int64_t)t.pc1.size();
+            break;
+          }
           o.vals = tg.slots1;
           if (kind_ == KK_JAC) {
             IdxVal iv; iv.aff = klin_aff(t, G, t.o1step, t.o1);
@@ -981,6 +992,22 @@ class KernelBuilder {
             adj = load(2, 0, idxval(iv), G.guard);
           }
           tg.hr0(t.root, 0, adj, C(0.0));
+          if (theta_coord()) {
+            // one second-order sweep, two COO streams: the mixed slots (d2L/dx dθ) leave through OUT, the slots with both
+            // entries in θ (d2L/dθ2) through AUX; the slots of x alone are dropped here, their partials fold away
+            Output p = o;
+            p.to_aux = true;
+            for (int s2 : t.pcx) o.vals.push_back(tg.slots2[s2] < 0 ? C(0.0) : tg.slots2[s2]);
+            for (int s2 : t.pcp) p.vals.push_back(tg.slots2[s2] < 0 ? C(0.0) : tg.slots2[s2]);
+            IdxVal ix; ix.aff = klin_aff(t, G, (int64_t)t.pcx.size(), t.pc_ox);
+            o.pos_idx = idxval(ix); o.pos_off = t.pc_ox;
+            IdxVal ipp; ipp.aff = klin_aff(t, G, (int64_t)t.pcp.size(), t.pc_op);
+            p.pos_idx = idxval(ipp); p.pos_off = t.pc_op;
+            alg_w_ += t.n_items * (int64_t)(t.pcx.size() + t.pcp.size());
+            if (o.vals.empty()) o = p;
+            else if (!p.vals.empty()) second_stream_.push_back(p);
+            break;
+          }
           o.vals = tg.slots2;
           for (int s2 = 0; s2 < t.o2step; ++s2) {
             o.slot_ia.push_back(tg.idx1(t.slot2_i[s2])); o.slot_ib.push_back(tg.idx1(t.slot2_j[s2]));
@@ -1007,6 +1034,8 @@ class KernelBuilder {
         continue;
       }
       outs_.push_back(make_output(pr.first, pr.second, 0, nullptr));
+      for (const Output &p : second_stream_) outs_.push_back(p);   // (hessp: the template's d2L/dθ2 stream behind its mixed one)
+      second_stream_.clear();
     }
     if (kind_ == KK_GRAD || kind_ == KK_JTPROD || kind_ == KK_HPROD) {
       if (opt_.pull_scatter) pull_neighbours(make_output);
@@ -1698,7 +1727,7 @@ class KernelBuilder {
                << "    iem_flat_split(fr1_, fr0_, 16, " << ip(g_.ext[0]) << ", r1_, r0_); const long long o16 = iem_ord_lt(r1_, r0_, " << box << ");\n"
                << "    iem_flat_split(fr1_, fr0_, " << qstep_str() << ", " << ip(g_.ext[0]) << ", r1_, r0_); const long long ou = iem_ord_lt(r1_, r0_, " << box << ");\n"
                << "    iem_flat_split(fr1_, fr0_, IEM_TILE, " << ip(g_.ext[0]) << ", r1_, r0_); const long long oa = iem_ord_lt(r1_, r0_, " << box << ");\n"
-               << "    iem_flush_ord<" << ns << ", " << qstep_str() << ">(OUT, " << ip(o.pos_off, 3) << ", " << on << ", o16, ou, oa, lds_blk + "
+               << "    iem_flush_ord<" << ns << ", " << qstep_str() << ">(" << (o.to_aux ? "AUX" : "OUT") << ", " << ip(o.pos_off, 3) << ", " << on << ", o16, ou, oa, lds_blk + "
                << (batch_slots * opt_.block) << ", sl" << oi << ", " << g << "); }\n";
             pending_flush.push_back(fl.str());
             batch_slots += ns;
@@ -1736,7 +1765,7 @@ class KernelBuilder {
             fl << "    const int v1 = " << (any ? "(" + gb.str() + ") ? " : "") << "iem_clamp256(" << ip(std::min(o.qhi[0], g_.ext[0])) << " - qb0)"
                << (any ? " : v0" : "") << ";\n";
             }
-            fl << "    iem_flush<" << ns << ", " << qstep_str() << ">(OUT, pb, v0, v1, qb0 <= " << coefstr(g_.flat ? 0 : o.qlo[0]) << ", lds_blk + "
+            fl << "    iem_flush<" << ns << ", " << qstep_str() << ">(" << (o.to_aux ? "AUX" : "OUT") << ", pb, v0, v1, qb0 <= " << coefstr(g_.flat ? 0 : o.qlo[0]) << ", lds_blk + "
                << (batch_slots * opt_.block) << "); }\n";
             pending_flush.push_back(fl.str());
             batch_slots += ns;
@@ -1745,8 +1774,8 @@ class KernelBuilder {
           tail << "  { const double r[" << ns << "] = {";
           for (int s = 0; s < ns; ++s) tail << (s ? ", " : "") << "v" << o.vals[s];
           tail << "};\n";
-          if (use_lds && !scalar_tpl) tail << "    iem_store_rows<" << ns << ">(OUT, i" << o.pos_idx << ", " << g << ", r, lds_wave); }\n";
-          else tail << "    iem_store_rows_direct<" << ns << ">(OUT, i" << o.pos_idx << ", " << g << ", r); }\n";
+          if (use_lds && !scalar_tpl) tail << "    iem_store_rows<" << ns << ">(" << (o.to_aux ? "AUX" : "OUT") << ", i" << o.pos_idx << ", " << g << ", r, lds_wave); }\n";
+          else tail << "    iem_store_rows_direct<" << ns << ">(" << (o.to_aux ? "AUX" : "OUT") << ", i" << o.pos_idx << ", " << g << ", r); }\n";
           break;
         }
         case KK_OBJ:
@@ -2085,6 +2114,7 @@ class KernelBuilder {
   std::vector<std::string> guards_;
   std::map<std::string, int> guard_ids_;
   std::vector<Output> outs_;
+  std::vector<Output> second_stream_;   // make_output (hessp): the Output of the template's second COO stream
   std::map<std::pair<int, int64_t>, int> ip_ids_;
   std::vector<int64_t> ipv_;
   std::map<uint64_t, int> dp_ids_;
@@ -2503,7 +2533,8 @@ static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod
 static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod", "hpprod"};
 static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"};   // param_kinds = 2: the adjoint program
 static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"};   // param_kinds = 3: the θθ program
-static const char *const *kind_names(const Options &o) { return o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", ""};     // param_kinds = 4: the explicit blocks in COO
+static const char *const *kind_names(const Options &o) { return o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2892,13 +2923,23 @@ Program generate(const Model &m, const Options &opt_in) {
   if (!opt_in.param_kinds) return generate_kinds(m, opt_in);
   // the kinds d/dθ: the same machinery over the parameter view of the model (θ nodes are variables of the extended
   // vector [x; θ]); the builders keep the slots the kind asks for and drop the rest before anything is emitted
-  const Model view = parameter_view(m);
+  Model view = parameter_view(m);
+  if (opt_in.param_kinds == 4) {
+    // the explicit blocks dc/dθ, d2L/dx dθ, d2L/dθ2 in COO: row-owned stores through the staged store path of jac_coord! /
+    // hess_coord!, one lane per item.  Item-owned stores need none of the scatter machinery (no folded collocation boxes),
+    // and the blocks are small next to the model's own COO outputs: one body per grid and kind, the model's tile.
+    param_coord_layout(view);
+    Options o = opt_in;
+    o.fold_colloc = 0; o.jac_split = 0; o.hess_merge = 0; o.phase_kernels = 0; o.pair_kernel = 0;
+    o.big_batch_jac = o.big_batch_hess = 0;
+    return generate_kinds(view, o);
+  }
   return generate_kinds(view, opt_in);
 }
 
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
-  const bool theta = opt.param_kinds != 0;
+  const bool theta = opt.param_kinds != 0, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
   // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod, hptprod and hppprod (an entry per θ)
   auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (opt.param_kinds >= 2 && kind == KK_HPROD) ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
@@ -2957,8 +2998,8 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       throw std::runtime_error("support grid too large in dims 2/3 (limit 65535 per dimension for 3-D grids)");
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
-      if (theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
-      if (opt.param_kinds >= 2 && kind != KK_HPROD) continue;
+      if (coord ? kind != KK_JAC && kind != KK_HESS : theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
+      if (!coord && opt.param_kinds >= 2 && kind != KK_HPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3258,7 +3299,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       pos = std::max(pos, c.second + 1);
     }
     if (theta && kind == KK_GRAD) continue;
-    if (opt.param_kinds >= 2 && kind != KK_HPROD) continue;
+    if (coord || (opt.param_kinds >= 2 && kind != KK_HPROD)) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)

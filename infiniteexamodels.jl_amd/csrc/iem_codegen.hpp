@@ -137,6 +137,10 @@ struct Options {
   // 3: the θθ program, one more of its own (the sources of 1 and 2 do not move): hppprod (d2L/dθ2) w alone — the second-order
   // slots with BOTH entries in θ, hprod's arithmetic on them (the symmetric addend behind the same select), tangent and
   // output over θ; KK_HPROD's table slot again, npar entries out, scattered like hptprod's (no float atomic).
+  // 4: the explicit blocks in COO, a fifth program (the sources of 0 - 3 do not move): jacp — dc/dθ, the θ slots of the
+  // constraint templates' first-order slots — on KK_JAC's table slot, and hessp — d2L/dx dθ (out) and d2L/dθ2 (aux), the
+  // second-order slots with one / with two entries in θ, from ONE sweep — on KK_HESS's.  One lane per item, every slot
+  // stored once through the staged COO store path, layout by param_coord_layout (iem_model.hpp); no scatter kind, no atomic.
   int param_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)

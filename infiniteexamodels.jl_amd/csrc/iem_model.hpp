@@ -96,6 +96,12 @@ struct Template {
   // every θ node got a copy of its expression, so that a slot is either a variable's or a parameter's
   int theta_idx0 = -1;
   bool is_theta_idx(int id) const { return theta_idx0 >= 0 && id >= theta_idx0; }
+  // the explicit parameter-derivative blocks in COO (param_coord_layout, on a parameter view): the KEPT slots of ∂c/∂θ
+  // (pc1: first-order slots of a constraint whose entry is θ's), of ∂²L/∂x∂θ (pcx: second-order slots with exactly one
+  // θ entry) and of ∂²L/∂θ² (pcp: both entries θ's), each in the order slot1_idx / slot2_i,j list them, and the position
+  // of the template's first item in each block — the o1 / o2 of those blocks, counted over the kept slots only
+  std::vector<int> pc1, pcx, pcp;
+  int64_t pc_o1 = 0, pc_ox = 0, pc_op = 0;
 };
 
 // one add_var slab of x: `dims` (first index fastest) starting at 0-based `off`; `group[a]` = the
@@ -110,6 +116,7 @@ struct Model {
   std::vector<int64_t> blob;  // owned copy
   std::vector<Slab> slabs;    // empty when the producer wrote no slab table
   int64_t nvar = 0, npar = 0, ncon = 0, nnzj = 0, nnzh = 0;
+  int64_t nnzjp = 0, nnzhxp = 0, nnzhpp = 0;   // a parameter view after param_coord_layout: entries of ∂c/∂θ, ∂²L/∂x∂θ, ∂²L/∂θ²
   int minimize = 1;
   int arr_x0 = 0, arr_lvar = 0, arr_uvar = 0, arr_theta = 0;
   std::vector<ArrayDesc> arrs;
@@ -259,6 +266,27 @@ inline Model parameter_view(const Model &m) {
     analyse_template(t, true);
   }
   return v;
+}
+
+// COO layout of the explicit blocks ∂c/∂θ, ∂²L/∂x∂θ, ∂²L/∂θ² on a parameter view: template order first, within a template
+// item ordinal times kept slots per item, within an item the order in which slot1_idx / slot2_i,j list the kept slots.
+// The pattern is symbolic — every kept slot, whatever x, y and θ are.  Slots with both entries in x are not kept.
+inline void param_coord_layout(Model &v) {
+  int64_t o1 = 0, ox = 0, op = 0;
+  for (Template &t : v.tpl) {
+    t.pc1.clear(); t.pcx.clear(); t.pcp.clear();
+    if (t.kind == IEM_T_CON)
+      for (int s = 0; s < t.o1step; ++s) if (t.is_theta_idx(t.slot1_idx[s])) t.pc1.push_back(s);
+    for (int s = 0; s < t.o2step; ++s) {
+      const bool a = t.is_theta_idx(t.slot2_i[s]), b = t.is_theta_idx(t.slot2_j[s]);
+      if (a && b) t.pcp.push_back(s);
+      else if (a != b) t.pcx.push_back(s);
+    }
+    t.pc_o1 = o1; o1 += t.n_items * (int64_t)t.pc1.size();
+    t.pc_ox = ox; ox += t.n_items * (int64_t)t.pcx.size();
+    t.pc_op = op; op += t.n_items * (int64_t)t.pcp.size();
+  }
+  v.nnzjp = o1; v.nnzhxp = ox; v.nnzhpp = op;
 }
 
 // A foreign producer (the Julia writer) sees a template's iterator as a flat list of records and

@@ -200,6 +200,37 @@ function hppprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, 
                 m.handle, dptr(x), dptr(y), obj_weight, dptr(w), dptr(out)))
     return out
 end
+# ... and the three blocks themselves in COO (include/iem.h has the slot order and the triangle convention of ∂²L/∂θ²):
+# Jθ = ∂c/∂θ, Hxθ = ∂²L/∂x∂θ, Hθθ = ∂²L/∂θ² — what a host with its own linear algebra assembles G = [Hxθ; Jθ] from.
+function param_coord_nnz(m::MI355XModel)
+    out = zeros(Int64, 3)
+    check(ccall((:iem_param_coord_nnz, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int64}), m.handle, out))
+    return (out[1], out[2], out[3])
+end
+function param_coord_prepare!(m::MI355XModel)
+    n = Ref{Int32}(0)
+    check(ccall((:iem_param_coord_prepare, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.handle, n))
+    return Int(n[])
+end
+for (fn, sym, blk) in ((:jacp_structure!, :iem_jacp_structure, 1), (:hessxp_structure!, :iem_hessxp_structure, 2), (:hesspp_structure!, :iem_hesspp_structure, 3))
+    @eval function $fn(m::MI355XModel, rows::Vector{Int64}, cols::Vector{Int64})      # 1-based, like jac_structure!
+        @assert length(rows) == length(cols) == param_coord_nnz(m)[$blk]
+        check(ccall(($(QuoteNode(sym)), LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Cint), m.handle, rows, cols, 1))
+        return rows, cols
+    end
+end
+function jacp_coord!(m::MI355XModel, x::ROCVector{Float64}, vals::ROCVector{Float64})
+    check(ccall((:iem_jacp_coord, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(vals)))
+    return vals
+end
+# both second-order blocks from one launch; pass `nothing` for a block that is not wanted (not for both)
+function hessp_coord!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, hessxp, hesspp; obj_weight = 1.0)
+    px = hessxp === nothing ? Ptr{Float64}(C_NULL) : dptr(hessxp)
+    pp = hesspp === nothing ? Ptr{Float64}(C_NULL) : dptr(hesspp)
+    check(ccall((:iem_hessp_coord, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, px, pp))
+    return hessxp, hesspp
+end
 
 # ExaModels.set_parameter!(core, param, vals)  (src/infiniteopt_backend.jl:522,546)
 function set_parameter!(m::MI355XModel, param, vals)

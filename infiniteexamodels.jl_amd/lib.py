@@ -85,8 +85,8 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_shard_template_items", "iem_shard_blob", "iem_comm_export", "iem_comm_connect", "iem_halo_exchange", "iem_halo_exchange_async", "iem_halo_wait", "iem_halo_reads", "iem_halo_fold", "iem_allreduce_obj_grad", "iem_comm_status",
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
-           "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_array", "iem_free",
+           "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -169,7 +169,13 @@ def lib():
     L.iem_hptprod.argtypes = [vp, vp, vp, dbl, vp, vp]
     L.iem_hppprod_prepare.argtypes = [vp, C.POINTER(C.c_int32)]
     L.iem_hppprod.argtypes = [vp, vp, vp, dbl, vp, vp]
-    for f in ("iem_jac_structure", "iem_hess_structure", "iem_jac_structure_device", "iem_hess_structure_device"):
+    L.iem_param_coord_prepare.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.iem_param_coord_nnz.argtypes = [vp, C.POINTER(C.c_int64 * 3)]
+    L.iem_kernel_count.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.iem_jacp_coord.argtypes = [vp, vp, vp]
+    L.iem_hessp_coord.argtypes = [vp, vp, vp, dbl, vp, vp]
+    for f in ("iem_jac_structure", "iem_hess_structure", "iem_jac_structure_device", "iem_hess_structure_device", "iem_jacp_structure", "iem_hessxp_structure",
+              "iem_hesspp_structure"):
         getattr(L, f).argtypes = [vp, vp, vp, i32]
     L.iem_csr_values.argtypes = [vp, i64, vp, vp, vp, vp]
     L.iem_csr_values32.argtypes = [vp, i64, vp, vp, vp, vp]
@@ -358,6 +364,24 @@ def blob_hess_structure(blob: bytes, base: int = 0):
                                           C.POINTER(C.c_int64)]
     r, c, n = C.c_void_p(), C.c_void_p(), C.c_int64()
     check(L.iem_blob_hess_structure(blob, len(blob), base, C.byref(r), C.byref(c), C.byref(n)))
+    try:
+        rows = np.ctypeslib.as_array(C.cast(r, C.POINTER(C.c_int64)), shape=(max(n.value, 1),))[:n.value].copy()
+        cols = np.ctypeslib.as_array(C.cast(c, C.POINTER(C.c_int64)), shape=(max(n.value, 1),))[:n.value].copy()
+    finally:
+        L.iem_free(r)
+        L.iem_free(c)
+    return rows, cols
+
+
+def blob_param_coord_structure(blob: bytes, which: int, base: int = 0):
+    """Structure of one explicit θ block of a blob (host computation, no device): ``which`` = 0 ``∂c/∂θ``, 1 ``∂²L/∂x∂θ``,
+    2 ``∂²L/∂θ²`` — what ``ExaModel.jacp_structure`` / ``hessxp_structure`` / ``hesspp_structure`` report."""
+    import numpy as np
+    L = lib()
+    L.iem_blob_param_coord_structure.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_int64)]
+    r, c, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+    check(L.iem_blob_param_coord_structure(blob, len(blob), int(which), int(base), C.byref(r), C.byref(c), C.byref(n)))
     try:
         rows = np.ctypeslib.as_array(C.cast(r, C.POINTER(C.c_int64)), shape=(max(n.value, 1),))[:n.value].copy()
         cols = np.ctypeslib.as_array(C.cast(c, C.POINTER(C.c_int64)), shape=(max(n.value, 1),))[:n.value].copy()

@@ -97,6 +97,7 @@ class ExaModel:
         else:
             _lib.check(self._L.iem_create_sharded(blob, len(blob), device, _shard[0], _shard[1], _shard[2], arr, n, C.byref(h)))
         self._h = h
+        self._pc_nnz = None      # lengths of the explicit θ blocks (param_coord_nnz), asked once
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -383,6 +384,78 @@ class ExaModel:
         ``iem_hppprod*``): they are listed behind the model's kernels and those ``param_kernels`` returns."""
         first = self.meta.n_kernels + self.param_prepare()
         return self._kernel_infos(first, first + self.hppprod_prepare())
+
+    # ---- the blocks themselves in COO: Jθ = ∂c/∂θ, Hxθ = ∂²L/∂x∂θ, Hθθ = ∂²L/∂θ² (include/iem.h has the slot order) ----
+    def param_coord_prepare(self) -> int:
+        """Set up the program of ``jacp_coord`` / ``hessp_coord`` now (``iem_param_coord_prepare``: otherwise their first call
+        does — synchronously, and not inside a stream capture); the number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_param_coord_prepare(self._h, C.byref(n)))
+        return int(n.value)
+
+    def param_coord_nnz(self):
+        """``(nnz of Jθ, nnz of Hxθ, nnz of Hθθ)``: the lengths of the three COO blocks (symbolic pattern)."""
+        if self._pc_nnz is None:
+            out = (C.c_int64 * 3)()
+            _lib.check(self._L.iem_param_coord_nnz(self._h, C.byref(out)))
+            self._pc_nnz = tuple(int(v) for v in out)
+        return self._pc_nnz
+
+    def _pc_structure(self, fn, n: int, base: int):
+        r = np.zeros(max(n, 1), dtype=np.int64)
+        c = np.zeros(max(n, 1), dtype=np.int64)
+        _lib.check(fn(self._h, r.ctypes.data, c.ctypes.data, base))
+        return r[:n], c[:n]
+
+    def jacp_structure(self, base: int = 0):
+        """Rows (constraints) and columns (entries of θ) of ``∂c/∂θ`` → host int64 arrays (``base`` 1 = Julia)."""
+        return self._pc_structure(self._L.iem_jacp_structure, self.param_coord_nnz()[0], base)
+
+    def hessxp_structure(self, base: int = 0):
+        """Rows (entries of x) and columns (entries of θ) of ``∂²L/∂x∂θ`` (rectangular, no triangle)."""
+        return self._pc_structure(self._L.iem_hessxp_structure, self.param_coord_nnz()[1], base)
+
+    def hesspp_structure(self, base: int = 0):
+        """Rows and columns of ``∂²L/∂θ²``: one triangle (row >= col), like ``hess_structure``."""
+        return self._pc_structure(self._L.iem_hesspp_structure, self.param_coord_nnz()[2], base)
+
+    def jacp_coord(self, x, vals=None):
+        """The values of ``∂c/∂θ`` at ``(x, the model's current θ)`` in the order of ``jacp_structure``."""
+        n = self.param_coord_nnz()[0]
+        self._chk(x, self.meta.nvar, "x")
+        vals = vals if vals is not None else self._new(n)
+        self._chk(vals, n, "vals")
+        self._sync_stream()
+        _lib.check(self._L.iem_jacp_coord(self._h, _ptr(x), _ptr(vals)))
+        return vals
+
+    def hessp_coord(self, x, y, obj_weight: float = 1.0, vals_xp=None, vals_pp=None):
+        """The values of ``∂²L/∂x∂θ`` and ``∂²L/∂θ²`` (``L = obj_weight·f + yᵀc``) from ONE launch, in the orders of
+        ``hessxp_structure`` / ``hesspp_structure``.  Returns ``(vals_xp, vals_pp)``.  ``None`` allocates a block's output;
+        ``False`` means the block is NOT WANTED (the C-ABI's NULL: ``None`` is returned in its place) — not for both."""
+        _, nxp, npp = self.param_coord_nnz()
+        self._chk(x, self.meta.nvar, "x"); self._chk(y, self.meta.ncon, "y")
+        if vals_xp is False and vals_pp is False:
+            raise ValueError("hessp_coord: at least one of the two blocks must be wanted")
+        vals_xp = None if vals_xp is False else vals_xp if vals_xp is not None else self._new(nxp)
+        vals_pp = None if vals_pp is False else vals_pp if vals_pp is not None else self._new(npp)
+        if vals_xp is not None:
+            self._chk(vals_xp, nxp, "vals_xp")
+        if vals_pp is not None:
+            self._chk(vals_pp, npp, "vals_pp")
+        if nxp + npp == 0 or (vals_xp is None and npp == 0) or (vals_pp is None and nxp == 0):      # no second-order slot touches θ: nothing to launch (and no pointer to pass: NULL / NULL is an error)
+            return vals_xp, vals_pp
+        self._sync_stream()
+        _lib.check(self._L.iem_hessp_coord(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(vals_xp), _ptr(vals_pp)))
+        return vals_xp, vals_pp
+
+    def param_coord_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of ``jacp_coord`` / ``hessp_coord`` (kinds jac / hess of a
+        program of their own, names ``iem_jacp*`` / ``iem_hessp*``): always the LAST kernels ``iem_kernel_info`` lists."""
+        n = self.param_coord_prepare()
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        return self._kernel_infos(int(total.value) - n, int(total.value))
 
     def param_prepare(self) -> int:
         """Set up the programs of jpprod / jptprod / hpprod and of hptprod now (``iem_param_prepare``: otherwise the first

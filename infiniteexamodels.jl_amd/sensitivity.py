@@ -22,7 +22,12 @@ bilevel design).  At a KKT point its gradient is the partial one (envelope theor
     φ''(θ)·δθ = L_θθ·δθ + Gᵀ·[dx; dy] = (L_θθ − Gᵀ·K⁻¹·G)·δθ
               = ``hppprod(x, y, δθ)`` + ``hptprod(x, y, dx)`` + ``jptprod(x, dy, obj_weight=0)``
 
-(``value_hessian_product(s)``): one solve and three matrix-free products per direction."""
+(``value_hessian_product(s)``): one solve and three matrix-free products per direction.
+
+THE FULL SENSITIVITY MATRIX over chosen entries of θ (``parameter_jacobian``): for unit directions the right-hand side of
+the forward step is just ``−G[:, cols]``.  With G in COO (``ExaModel.hessp_coord`` / ``jacp_coord``: two launches, whatever K
+is) the K columns are ONE deterministic segmented gather from a plan built once per ``(model, cols)`` — no product per
+column, no loop over K on the host."""
 from __future__ import annotations
 
 
@@ -65,6 +70,110 @@ def parameter_steps(model, kkt, x, y, dthetas, obj_weight: float = 1.0):
         model.jpprod(x, d, out=buf[j, n:])
     buf.neg_()
     sol = kkt.solve(buf.t())
+    return sol[:n], sol[n:]
+
+
+class ParameterJacobianPlan:
+    """Host-built gather plan of ``parameter_jacobian`` for one ``(model, theta_cols)``.
+
+    The COO values of ``G = [∇²ₓθL ; ∂c/∂θ]`` live in ONE buffer — the ``nnz(Hxθ)`` values of ``hessp_coord`` first, the
+    ``nnz(Jθ)`` values of ``jacp_coord`` behind them.  Every entry whose θ column is ``theta_cols[k]`` goes to position
+    ``k·(nvar + ncon) + row`` (rows of Jθ behind those of Hxθ) of a ``(K, nvar + ncon)`` right-hand side: the selected
+    entries are sorted by that destination — stable, so duplicates of a position keep their COO order — and ``dest``
+    (the distinct destinations, ascending), ``seg`` (``len(dest) + 1`` boundaries) and ``perm`` (COO positions) are the
+    ``seg`` / ``perm`` shape ``csr.build_plan`` makes and ``iem_csr_values`` consumes.  An index may repeat in
+    ``theta_cols``: its column is produced once per occurrence."""
+
+    def __init__(self, struct_xp, struct_jp, nvar: int, ncon: int, npar: int, theta_cols):
+        import numpy as np
+        cols = np.asarray(theta_cols)
+        if cols.ndim != 1 or cols.size == 0:
+            raise ValueError("parameter_jacobian: theta_cols must be a non-empty list of indices into θ")
+        if not np.issubdtype(cols.dtype, np.integer):
+            raise TypeError("parameter_jacobian: theta_cols must be integers")
+        if cols.min() < 0 or cols.max() >= npar:
+            raise IndexError(f"parameter_jacobian: theta_cols must lie in 0 .. {npar - 1}")
+        (xr, xc), (jr, jc) = struct_xp, struct_jp
+        self.nvar, self.ncon, self.K = int(nvar), int(ncon), int(cols.size)
+        self.n_xp, self.n_jp = int(len(xr)), int(len(jr))
+        rows = np.concatenate([np.asarray(xr, dtype=np.int64), np.asarray(jr, dtype=np.int64) + nvar])
+        tcol = np.concatenate([np.asarray(xc, dtype=np.int64), np.asarray(jc, dtype=np.int64)])
+        # the occurrences k of every θ index, ascending: entries fan out to each of them
+        order = np.argsort(cols, kind="stable")
+        first = np.searchsorted(cols[order], tcol, side="left")
+        count = np.searchsorted(cols[order], tcol, side="right") - first
+        pos = np.repeat(np.arange(rows.size, dtype=np.int64), count)
+        within = np.arange(pos.size, dtype=np.int64) - np.repeat(np.cumsum(count) - count, count)
+        k = order[np.repeat(first, count) + within]
+        dest = k.astype(np.int64) * (nvar + ncon) + rows[pos]
+        by_dest = np.argsort(dest, kind="stable")
+        sdest = dest[by_dest]
+        self.perm = pos[by_dest]
+        start = np.flatnonzero(np.concatenate([[True], sdest[1:] != sdest[:-1]])) if sdest.size else np.zeros(0, dtype=np.int64)
+        self.dest = sdest[start].astype(np.int64)
+        self.seg = np.concatenate([start, [sdest.size]]).astype(np.int64)
+        self._dev = {}
+
+    def on(self, device):
+        """(dest, seg, perm) as int64 tensors on ``device`` (uploaded once)"""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.as_tensor(a, dtype=torch.int64).to(device) for a in (self.dest, self.seg, self.perm))
+        return self._dev[key]
+
+    def rhs(self, model, vals):
+        """``−G[:, cols]`` as a ``(K, nvar + ncon)`` tensor from the COO buffer ``vals``: one segmented gather (fixed
+        summation order, no atomics), negated, into zeros.  Device values go through ``iem_csr_values``; host tensors —
+        a device-free model — through the same sums in the same order."""
+        import torch
+        dest, seg, perm = self.on(vals.device)
+        buf = torch.zeros(self.K, self.nvar + self.ncon, dtype=vals.dtype, device=vals.device)
+        n = int(dest.numel())
+        if n == 0:
+            return buf
+        compact = torch.empty(n, dtype=vals.dtype, device=vals.device)
+        if vals.is_cuda:
+            from . import lib as _lib
+            model._sync_stream()
+            _lib.check(model._L.iem_csr_values(model._h, n, seg.data_ptr(), perm.data_ptr(), vals.data_ptr(), compact.data_ptr()))
+        else:
+            compact.zero_()
+            compact.index_add_(0, torch.repeat_interleave(torch.arange(n), seg[1:] - seg[:-1]), vals[perm])
+        buf.view(-1).index_copy_(0, dest, compact.neg_())
+        return buf
+
+
+def parameter_jacobian_plan(model, theta_cols) -> ParameterJacobianPlan:
+    """The plan of ``parameter_jacobian`` for ``theta_cols``, built once per ``(model, theta_cols)`` and kept on the model."""
+    import numpy as np
+    cols = np.asarray(theta_cols)
+    key = (cols.dtype.kind, tuple(cols.reshape(-1).tolist()))
+    plans = model.__dict__.setdefault("_parameter_jacobian_plans", {})
+    if key not in plans:
+        plans[key] = ParameterJacobianPlan(model.hessxp_structure(), model.jacp_structure(), model.meta.nvar, model.meta.ncon,
+                                           model.meta.npar, cols)
+    return plans[key]
+
+
+def parameter_jacobian(model, kkt, x, y, theta_cols, obj_weight: float = 1.0):
+    """``(dX, dY)``, shapes ``(nvar, K)`` and ``(ncon, K)``: the columns of the sensitivity matrix ``d(x, y)/dθ`` for the K
+    entries ``theta_cols`` of θ (indices into θ; ``ExaTranscriptionBackend.parameter_columns(p)`` has those of a parameter)
+    at the primal-dual point ``(x, y)`` — what ``parameter_steps`` returns for the K unit directions, sign convention
+    included (``K·[dx; dy] = −G·e_k``), from TWO launches and ONE gather instead of 2·K products and K copies:
+
+        vals = [hessp_coord(x, y) ; jacp_coord(x)]      (G in COO)
+        rhs  = −gather(plan, vals)                       (``(K, nvar + ncon)``, zeros where G has no entry)
+        sol  = kkt.solve(rhsᵀ)                           (one solve with the 2-D right-hand side)
+
+    ``kkt`` is an ASSEMBLED AND FACTORISED system at that point, as for ``parameter_step``."""
+    import torch
+    n = model.meta.nvar
+    plan = parameter_jacobian_plan(model, theta_cols)
+    vals = torch.empty(plan.n_xp + plan.n_jp, dtype=x.dtype, device=x.device)
+    model.hessp_coord(x, y, obj_weight=obj_weight, vals_xp=vals[:plan.n_xp], vals_pp=False)      # (∂²L/∂θ² is not wanted here)
+    model.jacp_coord(x, vals=vals[plan.n_xp:])
+    sol = kkt.solve(plan.rhs(model, vals).t())
     return sol[:n], sol[n:]
 
 
