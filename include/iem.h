@@ -246,6 +246,31 @@ int iem_eval_accepted(iem_model *m, const double *d_x, const double *d_y, double
 int iem_eval_all(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_c, double *d_g, double *d_jac, double *d_hess,
                  double *h_obj /* may be NULL */);
 
+/* The CONVERGENCE CHECK of a solver (extensions): the dual residual  obj_weight*grad f(x) + J(x)' y  — the gradient of the
+ * Lagrangian; the dual infeasibility of Ipopt / MadNLP is this vector minus the bound multipliers — from ONE kernel, and
+ * with c(x) and f(x) from ONE launch:
+ *   iem_lagrad         out = obj_weight*grad f(x) + J(x)' y        y: ncon, out: nvar
+ *   iem_eval_residual  the same vector into d_lagrad, c = cons(x) into d_c, f = obj(x) into the DEVICE scalar d_obj
+ *                      (as iem_obj_device: no mapped host slot, nothing to collect with iem_obj_end)
+ * In the kernel an objective template is seeded with obj_weight and a constraint template with y[row] (as iem_jptprod does
+ * for θ), every first-order slot is kept, and ONE deterministic scatter handles both: no float atomics, bitwise reproducible
+ * from call to call; entries of x no template touches get 0, the outputs are fully overwritten.  d_lagrad is bitwise what
+ * iem_lagrad writes, d_c what iem_cons writes, d_obj what iem_obj_device writes.  ncon == 0: d_y and d_c may be NULL and the
+ * vector is obj_weight*grad f; a model without objective gets d_obj = 0; a model without any first-order slot: a memset.
+ * The kernels (kinds 0 / 3 / 6 — names iem_cons*, iem_obj*, iem_lagrad* — and the phase kernel iem_residual_all, kind 9) are
+ * a SIXTH program of their own over the plain model, set up by the first of the two calls — synchronous, outside a stream
+ * capture; every later call is asynchronous on the handle's stream and capturable — or by iem_lagrad_prepare (idempotent;
+ * returns the number of this program's kernels; a runtime failure of the set-up is not remembered).  The other prepare
+ * calls do not prepare it and keep their counts; iem_kernel_info lists these kernels LAST, behind every other program that
+ * exists on the handle (the explicit θ blocks' included), with their algorithmic bytes — the phase kernel reports the union
+ * of its members' reads.  Where the phase kernel does not exist (a member missing, kinds of different workgroup sizes, more
+ * workgroups than one launch takes) iem_eval_residual makes the member launches itself.  A sharded handle refuses all three
+ * calls with IEM_E_ARG: the result would need the halo fold and the all-reduce. */
+int iem_lagrad_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_lagrad(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out /* nvar */);
+int iem_eval_residual(iem_model *m, const double *d_x, const double *d_y, double obj_weight,
+                      double *d_c /* ncon */, double *d_lagrad /* nvar */, double *d_obj /* device scalar */);
+
 /* matrix-free products (NLPModels jprod! / jtprod! / hprod!; ExaModels' `prod = true` path —
  * not used by the reference's solvers): Jv (ncon), J'v (nvar), Hv (nvar) with
  * H the Hessian of obj_weight*f + y'c. */
@@ -340,7 +365,7 @@ int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
  * structure calls and iem_param_coord_nnz need no program and no device work: they evaluate the index expressions on the
  * host, like iem_jac_structure.  A sharded handle refuses all of them with IEM_E_ARG like the products above. */
 int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels);
-/* how many kernels iem_kernel_info answers for right now: the model's own and those of every θ program set up so far */
+/* how many kernels iem_kernel_info answers for right now: the model's own and those of every further program set up so far */
 int iem_kernel_count(const iem_model *m, int32_t *out_total);
 int iem_param_coord_nnz(iem_model *m, int64_t out[3]);
 int iem_jacp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int base);

@@ -249,6 +249,11 @@ struct iem_model {
   // blocks' layout (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.
   // `d_pc_spare`: where a block the caller passed NULL for is written when it is not empty (allocated by the first such call)
   ParamKinds pc;
+  // the residual program (iem_lagrad / iem_eval_residual; param_kinds = 5, over the plain model): a sixth program, set up by
+  // its own first call or by iem_lagrad_prepare — the other prepare calls do not know of it.  `d_lag_partials`: the partials
+  // and ticket words of ITS objective kernels (the model's own keep theirs)
+  ParamKinds lag;
+  double *d_lag_partials = nullptr;
   iem::Model pc_view;
   bool pc_have_view = false;
   double *d_pc_spare[2] = {nullptr, nullptr};
@@ -383,8 +388,14 @@ struct LaunchHead {
     double *g = nullptr;        // KK_ACCEPTED / KK_ALL: grad!'s output
     double *trial_partials;     // KK_TRIAL: the objective's partials
   };
-  double *g_red = nullptr;      // KK_ACCEPTED / KK_ALL: grad!'s reduction buffer
-  double *c = nullptr;          // KK_ALL: cons!'s output
+  union {
+    double *g_red = nullptr;    // KK_ACCEPTED / KK_ALL: grad!'s reduction buffer
+    double *lag_out;            // KK_TRIAL of the residual program: lagrad's output
+  };
+  union {
+    double *c = nullptr;        // KK_ALL: cons!'s output
+    double *lag_red;            // KK_TRIAL of the residual program: lagrad's reduction buffer
+  };
   double *partials = nullptr;   // KK_ALL: the objective's partials
   double *obj = nullptr;        // KK_ALL: the objective scalar
 };
@@ -941,7 +952,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "jac_split") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "jac_split must be 0 or 1"); o.jac_split = (int)value; return IEM_OK; }
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
-  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 4 ? (int)value : value != 0; return IEM_OK; }
+  if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 5 ? (int)value : value != 0; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1237,6 +1248,11 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->th2.d_gather) if (r) hipFree(r);
   free_program(m->th2.code);
   free_program(m->pc.code);
+  for (double *r : m->lag.d_red) if (r) hipFree(r);
+  for (long long *r : m->lag.d_axis) if (r) hipFree(r);
+  for (long long *r : m->lag.d_gather) if (r) hipFree(r);
+  free_program(m->lag.code);
+  if (m->d_lag_partials) hipFree(m->d_lag_partials);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
@@ -1265,15 +1281,18 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
-  // behind the model's own kernels: those of the parameter kinds, once their program exists (after the first such call),
-  // behind those the adjoint kind's (iem_hptprod), once ITS program exists, and last the θθ kind's (iem_hppprod)
-  const int n_own = (int)m->code.prog.kernels.size(), n_par = m->par.tried && m->par.rc == IEM_OK ? (int)m->par.code.prog.kernels.size() : 0;
-  const int n_adj = m->adj.tried && m->adj.rc == IEM_OK ? (int)m->adj.code.prog.kernels.size() : 0;
-  const int n_th2 = m->th2.tried && m->th2.rc == IEM_OK ? (int)m->th2.code.prog.kernels.size() : 0;
-  const int n_pc = m->pc.tried && m->pc.rc == IEM_OK ? (int)m->pc.code.prog.kernels.size() : 0;   // ... and behind all of them the explicit blocks' (iem_jacp_coord / iem_hessp_coord)
-  if (k >= n_own + n_par + n_adj + n_th2 + n_pc) return fail(IEM_E_ARG, "bad kernel index");
-  const iem::KernelDesc &kd = k >= n_own + n_par + n_adj + n_th2 ? m->pc.code.prog.kernels[k - n_own - n_par - n_adj - n_th2] : k < n_own ? m->code.prog.kernels[k] : k < n_own + n_par ? m->par.code.prog.kernels[k - n_own]
-                            : k < n_own + n_par + n_adj ? m->adj.code.prog.kernels[k - n_own - n_par] : m->th2.code.prog.kernels[k - n_own - n_par - n_adj];
+  // behind the model's own kernels: those of every further program that exists on the handle (set up by its first call or
+  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program
+  const iem::KernelDesc *found = k < (int)m->code.prog.kernels.size() ? &m->code.prog.kernels[k] : nullptr;
+  int base = (int)m->code.prog.kernels.size();
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag}) {
+    if (found || !P->tried || P->rc != IEM_OK) continue;
+    const int n = (int)P->code.prog.kernels.size();
+    if (k < base + n) found = &P->code.prog.kernels[k - base];
+    base += n;
+  }
+  if (!found) return fail(IEM_E_ARG, "bad kernel index");
+  const iem::KernelDesc &kd = *found;
   std::memset(out, 0, sizeof *out);
   std::strncpy(out->name, kd.name.c_str(), sizeof(out->name) - 1);
   out->kind = kd.kind;
@@ -1288,7 +1307,7 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
 int iem_kernel_count(const iem_model *m, int32_t *out_total) {
   if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
   size_t n = m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc})
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag})
     if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
   *out_total = (int32_t)n;
   return IEM_OK;
@@ -1451,8 +1470,8 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 }
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
-// The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2) or of the θθ kind
-// (P = m->th2, kinds = 3), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
+// The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2), of the θθ kind
+// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4) or the residual program (P = m->lag, kinds = 5), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
 // later call.
 static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
@@ -1672,6 +1691,89 @@ int iem_hessp_coord(iem_model *m, const double *d_x, const double *d_y, double o
   for (int k : m->pc.code.launchable[iem::KK_HESS])
     if ((rc = launch_one(m, m->pc.code, k, h))) return rc;
   return IEM_OK;
+}
+
+// ---- the convergence check: the Lagrangian's gradient in one kernel, c, f and that gradient in one launch ------------------
+// The residual program (P = m->lag, kinds = 5: lagrad on KK_JTPROD's table slot, the model's own cons and obj, KK_TRIAL with
+// lagrad as third member), set up like the θ programs, and the partials of its objective kernels.
+static int lagrad_refuse_sharded(const iem_model *m, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the gradient of the Lagrangian would need the halo fold and the "
+                         "all-reduce of grad! and jtprod!; a sharded residual is out of scope");
+}
+
+static int lagrad_program(iem_model *m) {
+  int rc = param_program(m, m->lag, 5);
+  if (rc) return rc;
+  if (!m->d_lag_partials) {   // partials + ticket counters, zeroed once (the workgroups that complete a count reset it)
+    const size_t np = (size_t)std::max<int64_t>(m->lag.code.prog.n_partials, 1);
+    const size_t words = np + 1 + (np + 31) / 32;
+    if (hipMalloc((void **)&m->d_lag_partials, words * 8) != hipSuccess) { m->d_lag_partials = nullptr; return fail(IEM_E_HIP, "hipMalloc partials"); }
+    if (hipMemsetAsync(m->d_lag_partials, 0, words * 8, m->stream) != hipSuccess) {
+      hipFree(m->d_lag_partials);
+      m->d_lag_partials = nullptr;
+      return fail(IEM_E_HIP, "hipMemsetAsync partials");
+    }
+  }
+  return IEM_OK;
+}
+
+int iem_lagrad_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = lagrad_refuse_sharded(m, "iem_lagrad_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = lagrad_program(m))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->lag.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+/* σ ∇f(x) + J(x)' y — the dual residual of a solver's convergence check, without the bound multipliers */
+int iem_lagrad(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out) {
+  if (!m || !d_x || (!d_y && m->model.ncon) || (!d_out && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
+  int rc = lagrad_refuse_sharded(m, "iem_lagrad");
+  if (rc) return rc;
+  if (m->model.nvar == 0) return IEM_OK;   // a zero-length output: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = lagrad_program(m))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_y; h.out = d_out; h.w = obj_weight;
+  return param_launch(m, m->lag, iem::KK_JTPROD, h);   // (no first-order slot at all: the zero range is the whole output, a memset)
+}
+
+/* c(x), f(x) and the gradient above in ONE launch (the residual program's KK_TRIAL), lagrad's follow-ups behind it; where
+ * that kernel does not exist (no objective, no constraint or no first-order slot; kinds of different workgroup sizes; more
+ * workgroups than one launch takes) the member launches */
+int iem_eval_residual(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_c, double *d_lagrad, double *d_obj) {
+  if (!m || !d_x || !d_obj || ((!d_y || !d_c) && m->model.ncon) || (!d_lagrad && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
+  int rc = lagrad_refuse_sharded(m, "iem_eval_residual");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = lagrad_program(m))) return rc;
+  iem_model::ParamKinds &P = m->lag;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.v = d_y; h.w = obj_weight;
+  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
+    for (auto &z : P.code.prog.zero_ranges[iem::KK_JTPROD])
+      HIP_TRY(hipMemsetAsync(d_lagrad + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
+    h.out = d_c; h.aux = d_obj; h.trial_partials = m->d_lag_partials; h.lag_out = d_lagrad; h.lag_red = P.d_red[iem::KK_JTPROD];
+    for (int k : P.code.launchable[iem::KK_TRIAL])
+      if ((rc = launch_one(m, P.code, k, h))) return rc;
+    return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_JTPROD, d_lagrad, P.d_red[iem::KK_JTPROD]);
+  }
+  h.out = d_c;
+  for (int k : P.code.launchable[iem::KK_CONS])
+    if ((rc = launch_one(m, P.code, k, h))) return rc;
+  if (P.code.launchable[iem::KK_OBJ].empty()) {   // no objective template: f = 0
+    HIP_TRY(hipMemsetAsync(d_obj, 0, 8, m->stream));
+  } else {
+    h.out = m->d_lag_partials; h.aux = d_obj;
+    for (int k : P.code.launchable[iem::KK_OBJ])
+      if ((rc = launch_one(m, P.code, k, h))) return rc;
+  }
+  if (m->model.nvar == 0) return IEM_OK;
+  h.out = d_lagrad; h.aux = nullptr;
+  return param_launch(m, P, iem::KK_JTPROD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

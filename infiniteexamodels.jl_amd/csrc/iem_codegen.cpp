@@ -767,7 +767,10 @@ class KernelBuilder {
 
   // ---- build the kernel's outputs ---------------------------------------------
   // parameter kinds (Options::param_kinds; m_ is the parameter view): slots of θ
-  bool theta_kinds() const { return opt_.param_kinds != 0; }
+  bool theta_kinds() const { return opt_.param_kinds >= 1 && opt_.param_kinds <= 4; }
+  // param_kinds = 5: the residual program over the PLAIN model — lagrad (σ ∇f + J' y) on the table slot of jtprod, next to the
+  // model's own cons and obj
+  bool lagrangian() const { return opt_.param_kinds == 5; }
   // param_kinds = 2: the adjoint program, hptprod alone on the table slot of hprod — tangents on the slots of x, outputs on the slots of θ
   bool theta_adjoint() const { return opt_.param_kinds == 2; }
   // param_kinds = 3: the θθ program, hppprod alone on the same table slot — tangents AND outputs on the slots of θ
@@ -790,6 +793,12 @@ class KernelBuilder {
     if (theta_coord()) return kind_ == KK_JAC ? !t.pc1.empty() : kind_ == KK_HESS && (!t.pcx.empty() || !t.pcp.empty());
     if (theta_second()) return kind_ == KK_HPROD && has_theta_slot2(t);
     if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
+    if (lagrangian()) switch (kind_) {
+      case KK_CONS: return t.kind == IEM_T_CON;
+      case KK_OBJ: return t.kind == IEM_T_OBJ;
+      case KK_JTPROD: return t.o1step > 0;                 // constraints (seed y) and objective terms (seed σ): every first-order slot
+      default: return false;
+    }
     if (theta_kinds()) switch (kind_) {
       case KK_JPROD: return t.kind == IEM_T_CON;           // every row is written: zero where c does not depend on θ
       case KK_JTPROD: return has_theta_slot1(t);           // constraints (seed y) and objective terms (seed σ)
@@ -917,8 +926,12 @@ class KernelBuilder {
         } else {  // (J' v)[col] += dc/dx_slot * v[row]  == gradient of  v . c(x)
           tg.forward(1);
           tg.slots1.assign(t.o1step, -1);
-          IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into v), not an output position
-          int seed = load(4, 0, idxval(rv), G.guard);
+          int seed;
+          if (lagrangian() && t.kind == IEM_T_OBJ) seed = mk(VW, 0, -1, -1, -1, 0);   // lagrad: the gradient of  σ f + v . c, an objective template seeded with σ
+          else {
+            IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into v), not an output position
+            seed = load(4, 0, idxval(rv), G.guard);
+          }
           tg.gr(t.root, 0, seed);
           o.vals = tg.slots1;
           for (int s = 0; s < t.o1step; ++s) {
@@ -2534,7 +2547,8 @@ static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod
 static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"};   // param_kinds = 2: the adjoint program
 static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"};   // param_kinds = 3: the θθ program
 static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", ""};     // param_kinds = 4: the explicit blocks in COO
-static const char *const *kind_names(const Options &o) { return o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_lag[] = {"cons", "", "", "obj", "", "", "lagrad", ""};   // param_kinds = 5: the residual program (plain model)
+static const char *const *kind_names(const Options &o) { return o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2771,7 +2785,7 @@ static void emit_kinds(Emitter &E) {
     for (size_t k = 0; k < E.descs.size(); ++k) if (E.descs[k].kind == kind) ks.push_back(k);
     if (ks.empty()) continue;
     const int ktile = E.descs[ks[0]].block;   // one workgroup size per kind (kind_options)
-    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS);
+    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS || (opt.param_kinds == 5 && kind == KK_JTPROD));
     const bool unfused = !opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2);   // fuse_groups = 2: experiments (one launch of per-template bodies)
     if (kind != KK_OBJ && (unfused || (ks.size() == 1 && !in_a_phase))) {
       for (size_t k : ks) { E.ns_begin(ktile); E.src << E.builders[k]->emit(E.descs[k]); E.ns_end(ktile); E.P.kernels.push_back(E.descs[k]); }
@@ -2792,12 +2806,17 @@ static void emit_kinds(Emitter &E) {
 // code at its own table base; bytes identical to the separate calls (same bodies).  Pointers: trial  out = c, aux = the
 // objective scalar, p2 = the objective's partials;  accepted  out = jac values, aux = hess values, p2 = g, p3 = grad!'s
 // reduction buffer.  Follow-ups of grad! (axis sums, plan-driven gather, runtime memsets) stay with the runtime.
+// The residual program (Options::param_kinds = 5) has ONE phase, the convergence check (iem_eval_residual): KK_TRIAL with a
+// third member, lagrad on KK_JTPROD's table slot — p3 = its output, p4 = its reduction buffer, A.v = y, A.w = σ; its
+// follow-ups stay with the runtime like grad!'s.
 static void emit_phases(Emitter &E) {
   if (!E.phases_on()) return;
   std::ostringstream &src = E.src;
   struct Member { int kind; const char *out, *aux; };
   struct Phase { int id; const char *name; std::vector<Member> mem; };
-  const Phase phases[] = {
+  const std::vector<Phase> phases = E.opt.param_kinds == 5 ? std::vector<Phase>{
+    {KK_TRIAL, "iem_residual_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}, {KK_JTPROD, "A.p3", "A.p4"}}},
+  } : std::vector<Phase>{
     {KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
     {KK_ACCEPTED, "iem_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}}},
     // all five evaluations of one point in ONE launch (iem_eval_all: the solver's first trial point is usually accepted —
@@ -2815,7 +2834,7 @@ static void emit_phases(Emitter &E) {
       ok = ok && it->second.tile == tile;   // (kinds of different workgroup sizes cannot share a launch)
       present.push_back(mb);
     }
-    if (!ok || present.size() < 2 || (ph.id == KK_ALL && present.size() < 3)) continue;
+    if (!ok || present.size() < 2 || (ph.id == KK_ALL && present.size() < 3)) continue;   // (KK_TRIAL: every member or none)
     KernelDesc F;
     F.name = std::string(ph.name) + E.name_tag;
     F.kind = ph.id; F.block = tile;
@@ -2921,6 +2940,8 @@ static Program generate_kinds(const Model &m, const Options &opt_in);
 Program generate(const Model &m, const Options &opt_in) {
   validate_indices(m);
   if (!opt_in.param_kinds) return generate_kinds(m, opt_in);
+  // the residual program: lagrad next to the model's own cons and obj, over the PLAIN model — no slot of θ is differentiated
+  if (opt_in.param_kinds == 5) return generate_kinds(m, opt_in);
   // the kinds d/dθ: the same machinery over the parameter view of the model (θ nodes are variables of the extended
   // vector [x; θ]); the builders keep the slots the kind asks for and drop the rest before anything is emitted
   Model view = parameter_view(m);
@@ -2939,9 +2960,11 @@ Program generate(const Model &m, const Options &opt_in) {
 
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
-  const bool theta = opt.param_kinds != 0, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
+  const bool lag = opt.param_kinds == 5;                                   // lag: the residual program — cons, obj and lagrad of the plain model
+  const bool theta = opt.param_kinds != 0 && !lag, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
+  const bool theta_hi = theta && opt.param_kinds >= 2;                     // the θ programs that hold ONE kind of their own
   // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod, hptprod and hppprod (an entry per θ)
-  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (opt.param_kinds >= 2 && kind == KK_HPROD) ? m.npar : m.nvar; };
+  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (theta_hi && kind == KK_HPROD) ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
   Program P;
   P.block = opt.block;
@@ -2999,7 +3022,8 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
       if (coord ? kind != KK_JAC && kind != KK_HESS : theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
-      if (!coord && opt.param_kinds >= 2 && kind != KK_HPROD) continue;
+      if (!coord && theta_hi && kind != KK_HPROD) continue;
+      if (lag && kind != KK_CONS && kind != KK_OBJ && kind != KK_JTPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3299,7 +3323,8 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       pos = std::max(pos, c.second + 1);
     }
     if (theta && kind == KK_GRAD) continue;
-    if (coord || (opt.param_kinds >= 2 && kind != KK_HPROD)) continue;
+    if (coord || (theta_hi && kind != KK_HPROD)) continue;
+    if (lag && kind != KK_JTPROD) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
@@ -3375,7 +3400,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   emit_kinds(E);
   if (!theta) {
     emit_phases(E);
-    emit_pair(E, m, whole_of, second_half);
+    if (!lag) emit_pair(E, m, whole_of, second_half);
   }
   P.source = src.str();
   P.key = fnv1a64(P.source);

@@ -141,6 +141,11 @@ struct Options {
   // constraint templates' first-order slots — on KK_JAC's table slot, and hessp — d2L/dx dθ (out) and d2L/dθ2 (aux), the
   // second-order slots with one / with two entries in θ, from ONE sweep — on KK_HESS's.  One lane per item, every slot
   // stored once through the staged COO store path, layout by param_coord_layout (iem_model.hpp); no scatter kind, no atomic.
+  // 5: the residual program, a sixth one (the sources of 0 - 4 do not move), over the PLAIN model: lagrad — σ ∇f + J' y, the
+  // gradient of  σ f + y . c: objective templates seeded with σ (A.w), constraint templates with y[row] (A.v), every first-order
+  // slot kept, ONE deterministic scatter over both — on KK_JTPROD's table slot (nvar entries out), next to the model's own
+  // cons and obj (same builders, same bodies), and KK_TRIAL with lagrad as third member (p3 = its output, p4 = its reduction
+  // buffer): c, f and the dual residual of a convergence check in one launch (iem_eval_residual).
   int param_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)

@@ -200,6 +200,24 @@ function hppprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, 
                 m.handle, dptr(x), dptr(y), obj_weight, dptr(w), dptr(out)))
     return out
 end
+# The convergence check of a solver: r = obj_weight·∇f(x) + J(x)ᵀ·y (the dual infeasibility of Ipopt / MadNLP is r minus the
+# bound multipliers) from one atomic-free kernel, and with c(x) and f(x) — a device scalar, obj[1] — from one launch.
+function lagrangian_prepare!(m::MI355XModel)
+    n = Ref{Int32}(0)
+    check(ccall((:iem_lagrad_prepare, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.handle, n))
+    return Int(n[])
+end
+function lagrangian_grad!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, out::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_lagrad, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(out)))
+    return out
+end
+function eval_residual!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, c::ROCVector{Float64},
+                        r::ROCVector{Float64}, obj::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_eval_residual, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(c), dptr(r), dptr(obj)))
+    return obj, c, r
+end
 # ... and the three blocks themselves in COO (include/iem.h has the slot order and the triangle convention of ∂²L/∂θ²):
 # Jθ = ∂c/∂θ, Hxθ = ∂²L/∂x∂θ, Hθθ = ∂²L/∂θ² — what a host with its own linear algebra assembles G = [Hxθ; Jθ] from.
 function param_coord_nnz(m::MI355XModel)

@@ -85,7 +85,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_shard_template_items", "iem_shard_blob", "iem_comm_export", "iem_comm_connect", "iem_halo_exchange", "iem_halo_exchange_async", "iem_halo_wait", "iem_halo_reads", "iem_halo_fold", "iem_allreduce_obj_grad", "iem_comm_status",
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
-           "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
+           "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
            "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
@@ -155,6 +155,9 @@ def lib():
     L.iem_eval_trial.argtypes = [vp, vp, vp, C.POINTER(dbl)]
     L.iem_eval_accepted.argtypes = [vp, vp, vp, dbl, vp, vp, vp]
     L.iem_eval_all.argtypes = [vp, vp, vp, dbl, vp, vp, vp, vp, C.POINTER(dbl)]
+    L.iem_lagrad_prepare.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.iem_lagrad.argtypes = [vp, vp, vp, dbl, vp]
+    L.iem_eval_residual.argtypes = [vp, vp, vp, dbl, vp, vp, vp]
     L.iem_grad.argtypes = [vp, vp, vp]
     L.iem_cons.argtypes = [vp, vp, vp]
     L.iem_jac_coord.argtypes = [vp, vp, vp]

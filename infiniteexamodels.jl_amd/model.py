@@ -98,6 +98,7 @@ class ExaModel:
             _lib.check(self._L.iem_create_sharded(blob, len(blob), device, _shard[0], _shard[1], _shard[2], arr, n, C.byref(h)))
         self._h = h
         self._pc_nnz = None      # lengths of the explicit θ blocks (param_coord_nnz), asked once
+        self._lag_n = None       # kernels of the residual program (lagrangian_prepare), once it is set up
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -297,6 +298,58 @@ class ExaModel:
             setattr(self.counters, "neval_" + k, getattr(self.counters, "neval_" + k) + 1)
         return (None if defer_obj else float(out.value)), c, g, jac, hess
 
+    # ---- the convergence check: the gradient of the Lagrangian in one kernel; with c and f in one launch ----
+    def lagrangian_prepare(self) -> int:
+        """Set up the program of ``lagrangian_grad`` / ``eval_residual`` now (``iem_lagrad_prepare``: otherwise their first
+        call does — synchronously, and not inside a stream capture); the number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_lagrad_prepare(self._h, C.byref(n)))
+        self._lag_n = int(n.value)
+        return self._lag_n
+
+    def lagrangian_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of the residual program (kinds cons / obj / jtprod — the
+        latter named ``iem_lagrad*`` — and the phase kernel ``iem_residual_all``, kind trial): always the LAST kernels
+        ``iem_kernel_info`` lists."""
+        n = self.lagrangian_prepare()
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        return self._kernel_infos(int(total.value) - n, int(total.value))
+
+    def lagrangian_grad(self, x, y, obj_weight: float = 1.0, out=None):
+        """``obj_weight·∇f(x) + J(x)ᵀ·y`` (nvar) from ONE atomic-free kernel (``iem_lagrad``): the dual residual of a solver's
+        convergence check, without the bound multipliers.  ``y`` may be ``None`` on a model without constraints."""
+        self._chk(x, self.meta.nvar, "x")
+        if y is not None or self.meta.ncon:
+            self._chk(y, self.meta.ncon, "y")
+        out = out if out is not None else self._new(self.meta.nvar)
+        self._chk(out, self.meta.nvar, "out")
+        self._sync_stream()
+        if self._lag_n is None:
+            self.lagrangian_prepare()
+        _lib.check(self._L.iem_lagrad(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(out)))
+        return out
+
+    def eval_residual(self, x, y, obj_weight: float = 1.0, c=None, out=None, obj=None):
+        """``obj(m, x)``, ``cons!(m, x, c)`` and :meth:`lagrangian_grad` in ONE launch (``iem_eval_residual``: what a solver
+        evaluates for its convergence check).  Returns ``(obj, c, r)``; ``obj`` is a device scalar (a tensor of one entry,
+        as :meth:`obj_device` returns), so the call is asynchronous and graph-capturable.  Identical bytes to the three
+        calls."""
+        self._chk(x, self.meta.nvar, "x")
+        if y is not None or self.meta.ncon:
+            self._chk(y, self.meta.ncon, "y")
+        c = c if c is not None else self._new(self.meta.ncon)
+        out = out if out is not None else self._new(self.meta.nvar)
+        obj = obj if obj is not None else self._new(1)
+        self._chk(c, self.meta.ncon, "c"); self._chk(out, self.meta.nvar, "out"); self._chk(obj, 1, "obj")
+        self._sync_stream()
+        if self._lag_n is None:
+            self.lagrangian_prepare()
+        _lib.check(self._L.iem_eval_residual(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(c), _ptr(out), _ptr(obj)))
+        self.counters.neval_obj += 1
+        self.counters.neval_cons += 1
+        return obj, c, out
+
     def jprod(self, x, v, Jv=None):
         """``jprod!(m, x, v, Jv)``: Jacobian–vector product (ncon)."""
         self._chk(x, self.meta.nvar, "x"); self._chk(v, self.meta.nvar, "v")
@@ -451,11 +504,13 @@ class ExaModel:
 
     def param_coord_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of ``jacp_coord`` / ``hessp_coord`` (kinds jac / hess of a
-        program of their own, names ``iem_jacp*`` / ``iem_hessp*``): always the LAST kernels ``iem_kernel_info`` lists."""
+        program of their own, names ``iem_jacp*`` / ``iem_hessp*``): the last kernels ``iem_kernel_info`` lists in front of
+        the residual program's (``lagrangian_kernels``), where that exists."""
         n = self.param_coord_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        return self._kernel_infos(int(total.value) - n, int(total.value))
+        last = int(total.value) - (self._lag_n or 0)
+        return self._kernel_infos(last - n, last)
 
     def param_prepare(self) -> int:
         """Set up the programs of jpprod / jptprod / hpprod and of hptprod now (``iem_param_prepare``: otherwise the first
