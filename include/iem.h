@@ -261,8 +261,9 @@ int iem_eval_all(iem_model *m, const double *d_x, const double *d_y, double obj_
  * a SIXTH program of their own over the plain model, set up by the first of the two calls — synchronous, outside a stream
  * capture; every later call is asynchronous on the handle's stream and capturable — or by iem_lagrad_prepare (idempotent;
  * returns the number of this program's kernels; a runtime failure of the set-up is not remembered).  The other prepare
- * calls do not prepare it and keep their counts; iem_kernel_info lists these kernels LAST, behind every other program that
- * exists on the handle (the explicit θ blocks' included), with their algorithmic bytes — the phase kernel reports the union
+ * calls do not prepare it and keep their counts; iem_kernel_info lists these kernels behind those of the θ programs, in the
+ * full order  model / three kinds / adjoint / θθ / θ-COO / residual / scaled  (every program that exists on the handle;
+ * only the scaled program's kernels come behind these), with their algorithmic bytes — the phase kernel reports the union
  * of its members' reads.  Where the phase kernel does not exist (a member missing, kinds of different workgroup sizes, more
  * workgroups than one launch takes) iem_eval_residual makes the member launches itself.  A sharded handle refuses all three
  * calls with IEM_E_ARG: the result would need the halo fold and the all-reduce. */
@@ -270,6 +271,33 @@ int iem_lagrad_prepare(iem_model *m, int32_t *out_n_kernels);
 int iem_lagrad(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out /* nvar */);
 int iem_eval_residual(iem_model *m, const double *d_x, const double *d_y, double obj_weight,
                       double *d_c /* ncon */, double *d_lagrad /* nvar */, double *d_obj /* device scalar */);
+
+/* ROW SCALING inside the kernels (extensions): what a solver that scales the NLP — Ipopt's gradient-based scaling, MadNLP's
+ * scale_constraints! — does around jac_coord! and cons!, without a pass over nnzj of its own:
+ *   iem_jac_rowmax        out[r] = max over the first-order slots of row r of |dc_r/dx_slot| — the COO entries iem_jac_coord
+ *                         writes with row r; repeated positions are NOT summed (the solvers take the maximum over the
+ *                         triplets); EVERY row is written, 0.0 for a row without a slot; a NaN slot gives NaN for its row
+ *   iem_cons_scaled       out[r] = s[r] * c_r(x)
+ *   iem_jac_coord_scaled  out[k] = s[row(k)] * jac[k], at the positions of iem_jac_structure
+ * Under the default options (fp_contract = 0), on one handle at one (x, θ): iem_cons_scaled is bitwise fl(s * c) of what
+ * iem_cons writes, iem_jac_coord_scaled bitwise fl(s[row] * v) of what iem_jac_coord writes — ONE rounded multiply of the
+ * finished value, data rows and computed rows alike — and iem_jac_rowmax bitwise the per-row maximum of |.| over what
+ * iem_jac_coord writes.  The objective and the Hessian need nothing new: iem_hess_coord(x, y .* s, obj_weight * s_f) is the
+ * scaled Hessian.  One lane per item, an item is one row: the maximum is a per-lane reduction with one exclusive store per
+ * row, the scaling one load of s[row] per row and a multiply per slot in front of the store path of jac_coord! / cons!; no
+ * atomics, every entry stored once, outputs fully overwritten, the handle's current θ (iem_set_parameter) is seen.
+ * The kernels (kinds 5 / 0 / 1, names iem_rowmax*, iem_cons_scaled*, iem_jac_scaled*) are a SEVENTH program of their own
+ * over the plain model, set up by the first of the three calls — synchronous, outside a stream capture; every later call is
+ * asynchronous on the handle's stream and capturable — or by iem_scaled_prepare (idempotent; returns the number of this
+ * program's kernels; a runtime failure of the set-up is not remembered).  The other prepare calls do not prepare it and
+ * keep their counts; iem_kernel_info lists these kernels LAST: model / three kinds / adjoint / θθ / θ-COO / residual /
+ * scaled, with their algorithmic bytes.  ncon == 0 or nnzj == 0: nothing is launched for the empty output, NULL is accepted
+ * for a zero-length array.  A sharded handle refuses all four calls with IEM_E_ARG: the values need no communication, but
+ * the deferred halo exchange (carrier workgroup, flush logic) is not taught this program — out of scope. */
+int iem_scaled_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_jac_rowmax(iem_model *m, const double *d_x, double *d_rowmax /* ncon */);
+int iem_cons_scaled(iem_model *m, const double *d_x, const double *d_s /* ncon */, double *d_c /* ncon */);
+int iem_jac_coord_scaled(iem_model *m, const double *d_x, const double *d_s /* ncon */, double *d_vals /* nnzj */);
 
 /* matrix-free products (NLPModels jprod! / jtprod! / hprod!; ExaModels' `prod = true` path —
  * not used by the reference's solvers): Jv (ncon), J'v (nvar), Hv (nvar) with
@@ -361,7 +389,8 @@ int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
  * synchronous, outside a stream capture; every later call is asynchronous and capturable — or by iem_param_coord_prepare
  * (idempotent; returns the number of this program's kernels; a runtime failure of the set-up is not remembered).
  * iem_param_prepare and iem_hppprod_prepare do not prepare it and keep their counts; iem_kernel_info lists these kernels
- * LAST, behind every other program that exists on the handle, with their algorithmic bytes read and written.  The
+ * behind those of the other θ programs, in the full order  model / three kinds / adjoint / θθ / θ-COO / residual / scaled
+ * (every program that exists on the handle), with their algorithmic bytes read and written.  The
  * structure calls and iem_param_coord_nnz need no program and no device work: they evaluate the index expressions on the
  * host, like iem_jac_structure.  A sharded handle refuses all of them with IEM_E_ARG like the products above. */
 int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels);

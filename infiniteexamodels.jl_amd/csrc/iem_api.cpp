@@ -254,6 +254,9 @@ struct iem_model {
   // and ticket words of ITS objective kernels (the model's own keep theirs)
   ParamKinds lag;
   double *d_lag_partials = nullptr;
+  // the scaled program (iem_jac_rowmax / iem_cons_scaled / iem_jac_coord_scaled; scaled_kinds = 1, over the plain model): a
+  // seventh program, set up by its own first call or by iem_scaled_prepare — the other prepare calls do not know of it
+  ParamKinds scl;
   iem::Model pc_view;
   bool pc_have_view = false;
   double *d_pc_spare[2] = {nullptr, nullptr};
@@ -953,6 +956,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "cons_direct_2d") == 0) { o.cons_direct_2d = value != 0; return IEM_OK; }
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
   if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 5 ? (int)value : value != 0; return IEM_OK; }
+  if (std::strcmp(name, "scaled_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "scaled_kinds must be 0 or 1"); o.scaled_kinds = (int)value; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1106,6 +1110,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   iem_model *m = new iem_model();
   m->device = device;
   hopt.param_kinds = 0;   // (the handle's own program; the parameter kinds are a second one, iem_model::par)
+  hopt.scaled_kinds = 0;  // (... and the scaled program a seventh, iem_model::scl)
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1253,6 +1258,7 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->lag.d_gather) if (r) hipFree(r);
   free_program(m->lag.code);
   if (m->d_lag_partials) hipFree(m->d_lag_partials);
+  free_program(m->scl.code);   // (no scatter kind: no reduction buffer, no plan)
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
@@ -1282,10 +1288,10 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
   // behind the model's own kernels: those of every further program that exists on the handle (set up by its first call or
-  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program
+  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program / scaled program
   const iem::KernelDesc *found = k < (int)m->code.prog.kernels.size() ? &m->code.prog.kernels[k] : nullptr;
   int base = (int)m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag}) {
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl}) {
     if (found || !P->tried || P->rc != IEM_OK) continue;
     const int n = (int)P->code.prog.kernels.size();
     if (k < base + n) found = &P->code.prog.kernels[k - base];
@@ -1307,7 +1313,7 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
 int iem_kernel_count(const iem_model *m, int32_t *out_total) {
   if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
   size_t n = m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag})
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl})
     if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
   *out_total = (int32_t)n;
   return IEM_OK;
@@ -1471,9 +1477,9 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
 // The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2), of the θθ kind
-// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4) or the residual program (P = m->lag, kinds = 5), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
+// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4), the residual program (P = m->lag, kinds = 5) or the scaled program (P = m->scl, kinds = 0, scaled = 1), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
 // later call.
-static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
+static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
   P.tried = true;
   // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
@@ -1493,6 +1499,7 @@ static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds) {
   };
   iem::Options po = m->opt;
   po.param_kinds = kinds;
+  po.scaled_kinds = scaled;
   try {
     P.code.prog = iem::generate(m->model, po);
   } catch (const std::exception &e) {
@@ -1774,6 +1781,68 @@ int iem_eval_residual(iem_model *m, const double *d_x, const double *d_y, double
   if (m->model.nvar == 0) return IEM_OK;
   h.out = d_lagrad; h.aux = nullptr;
   return param_launch(m, P, iem::KK_JTPROD, h);
+}
+
+// ---- row scaling in the kernels: the row maxima of the Jacobian, scaled cons! and scaled jac_coord! -------------------------
+// The scaled program (P = m->scl, scaled_kinds = 1: rowmax on KK_JPROD's table slot, cons_scaled on KK_CONS's, jac_scaled on
+// KK_JAC's; s = the head's v), set up like the θ programs.  No scatter kind: no follow-up, no memset.
+static int scaled_refuse_sharded(const iem_model *m, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the values need no communication, but the deferred halo "
+                         "exchange (carrier workgroup, flush in front of a launch that reads a halo entry) is not taught this program; "
+                         "scaled kernels on a sharded handle are out of scope");
+}
+
+static int scaled_launch(iem_model *m, int kind, const double *d_x, const double *d_s, double *d_out) {
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.v = d_s; h.out = d_out;
+  int rc;
+  for (int k : m->scl.code.launchable[kind])
+    if ((rc = launch_one(m, m->scl.code, k, h))) return rc;
+  return IEM_OK;
+}
+
+int iem_scaled_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = scaled_refuse_sharded(m, "iem_scaled_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->scl.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+/* max over the first-order slots of row r of |dc_r/dx_slot| (repeated positions not summed; 0 for a row without a slot; NaN stays) */
+int iem_jac_rowmax(iem_model *m, const double *d_x, double *d_rowmax) {
+  if (!m || !d_x || (!d_rowmax && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
+  int rc = scaled_refuse_sharded(m, "iem_jac_rowmax");
+  if (rc) return rc;
+  if (m->model.ncon == 0) return IEM_OK;   // a zero-length output: nothing to launch
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
+  return scaled_launch(m, iem::KK_JPROD, d_x, nullptr, d_rowmax);
+}
+
+/* s[r] * c_r(x) */
+int iem_cons_scaled(iem_model *m, const double *d_x, const double *d_s, double *d_c) {
+  if (!m || !d_x || ((!d_s || !d_c) && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
+  int rc = scaled_refuse_sharded(m, "iem_cons_scaled");
+  if (rc) return rc;
+  if (m->model.ncon == 0) return IEM_OK;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
+  return scaled_launch(m, iem::KK_CONS, d_x, d_s, d_c);
+}
+
+/* s[row(k)] * jac[k] at the positions of iem_jac_structure */
+int iem_jac_coord_scaled(iem_model *m, const double *d_x, const double *d_s, double *d_vals) {
+  if (!m || !d_x || (!d_s && m->model.ncon) || (!d_vals && m->model.nnzj)) return fail(IEM_E_ARG, "null argument");
+  int rc = scaled_refuse_sharded(m, "iem_jac_coord_scaled");
+  if (rc) return rc;
+  if (m->model.nnzj == 0) return IEM_OK;
+  DevGuard dg_(m->device);
+  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
+  return scaled_launch(m, iem::KK_JAC, d_x, d_s, d_vals);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

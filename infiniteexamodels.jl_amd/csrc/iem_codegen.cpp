@@ -128,6 +128,8 @@ static void emit_carrier_prologue(std::ostream &os, const std::string &wg, const
 
 // pseudo unary ops beyond the blob vocabulary
 enum { U_SGN = 1000 };
+// ... and a pseudo binary op: the NaN-propagating maximum of the scaled program's row maxima (b > a || b != b ? b : a)
+enum { B_NANMAX = 2000 };
 
 // ---------------------------------------------------------------------------
 // expression DAG
@@ -771,6 +773,16 @@ class KernelBuilder {
   // param_kinds = 5: the residual program over the PLAIN model — lagrad (σ ∇f + J' y) on the table slot of jtprod, next to the
   // model's own cons and obj
   bool lagrangian() const { return opt_.param_kinds == 5; }
+  // scaled_kinds = 1: the scaled program over the PLAIN model — rowmax on the table slot of jprod, cons_scaled on that of cons!,
+  // jac_scaled on that of jac_coord!; the factors s are A.v, indexed by the row
+  bool scaled() const { return opt_.scaled_kinds != 0; }
+  // s[row] of a constraint template's item: one load per row, where jtprod loads its seed
+  int scale_of_row(const Template &t, const TGeo &G) {
+    IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into s), not an output position
+    return load(4, 0, idxval(rv), G.guard);
+  }
+  // ONE rounded multiply of a finished value — never folded away (a slot that is the constant 1 or -0.0 still gives fl(s * slot))
+  int scaled_by(int val, int s) { return mk(VBIN, IEM_OP_MUL, s, val < 0 ? C(0.0) : val, -1, 0); }
   // param_kinds = 2: the adjoint program, hptprod alone on the table slot of hprod — tangents on the slots of x, outputs on the slots of θ
   bool theta_adjoint() const { return opt_.param_kinds == 2; }
   // param_kinds = 3: the θθ program, hppprod alone on the same table slot — tangents AND outputs on the slots of θ
@@ -793,6 +805,12 @@ class KernelBuilder {
     if (theta_coord()) return kind_ == KK_JAC ? !t.pc1.empty() : kind_ == KK_HESS && (!t.pcx.empty() || !t.pcp.empty());
     if (theta_second()) return kind_ == KK_HPROD && has_theta_slot2(t);
     if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
+    if (scaled()) switch (kind_) {
+      case KK_CONS: return t.kind == IEM_T_CON;
+      case KK_JAC: return t.kind == IEM_T_CON && t.o1step > 0;
+      case KK_JPROD: return t.kind == IEM_T_CON;           // rowmax: every row is written, 0.0 for a row without a slot
+      default: return false;
+    }
     if (lagrangian()) switch (kind_) {
       case KK_CONS: return t.kind == IEM_T_CON;
       case KK_OBJ: return t.kind == IEM_T_OBJ;
@@ -840,6 +858,7 @@ class KernelBuilder {
           IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0);
           o.pos_idx = idxval(iv); o.pos_off = t.o0;
           o.vals = {tg.val[t.root]};
+          if (scaled()) o.vals[0] = scaled_by(o.vals[0], scale_of_row(t, G));   // cons_scaled: s[row] * c_row
           alg_w_ += t.n_items;
           break;
         }
@@ -860,6 +879,10 @@ class KernelBuilder {
             break;
           }
           o.vals = tg.slots1;
+          if (kind_ == KK_JAC && scaled()) {   // jac_scaled: every finished slot times its row's factor (data rows and computed rows alike)
+            const int sc = scale_of_row(t, G);
+            for (int &v : o.vals) v = scaled_by(v, sc);
+          }
           if (kind_ == KK_JAC) {
             IdxVal iv; iv.aff = klin_aff(t, G, t.o1step, t.o1);
             o.pos_idx = idxval(iv); o.pos_off = t.o1;
@@ -883,6 +906,20 @@ class KernelBuilder {
           for (int s = 0; s < t.o1step; ++s) {
             if (!t.is_theta_idx(t.slot1_idx[s]) || tg.slots1[s] < 0) continue;
             acc = add(acc, mul(tg.slots1[s], load(4, 0, tg.pos0(t.slot1_idx[s]), G.guard)));
+          }
+          IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0);
+          o.pos_idx = idxval(iv); o.pos_off = t.o0;
+          o.vals = {acc};
+          alg_w_ += t.n_items;
+          break;
+        } else if (scaled()) {   // rowmax[row] = max over the row's first-order slots of |slot|: what a solver takes from the triplets
+          tg.forward(1);
+          tg.slots1.assign(t.o1step, -1);
+          tg.gr(t.root, 0, C(1.0));
+          int acc = C(0.0);      // a row without a slot: 0.0; a slot nothing flows into is jac_coord!'s 0.0
+          for (int s = 0; s < t.o1step; ++s) {
+            if (tg.slots1[s] < 0) continue;
+            acc = mk(VBIN, B_NANMAX, acc, mk(VUN, IEM_OP_ABS, tg.slots1[s], -1, -1, 0), -1, 0);
           }
           IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0);
           o.pos_idx = idxval(iv); o.pos_off = t.o0;
@@ -1582,7 +1619,9 @@ class KernelBuilder {
       }
       case VBIN: {
         const char *o = n.sub == IEM_OP_ADD ? "+" : n.sub == IEM_OP_SUB ? "-" : n.sub == IEM_OP_MUL ? "*" : n.sub == IEM_OP_DIV ? "/" : nullptr;
-        if (o) os << "  const double " << nm << " = v" << n.a << " " << o << " v" << n.b << ";\n";
+        if (n.sub == B_NANMAX)   // a NaN on either side stays (fmax would drop it): torch.amax's rule
+          os << "  const double " << nm << " = (v" << n.b << " > v" << n.a << " || v" << n.b << " != v" << n.b << ") ? v" << n.b << " : v" << n.a << ";\n";
+        else if (o) os << "  const double " << nm << " = v" << n.a << " " << o << " v" << n.b << ";\n";
         else os << "  const double " << nm << " = pow(v" << n.a << ", v" << n.b << ");\n";
         break;
       }
@@ -2073,7 +2112,7 @@ class KernelBuilder {
         const int id = st.back(); st.pop_back();
         if (id < 0 || !seen.insert(id).second) continue;
         const VNode &n = v_[id];
-        if (n.op == VLD) { if (loads_[n.sub].arr != 3) pure = false; }
+        if (n.op == VLD) { if (loads_[n.sub].arr != 3 && !(scaled() && loads_[n.sub].arr == 4)) pure = false; }   // (jac_scaled: the row's factor is no reason to join the computed rows)
         else if (n.op == VW) pure = false;
         else if (n.op == VUN || n.op == VGUARD) st.push_back(n.a);
         else if (n.op == VBIN || n.op == VSEL) { st.push_back(n.a); st.push_back(n.b); }
@@ -2548,7 +2587,8 @@ static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"
 static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"};   // param_kinds = 3: the θθ program
 static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", ""};     // param_kinds = 4: the explicit blocks in COO
 static const char *const kname_lag[] = {"cons", "", "", "obj", "", "", "lagrad", ""};   // param_kinds = 5: the residual program (plain model)
-static const char *const *kind_names(const Options &o) { return o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_scaled[] = {"cons_scaled", "jac_scaled", "", "", "", "rowmax", "", ""};   // scaled_kinds = 1: the scaled program (plain model)
+static const char *const *kind_names(const Options &o) { return o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2939,6 +2979,15 @@ static Program generate_kinds(const Model &m, const Options &opt_in);
 
 Program generate(const Model &m, const Options &opt_in) {
   validate_indices(m);
+  if (opt_in.scaled_kinds) {
+    // the scaled program: rowmax, cons_scaled and jac_scaled over the PLAIN model, through the store path of the model's own
+    // kinds; the model's tile on every grid (as the explicit θ blocks), no pair, no phase kernel
+    if (opt_in.param_kinds) throw std::runtime_error("scaled_kinds and param_kinds name different programs: set one of them");
+    Options o = opt_in;
+    o.hess_merge = 0; o.phase_kernels = 0; o.pair_kernel = 0;
+    o.big_batch_jac = o.big_batch_hess = 0;
+    return generate_kinds(m, o);
+  }
   if (!opt_in.param_kinds) return generate_kinds(m, opt_in);
   // the residual program: lagrad next to the model's own cons and obj, over the PLAIN model — no slot of θ is differentiated
   if (opt_in.param_kinds == 5) return generate_kinds(m, opt_in);
@@ -2960,6 +3009,7 @@ Program generate(const Model &m, const Options &opt_in) {
 
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
+  const bool scl = opt.scaled_kinds != 0;                                  // scl: the scaled program — cons_scaled, jac_scaled and rowmax of the plain model
   const bool lag = opt.param_kinds == 5;                                   // lag: the residual program — cons, obj and lagrad of the plain model
   const bool theta = opt.param_kinds != 0 && !lag, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
   const bool theta_hi = theta && opt.param_kinds >= 2;                     // the θ programs that hold ONE kind of their own
@@ -3024,6 +3074,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       if (coord ? kind != KK_JAC && kind != KK_HESS : theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
       if (!coord && theta_hi && kind != KK_HPROD) continue;
       if (lag && kind != KK_CONS && kind != KK_OBJ && kind != KK_JTPROD) continue;
+      if (scl && kind != KK_CONS && kind != KK_JAC && kind != KK_JPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3325,6 +3376,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     if (theta && kind == KK_GRAD) continue;
     if (coord || (theta_hi && kind != KK_HPROD)) continue;
     if (lag && kind != KK_JTPROD) continue;
+    if (scl) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
@@ -3400,7 +3452,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   emit_kinds(E);
   if (!theta) {
     emit_phases(E);
-    if (!lag) emit_pair(E, m, whole_of, second_half);
+    if (!lag && !scl) emit_pair(E, m, whole_of, second_half);
   }
   P.source = src.str();
   P.key = fnv1a64(P.source);

@@ -147,6 +147,17 @@ struct Options {
   // cons and obj (same builders, same bodies), and KK_TRIAL with lagrad as third member (p3 = its output, p4 = its reduction
   // buffer): c, f and the dual residual of a convergence check in one launch (iem_eval_residual).
   int param_kinds = 0;
+  // 1: generate() emits the SCALED program instead — a seventh one over the PLAIN model (param_kinds must be 0; with 0 here
+  // the sources, keys and launch plans of every other program are what they were): the row scaling of a solver
+  // (Ipopt's gradient-based scaling, MadNLP's scale_constraints!) inside the kernels.  s = A.v (ncon factors):
+  //   rowmax      on KK_JPROD's table slot (ncon out, no tangent loaded): max over the first-order slots of the row of |slot|,
+  //               NaN-propagating, 0.0 for a row without a slot — a per-lane reduction, one exclusive store per row
+  //   cons_scaled on KK_CONS's: s[row] * c_row(x), ONE rounded multiply of the value cons! computes
+  //   jac_scaled  on KK_JAC's: s[row] * slot, ONE rounded multiply of every finished slot value (the reverse sweep is NOT
+  //               seeded with s: the linear rows' partials are item data), at the positions of jac_structure
+  // Same groups, folds, halves (jac_split) and store path as the model's own kinds; like the explicit θ blocks the program
+  // keeps the model's tile on every grid (no large-grid shape), and it has no pair and no phase kernel.  No atomics.
+  int scaled_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };

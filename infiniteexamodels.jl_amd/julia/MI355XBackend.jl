@@ -218,6 +218,26 @@ function eval_residual!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Floa
                 m.handle, dptr(x), dptr(y), obj_weight, dptr(c), dptr(r), dptr(obj)))
     return obj, c, r
 end
+# Row scaling inside the kernels (Ipopt's gradient-based scaling, MadNLP's scale_constraints!): the row maxima of the Jacobian
+# from one kernel — no triplet buffer —, and cons! / jac_coord! with every value times its row's factor s[row] in front of the
+# store (bitwise c .* s and vals .* s[rows]).  The scaled Hessian is hess_coord!(m, x, y .* s, vals; obj_weight = σ * obj_scale).
+function scaled_prepare!(m::MI355XModel)
+    n = Ref{Int32}(0)
+    check(ccall((:iem_scaled_prepare, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.handle, n))
+    return Int(n[])
+end
+function jac_row_maxabs!(m::MI355XModel, x::ROCVector{Float64}, out::ROCVector{Float64})
+    check(ccall((:iem_jac_rowmax, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(out)))
+    return out
+end
+function cons_scaled!(m::MI355XModel, x::ROCVector{Float64}, s::ROCVector{Float64}, c::ROCVector{Float64})
+    check(ccall((:iem_cons_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(s), dptr(c)))
+    return c
+end
+function jac_coord_scaled!(m::MI355XModel, x::ROCVector{Float64}, s::ROCVector{Float64}, vals::ROCVector{Float64})
+    check(ccall((:iem_jac_coord_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(s), dptr(vals)))
+    return vals
+end
 # ... and the three blocks themselves in COO (include/iem.h has the slot order and the triangle convention of ∂²L/∂θ²):
 # Jθ = ∂c/∂θ, Hxθ = ∂²L/∂x∂θ, Hθθ = ∂²L/∂θ² — what a host with its own linear algebra assembles G = [Hxθ; Jθ] from.
 function param_coord_nnz(m::MI355XModel)

@@ -99,6 +99,7 @@ class ExaModel:
         self._h = h
         self._pc_nnz = None      # lengths of the explicit θ blocks (param_coord_nnz), asked once
         self._lag_n = None       # kernels of the residual program (lagrangian_prepare), once it is set up
+        self._scl_n = None       # kernels of the scaled program (scaled_prepare), once it is set up
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -310,11 +311,12 @@ class ExaModel:
     def lagrangian_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the residual program (kinds cons / obj / jtprod — the
         latter named ``iem_lagrad*`` — and the phase kernel ``iem_residual_all``, kind trial): always the LAST kernels
-        ``iem_kernel_info`` lists."""
+        ``iem_kernel_info`` lists in front of the scaled program's (``scaled_kernels``), where that exists."""
         n = self.lagrangian_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        return self._kernel_infos(int(total.value) - n, int(total.value))
+        last = int(total.value) - (self._scl_n or 0)
+        return self._kernel_infos(last - n, last)
 
     def lagrangian_grad(self, x, y, obj_weight: float = 1.0, out=None):
         """``obj_weight·∇f(x) + J(x)ᵀ·y`` (nvar) from ONE atomic-free kernel (``iem_lagrad``): the dual residual of a solver's
@@ -349,6 +351,61 @@ class ExaModel:
         self.counters.neval_obj += 1
         self.counters.neval_cons += 1
         return obj, c, out
+
+    # ---- row scaling in the kernels: the Jacobian's row maxima, scaled cons! and scaled jac_coord! ----
+    def scaled_prepare(self) -> int:
+        """Set up the program of ``jac_row_maxabs`` / ``cons_scaled`` / ``jac_coord_scaled`` now (``iem_scaled_prepare``:
+        otherwise their first call does — synchronously, and not inside a stream capture); the number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_scaled_prepare(self._h, C.byref(n)))
+        self._scl_n = int(n.value)
+        return self._scl_n
+
+    def scaled_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of the scaled program (kinds jprod / cons / jac, names
+        ``iem_rowmax*`` / ``iem_cons_scaled*`` / ``iem_jac_scaled*``): always the LAST kernels ``iem_kernel_info`` lists."""
+        n = self.scaled_prepare()
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        return self._kernel_infos(int(total.value) - n, int(total.value))
+
+    def jac_row_maxabs(self, x, out=None):
+        """Per constraint row the largest ``|∂c_r/∂x_j|`` over the entries ``jac_coord`` writes for it (ncon; repeated
+        positions are not summed, a row without an entry gets 0, a NaN entry gives NaN) from ONE kernel
+        (``iem_jac_rowmax``): no COO buffer, no structure — what gradient-based scaling needs at the start point."""
+        self._chk(x, self.meta.nvar, "x")
+        out = out if out is not None else self._new(self.meta.ncon)
+        self._chk(out, self.meta.ncon, "out")
+        self._sync_stream()
+        if self._scl_n is None:
+            self.scaled_prepare()
+        _lib.check(self._L.iem_jac_rowmax(self._h, _ptr(x), _ptr(out)))
+        return out
+
+    def cons_scaled(self, x, s, c=None):
+        """``s ∘ cons(x)`` from the constraint kernel itself (``iem_cons_scaled``): bitwise ``cons(x).mul_(s)``."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(s, self.meta.ncon, "s")
+        c = c if c is not None else self._new(self.meta.ncon)
+        self._chk(c, self.meta.ncon, "c")
+        self._sync_stream()
+        if self._scl_n is None:
+            self.scaled_prepare()
+        _lib.check(self._L.iem_cons_scaled(self._h, _ptr(x), _ptr(s), _ptr(c)))
+        self.counters.neval_cons += 1
+        return c
+
+    def jac_coord_scaled(self, x, s, vals=None):
+        """``jac_coord(x)`` with every entry times its row's factor ``s[row]`` (``iem_jac_coord_scaled``), at the positions
+        of ``jac_structure``: bitwise ``jac_coord(x).mul_(s[rows])``, without the row gather."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(s, self.meta.ncon, "s")
+        vals = vals if vals is not None else self._new(self.meta.nnzj)
+        self._chk(vals, self.meta.nnzj, "vals")
+        self._sync_stream()
+        if self._scl_n is None:
+            self.scaled_prepare()
+        _lib.check(self._L.iem_jac_coord_scaled(self._h, _ptr(x), _ptr(s), _ptr(vals)))
+        self.counters.neval_jac += 1
+        return vals
 
     def jprod(self, x, v, Jv=None):
         """``jprod!(m, x, v, Jv)``: Jacobian–vector product (ncon)."""
@@ -505,11 +562,11 @@ class ExaModel:
     def param_coord_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of ``jacp_coord`` / ``hessp_coord`` (kinds jac / hess of a
         program of their own, names ``iem_jacp*`` / ``iem_hessp*``): the last kernels ``iem_kernel_info`` lists in front of
-        the residual program's (``lagrangian_kernels``), where that exists."""
+        the residual program's (``lagrangian_kernels``) and the scaled program's (``scaled_kernels``), where those exist."""
         n = self.param_coord_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._lag_n or 0)
+        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0)
         return self._kernel_infos(last - n, last)
 
     def param_prepare(self) -> int:
