@@ -299,6 +299,24 @@ int iem_jac_rowmax(iem_model *m, const double *d_x, double *d_rowmax /* ncon */)
 int iem_cons_scaled(iem_model *m, const double *d_x, const double *d_s /* ncon */, double *d_c /* ncon */);
 int iem_jac_coord_scaled(iem_model *m, const double *d_x, const double *d_s /* ncon */, double *d_vals /* nnzj */);
 
+/* ---- the KKT operator in one launch ------------------------------------------------------------------------------------------
+ * out_x = W u + J' v,  out_y = J u   with  W = obj_weight ∇²f(x) + Σ_r y_r ∇²c_r(x)  (the full symmetric operator, as iem_hprod
+ * applies it) and J = ∂c/∂x: the product with K0 = [W, J'; J, 0] that a Newton step's residual and every matrix-free method need,
+ * from ONE launch (kernel iem_kktprod_all: the x-part is hprod's symbolic sweep with one more addend per first-order slot of a
+ * constraint row, v[row] ∂c_row/∂x_slot, through one deterministic scatter — no float atomic, bitwise reproducible; the y-part
+ * is the model's own jprod body, out_y carries the bits of iem_jprod).  Where that kernel does not exist (no constraint, kinds
+ * of different workgroup sizes, more workgroups than one launch takes) the two member launches are made.  An entry of out_x no
+ * template touches is 0; both outputs are fully overwritten; the handle's current θ is seen.  d_v == NULL means v = 0
+ * (out_x = W u).  ncon == 0: d_y, d_v and d_out_y may be NULL.  The outputs may not overlap each other or an input: IEM_E_ARG.
+ * The kernels (kinds 7 / 5 / 9, names iem_kktx*, iem_kkty*, iem_kktprod_all) are an EIGHTH program of their own over the plain
+ * model, set up by the first call — synchronous, outside a stream capture; every later call is asynchronous on the handle's
+ * stream and capturable — or by iem_kktprod_prepare (idempotent; the number of this program's kernels).  The other prepare
+ * calls do not prepare it and keep their counts; iem_kernel_info lists these kernels LAST, behind the scaled program's.
+ * A sharded handle refuses both calls with IEM_E_ARG (the x-part would need the halo fold of hprod and jtprod). */
+int iem_kktprod_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u /* nvar */,
+                const double *d_v /* ncon, NULL = 0 */, double *d_out_x /* nvar */, double *d_out_y /* ncon */);
+
 /* matrix-free products (NLPModels jprod! / jtprod! / hprod!; ExaModels' `prod = true` path —
  * not used by the reference's solvers): Jv (ncon), J'v (nvar), Hv (nvar) with
  * H the Hessian of obj_weight*f + y'c. */
@@ -491,8 +509,8 @@ int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, 
  *                                                                   wrote; d_sigma: nvar doubles or NULL)
  *   iem_kkt_factor(k, inertia)        block cyclic reduction + the border's Schur complement; inertia[3] = {positive, negative,
  *                                     doubtful} pivots of K (a correctly regularised system has ncon negative ones); synchronises
- *   iem_kkt_solve(k, d_rhs, d_sol)    K sol = rhs (nvar + ncon doubles each; no refinement — K x for a residual is
- *                                     iem_hprod + iem_jtprod / iem_jprod + the diagonal terms)
+ *   iem_kkt_solve(k, d_rhs, d_sol)    K sol = rhs (nvar + ncon doubles each; one pass through the factors — the residual
+ *                                     rhs − K sol and iterative refinement: iem_kkt_residual / iem_kkt_solve_refined below)
  * d_rhs and d_sol may be the same array.  The object borrows the model handle (its stream, device and kernel cache): destroy
  * it before iem_destroy(m).  Models whose blocks / border / coupling exceed the solver's limits (96 / 64 / 48) are refused by
  * iem_kkt_create. */
@@ -532,6 +550,26 @@ int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs
 
 /* HIP source of the solver's kernels for one (nb, ne, nc) and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key);
+
+/* r = rhs − K sol  with  K = [W + diag(sigma) + delta_w I, J'; J, −delta_c I]  at (x, y, obj_weight) — matrix-free: iem_kktprod
+ * on the borrowed model handle (K0 sol into a workspace of nvar + ncon doubles that the first call allocates and iem_kkt_destroy
+ * frees) and ONE finishing kernel that computes, without contraction and in this order,
+ *     r_x = rhs_x − (p_x + (sigma + delta_w) ∘ sol_x),     r_y = rhs_y − (p_y − delta_c · sol_y)
+ * and — d_norm != NULL — the device scalar max_i |r_i|: an integer maximum over the bit patterns (a NaN in r gives a NaN), order-
+ * independent and bitwise reproducible.  d_sigma: nvar doubles or NULL.  d_r may be d_rhs; no other overlap.  The factors are not
+ * touched: every mode of the object (1-D chain, lanes, hubs), factorised or not.  Asynchronous and capturable after the first
+ * call (or after iem_kktprod_prepare and one call). */
+int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma /* nvar or NULL */,
+                     double delta_w, double delta_c, const double *d_rhs, const double *d_sol, double *d_r, double *d_norm);
+/* sol = solve(rhs); then `steps` times  r = residual(sol), sol += solve(r)  — each step bitwise what iem_kkt_solve,
+ * iem_kkt_residual and a vector add give.  d_norms (steps + 1 doubles or NULL): d_norms[i] = max |r| in front of step i, the
+ * last entry the one behind the last step (with d_norms == NULL that last residual is not computed).  steps = 0 is iem_kkt_solve
+ * (plus one norm).  No host read-back of a norm and no early exit: as asynchronous and capturable as iem_kkt_solve itself is for
+ * the object (a border is solved on the host).  d_sol may not overlap d_rhs.  Workspace: 3 (nvar + ncon) doubles, as above. */
+int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w,
+                          double delta_c, const double *d_rhs, double *d_sol, int steps, double *d_norms /* steps + 1 or NULL */);
+/* HIP source of the two finishing kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_kkt_residual_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

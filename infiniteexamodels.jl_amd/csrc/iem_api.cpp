@@ -41,6 +41,9 @@ static const char *kKktSource =
 static const char *kKktManySource =   // the multi-column solve kernels, behind the single-column ones in every chain KKT code object
 #include "iem_kkt_many_device_h.inc"
     ;
+static const char *kKktResidualSource =   // the finishing kernels of iem_kkt_residual / iem_kkt_solve_refined: a code object of their own
+#include "iem_kkt_residual_device_h.inc"
+    ;
 
 namespace {
 
@@ -257,6 +260,13 @@ struct iem_model {
   // the scaled program (iem_jac_rowmax / iem_cons_scaled / iem_jac_coord_scaled; scaled_kinds = 1, over the plain model): a
   // seventh program, set up by its own first call or by iem_scaled_prepare — the other prepare calls do not know of it
   ParamKinds scl;
+  // the KKT operator (iem_kktprod; kkt_kinds = 1, over the plain model): an eighth program, set up by its own first call or by
+  // iem_kktprod_prepare — the other prepare calls do not know of it.  `d_kkt_zero`: ncon zeros, the dual direction of a call
+  // with d_v == NULL.  `kres_*`: the finishing kernels of iem_kkt_residual (loaded by its first call)
+  ParamKinds kkt;
+  double *d_kkt_zero = nullptr;
+  hipModule_t kres_mod = nullptr;
+  hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
   iem::Model pc_view;
   bool pc_have_view = false;
   double *d_pc_spare[2] = {nullptr, nullptr};
@@ -957,6 +967,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "digit_fields") == 0) { o.digit_fields = value != 0; return IEM_OK; }
   if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 5 ? (int)value : value != 0; return IEM_OK; }
   if (std::strcmp(name, "scaled_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "scaled_kinds must be 0 or 1"); o.scaled_kinds = (int)value; return IEM_OK; }
+  if (std::strcmp(name, "kkt_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "kkt_kinds must be 0 or 1"); o.kkt_kinds = (int)value; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1111,6 +1122,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   m->device = device;
   hopt.param_kinds = 0;   // (the handle's own program; the parameter kinds are a second one, iem_model::par)
   hopt.scaled_kinds = 0;  // (... and the scaled program a seventh, iem_model::scl)
+  hopt.kkt_kinds = 0;     // (... and the KKT operator an eighth, iem_model::kkt)
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1259,6 +1271,12 @@ int iem_destroy(iem_model *m) {
   free_program(m->lag.code);
   if (m->d_lag_partials) hipFree(m->d_lag_partials);
   free_program(m->scl.code);   // (no scatter kind: no reduction buffer, no plan)
+  for (double *r : m->kkt.d_red) if (r) hipFree(r);
+  for (long long *r : m->kkt.d_axis) if (r) hipFree(r);
+  for (long long *r : m->kkt.d_gather) if (r) hipFree(r);
+  free_program(m->kkt.code);
+  if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
+  if (m->kres_mod) hipModuleUnload(m->kres_mod);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
@@ -1288,10 +1306,11 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
   // behind the model's own kernels: those of every further program that exists on the handle (set up by its first call or
-  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program / scaled program
+  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program / scaled program /
+  // KKT operator
   const iem::KernelDesc *found = k < (int)m->code.prog.kernels.size() ? &m->code.prog.kernels[k] : nullptr;
   int base = (int)m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl}) {
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt}) {
     if (found || !P->tried || P->rc != IEM_OK) continue;
     const int n = (int)P->code.prog.kernels.size();
     if (k < base + n) found = &P->code.prog.kernels[k - base];
@@ -1313,7 +1332,7 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
 int iem_kernel_count(const iem_model *m, int32_t *out_total) {
   if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
   size_t n = m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl})
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt})
     if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
   *out_total = (int32_t)n;
   return IEM_OK;
@@ -1479,7 +1498,7 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 // The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2), of the θθ kind
 // (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4), the residual program (P = m->lag, kinds = 5) or the scaled program (P = m->scl, kinds = 0, scaled = 1), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
 // later call.
-static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0) {
+static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0, int kkt = 0) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
   P.tried = true;
   // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
@@ -1500,6 +1519,7 @@ static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int 
   iem::Options po = m->opt;
   po.param_kinds = kinds;
   po.scaled_kinds = scaled;
+  po.kkt_kinds = kkt;
   try {
     P.code.prog = iem::generate(m->model, po);
   } catch (const std::exception &e) {
@@ -1843,6 +1863,80 @@ int iem_jac_coord_scaled(iem_model *m, const double *d_x, const double *d_s, dou
   DevGuard dg_(m->device);
   if ((rc = param_program(m, m->scl, 0, 1))) return rc;
   return scaled_launch(m, iem::KK_JAC, d_x, d_s, d_vals);
+}
+
+// ---- the KKT operator: out_x = W u + J' v, out_y = J u in one launch ----------------------------------------------------------
+// The eighth program (P = m->kkt, kkt_kinds = 1: kktx on KK_HPROD's table slot, kkty on KK_JPROD's, KK_TRIAL with both as
+// members; u = the head's v, the dual direction = the head's last word), set up like the θ programs; kktx's memsets and
+// follow-ups stay here, as lagrad's do.
+static int kktprod_refuse_sharded(const iem_model *m, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the x-part would need the halo fold and the all-reduce of "
+                         "hprod! and jtprod!; a sharded KKT operator is out of scope");
+}
+
+static int kktprod_program(iem_model *m) {
+  int rc = param_program(m, m->kkt, 0, 0, 1);
+  if (rc) return rc;
+  if (!m->d_kkt_zero && m->model.ncon > 0) {   // the dual direction of a call with d_v == NULL
+    const size_t bytes = (size_t)m->model.ncon * 8;
+    if (hipMalloc((void **)&m->d_kkt_zero, bytes) != hipSuccess) { m->d_kkt_zero = nullptr; return fail(IEM_E_HIP, "hipMalloc zero direction"); }
+    if (hipMemset(m->d_kkt_zero, 0, bytes) != hipSuccess) { hipFree(m->d_kkt_zero); m->d_kkt_zero = nullptr; return fail(IEM_E_HIP, "hipMemset zero direction"); }
+  }
+  return IEM_OK;
+}
+
+int iem_kktprod_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = kktprod_refuse_sharded(m, "iem_kktprod_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = kktprod_program(m))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->kkt.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+static bool kkt_overlap(const double *a, int64_t na, const double *b, int64_t nb) {
+  if (!a || !b || na <= 0 || nb <= 0) return false;
+  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)na * 8, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)nb * 8;
+  return a0 < b1 && b0 < a1;
+}
+
+int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u, const double *d_v, double *d_out_x, double *d_out_y) {
+  if (!m) return fail(IEM_E_ARG, "null argument");
+  const int64_t nvar = m->model.nvar, ncon = m->model.ncon;
+  if (((!d_x || !d_u || !d_out_x) && nvar) || ((!d_y || !d_out_y) && ncon)) return fail(IEM_E_ARG, "null argument");
+  int rc = kktprod_refuse_sharded(m, "iem_kktprod");
+  if (rc) return rc;
+  for (const auto &in : {std::make_pair(d_x, nvar), std::make_pair(d_u, nvar), std::make_pair(d_y, ncon), std::make_pair(d_v, ncon)})
+    if (kkt_overlap(d_out_x, nvar, in.first, in.second) || kkt_overlap(d_out_y, ncon, in.first, in.second))
+      return fail(IEM_E_ARG, "iem_kktprod: an output overlaps an input");
+  if (kkt_overlap(d_out_x, nvar, d_out_y, ncon)) return fail(IEM_E_ARG, "iem_kktprod: the two outputs overlap");
+  if (nvar == 0 && ncon == 0) return IEM_OK;
+  DevGuard dg_(m->device);
+  if ((rc = kktprod_program(m))) return rc;
+  iem_model::ParamKinds &P = m->kkt;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_u; h.w = obj_weight;
+  h.obj = const_cast<double *>(d_v ? d_v : m->d_kkt_zero);   // (the head's last word: read only)
+  double *red = P.d_red[iem::KK_HPROD];
+  if (nvar)
+    for (auto &z : P.code.prog.zero_ranges[iem::KK_HPROD])
+      HIP_TRY(hipMemsetAsync(d_out_x + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
+  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
+    h.out = d_out_x; h.aux = red; h.g = d_out_y;
+    for (int k : P.code.launchable[iem::KK_TRIAL])
+      if ((rc = launch_one(m, P.code, k, h))) return rc;
+    return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_HPROD, d_out_x, red);
+  }
+  h.out = d_out_y; h.aux = nullptr;
+  for (int k : P.code.launchable[iem::KK_JPROD])
+    if ((rc = launch_one(m, P.code, k, h))) return rc;
+  if (nvar == 0) return IEM_OK;
+  h.out = d_out_x; h.aux = red;
+  for (int k : P.code.launchable[iem::KK_HPROD])
+    if ((rc = launch_one(m, P.code, k, h))) return rc;
+  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_HPROD, d_out_x, red);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {
@@ -2773,6 +2867,7 @@ struct iem_kkt {
   int64_t n_dest = 0, n_on = 0, n_h = 0, n_j = 0;
   double *m_r = nullptr, *m_z = nullptr, *m_rBp = nullptr, *m_xB = nullptr, *m_part = nullptr;      // iem_kkt_solve_many: ONE chunk of columns, allocated by its first call
   std::vector<double> Gs;        // the border's Schur complement (host), set by iem_kkt_factor
+  double *w_ref = nullptr;       // iem_kkt_residual / iem_kkt_solve_refined: p, r, dsol (3 (nvar + ncon) doubles), allocated by the first call
   bool factored = false;
   struct KktHub *hub = nullptr;  // hub mode (L.hubs): the span-sparse border's buffers and the library handle of its GEMMs
 };
@@ -3198,7 +3293,7 @@ int iem_kkt_destroy(iem_kkt *k) {
   DevGuard dg_(k->m->device);
   hub_free(k);
   for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_r, (void *)k->d_z, (void *)k->d_rBp, (void *)k->d_xB, (void *)k->d_part,
-                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part,
+                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref,
                   (void *)k->d_rows, (void *)k->d_cols, (void *)k->d_dest, (void *)k->d_on, (void *)k->d_pos, (void *)k->d_border, (void *)k->d_bloc, (void *)k->d_info,
                   (void *)k->d_seg, (void *)k->d_perm})
     if (p) hipFree(p);
@@ -3318,6 +3413,76 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
     return rc;
   { Mv A{d_sol, k->d_r, k->d_on, k->d_pos, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
   if (L.n_border) { Mv A{d_sol, k->d_xB, k->d_border, k->d_bloc, (long long)L.n_border}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc; }
+  return IEM_OK;
+}
+
+/* ---- the residual of a KKT solve, matrix-free, and iterative refinement with it ---------------------------------------------- */
+namespace {
+std::string kkt_residual_source() {
+  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktResidualSource;
+}
+// the finishing kernels and the workspace {p, r, dsol}: the synchronous part of the first call
+int kkt_refine_setup(iem_kkt *k) {
+  iem_model *m = k->m;
+  if (!m->kres_fn) {
+    int rc = load_source(m, kkt_residual_source(), &m->kres_mod);
+    if (rc) return rc;
+    HIP_TRY(hipModuleGetFunction(&m->kres_axpy, m->kres_mod, "kkt_axpy1"));
+    HIP_TRY(hipModuleGetFunction(&m->kres_fn, m->kres_mod, "kkt_residual"));
+  }
+  if (!k->w_ref) HIP_TRY(hipMalloc((void **)&k->w_ref, (size_t)std::max<int64_t>(3 * (k->L.nvar + k->L.ncon), 1) * 8));
+  return IEM_OK;
+}
+long long kkt_stream_grid(int64_t n) { return (long long)std::min<int64_t>((n + 255) / 256, 4096); }
+}  // namespace
+
+int iem_kkt_residual_source(char **out_src, uint64_t *out_key) {
+  const std::string s = kkt_residual_source();
+  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
+  if (out_key) *out_key = iem::fnv1a64(s);
+  return IEM_OK;
+}
+
+int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
+                     const double *d_rhs, const double *d_sol, double *d_r, double *d_norm) {
+  if (!k || !d_rhs || !d_sol || !d_r) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = k->m;
+  const int64_t nvar = k->L.nvar, ncon = k->L.ncon, n = nvar + ncon;
+  if (kkt_overlap(d_r, n, d_sol, n) || (d_r != d_rhs && kkt_overlap(d_r, n, d_rhs, n)) || kkt_overlap(d_r, n, d_norm, 1) || kkt_overlap(d_norm, 1, d_sol, n) ||
+      kkt_overlap(d_norm, 1, d_rhs, n))
+    return fail(IEM_E_ARG, "iem_kkt_residual: d_r overlaps d_sol or part of d_rhs, or d_norm lies inside a vector");
+  DevGuard dg_(m->device);
+  int rc = kkt_refine_setup(k);
+  if (rc) return rc;
+  double *p = k->w_ref;
+  if ((rc = iem_kktprod(m, d_x, d_y, obj_weight, d_sol, ncon ? d_sol + nvar : nullptr, p, ncon ? p + nvar : nullptr))) return rc;
+  if (d_norm) HIP_TRY(hipMemsetAsync(d_norm, 0, 8, m->stream));
+  struct { const double *p, *rhs, *sol, *sigma; double *r; unsigned long long *norm; double dw, dc; long long nvar, n; } A{
+      p, d_rhs, d_sol, d_sigma, d_r, (unsigned long long *)d_norm, delta_w, delta_c, (long long)nvar, (long long)n};
+  return kkt_launch_raw(m, m->kres_fn, &A, sizeof A, kkt_stream_grid(n), 256);
+}
+
+int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
+                          const double *d_rhs, double *d_sol, int steps, double *d_norms) {
+  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
+  if (steps < 0) return fail(IEM_E_ARG, "iem_kkt_solve_refined: steps must not be negative");
+  const int64_t n = k->L.nvar + k->L.ncon;
+  if (kkt_overlap(d_sol, n, d_rhs, n) || kkt_overlap(d_norms, steps + 1, d_sol, n) || kkt_overlap(d_norms, steps + 1, d_rhs, n))
+    return fail(IEM_E_ARG, "iem_kkt_solve_refined: d_sol, d_rhs and d_norms may not overlap");
+  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc = kkt_refine_setup(k);
+  if (rc) return rc;
+  double *r = k->w_ref + n, *dsol = k->w_ref + 2 * n;
+  if ((rc = iem_kkt_solve(k, d_rhs, d_sol))) return rc;
+  for (int i = 0; i < steps; ++i) {
+    if ((rc = iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms ? d_norms + i : nullptr))) return rc;
+    if ((rc = iem_kkt_solve(k, r, dsol))) return rc;
+    struct { double *sol; const double *d; long long n; } A{d_sol, dsol, (long long)n};
+    if ((rc = kkt_launch_raw(m, m->kres_axpy, &A, sizeof A, kkt_stream_grid(n), 256))) return rc;
+  }
+  if (d_norms) return iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms + steps);
   return IEM_OK;
 }
 

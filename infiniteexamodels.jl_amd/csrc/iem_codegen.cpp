@@ -172,7 +172,7 @@ struct ILoad {
 };
 
 struct Load {
-  int arr;       // 0 x, 1 theta, 2 y, 3 fa[slot]
+  int arr;       // 0 x, 1 theta, 2 y, 3 fa[slot], 4 v, 5 dv (the KKT operator's dual direction, read at row indices)
   int slot;
   int idxval;    // position (0-based) as IdxVal id
   std::set<int> guards;
@@ -776,6 +776,9 @@ class KernelBuilder {
   // scaled_kinds = 1: the scaled program over the PLAIN model — rowmax on the table slot of jprod, cons_scaled on that of cons!,
   // jac_scaled on that of jac_coord!; the factors s are A.v, indexed by the row
   bool scaled() const { return opt_.scaled_kinds != 0; }
+  // kkt_kinds = 1: the KKT operator over the PLAIN model — kktx (W u + J' dv) on the table slot of hprod, kkty (J u) on that of
+  // jprod with the model's own builder; u = A.v, the dual direction dv = A.p6, read at row indices like y
+  bool kkt() const { return opt_.kkt_kinds != 0; }
   // s[row] of a constraint template's item: one load per row, where jtprod loads its seed
   int scale_of_row(const Template &t, const TGeo &G) {
     IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into s), not an output position
@@ -809,6 +812,13 @@ class KernelBuilder {
       case KK_CONS: return t.kind == IEM_T_CON;
       case KK_JAC: return t.kind == IEM_T_CON && t.o1step > 0;
       case KK_JPROD: return t.kind == IEM_T_CON;           // rowmax: every row is written, 0.0 for a row without a slot
+      default: return false;
+    }
+    if (kkt()) switch (kind_) {
+      case KK_JPROD: return t.kind == IEM_T_CON;
+      // every template with a second-order slot, and every constraint template with a first-order one (an objective template
+      // contributes no first-order term: without a second-order slot it has nothing to add)
+      case KK_HPROD: return t.o2step > 0 || (t.kind == IEM_T_CON && t.o1step > 0);
       default: return false;
     }
     if (lagrangian()) switch (kind_) {
@@ -980,15 +990,19 @@ class KernelBuilder {
           break;
         }
         case KK_HPROD: {   // (H v): slot (a, b) with value h adds h*v[b] to row a and, if a != b, h*v[a] to row b
-          tg.forward(2);
+          // kktx: a linear row (no second-order slot) has a first-order sweep only — its partials are item data
+          const bool kkt_first = kkt() && t.kind == IEM_T_CON && t.o1step > 0, second = !kkt() || t.o2step > 0;
+          tg.forward(second ? 2 : 1);
           tg.slots2.assign(t.o2step, -1);
-          int adj;
-          if (t.kind == IEM_T_OBJ) adj = mk(VW, 0, -1, -1, -1, 0);
-          else {
-            IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0); iv.aff.space = 4;   // a row index (into y), not an output position
-            adj = load(2, 0, idxval(iv), G.guard);
+          if (second) {
+            int adj;
+            if (t.kind == IEM_T_OBJ) adj = mk(VW, 0, -1, -1, -1, 0);
+            else {
+              IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0); iv.aff.space = 4;   // a row index (into y), not an output position
+              adj = load(2, 0, idxval(iv), G.guard);
+            }
+            tg.hr0(t.root, 0, adj, C(0.0));
           }
-          tg.hr0(t.root, 0, adj, C(0.0));
           std::map<int, int> dest;   // destination IdxVal id (0-based position) -> accumulated DAG value
           std::map<int, int> dest_tidx;
           std::vector<int> dest_order;
@@ -1022,6 +1036,13 @@ class KernelBuilder {
               if (!never) c2 = mk(VSEL, sel_id(ia, ib), C(0.0), c2, -1, 0);
               contribute(pb, c2, t.slot2_j[s]);
             }
+          }
+          if (kkt_first) {   // + (J' dv): the row's first-order sweep seeded with dv[row], as jtprod's with v[row] — through the same map
+            IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into dv), not an output position
+            tg.slots1.assign(t.o1step, -1);
+            tg.gr(t.root, 0, load(5, 0, idxval(rv), G.guard));
+            for (int s = 0; s < t.o1step; ++s)
+              contribute(tg.pos0(t.slot1_idx[s]), tg.slots1[s] < 0 ? C(0.0) : tg.slots1[s], t.slot1_idx[s]);
           }
           for (int pid : dest_order) {
             o.vals.push_back(dest[pid]);
@@ -1533,7 +1554,7 @@ class KernelBuilder {
 
   std::string load_stmt(int i) {
     const Load &l = loads_[i];
-    std::string arr = l.arr == 0 ? "X" : l.arr == 1 ? "TH" : l.arr == 2 ? "Y" : l.arr == 4 ? "V" : "FA[" + std::to_string(l.slot) + "]";
+    std::string arr = l.arr == 0 ? "X" : l.arr == 1 ? "TH" : l.arr == 2 ? "Y" : l.arr == 4 ? "V" : l.arr == 5 ? "DV" : "FA[" + std::to_string(l.slot) + "]";
     return "const double l" + std::to_string(i) + " = " + guard_or(l.guards) + " ? " + arr + "[i" + std::to_string(l.idxval) + "] : 0.0;\n";
   }
 
@@ -1652,7 +1673,7 @@ class KernelBuilder {
     lazy_load_.assign(loads_.size(), 0);
     if (opt_.lazy_loads > 0 && (opt_.lazy_all_kinds || kind_ == KK_GRAD || kind_ == KK_JTPROD || kind_ == KK_HPROD || kind_ == KK_JPROD) && (int)loads_.size() >= opt_.lazy_min_loads)
       for (size_t i = 0; i < loads_.size(); ++i)
-        if (opt_.lazy_loads >= 2 || loads_[i].arr == 4 || loads_[i].arr == 2) lazy_load_[i] = 1;
+        if (opt_.lazy_loads >= 2 || loads_[i].arr == 4 || loads_[i].arr == 2 || loads_[i].arr == 5) lazy_load_[i] = 1;
     for (auto &o : outs_)
       for (size_t s = 0; s < o.vals.size(); ++s)
         if (o.grad_mode.size() != o.vals.size() || o.grad_mode[s] >= 0) mark_live(o.vals[s], live);   // not the slots merge_scatter folded away
@@ -1977,7 +1998,7 @@ class KernelBuilder {
         lo += std::min(e0, e1); hi += std::max(e0, e1);
       }
       if (!iv.ind.empty()) { lo = 0; hi = g_.ext[0] * g_.ext[1] * g_.ext[2] - 1; }
-      int akey = l.arr == 3 ? 100 + l.slot : l.arr;   // 0 x, 1 theta, 2 y, 4 v, 100+ item columns
+      int akey = l.arr == 3 ? 100 + l.slot : l.arr;   // 0 x, 1 theta, 2 y, 4 v, 5 dv, 100+ item columns
       ranges_[akey].emplace_back(lo, hi);
       // what a sharded handle needs to know: can this kernel touch a halo entry of x (or of a variable-space v)?
       const bool var_space_v = l.arr == 4 && (kind_ == KK_JPROD || kind_ == KK_HPROD);
@@ -2024,16 +2045,18 @@ class KernelBuilder {
     kd.tables_in_memory = !tables_fit_arguments(ipv_.size(), dpv_.size(), fav_.size(), iav_.size());
     if (as_body) {
       os << "__device__ __forceinline__ " << (kind_ == KK_OBJ ? "double " : "void ") << name_ << "_body(const double* __restrict__ X, const double* __restrict__ TH, "
-         << "const double* __restrict__ Y, const double* __restrict__ V, double* __restrict__ OUT, const double w_, double* __restrict__ AUX,\n"
+         << "const double* __restrict__ Y, const double* __restrict__ V, " << (kkt() ? "const double* __restrict__ DV, " : "") << "double* __restrict__ OUT, const double w_, double* __restrict__ AUX,\n"
          << "    const long long* ip_, const double* dp_, const double* const* FA, const long long* const* IA, double* lds_blk, double* lds4,\n"
          << "    const long long BX_, const long long BY_, const long long BZ_, const long long GX_, const long long GY_, const long long GZ_) {\n";
       os << "  const struct { const long long* ip; const double* dp; double w; } A = {ip_, dp_, w_};\n";
       os << "  (void)X; (void)TH; (void)Y; (void)V; (void)FA; (void)IA; (void)A; (void)AUX; (void)lds_blk; (void)lds4; (void)BY_; (void)BZ_; (void)GX_; (void)GY_; (void)GZ_;\n";
+      if (kkt()) os << "  (void)DV;\n";
       kd.tables_in_memory = false;
     } else {
     emit_kernel_head(os, name_, kd.tables_in_memory, ipv_.size(), dpv_.size(), fav_.size(), iav_.size(), opt_.min_waves);
     os << "  const double* __restrict__ X = A.x; const double* __restrict__ TH = A.th; const double* __restrict__ Y = A.y;\n";
     os << "  const double* __restrict__ V = A.v; (void)V;\n";
+    if (kkt()) os << "  const double* __restrict__ DV = A.p6; (void)DV;\n";   // the dual direction rides on the head's last word
     os << "  double* __restrict__ OUT = A.out; double* __restrict__ AUX = A.aux; (void)AUX;\n";
     os << "  const double* const* FA = A.fa; const long long* const* IA = A.ia;\n";
     os << "  (void)X; (void)TH; (void)Y; (void)FA; (void)IA;\n";
@@ -2588,7 +2611,8 @@ static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"
 static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", ""};     // param_kinds = 4: the explicit blocks in COO
 static const char *const kname_lag[] = {"cons", "", "", "obj", "", "", "lagrad", ""};   // param_kinds = 5: the residual program (plain model)
 static const char *const kname_scaled[] = {"cons_scaled", "jac_scaled", "", "", "", "rowmax", "", ""};   // scaled_kinds = 1: the scaled program (plain model)
-static const char *const *kind_names(const Options &o) { return o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_kkt[] = {"", "", "", "", "", "kkty", "", "kktx"};   // kkt_kinds = 1: the KKT operator (plain model)
+static const char *const *kind_names(const Options &o) { return o.kkt_kinds ? kname_kkt : o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2618,6 +2642,7 @@ struct Launch {
   int sh_lds = 0;
   bool any_remap = false;
   size_t run = 1;                              // leading bodies whose workgroups are interleaved (Options::jac_split)
+  bool dv = false;                             // the KKT operator: its bodies take the dual direction (the head's p6) behind v
 };
 
 // where a Launch's tables start in the tables of the kernel that dispatches to its bodies, and the index of its workgroup ->
@@ -2710,7 +2735,7 @@ static std::string dispatch_code(const Launch &E, const Place &at, const std::st
   auto ipx = [&](size_t i) { return "A.ip[" + std::to_string(ipb + i) + "]"; };
   auto call = [&](size_t j, const std::string &ind) {
     std::ostringstream s;
-    s << ind << (is_obj ? "acc += " : "") << E.bodies[j].d->name << "_body(A.x, A.th, A.y, A.v, " << out(j) << ", A.w, " << aux(j) << ", A.ip + " << (ipb + E.oip[j])
+    s << ind << (is_obj ? "acc += " : "") << E.bodies[j].d->name << "_body(A.x, A.th, A.y, A.v, " << (E.dv ? "A.p6, " : "") << out(j) << ", A.w, " << aux(j) << ", A.ip + " << (ipb + E.oip[j])
       << ", A.dp + " << (at.dp + E.odp[j]) << ", A.fa + " << (at.fa + E.ofa[j]) << ", A.ia + " << (at.ia + E.oia[j])
       << ", lds_blk, lds4, lb % gx, (lb / gx) % gy, lb / (gx * gy), gx, gy, gz);\n";
     return s.str();
@@ -2825,7 +2850,7 @@ static void emit_kinds(Emitter &E) {
     for (size_t k = 0; k < E.descs.size(); ++k) if (E.descs[k].kind == kind) ks.push_back(k);
     if (ks.empty()) continue;
     const int ktile = E.descs[ks[0]].block;   // one workgroup size per kind (kind_options)
-    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS || (opt.param_kinds == 5 && kind == KK_JTPROD));
+    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS || (opt.param_kinds == 5 && kind == KK_JTPROD) || (opt.kkt_kinds && (kind == KK_JPROD || kind == KK_HPROD)));
     const bool unfused = !opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2);   // fuse_groups = 2: experiments (one launch of per-template bodies)
     if (kind != KK_OBJ && (unfused || (ks.size() == 1 && !in_a_phase))) {
       for (size_t k : ks) { E.ns_begin(ktile); E.src << E.builders[k]->emit(E.descs[k]); E.ns_end(ktile); E.P.kernels.push_back(E.descs[k]); }
@@ -2833,7 +2858,7 @@ static void emit_kinds(Emitter &E) {
     }
     std::stable_sort(ks.begin(), ks.end(), [&](size_t a, size_t b) { return E.descs[a].n_blocks > E.descs[b].n_blocks; });
     Launch &L = E.emitted[kind];
-    L.kind = kind; L.tile = ktile;
+    L.kind = kind; L.tile = ktile; L.dv = opt.kkt_kinds != 0;
     for (size_t k : ks) L.bodies.push_back(Body{E.builders[k].get(), &E.descs[k], "A.out", "A.aux", E.kopts[k].xcd_remap != 0});
     if (!emit_launch(E, L, std::string("iem_") + kind_names(opt)[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
     if (kind == KK_OBJ) E.P.n_partials = L.F.grid[0];
@@ -2854,7 +2879,11 @@ static void emit_phases(Emitter &E) {
   std::ostringstream &src = E.src;
   struct Member { int kind; const char *out, *aux; };
   struct Phase { int id; const char *name; std::vector<Member> mem; };
-  const std::vector<Phase> phases = E.opt.param_kinds == 5 ? std::vector<Phase>{
+  // The KKT operator (Options::kkt_kinds = 1) has ONE phase too, on the free slot KK_TRIAL: kkty (out = p2) and kktx (out, aux =
+  // its reduction buffer), u = A.v, the dual direction = p6; kktx's follow-ups stay with the runtime.
+  const std::vector<Phase> phases = E.opt.kkt_kinds ? std::vector<Phase>{
+    {KK_TRIAL, "iem_kktprod_all", {{KK_JPROD, "A.p2", "nullptr"}, {KK_HPROD, "A.out", "A.aux"}}},
+  } : E.opt.param_kinds == 5 ? std::vector<Phase>{
     {KK_TRIAL, "iem_residual_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}, {KK_JTPROD, "A.p3", "A.p4"}}},
   } : std::vector<Phase>{
     {KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
@@ -2983,8 +3012,18 @@ Program generate(const Model &m, const Options &opt_in) {
     // the scaled program: rowmax, cons_scaled and jac_scaled over the PLAIN model, through the store path of the model's own
     // kinds; the model's tile on every grid (as the explicit θ blocks), no pair, no phase kernel
     if (opt_in.param_kinds) throw std::runtime_error("scaled_kinds and param_kinds name different programs: set one of them");
+    if (opt_in.kkt_kinds) throw std::runtime_error("scaled_kinds and kkt_kinds name different programs: set one of them");
     Options o = opt_in;
     o.hess_merge = 0; o.phase_kernels = 0; o.pair_kernel = 0;
+    o.big_batch_jac = o.big_batch_hess = 0;
+    return generate_kinds(m, o);
+  }
+  if (opt_in.kkt_kinds) {
+    // the KKT operator: kktx and kkty over the PLAIN model, the model's tile on every grid (no large-grid shape), no pair; its
+    // one phase kernel is the whole operator in one launch
+    if (opt_in.param_kinds) throw std::runtime_error("kkt_kinds and param_kinds name different programs: set one of them");
+    Options o = opt_in;
+    o.hess_merge = 0; o.pair_kernel = 0;
     o.big_batch_jac = o.big_batch_hess = 0;
     return generate_kinds(m, o);
   }
@@ -3009,6 +3048,7 @@ Program generate(const Model &m, const Options &opt_in) {
 
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
+  const bool kkt = opt.kkt_kinds != 0;                                     // kkt: the KKT operator — kktx and kkty of the plain model
   const bool scl = opt.scaled_kinds != 0;                                  // scl: the scaled program — cons_scaled, jac_scaled and rowmax of the plain model
   const bool lag = opt.param_kinds == 5;                                   // lag: the residual program — cons, obj and lagrad of the plain model
   const bool theta = opt.param_kinds != 0 && !lag, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
@@ -3075,6 +3115,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       if (!coord && theta_hi && kind != KK_HPROD) continue;
       if (lag && kind != KK_CONS && kind != KK_OBJ && kind != KK_JTPROD) continue;
       if (scl && kind != KK_CONS && kind != KK_JAC && kind != KK_JPROD) continue;
+      if (kkt && kind != KK_JPROD && kind != KK_HPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3305,7 +3346,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     };
     // (not the adjoint parameter kind, nor the θθ kind: its output must be written without any float atomic — and the atomics would need a
     //  memset launch in front of the kernel where the gather needs its launch behind it)
-    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2) {
+    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2 && !kkt) {
       // at most TWO addends per entry: a + b = b + a, those atomics are already order-independent — and cheaper than
       // a second launch
       std::vector<int64_t> d0;
@@ -3377,6 +3418,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     if (coord || (theta_hi && kind != KK_HPROD)) continue;
     if (lag && kind != KK_JTPROD) continue;
     if (scl) continue;
+    if (kkt && kind != KK_HPROD) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
@@ -3452,7 +3494,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   emit_kinds(E);
   if (!theta) {
     emit_phases(E);
-    if (!lag && !scl) emit_pair(E, m, whole_of, second_half);
+    if (!lag && !scl && !kkt) emit_pair(E, m, whole_of, second_half);
   }
   P.source = src.str();
   P.key = fnv1a64(P.source);

@@ -158,6 +158,17 @@ struct Options {
   // Same groups, folds, halves (jac_split) and store path as the model's own kinds; like the explicit θ blocks the program
   // keeps the model's tile on every grid (no large-grid shape), and it has no pair and no phase kernel.  No atomics.
   int scaled_kinds = 0;
+  // 1: generate() emits the KKT OPERATOR instead — an eighth program over the PLAIN model (param_kinds and scaled_kinds must be
+  // 0; with 0 here the sources, keys and launch plans of every other program are what they were).  u = A.v (nvar), the dual
+  // direction dv = the head's p6 (ncon, read at row indices like y), σ = A.w:
+  //   kktx on KK_HPROD's table slot (nvar out): W u + J' dv, W = σ ∇²f + Σ y_r ∇²c_r — hprod's contributions of every template
+  //        with a second-order slot, and for every constraint template with a first-order slot the first-order sweep seeded
+  //        with dv[row], both through ONE contribute map and ONE deterministic scatter (no float atomic, the two-addend
+  //        shortcut off); an entry no template touches comes out as 0
+  //   kkty on KK_JPROD's (ncon out): J u, the model's own jprod builder and kind options
+  // and KK_TRIAL, free in this program, holds both behind one dispatcher (iem_kktprod_all: kkty's out = p2, kktx's out / aux as
+  // in its own launch); kktx's follow-ups stay with the runtime.  The model's tile on every grid, no pair.
+  int kkt_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };

@@ -238,6 +238,20 @@ function jac_coord_scaled!(m::MI355XModel, x::ROCVector{Float64}, s::ROCVector{F
     check(ccall((:iem_jac_coord_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(s), dptr(vals)))
     return vals
 end
+# The KKT operator in one launch: out_x = W u + J' v, out_y = J u with W = obj_weight ∇²f + Σ y_r ∇²c_r — the product with
+# [W J'; J 0] a matrix-free method (and the residual of a Newton step) needs.  v === nothing means v = 0; outputs may not alias inputs.
+function kktprod_prepare!(m::MI355XModel)
+    n = Ref{Int32}(0)
+    check(ccall((:iem_kktprod_prepare, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.handle, n))
+    return Int(n[])
+end
+function kktprod!(m::MI355XModel, x::ROCVector{Float64}, y::ROCVector{Float64}, u::ROCVector{Float64}, v, out_x::ROCVector{Float64},
+                  out_y::ROCVector{Float64}; obj_weight = 1.0)
+    pv = v === nothing ? Ptr{Float64}(C_NULL) : dptr(v)
+    check(ccall((:iem_kktprod, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), dptr(y), obj_weight, dptr(u), pv, dptr(out_x), dptr(out_y)))
+    return out_x, out_y
+end
 # ... and the three blocks themselves in COO (include/iem.h has the slot order and the triangle convention of ∂²L/∂θ²):
 # Jθ = ∂c/∂θ, Hxθ = ∂²L/∂x∂θ, Hθθ = ∂²L/∂θ² — what a host with its own linear algebra assembles G = [Hxθ; Jθ] from.
 function param_coord_nnz(m::MI355XModel)
@@ -340,6 +354,26 @@ solve!(s::ChainKKTSolver, x::ROCVector{Float64}) =       # in place: the right-h
     (check(ccall((:iem_kkt_solve, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.k, dptr(x), dptr(x))); x)
 solve!(s::ChainKKTSolver, X::ROCMatrix{Float64}) =       # the columns of X in one pass over the factors (iem_kkt_solve_many), in place
     (check(ccall((:iem_kkt_solve_many, LIBIEM), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64), s.k, size(X, 2), dptr(X), stride(X, 2), dptr(X), stride(X, 2))); X)
+# r = rhs − K sol at (x, y, obj_weight) with the solver's own sigma / delta_w / delta_c, matrix-free (iem_kkt_residual); `norm`: a
+# device vector of one entry that receives max |r|, or nothing
+function residual!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{Float64}, rhs::ROCVector{Float64}, sol::ROCVector{Float64},
+                   r::ROCVector{Float64}; obj_weight = 1.0, norm = nothing)
+    pn = norm === nothing ? Ptr{Float64}(C_NULL) : dptr(norm)
+    check(ccall((:iem_kkt_residual, LIBIEM), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), s.delta_w, s.delta_c, dptr(rhs), dptr(sol), dptr(r), pn))
+    return r
+end
+# sol = solve(rhs) and `steps` steps of iterative refinement against that residual, in one asynchronous call
+# (iem_kkt_solve_refined); `norms`: a device vector of steps + 1 entries (max |r| in front of every step and behind the last), or nothing
+function solve_refined!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{Float64}, rhs::ROCVector{Float64}, sol::ROCVector{Float64};
+                        obj_weight = 1.0, steps = 1, norms = nothing)
+    pn = norms === nothing ? Ptr{Float64}(C_NULL) : dptr(norms)
+    check(ccall((:iem_kkt_solve_refined, LIBIEM), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Float64}),
+                s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), s.delta_w, s.delta_c, dptr(rhs), dptr(sol), steps, pn))
+    return sol
+end
 is_inertia(::ChainKKTSolver) = true
 inertia(s::ChainKKTSolver) = (s.inertia[1], s.inertia[3], s.inertia[2])      # (positive, zero, negative)
 

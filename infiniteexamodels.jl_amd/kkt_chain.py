@@ -302,6 +302,42 @@ class ChainLayout:
         return on, self.blk[on] * self.nb + self.loc[on], np.nonzero(self.blk < 0)[0]
 
 
+class MatrixFreeKKT:
+    """The augmented system ``K = [W + diag(sigma) + delta_w·I, Jᵀ; J, −delta_c·I]`` at ``(x, y, obj_weight)`` as an OPERATOR:
+    ``matvec(z)`` is ONE generated launch (``model.kktprod``: ``W·z_x + Jᵀ·z_y`` and ``J·z_x``) plus the diagonal terms — no
+    COO values, no CSR copy of K, nothing to refresh when the point moves except the three references held here.
+    ``residual(rhs, sol)`` is ``rhs − K·sol``.  ``ChainKKT.solve(..., operator=...)`` refines with it in place of the CSR
+    product.  The C-ABI's ``iem_kkt_residual`` / ``iem_kkt_solve_refined`` do the same behind one call."""
+
+    def __init__(self, model, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c: float = 0.0):
+        self.model = model
+        self.nvar, self.ncon = int(model.meta.nvar), int(model.meta.ncon)
+        self.n = self.nvar + self.ncon
+        self.update(x, y, obj_weight, sigma, delta_w, delta_c)
+
+    def update(self, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c: float = 0.0):
+        """Move the operator to another point / regularisation (references are kept, nothing is evaluated)."""
+        self.x, self.y, self.obj_weight = x, y, float(obj_weight)
+        self.sigma, self.delta_w, self.delta_c = sigma, float(delta_w), float(delta_c)
+        return self
+
+    def matvec(self, z):
+        """``K·z`` for a tensor of length ``nvar + ncon`` (a new tensor; ``z`` is not written)."""
+        n = self.nvar
+        zx, zy = z[:n], z[n:]
+        out = z.new_empty(self.n)
+        self.model.kktprod(self.x, self.y, zx, zy if self.ncon else None, obj_weight=self.obj_weight, out_x=out[:n], out_y=out[n:])
+        d = self.delta_w if self.sigma is None else self.sigma + self.delta_w
+        out[:n] += d * zx
+        if self.ncon:
+            out[n:] -= self.delta_c * zy
+        return out
+
+    def residual(self, rhs, sol):
+        """``rhs − K·sol``"""
+        return rhs - self.matvec(sol)
+
+
 class ChainKKT:
     """Factor / solve the augmented system assembled by a :class:`kkt.KKTSystem` with the chain solver."""
 
@@ -377,33 +413,37 @@ class ChainKKT:
         n = self.layout.nvar + self.layout.ncon
         return n - neg, neg, int(info[1])
 
-    def solve(self, rhs, refine=1, rtol: float = 1e-9):
+    def solve(self, rhs, refine=1, rtol: float = 1e-9, operator=None):
         """``K x = rhs`` (device tensor of length ``nvar + ncon``) with the current factors; ``refine`` steps of iterative
         refinement against the CSR matrix — or ``refine = "auto"``: up to two steps, each only while the residual exceeds
-        ``rtol * max|rhs|`` (one product with the CSR matrix decides; a solve is eight times that).
+        ``rtol * max|rhs|`` (one product with the CSR matrix decides; a solve is eight times that).  ``operator`` (a
+        :class:`MatrixFreeKKT` at the point and regularisation the factors were assembled at): the residuals come from its
+        ``matvec`` — one generated launch — instead of the CSR product.
 
         ``rhs`` may also be 2-D, ``(nvar + ncon, K)`` with columns of any stride: the K columns go through the levels
         together (``iem_kkt_chain_solve_many``: the factors are read once per chunk of columns, not once per column) and
         the result has the same shape.  Refinement is per column — with ``"auto"`` a column stops when ITS residual is
         under ITS bound — and column ``j`` carries the bits ``solve(rhs[:, j])`` gives."""
+        mv = self._matvec if operator is None else operator.matvec
         if rhs.dim() == 2:
-            return self._solve_many(rhs, refine, rtol)
+            return self._solve_many(rhs, refine, rtol, mv)
         x = self._solve_once(rhs)
         if refine == "auto":
             bound = rtol * max(1.0, float(rhs.abs().max().item()))
             for _ in range(2):
-                res = rhs - self._matvec(x)
+                res = rhs - mv(x)
                 if float(res.abs().max().item()) <= bound:
                     break
                 x = x + self._solve_once(res)
             return x
         for _ in range(int(refine)):
-            res = rhs - self._matvec(x)
+            res = rhs - mv(x)
             x = x + self._solve_once(res)
         return x
 
-    def _solve_many(self, rhs, refine, rtol):
+    def _solve_many(self, rhs, refine, rtol, mv=None):
         t = self._torch
+        mv = mv if mv is not None else self._matvec
         K = rhs.shape[1]
         B = rhs.t().contiguous()                       # (K, n): a column per row, contiguous whatever the strides of rhs were
         X = self._solve_once_many(B)
@@ -412,7 +452,7 @@ class ChainKKT:
         for _ in range(2 if refine == "auto" else int(refine)):
             if not live:
                 break
-            res = t.stack([B[j] - self._matvec(X[j]) for j in live])
+            res = t.stack([B[j] - mv(X[j]) for j in live])
             if bounds is not None:
                 keep = [i for i, j in enumerate(live) if float(res[i].abs().max().item()) > bounds[j]]
                 live, res = [live[i] for i in keep], res[keep]
@@ -855,10 +895,19 @@ class HubChainKKT:
         _lib.check(m._L.iem_kkt_chain_solve_lanes(*args, None, 1))
         return r
 
-    def solve(self, rhs, profile: Optional[dict] = None):
+    def solve(self, rhs, profile: Optional[dict] = None, refine: int = 0, operator=None):
+        """``K x = rhs`` through the hubs' factors.  ``refine`` steps of iterative refinement need an ``operator`` (a
+        :class:`MatrixFreeKKT`): this class keeps no matrix to form a residual with.  The default is one pass, as before."""
         t = self._torch
         if rhs.dim() == 2:      # column by column (the hubs' side is matrix-vector work per column)
-            return t.stack([self.solve(rhs[:, j].contiguous(), profile) for j in range(rhs.shape[1])], 1)
+            return t.stack([self.solve(rhs[:, j].contiguous(), profile, refine, operator) for j in range(rhs.shape[1])], 1)
+        if int(refine) > 0:
+            if operator is None:
+                raise ValueError("HubChainKKT.solve: refinement needs operator= (a MatrixFreeKKT); there is no CSR copy of K here")
+            x = self.solve(rhs, profile)
+            for _ in range(int(refine)):
+                x = x + self.solve(rhs - operator.matvec(x), profile)
+            return x
         if self._levels is None:
             self.model._sync_stream()
         import time as _time

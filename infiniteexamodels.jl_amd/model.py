@@ -100,6 +100,7 @@ class ExaModel:
         self._pc_nnz = None      # lengths of the explicit θ blocks (param_coord_nnz), asked once
         self._lag_n = None       # kernels of the residual program (lagrangian_prepare), once it is set up
         self._scl_n = None       # kernels of the scaled program (scaled_prepare), once it is set up
+        self._kkt_n = None       # kernels of the KKT operator (kkt_prepare), once it is set up
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -315,7 +316,7 @@ class ExaModel:
         n = self.lagrangian_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._scl_n or 0)
+        last = int(total.value) - (self._scl_n or 0) - (self._kkt_n or 0)
         return self._kernel_infos(last - n, last)
 
     def lagrangian_grad(self, x, y, obj_weight: float = 1.0, out=None):
@@ -363,11 +364,50 @@ class ExaModel:
 
     def scaled_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the scaled program (kinds jprod / cons / jac, names
-        ``iem_rowmax*`` / ``iem_cons_scaled*`` / ``iem_jac_scaled*``): always the LAST kernels ``iem_kernel_info`` lists."""
+        ``iem_rowmax*`` / ``iem_cons_scaled*`` / ``iem_jac_scaled*``): always the LAST kernels ``iem_kernel_info`` lists in
+        front of the KKT operator's (``kkt_kernels``), where that exists."""
         n = self.scaled_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        last = int(total.value) - (self._kkt_n or 0)
+        return self._kernel_infos(last - n, last)
+
+    # ---- the KKT operator in one launch: W·u + Jᵀ·v and J·u ----
+    def kkt_prepare(self) -> int:
+        """Set up the program of ``kktprod`` now (``iem_kktprod_prepare``: otherwise its first call does — synchronously, and
+        not inside a stream capture); the number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_kktprod_prepare(self._h, C.byref(n)))
+        self._kkt_n = int(n.value)
+        return self._kkt_n
+
+    def kkt_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of the KKT operator (kinds hprod / jprod, names ``iem_kktx*`` /
+        ``iem_kkty*``, and the one-launch kernel ``iem_kktprod_all``, kind trial): always the LAST kernels ``iem_kernel_info``
+        lists."""
+        n = self.kkt_prepare()
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
         return self._kernel_infos(int(total.value) - n, int(total.value))
+
+    def kktprod(self, x, y, u, v=None, obj_weight: float = 1.0, out_x=None, out_y=None):
+        """``(W·u + J(x)ᵀ·v, J(x)·u)`` with ``W = obj_weight·∇²f(x) + Σ y_r·∇²c_r(x)`` from ONE launch (``iem_kktprod``): the
+        product with ``[W, Jᵀ; J, 0]`` that a Newton step's residual needs — atomic-free and bitwise reproducible, ``out_y``
+        bitwise ``jprod(x, u)``.  ``v = None`` means ``v = 0``; ``y`` may be ``None`` on a model without constraints.  The
+        outputs may not overlap an input."""
+        self._chk(x, self.meta.nvar, "x"); self._chk(u, self.meta.nvar, "u")
+        if y is not None or self.meta.ncon:
+            self._chk(y, self.meta.ncon, "y")
+        if v is not None:
+            self._chk(v, self.meta.ncon, "v")
+        out_x = out_x if out_x is not None else self._new(self.meta.nvar)
+        out_y = out_y if out_y is not None else self._new(self.meta.ncon)
+        self._chk(out_x, self.meta.nvar, "out_x"); self._chk(out_y, self.meta.ncon, "out_y")
+        self._sync_stream()
+        if self._kkt_n is None:
+            self.kkt_prepare()
+        _lib.check(self._L.iem_kktprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(u), _ptr(v), _ptr(out_x), _ptr(out_y)))
+        return out_x, out_y
 
     def jac_row_maxabs(self, x, out=None):
         """Per constraint row the largest ``|∂c_r/∂x_j|`` over the entries ``jac_coord`` writes for it (ncon; repeated
@@ -566,7 +606,7 @@ class ExaModel:
         n = self.param_coord_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0)
+        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0) - (self._kkt_n or 0)
         return self._kernel_infos(last - n, last)
 
     def param_prepare(self) -> int:
