@@ -104,6 +104,25 @@ int main(int argc, char **argv) {
     IEM(iem_synchronize(m));
     printf("kkt_inertia %lld %lld %lld\n", (long long)inertia[0], (long long)inertia[1], (long long)inertia[2]);
     if (report("kkt_solution", rhs, meta.nvar + meta.ncon)) return 1;
+    /* the same solve with a dense border (first-stage variables: info.ne > 0) kept on the device — mode 1: the inertia goes to a
+     * device array, nothing between assemble and the solution synchronises; a no-op switch for models without a border */
+    iem_kkt_info_t info;
+    IEM(iem_kkt_info(k, &info));
+    if (info.ne > 0 && !info.hubs) {
+      int64_t *d_inertia;
+      HIP(hipMalloc((void **)&d_inertia, 24));
+      HIP(hipMemcpy(rhs, g, nx, hipMemcpyDeviceToDevice));
+      HIP(hipMemcpy((char *)rhs + nx, c, ny, hipMemcpyDeviceToDevice));
+      IEM(iem_kkt_set_border(k, 1));
+      IEM(iem_kkt_assemble(k, hv, jv, NULL, 1e-2, 1e-6));
+      IEM(iem_kkt_factor_async(k, d_inertia));
+      IEM(iem_kkt_solve(k, rhs, rhs));
+      IEM(iem_synchronize(m));
+      HIP(hipMemcpy(inertia, d_inertia, 24, hipMemcpyDeviceToHost));
+      printf("kkt_inertia_device %lld %lld %lld\n", (long long)inertia[0], (long long)inertia[1], (long long)inertia[2]);
+      if (report("kkt_solution_device", rhs, meta.nvar + meta.ncon)) return 1;
+      HIP(hipFree(d_inertia));
+    }
     IEM(iem_kkt_destroy(k));
   } else {
     printf("kkt_refused %s\n", iem_last_error());

@@ -499,6 +499,31 @@ int iem_kkt_chain_solve_lanes(iem_model *m, int64_t S, int64_t lane_len, int nb,
 int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, int ne, int nc, const double *d_Dinv, const double *d_Bt,
                              const double *d_BR, const int32_t *d_rows, const int32_t *d_cols, const double *d_Z, double *d_r, double *d_z,
                              double *d_rBp, const double *d_xB, int nrhs, int phase);
+/* The dense border on the device (csrc/iem_kkt_border_device.h; the low-level pair behind iem_kkt_set_border(k, 1)).
+ * iem_kkt_border_factor: Gs = G - sum_k Gp[k] (G: ne x ne, Gp: S x ne x ne as iem_kkt_chain_factor leaves it; summed by the
+ * deterministic two-launch column sum) and, in ONE workgroup with Gs in LDS (8 (ne (ne + 1) + 2 ne + 16) + 4 (2 ne + 16) bytes:
+ * 135 360 at ne = 128), an unblocked Bunch-Kaufman LDL' with partial pivoting (alpha = (1 + sqrt 17) / 8, ties to the lowest
+ * index): P Gs P' = L D L'.  d_F (ne x ne, row-major): unit L strictly below the diagonal, D on it, the off-diagonal of a 2 x 2
+ * pivot in the subdiagonal place, zeros above.  d_piv (ne int32) holds the PERMUTATION and the block structure, not LAPACK's
+ * interchange sequence: with p the row of Gs that sits in row i of the factor, d_piv[i] = p for a 1 x 1 pivot, -(p + 1) for the
+ * first and -(p + 1) - ne for the second row of a 2 x 2 pivot.  d_info[0] += negative pivots, d_info[1] += doubtful ones (the
+ * counters iem_kkt_chain_factor fills; the caller zeroes them otherwise): with scale = max |Gs_ij|, a step whose diagonal entry
+ * and column maximum are both <= rel scale (or scale == 0) is doubtful — counted, its pivot replaced by copysign(rel scale, d),
+ * its column zeroed and not eliminated (do not trust the factors); a 1 x 1 pivot counts by its sign, a 2 x 2 pivot one negative
+ * when its determinant is negative and by the sign of its diagonal otherwise.  n_border: the unknowns in front of the padding's
+ * unit diagonal (positive, never counted).
+ * iem_kkt_border_solve: xB_u = Gs^-1 (rB_u - sum_k rBp_u[k]) for nrhs columns, one workgroup per column: d_rBp nrhs x S x ne (what
+ * phase 0 of iem_kkt_chain_solve / _solve_many writes), d_rB nrhs x ne (entries from n_border on are taken as zero), d_xB nrhs x ne
+ * (what phase 1 reads).  Fixed summation order, no atomics: bitwise reproducible.
+ * ne: a multiple of 4 in 4..128, 0 <= n_border <= ne, S >= 1, nrhs >= 1 — anything else is IEM_E_ARG before any device work.
+ * Both are asynchronous on the handle's stream and capturable once the code object is loaded and the workspace of the column
+ * sums (owned by the handle, grown on demand) is large enough: after a first call with the same sizes. */
+int iem_kkt_border_factor(iem_model *m, int64_t S, int ne, int n_border, const double *d_G, const double *d_Gp, double *d_F, int32_t *d_piv,
+                          int64_t *d_info, double rel);
+int iem_kkt_border_solve(iem_model *m, int64_t S, int ne, int n_border, int nrhs, const double *d_F, const int32_t *d_piv, const double *d_rBp,
+                         const double *d_rB, double *d_xB);
+/* HIP source of those kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_kkt_border_source(char **out_src, uint64_t *out_key);
 /* The same solver as ONE object — what a host without the Python layer (a Julia MadNLP linear-solver wrapper) binds.
  * iem_kkt_create analyses the model once on the host: grouping of the unknowns (variable u, then the multiplier of row
  * u - nvar) into chain blocks + border from the slab table and the Jacobian / Hessian structure, the narrow coupling, and a
@@ -536,6 +561,19 @@ int iem_kkt_analyse_blob(const void *blob, size_t nbytes, int group, iem_kkt_inf
                          int32_t **out_cols, int64_t **out_dest, uint32_t **out_seg, uint32_t **out_perm, int64_t *out_n_dest, int64_t *out_n_perm);
 int iem_kkt_assemble(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, double delta_w, double delta_c);
 int iem_kkt_factor(iem_kkt *k, int64_t *out_inertia);
+/* Where the dense border (info.ne > 0, no hubs) is factorised and solved.  mode 0 (the default): on the host — iem_kkt_factor
+ * brings Gs home for its inertia, every solve synchronises twice and eliminates Gs again.  mode 1: on the device
+ * (iem_kkt_border_factor / _solve above): iem_kkt_factor synchronises only to read the counters, and iem_kkt_solve,
+ * iem_kkt_solve_many (one border launch per chunk, a workgroup per column; column u still carries the bits of iem_kkt_solve in
+ * the same mode) and iem_kkt_solve_refined contain no synchronisation and no copy to or from the host: graph-capturable after
+ * their first call.  The inertia is that of a Bunch-Kaufman LDL' in mode 1 (2 x 2 pivots: an indefinite border with a zero
+ * diagonal is counted, not reported doubtful).  Switching modes invalidates the factorisation.  A no-op without a dense border
+ * (ne == 0, hub mode). */
+int iem_kkt_set_border(iem_kkt *k, int mode);
+/* iem_kkt_factor without the read-back: {positive, negative, doubtful} into d_inertia (3 int64 on the device) by a one-thread
+ * finishing kernel.  No synchronisation; capturable after iem_kkt_set_border(k, 1) (or, without a border, after a first call).
+ * IEM_E_ARG in hub mode (its factorisation works on the host between launches) and for ne > 0 in mode 0. */
+int iem_kkt_factor_async(iem_kkt *k, int64_t *d_inertia);
 int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol);
 /* K sol_u = rhs_u for nrhs columns with ONE pass over the factors per chunk of columns (sensitivity matrices, several refinement
  * residuals, predictor + corrector): column u is d_rhs + u ld_rhs / d_sol + u ld_sol, nvar + ncon doubles; ld >= nvar + ncon, the
@@ -543,8 +581,8 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol);
  * IEM_E_ARG — judged on the whole extents [d, d + (nrhs - 1) ld + n), so columns of d_sol interleaved with those of d_rhs
  * (disjoint, but inside each other's extent) are refused as well.  Any nrhs: the columns are processed in chunks (see iem_kkt_chain_solve_many) through a workspace of ONE chunk that
  * the first call allocates and iem_kkt_destroy frees — memory does not grow with nrhs.  Column u carries the bits
- * iem_kkt_solve gives for it.  The border system is solved on the host once per column, with one read-back and one upload per
- * chunk.  Hub mode (info.hubs != 0) is accepted as a loop of single solves: the hubs' side stays matrix-vector work per column
+ * iem_kkt_solve gives for it.  In mode 0 the border system is solved on the host once per column, with one read-back and one upload per
+ * chunk; in mode 1 (iem_kkt_set_border) on the device, one launch per chunk.  Hub mode (info.hubs != 0) is accepted as a loop of single solves: the hubs' side stays matrix-vector work per column
  * (sharing its factors across columns — GEMM for GEMV — is not done). */
 int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol);
 
@@ -565,7 +603,7 @@ int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double ob
  * iem_kkt_residual and a vector add give.  d_norms (steps + 1 doubles or NULL): d_norms[i] = max |r| in front of step i, the
  * last entry the one behind the last step (with d_norms == NULL that last residual is not computed).  steps = 0 is iem_kkt_solve
  * (plus one norm).  No host read-back of a norm and no early exit: as asynchronous and capturable as iem_kkt_solve itself is for
- * the object (a border is solved on the host).  d_sol may not overlap d_rhs.  Workspace: 3 (nvar + ncon) doubles, as above. */
+ * the object (a dense border is solved on the host in mode 0 only: iem_kkt_set_border).  d_sol may not overlap d_rhs.  Workspace: 3 (nvar + ncon) doubles, as above. */
 int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w,
                           double delta_c, const double *d_rhs, double *d_sol, int steps, double *d_norms /* steps + 1 or NULL */);
 /* HIP source of the two finishing kernels and its cache key — for offline builds (no device needed; malloc'ed) */

@@ -44,6 +44,9 @@ static const char *kKktManySource =   // the multi-column solve kernels, behind 
 static const char *kKktResidualSource =   // the finishing kernels of iem_kkt_residual / iem_kkt_solve_refined: a code object of their own
 #include "iem_kkt_residual_device_h.inc"
     ;
+static const char *kKktBorderSource =     // the dense border on the device (kkt_border_ldl / kkt_border_solve): a code object of its own
+#include "iem_kkt_border_device_h.inc"
+    ;
 
 namespace {
 
@@ -267,6 +270,12 @@ struct iem_model {
   double *d_kkt_zero = nullptr;
   hipModule_t kres_mod = nullptr;
   hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
+  // the dense border on the device (csrc/iem_kkt_border_device.h; loaded by the first call that needs it).  `kb_part`: the column
+  // sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
+  hipModule_t kb_mod = nullptr;
+  hipFunction_t kb_ldl = nullptr, kb_solve = nullptr, kb_colsum = nullptr, kb_inertia = nullptr;
+  double *kb_part = nullptr;
+  int64_t kb_part_n = 0;
   iem::Model pc_view;
   bool pc_have_view = false;
   double *d_pc_spare[2] = {nullptr, nullptr};
@@ -1277,6 +1286,8 @@ int iem_destroy(iem_model *m) {
   free_program(m->kkt.code);
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
   if (m->kres_mod) hipModuleUnload(m->kres_mod);
+  if (m->kb_mod) hipModuleUnload(m->kb_mod);
+  if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
   free_program(m->code);
@@ -2855,6 +2866,99 @@ int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, 
   return IEM_OK;
 }
 
+/* ---- the dense border on the device (csrc/iem_kkt_border_device.h) ------------------------------------------------------------ */
+namespace {
+std::string kkt_border_source() {
+  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktBorderSource;
+}
+// the code object: the synchronous part of the first call
+int kkt_border_setup(iem_model *m) {
+  if (m->kb_ldl) return IEM_OK;
+  int rc = load_source(m, kkt_border_source(), &m->kb_mod);
+  if (rc) return rc;
+  HIP_TRY(hipModuleGetFunction(&m->kb_solve, m->kb_mod, "kkt_border_solve"));
+  HIP_TRY(hipModuleGetFunction(&m->kb_colsum, m->kb_mod, "kkt_border_colsum"));
+  HIP_TRY(hipModuleGetFunction(&m->kb_inertia, m->kb_mod, "kkt_border_inertia"));
+  HIP_TRY(hipModuleGetFunction(&m->kb_ldl, m->kb_mod, "kkt_border_ldl"));
+  return IEM_OK;
+}
+bool kkt_border_shape_ok(int64_t S, int ne, int n_border) { return S >= 1 && ne >= 4 && ne <= 128 && ne % 4 == 0 && n_border >= 0 && n_border <= ne; }
+// LDS of kkt_border_ldl / kkt_border_solve (the layout at the head of csrc/iem_kkt_border_device.h)
+unsigned kkt_border_lds(int ne) { return (unsigned)(8 * (ne * (ne + 1) + 2 * ne + 16) + 4 * (2 * ne + 16)); }
+unsigned kkt_border_wg(int ne) { return ne <= 32 ? 64u : 256u; }
+int kkt_launch_lds(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, unsigned block, unsigned lds) {
+  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, lds, m->stream, nullptr, cfg));
+  return IEM_OK;
+}
+// kkt_colsum's pair of launches for nr matrices of rows x w (matrix u at in + u in_ld) through `fn` (kkt_colsum_m of a chain module
+// or its twin kkt_border_colsum): partial rows at part + u part_ld, the sums at part + u part_ld + res_off
+int kkt_border_sums(iem_model *m, hipFunction_t fn, const double *in, long long in_ld, int64_t rows, int64_t w, int nr, double *part, long long part_ld, long long res_off) {
+  struct Sum { const double *in; double *out; long long rows, w, rows_per_wg, in_ld, out_ld, wgs; };
+  const int64_t ncc = (w + 255) / 256, per = (rows + 511) / 512, nrc = (rows + per - 1) / per;
+  Sum A{in, part, (long long)rows, (long long)w, (long long)per, in_ld, part_ld, (long long)(nrc * ncc)};
+  int rc = kkt_launch_raw(m, fn, &A, sizeof A, nr * nrc * ncc, 256);
+  if (rc) return rc;
+  Sum B{part, part + res_off, (long long)nrc, (long long)w, (long long)nrc, part_ld, part_ld, (long long)ncc};
+  return kkt_launch_raw(m, fn, &B, sizeof B, nr * ncc, 256);
+}
+// Gs = G - sum_k Gp[k] factorised by ONE workgroup; `part`: 513 ne^2 doubles (res_off = 512 ne^2) or what the caller states
+int kkt_border_factor_run(iem_model *m, hipFunction_t colsum, int64_t S, int ne, int n_border, const double *d_G, const double *d_Gp, double *d_F, int32_t *d_piv,
+                          int64_t *d_info, double rel, double *part, long long res_off) {
+  const int64_t w = (int64_t)ne * ne;
+  int rc = kkt_border_sums(m, colsum, d_Gp, w * S, S, w, 1, part, 0, res_off);
+  if (rc) return rc;
+  struct { const double *G, *gsum; double *F; int *piv; long long *info; int ne, n_border; double rel; } A{d_G, part + res_off, d_F, d_piv, (long long *)d_info, ne, n_border, rel};
+  return kkt_launch_lds(m, m->kb_ldl, &A, sizeof A, 1, kkt_border_wg(ne), kkt_border_lds(ne));
+}
+struct KktBorderSolveArgsH { const double *F; const int *piv; const double *rhs; const long long *src, *dst; const double *sum; double *xB; long long ld_rhs, ld_sum, ld_x; int ne, n_border; };
+int kkt_border_solve_run(iem_model *m, const KktBorderSolveArgsH &a, int nrhs) {
+  KktBorderSolveArgsH A = a;
+  return kkt_launch_lds(m, m->kb_solve, &A, sizeof A, nrhs, kkt_border_wg(a.ne), kkt_border_lds(a.ne));
+}
+int kkt_border_workspace(iem_model *m, int64_t doubles) {
+  if (m->kb_part_n >= doubles) return IEM_OK;
+  if (m->kb_part) { HIP_TRY(hipStreamSynchronize(m->stream)); hipFree(m->kb_part); m->kb_part = nullptr; m->kb_part_n = 0; }
+  HIP_TRY(hipMalloc((void **)&m->kb_part, (size_t)doubles * 8));
+  m->kb_part_n = doubles;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_kkt_border_source(char **out_src, uint64_t *out_key) {
+  const std::string s = kkt_border_source();
+  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
+  if (out_key) *out_key = iem::fnv1a64(s);
+  return IEM_OK;
+}
+
+int iem_kkt_border_factor(iem_model *m, int64_t S, int ne, int n_border, const double *d_G, const double *d_Gp, double *d_F, int32_t *d_piv, int64_t *d_info,
+                          double rel) {
+  if (!m || !d_G || !d_Gp || !d_F || !d_piv || !d_info) return fail(IEM_E_ARG, "iem_kkt_border_factor: null argument");
+  if (!kkt_border_shape_ok(S, ne, n_border) || !(rel >= 0.0))
+    return fail(IEM_E_ARG, "iem_kkt_border_factor: S >= 1, ne a multiple of 4 in 4..128, 0 <= n_border <= ne, rel >= 0");
+  DevGuard dg_(m->device);
+  int rc = kkt_border_setup(m);
+  if (rc) return rc;
+  const int64_t w = (int64_t)ne * ne, nrc = std::min<int64_t>(S, 512);      // (at most 512 partial rows, then the result)
+  if ((rc = kkt_border_workspace(m, (nrc + 1) * w))) return rc;
+  return kkt_border_factor_run(m, m->kb_colsum, S, ne, n_border, d_G, d_Gp, d_F, d_piv, d_info, rel, m->kb_part, nrc * w);
+}
+
+int iem_kkt_border_solve(iem_model *m, int64_t S, int ne, int n_border, int nrhs, const double *d_F, const int32_t *d_piv, const double *d_rBp, const double *d_rB,
+                         double *d_xB) {
+  if (!m || !d_F || !d_piv || !d_rBp || !d_rB || !d_xB) return fail(IEM_E_ARG, "iem_kkt_border_solve: null argument");
+  if (!kkt_border_shape_ok(S, ne, n_border) || nrhs < 1)
+    return fail(IEM_E_ARG, "iem_kkt_border_solve: S >= 1, ne a multiple of 4 in 4..128, 0 <= n_border <= ne, nrhs >= 1");
+  DevGuard dg_(m->device);
+  int rc = kkt_border_setup(m);
+  if (rc) return rc;
+  const int64_t nrc = std::min<int64_t>(S, 512), wp = (nrc + 1) * ne;
+  if ((rc = kkt_border_workspace(m, (int64_t)nrhs * wp))) return rc;
+  if ((rc = kkt_border_sums(m, m->kb_colsum, d_rBp, (long long)(S * ne), S, ne, nrhs, m->kb_part, (long long)wp, (long long)(nrc * ne)))) return rc;
+  return kkt_border_solve_run(m, KktBorderSolveArgsH{d_F, d_piv, d_rB, nullptr, nullptr, m->kb_part + nrc * ne, d_xB, (long long)ne, (long long)wp, (long long)ne, ne, n_border}, nrhs);
+}
+
 /* ---- the chain KKT solver as ONE object behind the C-ABI (what a host without the Python layer binds) ---------------------- */
 struct iem_kkt {
   iem_model *m = nullptr;
@@ -2868,6 +2972,9 @@ struct iem_kkt {
   double *m_r = nullptr, *m_z = nullptr, *m_rBp = nullptr, *m_xB = nullptr, *m_part = nullptr;      // iem_kkt_solve_many: ONE chunk of columns, allocated by its first call
   std::vector<double> Gs;        // the border's Schur complement (host), set by iem_kkt_factor
   double *w_ref = nullptr;       // iem_kkt_residual / iem_kkt_solve_refined: p, r, dsol (3 (nvar + ncon) doubles), allocated by the first call
+  int border_mode = 0;           // iem_kkt_set_border: 0 the border on the host, 1 on the device (d_F, d_piv: its factors)
+  double *d_F = nullptr;
+  int32_t *d_piv = nullptr;
   bool factored = false;
   struct KktHub *hub = nullptr;  // hub mode (L.hubs): the span-sparse border's buffers and the library handle of its GEMMs
 };
@@ -3280,6 +3387,8 @@ int iem_kkt_create(iem_model *m, int group, iem_kkt **out) {
     HIP_TRY(hipMalloc((void **)&k->d_xB, (size_t)std::max<int64_t>(ne, 1) * 8));
     HIP_TRY(hipMalloc((void **)&k->d_part, (size_t)(513 * std::max<int64_t>(ne * ne, 1)) * 8));      // kkt_colsum_host: 512 partial rows + the result
     HIP_TRY(hipMalloc((void **)&k->d_info, 32));
+    HIP_TRY(hipMalloc((void **)&k->d_F, (size_t)std::max<int64_t>(ne * ne, 1) * 8));
+    HIP_TRY(hipMalloc((void **)&k->d_piv, (size_t)std::max<int64_t>(ne, 1) * 4));
     if (L.hubs && (rc = hub_alloc(k.get()))) return rc;
   } catch (const std::exception &e) {
     return fail(IEM_E_ARG, e.what());
@@ -3293,7 +3402,7 @@ int iem_kkt_destroy(iem_kkt *k) {
   DevGuard dg_(k->m->device);
   hub_free(k);
   for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_r, (void *)k->d_z, (void *)k->d_rBp, (void *)k->d_xB, (void *)k->d_part,
-                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref,
+                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref, (void *)k->d_F, (void *)k->d_piv,
                   (void *)k->d_rows, (void *)k->d_cols, (void *)k->d_dest, (void *)k->d_on, (void *)k->d_pos, (void *)k->d_border, (void *)k->d_bloc, (void *)k->d_info,
                   (void *)k->d_seg, (void *)k->d_perm})
     if (p) hipFree(p);
@@ -3331,19 +3440,59 @@ int iem_kkt_assemble(iem_kkt *k, const double *d_hess, const double *d_jac, cons
   return kkt_launch_raw(m, k->km->gather, &A, sizeof A, (k->n_dest + 255) / 256, 256);
 }
 
+namespace {
+// the launches of a factorisation: the chain's levels and — device border — the column sum of Gp and kkt_border_ldl behind them
+int kkt_factor_launch(iem_kkt *k) {
+  iem_model *m = k->m;
+  const iem::KktLayout &L = k->L;
+  const bool chained = L.reach > 0;
+  double *D = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB(), *E = k->d_flat + L.oE();
+  int rc = iem_kkt_chain_factor(m, L.S, L.nb, L.ne, L.nc, D, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
+                                chained ? k->d_cols : nullptr, E, k->d_Z, k->d_Gp, (int64_t *)k->d_info, 1e-30);
+  if (rc || L.ne <= 0 || k->border_mode != 1) return rc;
+  return kkt_border_factor_run(m, k->km->colsum_m, L.S, L.ne, (int)L.n_border, k->d_flat + L.oG(), k->d_Gp, k->d_F, k->d_piv, (int64_t *)k->d_info, 1e-14, k->d_part,
+                               512LL * L.ne * L.ne);
+}
+}  // namespace
+
+int iem_kkt_set_border(iem_kkt *k, int mode) {
+  if (!k || (mode != 0 && mode != 1)) return fail(IEM_E_ARG, "iem_kkt_set_border: mode 0 (host) or 1 (device)");
+  if (k->L.hubs || k->L.ne <= 0 || mode == k->border_mode) return IEM_OK;
+  if (mode == 1) {
+    DevGuard dg_(k->m->device);
+    int rc = kkt_border_setup(k->m);
+    if (rc) return rc;
+  }
+  k->border_mode = mode;
+  k->factored = false;
+  return IEM_OK;
+}
+
+int iem_kkt_factor_async(iem_kkt *k, int64_t *d_inertia) {
+  if (!k || !d_inertia) return fail(IEM_E_ARG, "null argument");
+  const iem::KktLayout &L = k->L;
+  if (L.hubs) return fail(IEM_E_ARG, "iem_kkt_factor_async: hub mode factorises with host steps between its launches (iem_kkt_factor)");
+  if (L.ne > 0 && k->border_mode != 1) return fail(IEM_E_ARG, "iem_kkt_factor_async: the border is factorised on the host in mode 0 (iem_kkt_set_border(k, 1) first)");
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc = kkt_border_setup(m);
+  if (rc || (rc = kkt_factor_launch(k))) return rc;
+  struct { const long long *info; long long *out; long long n; } A{k->d_info, (long long *)d_inertia, (long long)(L.nvar + L.ncon)};
+  if ((rc = kkt_launch_raw(m, m->kb_inertia, &A, sizeof A, 1, 64))) return rc;
+  k->factored = true;
+  return IEM_OK;
+}
+
 int iem_kkt_factor(iem_kkt *k, int64_t *out_inertia) {
   if (!k) return fail(IEM_E_ARG, "null argument");
   iem_model *m = k->m;
   DevGuard dg_(m->device);
   const iem::KktLayout &L = k->L;
   if (L.hubs) return hub_factor(k, out_inertia);
-  const bool chained = L.reach > 0;
-  double *D = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB(), *E = k->d_flat + L.oE();
-  int rc = iem_kkt_chain_factor(m, L.S, L.nb, L.ne, L.nc, D, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
-                                chained ? k->d_cols : nullptr, E, k->d_Z, k->d_Gp, (int64_t *)k->d_info, 1e-30);
+  int rc = kkt_factor_launch(k);
   if (rc) return rc;
   int64_t neg = 0, doubtful = 0;
-  if (L.ne > 0) {      // the border: G - sum_k Gp[k] on the host (ne <= 64)
+  if (L.ne > 0 && k->border_mode == 0) {      // the border: G - sum_k Gp[k] on the host (ne <= 64)
     std::vector<double> gp, G((size_t)(L.ne * L.ne));
     if ((rc = kkt_colsum_host(k, k->d_Gp, L.S, (int64_t)L.ne * L.ne, gp))) return rc;
     HIP_TRY(hipMemcpy(G.data(), k->d_flat + L.oG(), G.size() * 8, hipMemcpyDeviceToHost));
@@ -3392,7 +3541,11 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
   if ((rc = iem_kkt_chain_solve(m, L.S, L.nb, L.ne, L.nc, Dinv, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
                                 chained ? k->d_cols : nullptr, k->d_Z, k->d_r, chained ? k->d_z : nullptr, k->d_rBp, nullptr, 0)))
     return rc;
-  if (L.ne > 0) {      // border system on the host: Gs xB = rB - sum_k rBp[k]
+  if (L.ne > 0 && k->border_mode == 1) {      // border system on the device: the column sum of rBp, then ONE workgroup
+    if ((rc = kkt_border_sums(m, k->km->colsum_m, k->d_rBp, 0, L.S, L.ne, 1, k->d_part, 0, 512LL * L.ne))) return rc;
+    if ((rc = kkt_border_solve_run(m, KktBorderSolveArgsH{k->d_F, k->d_piv, d_rhs, k->d_border, k->d_bloc, k->d_part + 512 * L.ne, k->d_xB, 0, 0, 0, L.ne, (int)L.n_border}, 1)))
+      return rc;
+  } else if (L.ne > 0) {      // border system on the host: Gs xB = rB - sum_k rBp[k]
     std::vector<double> rbp, rB((size_t)L.ne, 0.0);
     if ((rc = kkt_colsum_host(k, k->d_rBp, L.S, L.ne, rbp))) return rc;
     std::vector<double> rhs_b((size_t)L.n_border);
@@ -3533,7 +3686,12 @@ int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs
     HIP_TRY(hipMemsetAsync(k->m_r, 0, (size_t)(nr * pl) * 8, m->stream));
     if ((rc = move(Mv{k->m_r, rhs, k->d_pos, k->d_on, 0, (long long)pl, (long long)ld_rhs, nr}, k->n_on))) return rc;
     if ((rc = chain(nr, 0))) return rc;
-    if (ne > 0) {      // the border systems on the host: Gs xB = rB - sum_k rBp[k] per column — ONE read-back and ONE upload per chunk
+    if (ne > 0 && k->border_mode == 1) {      // the border systems on the device: ONE launch, a workgroup per column
+      if ((rc = kkt_border_sums(m, k->km->colsum_m, k->m_rBp, (long long)(L.S * ne), L.S, ne, nr, k->m_part, (long long)wp, 512LL * ne))) return rc;
+      if ((rc = kkt_border_solve_run(m, KktBorderSolveArgsH{k->d_F, k->d_piv, rhs, k->d_border, k->d_bloc, k->m_part + 512 * ne, k->m_xB, (long long)ld_rhs, (long long)wp,
+                                                            (long long)ne, (int)ne, (int)L.n_border}, nr)))
+        return rc;
+    } else if (ne > 0) {      // the border systems on the host: Gs xB = rB - sum_k rBp[k] per column — ONE read-back and ONE upload per chunk
       const int64_t ncc = (ne + 255) / 256, per = (L.S + 511) / 512, nrc = (L.S + per - 1) / per;      // kkt_colsum_host's two launches, for every column
       Sum A{k->m_rBp, k->m_part, (long long)L.S, (long long)ne, (long long)per, (long long)(L.S * ne), (long long)wp, (long long)(nrc * ncc)};
       if ((rc = kkt_launch_raw(m, k->km->colsum_m, &A, sizeof A, nr * nrc * ncc, 256))) return rc;

@@ -374,6 +374,27 @@ function solve_refined!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{F
                 s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), s.delta_w, s.delta_c, dptr(rhs), dptr(sol), steps, pn))
     return sol
 end
+# A dense border (first-stage variables, u(t) of a laned grid) on the device: mode 1 factorises its Schur complement with a
+# Bunch–Kaufman LDL' in one workgroup and solves it there — solve! / solve_refined! then contain no synchronisation and can be
+# captured; mode 0 (the default) keeps it on the host.  A no-op for models without a dense border.
+border_on_device!(s::ChainKKTSolver, on::Bool = true) =
+    (check(ccall((:iem_kkt_set_border, LIBIEM), Cint, (Ptr{Cvoid}, Cint), s.k, on ? 1 : 0)); s)
+# factorize! without the read-back: (positive, negative, doubtful) into a device vector of three Int64 (mode 1, or no border)
+function factorize_async!(s::ChainKKTSolver, inertia::ROCVector{Int64})
+    check(ccall((:iem_kkt_assemble, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                s.k, dptr(s.hess), dptr(s.jac), dptr(s.sigma), s.delta_w, s.delta_c))
+    check(ccall((:iem_kkt_factor_async, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.k, dptr(inertia)))
+    return s
+end
+# the low-level pair on raw buffers (include/iem.h): Gs = G − Σ Gp[k] → F, piv (+ the pivot counters), xB = Gs⁻¹ (rB − Σ rBp[k])
+border_factor!(m::MI355XModel, S, ne, n_border, G, Gp, F, piv::ROCVector{Int32}, info::ROCVector{Int64}; rel = 1e-14) =
+    check(ccall((:iem_kkt_border_factor, LIBIEM), Cint,
+                (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}, Cdouble),
+                m.handle, S, ne, n_border, dptr(G), dptr(Gp), dptr(F), dptr(piv), dptr(info), rel))
+border_solve!(m::MI355XModel, S, ne, n_border, nrhs, F, piv::ROCVector{Int32}, rBp, rB, xB) =
+    check(ccall((:iem_kkt_border_solve, LIBIEM), Cint,
+                (Ptr{Cvoid}, Int64, Cint, Cint, Cint, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                m.handle, S, ne, n_border, nrhs, dptr(F), dptr(piv), dptr(rBp), dptr(rB), dptr(xB)))
 is_inertia(::ChainKKTSolver) = true
 inertia(s::ChainKKTSolver) = (s.inertia[1], s.inertia[3], s.inertia[2])      # (positive, zero, negative)
 

@@ -339,10 +339,18 @@ class MatrixFreeKKT:
 
 
 class ChainKKT:
-    """Factor / solve the augmented system assembled by a :class:`kkt.KKTSystem` with the chain solver."""
+    """Factor / solve the augmented system assembled by a :class:`kkt.KKTSystem` with the chain solver.
 
-    def __init__(self, kkt, group: Optional[int] = None):
+    ``border``: where a dense border's Schur complement is factorised and solved — ``"torch"`` (the default:
+    ``torch.linalg.lu_factor`` / ``eigvalsh`` / ``lu_solve``) or ``"device"``: the library's own Bunch–Kaufman LDLᵀ in one
+    workgroup and its substitution kernel (``iem_kkt_border_factor`` / ``iem_kkt_border_solve``), whose pivot counts give the
+    inertia without an eigenvalue decomposition."""
+
+    def __init__(self, kkt, group: Optional[int] = None, border: str = "torch"):
         import torch
+        if border not in ("torch", "device"):
+            raise ValueError("border must be 'torch' or 'device'")
+        self.border = border
         self._torch = torch
         self.kkt = kkt
         m = self.model = kkt.model
@@ -377,6 +385,8 @@ class ChainKKT:
         self._on, self._pos, self._border = (torch.as_tensor(a, device=dev) for a in (on, pos, border))
         self._glu = None
         self.negative_pivots = None
+        if self.border == "device" and ne:
+            self._F, self._piv = torch.empty(ne, ne, **f64), torch.empty(ne, dtype=torch.int32, device=dev)
 
     def load(self):
         """Dense blocks from the CSR values of the last ``kkt.assemble`` (zero fill + one scatter)."""
@@ -395,7 +405,9 @@ class ChainKKT:
         _lib.check(m._L.iem_kkt_chain_factor(m._h, L.S, L.nb, L.ne, L.nc, p(self.D), p(self.B) if chained else None, p(self.BR) if chained else None,
                                             p(self._rows) if chained else None, p(self._cols) if chained else None, p(self.E), p(self.Z), p(self.Gp),
                                             p(self.info), float(tiny)))
-        if L.ne:
+        if L.ne and self.border == "device":      # behind the chain's launches on the stream: its counts join the chain's in self.info
+            _lib.check(m._L.iem_kkt_border_factor(m._h, L.S, L.ne, L.n_border, p(self.G), p(self.Gp), p(self._F), p(self._piv), p(self.info), 1e-14))
+        elif L.ne:
             Gs = self.G - self.Gp[:L.S * L.ne * L.ne].view(L.S, L.ne, L.ne).sum(0)
             self._Gs = Gs
             self._glu = t.linalg.lu_factor(Gs)
@@ -407,7 +419,7 @@ class ChainKKT:
         t, L = self._torch, self.layout
         info = self.info.cpu().numpy()
         neg = int(info[0])
-        if L.ne:
+        if L.ne and self.border != "device":
             ev = t.linalg.eigvalsh(self._Gs)
             neg += int((ev < 0).sum().item())
         n = self.layout.nvar + self.layout.ncon
@@ -485,7 +497,11 @@ class ChainKKT:
                 p(self._rows) if chained else None, p(self._cols) if chained else None, p(self.Z), p(r), p(z) if chained else None, p(rBp))
         xB = None
         _lib.check(m._L.iem_kkt_chain_solve_many(*args, None, K, 0))
-        if L.ne:
+        if L.ne and self.border == "device":
+            xB, rB = t.empty(K, L.ne, **f64), t.zeros(K, L.ne, **f64)
+            rB[:, :L.n_border] = B[:, self._border]
+            _lib.check(m._L.iem_kkt_border_solve(m._h, L.S, L.ne, L.n_border, K, p(self._F), p(self._piv), p(rBp), p(rB), p(xB)))
+        elif L.ne:
             xB = t.empty(K, L.ne, **f64)
             for j in range(K):                         # (the border system per column, with the expressions of _solve_once: the same bits)
                 rB = t.zeros(L.ne, **f64)
@@ -523,7 +539,11 @@ class ChainKKT:
                 p(self._rows) if chained else None, p(self._cols) if chained else None, p(self.Z), p(r), p(self._z) if chained else None, p(self._rBp))
         xB = None
         _lib.check(m._L.iem_kkt_chain_solve(*args, None, 0))
-        if L.ne:
+        if L.ne and self.border == "device":
+            xB, rB = t.empty(L.ne, dtype=t.float64, device=r.device), t.zeros(L.ne, dtype=t.float64, device=r.device)
+            rB[:L.n_border] = rhs[self._border]
+            _lib.check(m._L.iem_kkt_border_solve(m._h, L.S, L.ne, L.n_border, 1, p(self._F), p(self._piv), p(self._rBp), p(rB), p(xB)))
+        elif L.ne:
             rB = t.zeros(L.ne, dtype=t.float64, device=r.device)
             rB[:L.n_border] = rhs[self._border]
             rB = rB - self._rBp[:L.S * L.ne].view(L.S, L.ne).sum(0)
