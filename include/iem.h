@@ -317,6 +317,48 @@ int iem_kktprod_prepare(iem_model *m, int32_t *out_n_kernels);
 int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u /* nvar */,
                 const double *d_v /* ncon, NULL = 0 */, double *d_out_x /* nvar */, double *d_out_y /* ncon */);
 
+/* ---- one launch per solver phase for the SCALED NLP ---------------------------------------------------------------------------
+ * A solver that scales its NLP (s = d_s: ncon row factors, obj_scale = s_f) evaluates, per trial point, s∘c(x) and s_f·f(x),
+ * and per accepted point s_f·∇f(x), the row-scaled Jacobian and the Hessian of  σ·s_f·f + (y∘s)'c:
+ *   iem_eval_trial_scaled     c = iem_cons_scaled(x, s) and *h_obj = obj_scale * iem_obj(x), ONE launch (iem_sp_trial_all)
+ *   iem_eval_accepted_scaled  g = iem_grad_scaled(x, obj_scale), jac = iem_jac_coord_scaled(x, s) and
+ *                             hess = iem_hess_coord_scaled(x, y, s, fl(obj_weight * obj_scale)), ONE launch
+ *                             (iem_sp_accepted_all) and sp_grad's follow-ups; the product of the two scalars is formed
+ *                             here, in host double arithmetic
+ *   iem_grad_scaled           obj_scale * ∇f(x): grad!'s reverse sweep seeded with obj_scale instead of 1.0
+ *   iem_hess_coord_scaled     iem_hess_coord(x, fl(y∘s), obj_weight): a constraint row's multiplier is ONE rounded multiply
+ *                             y[row] * s[row] in the kernel; obj_weight is the weight AS USED (the caller has multiplied in s_f)
+ * Under the default options (fp_contract = 0), on one handle at one (x, θ): c, jac and hess carry the bits of the calls named
+ * above (hess: of iem_hess_coord with y∘s formed by one float64 multiply per row), *h_obj is bitwise obj_scale * iem_obj(x),
+ * the phases' outputs carry the bits of the member calls.  iem_grad_scaled(x, 1.0) and (x, 2^k) equal iem_grad(x) and
+ * 2^k * iem_grad(x) as IEEE values (NaNs in the same places; the sign of a zero may differ, a folded 0.0 + v against a
+ * runtime one); a general factor agrees to rounding.  No float atomic in any kernel: every call is bitwise reproducible.
+ * The objective: the kernel writes the model's own f into the mapped host slot, exactly as iem_eval_trial arms and collects
+ * it, and the library returns obj_scale * f.  With h_obj == NULL the handle remembers the factor and iem_obj_end applies it
+ * to THAT pending value; every later arm (iem_obj_begin, iem_eval_trial, iem_eval_all, this call) resets it, a pending
+ * unscaled value is returned untouched.  The deferred form (h_obj == NULL ... iem_obj_end) must NOT be captured in a graph:
+ * the sentinel is armed and the slot read on the host; the call with h_obj waits on the host and cannot be captured either.
+ * Where a phase kernel does not exist (option "phase_kernels" = 0, a member missing — no objective, no constraint —, more
+ * workgroups than one launch takes) the member launches are made.  ncon == 0: d_s, d_y, d_c and d_jac may be NULL; a model
+ * without an objective gives g = 0 (the runtime's memsets) and f = 0; a linear program has no Hessian member.
+ * The kernels (kinds 0 / 1 / 2 / 3 / 4 / 9 / 10, names iem_sp_cons*, iem_sp_jac*, iem_sp_hess*, iem_sp_obj*, iem_sp_grad*,
+ * iem_sp_trial_all, iem_sp_accepted_all) are a NINTH program of their own over the plain model — the model's tile on every
+ * grid, its own reduction buffer, axis sums and gather plan for the gradient —, set up by the first of the four calls —
+ * synchronous, outside a stream capture; every later call is asynchronous on the handle's stream and capturable, except
+ * for the host-collected objective — or by iem_scaled_phase_prepare (idempotent; the number of this program's kernels).
+ * The other prepare calls do not prepare it and keep their counts; iem_kernel_info lists these kernels LAST, behind the KKT
+ * operator's, with their algorithmic bytes (a phase kernel: the union of its members' reads).  A sharded handle refuses all
+ * five calls with IEM_E_ARG (the gradient would need the halo fold and the all-reduce). */
+int iem_scaled_phase_prepare(iem_model *m, int32_t *out_n_kernels);
+int iem_grad_scaled(iem_model *m, const double *d_x, double obj_scale, double *d_g /* nvar */);
+int iem_hess_coord_scaled(iem_model *m, const double *d_x, const double *d_y, const double *d_s /* ncon */,
+                          double obj_weight, double *d_vals /* nnzh */);
+int iem_eval_trial_scaled(iem_model *m, const double *d_x, const double *d_s /* ncon */, double obj_scale,
+                          double *d_c /* ncon */, double *h_obj /* may be NULL */);
+int iem_eval_accepted_scaled(iem_model *m, const double *d_x, const double *d_y, const double *d_s /* ncon */,
+                             double obj_scale, double obj_weight,
+                             double *d_g /* nvar */, double *d_jac /* nnzj */, double *d_hess /* nnzh */);
+
 /* matrix-free products (NLPModels jprod! / jtprod! / hprod!; ExaModels' `prod = true` path —
  * not used by the reference's solvers): Jv (ncon), J'v (nvar), Hv (nvar) with
  * H the Hessian of obj_weight*f + y'c. */

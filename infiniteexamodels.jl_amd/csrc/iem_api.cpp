@@ -268,6 +268,15 @@ struct iem_model {
   // with d_v == NULL.  `kres_*`: the finishing kernels of iem_kkt_residual (loaded by its first call)
   ParamKinds kkt;
   double *d_kkt_zero = nullptr;
+  // the scaled solver phases (iem_eval_trial_scaled / iem_eval_accepted_scaled and their members; scaled_phase_kinds = 1, over
+  // the plain model): a ninth program, set up by its own first call or by iem_scaled_phase_prepare — the other prepare calls do
+  // not know of it.  Its gradient's zero ranges, reduction buffer, axis sums and gather plan are its own (ParamKinds), and
+  // `d_sph_partials` the partials and ticket words of ITS objective kernels.  `obj_factor`: what iem_obj_end multiplies the
+  // pending objective value with when `obj_scaled` (set by iem_eval_trial_scaled, cleared by every arm)
+  ParamKinds sph;
+  double *d_sph_partials = nullptr;
+  bool obj_scaled = false;
+  double obj_factor = 1.0;
   hipModule_t kres_mod = nullptr;
   hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
   // the dense border on the device (csrc/iem_kkt_border_device.h; loaded by the first call that needs it).  `kb_part`: the column
@@ -977,6 +986,7 @@ static int apply_option(iem::Options &o, int &poll_obj, const char *name, int64_
   if (std::strcmp(name, "param_kinds") == 0) { o.param_kinds = value >= 2 && value <= 5 ? (int)value : value != 0; return IEM_OK; }
   if (std::strcmp(name, "scaled_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "scaled_kinds must be 0 or 1"); o.scaled_kinds = (int)value; return IEM_OK; }
   if (std::strcmp(name, "kkt_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "kkt_kinds must be 0 or 1"); o.kkt_kinds = (int)value; return IEM_OK; }
+  if (std::strcmp(name, "scaled_phase_kinds") == 0) { if (value < 0 || value > 1) return fail(IEM_E_ARG, "scaled_phase_kinds must be 0 or 1"); o.scaled_phase_kinds = (int)value; return IEM_OK; }
   if (std::strcmp(name, "comm_timeout_ms") == 0) {
     if (value < 1 || value > 600000) return fail(IEM_E_ARG, "comm_timeout_ms must be in 1..600000");
     o.comm_timeout_ms = (int)value;
@@ -1132,6 +1142,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   hopt.param_kinds = 0;   // (the handle's own program; the parameter kinds are a second one, iem_model::par)
   hopt.scaled_kinds = 0;  // (... and the scaled program a seventh, iem_model::scl)
   hopt.kkt_kinds = 0;     // (... and the KKT operator an eighth, iem_model::kkt)
+  hopt.scaled_phase_kinds = 0;   // (... and the scaled solver phases a ninth, iem_model::sph)
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1285,6 +1296,11 @@ int iem_destroy(iem_model *m) {
   for (long long *r : m->kkt.d_gather) if (r) hipFree(r);
   free_program(m->kkt.code);
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
+  for (double *r : m->sph.d_red) if (r) hipFree(r);
+  for (long long *r : m->sph.d_axis) if (r) hipFree(r);
+  for (long long *r : m->sph.d_gather) if (r) hipFree(r);
+  free_program(m->sph.code);
+  if (m->d_sph_partials) hipFree(m->d_sph_partials);
   if (m->kres_mod) hipModuleUnload(m->kres_mod);
   if (m->kb_mod) hipModuleUnload(m->kb_mod);
   if (m->kb_part) hipFree(m->kb_part);
@@ -1318,10 +1334,10 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
   // behind the model's own kernels: those of every further program that exists on the handle (set up by its first call or
   // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program / scaled program /
-  // KKT operator
+  // KKT operator / scaled solver phases
   const iem::KernelDesc *found = k < (int)m->code.prog.kernels.size() ? &m->code.prog.kernels[k] : nullptr;
   int base = (int)m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt}) {
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt, &m->sph}) {
     if (found || !P->tried || P->rc != IEM_OK) continue;
     const int n = (int)P->code.prog.kernels.size();
     if (k < base + n) found = &P->code.prog.kernels[k - base];
@@ -1343,7 +1359,7 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
 int iem_kernel_count(const iem_model *m, int32_t *out_total) {
   if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
   size_t n = m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt})
+  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt, &m->sph})
     if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
   *out_total = (int32_t)n;
   return IEM_OK;
@@ -1424,6 +1440,7 @@ static const uint64_t kObjSentinel = 0x7ff8dead0bad0b1eULL;
 static void obj_arm(iem_model *m) {
   *reinterpret_cast<volatile uint64_t *>(m->h_obj) = kObjSentinel;
   m->obj_armed = true;
+  m->obj_scaled = false;   // (iem_eval_trial_scaled sets its factor behind its own arm)
 }
 
 int iem_obj_begin(iem_model *m, const double *d_x) {
@@ -1440,7 +1457,9 @@ int iem_obj_end(iem_model *m, double *h_out) {
   if (!m || !h_out) return fail(IEM_E_ARG, "null argument");
   if (!m->obj_armed) return fail(IEM_E_ARG, "iem_obj_end without iem_obj_begin");
   m->obj_armed = false;
-  if (m->code.prog.n_partials == 0) { *h_out = 0.0; return comm_check(m); }
+  const bool scaled = m->obj_scaled;   // the pending value is iem_eval_trial_scaled's: times its factor, one host multiply
+  m->obj_scaled = false;
+  if (m->code.prog.n_partials == 0) { *h_out = scaled ? m->obj_factor * 0.0 : 0.0; return comm_check(m); }
   DevGuard dg_(m->device);
   volatile uint64_t *slot = reinterpret_cast<volatile uint64_t *>(m->h_obj);
   bool got = false;
@@ -1454,6 +1473,7 @@ int iem_obj_end(iem_model *m, double *h_out) {
   if (!got) HIP_TRY(hipStreamSynchronize(m->stream));   // large models, or a result that happens to BE the sentinel
   uint64_t bits = *slot;
   std::memcpy(h_out, &bits, 8);
+  if (scaled) *h_out = m->obj_factor * *h_out;
   return comm_check(m);
 }
 
@@ -1507,9 +1527,9 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
 // The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2), of the θθ kind
-// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4), the residual program (P = m->lag, kinds = 5) or the scaled program (P = m->scl, kinds = 0, scaled = 1), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
+// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4), the residual program (P = m->lag, kinds = 5) or the scaled program (P = m->scl, kinds = 0, scaled = 1), the KKT operator (P = m->kkt, kkt = 1) or the scaled solver phases (P = m->sph, sphase = 1), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
 // later call.
-static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0, int kkt = 0) {
+static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0, int kkt = 0, int sphase = 0) {
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
   P.tried = true;
   // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
@@ -1531,6 +1551,7 @@ static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int 
   po.param_kinds = kinds;
   po.scaled_kinds = scaled;
   po.kkt_kinds = kkt;
+  po.scaled_phase_kinds = sphase;
   try {
     P.code.prog = iem::generate(m->model, po);
   } catch (const std::exception &e) {
@@ -1948,6 +1969,151 @@ int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   for (int k : P.code.launchable[iem::KK_HPROD])
     if ((rc = launch_one(m, P.code, k, h))) return rc;
   return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_HPROD, d_out_x, red);
+}
+
+// ---- one launch per solver phase for the SCALED NLP ---------------------------------------------------------------------------
+// The ninth program (P = m->sph, scaled_phase_kinds = 1: sp_cons / sp_jac / sp_hess / sp_obj / sp_grad on the model's own table
+// slots, KK_TRIAL and KK_ACCEPTED over them; s = the head's v, y = the head's y), set up like the θ programs, and the partials
+// of its objective kernels.  The accepted phase has two scalars: the head's w is the Hessian's objective weight, the
+// gradient's seed travels as the bits of a double in the head's word p4.  sp_grad's memsets and follow-ups stay here.
+static int sphase_refuse_sharded(const iem_model *m, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the scaled gradient would need the halo fold and the all-reduce "
+                         "of grad!, and the deferred halo exchange is not taught this program; scaled solver phases on a sharded handle are out of scope");
+}
+
+static int sphase_program(iem_model *m) {
+  int rc = param_program(m, m->sph, 0, 0, 0, 1);
+  if (rc) return rc;
+  if (!m->d_sph_partials) {   // partials + ticket counters, zeroed once (the workgroups that complete a count reset it)
+    const size_t np = (size_t)std::max<int64_t>(m->sph.code.prog.n_partials, 1);
+    const size_t words = np + 1 + (np + 31) / 32;
+    if (hipMalloc((void **)&m->d_sph_partials, words * 8) != hipSuccess) { m->d_sph_partials = nullptr; return fail(IEM_E_HIP, "hipMalloc partials"); }
+    if (hipMemsetAsync(m->d_sph_partials, 0, words * 8, m->stream) != hipSuccess) {
+      hipFree(m->d_sph_partials);
+      m->d_sph_partials = nullptr;
+      return fail(IEM_E_HIP, "hipMemsetAsync partials");
+    }
+  }
+  return IEM_OK;
+}
+
+// the launchable kernels of one member kind of the program
+static int sphase_members(iem_model *m, int kind, const LaunchHead &h) {
+  int rc;
+  for (int k : m->sph.code.launchable[kind])
+    if ((rc = launch_one(m, m->sph.code, k, h))) return rc;
+  return IEM_OK;
+}
+
+// what the runtime memsets in front of sp_grad (the whole of g on a model without an objective)
+static int sphase_zero_grad(iem_model *m, double *d_g) {
+  for (auto &z : m->sph.code.prog.zero_ranges[iem::KK_GRAD])
+    HIP_TRY(hipMemsetAsync(d_g + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
+  return IEM_OK;
+}
+
+static int sphase_grad_followups(iem_model *m, double *d_g) {
+  iem_model::ParamKinds &P = m->sph;
+  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_GRAD, d_g, P.d_red[iem::KK_GRAD]);
+}
+
+int iem_scaled_phase_prepare(iem_model *m, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = sphase_refuse_sharded(m, "iem_scaled_phase_prepare");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = sphase_program(m))) return rc;
+  if (out_n_kernels) *out_n_kernels = (int32_t)m->sph.code.prog.kernels.size();
+  return IEM_OK;
+}
+
+/* obj_scale * grad f(x): the reverse sweep seeded with obj_scale */
+int iem_grad_scaled(iem_model *m, const double *d_x, double obj_scale, double *d_g) {
+  if (!m || !d_x || (!d_g && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
+  int rc = sphase_refuse_sharded(m, "iem_grad_scaled");
+  if (rc) return rc;
+  if (m->model.nvar == 0) return IEM_OK;
+  DevGuard dg_(m->device);
+  if ((rc = sphase_program(m)) || (rc = sphase_zero_grad(m, d_g))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.out = d_g; h.w = obj_scale; h.aux = m->sph.d_red[iem::KK_GRAD];
+  if ((rc = sphase_members(m, iem::KK_GRAD, h))) return rc;
+  return sphase_grad_followups(m, d_g);
+}
+
+/* hess_coord!(x, fl(y∘s); obj_weight): the multiplier of a scaled row formed in the kernel */
+int iem_hess_coord_scaled(iem_model *m, const double *d_x, const double *d_y, const double *d_s, double obj_weight, double *d_vals) {
+  if (!m || !d_x || ((!d_y || !d_s) && m->model.ncon) || (!d_vals && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
+  int rc = sphase_refuse_sharded(m, "iem_hess_coord_scaled");
+  if (rc) return rc;
+  if (m->model.nnzh == 0) return IEM_OK;
+  DevGuard dg_(m->device);
+  if ((rc = sphase_program(m))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_s; h.out = d_vals; h.w = obj_weight;
+  return sphase_members(m, iem::KK_HESS, h);
+}
+
+/* s∘cons(x) and obj_scale·obj(x) in ONE launch (the program's KK_TRIAL); where that kernel does not exist (option
+ * "phase_kernels" = 0, no objective or no constraint, more workgroups than one launch takes) the member launches */
+int iem_eval_trial_scaled(iem_model *m, const double *d_x, const double *d_s, double obj_scale, double *d_c, double *h_obj) {
+  if (!m || !d_x || ((!d_s || !d_c) && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
+  int rc = sphase_refuse_sharded(m, "iem_eval_trial_scaled");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = sphase_program(m))) return rc;
+  if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_trial_scaled: the previous iem_obj_begin / iem_eval_trial has not been collected (iem_obj_end)");
+  iem_model::ParamKinds &P = m->sph;
+  obj_arm(m);
+  m->obj_scaled = true; m->obj_factor = obj_scale;
+  LaunchHead h;   // the kernel writes the model's own f into the mapped slot, the factor meets it on the host (iem_obj_end)
+  h.x = d_x; h.th = m->d_theta; h.v = d_s;
+  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
+    h.out = d_c; h.aux = m->d_hobj; h.trial_partials = m->d_sph_partials;
+    rc = sphase_members(m, iem::KK_TRIAL, h);
+  } else {
+    h.out = d_c;
+    rc = sphase_members(m, iem::KK_CONS, h);
+    if (rc == IEM_OK) {   // (no objective template: nothing is launched and iem_obj_end gives 0)
+      h.out = m->d_sph_partials; h.aux = m->d_hobj;
+      rc = sphase_members(m, iem::KK_OBJ, h);
+    }
+  }
+  if (rc) { m->obj_armed = false; m->obj_scaled = false; return rc; }
+  return h_obj ? iem_obj_end(m, h_obj) : IEM_OK;
+}
+
+/* obj_scale·grad f, s[row]·jac and hess_coord!(x, fl(y∘s); fl(obj_weight·obj_scale)) in ONE launch (the program's
+ * KK_ACCEPTED), sp_grad's follow-ups behind it; where that kernel does not exist, the member launches */
+int iem_eval_accepted_scaled(iem_model *m, const double *d_x, const double *d_y, const double *d_s, double obj_scale, double obj_weight,
+                             double *d_g, double *d_jac, double *d_hess) {
+  if (!m || !d_x || (!d_g && m->model.nvar) || ((!d_y || !d_s) && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh))
+    return fail(IEM_E_ARG, "null argument");
+  int rc = sphase_refuse_sharded(m, "iem_eval_accepted_scaled");
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  if ((rc = sphase_program(m))) return rc;
+  iem_model::ParamKinds &P = m->sph;
+  const double w = obj_weight * obj_scale;   // the Hessian's objective weight as used: one host multiply
+  if (m->model.nvar && (rc = sphase_zero_grad(m, d_g))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_s; h.w = w;
+  if (!P.code.launchable[iem::KK_ACCEPTED].empty()) {
+    h.out = d_jac; h.aux = d_hess; h.g = d_g; h.g_red = P.d_red[iem::KK_GRAD];
+    static_assert(sizeof h.c == sizeof obj_scale, "the gradient's seed rides on one word of the head");
+    std::memcpy(&h.c, &obj_scale, 8);   // (the head's p4: the bits of sp_grad's seed, iem_sp_word)
+    if ((rc = sphase_members(m, iem::KK_ACCEPTED, h))) return rc;
+    return sphase_grad_followups(m, d_g);
+  }
+  h.out = d_jac;
+  if ((rc = sphase_members(m, iem::KK_JAC, h))) return rc;
+  h.out = d_hess;
+  if ((rc = sphase_members(m, iem::KK_HESS, h))) return rc;
+  if (m->model.nvar == 0) return IEM_OK;
+  h.out = d_g; h.w = obj_scale; h.aux = P.d_red[iem::KK_GRAD];
+  if ((rc = sphase_members(m, iem::KK_GRAD, h))) return rc;
+  return sphase_grad_followups(m, d_g);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {

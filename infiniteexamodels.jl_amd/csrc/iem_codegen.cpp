@@ -779,6 +779,10 @@ class KernelBuilder {
   // kkt_kinds = 1: the KKT operator over the PLAIN model — kktx (W u + J' dv) on the table slot of hprod, kkty (J u) on that of
   // jprod with the model's own builder; u = A.v, the dual direction dv = A.p6, read at row indices like y
   bool kkt() const { return opt_.kkt_kinds != 0; }
+  // scaled_phase_kinds = 1: the scaled solver phases over the PLAIN model — the model's five kinds on their own table slots with
+  // the row factors s = A.v inside (sp_cons, sp_jac as the scaled program's; sp_hess seeded with fl(y[row] * s[row])) and the
+  // gradient seeded with A.w (sp_grad); sp_obj is the model's own objective
+  bool sphase() const { return opt_.scaled_phase_kinds != 0; }
   // s[row] of a constraint template's item: one load per row, where jtprod loads its seed
   int scale_of_row(const Template &t, const TGeo &G) {
     IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into s), not an output position
@@ -821,6 +825,7 @@ class KernelBuilder {
       case KK_HPROD: return t.o2step > 0 || (t.kind == IEM_T_CON && t.o1step > 0);
       default: return false;
     }
+    if (sphase() && kind_ >= KK_JPROD) return false;   // the model's five evaluation kinds below, no product kind
     if (lagrangian()) switch (kind_) {
       case KK_CONS: return t.kind == IEM_T_CON;
       case KK_OBJ: return t.kind == IEM_T_OBJ;
@@ -868,7 +873,7 @@ class KernelBuilder {
           IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0);
           o.pos_idx = idxval(iv); o.pos_off = t.o0;
           o.vals = {tg.val[t.root]};
-          if (scaled()) o.vals[0] = scaled_by(o.vals[0], scale_of_row(t, G));   // cons_scaled: s[row] * c_row
+          if (scaled() || sphase()) o.vals[0] = scaled_by(o.vals[0], scale_of_row(t, G));   // cons_scaled / sp_cons: s[row] * c_row
           alg_w_ += t.n_items;
           break;
         }
@@ -880,7 +885,8 @@ class KernelBuilder {
         case KK_GRAD: {
           tg.forward(1);
           tg.slots1.assign(t.o1step, -1);
-          tg.gr(t.root, 0, C(1.0));
+          // sp_grad: the gradient of  s_f f — the sweep seeded with A.w, as lagrad seeds an objective template with σ
+          tg.gr(t.root, 0, kind_ == KK_GRAD && sphase() ? mk(VW, 0, -1, -1, -1, 0) : C(1.0));
           if (kind_ == KK_JAC && theta_coord()) {   // dc/dθ: the θ slots of the row, the partials of x are never built into it
             for (int s : t.pc1) o.vals.push_back(tg.slots1[s]);
             IdxVal iv; iv.aff = klin_aff(t, G, (int64_t)t.pc1.size(), t.pc_o1);
@@ -889,7 +895,7 @@ class KernelBuilder {
             break;
           }
           o.vals = tg.slots1;
-          if (kind_ == KK_JAC && scaled()) {   // jac_scaled: every finished slot times its row's factor (data rows and computed rows alike)
+          if (kind_ == KK_JAC && (scaled() || sphase())) {   // jac_scaled / sp_jac: every finished slot times its row's factor (data rows and computed rows alike)
             const int sc = scale_of_row(t, G);
             for (int &v : o.vals) v = scaled_by(v, sc);
           }
@@ -1061,6 +1067,7 @@ class KernelBuilder {
           else {
             IdxVal iv; iv.aff = klin_aff(t, G, 1, t.o0); iv.aff.space = 4;   // a row index (into y), not an output position
             adj = load(2, 0, idxval(iv), G.guard);
+            if (sphase()) adj = scaled_by(adj, scale_of_row(t, G));   // sp_hess: the multiplier of the scaled row, fl(y[row] * s[row])
           }
           tg.hr0(t.root, 0, adj, C(0.0));
           if (theta_coord()) {
@@ -2135,7 +2142,7 @@ class KernelBuilder {
         const int id = st.back(); st.pop_back();
         if (id < 0 || !seen.insert(id).second) continue;
         const VNode &n = v_[id];
-        if (n.op == VLD) { if (loads_[n.sub].arr != 3 && !(scaled() && loads_[n.sub].arr == 4)) pure = false; }   // (jac_scaled: the row's factor is no reason to join the computed rows)
+        if (n.op == VLD) { if (loads_[n.sub].arr != 3 && !((scaled() || sphase()) && loads_[n.sub].arr == 4)) pure = false; }   // (jac_scaled / sp_jac: the row's factor is no reason to join the computed rows)
         else if (n.op == VW) pure = false;
         else if (n.op == VUN || n.op == VGUARD) st.push_back(n.a);
         else if (n.op == VBIN || n.op == VSEL) { st.push_back(n.a); st.push_back(n.b); }
@@ -2612,7 +2619,8 @@ static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", 
 static const char *const kname_lag[] = {"cons", "", "", "obj", "", "", "lagrad", ""};   // param_kinds = 5: the residual program (plain model)
 static const char *const kname_scaled[] = {"cons_scaled", "jac_scaled", "", "", "", "rowmax", "", ""};   // scaled_kinds = 1: the scaled program (plain model)
 static const char *const kname_kkt[] = {"", "", "", "", "", "kkty", "", "kktx"};   // kkt_kinds = 1: the KKT operator (plain model)
-static const char *const *kind_names(const Options &o) { return o.kkt_kinds ? kname_kkt : o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+static const char *const kname_sphase[] = {"sp_cons", "sp_jac", "sp_hess", "sp_obj", "sp_grad", "", "", ""};   // scaled_phase_kinds = 1: the scaled solver phases (plain model)
+static const char *const *kind_names(const Options &o) { return o.scaled_phase_kinds ? kname_sphase : o.kkt_kinds ? kname_kkt : o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2651,6 +2659,7 @@ struct Place {
   size_t ip = 0, dp = 0, fa = 0, ia = 0;
   std::string tbl;
   const char *out = nullptr, *aux = nullptr;
+  const char *w = nullptr;   // the scalar the member's bodies get in place of A.w (the scaled accepted phase: sp_grad's seed)
 };
 
 static bool fits_one_launch(int64_t workgroups) { return workgroups <= 2147483647LL; }
@@ -2735,7 +2744,7 @@ static std::string dispatch_code(const Launch &E, const Place &at, const std::st
   auto ipx = [&](size_t i) { return "A.ip[" + std::to_string(ipb + i) + "]"; };
   auto call = [&](size_t j, const std::string &ind) {
     std::ostringstream s;
-    s << ind << (is_obj ? "acc += " : "") << E.bodies[j].d->name << "_body(A.x, A.th, A.y, A.v, " << (E.dv ? "A.p6, " : "") << out(j) << ", A.w, " << aux(j) << ", A.ip + " << (ipb + E.oip[j])
+    s << ind << (is_obj ? "acc += " : "") << E.bodies[j].d->name << "_body(A.x, A.th, A.y, A.v, " << (E.dv ? "A.p6, " : "") << out(j) << ", " << (at.w ? at.w : "A.w") << ", " << aux(j) << ", A.ip + " << (ipb + E.oip[j])
       << ", A.dp + " << (at.dp + E.odp[j]) << ", A.fa + " << (at.fa + E.ofa[j]) << ", A.ia + " << (at.ia + E.oia[j])
       << ", lds_blk, lds4, lb % gx, (lb / gx) % gy, lb / (gx * gy), gx, gy, gz);\n";
     return s.str();
@@ -2877,12 +2886,17 @@ static void emit_kinds(Emitter &E) {
 static void emit_phases(Emitter &E) {
   if (!E.phases_on()) return;
   std::ostringstream &src = E.src;
-  struct Member { int kind; const char *out, *aux; };
+  struct Member { int kind; const char *out, *aux; const char *w = nullptr; };   // w: passed to the member's bodies in place of A.w
   struct Phase { int id; const char *name; std::vector<Member> mem; };
   // The KKT operator (Options::kkt_kinds = 1) has ONE phase too, on the free slot KK_TRIAL: kkty (out = p2) and kktx (out, aux =
   // its reduction buffer), u = A.v, the dual direction = p6; kktx's follow-ups stay with the runtime.
   const std::vector<Phase> phases = E.opt.kkt_kinds ? std::vector<Phase>{
     {KK_TRIAL, "iem_kktprod_all", {{KK_JPROD, "A.p2", "nullptr"}, {KK_HPROD, "A.out", "A.aux"}}},
+  } : E.opt.scaled_phase_kinds ? std::vector<Phase>{
+    // the scaled solver phases (Options::scaled_phase_kinds = 1): the two phases below with this program's members; A.w is
+    // the Hessian's objective weight, sp_grad's seed s_f the double whose bits the head's word p4 holds.  No KK_ALL.
+    {KK_TRIAL, "iem_sp_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
+    {KK_ACCEPTED, "iem_sp_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3", "iem_sp_word(A.p4)"}}},
   } : E.opt.param_kinds == 5 ? std::vector<Phase>{
     {KK_TRIAL, "iem_residual_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}, {KK_JTPROD, "A.p3", "A.p4"}}},
   } : std::vector<Phase>{
@@ -2916,7 +2930,7 @@ static void emit_phases(Emitter &E) {
       const Launch &L = E.emitted[mb.kind];
       // the member's tables WITHOUT its per-workgroup table (the only part whose length depends on the launch size:
       // those go behind everything else, so that every index the source names is size-independent)
-      base.push_back(Place{F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), std::string(), mb.out, mb.aux});
+      base.push_back(Place{F.ip.size(), F.dp.size(), F.fa.size(), F.ia.size(), std::string(), mb.out, mb.aux, mb.w});
       first.push_back(F.grid[0]);
       F.ip.insert(F.ip.end(), L.F.ip.begin(), L.F.ip.begin() + (long)L.tbl);
       F.dp.insert(F.dp.end(), L.F.dp.begin(), L.F.dp.end());
@@ -3008,6 +3022,17 @@ static Program generate_kinds(const Model &m, const Options &opt_in);
 
 Program generate(const Model &m, const Options &opt_in) {
   validate_indices(m);
+  if (opt_in.scaled_phase_kinds) {
+    // the scaled solver phases: the model's five kinds with the row factors inside and the gradient seeded with A.w, over the
+    // PLAIN model; the model's tile on every grid (as the scaled program), no pair, its phase kernels are TRIAL and ACCEPTED
+    if (opt_in.param_kinds) throw std::runtime_error("scaled_phase_kinds and param_kinds name different programs: set one of them");
+    if (opt_in.scaled_kinds) throw std::runtime_error("scaled_phase_kinds and scaled_kinds name different programs: set one of them");
+    if (opt_in.kkt_kinds) throw std::runtime_error("scaled_phase_kinds and kkt_kinds name different programs: set one of them");
+    Options o = opt_in;
+    o.hess_merge = 0; o.pair_kernel = 0;
+    o.big_batch_jac = o.big_batch_hess = 0;
+    return generate_kinds(m, o);
+  }
   if (opt_in.scaled_kinds) {
     // the scaled program: rowmax, cons_scaled and jac_scaled over the PLAIN model, through the store path of the model's own
     // kinds; the model's tile on every grid (as the explicit θ blocks), no pair, no phase kernel
@@ -3049,6 +3074,7 @@ Program generate(const Model &m, const Options &opt_in) {
 static Program generate_kinds(const Model &m, const Options &opt_in) {
   Options opt = opt_in;
   const bool kkt = opt.kkt_kinds != 0;                                     // kkt: the KKT operator — kktx and kkty of the plain model
+  const bool sph = opt.scaled_phase_kinds != 0;                            // sph: the scaled solver phases — the model's five kinds, scaled, and their two phases
   const bool scl = opt.scaled_kinds != 0;                                  // scl: the scaled program — cons_scaled, jac_scaled and rowmax of the plain model
   const bool lag = opt.param_kinds == 5;                                   // lag: the residual program — cons, obj and lagrad of the plain model
   const bool theta = opt.param_kinds != 0 && !lag, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
@@ -3089,6 +3115,9 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   }
   std::ostringstream src;
   src << "// generated by libiem_hip (iem_codegen.cpp) — do not edit\n";
+  if (sph)   // device code of this program alone (the device header is part of every model's source and stays as it is)
+    src << "// the second scalar of the scaled accepted phase: sp_grad's seed, carried as the bits of a double in a pointer word of the head\n"
+        << "__device__ __forceinline__ double iem_sp_word(const double* p) { double d; __builtin_memcpy(&d, &p, 8); return d; }\n";
 
   // gradient slot classification needs a global view of every objective slot's index range
   struct GSlot { int kind; int kernel; int out; int slot; int64_t lo, hi; bool injective, uniform0; AffQ aff; bool pure; int64_t count = 0;
@@ -3116,6 +3145,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       if (lag && kind != KK_CONS && kind != KK_OBJ && kind != KK_JTPROD) continue;
       if (scl && kind != KK_CONS && kind != KK_JAC && kind != KK_JPROD) continue;
       if (kkt && kind != KK_JPROD && kind != KK_HPROD) continue;
+      if (sph && kind >= KK_JPROD) continue;
       std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
       auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
@@ -3346,7 +3376,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     };
     // (not the adjoint parameter kind, nor the θθ kind: its output must be written without any float atomic — and the atomics would need a
     //  memset launch in front of the kernel where the gather needs its launch behind it)
-    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2 && !kkt) {
+    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2 && !kkt && !sph) {
       // at most TWO addends per entry: a + b = b + a, those atomics are already order-independent — and cheaper than
       // a second launch
       std::vector<int64_t> d0;
@@ -3419,6 +3449,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     if (lag && kind != KK_JTPROD) continue;
     if (scl) continue;
     if (kkt && kind != KK_HPROD) continue;
+    if (sph && kind != KK_GRAD) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
@@ -3494,7 +3525,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   emit_kinds(E);
   if (!theta) {
     emit_phases(E);
-    if (!lag && !scl && !kkt) emit_pair(E, m, whole_of, second_half);
+    if (!lag && !scl && !kkt && !sph) emit_pair(E, m, whole_of, second_half);
   }
   P.source = src.str();
   P.key = fnv1a64(P.source);

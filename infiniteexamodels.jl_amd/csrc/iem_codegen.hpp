@@ -169,6 +169,20 @@ struct Options {
   // and KK_TRIAL, free in this program, holds both behind one dispatcher (iem_kktprod_all: kkty's out = p2, kktx's out / aux as
   // in its own launch); kktx's follow-ups stay with the runtime.  The model's tile on every grid, no pair.
   int kkt_kinds = 0;
+  // 1: generate() emits the SCALED SOLVER PHASES instead — a ninth program over the PLAIN model (param_kinds, scaled_kinds and
+  // kkt_kinds must be 0; with 0 here the sources, keys and launch plans of every other program are what they were): the five
+  // evaluations of a solver that scales its NLP, on the model's own table slots.  s = A.v (ncon row factors), y = A.y:
+  //   sp_cons on KK_CONS's: s[row] * c_row(x), as cons_scaled           sp_jac on KK_JAC's: s[row] * slot, as jac_scaled
+  //   sp_obj  on KK_OBJ's:  the model's own objective bodies (the factor s_f meets the 8-byte scalar on the host)
+  //   sp_hess on KK_HESS's: hess_coord! with a constraint template seeded by fl(y[row] * s[row]) — ONE rounded multiply, never
+  //           folded, s[row] loaded where scale_of_row loads it; an objective template's seed stays A.w
+  //   sp_grad on KK_GRAD's: grad! with the reverse sweep seeded by A.w (= s_f) instead of 1.0, through the same deterministic
+  //           scatter (no float atomic, the two-addend shortcut off)
+  // and the two solver phases over them: KK_TRIAL {sp_cons -> out, sp_obj -> p2 / aux}, KK_ACCEPTED {sp_jac -> out, sp_hess ->
+  // aux, sp_grad -> p2 / p3}.  The accepted phase has TWO scalars: A.w is the Hessian's objective weight, the gradient's seed
+  // travels as the bits of a double in the head's word p4 (iem_sp_word, emitted with this program's source only).  The
+  // model's tile on every grid, no pair, no KK_ALL (iem_point_all uses p4 .. p6 itself).
+  int scaled_phase_kinds = 0;
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };

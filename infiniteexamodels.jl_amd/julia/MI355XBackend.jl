@@ -238,6 +238,38 @@ function jac_coord_scaled!(m::MI355XModel, x::ROCVector{Float64}, s::ROCVector{F
     check(ccall((:iem_jac_coord_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), m.handle, dptr(x), dptr(s), dptr(vals)))
     return vals
 end
+# One launch per solver phase for the scaled NLP (a ninth program of the handle): s the row factors, obj_scale the factor of the
+# objective.  eval_trial_scaled! gives (obj_scale * f, s .* c), eval_accepted_scaled! gives obj_scale * ∇f, s[rows] .* jac and
+# hess_coord!(x, y .* s; obj_weight * obj_scale) — bitwise the scaled calls above / the composed ones.  A model without
+# constraints passes `nothing` for s, y, c and jac.
+spptr(v) = v === nothing ? Ptr{Float64}(C_NULL) : dptr(v)
+function scaled_phase_prepare!(m::MI355XModel)
+    n = Ref{Int32}(0)
+    check(ccall((:iem_scaled_phase_prepare, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int32}), m.handle, n))
+    return Int(n[])
+end
+function grad_scaled!(m::MI355XModel, x::ROCVector{Float64}, obj_scale::Real, g::ROCVector{Float64})
+    check(ccall((:iem_grad_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cdouble, Ptr{Float64}), m.handle, dptr(x), obj_scale, dptr(g)))
+    return g
+end
+function hess_coord_scaled!(m::MI355XModel, x::ROCVector{Float64}, y, s, vals::ROCVector{Float64}; obj_weight = 1.0)
+    check(ccall((:iem_hess_coord_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+                m.handle, dptr(x), spptr(y), spptr(s), obj_weight, dptr(vals)))
+    return vals
+end
+function eval_trial_scaled!(m::MI355XModel, x::ROCVector{Float64}, s, obj_scale::Real, c)
+    f = Ref{Float64}(0.0)
+    check(ccall((:iem_eval_trial_scaled, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), spptr(s), obj_scale, spptr(c), f))
+    return f[], c
+end
+function eval_accepted_scaled!(m::MI355XModel, x::ROCVector{Float64}, y, s, obj_scale::Real, g::ROCVector{Float64}, jac,
+                               hess; obj_weight = 1.0)
+    check(ccall((:iem_eval_accepted_scaled, LIBIEM), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                m.handle, dptr(x), spptr(y), spptr(s), obj_scale, obj_weight, dptr(g), spptr(jac), spptr(hess)))
+    return g, jac, hess
+end
 # The KKT operator in one launch: out_x = W u + J' v, out_y = J u with W = obj_weight ∇²f + Σ y_r ∇²c_r — the product with
 # [W J'; J 0] a matrix-free method (and the residual of a Newton step) needs.  v === nothing means v = 0; outputs may not alias inputs.
 function kktprod_prepare!(m::MI355XModel)

@@ -101,6 +101,7 @@ class ExaModel:
         self._lag_n = None       # kernels of the residual program (lagrangian_prepare), once it is set up
         self._scl_n = None       # kernels of the scaled program (scaled_prepare), once it is set up
         self._kkt_n = None       # kernels of the KKT operator (kkt_prepare), once it is set up
+        self._sph_n = None       # kernels of the scaled solver phases (scaled_phase_prepare), once they are set up
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -316,7 +317,7 @@ class ExaModel:
         n = self.lagrangian_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._scl_n or 0) - (self._kkt_n or 0)
+        last = int(total.value) - (self._scl_n or 0) - (self._kkt_n or 0) - (self._sph_n or 0)
         return self._kernel_infos(last - n, last)
 
     def lagrangian_grad(self, x, y, obj_weight: float = 1.0, out=None):
@@ -369,7 +370,7 @@ class ExaModel:
         n = self.scaled_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._kkt_n or 0)
+        last = int(total.value) - (self._kkt_n or 0) - (self._sph_n or 0)
         return self._kernel_infos(last - n, last)
 
     # ---- the KKT operator in one launch: W·u + Jᵀ·v and J·u ----
@@ -384,11 +385,96 @@ class ExaModel:
     def kkt_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the KKT operator (kinds hprod / jprod, names ``iem_kktx*`` /
         ``iem_kkty*``, and the one-launch kernel ``iem_kktprod_all``, kind trial): always the LAST kernels ``iem_kernel_info``
-        lists."""
+        lists in front of the scaled solver phases' (``scaled_phase_kernels``), where those exist."""
         n = self.kkt_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        last = int(total.value) - (self._sph_n or 0)
+        return self._kernel_infos(last - n, last)
+
+    # ---- one launch per solver phase for the scaled NLP ----
+    def scaled_phase_prepare(self) -> int:
+        """Set up the program of ``eval_trial_scaled`` / ``eval_accepted_scaled`` / ``grad_scaled`` / ``hess_coord_scaled`` now
+        (``iem_scaled_phase_prepare``: otherwise their first call does — synchronously, and not inside a stream capture); the
+        number of its kernels."""
+        n = C.c_int32()
+        _lib.check(self._L.iem_scaled_phase_prepare(self._h, C.byref(n)))
+        self._sph_n = int(n.value)
+        return self._sph_n
+
+    def scaled_phase_kernels(self):
+        """Launch shape and algorithmic traffic of the kernels of the scaled solver phases (kinds cons / jac / hess / obj /
+        grad, names ``iem_sp_*``, and the phase kernels ``iem_sp_trial_all`` / ``iem_sp_accepted_all``, kinds trial /
+        accepted): always the LAST kernels ``iem_kernel_info`` lists."""
+        n = self.scaled_phase_prepare()
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
         return self._kernel_infos(int(total.value) - n, int(total.value))
+
+    def _chk_opt(self, t, n: int, name: str):
+        """``None`` is the C-ABI's NULL for a zero-length array"""
+        if t is not None or n:
+            self._chk(t, n, name)
+
+    def grad_scaled(self, x, obj_scale: float, g=None):
+        """``obj_scale·∇f(x)`` from the gradient kernel itself (``iem_grad_scaled``: the reverse sweep seeded with the factor);
+        equal to ``grad(x)`` for the factor 1 and to ``2^k·grad(x)`` for a power of two, to rounding otherwise."""
+        self._chk(x, self.meta.nvar, "x")
+        g = g if g is not None else self._new(self.meta.nvar)
+        self._chk(g, self.meta.nvar, "g")
+        self._sync_stream()
+        if self._sph_n is None:
+            self.scaled_phase_prepare()
+        _lib.check(self._L.iem_grad_scaled(self._h, _ptr(x), float(obj_scale), _ptr(g)))
+        self.counters.neval_grad += 1
+        return g
+
+    def hess_coord_scaled(self, x, y, s, vals=None, obj_weight: float = 1.0):
+        """``hess_coord(x, y∘s, obj_weight)`` with the row's multiplier formed in the kernel (``iem_hess_coord_scaled``):
+        bitwise ``hess_coord(x, y * s, obj_weight)``.  ``obj_weight`` is the weight as used (the objective's factor included)."""
+        self._chk(x, self.meta.nvar, "x"); self._chk_opt(y, self.meta.ncon, "y"); self._chk_opt(s, self.meta.ncon, "s")
+        vals = vals if vals is not None else self._new(self.meta.nnzh)
+        self._chk(vals, self.meta.nnzh, "vals")
+        self._sync_stream()
+        if self._sph_n is None:
+            self.scaled_phase_prepare()
+        _lib.check(self._L.iem_hess_coord_scaled(self._h, _ptr(x), _ptr(y), _ptr(s), float(obj_weight), _ptr(vals)))
+        self.counters.neval_hess += 1
+        return vals
+
+    def eval_trial_scaled(self, x, s, obj_scale: float, c=None, defer_obj: bool = False):
+        """``obj_scale·obj(x)`` and ``s ∘ cons(x)`` in ONE launch (``iem_eval_trial_scaled``).  Returns ``(f, c)``; ``c`` is
+        bitwise ``cons_scaled(x, s)``, ``f`` bitwise ``obj_scale * obj(x)``.  ``defer_obj``: returns ``(None, c)`` at once and
+        :meth:`obj_end` collects the SCALED value later (not inside a stream capture)."""
+        self._chk(x, self.meta.nvar, "x"); self._chk_opt(s, self.meta.ncon, "s")
+        c = c if c is not None else self._new(self.meta.ncon)
+        self._chk(c, self.meta.ncon, "c")
+        self._sync_stream()
+        if self._sph_n is None:
+            self.scaled_phase_prepare()
+        out = C.c_double()
+        _lib.check(self._L.iem_eval_trial_scaled(self._h, _ptr(x), _ptr(s), float(obj_scale), _ptr(c), None if defer_obj else C.byref(out)))
+        self.counters.neval_obj += 1
+        self.counters.neval_cons += 1
+        return (None if defer_obj else float(out.value)), c
+
+    def eval_accepted_scaled(self, x, y, s, obj_scale: float, g=None, jac=None, hess=None, obj_weight: float = 1.0):
+        """``grad_scaled(x, obj_scale)``, ``jac_coord_scaled(x, s)`` and ``hess_coord_scaled(x, y, s, obj_weight·obj_scale)`` in
+        ONE launch (``iem_eval_accepted_scaled``): identical bytes to the three calls."""
+        self._chk(x, self.meta.nvar, "x"); self._chk_opt(y, self.meta.ncon, "y"); self._chk_opt(s, self.meta.ncon, "s")
+        g = g if g is not None else self._new(self.meta.nvar)
+        jac = jac if jac is not None else self._new(self.meta.nnzj)
+        hess = hess if hess is not None else self._new(self.meta.nnzh)
+        self._chk(g, self.meta.nvar, "g"); self._chk(jac, self.meta.nnzj, "jac"); self._chk(hess, self.meta.nnzh, "hess")
+        self._sync_stream()
+        if self._sph_n is None:
+            self.scaled_phase_prepare()
+        _lib.check(self._L.iem_eval_accepted_scaled(self._h, _ptr(x), _ptr(y), _ptr(s), float(obj_scale), float(obj_weight),
+                                                    _ptr(g), _ptr(jac), _ptr(hess)))
+        self.counters.neval_grad += 1
+        self.counters.neval_jac += 1
+        self.counters.neval_hess += 1
+        return g, jac, hess
 
     def kktprod(self, x, y, u, v=None, obj_weight: float = 1.0, out_x=None, out_y=None):
         """``(W·u + J(x)ᵀ·v, J(x)·u)`` with ``W = obj_weight·∇²f(x) + Σ y_r·∇²c_r(x)`` from ONE launch (``iem_kktprod``): the
@@ -606,7 +692,7 @@ class ExaModel:
         n = self.param_coord_prepare()
         total = C.c_int32()
         _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0) - (self._kkt_n or 0)
+        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0) - (self._kkt_n or 0) - (self._sph_n or 0)
         return self._kernel_infos(last - n, last)
 
     def param_prepare(self) -> int:

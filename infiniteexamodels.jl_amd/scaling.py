@@ -5,9 +5,13 @@ objective by ``min(1, max_gradient / ‖∇f(x0)‖∞)`` and every constraint r
 then iterate on the scaled functions.  ``gradient_scaling`` computes the factors from ``grad`` and ``jac_row_maxabs`` alone —
 no COO buffer, no structure download, no atomic scatter — and ``ScaledModel`` is the scaled problem behind the evaluation
 surface of ``model.ExaModel``: ``cons`` and ``jac_coord`` come out of the scaled kernels (``cons_scaled`` /
-``jac_coord_scaled``: the factor is applied in front of the store), the Hessian is ``hess_coord(x, y∘s, obj_weight·s_f)``.
+``jac_coord_scaled``: the factor is applied in front of the store), the gradient and the Hessian out of ``grad_scaled`` (the
+reverse sweep seeded with ``s_f``) and ``hess_coord_scaled`` (the row's multiplier ``y∘s`` formed in the kernel), and the
+one-launch solver phases ``eval_trial`` / ``eval_accepted`` are the scaled phase kernels (``eval_trial_scaled`` /
+``eval_accepted_scaled``): one launch per phase, as for the unscaled model.  A model that lacks the scaled gradient / Hessian
+entry points (a host stand-in) gets the composed forms ``grad(x)·s_f`` and ``hess_coord(x, y∘s, obj_weight·s_f)``.
 
-Not scaled here: the variables (x scaling), and the one-launch solver phases (``eval_trial`` / ``eval_accepted``).
+Not scaled here: the variables (x scaling).
 """
 from __future__ import annotations
 
@@ -68,6 +72,8 @@ class ScaledModel:
         return self.inner.obj_device(x, out).mul_(self.obj_scale)
 
     def grad(self, x, g=None):
+        if hasattr(self.inner, "grad_scaled"):
+            return self.inner.grad_scaled(x, self.obj_scale, g)
         return self.inner.grad(x, g).mul_(self.obj_scale)
 
     def cons(self, x, c=None):
@@ -77,7 +83,21 @@ class ScaledModel:
         return self.inner.jac_coord_scaled(x, self.con_scale, vals)
 
     def hess_coord(self, x, y, vals=None, obj_weight: float = 1.0):
+        if hasattr(self.inner, "hess_coord_scaled"):
+            return self.inner.hess_coord_scaled(x, y, self.con_scale, vals, obj_weight=obj_weight * self.obj_scale)
         return self.inner.hess_coord(x, y * self.con_scale, vals, obj_weight=obj_weight * self.obj_scale)
+
+    def eval_trial(self, x, c=None, defer_obj: bool = False):
+        """``(s_f·f(x), s∘c(x))`` in ONE launch; ``defer_obj``: ``(None, c)`` at once, the model's ``obj_end`` collects the
+        scaled value later."""
+        return self.inner.eval_trial_scaled(x, self.con_scale, self.obj_scale, c, defer_obj)
+
+    def eval_accepted(self, x, y, g=None, jac=None, hess=None, obj_weight: float = 1.0):
+        """Gradient, Jacobian and Hessian of the scaled problem in ONE launch (``y``: the scaled problem's multipliers)."""
+        return self.inner.eval_accepted_scaled(x, y, self.con_scale, self.obj_scale, g, jac, hess, obj_weight)
+
+    def obj_end(self) -> float:
+        return self.inner.obj_end()
 
     def jac_hess_coord(self, x, y, jac=None, hess=None, obj_weight: float = 1.0):
         return self.jac_coord(x, jac), self.hess_coord(x, y, hess, obj_weight)
