@@ -651,6 +651,43 @@ int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, doub
 /* HIP source of the two finishing kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_kkt_residual_source(char **out_src, uint64_t *out_key);
 
+/* A PER-ROW diagonal in the constraint block — what an interior-point method with eliminated slacks assembles (Sigma_s^-1 on its
+ * inequality rows, another value per row at every iterate) — and the residual / refinement over several columns:
+ *     K = [W + diag(sigma) + delta_w I, J'; J, −diag(dcon + delta_c)]          (delta_c is added on EVERY row, as Ipopt's is)
+ * d_dcon: ncon doubles on the device, or NULL = zeros; ignored when ncon == 0.  Its entries are NOT inspected — none of the
+ * calls synchronises —: a negative or NaN entry goes into the matrix (and into the residuals) as it is.
+ * iem_kkt_assemble_diag: iem_kkt_assemble with the per-row source −(dcon[row] + delta_c) (one rounded add, then the negation;
+ * every other source and the summation order are unchanged), in every mode of the object (1-D chain, lanes with a dense border
+ * in both border modes, hubs); d_dcon == NULL is iem_kkt_assemble itself.  Invalidates the factorisation.
+ * iem_kkt_residual_diag: r_u = rhs_u − K sol_u for nrhs columns (column u at d + u ld; ld >= nvar + ncon, the entries between the
+ * columns are neither read nor written): one iem_kktprod per column into a workspace plane, then ONE finishing launch per slab
+ * of 8 columns that computes, without contraction and in this order,
+ *     r_x = rhs_x − (p_x + (sigma + delta_w) ∘ sol_x),     d = dcon + delta_c (delta_c alone for d_dcon == NULL),  r_y = rhs_y − (p_y − d ∘ sol_y)
+ * and — d_norms != NULL — d_norms[u] = max_i |r_u[i]| as iem_kkt_residual forms it (integer maximum on the bit patterns: a NaN
+ * gives a NaN, order-independent).  With nrhs = 1 and d_dcon == NULL: the bits of iem_kkt_residual.  Column u carries the bits of
+ * the call on that column alone.  d_r may be d_rhs when ld_r == ld_rhs; every other overlap of d_r, d_sol, d_rhs, d_norms —
+ * judged on the whole extents [d, d + (nrhs − 1) ld + n), as for iem_kkt_solve_many — is IEM_E_ARG.  A sharded model handle is
+ * refused where iem_kktprod refuses it.
+ * iem_kkt_solve_refined_diag: iem_kkt_solve_many, then `steps` times: the residuals, iem_kkt_solve_many on them, ONE add kernel
+ * (sol_u += dsol_u).  d_norms ((steps + 1) nrhs doubles or NULL): d_norms[i nrhs + u] = max |r_u| in front of step i, the last row
+ * the one behind the last step (with d_norms == NULL that last residual is not formed).  steps >= 0.  No read-back of a norm and
+ * no early exit: as asynchronous and capturable as iem_kkt_solve_many is for the object's mode, after a first call.  d_sol may
+ * not overlap d_rhs (nor d_norms either).  With nrhs = 1 and d_dcon == NULL: the bits of iem_kkt_solve_refined.
+ * Workspace: 3 (nvar + ncon) doubles per column of ONE slab (8 columns — a multiple of every chunk width of iem_kkt_solve_many),
+ * owned by the object: allocated by the first call, freed by iem_kkt_destroy; it does not grow with nrhs. */
+int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma /* nvar | NULL */,
+                          const double *d_dcon /* ncon | NULL */, double delta_w, double delta_c);
+int iem_kkt_residual_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma,
+                          const double *d_dcon, double delta_w, double delta_c, int nrhs,
+                          const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol,
+                          double *d_r, int64_t ld_r, double *d_norms /* nrhs | NULL */);
+int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma,
+                               const double *d_dcon, double delta_w, double delta_c, int nrhs,
+                               const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol,
+                               int steps, double *d_norms /* (steps + 1)·nrhs | NULL; entry [i·nrhs + u] */);
+/* HIP source of kkt_gather_d / kkt_residual_dm / kkt_axpy_m and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_kkt_diag_source(char **out_src, uint64_t *out_key);
+
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache

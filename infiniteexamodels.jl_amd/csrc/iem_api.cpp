@@ -44,6 +44,9 @@ static const char *kKktManySource =   // the multi-column solve kernels, behind 
 static const char *kKktResidualSource =   // the finishing kernels of iem_kkt_residual / iem_kkt_solve_refined: a code object of their own
 #include "iem_kkt_residual_device_h.inc"
     ;
+static const char *kKktDiagSource =       // the per-row diagonal's gather and the multi-column residual / add (iem_kkt_*_diag): a code object of its own
+#include "iem_kkt_diag_device_h.inc"
+    ;
 static const char *kKktBorderSource =     // the dense border on the device (kkt_border_ldl / kkt_border_solve): a code object of its own
 #include "iem_kkt_border_device_h.inc"
     ;
@@ -279,6 +282,10 @@ struct iem_model {
   double obj_factor = 1.0;
   hipModule_t kres_mod = nullptr;
   hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
+  // the kernels of iem_kkt_assemble_diag / iem_kkt_residual_diag / iem_kkt_solve_refined_diag (csrc/iem_kkt_diag_device.h; loaded
+  // by the first of those calls)
+  hipModule_t kdg_mod = nullptr;
+  hipFunction_t kdg_gather = nullptr, kdg_res = nullptr, kdg_axpy = nullptr;
   // the dense border on the device (csrc/iem_kkt_border_device.h; loaded by the first call that needs it).  `kb_part`: the column
   // sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   hipModule_t kb_mod = nullptr;
@@ -1302,6 +1309,7 @@ int iem_destroy(iem_model *m) {
   free_program(m->sph.code);
   if (m->d_sph_partials) hipFree(m->d_sph_partials);
   if (m->kres_mod) hipModuleUnload(m->kres_mod);
+  if (m->kdg_mod) hipModuleUnload(m->kdg_mod);
   if (m->kb_mod) hipModuleUnload(m->kb_mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -3138,6 +3146,7 @@ struct iem_kkt {
   double *m_r = nullptr, *m_z = nullptr, *m_rBp = nullptr, *m_xB = nullptr, *m_part = nullptr;      // iem_kkt_solve_many: ONE chunk of columns, allocated by its first call
   std::vector<double> Gs;        // the border's Schur complement (host), set by iem_kkt_factor
   double *w_ref = nullptr;       // iem_kkt_residual / iem_kkt_solve_refined: p, r, dsol (3 (nvar + ncon) doubles), allocated by the first call
+  double *w_diag = nullptr;      // iem_kkt_residual_diag / iem_kkt_solve_refined_diag: p | r | dsol for ONE slab of columns, allocated by the first call
   int border_mode = 0;           // iem_kkt_set_border: 0 the border on the host, 1 on the device (d_F, d_piv: its factors)
   double *d_F = nullptr;
   int32_t *d_piv = nullptr;
@@ -3568,7 +3577,7 @@ int iem_kkt_destroy(iem_kkt *k) {
   DevGuard dg_(k->m->device);
   hub_free(k);
   for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_r, (void *)k->d_z, (void *)k->d_rBp, (void *)k->d_xB, (void *)k->d_part,
-                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref, (void *)k->d_F, (void *)k->d_piv,
+                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref, (void *)k->w_diag, (void *)k->d_F, (void *)k->d_piv,
                   (void *)k->d_rows, (void *)k->d_cols, (void *)k->d_dest, (void *)k->d_on, (void *)k->d_pos, (void *)k->d_border, (void *)k->d_bloc, (void *)k->d_info,
                   (void *)k->d_seg, (void *)k->d_perm})
     if (p) hipFree(p);
@@ -3884,6 +3893,136 @@ int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs
     if ((rc = chain(nr, 1))) return rc;
     if ((rc = move(Mv{sol, k->m_r, k->d_on, k->d_pos, 0, (long long)ld_sol, (long long)pl, nr}, k->n_on))) return rc;
     if (L.n_border && (rc = move(Mv{sol, k->m_xB, k->d_border, k->d_bloc, 0, (long long)ld_sol, (long long)ne, nr}, L.n_border))) return rc;
+  }
+  return IEM_OK;
+}
+
+/* ---- a per-row diagonal in the constraint block, and the residual / refinement over several columns ----------------------------
+ * K = [W + diag(sigma) + delta_w I, J'; J, -diag(dcon + delta_c)]  (csrc/iem_kkt_diag_device.h) */
+namespace {
+constexpr int KKT_DIAG_SLAB = 8;      // columns per pass: a multiple of every chunk width of the multi-column kernels (kkt_many_width: 2 or 4)
+std::string kkt_diag_source() {
+  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktDiagSource;
+}
+// the code object and — `workspace` — the planes {p, r, dsol} of one slab: the synchronous part of the first call
+int kkt_diag_setup(iem_kkt *k, bool workspace) {
+  iem_model *m = k->m;
+  if (!m->kdg_res) {
+    int rc = load_source(m, kkt_diag_source(), &m->kdg_mod);
+    if (rc) return rc;
+    HIP_TRY(hipModuleGetFunction(&m->kdg_gather, m->kdg_mod, "kkt_gather_d"));
+    HIP_TRY(hipModuleGetFunction(&m->kdg_axpy, m->kdg_mod, "kkt_axpy_m"));
+    HIP_TRY(hipModuleGetFunction(&m->kdg_res, m->kdg_mod, "kkt_residual_dm"));
+  }
+  if (workspace && !k->w_diag) HIP_TRY(hipMalloc((void **)&k->w_diag, (size_t)std::max<int64_t>(3 * KKT_DIAG_SLAB * (k->L.nvar + k->L.ncon), 1) * 8));
+  return IEM_OK;
+}
+int kkt_launch_cols(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, int cols) {
+  if (grid <= 0 || cols <= 0) return IEM_OK;
+  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, (unsigned)cols, 1, 256, 1, 1, 0, m->stream, nullptr, cfg));
+  return IEM_OK;
+}
+// the whole extent [d, d + (nrhs - 1) ld + n) of a set of columns
+int64_t kkt_extent(int nrhs, int64_t ld, int64_t n) { return (int64_t)(nrhs - 1) * ld + n; }
+// the residuals of nr <= KKT_DIAG_SLAB columns: one iem_kktprod per column into the slab's p planes, then ONE launch
+int kkt_residual_slab(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c,
+                      int nr, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, double *d_r, int64_t ld_r, double *d_norms) {
+  iem_model *m = k->m;
+  const int64_t nvar = k->L.nvar, ncon = k->L.ncon, n = nvar + ncon;
+  double *p = k->w_diag;
+  int rc;
+  for (int u = 0; u < nr; ++u) {
+    const double *s = d_sol + (int64_t)u * ld_sol;
+    double *pu = p + (int64_t)u * n;
+    if ((rc = iem_kktprod(m, d_x, d_y, obj_weight, s, ncon ? s + nvar : nullptr, pu, ncon ? pu + nvar : nullptr))) return rc;
+  }
+  if (d_norms) HIP_TRY(hipMemsetAsync(d_norms, 0, (size_t)nr * 8, m->stream));
+  struct { const double *p, *rhs, *sol, *sigma, *dcon; double *r; unsigned long long *norms; double dw, dc; long long nvar, n, ld_p, ld_rhs, ld_sol, ld_r; } A{
+      p, d_rhs, d_sol, d_sigma, ncon ? d_dcon : nullptr, d_r, (unsigned long long *)d_norms, delta_w, delta_c, (long long)nvar, (long long)n, (long long)n,
+      (long long)ld_rhs, (long long)ld_sol, (long long)ld_r};
+  return kkt_launch_cols(m, m->kdg_res, &A, sizeof A, kkt_stream_grid(n), nr);
+}
+}  // namespace
+
+int iem_kkt_diag_source(char **out_src, uint64_t *out_key) {
+  const std::string s = kkt_diag_source();
+  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
+  if (out_key) *out_key = iem::fnv1a64(s);
+  return IEM_OK;
+}
+
+int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c) {
+  if (!k || (!d_hess && k->n_h) || (!d_jac && k->n_j)) return fail(IEM_E_ARG, "null argument");
+  if (!d_dcon || k->L.ncon == 0) return iem_kkt_assemble(k, d_hess, d_jac, d_sigma, delta_w, delta_c);      // no per-row part: kkt_gather as it is
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc = kkt_diag_setup(k, false);
+  if (rc) return rc;
+  const iem::KktLayout &L = k->L;
+  HIP_TRY(hipMemsetAsync(k->d_flat, 0, (size_t)L.total() * 8, m->stream));
+  struct { double *flat; const long long *dest; const unsigned *seg, *perm; const double *hess, *jac, *sigma, *dcon; double dw, dc; long long n_dest, n_h, n_j, n_var, n_con; } A{
+      k->d_flat, k->d_dest, k->d_seg, k->d_perm, d_hess, d_jac, d_sigma, d_dcon, delta_w, delta_c, (long long)k->n_dest, (long long)k->n_h, (long long)k->n_j,
+      (long long)L.nvar, (long long)L.ncon};
+  k->factored = false;
+  return kkt_launch_raw(m, m->kdg_gather, &A, sizeof A, (k->n_dest + 255) / 256, 256);
+}
+
+int iem_kkt_residual_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w,
+                          double delta_c, int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, double *d_r, int64_t ld_r, double *d_norms) {
+  if (!k || !d_rhs || !d_sol || !d_r) return fail(IEM_E_ARG, "null argument");
+  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_residual_diag: nrhs must be at least 1");
+  iem_model *m = k->m;
+  const int64_t n = k->L.nvar + k->L.ncon;
+  if (ld_rhs < n || ld_sol < n || ld_r < n) return fail(IEM_E_ARG, "iem_kkt_residual_diag: a leading dimension is shorter than nvar + ncon");
+  const int64_t er = kkt_extent(nrhs, ld_r, n), eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n);
+  if (kkt_overlap(d_r, er, d_sol, es) || (!(d_r == d_rhs && ld_r == ld_rhs) && kkt_overlap(d_r, er, d_rhs, eb)) || kkt_overlap(d_r, er, d_norms, nrhs) ||
+      kkt_overlap(d_norms, nrhs, d_sol, es) || kkt_overlap(d_norms, nrhs, d_rhs, eb))
+    return fail(IEM_E_ARG, "iem_kkt_residual_diag: overlap — d_r overlaps d_sol or d_rhs (allowed: d_r == d_rhs with ld_r == ld_rhs), or d_norms lies inside the vectors");
+  DevGuard dg_(m->device);
+  int rc = kkt_diag_setup(k, true);
+  if (rc) return rc;
+  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
+    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
+    if ((rc = kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, d_rhs + (int64_t)c0 * ld_rhs, ld_rhs, d_sol + (int64_t)c0 * ld_sol, ld_sol,
+                                d_r + (int64_t)c0 * ld_r, ld_r, d_norms ? d_norms + c0 : nullptr)))
+      return rc;
+  }
+  return IEM_OK;
+}
+
+int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w,
+                               double delta_c, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol, int steps, double *d_norms) {
+  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
+  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: nrhs must be at least 1");
+  if (steps < 0) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: steps must not be negative");
+  const int64_t n = k->L.nvar + k->L.ncon;
+  if (ld_rhs < n || ld_sol < n) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: a leading dimension is shorter than nvar + ncon");
+  const int64_t eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n), en = (int64_t)(steps + 1) * nrhs;
+  if (kkt_overlap(d_sol, es, d_rhs, eb) || kkt_overlap(d_norms, en, d_sol, es) || kkt_overlap(d_norms, en, d_rhs, eb))
+    return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: overlap — d_sol, d_rhs and d_norms may not overlap");
+  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc = kkt_diag_setup(k, true);
+  if (rc) return rc;
+  double *r = k->w_diag + (int64_t)KKT_DIAG_SLAB * n, *dsol = k->w_diag + 2 * (int64_t)KKT_DIAG_SLAB * n;
+  // slab by slab (the columns do not interact, and the chunks of iem_kkt_solve_many inside a slab are those of the whole set)
+  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
+    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
+    const double *rhs = d_rhs + (int64_t)c0 * ld_rhs;
+    double *sol = d_sol + (int64_t)c0 * ld_sol;
+    auto residual = [&](int i) {
+      return kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, rhs, ld_rhs, sol, ld_sol, r, n, d_norms ? d_norms + (int64_t)i * nrhs + c0 : nullptr);
+    };
+    if ((rc = iem_kkt_solve_many(k, nr, rhs, ld_rhs, sol, ld_sol))) return rc;
+    for (int i = 0; i < steps; ++i) {
+      if ((rc = residual(i))) return rc;
+      if ((rc = iem_kkt_solve_many(k, nr, r, n, dsol, n))) return rc;
+      struct { double *sol; const double *d; long long n, ld_s, ld_d; } A{sol, dsol, (long long)n, (long long)ld_sol, (long long)n};
+      if ((rc = kkt_launch_cols(m, m->kdg_axpy, &A, sizeof A, kkt_stream_grid(n), nr))) return rc;
+    }
+    if (d_norms && (rc = residual(steps))) return rc;
   }
   return IEM_OK;
 }

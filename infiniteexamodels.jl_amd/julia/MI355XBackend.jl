@@ -406,6 +406,40 @@ function solve_refined!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{F
                 s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), s.delta_w, s.delta_c, dptr(rhs), dptr(sol), steps, pn))
     return sol
 end
+# A PER-ROW diagonal in the constraint block (an interior-point method with eliminated slacks: Σs⁻¹ on the inequality rows):
+# K = [W + Σ + δw·I, Jᵀ; J, −diag(dcon + δc)], `dcon` a device vector of ncon entries (nothing: zeros — iem_kkt_assemble itself).
+# The entries are not inspected.  UNEXECUTED, like the rest of this file.
+dcon_ptr(dcon) = dcon === nothing ? Ptr{Float64}(C_NULL) : dptr(dcon)
+function factorize_diag!(s::ChainKKTSolver, dcon)
+    check(ccall((:iem_kkt_assemble_diag, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                s.k, dptr(s.hess), dptr(s.jac), dptr(s.sigma), dcon_ptr(dcon), s.delta_w, s.delta_c))
+    check(ccall((:iem_kkt_factor, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Int64}), s.k, s.inertia))
+    return s
+end
+# R = RHS − K·SOL column for column (iem_kkt_residual_diag: one operator launch per column, one finishing launch per eight);
+# `norms`: a device vector of size(RHS, 2) entries that receives max |r| per column, or nothing.  R may be RHS itself.
+function residual_diag!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{Float64}, dcon, RHS::ROCMatrix{Float64}, SOL::ROCMatrix{Float64},
+                        R::ROCMatrix{Float64}; obj_weight = 1.0, norms = nothing)
+    pn = norms === nothing ? Ptr{Float64}(C_NULL) : dptr(norms)
+    check(ccall((:iem_kkt_residual_diag, LIBIEM), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                 Ptr{Float64}, Int64, Ptr{Float64}),
+                s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), dcon_ptr(dcon), s.delta_w, s.delta_c, size(RHS, 2), dptr(RHS), stride(RHS, 2),
+                dptr(SOL), stride(SOL, 2), dptr(R), stride(R, 2), pn))
+    return R
+end
+# SOL = K⁻¹ RHS with `steps` steps of refinement per column (iem_kkt_solve_refined_diag: iem_kkt_solve_many, then residuals, solves
+# and one add per step); `norms`: a device matrix size(RHS, 2) x (steps + 1) — column i the norms in front of step i — or nothing
+function solve_refined_diag!(s::ChainKKTSolver, x::ROCVector{Float64}, y::ROCVector{Float64}, dcon, RHS::ROCMatrix{Float64}, SOL::ROCMatrix{Float64};
+                             obj_weight = 1.0, steps = 1, norms = nothing)
+    pn = norms === nothing ? Ptr{Float64}(C_NULL) : dptr(norms)
+    check(ccall((:iem_kkt_solve_refined_diag, LIBIEM), Cint,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                 Cint, Ptr{Float64}),
+                s.k, dptr(x), dptr(y), obj_weight, dptr(s.sigma), dcon_ptr(dcon), s.delta_w, s.delta_c, size(RHS, 2), dptr(RHS), stride(RHS, 2),
+                dptr(SOL), stride(SOL, 2), steps, pn))
+    return SOL
+end
 # A dense border (first-stage variables, u(t) of a laned grid) on the device: mode 1 factorises its Schur complement with a
 # Bunch–Kaufman LDL' in one workgroup and solves it there — solve! / solve_refined! then contain no synchronisation and can be
 # captured; mode 0 (the default) keeps it on the host.  A no-op for models without a dense border.

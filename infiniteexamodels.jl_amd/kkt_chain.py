@@ -307,18 +307,26 @@ class MatrixFreeKKT:
     ``matvec(z)`` is ONE generated launch (``model.kktprod``: ``W·z_x + Jᵀ·z_y`` and ``J·z_x``) plus the diagonal terms — no
     COO values, no CSR copy of K, nothing to refresh when the point moves except the three references held here.
     ``residual(rhs, sol)`` is ``rhs − K·sol``.  ``ChainKKT.solve(..., operator=...)`` refines with it in place of the CSR
-    product.  The C-ABI's ``iem_kkt_residual`` / ``iem_kkt_solve_refined`` do the same behind one call."""
+    product.  The C-ABI's ``iem_kkt_residual`` / ``iem_kkt_solve_refined`` do the same behind one call.
 
-    def __init__(self, model, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c: float = 0.0):
+    ``delta_c``: a float, or a device tensor of ``ncon`` entries — the constraint block is then ``−diag(delta_c)``, the per-row
+    diagonal of an interior-point method with eliminated slacks (``iem_kkt_assemble_diag``'s ``dcon + delta_c``, already added)."""
+
+    def __init__(self, model, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c=0.0):
         self.model = model
         self.nvar, self.ncon = int(model.meta.nvar), int(model.meta.ncon)
         self.n = self.nvar + self.ncon
         self.update(x, y, obj_weight, sigma, delta_w, delta_c)
 
-    def update(self, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c: float = 0.0):
+    def update(self, x, y, obj_weight: float = 1.0, sigma=None, delta_w: float = 0.0, delta_c=0.0):
         """Move the operator to another point / regularisation (references are kept, nothing is evaluated)."""
         self.x, self.y, self.obj_weight = x, y, float(obj_weight)
-        self.sigma, self.delta_w, self.delta_c = sigma, float(delta_w), float(delta_c)
+        if hasattr(delta_c, "dim"):
+            if delta_c.dim() != 1 or delta_c.numel() != self.ncon:
+                raise ValueError("delta_c: a float or a tensor of ncon entries")
+        else:
+            delta_c = float(delta_c)
+        self.sigma, self.delta_w, self.delta_c = sigma, float(delta_w), delta_c
         return self
 
     def matvec(self, z):
@@ -336,6 +344,119 @@ class MatrixFreeKKT:
     def residual(self, rhs, sol):
         """``rhs − K·sol``"""
         return rhs - self.matvec(sol)
+
+
+class KKTObject:
+    """The chain solver as the ONE object of the C-ABI (``iem_kkt_create``): what a host without this package binds, held from
+    Python.  The library analyses the model, owns the blocks and the workspaces, and takes the ``hess_coord!`` / ``jac_coord!``
+    value buffers as they are — no CSR matrix in between (:class:`ChainKKT` / :class:`HubChainKKT` are the Python-held forms
+    of the same pipeline, fed by ``kkt.KKTSystem``).
+
+    ``assemble(hess, jac, sigma, delta_w, delta_c, dcon, at)`` sets ``K = [W + diag(sigma) + delta_w·I, Jᵀ; J, −diag(dcon +
+    delta_c)]`` (``dcon``: a device tensor of ``ncon`` entries or ``None``); ``at = (x, y, obj_weight)`` is the point the values were
+    evaluated at — remembered, because the matrix-free residuals of ``residual`` and ``solve(refine > 0)`` are formed there.
+    ``factor()`` returns ``(positive, negative, doubtful)``; ``solve(rhs, refine)`` follows ``ChainKKT.solve``'s convention."""
+
+    def __init__(self, model, group: int = 0):
+        import torch
+        self._torch = torch
+        self.model = model
+        self._k = C.c_void_p()
+        _lib.check(model._L.iem_kkt_create(model._h, int(group), C.byref(self._k)))
+        info = _lib.KktInfo()
+        _lib.check(model._L.iem_kkt_info(self._k, C.byref(info)))
+        self.info = {name: int(getattr(info, name)) for name, _ in _lib.KktInfo._fields_}
+        self.nvar, self.ncon = int(model.meta.nvar), int(model.meta.ncon)
+        self.n = self.nvar + self.ncon
+        self._at = None
+        self._sigma = self._dcon = None
+        self._dw = self._dc = 0.0
+
+    @staticmethod
+    def _p(a):
+        return C.c_void_p(a.data_ptr()) if a is not None else None
+
+    def _handle(self):
+        if self._k is None:
+            raise _lib.IemError("KKTObject: closed")
+        self.model._sync_stream()
+        return self.model._L, self._k
+
+    def set_border(self, mode: int):
+        """Where a dense border is factorised and solved: 0 on the host, 1 on the device (``iem_kkt_set_border``)."""
+        L, k = self._handle()
+        _lib.check(L.iem_kkt_set_border(k, int(mode)))
+        return self
+
+    def assemble(self, hess, jac, sigma=None, delta_w: float = 0.0, delta_c: float = 0.0, dcon=None, at=None):
+        L, k = self._handle()
+        if dcon is not None and (dcon.dim() != 1 or dcon.numel() != self.ncon or not dcon.is_contiguous()):
+            raise ValueError("dcon: a contiguous tensor of ncon entries")
+        if at is not None:
+            x, y, w = at
+            at = (x, y, float(w))
+        _lib.check(L.iem_kkt_assemble_diag(k, self._p(hess), self._p(jac), self._p(sigma), self._p(dcon), float(delta_w), float(delta_c)))
+        self._sigma, self._dcon, self._dw, self._dc, self._at = sigma, dcon, float(delta_w), float(delta_c), at
+        return self
+
+    def factor(self):
+        """``(positive, negative, doubtful)`` pivots of ``K``; synchronises (``iem_kkt_factor``)."""
+        L, k = self._handle()
+        inertia = (C.c_int64 * 3)()
+        _lib.check(L.iem_kkt_factor(k, inertia))
+        return int(inertia[0]), int(inertia[1]), int(inertia[2])
+
+    def _columns(self, a):
+        """``(K, n)`` contiguous rows of a 1-D or ``(n, K)`` tensor."""
+        if a.dim() == 1:
+            return a.contiguous().view(1, -1)
+        return a.t().contiguous()
+
+    def _point(self, what):
+        if self._at is None:
+            raise ValueError(f"KKTObject.{what}: the residuals are formed matrix-free at the point of the values — assemble(..., at=(x, y, obj_weight))")
+        return self._at
+
+    def residual(self, rhs, sol):
+        """``rhs − K·sol`` at the remembered point (``iem_kkt_residual_diag``): 1-D, or ``(n, K)`` with the result in that shape."""
+        x, y, w = self._point("residual")
+        B, X = self._columns(rhs), self._columns(sol)
+        R = self._torch.empty_like(B)
+        L, k = self._handle()
+        _lib.check(L.iem_kkt_residual_diag(k, self._p(x), self._p(y), w, self._p(self._sigma), self._p(self._dcon), self._dw, self._dc, B.shape[0],
+                                           self._p(B), self.n, self._p(X), self.n, self._p(R), self.n, None))
+        return R[0] if rhs.dim() == 1 else R.t()
+
+    def solve(self, rhs, refine: int = 0):
+        """``K x = rhs`` with the current factors: ``rhs`` 1-D, or ``(n, K)`` with columns of any stride (a contiguous ``(K, n)``
+        buffer inside, ``iem_kkt_solve_many``) and the same shape out.  ``refine`` steps of refinement with the matrix-free
+        residual (``iem_kkt_solve_refined_diag``) need the point: ``assemble(..., at=...)``."""
+        refine = int(refine)
+        if refine < 0:
+            raise ValueError("refine must not be negative")
+        if refine:
+            x, y, w = self._point("solve(refine > 0)")
+        B = self._columns(rhs)
+        X = self._torch.empty_like(B)
+        L, k = self._handle()
+        if refine:
+            _lib.check(L.iem_kkt_solve_refined_diag(k, self._p(x), self._p(y), w, self._p(self._sigma), self._p(self._dcon), self._dw, self._dc, B.shape[0],
+                                                    self._p(B), self.n, self._p(X), self.n, refine, None))
+        else:
+            _lib.check(L.iem_kkt_solve_many(k, B.shape[0], self._p(B), self.n, self._p(X), self.n))
+        return X[0] if rhs.dim() == 1 else X.t()
+
+    def close(self):
+        if self._k is not None:
+            _lib.check(self.model._L.iem_kkt_destroy(self._k))
+            self._k = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class ChainKKT:
