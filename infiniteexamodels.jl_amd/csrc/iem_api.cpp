@@ -166,26 +166,42 @@ struct CodeObject {
   std::vector<int> launchable[iem::KK_LAST + 1];
 };
 
+// Everything a program owns on a handle: the code object and the device buffers its kernels and their follow-ups use.  The
+// model's own program, the tuner's second object and every derived program (kDerived) are instances; release_program
+// frees one, whatever of it exists.
+struct LoadedProgram : CodeObject {
+  double *d_red[iem::KK_COUNT] = {};         // per scatter kind: parked shared-entry values + tickets (iem_shared_*)
+  long long *d_axis[iem::KK_COUNT] = {};     // per scatter kind: table of its axis sums (iem_axis_sum_kernel)
+  long long *d_gather[iem::KK_COUNT] = {};   // per scatter kind: dest | seg | perm of its plan-driven gather (iem_gather_sum_kernel)
+  std::vector<std::pair<int64_t, int64_t>> zero_ranges[iem::KK_COUNT];  // per scatter kind: [lo, hi) of the output its kernels do not overwrite
+  double *d_partials = nullptr;              // the partials and ticket words of its objective kernels (programs that have some)
+  // a derived program: set up by its first call or its prepare call; a failure that is remembered is reported by every later call
+  bool tried = false;
+  int rc = IEM_OK;
+  std::string err;
+};
+
+// The derived programs of a handle, in the order iem_kernel_info lists their kernels behind the model's own (kDerived has
+// a row for each)
+enum Derived { D_PAR, D_ADJ, D_TH2, D_PC, D_LAG, D_SCL, D_KKT, D_SPH, D_COUNT };
+
 struct iem_model {
   iem::Model model;
-  CodeObject code;      // the model's program
+  LoadedProgram code;   // the model's program
   iem::Options opt;     // this handle's generator options (process defaults + iem_create_opts overrides)
   int poll_obj = 1;
   int device = 0;
   hipStream_t stream = nullptr;
   hipFunction_t fn_struct = nullptr, fn_csr = nullptr, fn_csr32 = nullptr, fn_axis = nullptr, fn_spmv = nullptr, fn_spmv_long = nullptr;
-  long long *d_axis[iem::KK_COUNT] = {};
-  long long *d_gather[iem::KK_COUNT] = {};   // per scatter kind: dest | seg | perm of its plan-driven gather (iem_gather_sum_kernel)
-  hipFunction_t fn_gather = nullptr;   // per scatter kind: table of its axis sums (iem_axis_sum_kernel)
-  double *d_theta = nullptr, *d_partials = nullptr;
-  double *d_red[iem::KK_COUNT] = {};   // per scatter kind: parked shared-entry values + tickets (iem_shared_*)
+  hipFunction_t fn_gather = nullptr;
+  double *d_theta = nullptr;
   // Second code object of jac_coord!/hess_coord! with a larger LDS staging batch (lds_slots = 48: one 96-KB
   // workgroup per CU, a third of the concurrently open store streams) and the tuner that picks, per kind and
   // per OUTPUT BUFFER, whichever of the two is faster there — how a COO buffer's physical pages fall onto the HBM
   // channels decides that, and both variants write identical bytes, so the first twenty calls into a
   // buffer run ten with one, ten with the other, under HIP events, and every call is a valid evaluation.
 #define IEM_TUNE_CALLS 20   // measured calls per output buffer: a block of ten per variant
-  CodeObject alt;      // loaded (alt.mod set) only where the tuner runs
+  LoadedProgram alt;   // loaded (alt.mod set) only where the tuner runs; jac_coord! / hess_coord! only, so it owns no buffer
   struct Tune {
     const void *out = nullptr;   // the buffer the decision belongs to
     int calls = 0, choice = -1;  // choice: -1 undecided, 0 default, 1 alt
@@ -236,50 +252,16 @@ struct iem_model {
   std::map<int, void *> d_arrays;  // model array id -> device copy
   std::vector<double> theta_host;
   bool jit = false;
-  std::vector<std::pair<int64_t, int64_t>> zero_ranges[iem::KK_COUNT];  // per scatter kind: [lo, hi) of the output its kernels do not overwrite
-  // The parameter kinds (iem_jpprod / iem_jptprod / iem_hpprod; Options::param_kinds): a program of their own with its own
-  // scatter buffers, generated and loaded by the first such call — the model's program and its cache key do not know of it.
-  struct ParamKinds {
-    bool tried = false;
-    int rc = IEM_OK;
-    std::string err;
-    CodeObject code;
-    double *d_red[iem::KK_COUNT] = {};
-    long long *d_axis[iem::KK_COUNT] = {}, *d_gather[iem::KK_COUNT] = {};
-  } par;
-  // the adjoint parameter kind (iem_hptprod; param_kinds = 2): a third program, set up in the same way — the source and the
-  // key of `par` do not know of it either
-  ParamKinds adj;
-  // the θθ kind (iem_hppprod; param_kinds = 3): a fourth program, set up by its own first call or by iem_hppprod_prepare —
-  // iem_param_prepare does not know of it
-  ParamKinds th2;
-  // the explicit blocks in COO (iem_jacp_coord / iem_hessp_coord; param_kinds = 4): a fifth program, set up by its own first
-  // call or by iem_param_coord_prepare — the other prepare calls do not know of it.  `pc_view`: the parameter view with the
-  // blocks' layout (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.
-  // `d_pc_spare`: where a block the caller passed NULL for is written when it is not empty (allocated by the first such call)
-  ParamKinds pc;
-  // the residual program (iem_lagrad / iem_eval_residual; param_kinds = 5, over the plain model): a sixth program, set up by
-  // its own first call or by iem_lagrad_prepare — the other prepare calls do not know of it.  `d_lag_partials`: the partials
-  // and ticket words of ITS objective kernels (the model's own keep theirs)
-  ParamKinds lag;
-  double *d_lag_partials = nullptr;
-  // the scaled program (iem_jac_rowmax / iem_cons_scaled / iem_jac_coord_scaled; scaled_kinds = 1, over the plain model): a
-  // seventh program, set up by its own first call or by iem_scaled_prepare — the other prepare calls do not know of it
-  ParamKinds scl;
-  // the KKT operator (iem_kktprod; kkt_kinds = 1, over the plain model): an eighth program, set up by its own first call or by
-  // iem_kktprod_prepare — the other prepare calls do not know of it.  `d_kkt_zero`: ncon zeros, the dual direction of a call
-  // with d_v == NULL.  `kres_*`: the finishing kernels of iem_kkt_residual (loaded by its first call)
-  ParamKinds kkt;
+  // The derived programs (kDerived), each over its own generator options, with its own source, cache key and buffers: generated
+  // and loaded by the first call that needs it or by its prepare call — the model's program and its cache key do not know of them.
+  LoadedProgram derived[D_COUNT];
+  // `d_kkt_zero`: ncon zeros, the dual direction of an iem_kktprod call with d_v == NULL
   double *d_kkt_zero = nullptr;
-  // the scaled solver phases (iem_eval_trial_scaled / iem_eval_accepted_scaled and their members; scaled_phase_kinds = 1, over
-  // the plain model): a ninth program, set up by its own first call or by iem_scaled_phase_prepare — the other prepare calls do
-  // not know of it.  Its gradient's zero ranges, reduction buffer, axis sums and gather plan are its own (ParamKinds), and
-  // `d_sph_partials` the partials and ticket words of ITS objective kernels.  `obj_factor`: what iem_obj_end multiplies the
-  // pending objective value with when `obj_scaled` (set by iem_eval_trial_scaled, cleared by every arm)
-  ParamKinds sph;
-  double *d_sph_partials = nullptr;
+  // `obj_factor`: what iem_obj_end multiplies the pending objective value with when `obj_scaled` (set by
+  // iem_eval_trial_scaled, cleared by every arm)
   bool obj_scaled = false;
   double obj_factor = 1.0;
+  // `kres_*`: the finishing kernels of iem_kkt_residual (loaded by its first call)
   hipModule_t kres_mod = nullptr;
   hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
   // the kernels of iem_kkt_assemble_diag / iem_kkt_residual_diag / iem_kkt_solve_refined_diag (csrc/iem_kkt_diag_device.h; loaded
@@ -292,6 +274,9 @@ struct iem_model {
   hipFunction_t kb_ldl = nullptr, kb_solve = nullptr, kb_colsum = nullptr, kb_inertia = nullptr;
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
+  // the explicit blocks in COO (iem_jacp_coord / iem_hessp_coord).  `pc_view`: the parameter view with the blocks' layout
+  // (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.  `d_pc_spare`: where a
+  // block the caller passed NULL for is written when it is not empty (allocated by the first such call)
   iem::Model pc_view;
   bool pc_have_view = false;
   double *d_pc_spare[2] = {nullptr, nullptr};
@@ -393,9 +378,15 @@ int load_program(iem_model *m, CodeObject &co, const iem::Options &opt) {
   return IEM_OK;
 }
 
-void free_program(CodeObject &co) {
-  for (void *t : co.d_tables) if (t) hipFree(t);
-  if (co.mod) hipModuleUnload(co.mod);
+// frees whatever of `P` exists and leaves it as never set up
+void release_program(LoadedProgram &P) {
+  for (double *r : P.d_red) if (r) hipFree(r);
+  for (long long *r : P.d_axis) if (r) hipFree(r);
+  for (long long *r : P.d_gather) if (r) hipFree(r);
+  if (P.d_partials) hipFree(P.d_partials);
+  for (void *t : P.d_tables) if (t) hipFree(t);
+  if (P.mod) hipModuleUnload(P.mod);
+  P = LoadedProgram();
 }
 
 int compile_or_load(iem_model *m) {
@@ -537,18 +528,19 @@ int halo_plan(iem_model *m, int kind, const void *x, const void *v, bool *carry)
 }
 
 // what runs BEHIND the kernels of a scatter kind (also behind the one-launch phases that contain grad!)
-int kind_followups(iem_model *m, const iem::Program &prog, long long *const *d_axis, long long *const *d_gather, int kind, double *out, double *aux) {
+int kind_followups(iem_model *m, const LoadedProgram &P, int kind, double *out, double *aux) {
+  const iem::Program &prog = P.prog;
   if (!prog.axis[kind].empty()) {   // sums over a non-lane axis: the rows the kernels parked -> one write per entry (iem_axis_sum_kernel)
     int64_t n0 = 1;
     for (auto &a : prog.axis[kind]) n0 = std::max(n0, a.n0);
-    void *args[] = {(void *)&out, (void *)&aux, (void *)&d_axis[kind]};
+    void *args[] = {(void *)&out, (void *)&aux, (void *)&P.d_axis[kind]};
     HIP_TRY(hipModuleLaunchKernel(m->fn_axis, (unsigned)((n0 + 63) / 64), (unsigned)prog.axis[kind].size(), 1, 256, 1, 1, 0, m->stream, args, nullptr));   // 64 lanes x 4 row groups per workgroup
   }
   if (!prog.gather[kind].dest.empty()) {   // what would have been float atomics: parked addends summed per entry in plan order
     const iem::Program::Gather &G = prog.gather[kind];
     long long n = (long long)G.dest.size();
     const double *parked = aux + G.aux_off;
-    const long long *dest = d_gather[kind], *seg = dest + n;
+    const long long *dest = P.d_gather[kind], *seg = dest + n;
     const void *perm = seg + n + 1;
     int wide = G.park_doubles >= (1LL << 32) ? 1 : 0;
     void *args[] = {(void *)&out, (void *)&parked, (void *)&dest, (void *)&seg, (void *)&perm, (void *)&n, (void *)&wide};
@@ -556,20 +548,18 @@ int kind_followups(iem_model *m, const iem::Program &prog, long long *const *d_a
   }
   return IEM_OK;
 }
-int kind_followups(iem_model *m, int kind, double *out, double *aux) {
-  return kind_followups(m, m->code.prog, m->d_axis, m->d_gather, kind, out, aux);
-}
 
 // device buffers of a program's scatter kinds: the aux buffer (shared-entry values x workgroups + ticket words, zeroed once,
 // then the rows of its axis sums and the parked addends), the plan of its gather, the table of its axis sums
 // `on_stream`: zero the aux buffers on that stream (a program set up between launches of a running handle) instead of
 // with a plain hipMemset (handle creation)
-int scatter_buffers(const iem::Program &prog, double **d_red, long long **d_gather, long long **d_axis, const hipStream_t *on_stream = nullptr) {
+int scatter_buffers(LoadedProgram &P, const hipStream_t *on_stream = nullptr) {
+  const iem::Program &prog = P.prog;
   for (int kind = 0; kind < iem::KK_COUNT; ++kind) {
     const size_t words = (size_t)prog.aux_doubles[kind];
     if (words == 0) continue;
-    if (hipMalloc((void **)&d_red[kind], words * 8) != hipSuccess ||
-        (on_stream ? hipMemsetAsync(d_red[kind], 0, words * 8, *on_stream) : hipMemset(d_red[kind], 0, words * 8)) != hipSuccess)
+    if (hipMalloc((void **)&P.d_red[kind], words * 8) != hipSuccess ||
+        (on_stream ? hipMemsetAsync(P.d_red[kind], 0, words * 8, *on_stream) : hipMemset(P.d_red[kind], 0, words * 8)) != hipSuccess)
       return fail(IEM_E_HIP, "hipMalloc reduction buffer");
     if (!prog.gather[kind].dest.empty()) {
       const iem::Program::Gather &G = prog.gather[kind];
@@ -577,19 +567,33 @@ int scatter_buffers(const iem::Program &prog, double **d_red, long long **d_gath
       const bool wide = G.park_doubles >= (1LL << 32);   // parked positions fit 32 bits otherwise: half the plan traffic
       std::vector<uint32_t> p32;
       if (!wide) { p32.resize(np); for (size_t k = 0; k < np; ++k) p32[k] = (uint32_t)G.perm[k]; }
-      if (hipMalloc((void **)&d_gather[kind], (2 * nd + 1) * 8 + np * (wide ? 8 : 4)) != hipSuccess ||
-          hipMemcpy(d_gather[kind], G.dest.data(), nd * 8, hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(d_gather[kind] + nd, G.seg.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(d_gather[kind] + 2 * nd + 1, wide ? (const void *)G.perm.data() : (const void *)p32.data(), np * (wide ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess)
+      if (hipMalloc((void **)&P.d_gather[kind], (2 * nd + 1) * 8 + np * (wide ? 8 : 4)) != hipSuccess ||
+          hipMemcpy(P.d_gather[kind], G.dest.data(), nd * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(P.d_gather[kind] + nd, G.seg.data(), (nd + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(P.d_gather[kind] + 2 * nd + 1, wide ? (const void *)G.perm.data() : (const void *)p32.data(), np * (wide ? 8 : 4), hipMemcpyHostToDevice) != hipSuccess)
         return fail(IEM_E_HIP, "hipMalloc gather plan");
     }
     if (!prog.axis[kind].empty()) {
       std::vector<long long> tab;
       for (auto &a : prog.axis[kind]) { tab.push_back(a.c); tab.push_back(a.k0); tab.push_back(a.n0); tab.push_back(a.rows); tab.push_back(a.off); }
-      if (hipMalloc((void **)&d_axis[kind], tab.size() * 8) != hipSuccess ||
-          hipMemcpy(d_axis[kind], tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+      if (hipMalloc((void **)&P.d_axis[kind], tab.size() * 8) != hipSuccess ||
+          hipMemcpy(P.d_axis[kind], tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
         return fail(IEM_E_HIP, "hipMalloc axis-sum table");
     }
+  }
+  return IEM_OK;
+}
+
+// the partials of the program's objective kernels + the ticket counters behind them (iem_block_partial: 1 top + one per 32
+// workgroups), zeroed once — the workgroups that complete a count reset it.  `on_stream` as for scatter_buffers
+int partials_buffer(LoadedProgram &P, const hipStream_t *on_stream = nullptr) {
+  const size_t np = (size_t)std::max<int64_t>(P.prog.n_partials, 1);
+  const size_t words = np + 1 + (np + 31) / 32;
+  if (hipMalloc((void **)&P.d_partials, words * 8) != hipSuccess) { P.d_partials = nullptr; return fail(IEM_E_HIP, "hipMalloc partials"); }
+  if (on_stream) {
+    if (hipMemsetAsync(P.d_partials, 0, words * 8, *on_stream) != hipSuccess) return fail(IEM_E_HIP, "hipMemsetAsync partials");
+  } else if (hipMemset(P.d_partials, 0, words * 8) != hipSuccess) {
+    return fail(IEM_E_HIP, "hipMalloc partials");
   }
   return IEM_OK;
 }
@@ -608,33 +612,38 @@ int launch_one(iem_model *m, CodeObject &co, int k, const LaunchHead &h) {
   return IEM_OK;
 }
 
-// One evaluation call: the launchable kernels of `kind` in `co` with the head `h` (th and comm filled in here), ordered
+// One evaluation call: the launchable kernels of `kind` in `P` with the head `h` (th and comm filled in here), ordered
 // against a deferred halo exchange (halo_plan) — the first kernel launched carries it, and it stays deferred when the kind
-// launches nothing — then what runs behind them: a scatter kind's own follow-ups, grad!'s behind the phases that contain
-// it; none behind the pair and trial kinds, nor behind the tuner's second object (jac_coord! / hess_coord! only).
-int launch_kind(iem_model *m, CodeObject &co, int kind, const LaunchHead &h) {
+// launches nothing — then a scatter kind's own follow-ups.  What runs behind a phase kind (grad!'s follow-ups behind the
+// phases that contain it, lagrad's and kktx's behind their programs' KK_TRIAL) is the caller's to launch.
+int launch_kind(iem_model *m, LoadedProgram &P, int kind, const LaunchHead &h) {
   bool carry = false;
   int rc = halo_plan(m, kind, h.x, h.v, &carry);
   if (rc) return rc;
   LaunchHead a = h;
   a.th = m->d_theta;
-  for (int k : co.launchable[kind]) {
+  for (int k : P.launchable[kind]) {
     a.comm = carry ? m->d_comm : nullptr;
-    if ((rc = launch_one(m, co, k, a))) return rc;
+    if ((rc = launch_one(m, P, k, a))) return rc;
     carry = false;
   }
   if (carry) m->halo_deferred = true;
-  if (&co != &m->code) return IEM_OK;
-  if (kind < iem::KK_COUNT) return kind_followups(m, kind, h.out, h.aux);
-  if (kind == iem::KK_ACCEPTED || kind == iem::KK_ALL) return kind_followups(m, iem::KK_GRAD, h.g, h.g_red);
+  return kind < iem::KK_COUNT ? kind_followups(m, P, kind, h.out, h.aux) : IEM_OK;
+}
+
+// memsets what the kernels of a scatter kind of `P` do not overwrite completely, in front of them
+int zero_uncovered(iem_model *m, const LoadedProgram &P, int kind, double *out) {
+  for (auto &z : P.zero_ranges[kind])
+    HIP_TRY(hipMemsetAsync(out + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
   return IEM_OK;
 }
 
-// memsets what the kernels of a scatter kind do not overwrite completely, in front of them
-int zero_uncovered(iem_model *m, int kind, double *out) {
-  for (auto &z : m->zero_ranges[kind])
-    HIP_TRY(hipMemsetAsync(out + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  return IEM_OK;
+// a scatter kind as its own call: the memsets, the kernels with the kind's reduction buffer as aux, the follow-ups
+int launch_scatter(iem_model *m, LoadedProgram &P, int kind, LaunchHead h) {
+  int rc = zero_uncovered(m, P, kind, h.out);
+  if (rc) return rc;
+  h.aux = P.d_red[kind];
+  return launch_kind(m, P, kind, h);
 }
 
 // the tuner's record of jac_coord! (which = 0) / hess_coord! (1) into the buffer `out`; a buffer not seen lately takes the oldest slot, undecided
@@ -1146,10 +1155,10 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   if (device < 0 || device >= ndev) return fail(IEM_E_ARG, "device ordinal out of range");
   iem_model *m = new iem_model();
   m->device = device;
-  hopt.param_kinds = 0;   // (the handle's own program; the parameter kinds are a second one, iem_model::par)
-  hopt.scaled_kinds = 0;  // (... and the scaled program a seventh, iem_model::scl)
-  hopt.kkt_kinds = 0;     // (... and the KKT operator an eighth, iem_model::kkt)
-  hopt.scaled_phase_kinds = 0;   // (... and the scaled solver phases a ninth, iem_model::sph)
+  hopt.param_kinds = 0;   // (the handle's own program; a derived program sets the one field of its row in kDerived)
+  hopt.scaled_kinds = 0;
+  hopt.kkt_kinds = 0;
+  hopt.scaled_phase_kinds = 0;
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1181,15 +1190,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   if (hipMalloc((void **)&m->d_theta, m->theta_host.size() * 8) != hipSuccess) return bail(fail(IEM_E_HIP, "hipMalloc theta"));
   if (hipMemcpy(m->d_theta, m->theta_host.data(), m->theta_host.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
     return bail(fail(IEM_E_HIP, "upload theta"));
-  // partials + the ticket counters behind them (iem_block_partial: 1 top + one per 32 workgroups),
-  // zeroed once — the workgroups that complete a count reset it
-  {
-    const size_t np = (size_t)std::max<int64_t>(m->code.prog.n_partials, 1);
-    const size_t words = np + 1 + (np + 31) / 32;
-    if (hipMalloc((void **)&m->d_partials, words * 8) != hipSuccess || hipMemset(m->d_partials, 0, words * 8) != hipSuccess)
-      return bail(fail(IEM_E_HIP, "hipMalloc partials"));
-  }
-  if ((rc = scatter_buffers(m->code.prog, m->d_red, m->d_gather, m->d_axis)) != IEM_OK) return bail(rc);
+  if ((rc = partials_buffer(m->code)) != IEM_OK || (rc = scatter_buffers(m->code)) != IEM_OK) return bail(rc);
   if (hipHostMalloc((void **)&m->h_obj, 16, hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer((void **)&m->d_hobj, m->h_obj, 0) != hipSuccess) return bail(fail(IEM_E_HIP, "hipHostMalloc"));
   m->h_status = reinterpret_cast<volatile unsigned long long *>(m->h_obj + 1);   // second word: comm time-outs (IemCommErr::hstatus)
@@ -1245,7 +1246,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
     // ranges the kernels of the kind do not overwrite completely.  Neighbouring ranges separated by a SHORT
     // fully-overwritten stretch are zeroed as one (what lies between is written afterwards, on the same
     // stream): one memset launch instead of two around pandemic's u(t) slab (grad! 11.5 -> 6 us of memsets)
-    auto &zr = m->zero_ranges[kind];
+    auto &zr = m->code.zero_ranges[kind];
     for (auto &z : m->code.prog.zero_ranges[kind]) {
       // the gap is measured against the two NEIGHBOURING ranges (never the whole span so far) and capped: a memset
       // never swallows more than 64 K doubles that a kernel is about to overwrite anyway
@@ -1262,10 +1263,6 @@ int iem_destroy(iem_model *m) {
   if (!m) return IEM_OK;
   DevGuard dg_(m->device);
   if (m->d_theta) hipFree(m->d_theta);
-  if (m->d_partials) hipFree(m->d_partials);
-  for (double *r : m->d_red) if (r) hipFree(r);
-  for (long long *r : m->d_axis) if (r) hipFree(r);
-  for (long long *r : m->d_gather) if (r) hipFree(r);
   for (void *p : m->ipc_opened) hipIpcCloseMemHandle(p);
   if (m->mailbox) hipFree(m->mailbox);
   if (m->d_peers) hipFree(m->d_peers);
@@ -1278,43 +1275,16 @@ int iem_destroy(iem_model *m) {
   if (m->d_comm) hipFree(m->d_comm);
   for (auto &kv : m->kkt_mods) if (kv.second.mod) hipModuleUnload(kv.second.mod);
   for (auto &kv : m->d_arrays) hipFree(kv.second);
-  free_program(m->alt);
-  for (double *r : m->par.d_red) if (r) hipFree(r);
-  for (long long *r : m->par.d_axis) if (r) hipFree(r);
-  for (long long *r : m->par.d_gather) if (r) hipFree(r);
-  free_program(m->par.code);
-  for (double *r : m->adj.d_red) if (r) hipFree(r);
-  for (long long *r : m->adj.d_axis) if (r) hipFree(r);
-  for (long long *r : m->adj.d_gather) if (r) hipFree(r);
-  free_program(m->adj.code);
-  for (double *r : m->th2.d_red) if (r) hipFree(r);
-  for (long long *r : m->th2.d_axis) if (r) hipFree(r);
-  for (long long *r : m->th2.d_gather) if (r) hipFree(r);
-  free_program(m->th2.code);
-  free_program(m->pc.code);
-  for (double *r : m->lag.d_red) if (r) hipFree(r);
-  for (long long *r : m->lag.d_axis) if (r) hipFree(r);
-  for (long long *r : m->lag.d_gather) if (r) hipFree(r);
-  free_program(m->lag.code);
-  if (m->d_lag_partials) hipFree(m->d_lag_partials);
-  free_program(m->scl.code);   // (no scatter kind: no reduction buffer, no plan)
-  for (double *r : m->kkt.d_red) if (r) hipFree(r);
-  for (long long *r : m->kkt.d_axis) if (r) hipFree(r);
-  for (long long *r : m->kkt.d_gather) if (r) hipFree(r);
-  free_program(m->kkt.code);
+  release_program(m->alt);
+  for (LoadedProgram &P : m->derived) release_program(P);
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
-  for (double *r : m->sph.d_red) if (r) hipFree(r);
-  for (long long *r : m->sph.d_axis) if (r) hipFree(r);
-  for (long long *r : m->sph.d_gather) if (r) hipFree(r);
-  free_program(m->sph.code);
-  if (m->d_sph_partials) hipFree(m->d_sph_partials);
   if (m->kres_mod) hipModuleUnload(m->kres_mod);
   if (m->kdg_mod) hipModuleUnload(m->kdg_mod);
   if (m->kb_mod) hipModuleUnload(m->kb_mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
-  free_program(m->code);
+  release_program(m->code);
   delete m;
   return IEM_OK;
 }
@@ -1340,15 +1310,14 @@ int iem_template_info(const iem_model *m, int64_t i, iem_template_info_t *out) {
 
 int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
   if (!m || !out || k < 0) return fail(IEM_E_ARG, "bad kernel index");
-  // behind the model's own kernels: those of every further program that exists on the handle (set up by its first call or
-  // its prepare call), in the order  three parameter kinds / adjoint / θθ / explicit blocks / residual program / scaled program /
-  // KKT operator / scaled solver phases
+  // behind the model's own kernels: those of every derived program that exists on the handle (set up by its first call or
+  // its prepare call), in the order of kDerived
   const iem::KernelDesc *found = k < (int)m->code.prog.kernels.size() ? &m->code.prog.kernels[k] : nullptr;
   int base = (int)m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt, &m->sph}) {
-    if (found || !P->tried || P->rc != IEM_OK) continue;
-    const int n = (int)P->code.prog.kernels.size();
-    if (k < base + n) found = &P->code.prog.kernels[k - base];
+  for (const LoadedProgram &P : m->derived) {
+    if (found || !P.tried || P.rc != IEM_OK) continue;
+    const int n = (int)P.prog.kernels.size();
+    if (k < base + n) found = &P.prog.kernels[k - base];
     base += n;
   }
   if (!found) return fail(IEM_E_ARG, "bad kernel index");
@@ -1367,8 +1336,8 @@ int iem_kernel_info(const iem_model *m, int k, iem_kernel_info_t *out) {
 int iem_kernel_count(const iem_model *m, int32_t *out_total) {
   if (!m || !out_total) return fail(IEM_E_ARG, "null argument");
   size_t n = m->code.prog.kernels.size();
-  for (const iem_model::ParamKinds *P : {&m->par, &m->adj, &m->th2, &m->pc, &m->lag, &m->scl, &m->kkt, &m->sph})
-    if (P->tried && P->rc == IEM_OK) n += P->code.prog.kernels.size();
+  for (const LoadedProgram &P : m->derived)
+    if (P.tried && P.rc == IEM_OK) n += P.prog.kernels.size();
   *out_total = (int32_t)n;
   return IEM_OK;
 }
@@ -1432,7 +1401,7 @@ int iem_obj_device(iem_model *m, const double *d_x, double *d_out) {
     return IEM_OK;
   }
   LaunchHead h;   // the last workgroup of the objective kernel(s) to finish writes the scalar to aux
-  h.x = d_x; h.out = m->d_partials; h.aux = d_out;
+  h.x = d_x; h.out = m->code.d_partials; h.aux = d_out;
   return launch_kind(m, m->code, iem::KK_OBJ, h);
 }
 
@@ -1495,11 +1464,9 @@ int iem_obj(iem_model *m, const double *d_x, double *h_out) {
 int iem_grad(iem_model *m, const double *d_x, double *d_g) {
   if (!m || !d_x || !d_g) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  int rc = zero_uncovered(m, iem::KK_GRAD, d_g);
-  if (rc) return rc;
   LaunchHead h;
-  h.x = d_x; h.out = d_g; h.aux = m->d_red[iem::KK_GRAD];
-  return launch_kind(m, m->code, iem::KK_GRAD, h);
+  h.x = d_x; h.out = d_g;
+  return launch_scatter(m, m->code, iem::KK_GRAD, h);
 }
 
 /* NLPModels.jprod!(m, x, v, Jv) */
@@ -1515,164 +1482,178 @@ int iem_jprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jv) 
 int iem_jtprod(iem_model *m, const double *d_x, const double *d_v, double *d_Jtv) {
   if (!m || !d_x || (!d_v && m->model.ncon) || !d_Jtv) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  int rc = zero_uncovered(m, iem::KK_JTPROD, d_Jtv);
-  if (rc) return rc;
   LaunchHead h;
-  h.x = d_x; h.v = d_v; h.out = d_Jtv; h.aux = m->d_red[iem::KK_JTPROD];
-  return launch_kind(m, m->code, iem::KK_JTPROD, h);
+  h.x = d_x; h.v = d_v; h.out = d_Jtv;
+  return launch_scatter(m, m->code, iem::KK_JTPROD, h);
 }
 
 /* NLPModels.hprod!(m, x, y, v, Hv; obj_weight) */
 int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *d_v, double obj_weight, double *d_Hv) {
   if (!m || !d_x || (!d_y && m->model.ncon) || !d_v || !d_Hv) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  int rc = zero_uncovered(m, iem::KK_HPROD, d_Hv);
-  if (rc) return rc;
   LaunchHead h;
-  h.x = d_x; h.y = d_y; h.v = d_v; h.out = d_Hv; h.w = obj_weight; h.aux = m->d_red[iem::KK_HPROD];
-  return launch_kind(m, m->code, iem::KK_HPROD, h);
+  h.x = d_x; h.y = d_y; h.v = d_v; h.out = d_Hv; h.w = obj_weight;
+  return launch_scatter(m, m->code, iem::KK_HPROD, h);
 }
+
+// ---- the derived programs ---------------------------------------------------------------------------------------------------
+// One row per program of iem_model::derived, in the order of `Derived`.  `field` = `value`: the one generator option that
+// selects the program (the other three stay 0, as in the handle's own options).  `sharded`: why its entry points refuse a
+// sharded handle.  `partials`: it has objective kernels, so it owns partials and ticket words.  To add a program: a row
+// here (and a name in `Derived`), its entry points, and a row in build().
+struct DerivedRow {
+  int iem::Options::*field;
+  int value;
+  const char *sharded;
+  bool partials;
+};
+static const char kShardedTheta[] = "θ is replicated on every rank, so the products with d/dθ would need an all-reduce over the ranks; "
+                                    "sharded parameter products are out of scope";
+static const DerivedRow kDerived[D_COUNT] = {
+    // D_PAR: the three parameter kinds (iem_jpprod / iem_jptprod / iem_hpprod), shaped like jprod / jtprod / hprod
+    {&iem::Options::param_kinds, 1, kShardedTheta, false},
+    // D_ADJ: the adjoint parameter kind (iem_hptprod) on KK_HPROD's table slot
+    {&iem::Options::param_kinds, 2, kShardedTheta, false},
+    // D_TH2: the θθ kind (iem_hppprod) on KK_HPROD's table slot
+    {&iem::Options::param_kinds, 3, kShardedTheta, false},
+    // D_PC: the explicit θ blocks in COO (iem_jacp_coord on KK_JAC's table slot, iem_hessp_coord on KK_HESS's); no scatter kind
+    {&iem::Options::param_kinds, 4, kShardedTheta, false},
+    // D_LAG: the residual program (iem_lagrad / iem_eval_residual): lagrad on KK_JTPROD's table slot, the model's own cons and
+    // obj, KK_TRIAL with lagrad as third member
+    {&iem::Options::param_kinds, 5,
+     "the gradient of the Lagrangian would need the halo fold and the all-reduce of grad! and jtprod!; a sharded residual is out of scope", true},
+    // D_SCL: the scaled program (iem_jac_rowmax / iem_cons_scaled / iem_jac_coord_scaled): rowmax on KK_JPROD's table slot,
+    // cons_scaled on KK_CONS's, jac_scaled on KK_JAC's; s = the head's v.  No scatter kind: no follow-up, no memset
+    {&iem::Options::scaled_kinds, 1,
+     "the values need no communication, but the deferred halo exchange (carrier workgroup, flush in front of a launch that reads a halo entry) "
+     "is not taught this program; scaled kernels on a sharded handle are out of scope", false},
+    // D_KKT: the KKT operator (iem_kktprod): kktx on KK_HPROD's table slot, kkty on KK_JPROD's, KK_TRIAL with both as members;
+    // u = the head's v, the dual direction = the head's last word
+    {&iem::Options::kkt_kinds, 1,
+     "the x-part would need the halo fold and the all-reduce of hprod! and jtprod!; a sharded KKT operator is out of scope", false},
+    // D_SPH: the scaled solver phases (iem_eval_trial_scaled / iem_eval_accepted_scaled and their members): sp_cons / sp_jac /
+    // sp_hess / sp_obj / sp_grad on the model's own table slots, KK_TRIAL and KK_ACCEPTED over them; s = the head's v, y = the head's y
+    {&iem::Options::scaled_phase_kinds, 1,
+     "the scaled gradient would need the halo fold and the all-reduce of grad!, and the deferred halo exchange is not taught this program; "
+     "scaled solver phases on a sharded handle are out of scope", true},
+};
+
+static int sharded_refusal(const iem_model *m, Derived d, const char *what) {
+  if (!m->sharded) return IEM_OK;
+  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — " + kDerived[d].sharded);
+}
+
+// The derived program `d` of the handle, generated and loaded by the first call that needs it (code-object cache -> hiprtc
+// on a miss, like the model's own).  A model the generator refuses stays refused, and every later call reports that; a runtime
+// failure (out of memory, a compile that did not go through) is not remembered: what was set up is released and the next
+// call tries again.
+static int derived_program(iem_model *m, Derived d) {
+  LoadedProgram &P = m->derived[d];
+  if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
+  iem::Options po = m->opt;
+  po.*kDerived[d].field = kDerived[d].value;
+  int rc = IEM_OK;
+  try {
+    P.prog = iem::generate(m->model, po);
+  } catch (const std::exception &e) {
+    rc = fail(IEM_E_BLOB, e.what());
+  }
+  // (a program without a kernel — no mixed / no θθ term at all: hptprod / hppprod is the runtime's memset — has no code object)
+  if (rc == IEM_OK && !P.prog.kernels.empty() && (rc = load_program(m, P, po)) == IEM_OK && (rc = scatter_buffers(P, &m->stream)) == IEM_OK)
+    rc = prepare_program(m, P);
+  if (rc == IEM_OK && kDerived[d].partials) rc = partials_buffer(P, &m->stream);
+  if (rc != IEM_OK && rc != IEM_E_BLOB) {
+    release_program(P);
+    return rc;
+  }
+  for (int kind = 0; kind < iem::KK_COUNT; ++kind) P.zero_ranges[kind] = P.prog.zero_ranges[kind];
+  P.tried = true;
+  P.rc = rc;
+  if (rc) P.err = g_err;
+  return rc;
+}
+
+// the prepare entry points: the programs `first` .. `last` set up, the number of their kernels out
+static int derived_prepare(iem_model *m, const char *what, Derived first, Derived last, int32_t *out_n_kernels) {
+  if (!m) return fail(IEM_E_ARG, "null handle");
+  int rc = sharded_refusal(m, first, what);
+  if (rc) return rc;
+  DevGuard dg_(m->device);
+  size_t n = 0;
+  for (int d = first; d <= last; ++d) {
+    if ((rc = derived_program(m, (Derived)d))) return rc;
+    n += m->derived[d].prog.kernels.size();
+  }
+  if (out_n_kernels) *out_n_kernels = (int32_t)n;
+  return IEM_OK;
+}
+
+int iem_param_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_param_prepare", D_PAR, D_ADJ, out_n_kernels); }
+int iem_hppprod_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_hppprod_prepare", D_TH2, D_TH2, out_n_kernels); }
+int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_param_coord_prepare", D_PC, D_PC, out_n_kernels); }
+int iem_lagrad_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_lagrad_prepare", D_LAG, D_LAG, out_n_kernels); }
+int iem_scaled_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_scaled_prepare", D_SCL, D_SCL, out_n_kernels); }
+int iem_scaled_phase_prepare(iem_model *m, int32_t *out_n_kernels) { return derived_prepare(m, "iem_scaled_phase_prepare", D_SPH, D_SPH, out_n_kernels); }
 
 // ---- parameter sensitivities: products with d/dθ at (x, the handle's current θ) ------------------------------------------
-// The program of the three kinds (P = m->par, kinds = 1), of the adjoint kind (P = m->adj, kinds = 2), of the θθ kind
-// (P = m->th2, kinds = 3), of the explicit blocks (P = m->pc, kinds = 4), the residual program (P = m->lag, kinds = 5) or the scaled program (P = m->scl, kinds = 0, scaled = 1), the KKT operator (P = m->kkt, kkt = 1) or the scaled solver phases (P = m->sph, sphase = 1), generated and loaded by the first call (code-object cache -> hiprtc on a miss, like the model's own); a failure is remembered and reported by every
-// later call.
-static int param_program(iem_model *m, iem_model::ParamKinds &P, int kinds, int scaled = 0, int kkt = 0, int sphase = 0) {
-  if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
-  P.tried = true;
-  // a model the generator refuses stays refused; a runtime failure (out of memory, a compile that did not go through) is
-  // not remembered: what was set up is released and the next call tries again
-  auto done = [&](int rc) {
-    P.rc = rc;
-    if (rc) P.err = g_err;
-    if (rc != IEM_OK && rc != IEM_E_BLOB) {
-      for (double *&r : P.d_red) { if (r) hipFree(r); r = nullptr; }
-      for (long long *&r : P.d_axis) { if (r) hipFree(r); r = nullptr; }
-      for (long long *&r : P.d_gather) { if (r) hipFree(r); r = nullptr; }
-      free_program(P.code);
-      P.code = CodeObject();
-      P.tried = false; P.rc = IEM_OK;
-    }
-    return rc;
-  };
-  iem::Options po = m->opt;
-  po.param_kinds = kinds;
-  po.scaled_kinds = scaled;
-  po.kkt_kinds = kkt;
-  po.scaled_phase_kinds = sphase;
-  try {
-    P.code.prog = iem::generate(m->model, po);
-  } catch (const std::exception &e) {
-    return done(fail(IEM_E_BLOB, e.what()));
-  }
-  int rc;
-  if (P.code.prog.kernels.empty()) return done(IEM_OK);   // (no mixed / no θθ term at all: hptprod / hppprod is the runtime's memset, no code object)
-  if ((rc = load_program(m, P.code, po)) != IEM_OK) return done(rc);
-  if ((rc = scatter_buffers(P.code.prog, P.d_red, P.d_gather, P.d_axis, &m->stream)) != IEM_OK) return done(rc);
-  return done(prepare_program(m, P.code));
-}
-
-static int param_refuse_sharded(const iem_model *m, const char *what);
-
-int iem_param_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = param_refuse_sharded(m, "iem_param_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->par, 1)) || (rc = param_program(m, m->adj, 2))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)(m->par.code.prog.kernels.size() + m->adj.code.prog.kernels.size());
-  return IEM_OK;
-}
-
-int iem_hppprod_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = param_refuse_sharded(m, "iem_hppprod_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->th2, 3))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->th2.code.prog.kernels.size();
-  return IEM_OK;
-}
-
-static int param_refuse_sharded(const iem_model *m, const char *what) {
-  if (!m->sharded) return IEM_OK;
-  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — θ is replicated on every rank, so the products with d/dθ "
-                         "would need an all-reduce over the ranks; sharded parameter products are out of scope");
-}
-
-// the launchable kernels of a parameter kind (table slot `kind`) and what runs behind them; out fully overwritten
-static int param_launch(iem_model *m, iem_model::ParamKinds &P, int kind, LaunchHead h) {
-  h.th = m->d_theta;
-  int rc;
-  if (iem::KK_JTPROD == kind || iem::KK_HPROD == kind) {
-    h.aux = P.d_red[kind];
-    for (auto &z : P.code.prog.zero_ranges[kind])
-      HIP_TRY(hipMemsetAsync(h.out + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  }
-  for (int k : P.code.launchable[kind])
-    if ((rc = launch_one(m, P.code, k, h))) return rc;
-  if (kind == iem::KK_JPROD) return IEM_OK;
-  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, kind, h.out, h.aux);
-}
-
 int iem_jpprod(iem_model *m, const double *d_x, const double *d_w, double *d_out) {
   if (!m || !d_x || (!d_w && m->model.npar) || (!d_out && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_jpprod");
+  int rc = sharded_refusal(m, D_PAR, "iem_jpprod");
   if (rc) return rc;
   DevGuard dg_(m->device);
   if (m->model.ncon == 0) return IEM_OK;
-  if ((rc = param_program(m, m->par, 1))) return rc;
+  if ((rc = derived_program(m, D_PAR))) return rc;
   LaunchHead h;
   h.x = d_x; h.v = d_w; h.out = d_out;
-  return param_launch(m, m->par, iem::KK_JPROD, h);
+  return launch_kind(m, m->derived[D_PAR], iem::KK_JPROD, h);
 }
 
 int iem_jptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_out && m->model.npar)) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_jptprod");
+  int rc = sharded_refusal(m, D_PAR, "iem_jptprod");
   if (rc) return rc;
   if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->par, 1))) return rc;
+  if ((rc = derived_program(m, D_PAR))) return rc;
   LaunchHead h;
   h.x = d_x; h.v = d_y; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, m->par, iem::KK_JTPROD, h);
+  return launch_scatter(m, m->derived[D_PAR], iem::KK_JTPROD, h);
 }
 
 int iem_hpprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_w && m->model.npar) || (!d_out && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_hpprod");
+  int rc = sharded_refusal(m, D_PAR, "iem_hpprod");
   if (rc) return rc;
   DevGuard dg_(m->device);
   if (m->model.nvar == 0) return IEM_OK;
-  if ((rc = param_program(m, m->par, 1))) return rc;
+  if ((rc = derived_program(m, D_PAR))) return rc;
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, m->par, iem::KK_HPROD, h);
+  return launch_scatter(m, m->derived[D_PAR], iem::KK_HPROD, h);
 }
 
 int iem_hptprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_u, double *d_out) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_u && m->model.nvar) || (!d_out && m->model.npar)) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_hptprod");
+  int rc = sharded_refusal(m, D_ADJ, "iem_hptprod");
   if (rc) return rc;
   if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->adj, 2))) return rc;
+  if ((rc = derived_program(m, D_ADJ))) return rc;
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_u; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, m->adj, iem::KK_HPROD, h);
+  return launch_scatter(m, m->derived[D_ADJ], iem::KK_HPROD, h);
 }
 
 int iem_hppprod(iem_model *m, const double *d_x, const double *d_y, double obj_weight, const double *d_w, double *d_out) {
   if (!m || !d_x || (!d_y && m->model.ncon) || ((!d_w || !d_out) && m->model.npar)) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_hppprod");
+  int rc = sharded_refusal(m, D_TH2, "iem_hppprod");
   if (rc) return rc;
   if (m->model.npar == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->th2, 3))) return rc;
+  if ((rc = derived_program(m, D_TH2))) return rc;
   LaunchHead h;
   h.x = d_x; h.y = d_y; h.v = d_w; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, m->th2, iem::KK_HPROD, h);
+  return launch_scatter(m, m->derived[D_TH2], iem::KK_HPROD, h);
 }
 
 // ---- the blocks themselves in COO: dc/dθ, d2L/dx dθ, d2L/dθ2 at (x, the handle's current θ) ------------------------------
@@ -1687,19 +1668,9 @@ static const iem::Model &param_coord_view(iem_model *m) {
   return m->pc_view;
 }
 
-int iem_param_coord_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = param_refuse_sharded(m, "iem_param_coord_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->pc, 4))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->pc.code.prog.kernels.size();
-  return IEM_OK;
-}
-
 int iem_param_coord_nnz(iem_model *m, int64_t out[3]) {
   if (!m || !out) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_param_coord_nnz");
+  int rc = sharded_refusal(m, D_PC, "iem_param_coord_nnz");
   if (rc) return rc;
   const iem::Model &v = param_coord_view(m);
   out[0] = v.nnzjp; out[1] = v.nnzhxp; out[2] = v.nnzhpp;
@@ -1708,7 +1679,7 @@ int iem_param_coord_nnz(iem_model *m, int64_t out[3]) {
 
 static int param_coord_structure(iem_model *m, int which, int64_t *h_rows, int64_t *h_cols, int base, const char *what) {
   if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = param_refuse_sharded(m, what);
+  int rc = sharded_refusal(m, D_PC, what);
   if (rc) return rc;
   const iem::Model &v = param_coord_view(m);
   const int64_t n = which == 0 ? v.nnzjp : which == 1 ? v.nnzhxp : v.nnzhpp;
@@ -1723,28 +1694,26 @@ int iem_hesspp_structure(iem_model *m, int64_t *h_rows, int64_t *h_cols, int bas
 
 int iem_jacp_coord(iem_model *m, const double *d_x, double *d_vals) {
   if (!m || !d_x) return fail(IEM_E_ARG, "null argument");
-  int rc = param_refuse_sharded(m, "iem_jacp_coord");
+  int rc = sharded_refusal(m, D_PC, "iem_jacp_coord");
   if (rc) return rc;
   if (param_coord_view(m).nnzjp == 0) return IEM_OK;   // no θ slot in any constraint: nothing to launch
   if (!d_vals) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->pc, 4))) return rc;
+  if ((rc = derived_program(m, D_PC))) return rc;
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.out = d_vals;
-  for (int k : m->pc.code.launchable[iem::KK_JAC])
-    if ((rc = launch_one(m, m->pc.code, k, h))) return rc;
-  return IEM_OK;
+  h.x = d_x; h.out = d_vals;
+  return launch_kind(m, m->derived[D_PC], iem::KK_JAC, h);
 }
 
 int iem_hessp_coord(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_hessxp, double *d_hesspp) {
   if (!m || !d_x || (!d_y && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
   if (!d_hessxp && !d_hesspp) return fail(IEM_E_ARG, "iem_hessp_coord: both outputs are NULL");
-  int rc = param_refuse_sharded(m, "iem_hessp_coord");
+  int rc = sharded_refusal(m, D_PC, "iem_hessp_coord");
   if (rc) return rc;
   const iem::Model &v = param_coord_view(m);
   if (v.nnzhxp == 0 && v.nnzhpp == 0) return IEM_OK;   // no second-order slot touches θ: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->pc, 4))) return rc;
+  if ((rc = derived_program(m, D_PC))) return rc;
   // both blocks come out of ONE sweep: a block the caller does not want (NULL) but that has entries goes to a spare buffer
   double *outp[2] = {d_hessxp, d_hesspp};
   const int64_t nn[2] = {v.nnzhxp, v.nnzhpp};
@@ -1754,58 +1723,22 @@ int iem_hessp_coord(iem_model *m, const double *d_x, const double *d_y, double o
     outp[b] = m->d_pc_spare[b];
   }
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.w = obj_weight; h.out = outp[0]; h.aux = outp[1];
-  for (int k : m->pc.code.launchable[iem::KK_HESS])
-    if ((rc = launch_one(m, m->pc.code, k, h))) return rc;
-  return IEM_OK;
+  h.x = d_x; h.y = d_y; h.w = obj_weight; h.out = outp[0]; h.aux = outp[1];
+  return launch_kind(m, m->derived[D_PC], iem::KK_HESS, h);
 }
 
 // ---- the convergence check: the Lagrangian's gradient in one kernel, c, f and that gradient in one launch ------------------
-// The residual program (P = m->lag, kinds = 5: lagrad on KK_JTPROD's table slot, the model's own cons and obj, KK_TRIAL with
-// lagrad as third member), set up like the θ programs, and the partials of its objective kernels.
-static int lagrad_refuse_sharded(const iem_model *m, const char *what) {
-  if (!m->sharded) return IEM_OK;
-  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the gradient of the Lagrangian would need the halo fold and the "
-                         "all-reduce of grad! and jtprod!; a sharded residual is out of scope");
-}
-
-static int lagrad_program(iem_model *m) {
-  int rc = param_program(m, m->lag, 5);
-  if (rc) return rc;
-  if (!m->d_lag_partials) {   // partials + ticket counters, zeroed once (the workgroups that complete a count reset it)
-    const size_t np = (size_t)std::max<int64_t>(m->lag.code.prog.n_partials, 1);
-    const size_t words = np + 1 + (np + 31) / 32;
-    if (hipMalloc((void **)&m->d_lag_partials, words * 8) != hipSuccess) { m->d_lag_partials = nullptr; return fail(IEM_E_HIP, "hipMalloc partials"); }
-    if (hipMemsetAsync(m->d_lag_partials, 0, words * 8, m->stream) != hipSuccess) {
-      hipFree(m->d_lag_partials);
-      m->d_lag_partials = nullptr;
-      return fail(IEM_E_HIP, "hipMemsetAsync partials");
-    }
-  }
-  return IEM_OK;
-}
-
-int iem_lagrad_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = lagrad_refuse_sharded(m, "iem_lagrad_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = lagrad_program(m))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->lag.code.prog.kernels.size();
-  return IEM_OK;
-}
-
 /* σ ∇f(x) + J(x)' y — the dual residual of a solver's convergence check, without the bound multipliers */
 int iem_lagrad(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_out) {
   if (!m || !d_x || (!d_y && m->model.ncon) || (!d_out && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
-  int rc = lagrad_refuse_sharded(m, "iem_lagrad");
+  int rc = sharded_refusal(m, D_LAG, "iem_lagrad");
   if (rc) return rc;
   if (m->model.nvar == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = lagrad_program(m))) return rc;
+  if ((rc = derived_program(m, D_LAG))) return rc;
   LaunchHead h;
   h.x = d_x; h.v = d_y; h.out = d_out; h.w = obj_weight;
-  return param_launch(m, m->lag, iem::KK_JTPROD, h);   // (no first-order slot at all: the zero range is the whole output, a memset)
+  return launch_scatter(m, m->derived[D_LAG], iem::KK_JTPROD, h);   // (no first-order slot at all: the zero range is the whole output, a memset)
 }
 
 /* c(x), f(x) and the gradient above in ONE launch (the residual program's KK_TRIAL), lagrad's follow-ups behind it; where
@@ -1813,111 +1746,75 @@ int iem_lagrad(iem_model *m, const double *d_x, const double *d_y, double obj_we
  * workgroups than one launch takes) the member launches */
 int iem_eval_residual(iem_model *m, const double *d_x, const double *d_y, double obj_weight, double *d_c, double *d_lagrad, double *d_obj) {
   if (!m || !d_x || !d_obj || ((!d_y || !d_c) && m->model.ncon) || (!d_lagrad && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
-  int rc = lagrad_refuse_sharded(m, "iem_eval_residual");
+  int rc = sharded_refusal(m, D_LAG, "iem_eval_residual");
   if (rc) return rc;
   DevGuard dg_(m->device);
-  if ((rc = lagrad_program(m))) return rc;
-  iem_model::ParamKinds &P = m->lag;
+  if ((rc = derived_program(m, D_LAG))) return rc;
+  LoadedProgram &P = m->derived[D_LAG];
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.v = d_y; h.w = obj_weight;
-  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
-    for (auto &z : P.code.prog.zero_ranges[iem::KK_JTPROD])
-      HIP_TRY(hipMemsetAsync(d_lagrad + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-    h.out = d_c; h.aux = d_obj; h.trial_partials = m->d_lag_partials; h.lag_out = d_lagrad; h.lag_red = P.d_red[iem::KK_JTPROD];
-    for (int k : P.code.launchable[iem::KK_TRIAL])
-      if ((rc = launch_one(m, P.code, k, h))) return rc;
-    return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_JTPROD, d_lagrad, P.d_red[iem::KK_JTPROD]);
+  h.x = d_x; h.v = d_y; h.w = obj_weight;
+  if (!P.launchable[iem::KK_TRIAL].empty()) {
+    if ((rc = zero_uncovered(m, P, iem::KK_JTPROD, d_lagrad))) return rc;
+    h.out = d_c; h.aux = d_obj; h.trial_partials = P.d_partials; h.lag_out = d_lagrad; h.lag_red = P.d_red[iem::KK_JTPROD];
+    if ((rc = launch_kind(m, P, iem::KK_TRIAL, h))) return rc;
+    return kind_followups(m, P, iem::KK_JTPROD, h.lag_out, h.lag_red);
   }
   h.out = d_c;
-  for (int k : P.code.launchable[iem::KK_CONS])
-    if ((rc = launch_one(m, P.code, k, h))) return rc;
-  if (P.code.launchable[iem::KK_OBJ].empty()) {   // no objective template: f = 0
+  if ((rc = launch_kind(m, P, iem::KK_CONS, h))) return rc;
+  if (P.launchable[iem::KK_OBJ].empty()) {   // no objective template: f = 0
     HIP_TRY(hipMemsetAsync(d_obj, 0, 8, m->stream));
   } else {
-    h.out = m->d_lag_partials; h.aux = d_obj;
-    for (int k : P.code.launchable[iem::KK_OBJ])
-      if ((rc = launch_one(m, P.code, k, h))) return rc;
+    h.out = P.d_partials; h.aux = d_obj;
+    if ((rc = launch_kind(m, P, iem::KK_OBJ, h))) return rc;
   }
   if (m->model.nvar == 0) return IEM_OK;
-  h.out = d_lagrad; h.aux = nullptr;
-  return param_launch(m, P, iem::KK_JTPROD, h);
+  h.out = d_lagrad;
+  return launch_scatter(m, P, iem::KK_JTPROD, h);
 }
 
 // ---- row scaling in the kernels: the row maxima of the Jacobian, scaled cons! and scaled jac_coord! -------------------------
-// The scaled program (P = m->scl, scaled_kinds = 1: rowmax on KK_JPROD's table slot, cons_scaled on KK_CONS's, jac_scaled on
-// KK_JAC's; s = the head's v), set up like the θ programs.  No scatter kind: no follow-up, no memset.
-static int scaled_refuse_sharded(const iem_model *m, const char *what) {
-  if (!m->sharded) return IEM_OK;
-  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the values need no communication, but the deferred halo "
-                         "exchange (carrier workgroup, flush in front of a launch that reads a halo entry) is not taught this program; "
-                         "scaled kernels on a sharded handle are out of scope");
-}
-
-static int scaled_launch(iem_model *m, int kind, const double *d_x, const double *d_s, double *d_out) {
-  LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.v = d_s; h.out = d_out;
-  int rc;
-  for (int k : m->scl.code.launchable[kind])
-    if ((rc = launch_one(m, m->scl.code, k, h))) return rc;
-  return IEM_OK;
-}
-
-int iem_scaled_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = scaled_refuse_sharded(m, "iem_scaled_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->scl.code.prog.kernels.size();
-  return IEM_OK;
-}
-
 /* max over the first-order slots of row r of |dc_r/dx_slot| (repeated positions not summed; 0 for a row without a slot; NaN stays) */
 int iem_jac_rowmax(iem_model *m, const double *d_x, double *d_rowmax) {
   if (!m || !d_x || (!d_rowmax && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
-  int rc = scaled_refuse_sharded(m, "iem_jac_rowmax");
+  int rc = sharded_refusal(m, D_SCL, "iem_jac_rowmax");
   if (rc) return rc;
   if (m->model.ncon == 0) return IEM_OK;   // a zero-length output: nothing to launch
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
-  return scaled_launch(m, iem::KK_JPROD, d_x, nullptr, d_rowmax);
+  if ((rc = derived_program(m, D_SCL))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.out = d_rowmax;
+  return launch_kind(m, m->derived[D_SCL], iem::KK_JPROD, h);
 }
 
 /* s[r] * c_r(x) */
 int iem_cons_scaled(iem_model *m, const double *d_x, const double *d_s, double *d_c) {
   if (!m || !d_x || ((!d_s || !d_c) && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
-  int rc = scaled_refuse_sharded(m, "iem_cons_scaled");
+  int rc = sharded_refusal(m, D_SCL, "iem_cons_scaled");
   if (rc) return rc;
   if (m->model.ncon == 0) return IEM_OK;
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
-  return scaled_launch(m, iem::KK_CONS, d_x, d_s, d_c);
+  if ((rc = derived_program(m, D_SCL))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_s; h.out = d_c;
+  return launch_kind(m, m->derived[D_SCL], iem::KK_CONS, h);
 }
 
 /* s[row(k)] * jac[k] at the positions of iem_jac_structure */
 int iem_jac_coord_scaled(iem_model *m, const double *d_x, const double *d_s, double *d_vals) {
   if (!m || !d_x || (!d_s && m->model.ncon) || (!d_vals && m->model.nnzj)) return fail(IEM_E_ARG, "null argument");
-  int rc = scaled_refuse_sharded(m, "iem_jac_coord_scaled");
+  int rc = sharded_refusal(m, D_SCL, "iem_jac_coord_scaled");
   if (rc) return rc;
   if (m->model.nnzj == 0) return IEM_OK;
   DevGuard dg_(m->device);
-  if ((rc = param_program(m, m->scl, 0, 1))) return rc;
-  return scaled_launch(m, iem::KK_JAC, d_x, d_s, d_vals);
+  if ((rc = derived_program(m, D_SCL))) return rc;
+  LaunchHead h;
+  h.x = d_x; h.v = d_s; h.out = d_vals;
+  return launch_kind(m, m->derived[D_SCL], iem::KK_JAC, h);
 }
 
 // ---- the KKT operator: out_x = W u + J' v, out_y = J u in one launch ----------------------------------------------------------
-// The eighth program (P = m->kkt, kkt_kinds = 1: kktx on KK_HPROD's table slot, kkty on KK_JPROD's, KK_TRIAL with both as
-// members; u = the head's v, the dual direction = the head's last word), set up like the θ programs; kktx's memsets and
-// follow-ups stay here, as lagrad's do.
-static int kktprod_refuse_sharded(const iem_model *m, const char *what) {
-  if (!m->sharded) return IEM_OK;
-  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the x-part would need the halo fold and the all-reduce of "
-                         "hprod! and jtprod!; a sharded KKT operator is out of scope");
-}
-
-static int kktprod_program(iem_model *m) {
-  int rc = param_program(m, m->kkt, 0, 0, 1);
-  if (rc) return rc;
+// kktx's memsets and follow-ups stay here, as lagrad's do.
+static int kkt_zero_direction(iem_model *m) {
   if (!m->d_kkt_zero && m->model.ncon > 0) {   // the dual direction of a call with d_v == NULL
     const size_t bytes = (size_t)m->model.ncon * 8;
     if (hipMalloc((void **)&m->d_kkt_zero, bytes) != hipSuccess) { m->d_kkt_zero = nullptr; return fail(IEM_E_HIP, "hipMalloc zero direction"); }
@@ -1927,13 +1824,10 @@ static int kktprod_program(iem_model *m) {
 }
 
 int iem_kktprod_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = kktprod_refuse_sharded(m, "iem_kktprod_prepare");
+  int rc = derived_prepare(m, "iem_kktprod_prepare", D_KKT, D_KKT, out_n_kernels);
   if (rc) return rc;
   DevGuard dg_(m->device);
-  if ((rc = kktprod_program(m))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->kkt.code.prog.kernels.size();
-  return IEM_OK;
+  return kkt_zero_direction(m);   // (so that a prepared handle allocates nothing in iem_kktprod)
 }
 
 static bool kkt_overlap(const double *a, int64_t na, const double *b, int64_t nb) {
@@ -1946,7 +1840,7 @@ int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   if (!m) return fail(IEM_E_ARG, "null argument");
   const int64_t nvar = m->model.nvar, ncon = m->model.ncon;
   if (((!d_x || !d_u || !d_out_x) && nvar) || ((!d_y || !d_out_y) && ncon)) return fail(IEM_E_ARG, "null argument");
-  int rc = kktprod_refuse_sharded(m, "iem_kktprod");
+  int rc = sharded_refusal(m, D_KKT, "iem_kktprod");
   if (rc) return rc;
   for (const auto &in : {std::make_pair(d_x, nvar), std::make_pair(d_u, nvar), std::make_pair(d_y, ncon), std::make_pair(d_v, ncon)})
     if (kkt_overlap(d_out_x, nvar, in.first, in.second) || kkt_overlap(d_out_y, ncon, in.first, in.second))
@@ -1954,138 +1848,77 @@ int iem_kktprod(iem_model *m, const double *d_x, const double *d_y, double obj_w
   if (kkt_overlap(d_out_x, nvar, d_out_y, ncon)) return fail(IEM_E_ARG, "iem_kktprod: the two outputs overlap");
   if (nvar == 0 && ncon == 0) return IEM_OK;
   DevGuard dg_(m->device);
-  if ((rc = kktprod_program(m))) return rc;
-  iem_model::ParamKinds &P = m->kkt;
+  if ((rc = derived_program(m, D_KKT)) || (rc = kkt_zero_direction(m))) return rc;
+  LoadedProgram &P = m->derived[D_KKT];
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_u; h.w = obj_weight;
+  h.x = d_x; h.y = d_y; h.v = d_u; h.w = obj_weight;
   h.obj = const_cast<double *>(d_v ? d_v : m->d_kkt_zero);   // (the head's last word: read only)
   double *red = P.d_red[iem::KK_HPROD];
-  if (nvar)
-    for (auto &z : P.code.prog.zero_ranges[iem::KK_HPROD])
-      HIP_TRY(hipMemsetAsync(d_out_x + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
+  if (nvar && (rc = zero_uncovered(m, P, iem::KK_HPROD, d_out_x))) return rc;
+  if (!P.launchable[iem::KK_TRIAL].empty()) {
     h.out = d_out_x; h.aux = red; h.g = d_out_y;
-    for (int k : P.code.launchable[iem::KK_TRIAL])
-      if ((rc = launch_one(m, P.code, k, h))) return rc;
-    return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_HPROD, d_out_x, red);
+    if ((rc = launch_kind(m, P, iem::KK_TRIAL, h))) return rc;
+    return kind_followups(m, P, iem::KK_HPROD, d_out_x, red);
   }
-  h.out = d_out_y; h.aux = nullptr;
-  for (int k : P.code.launchable[iem::KK_JPROD])
-    if ((rc = launch_one(m, P.code, k, h))) return rc;
+  h.out = d_out_y;
+  if ((rc = launch_kind(m, P, iem::KK_JPROD, h))) return rc;
   if (nvar == 0) return IEM_OK;
   h.out = d_out_x; h.aux = red;
-  for (int k : P.code.launchable[iem::KK_HPROD])
-    if ((rc = launch_one(m, P.code, k, h))) return rc;
-  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_HPROD, d_out_x, red);
+  return launch_kind(m, P, iem::KK_HPROD, h);
 }
 
 // ---- one launch per solver phase for the SCALED NLP ---------------------------------------------------------------------------
-// The ninth program (P = m->sph, scaled_phase_kinds = 1: sp_cons / sp_jac / sp_hess / sp_obj / sp_grad on the model's own table
-// slots, KK_TRIAL and KK_ACCEPTED over them; s = the head's v, y = the head's y), set up like the θ programs, and the partials
-// of its objective kernels.  The accepted phase has two scalars: the head's w is the Hessian's objective weight, the
-// gradient's seed travels as the bits of a double in the head's word p4.  sp_grad's memsets and follow-ups stay here.
-static int sphase_refuse_sharded(const iem_model *m, const char *what) {
-  if (!m->sharded) return IEM_OK;
-  return fail(IEM_E_ARG, std::string(what) + ": not available on a sharded handle — the scaled gradient would need the halo fold and the all-reduce "
-                         "of grad!, and the deferred halo exchange is not taught this program; scaled solver phases on a sharded handle are out of scope");
-}
-
-static int sphase_program(iem_model *m) {
-  int rc = param_program(m, m->sph, 0, 0, 0, 1);
-  if (rc) return rc;
-  if (!m->d_sph_partials) {   // partials + ticket counters, zeroed once (the workgroups that complete a count reset it)
-    const size_t np = (size_t)std::max<int64_t>(m->sph.code.prog.n_partials, 1);
-    const size_t words = np + 1 + (np + 31) / 32;
-    if (hipMalloc((void **)&m->d_sph_partials, words * 8) != hipSuccess) { m->d_sph_partials = nullptr; return fail(IEM_E_HIP, "hipMalloc partials"); }
-    if (hipMemsetAsync(m->d_sph_partials, 0, words * 8, m->stream) != hipSuccess) {
-      hipFree(m->d_sph_partials);
-      m->d_sph_partials = nullptr;
-      return fail(IEM_E_HIP, "hipMemsetAsync partials");
-    }
-  }
-  return IEM_OK;
-}
-
-// the launchable kernels of one member kind of the program
-static int sphase_members(iem_model *m, int kind, const LaunchHead &h) {
-  int rc;
-  for (int k : m->sph.code.launchable[kind])
-    if ((rc = launch_one(m, m->sph.code, k, h))) return rc;
-  return IEM_OK;
-}
-
-// what the runtime memsets in front of sp_grad (the whole of g on a model without an objective)
-static int sphase_zero_grad(iem_model *m, double *d_g) {
-  for (auto &z : m->sph.code.prog.zero_ranges[iem::KK_GRAD])
-    HIP_TRY(hipMemsetAsync(d_g + z.first, 0, (size_t)(z.second - z.first) * 8, m->stream));
-  return IEM_OK;
-}
-
-static int sphase_grad_followups(iem_model *m, double *d_g) {
-  iem_model::ParamKinds &P = m->sph;
-  return kind_followups(m, P.code.prog, P.d_axis, P.d_gather, iem::KK_GRAD, d_g, P.d_red[iem::KK_GRAD]);
-}
-
-int iem_scaled_phase_prepare(iem_model *m, int32_t *out_n_kernels) {
-  if (!m) return fail(IEM_E_ARG, "null handle");
-  int rc = sphase_refuse_sharded(m, "iem_scaled_phase_prepare");
-  if (rc) return rc;
-  DevGuard dg_(m->device);
-  if ((rc = sphase_program(m))) return rc;
-  if (out_n_kernels) *out_n_kernels = (int32_t)m->sph.code.prog.kernels.size();
-  return IEM_OK;
-}
-
+// The accepted phase has two scalars: the head's w is the Hessian's objective weight, the gradient's seed travels as the bits
+// of a double in the head's word p4.  sp_grad's memsets and follow-ups stay here.
 /* obj_scale * grad f(x): the reverse sweep seeded with obj_scale */
 int iem_grad_scaled(iem_model *m, const double *d_x, double obj_scale, double *d_g) {
   if (!m || !d_x || (!d_g && m->model.nvar)) return fail(IEM_E_ARG, "null argument");
-  int rc = sphase_refuse_sharded(m, "iem_grad_scaled");
+  int rc = sharded_refusal(m, D_SPH, "iem_grad_scaled");
   if (rc) return rc;
   if (m->model.nvar == 0) return IEM_OK;
   DevGuard dg_(m->device);
-  if ((rc = sphase_program(m)) || (rc = sphase_zero_grad(m, d_g))) return rc;
+  if ((rc = derived_program(m, D_SPH))) return rc;
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.out = d_g; h.w = obj_scale; h.aux = m->sph.d_red[iem::KK_GRAD];
-  if ((rc = sphase_members(m, iem::KK_GRAD, h))) return rc;
-  return sphase_grad_followups(m, d_g);
+  h.x = d_x; h.out = d_g; h.w = obj_scale;
+  return launch_scatter(m, m->derived[D_SPH], iem::KK_GRAD, h);   // (the memset is the whole of g on a model without an objective)
 }
 
 /* hess_coord!(x, fl(y∘s); obj_weight): the multiplier of a scaled row formed in the kernel */
 int iem_hess_coord_scaled(iem_model *m, const double *d_x, const double *d_y, const double *d_s, double obj_weight, double *d_vals) {
   if (!m || !d_x || ((!d_y || !d_s) && m->model.ncon) || (!d_vals && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
-  int rc = sphase_refuse_sharded(m, "iem_hess_coord_scaled");
+  int rc = sharded_refusal(m, D_SPH, "iem_hess_coord_scaled");
   if (rc) return rc;
   if (m->model.nnzh == 0) return IEM_OK;
   DevGuard dg_(m->device);
-  if ((rc = sphase_program(m))) return rc;
+  if ((rc = derived_program(m, D_SPH))) return rc;
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_s; h.out = d_vals; h.w = obj_weight;
-  return sphase_members(m, iem::KK_HESS, h);
+  h.x = d_x; h.y = d_y; h.v = d_s; h.out = d_vals; h.w = obj_weight;
+  return launch_kind(m, m->derived[D_SPH], iem::KK_HESS, h);
 }
 
 /* s∘cons(x) and obj_scale·obj(x) in ONE launch (the program's KK_TRIAL); where that kernel does not exist (option
  * "phase_kernels" = 0, no objective or no constraint, more workgroups than one launch takes) the member launches */
 int iem_eval_trial_scaled(iem_model *m, const double *d_x, const double *d_s, double obj_scale, double *d_c, double *h_obj) {
   if (!m || !d_x || ((!d_s || !d_c) && m->model.ncon)) return fail(IEM_E_ARG, "null argument");
-  int rc = sphase_refuse_sharded(m, "iem_eval_trial_scaled");
+  int rc = sharded_refusal(m, D_SPH, "iem_eval_trial_scaled");
   if (rc) return rc;
   DevGuard dg_(m->device);
-  if ((rc = sphase_program(m))) return rc;
+  if ((rc = derived_program(m, D_SPH))) return rc;
   if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_trial_scaled: the previous iem_obj_begin / iem_eval_trial has not been collected (iem_obj_end)");
-  iem_model::ParamKinds &P = m->sph;
+  LoadedProgram &P = m->derived[D_SPH];
   obj_arm(m);
   m->obj_scaled = true; m->obj_factor = obj_scale;
   LaunchHead h;   // the kernel writes the model's own f into the mapped slot, the factor meets it on the host (iem_obj_end)
-  h.x = d_x; h.th = m->d_theta; h.v = d_s;
-  if (!P.code.launchable[iem::KK_TRIAL].empty()) {
-    h.out = d_c; h.aux = m->d_hobj; h.trial_partials = m->d_sph_partials;
-    rc = sphase_members(m, iem::KK_TRIAL, h);
+  h.x = d_x; h.v = d_s;
+  if (!P.launchable[iem::KK_TRIAL].empty()) {
+    h.out = d_c; h.aux = m->d_hobj; h.trial_partials = P.d_partials;
+    rc = launch_kind(m, P, iem::KK_TRIAL, h);
   } else {
     h.out = d_c;
-    rc = sphase_members(m, iem::KK_CONS, h);
+    rc = launch_kind(m, P, iem::KK_CONS, h);
     if (rc == IEM_OK) {   // (no objective template: nothing is launched and iem_obj_end gives 0)
-      h.out = m->d_sph_partials; h.aux = m->d_hobj;
-      rc = sphase_members(m, iem::KK_OBJ, h);
+      h.out = P.d_partials; h.aux = m->d_hobj;
+      rc = launch_kind(m, P, iem::KK_OBJ, h);
     }
   }
   if (rc) { m->obj_armed = false; m->obj_scaled = false; return rc; }
@@ -2098,30 +1931,29 @@ int iem_eval_accepted_scaled(iem_model *m, const double *d_x, const double *d_y,
                              double *d_g, double *d_jac, double *d_hess) {
   if (!m || !d_x || (!d_g && m->model.nvar) || ((!d_y || !d_s) && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh))
     return fail(IEM_E_ARG, "null argument");
-  int rc = sphase_refuse_sharded(m, "iem_eval_accepted_scaled");
+  int rc = sharded_refusal(m, D_SPH, "iem_eval_accepted_scaled");
   if (rc) return rc;
   DevGuard dg_(m->device);
-  if ((rc = sphase_program(m))) return rc;
-  iem_model::ParamKinds &P = m->sph;
+  if ((rc = derived_program(m, D_SPH))) return rc;
+  LoadedProgram &P = m->derived[D_SPH];
   const double w = obj_weight * obj_scale;   // the Hessian's objective weight as used: one host multiply
-  if (m->model.nvar && (rc = sphase_zero_grad(m, d_g))) return rc;
+  if (m->model.nvar && (rc = zero_uncovered(m, P, iem::KK_GRAD, d_g))) return rc;
   LaunchHead h;
-  h.x = d_x; h.th = m->d_theta; h.y = d_y; h.v = d_s; h.w = w;
-  if (!P.code.launchable[iem::KK_ACCEPTED].empty()) {
+  h.x = d_x; h.y = d_y; h.v = d_s; h.w = w;
+  if (!P.launchable[iem::KK_ACCEPTED].empty()) {
     h.out = d_jac; h.aux = d_hess; h.g = d_g; h.g_red = P.d_red[iem::KK_GRAD];
     static_assert(sizeof h.c == sizeof obj_scale, "the gradient's seed rides on one word of the head");
     std::memcpy(&h.c, &obj_scale, 8);   // (the head's p4: the bits of sp_grad's seed, iem_sp_word)
-    if ((rc = sphase_members(m, iem::KK_ACCEPTED, h))) return rc;
-    return sphase_grad_followups(m, d_g);
+    if ((rc = launch_kind(m, P, iem::KK_ACCEPTED, h))) return rc;
+    return kind_followups(m, P, iem::KK_GRAD, h.g, h.g_red);
   }
   h.out = d_jac;
-  if ((rc = sphase_members(m, iem::KK_JAC, h))) return rc;
+  if ((rc = launch_kind(m, P, iem::KK_JAC, h))) return rc;
   h.out = d_hess;
-  if ((rc = sphase_members(m, iem::KK_HESS, h))) return rc;
+  if ((rc = launch_kind(m, P, iem::KK_HESS, h))) return rc;
   if (m->model.nvar == 0) return IEM_OK;
   h.out = d_g; h.w = obj_scale; h.aux = P.d_red[iem::KK_GRAD];
-  if ((rc = sphase_members(m, iem::KK_GRAD, h))) return rc;
-  return sphase_grad_followups(m, d_g);
+  return launch_kind(m, P, iem::KK_GRAD, h);
 }
 
 int iem_cons(iem_model *m, const double *d_x, double *d_c) {
@@ -2180,7 +2012,7 @@ int iem_eval_trial(iem_model *m, const double *d_x, double *d_c, double *h_obj) 
     if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_trial: the previous iem_obj_begin / iem_eval_trial has not been collected (iem_obj_end)");
     obj_arm(m);
     LaunchHead h;
-    h.x = d_x; h.out = d_c; h.aux = m->d_hobj; h.trial_partials = m->d_partials;
+    h.x = d_x; h.out = d_c; h.aux = m->d_hobj; h.trial_partials = m->code.d_partials;
     rc = launch_kind(m, m->code, iem::KK_TRIAL, h);
   } else if ((rc = iem_obj_begin(m, d_x)) == IEM_OK) {
     rc = iem_cons(m, d_x, d_c);
@@ -2195,11 +2027,12 @@ int iem_eval_accepted(iem_model *m, const double *d_x, const double *d_y, double
   if (!m || !d_x || !d_g || (!d_y && m->model.ncon) || (!d_jac && m->model.nnzj) || (!d_hess && m->model.nnzh)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(m->device);
   if (!m->code.launchable[iem::KK_ACCEPTED].empty()) {
-    int rc = zero_uncovered(m, iem::KK_GRAD, d_g);
+    int rc = zero_uncovered(m, m->code, iem::KK_GRAD, d_g);
     if (rc) return rc;
     LaunchHead h;
-    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->d_red[iem::KK_GRAD];
-    return launch_kind(m, m->code, iem::KK_ACCEPTED, h);
+    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->code.d_red[iem::KK_GRAD];
+    if ((rc = launch_kind(m, m->code, iem::KK_ACCEPTED, h))) return rc;
+    return kind_followups(m, m->code, iem::KK_GRAD, h.g, h.g_red);
   }
   int rc = iem_grad(m, d_x, d_g);
   if (rc == IEM_OK) rc = iem_jac_hess_coord(m, d_x, d_y, obj_weight, d_jac, d_hess);
@@ -2216,12 +2049,12 @@ int iem_eval_all(iem_model *m, const double *d_x, const double *d_y, double obj_
   int rc;
   if (!m->code.launchable[iem::KK_ALL].empty() && m->code.prog.n_partials > 0) {
     if (m->obj_armed) return fail(IEM_E_ARG, "iem_eval_all: the previous iem_obj_begin / iem_eval_trial / iem_eval_all has not been collected (iem_obj_end)");
-    if ((rc = zero_uncovered(m, iem::KK_GRAD, d_g))) return rc;
+    if ((rc = zero_uncovered(m, m->code, iem::KK_GRAD, d_g))) return rc;
     obj_arm(m);
     LaunchHead h;
-    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->d_red[iem::KK_GRAD];
-    h.c = d_c; h.partials = m->d_partials; h.obj = m->d_hobj;
-    rc = launch_kind(m, m->code, iem::KK_ALL, h);
+    h.x = d_x; h.y = d_y; h.out = d_jac; h.w = obj_weight; h.aux = d_hess; h.g = d_g; h.g_red = m->code.d_red[iem::KK_GRAD];
+    h.c = d_c; h.partials = m->code.d_partials; h.obj = m->d_hobj;
+    if ((rc = launch_kind(m, m->code, iem::KK_ALL, h)) == IEM_OK) rc = kind_followups(m, m->code, iem::KK_GRAD, h.g, h.g_red);
   } else if ((rc = iem_eval_trial(m, d_x, d_c, nullptr)) == IEM_OK) {
     rc = iem_eval_accepted(m, d_x, d_y, obj_weight, d_g, d_jac, d_hess);
   } else {

@@ -35,6 +35,9 @@ class MI355XBackend:
         return f"MI355XBackend(device={self.device}" + (f", shard={self.shard})" if self.shard else ")")
 
 
+# The prepare calls of the derived programs, ``iem_<name>_prepare``, in the order ``iem_kernel_info`` lists the programs' kernels
+# behind the model's own (csrc/iem_api.cpp: kDerived; "param" covers the first two rows)
+PREPARE_CALLS = ("param", "hppprod", "param_coord", "lagrad", "scaled", "kktprod", "scaled_phase")
 KERNEL_KINDS = ("cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod", "pair", "trial", "accepted", "point")   # iem_kernel_info_t.kind
 
 
@@ -98,10 +101,7 @@ class ExaModel:
             _lib.check(self._L.iem_create_sharded(blob, len(blob), device, _shard[0], _shard[1], _shard[2], arr, n, C.byref(h)))
         self._h = h
         self._pc_nnz = None      # lengths of the explicit θ blocks (param_coord_nnz), asked once
-        self._lag_n = None       # kernels of the residual program (lagrangian_prepare), once it is set up
-        self._scl_n = None       # kernels of the scaled program (scaled_prepare), once it is set up
-        self._kkt_n = None       # kernels of the KKT operator (kkt_prepare), once it is set up
-        self._sph_n = None       # kernels of the scaled solver phases (scaled_phase_prepare), once they are set up
+        self._prepared = {}      # prepare call (a name of PREPARE_CALLS) -> the number of kernels it reported, once made
         if core is not None:
             core._model = self
         m = _lib.Meta()
@@ -305,20 +305,13 @@ class ExaModel:
     def lagrangian_prepare(self) -> int:
         """Set up the program of ``lagrangian_grad`` / ``eval_residual`` now (``iem_lagrad_prepare``: otherwise their first
         call does — synchronously, and not inside a stream capture); the number of its kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_lagrad_prepare(self._h, C.byref(n)))
-        self._lag_n = int(n.value)
-        return self._lag_n
+        return self._prepare("lagrad")
 
     def lagrangian_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the residual program (kinds cons / obj / jtprod — the
         latter named ``iem_lagrad*`` — and the phase kernel ``iem_residual_all``, kind trial): always the LAST kernels
         ``iem_kernel_info`` lists in front of the scaled program's (``scaled_kernels``), where that exists."""
-        n = self.lagrangian_prepare()
-        total = C.c_int32()
-        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._scl_n or 0) - (self._kkt_n or 0) - (self._sph_n or 0)
-        return self._kernel_infos(last - n, last)
+        return self._kernels_from_end("lagrad")
 
     def lagrangian_grad(self, x, y, obj_weight: float = 1.0, out=None):
         """``obj_weight·∇f(x) + J(x)ᵀ·y`` (nvar) from ONE atomic-free kernel (``iem_lagrad``): the dual residual of a solver's
@@ -329,8 +322,7 @@ class ExaModel:
         out = out if out is not None else self._new(self.meta.nvar)
         self._chk(out, self.meta.nvar, "out")
         self._sync_stream()
-        if self._lag_n is None:
-            self.lagrangian_prepare()
+        self._ensure("lagrad")
         _lib.check(self._L.iem_lagrad(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(out)))
         return out
 
@@ -347,8 +339,7 @@ class ExaModel:
         obj = obj if obj is not None else self._new(1)
         self._chk(c, self.meta.ncon, "c"); self._chk(out, self.meta.nvar, "out"); self._chk(obj, 1, "obj")
         self._sync_stream()
-        if self._lag_n is None:
-            self.lagrangian_prepare()
+        self._ensure("lagrad")
         _lib.check(self._L.iem_eval_residual(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(c), _ptr(out), _ptr(obj)))
         self.counters.neval_obj += 1
         self.counters.neval_cons += 1
@@ -358,58 +349,38 @@ class ExaModel:
     def scaled_prepare(self) -> int:
         """Set up the program of ``jac_row_maxabs`` / ``cons_scaled`` / ``jac_coord_scaled`` now (``iem_scaled_prepare``:
         otherwise their first call does — synchronously, and not inside a stream capture); the number of its kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_scaled_prepare(self._h, C.byref(n)))
-        self._scl_n = int(n.value)
-        return self._scl_n
+        return self._prepare("scaled")
 
     def scaled_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the scaled program (kinds jprod / cons / jac, names
         ``iem_rowmax*`` / ``iem_cons_scaled*`` / ``iem_jac_scaled*``): always the LAST kernels ``iem_kernel_info`` lists in
         front of the KKT operator's (``kkt_kernels``), where that exists."""
-        n = self.scaled_prepare()
-        total = C.c_int32()
-        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._kkt_n or 0) - (self._sph_n or 0)
-        return self._kernel_infos(last - n, last)
+        return self._kernels_from_end("scaled")
 
     # ---- the KKT operator in one launch: W·u + Jᵀ·v and J·u ----
     def kkt_prepare(self) -> int:
         """Set up the program of ``kktprod`` now (``iem_kktprod_prepare``: otherwise its first call does — synchronously, and
         not inside a stream capture); the number of its kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_kktprod_prepare(self._h, C.byref(n)))
-        self._kkt_n = int(n.value)
-        return self._kkt_n
+        return self._prepare("kktprod")
 
     def kkt_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the KKT operator (kinds hprod / jprod, names ``iem_kktx*`` /
         ``iem_kkty*``, and the one-launch kernel ``iem_kktprod_all``, kind trial): always the LAST kernels ``iem_kernel_info``
         lists in front of the scaled solver phases' (``scaled_phase_kernels``), where those exist."""
-        n = self.kkt_prepare()
-        total = C.c_int32()
-        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._sph_n or 0)
-        return self._kernel_infos(last - n, last)
+        return self._kernels_from_end("kktprod")
 
     # ---- one launch per solver phase for the scaled NLP ----
     def scaled_phase_prepare(self) -> int:
         """Set up the program of ``eval_trial_scaled`` / ``eval_accepted_scaled`` / ``grad_scaled`` / ``hess_coord_scaled`` now
         (``iem_scaled_phase_prepare``: otherwise their first call does — synchronously, and not inside a stream capture); the
         number of its kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_scaled_phase_prepare(self._h, C.byref(n)))
-        self._sph_n = int(n.value)
-        return self._sph_n
+        return self._prepare("scaled_phase")
 
     def scaled_phase_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of the scaled solver phases (kinds cons / jac / hess / obj /
         grad, names ``iem_sp_*``, and the phase kernels ``iem_sp_trial_all`` / ``iem_sp_accepted_all``, kinds trial /
         accepted): always the LAST kernels ``iem_kernel_info`` lists."""
-        n = self.scaled_phase_prepare()
-        total = C.c_int32()
-        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        return self._kernel_infos(int(total.value) - n, int(total.value))
+        return self._kernels_from_end("scaled_phase")
 
     def _chk_opt(self, t, n: int, name: str):
         """``None`` is the C-ABI's NULL for a zero-length array"""
@@ -423,8 +394,7 @@ class ExaModel:
         g = g if g is not None else self._new(self.meta.nvar)
         self._chk(g, self.meta.nvar, "g")
         self._sync_stream()
-        if self._sph_n is None:
-            self.scaled_phase_prepare()
+        self._ensure("scaled_phase")
         _lib.check(self._L.iem_grad_scaled(self._h, _ptr(x), float(obj_scale), _ptr(g)))
         self.counters.neval_grad += 1
         return g
@@ -436,8 +406,7 @@ class ExaModel:
         vals = vals if vals is not None else self._new(self.meta.nnzh)
         self._chk(vals, self.meta.nnzh, "vals")
         self._sync_stream()
-        if self._sph_n is None:
-            self.scaled_phase_prepare()
+        self._ensure("scaled_phase")
         _lib.check(self._L.iem_hess_coord_scaled(self._h, _ptr(x), _ptr(y), _ptr(s), float(obj_weight), _ptr(vals)))
         self.counters.neval_hess += 1
         return vals
@@ -450,8 +419,7 @@ class ExaModel:
         c = c if c is not None else self._new(self.meta.ncon)
         self._chk(c, self.meta.ncon, "c")
         self._sync_stream()
-        if self._sph_n is None:
-            self.scaled_phase_prepare()
+        self._ensure("scaled_phase")
         out = C.c_double()
         _lib.check(self._L.iem_eval_trial_scaled(self._h, _ptr(x), _ptr(s), float(obj_scale), _ptr(c), None if defer_obj else C.byref(out)))
         self.counters.neval_obj += 1
@@ -467,8 +435,7 @@ class ExaModel:
         hess = hess if hess is not None else self._new(self.meta.nnzh)
         self._chk(g, self.meta.nvar, "g"); self._chk(jac, self.meta.nnzj, "jac"); self._chk(hess, self.meta.nnzh, "hess")
         self._sync_stream()
-        if self._sph_n is None:
-            self.scaled_phase_prepare()
+        self._ensure("scaled_phase")
         _lib.check(self._L.iem_eval_accepted_scaled(self._h, _ptr(x), _ptr(y), _ptr(s), float(obj_scale), float(obj_weight),
                                                     _ptr(g), _ptr(jac), _ptr(hess)))
         self.counters.neval_grad += 1
@@ -490,8 +457,7 @@ class ExaModel:
         out_y = out_y if out_y is not None else self._new(self.meta.ncon)
         self._chk(out_x, self.meta.nvar, "out_x"); self._chk(out_y, self.meta.ncon, "out_y")
         self._sync_stream()
-        if self._kkt_n is None:
-            self.kkt_prepare()
+        self._ensure("kktprod")
         _lib.check(self._L.iem_kktprod(self._h, _ptr(x), _ptr(y), float(obj_weight), _ptr(u), _ptr(v), _ptr(out_x), _ptr(out_y)))
         return out_x, out_y
 
@@ -503,8 +469,7 @@ class ExaModel:
         out = out if out is not None else self._new(self.meta.ncon)
         self._chk(out, self.meta.ncon, "out")
         self._sync_stream()
-        if self._scl_n is None:
-            self.scaled_prepare()
+        self._ensure("scaled")
         _lib.check(self._L.iem_jac_rowmax(self._h, _ptr(x), _ptr(out)))
         return out
 
@@ -514,8 +479,7 @@ class ExaModel:
         c = c if c is not None else self._new(self.meta.ncon)
         self._chk(c, self.meta.ncon, "c")
         self._sync_stream()
-        if self._scl_n is None:
-            self.scaled_prepare()
+        self._ensure("scaled")
         _lib.check(self._L.iem_cons_scaled(self._h, _ptr(x), _ptr(s), _ptr(c)))
         self.counters.neval_cons += 1
         return c
@@ -527,8 +491,7 @@ class ExaModel:
         vals = vals if vals is not None else self._new(self.meta.nnzj)
         self._chk(vals, self.meta.nnzj, "vals")
         self._sync_stream()
-        if self._scl_n is None:
-            self.scaled_prepare()
+        self._ensure("scaled")
         _lib.check(self._L.iem_jac_coord_scaled(self._h, _ptr(x), _ptr(s), _ptr(vals)))
         self.counters.neval_jac += 1
         return vals
@@ -611,9 +574,7 @@ class ExaModel:
     def hppprod_prepare(self) -> int:
         """Set up the program of hppprod now (``iem_hppprod_prepare``: otherwise the first ``hppprod`` does — synchronously,
         and not inside a stream capture); the number of its kernels.  ``param_prepare`` does not include it."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_hppprod_prepare(self._h, C.byref(n)))
-        return int(n.value)
+        return self._prepare("hppprod")
 
     def hppprod_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of hppprod alone (kind hprod of its own program, names
@@ -625,9 +586,7 @@ class ExaModel:
     def param_coord_prepare(self) -> int:
         """Set up the program of ``jacp_coord`` / ``hessp_coord`` now (``iem_param_coord_prepare``: otherwise their first call
         does — synchronously, and not inside a stream capture); the number of its kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_param_coord_prepare(self._h, C.byref(n)))
-        return int(n.value)
+        return self._prepare("param_coord")
 
     def param_coord_nnz(self):
         """``(nnz of Jθ, nnz of Hxθ, nnz of Hθθ)``: the lengths of the three COO blocks (symbolic pattern)."""
@@ -689,24 +648,40 @@ class ExaModel:
         """Launch shape and algorithmic traffic of the kernels of ``jacp_coord`` / ``hessp_coord`` (kinds jac / hess of a
         program of their own, names ``iem_jacp*`` / ``iem_hessp*``): the last kernels ``iem_kernel_info`` lists in front of
         the residual program's (``lagrangian_kernels``) and the scaled program's (``scaled_kernels``), where those exist."""
-        n = self.param_coord_prepare()
-        total = C.c_int32()
-        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
-        last = int(total.value) - (self._lag_n or 0) - (self._scl_n or 0) - (self._kkt_n or 0) - (self._sph_n or 0)
-        return self._kernel_infos(last - n, last)
+        return self._kernels_from_end("param_coord")
 
     def param_prepare(self) -> int:
         """Set up the programs of jpprod / jptprod / hpprod and of hptprod now (``iem_param_prepare``: otherwise the first
         such call does — synchronously, and not inside a stream capture); the number of their kernels."""
-        n = C.c_int32()
-        _lib.check(self._L.iem_param_prepare(self._h, C.byref(n)))
-        return int(n.value)
+        return self._prepare("param")
 
     def param_kernels(self):
         """Launch shape and algorithmic traffic of the kernels of jpprod / jptprod / hpprod (kinds jprod / jtprod / hprod
         of a program of their own, listed behind the model's kernels) and, behind them, of hptprod (kind hprod of ITS
         program, names ``iem_hptprod*``)."""
         return self._kernel_infos(self.meta.n_kernels, self.meta.n_kernels + self.param_prepare())
+
+    def _prepare(self, call: str) -> int:
+        """``iem_<call>_prepare``: the number of kernels of the program(s) it sets up"""
+        n = C.c_int32()
+        _lib.check(getattr(self._L, "iem_%s_prepare" % call)(self._h, C.byref(n)))
+        self._prepared[call] = int(n.value)
+        return self._prepared[call]
+
+    def _ensure(self, call: str) -> None:
+        """What an evaluation method does first: the prepare call, unless it was made (so that ``_prepared`` knows the program)"""
+        if call not in self._prepared:
+            self._prepare(call)
+
+    def _kernels_from_end(self, call: str):
+        """The kernels of the program ``call`` sets up, counted from the END of ``iem_kernel_info``: every program behind it
+        exists only if its prepare call was made here (their evaluation methods make it), while the programs in front of
+        it can be set up by a bare evaluation call that this class never sees."""
+        n = self._prepare(call)
+        total = C.c_int32()
+        _lib.check(self._L.iem_kernel_count(self._h, C.byref(total)))
+        last = int(total.value) - sum(self._prepared.get(c, 0) for c in PREPARE_CALLS[PREPARE_CALLS.index(call) + 1:])
+        return self._kernel_infos(last - n, last)
 
     def _kernel_infos(self, first: int, last: int):
         out = []

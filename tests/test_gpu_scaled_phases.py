@@ -203,6 +203,40 @@ def test_kernel_counts(phases_first, built):
         gm.close(); ref.close()
 
 
+def test_kernel_order_does_not_depend_on_the_order_of_set_up(built):
+    """All seven prepare calls in reverse order on one handle, in forward order on another: iem_kernel_count, every
+    iem_kernel_info entry and every *_kernels() listing agree — the public order is the library's table of programs,
+    not the order in which a caller happened to set them up."""
+    from infiniteexamodels.jl_amd import lib as iemlib
+    from infiniteexamodels.jl_amd.model import ExaModel
+    core, blob, _, _ = model("shifted_pf")
+    prepares = ("param_prepare", "hppprod_prepare", "param_coord_prepare", "lagrangian_prepare", "scaled_prepare", "kkt_prepare", "scaled_phase_prepare")
+    listings = ("param_kernels", "hppprod_kernels", "param_coord_kernels", "lagrangian_kernels", "scaled_kernels", "kkt_kernels", "scaled_phase_kernels")
+    fwd = ExaModel(core, device=0, blob=blob)
+    rev = ExaModel(core, device=0, blob=blob)
+    try:
+        counts = {p: getattr(rev, p)() for p in reversed(prepares)}
+        assert counts == {p: getattr(fwd, p)() for p in prepares} and min(counts.values()) > 0
+        total = _count(fwd)
+        assert total == _count(rev) == fwd.meta.n_kernels + sum(counts.values())
+
+        def info(gm, k):
+            ki = iemlib.KernelInfo()
+            iemlib.check(gm._L.iem_kernel_info(gm._h, k, C.byref(ki)))
+            return ki.name.decode(), int(ki.kind), tuple(ki.grid)
+        for k in range(total):
+            assert info(fwd, k) == info(rev, k), k
+        first = fwd.meta.n_kernels      # ... and it is the order of the prepare calls above: each program's kernels behind the previous one's
+        for p, l in zip(prepares, listings):
+            mine = getattr(fwd, l)()
+            assert mine == getattr(rev, l)() and len(mine) == counts[p]
+            assert [k["name"] for k in mine] == [info(fwd, first + j)[0] for j in range(len(mine))], l
+            first += len(mine)
+        assert first == total
+    finally:
+        fwd.close(); rev.close()
+
+
 def test_the_result_follows_the_current_theta(built):
     from infiniteexamodels.jl_amd.model import ExaModel
     core, blob, om, rows = model("shifted_pf")
