@@ -584,8 +584,8 @@ class KernelBuilder {
         case IEM_OP_SIN: f = B.un(IEM_OP_SIN, x); if (need) { d = B.un(IEM_OP_COS, x); h = B.neg(f); } break;
         case IEM_OP_COS: f = B.un(IEM_OP_COS, x); if (need) { d = B.neg(B.un(IEM_OP_SIN, x)); h = B.neg(f); } break;
         case IEM_OP_TAN: { f = B.un(IEM_OP_TAN, x); if (need) { int u = B.add(Cn(1), B.mul(f, f)); d = u; h = B.mul(B.mul(Cn(2), f), u); } break; }
-        case IEM_OP_ASIN: { f = B.un(IEM_OP_ASIN, x); if (need) { int u = B.sub(Cn(1), B.mul(x, x)); int s = B.un(IEM_OP_SQRT, u); d = B.div(Cn(1), s); h = B.div(x, B.mul(u, s)); } break; }
-        case IEM_OP_ACOS: { f = B.un(IEM_OP_ACOS, x); if (need) { int u = B.sub(Cn(1), B.mul(x, x)); int s = B.un(IEM_OP_SQRT, u); d = B.div(Cn(-1), s); h = B.div(B.neg(x), B.mul(u, s)); } break; }
+        case IEM_OP_ASIN: { f = B.un(IEM_OP_ASIN, x); if (need) { int u = B.mul(B.sub(Cn(1), x), B.add(Cn(1), x)); int s = B.un(IEM_OP_SQRT, u); d = B.div(Cn(1), s); h = B.div(x, B.mul(u, s)); } break; }
+        case IEM_OP_ACOS: { f = B.un(IEM_OP_ACOS, x); if (need) { int u = B.mul(B.sub(Cn(1), x), B.add(Cn(1), x)); int s = B.un(IEM_OP_SQRT, u); d = B.div(Cn(-1), s); h = B.div(B.neg(x), B.mul(u, s)); } break; }
         case IEM_OP_CSC: { int s = B.div(Cn(1), B.un(IEM_OP_SIN, x)); f = s; if (need) { int tt = B.mul(B.un(IEM_OP_COS, x), s); d = B.mul(B.neg(s), tt); h = B.mul(s, B.add(B.mul(tt, tt), B.mul(s, s))); } break; }
         case IEM_OP_SEC: { int c = B.div(Cn(1), B.un(IEM_OP_COS, x)); f = c; if (need) { int tt = B.mul(B.un(IEM_OP_SIN, x), c); d = B.mul(c, tt); h = B.mul(c, B.add(B.mul(tt, tt), B.mul(c, c))); } break; }
         case IEM_OP_COT: { int tt = B.div(Cn(1), B.un(IEM_OP_TAN, x)); f = tt; if (need) { int u = B.add(Cn(1), B.mul(tt, tt)); d = B.neg(u); h = B.mul(B.mul(Cn(2), tt), u); } break; }
@@ -601,12 +601,12 @@ class KernelBuilder {
         case IEM_OP_ACOTD: { f = B.mul(Cn(kR2D), B.un(IEM_OP_ATAN, B.div(Cn(1), x))); if (need) { int u = B.div(Cn(1), B.add(Cn(1), B.mul(x, x))); d = B.mul(Cn(-kR2D), u); h = B.mul(B.mul(B.mul(Cn(kR2D * 2.0), x), u), u); } break; }
         case IEM_OP_SINH: f = B.un(IEM_OP_SINH, x); if (need) { d = B.un(IEM_OP_COSH, x); h = f; } break;
         case IEM_OP_COSH: f = B.un(IEM_OP_COSH, x); if (need) { d = B.un(IEM_OP_SINH, x); h = f; } break;
-        case IEM_OP_TANH: { f = B.un(IEM_OP_TANH, x); if (need) { int u = B.sub(Cn(1), B.mul(f, f)); d = u; h = B.mul(B.mul(Cn(-2), f), u); } break; }
+        case IEM_OP_TANH: { f = B.un(IEM_OP_TANH, x); if (need) { int c = B.div(Cn(1), B.un(IEM_OP_COSH, x)); int u = B.mul(c, c); d = u; h = B.mul(B.mul(Cn(-2), f), u); } break; }
         case IEM_OP_CSCH: { int s = B.div(Cn(1), B.un(IEM_OP_SINH, x)); f = s; if (need) { int tt = B.mul(B.un(IEM_OP_COSH, x), s); d = B.mul(B.neg(s), tt); h = B.mul(s, B.add(B.mul(tt, tt), B.mul(s, s))); } break; }
         case IEM_OP_SECH: { int c = B.div(Cn(1), B.un(IEM_OP_COSH, x)); f = c; if (need) { int tt = B.un(IEM_OP_TANH, x); d = B.mul(B.neg(c), tt); h = B.mul(c, B.sub(B.mul(tt, tt), B.mul(c, c))); } break; }
-        case IEM_OP_COTH: { int tt = B.div(Cn(1), B.un(IEM_OP_TANH, x)); f = tt; if (need) { int u = B.sub(Cn(1), B.mul(tt, tt)); d = u; h = B.mul(B.mul(Cn(-2), tt), u); } break; }
-        case IEM_OP_ATANH: { f = B.un(IEM_OP_ATANH, x); if (need) { int u = B.div(Cn(1), B.sub(Cn(1), B.mul(x, x))); d = u; h = B.mul(B.mul(B.mul(Cn(2), x), u), u); } break; }
-        case IEM_OP_ACOTH: { f = B.un(IEM_OP_ATANH, B.div(Cn(1), x)); if (need) { int u = B.div(Cn(1), B.sub(Cn(1), B.mul(x, x))); d = u; h = B.mul(B.mul(B.mul(Cn(2), x), u), u); } break; }
+        case IEM_OP_COTH: { int tt = B.div(Cn(1), B.un(IEM_OP_TANH, x)); f = tt; if (need) { int s = B.div(Cn(1), B.un(IEM_OP_SINH, x)); int u = B.neg(B.mul(s, s)); d = u; h = B.mul(B.mul(Cn(-2), tt), u); } break; }
+        case IEM_OP_ATANH: { f = B.un(IEM_OP_ATANH, x); if (need) { int u = B.div(Cn(1), B.mul(B.sub(Cn(1), x), B.add(Cn(1), x))); d = u; h = B.mul(B.mul(B.mul(Cn(2), x), u), u); } break; }
+        case IEM_OP_ACOTH: { f = B.un(IEM_OP_ATANH, B.div(Cn(1), x)); if (need) { int u = B.div(Cn(1), B.mul(B.sub(Cn(1), x), B.add(Cn(1), x))); d = u; h = B.mul(B.mul(B.mul(Cn(2), x), u), u); } break; }
         default: throw std::runtime_error("codegen: unsupported unary opcode " + std::to_string(nd.op));
       }
       val[n] = f;

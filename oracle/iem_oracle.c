@@ -158,8 +158,8 @@ static void un_eval(int op, double x, double *f, double *d, double *h) {
     case IEM_OP_SIN: s = sin(x); c = cos(x); *f = s; *d = c; *h = -s; break;
     case IEM_OP_COS: s = sin(x); c = cos(x); *f = c; *d = -s; *h = -c; break;
     case IEM_OP_TAN: t = tan(x); u = 1.0 + t * t; *f = t; *d = u; *h = 2.0 * t * u; break;
-    case IEM_OP_ASIN: u = 1.0 - x * x; s = sqrt(u); *f = asin(x); *d = 1.0 / s; *h = x / (u * s); break;
-    case IEM_OP_ACOS: u = 1.0 - x * x; s = sqrt(u); *f = acos(x); *d = -1.0 / s; *h = -x / (u * s); break;
+    case IEM_OP_ASIN: u = (1.0 - x) * (1.0 + x); s = sqrt(u); *f = asin(x); *d = 1.0 / s; *h = x / (u * s); break;
+    case IEM_OP_ACOS: u = (1.0 - x) * (1.0 + x); s = sqrt(u); *f = acos(x); *d = -1.0 / s; *h = -x / (u * s); break;
     case IEM_OP_CSC: s = 1.0 / sin(x); t = cos(x) * s; *f = s; *d = -s * t; *h = s * (t * t + s * s); break;
     case IEM_OP_SEC: c = 1.0 / cos(x); t = sin(x) * c; *f = c; *d = c * t; *h = c * (t * t + c * c); break;
     case IEM_OP_COT: t = 1.0 / tan(x); u = 1.0 + t * t; *f = t; *d = -u; *h = 2.0 * t * u; break;
@@ -175,12 +175,12 @@ static void un_eval(int op, double x, double *f, double *d, double *h) {
     case IEM_OP_ACOTD: u = 1.0 / (1.0 + x * x); *f = R2D * atan(1.0 / x); *d = -R2D * u; *h = R2D * 2.0 * x * u * u; break;
     case IEM_OP_SINH: s = sinh(x); c = cosh(x); *f = s; *d = c; *h = s; break;
     case IEM_OP_COSH: s = sinh(x); c = cosh(x); *f = c; *d = s; *h = c; break;
-    case IEM_OP_TANH: t = tanh(x); u = 1.0 - t * t; *f = t; *d = u; *h = -2.0 * t * u; break;
+    case IEM_OP_TANH: t = tanh(x); c = 1.0 / cosh(x); u = c * c; *f = t; *d = u; *h = -2.0 * t * u; break;
     case IEM_OP_CSCH: s = 1.0 / sinh(x); t = cosh(x) * s; *f = s; *d = -s * t; *h = s * (t * t + s * s); break;
     case IEM_OP_SECH: c = 1.0 / cosh(x); t = tanh(x); *f = c; *d = -c * t; *h = c * (t * t - c * c); break;
-    case IEM_OP_COTH: t = 1.0 / tanh(x); u = 1.0 - t * t; *f = t; *d = u; *h = -2.0 * t * u; break;
-    case IEM_OP_ATANH: u = 1.0 / (1.0 - x * x); *f = atanh(x); *d = u; *h = 2.0 * x * u * u; break;
-    case IEM_OP_ACOTH: u = 1.0 / (1.0 - x * x); *f = atanh(1.0 / x); *d = u; *h = 2.0 * x * u * u; break;
+    case IEM_OP_COTH: t = 1.0 / tanh(x); s = 1.0 / sinh(x); u = -(s * s); *f = t; *d = u; *h = -2.0 * t * u; break;
+    case IEM_OP_ATANH: u = 1.0 / ((1.0 - x) * (1.0 + x)); *f = atanh(x); *d = u; *h = 2.0 * x * u * u; break;
+    case IEM_OP_ACOTH: u = 1.0 / ((1.0 - x) * (1.0 + x)); *f = atanh(1.0 / x); *d = u; *h = 2.0 * x * u * u; break;
     default: *f = *d = *h = NAN;
   }
 }
@@ -197,7 +197,9 @@ static double bin_val(int op, double a, double b) {
 }
 
 /* partials of a binary op; `need` = FX_NONE (all), FX_FIRST (wrt b only), FX_SECOND (wrt a only) */
-static void bin_partials(int op, double a, double b, int need, double *y1, double *y2, double *h11,
+/* `bconst`: the second operand is a constant NODE — the generator folds a product with a zero constant away
+   (KernelBuilder::mul), so a pow term whose coefficient is such a zero contributes 0, not 0 * pow(a, b - k) */
+static void bin_partials(int op, double a, double b, int need, int bconst, double *y1, double *y2, double *h11,
                          double *h12, double *h22) {
   *y1 = *y2 = *h11 = *h12 = *h22 = 0.0;
   switch (op) {
@@ -214,8 +216,8 @@ static void bin_partials(int op, double a, double b, int need, double *y1, doubl
     }
     case IEM_OP_POW: {
       if (need != FX_FIRST) {
-        *y1 = b * pow(a, b - 1.0);
-        *h11 = b * (b - 1.0) * pow(a, b - 2.0);
+        *y1 = (bconst && b == 0.0) ? 0.0 : b * pow(a, b - 1.0);
+        *h11 = (bconst && b * (b - 1.0) == 0.0) ? 0.0 : b * (b - 1.0) * pow(a, b - 2.0);
       }
       if (need != FX_SECOND) {
         double la = log(a), p = pow(a, b);
@@ -562,7 +564,7 @@ static void forward(const orc_model *m, const otpl *t, int64_t k, const double *
           s->val[n] = bin_val(nd->op, a, b);
           if (order >= 1 && nd->kind != K_REAL) {
             double y1, y2, h11, h12, h22;
-            bin_partials(nd->op, a, b, nd->fixed, &y1, &y2, &h11, &h12, &h22);
+            bin_partials(nd->op, a, b, nd->fixed, t->nodes[nd->b].op == IEM_OP_CONST, &y1, &y2, &h11, &h12, &h22);
             if (nd->fixed == FX_FIRST) { s->y1[n] = y2; s->h11[n] = h22; }      /* unary in b */
             else if (nd->fixed == FX_SECOND) { s->y1[n] = y1; s->h11[n] = h11; } /* unary in a */
             else { s->y1[n] = y1; s->y2[n] = y2; s->h11[n] = h11; s->h12[n] = h12; s->h22[n] = h22; }
@@ -602,41 +604,55 @@ typedef struct {
   double *coo; /* hess values block of this item */
 } hctx;
 
-static int hdrpass(const hctx *c, int n1, int n2, int cnt, double adj) {
+/* Structural zeros.  The sweep starts from the second-order adjoint 0, and the partials of some nodes are the CONSTANT 0 (the
+   second derivative of neg / pos / abs, of + - *, of a / b in a).  The generator folds a product with such a constant away
+   (KernelBuilder::mul), so the kernels add nothing there — also where the other factor is infinite (sqrt'(0)² and the like),
+   which 0 * inf would turn into NaN.  `z` / `z2`: the adjoint passed down is still such a constant 0. */
+static int h11_zero(const onode *nd) {      /* ... of what forward() left in h11[n] */
+  if (IEM_OP_IS_UNARY(nd->op)) return nd->op == IEM_OP_NEG || nd->op == IEM_OP_POS || nd->op == IEM_OP_ABS;
+  if (nd->op == IEM_OP_ADD || nd->op == IEM_OP_SUB || nd->op == IEM_OP_MUL) return 1;
+  return nd->op == IEM_OP_DIV && !(nd->kind == K_N1 && nd->fixed == FX_FIRST);
+}
+static int h22_zero(const onode *nd) { return nd->op == IEM_OP_ADD || nd->op == IEM_OP_SUB || nd->op == IEM_OP_MUL; }
+static int h12_zero(const onode *nd) { return nd->op == IEM_OP_ADD || nd->op == IEM_OP_SUB; }
+
+static int hdrpass(const hctx *c, int n1, int n2, int cnt, double adj, int z) {
   const onode *a = &c->t->nodes[n1], *b = &c->t->nodes[n2];
   const scratch *s = c->s;
+#define ADJ(e) (z ? 0.0 : (e))
   if (a->kind == K_REAL || b->kind == K_REAL) return cnt;
   if (a->kind == K_VAR && b->kind == K_VAR) {
     if (s->idx[a->a] == s->idx[b->a]) c->coo[c->t->comp2[cnt]] += 2.0 * adj;
     else c->coo[c->t->comp2[cnt]] += adj;
     return cnt + 1;
   } else if (a->kind == K_N1 && b->kind == K_N1) {
-    return hdrpass(c, a->inner, b->inner, cnt, adj * s->y1[n1] * s->y1[n2]);
+    return hdrpass(c, a->inner, b->inner, cnt, ADJ(adj * s->y1[n1] * s->y1[n2]), z);
   } else if (a->kind == K_VAR && b->kind == K_N1) {
-    return hdrpass(c, n1, b->inner, cnt, adj * s->y1[n2]);
+    return hdrpass(c, n1, b->inner, cnt, ADJ(adj * s->y1[n2]), z);
   } else if (a->kind == K_N1 && b->kind == K_VAR) {
-    return hdrpass(c, a->inner, n2, cnt, adj * s->y1[n1]);
+    return hdrpass(c, a->inner, n2, cnt, ADJ(adj * s->y1[n1]), z);
   } else if (a->kind == K_N2 && b->kind == K_N2) {
-    cnt = hdrpass(c, a->a, b->a, cnt, adj * s->y1[n1] * s->y1[n2]);
-    cnt = hdrpass(c, a->a, b->b, cnt, adj * s->y1[n1] * s->y2[n2]);
-    cnt = hdrpass(c, a->b, b->a, cnt, adj * s->y2[n1] * s->y1[n2]);
-    return hdrpass(c, a->b, b->b, cnt, adj * s->y2[n1] * s->y2[n2]);
+    cnt = hdrpass(c, a->a, b->a, cnt, ADJ(adj * s->y1[n1] * s->y1[n2]), z);
+    cnt = hdrpass(c, a->a, b->b, cnt, ADJ(adj * s->y1[n1] * s->y2[n2]), z);
+    cnt = hdrpass(c, a->b, b->a, cnt, ADJ(adj * s->y2[n1] * s->y1[n2]), z);
+    return hdrpass(c, a->b, b->b, cnt, ADJ(adj * s->y2[n1] * s->y2[n2]), z);
   } else if (a->kind == K_N1 && b->kind == K_N2) {
-    cnt = hdrpass(c, a->inner, b->a, cnt, adj * s->y1[n1] * s->y1[n2]);
-    return hdrpass(c, a->inner, b->b, cnt, adj * s->y1[n1] * s->y2[n2]);
+    cnt = hdrpass(c, a->inner, b->a, cnt, ADJ(adj * s->y1[n1] * s->y1[n2]), z);
+    return hdrpass(c, a->inner, b->b, cnt, ADJ(adj * s->y1[n1] * s->y2[n2]), z);
   } else if (a->kind == K_N2 && b->kind == K_N1) {
-    cnt = hdrpass(c, a->a, b->inner, cnt, adj * s->y1[n1] * s->y1[n2]);
-    return hdrpass(c, a->b, b->inner, cnt, adj * s->y2[n1] * s->y1[n2]);
+    cnt = hdrpass(c, a->a, b->inner, cnt, ADJ(adj * s->y1[n1] * s->y1[n2]), z);
+    return hdrpass(c, a->b, b->inner, cnt, ADJ(adj * s->y2[n1] * s->y1[n2]), z);
   } else if (a->kind == K_VAR && b->kind == K_N2) {
-    cnt = hdrpass(c, n1, b->a, cnt, adj * s->y1[n2]);
-    return hdrpass(c, n1, b->b, cnt, adj * s->y2[n2]);
+    cnt = hdrpass(c, n1, b->a, cnt, ADJ(adj * s->y1[n2]), z);
+    return hdrpass(c, n1, b->b, cnt, ADJ(adj * s->y2[n2]), z);
   } else { /* N2 x VAR */
-    cnt = hdrpass(c, a->a, n2, cnt, adj * s->y1[n1]);
-    return hdrpass(c, a->b, n2, cnt, adj * s->y2[n1]);
+    cnt = hdrpass(c, a->a, n2, cnt, ADJ(adj * s->y1[n1]), z);
+    return hdrpass(c, a->b, n2, cnt, ADJ(adj * s->y2[n1]), z);
   }
+#undef ADJ
 }
 
-static int hrpass(const hctx *c, int n, int cnt, double adj, double adj2) {
+static int hrpass(const hctx *c, int n, int cnt, double adj, double adj2, int z2) {
   const onode *nd = &c->t->nodes[n];
   const scratch *s = c->s;
   switch (nd->kind) {
@@ -645,33 +661,35 @@ static int hrpass(const hctx *c, int n, int cnt, double adj, double adj2) {
       return cnt + 1;
     case K_N1: {
       double y = s->y1[n];
-      return hrpass(c, nd->inner, cnt, adj * y, adj2 * (y * y) + adj * s->h11[n]);
+      int hz = h11_zero(nd);
+      return hrpass(c, nd->inner, cnt, adj * y, (z2 ? 0.0 : adj2 * (y * y)) + (hz ? 0.0 : adj * s->h11[n]), z2 && hz);
     }
     case K_N2: {
       double y1 = s->y1[n], y2 = s->y2[n];
-      double adj2y1y2 = adj2 * y1 * y2;
-      double adjh12 = adj * s->h12[n];
-      cnt = hrpass(c, nd->a, cnt, adj * y1, adj2 * (y1 * y1) + adj * s->h11[n]);
-      cnt = hrpass(c, nd->b, cnt, adj * y2, adj2 * (y2 * y2) + adj * s->h22[n]);
-      return hdrpass(c, nd->a, nd->b, cnt, adj2y1y2 + adjh12);
+      int z11 = h11_zero(nd), z22 = h22_zero(nd), z12 = h12_zero(nd);
+      double adj2y1y2 = z2 ? 0.0 : adj2 * y1 * y2;
+      double adjh12 = z12 ? 0.0 : adj * s->h12[n];
+      cnt = hrpass(c, nd->a, cnt, adj * y1, (z2 ? 0.0 : adj2 * (y1 * y1)) + (z11 ? 0.0 : adj * s->h11[n]), z2 && z11);
+      cnt = hrpass(c, nd->b, cnt, adj * y2, (z2 ? 0.0 : adj2 * (y2 * y2)) + (z22 ? 0.0 : adj * s->h22[n]), z2 && z22);
+      return hdrpass(c, nd->a, nd->b, cnt, adj2y1y2 + adjh12, z2 && z12);
     }
     default: return cnt;
   }
 }
 
-static int hrpass0(const hctx *c, int n, int cnt, double adj, double adj2) {
+static int hrpass0(const hctx *c, int n, int cnt, double adj, double adj2, int z2) {
   const onode *nd = &c->t->nodes[n];
   const scratch *s = c->s;
   if (nd->kind == K_VAR || nd->kind == K_REAL) return cnt;
   if (is_linear_n1(nd)) {
     double y = s->y1[n];
-    return hrpass0(c, nd->inner, cnt, adj * y, adj2 * (y * y));
+    return hrpass0(c, nd->inner, cnt, adj * y, z2 ? 0.0 : adj2 * (y * y), z2);
   }
   if (nd->kind == K_N2 && (nd->op == IEM_OP_ADD || nd->op == IEM_OP_SUB)) {
-    cnt = hrpass0(c, nd->a, cnt, adj * s->y1[n], adj2);
-    return hrpass0(c, nd->b, cnt, adj * s->y2[n], adj2);
+    cnt = hrpass0(c, nd->a, cnt, adj * s->y1[n], adj2, z2);
+    return hrpass0(c, nd->b, cnt, adj * s->y2[n], adj2, z2);
   }
-  return hrpass(c, n, cnt, adj, adj2);
+  return hrpass(c, n, cnt, adj, adj2, z2);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -814,7 +832,7 @@ void orc_hess_coord(const orc_model *m, const double *x, const double *y, double
         forward(m, t, k, x, s, 2);
         hctx c = {t, s, vals + t->o2 + (int64_t)t->o2step * k};
         double adj = t->kind == IEM_T_OBJ ? obj_weight : y[t->o0 + k];
-        hrpass0(&c, t->root, 0, adj, 0.0);
+        hrpass0(&c, t->root, 0, adj, 0.0, 1);
       }
     }
     scratch_free(s);
