@@ -688,6 +688,93 @@ int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y,
 /* HIP source of kkt_gather_d / kkt_residual_dm / kkt_axpy_m and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_kkt_diag_source(char **out_src, uint64_t *out_key);
 
+/* ---- the interior-point barrier layer -------------------------------------------------------------------------------------------
+ * What sits between the evaluation calls and the KKT object in a primal-dual interior-point iteration (Ipopt / MadNLP with
+ * eliminated slacks), as an object beside iem_kkt: the barrier diagonal, the condensed right-hand side, the slack and bound-
+ * multiplier directions, the fraction-to-the-boundary step lengths, the update with the multiplier safeguard, Ipopt's error terms.
+ * Sign convention  grad f + J'y − zL + zU = 0.  Rows with lcon == ucon are equalities (c = ceq); every other row is an inequality
+ * with an eliminated slack s:  c − s = 0,  rl <= s <= ru.  Relaxed bounds, formed on the host at create time:
+ *     xl = lvar − relax·max(1, |lvar|),  xu = uvar + relax·max(1, |uvar|)  where finite (∓inf otherwise);  rl / ru likewise from the
+ *     lcon / ucon of inequality rows;  ceq = lcon, unrelaxed.
+ * State vectors are FULL LENGTH, nothing is compacted: x, zL, zU (and dzL, dzU) have nvar entries; s, vL, vU, ds, dvL, dvU have ncon
+ * entries of which those on equality rows are never read and never written.  zL[i] / zU[i] / vL[j] / vU[j] are read only where that
+ * bound is present (a finite relaxed bound — for v*: of an inequality row).  An absent bound contributes an exact +0.0.
+ * Gaps  dL = x − xl, dU = xu − x, eL = s − rl, eU = ru − s.  Every operation below is rounded once, in the order written (the code
+ * object is compiled with -ffp-contract=off):
+ *     sigma_i = (hasL ? zL/dL : 0) + (hasU ? zU/dU : 0)        gb_i = (hasU ? mu/dU : 0) − (hasL ? mu/dL : 0)     rhs_x_i = −(r_i + gb_i)
+ *     sigs_j  = (gL ? vL/eL : 0) + (gU ? vU/eU : 0)            gs_j = (gU ? mu/eU : 0) − (gL ? mu/eL : 0)
+ *     rs_j    = gs_j − y_j                                     inv_j = 1.0/sigs_j
+ *     equality row:    dcon_j = 0.0     rhs_y_j = −(c_j − ceq_j)
+ *     inequality row:  dcon_j = inv_j   rhs_y_j = −((c_j − s_j) + rs_j·inv_j)
+ *     ds_j  = (dy_j − rs_j)/sigs_j                                                                 (inequality rows)
+ *     dzL_i = hasL ? (mu/dL − zL) − (zL/dL)·dx : 0             dzU_i = hasU ? (mu/dU − zU) + (zU/dU)·dx : 0
+ *     dvL_j, dvU_j: the same with (eL, eU, vL, vU, ds)
+ * K = [W + diag(sigma) + delta_w I, J'; J, −diag(dcon + delta_c)] with this rhs is the system iem_kkt_assemble_diag /
+ * iem_kkt_solve_refined_diag solve; sol = [dx; dy].  r = obj_weight·grad f + J'y is what iem_eval_residual writes.
+ *
+ * iem_barrier_create: h_lvar / h_uvar (nvar) and h_lcon / h_ucon (ncon) host arrays, each NULL = the handle's own mirror
+ *     (iem_get_host); a scaled solver passes its scaled row bounds.  Loads the code object (first object of the handle), uploads
+ *     the bounds, allocates everything the calls below use.  IEM_E_ARG: a sharded handle, relax < 0, relax == 0 with a fixed
+ *     variable (lvar == uvar), a row with neither bound, lvar > uvar or lcon > ucon.  The object borrows the model handle (stream,
+ *     device, kernel cache): destroy it before iem_destroy(m).
+ * iem_barrier_start:  Ipopt's bound_push / bound_frac projection, for a bound pair (lo, hi) of which `both` are present:
+ *     pl = bound_push·max(|lo|, 1), pu = bound_push·max(|hi|, 1), both: pl = min(pl, bound_frac·(hi − lo)), pu likewise;
+ *     v = max(v, lo + pl) where lo is present, then v = min(v, hi − pu) where hi is.  x is projected in place, s = that projection of
+ *     c on inequality rows; zL, zU = 1.0 where present and 0.0 elsewhere, vL, vU likewise on inequality rows.
+ * iem_barrier_terms:  sigma (nvar), dcon (ncon), rhs (nvar + ncon) as above.
+ * iem_barrier_step:   ds, dzL, dzU, dvL, dvU from d_sol = [dx; dy], and d_alpha[0] = alpha_primal, d_alpha[1] = alpha_dual:
+ *     alpha = min(1, candidates) with the candidates ((−tau)·gapL)/d where d < 0 and the lower bound is present, (tau·gapU)/d where
+ *     d > 0 and the upper bound is present (d = dx on x, ds on s), and ((−tau)·z)/dz where dz < 0 for the four multiplier vectors.
+ *     The minimum is an integer minimum on the bit patterns (order-independent; the slots are seeded with the bits of 1.0 by a
+ *     device-to-device copy).  A candidate that is not > 0 — a NaN or non-positive gap in the state, met by a direction that moves
+ *     towards that bound — enters as +0.0, and so does a NaN anywhere in a direction: in dx, dy or ds for alpha_primal, in dzL, dzU,
+ *     dvL or dvU (present bounds) for alpha_dual.  (A point exactly on a bound with a direction that leaves it inwards gives no
+ *     candidate; its sigma is inf.)  ALPHA = +0.0 MEANS THE STATE OR THE DIRECTION WAS UNUSABLE, and
+ * iem_barrier_update with either step length +0.0 writes nothing: every state bit stays.  Otherwise  x += alpha_p·dx,
+ *     s += alpha_p·ds, y += alpha_p·dy, z* += alpha_d·dz*, v* += alpha_d·dv*  (the step lengths read from d_alpha on the device) and
+ *     then, with the NEW gaps, per present bound  z = min(max(z, mu/(kappa_sigma·gap)), (kappa_sigma·mu)/gap).
+ * iem_barrier_error:  d_out[0] = max_i |r − zL + zU|, [1] = max_j |−y − vL + vU| over inequality rows, [2] = max_j |infeasibility|
+ *     (c − ceq on equality rows, c − s on inequality rows), [3] = max |gap·z − mu| over present bounds, [4] = sum |y|, [5] = sum of
+ *     the present multipliers, [6] = theta = sum_j |infeasibility|, [7] = sum log gap over present bounds.  The maxima are integer
+ *     maxima on the bit patterns (a NaN wins); the sums are reduced in a fixed order (per workgroup, then by the workgroup that
+ *     finishes last): bitwise reproducible, no float atomic.  d_r == NULL: d_out[0] is written as NaN.
+ * iem_barrier_merit:  d_out[0] = theta, d_out[1] = sum log gap at a trial (x, s, c): the bits iem_barrier_error writes to [6], [7].
+ * All six run on the handle's stream, one launch each (step: a 16-byte copy in front, error: a 32-byte memset), asynchronous, without
+ * synchronisation, allocation or host copy: graph-capturable.  Entries of the device vectors are never inspected.  IEM_E_ARG before
+ * any device work: null required pointers (s, vL, vU, ds, dvL, dvU may be NULL without inequality rows; y, c, dcon without rows),
+ * tau outside (0, 1], mu < 0, kappa_sigma < 1, bound_push <= 0, bound_frac outside (0, 0.5]. */
+typedef struct iem_barrier iem_barrier;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_barrier_info_t): at most that many bytes are written */
+  int64_t nvar, ncon, n_eq, n_ineq;
+  int64_t n_xl, n_xu, n_sl, n_su;       /* present lower / upper bounds of x, of the inequality rows' slacks */
+  int64_t nz;                           /* their sum: the number of bound multipliers */
+  int64_t workgroups;                   /* of every launch (256 threads each, grid-stride over nvar + ncon entries) */
+} iem_barrier_info_t;
+int iem_barrier_create(iem_model *m, const double *h_lvar, const double *h_uvar, const double *h_lcon, const double *h_ucon, double relax, iem_barrier **out);
+/* the host analysis alone (no device needed), with iem_barrier_create's refusals: h_bounds (2 nvar + 3 ncon doubles) = xl | xu | rl | ru |
+ * ceq (rl / ru = ∓inf and ceq = lcon on equality rows, ceq = 0 elsewhere), h_flags (nvar + ncon bytes): bit 0 / 1 = the lower / upper
+ * bound is present, bit 2 = equality row; info as iem_barrier_info fills it */
+int iem_barrier_analyse(int64_t nvar, int64_t ncon, const double *h_lvar, const double *h_uvar, const double *h_lcon, const double *h_ucon, double relax,
+                        double *h_bounds, uint8_t *h_flags, iem_barrier_info_t *info);
+int iem_barrier_destroy(iem_barrier *b);
+int iem_barrier_info(const iem_barrier *b, iem_barrier_info_t *out);
+int iem_barrier_start(iem_barrier *b, double *d_x, const double *d_c, double *d_s, double *d_zL, double *d_zU, double *d_vL, double *d_vU, double bound_push,
+                      double bound_frac);
+int iem_barrier_terms(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                      const double *d_vU, const double *d_r, const double *d_c, double mu, double *d_sigma, double *d_dcon, double *d_rhs);
+int iem_barrier_step(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                     const double *d_vU, const double *d_sol, double mu, double tau, double *d_ds, double *d_dzL, double *d_dzU, double *d_dvL, double *d_dvU,
+                     double *d_alpha /* 2 */);
+int iem_barrier_update(iem_barrier *b, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
+                       const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha, double mu,
+                       double kappa_sigma);
+int iem_barrier_error(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                      const double *d_vU, const double *d_r /* nvar | NULL */, const double *d_c, double mu, double *d_out /* 8 */);
+int iem_barrier_merit(iem_barrier *b, const double *d_x, const double *d_s, const double *d_c, double *d_out /* 2 */);
+/* HIP source of the six kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_barrier_source(char **out_src, uint64_t *out_key);
+
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache

@@ -1,0 +1,189 @@
+"""The interior-point barrier layer of the C-ABI (``iem_barrier_*``, ``csrc/iem_barrier_device.h``) held from Python: what a
+primal-dual interior-point method computes between the evaluation calls and the KKT solver object — the barrier diagonal ``Σ``,
+``Σs⁻¹``, the condensed right-hand side, the slack and bound-multiplier directions, the fraction-to-the-boundary step lengths, the
+update with the multiplier safeguard, Ipopt's error terms — one launch per call, every scalar on the device.
+
+Formulation (``include/iem.h`` has the per-entry contract): ``∇f + Jᵀy − zL + zU = 0``; rows with ``lcon == ucon`` are equalities,
+every other row has an eliminated slack ``s``.  All vectors are full length: ``x, zL, zU`` have ``nvar`` entries, ``s, vL, vU`` (and
+``ds, dvL, dvU``) have ``ncon`` entries of which those on equality rows are never read and never written.
+
+    with BarrierLayer(model) as bar:
+        state = bar.start(x0, model.cons(x0))                      # (x, s, y, zL, zU, vL, vU)
+        _, c, r = model.eval_residual(state[0], state[2])
+        sigma, dcon, rhs = bar.terms(state, r, c, mu)              # -> KKTObject.assemble(..., sigma, dw, dc, dcon=dcon), solve(rhs)
+        dirs, alpha = bar.step(state, sol, mu, tau)                # (ds, dzL, dzU, dvL, dvU), device tensor of two
+        bar.update(state, sol, dirs, alpha, mu)                    # in place
+        out = bar.error(state, r, c, mu)                           # device tensor of eight
+
+Nothing above reads a value back; :meth:`BarrierLayer.optimality_error` is the only place that does."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _lib
+
+STATE = ("x", "s", "y", "zL", "zU", "vL", "vU")
+DIRECTIONS = ("ds", "dzL", "dzU", "dvL", "dvU")
+
+
+class BarrierLayer:
+    """``BarrierLayer(model, relax=1e-8, bounds=None)``: ``bounds = (lvar, uvar, lcon, ucon)`` host arrays, any of them ``None`` for
+    the model's own (a scaled solver passes its scaled row bounds).  Tensors are contiguous float64 CUDA tensors of the model's
+    device; every method takes ``out=`` and allocates what is not given."""
+
+    def __init__(self, model, relax: float = 1e-8, bounds=None):
+        import torch
+        self._torch = torch
+        self.model = model
+        self.nvar, self.ncon = int(model.meta.nvar), int(model.meta.ncon)
+        self.n = self.nvar + self.ncon
+        self._b = None
+        arrs = []
+        for a, n in zip(bounds if bounds is not None else (None,) * 4, (self.nvar, self.nvar, self.ncon, self.ncon)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != (n,):
+                    raise ValueError(f"bounds: an array of {n} entries expected, got shape {a.shape}")
+            arrs.append(a)
+        b = C.c_void_p()
+        _lib.check(model._L.iem_barrier_create(model._h, *[a.ctypes.data if a is not None else None for a in arrs], float(relax), C.byref(b)))
+        self._b = b
+        info = _lib.BarrierInfo()
+        info.struct_size = C.sizeof(_lib.BarrierInfo)
+        _lib.check(model._L.iem_barrier_info(b, C.byref(info)))
+        self.info = {name: int(getattr(info, name)) for name, _ in _lib.BarrierInfo._fields_ if name != "struct_size"}
+        self.relax = float(relax)
+
+    # ---- plumbing ----------------------------------------------------------------------------------------------
+    def _handle(self):
+        if self._b is None:
+            raise _lib.IemError("BarrierLayer: closed")
+        self.model._sync_stream()
+        return self.model._L, self._b
+
+    def _vec(self, t, n: int, name: str, optional: bool = False):
+        if t is None:
+            if optional or n == 0:
+                return None
+            raise ValueError(f"{name} is missing")
+        self.model._chk(t, n, name)
+        return C.c_void_p(t.data_ptr())
+
+    def _state(self, state):
+        if len(state) != 7:
+            raise ValueError("state: (x, s, y, zL, zU, vL, vU)")
+        sizes = (self.nvar, self.ncon, self.ncon, self.nvar, self.nvar, self.ncon, self.ncon)
+        slack = self.info["n_ineq"] == 0
+        return [self._vec(t, n, name, optional=slack and name in ("s", "vL", "vU")) for t, n, name in zip(state, sizes, STATE)]
+
+    def _dirs(self, dirs):
+        if len(dirs) != 5:
+            raise ValueError("dirs: (ds, dzL, dzU, dvL, dvU)")
+        sizes = (self.ncon, self.nvar, self.nvar, self.ncon, self.ncon)
+        slack = self.info["n_ineq"] == 0
+        return [self._vec(t, n, name, optional=slack and name in ("ds", "dvL", "dvU")) for t, n, name in zip(dirs, sizes, DIRECTIONS)]
+
+    def _new(self, n: int):
+        return self.model._new(n)
+
+    # ---- the six calls -----------------------------------------------------------------------------------------
+    def start(self, x, c, y=None, bound_push: float = 1e-2, bound_frac: float = 1e-2, out=None):
+        """Ipopt's ``bound_push`` / ``bound_frac`` projection (``iem_barrier_start``): ``x`` is projected IN PLACE, ``s`` is the
+        projection of ``c`` on inequality rows, the bound multipliers are 1 where their bound is present.  Returns the state
+        ``(x, s, y, zL, zU, vL, vU)``; ``y`` (default: zeros) is passed through; ``out = (s, zL, zU, vL, vU)`` to reuse buffers.
+        Entries of ``s, vL, vU`` on equality rows keep what the buffer held."""
+        s, zL, zU, vL, vU = out if out is not None else (self._new(self.ncon), self._new(self.nvar), self._new(self.nvar), self._new(self.ncon), self._new(self.ncon))
+        y = y if y is not None else self._torch.zeros(self.ncon, dtype=self._torch.float64, device=self.model.device)
+        state = (x, s, y, zL, zU, vL, vU)
+        p = self._state(state)
+        pc = self._vec(c, self.ncon, "c")
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_start(b, p[0], pc, p[1], p[3], p[4], p[5], p[6], float(bound_push), float(bound_frac)))
+        return state
+
+    def terms(self, state, r, c, mu: float, out=None):
+        """``(sigma, dcon, rhs)`` (``iem_barrier_terms``): exactly the inputs of ``iem_kkt_assemble_diag`` /
+        ``iem_kkt_solve_refined_diag``.  ``r = obj_weight·∇f + Jᵀy`` and ``c`` are what ``ExaModel.eval_residual`` writes."""
+        sigma, dcon, rhs = out if out is not None else (self._new(self.nvar), self._new(self.ncon), self._new(self.n))
+        p = self._state(state)
+        args = (self._vec(r, self.nvar, "r"), self._vec(c, self.ncon, "c"), float(mu), self._vec(sigma, self.nvar, "sigma"), self._vec(dcon, self.ncon, "dcon"),
+                self._vec(rhs, self.n, "rhs"))
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_terms(b, *p, *args))
+        return sigma, dcon, rhs
+
+    def step(self, state, sol, mu: float, tau: float, out=None, alpha=None):
+        """``((ds, dzL, dzU, dvL, dvU), alpha)`` from ``sol = [dx; dy]`` (``iem_barrier_step``).  ``alpha``: a DEVICE tensor
+        ``(alpha_primal, alpha_dual)``; ``+0.0`` means the state or the direction was unusable."""
+        dirs = out if out is not None else (self._new(self.ncon), self._new(self.nvar), self._new(self.nvar), self._new(self.ncon), self._new(self.ncon))
+        alpha = alpha if alpha is not None else self._new(2)
+        p, d = self._state(state), self._dirs(dirs)
+        ps, pa = self._vec(sol, self.n, "sol"), self._vec(alpha, 2, "alpha")
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_step(b, *p, ps, float(mu), float(tau), *d, pa))
+        return dirs, alpha
+
+    def update(self, state, sol, dirs, alpha, mu: float, kappa_sigma: float = 1e10):
+        """The accepted step IN PLACE with the step lengths read from the device tensor ``alpha``, then the safeguard of the bound
+        multipliers with the new gaps (``iem_barrier_update``).  A step length of ``+0.0`` moves nothing.  Returns ``state``."""
+        p, d = self._state(state), self._dirs(dirs)
+        ps, pa = self._vec(sol, self.n, "sol"), self._vec(alpha, 2, "alpha")
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_update(b, *p, ps, *d, pa, float(mu), float(kappa_sigma)))
+        return state
+
+    def error(self, state, r, c, mu: float = 0.0, out=None):
+        """The eight numbers of ``iem_barrier_error`` as a device tensor: max |r − zL + zU|, max |−y − vL + vU|, max |infeasibility|,
+        max |gap·z − mu|, Σ|y|, Σ multipliers, θ = Σ|infeasibility|, Σ log gap.  ``r = None``: entry 0 is NaN."""
+        out = out if out is not None else self._new(8)
+        p = self._state(state)
+        args = (self._vec(r, self.nvar, "r", optional=True), self._vec(c, self.ncon, "c"), float(mu), self._vec(out, 8, "out"))
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_error(b, *p, *args))
+        return out
+
+    def merit(self, x, s, c, out=None):
+        """``(θ, Σ log gap)`` at a trial point as a device tensor (``iem_barrier_merit``): the bits of ``error``'s entries 6, 7."""
+        out = out if out is not None else self._new(2)
+        args = (self._vec(x, self.nvar, "x"), self._vec(s, self.ncon, "s", optional=self.info["n_ineq"] == 0), self._vec(c, self.ncon, "c"), self._vec(out, 2, "out"))
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_merit(b, *args))
+        return out
+
+    # ---- the one read-back -------------------------------------------------------------------------------------
+    @staticmethod
+    def optimality_error(out, mu_counts):
+        """Ipopt's scaled optimality error ``E_μ`` from the eight numbers of :meth:`error` (a tensor: THIS is the read-back; or a
+        sequence of floats) and the static counts ``mu_counts = (ncon, nz)`` (``info["ncon"]``, ``info["nz"]``):
+        ``s_d = max(100, (Σ|y| + Σz)/(ncon + nz))/100``, ``s_c = max(100, Σz/nz)/100`` and
+        ``(max(e_d, e_p, e_c), e_d, e_p, e_c)`` with ``e_d = max(out[0], out[1])/s_d``, ``e_p = out[2]``, ``e_c = out[3]/s_c``."""
+        v = [float(a) for a in (out.tolist() if hasattr(out, "tolist") else out)]
+        m, nz = int(mu_counts[0]), int(mu_counts[1])
+        sd = max(100.0, (v[4] + v[5]) / max(1, m + nz)) / 100.0
+        sc = max(100.0, v[5] / max(1, nz)) / 100.0
+        ed = max(v[0], v[1]) / sd
+        ep = v[2] if m else 0.0
+        ec = v[3] / sc if nz else 0.0
+        return max(ed, ep, ec), ed, ep, ec
+
+    # ---- lifetime ----------------------------------------------------------------------------------------------
+    def close(self):
+        if self._b is not None:
+            _lib.check(self.model._L.iem_barrier_destroy(self._b))
+            self._b = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if getattr(self.model, "_h", None):
+                self.close()
+        except Exception:
+            pass

@@ -15,8 +15,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <map>
 #include <sstream>
 #include <string>
@@ -49,6 +51,9 @@ static const char *kKktDiagSource =       // the per-row diagonal's gather and t
     ;
 static const char *kKktBorderSource =     // the dense border on the device (kkt_border_ldl / kkt_border_solve): a code object of its own
 #include "iem_kkt_border_device_h.inc"
+    ;
+static const char *kBarrierSource =       // the interior-point barrier layer (iem_barrier_*): a code object of its own, behind the helpers of the device header (everything in front of its own kernels)
+#include "iem_barrier_device_h.inc"
     ;
 
 namespace {
@@ -274,6 +279,10 @@ struct iem_model {
   hipFunction_t kb_ldl = nullptr, kb_solve = nullptr, kb_colsum = nullptr, kb_inertia = nullptr;
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
+  // the kernels of the iem_barrier object (csrc/iem_barrier_device.h; loaded by the first iem_barrier_create of the handle), in the
+  // order start, terms, step, update, error, merit
+  hipModule_t kbar_mod = nullptr;
+  hipFunction_t kbar_fn[6] = {};
   // the explicit blocks in COO (iem_jacp_coord / iem_hessp_coord).  `pc_view`: the parameter view with the blocks' layout
   // (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.  `d_pc_spare`: where a
   // block the caller passed NULL for is written when it is not empty (allocated by the first such call)
@@ -1281,6 +1290,7 @@ int iem_destroy(iem_model *m) {
   if (m->kres_mod) hipModuleUnload(m->kres_mod);
   if (m->kdg_mod) hipModuleUnload(m->kdg_mod);
   if (m->kb_mod) hipModuleUnload(m->kb_mod);
+  if (m->kbar_mod) hipModuleUnload(m->kbar_mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -3858,6 +3868,265 @@ int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y,
     if (d_norms && (rc = residual(steps))) return rc;
   }
   return IEM_OK;
+}
+
+/* ---- the interior-point barrier layer: what sits between the evaluation calls and the KKT object (csrc/iem_barrier_device.h) ---- */
+struct iem_barrier {
+  iem_model *m = nullptr;
+  int64_t nvar = 0, ncon = 0, n_eq = 0, n_ineq = 0, n_xl = 0, n_xu = 0, n_sl = 0, n_su = 0, n_wg = 0;
+  double *d_bounds = nullptr;          // xl | xu (nvar each) | rl | ru | ceq (ncon each)
+  unsigned char *d_flags = nullptr;    // fx (nvar) | fc (ncon)
+  double *d_red = nullptr;             // 4 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  long long *d_tab = nullptr;          // offs[4] | first[4] | count[4] of iem_shared_totals
+  unsigned long long *d_ones = nullptr;   // the bits of {1.0, 1.0}: what the step lengths are seeded with (device-to-device copy)
+};
+
+namespace {
+// BarrierArgs of csrc/iem_barrier_device.h
+struct BarrierArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c, *sol;
+  double *ds, *dzL, *dzU, *dvL, *dvU;
+  double *sigma, *dcon, *rhs;
+  unsigned long long *alpha;
+  double *out;
+  double *red;
+  const long long *tab;
+  double mu, tau, kappa, push, frac;
+  long long nvar, n, n_wg;
+};
+enum { BAR_START, BAR_TERMS, BAR_STEP, BAR_UPDATE, BAR_ERROR, BAR_MERIT };
+
+std::string barrier_source() {
+  const std::string hdr(kDeviceHeader);
+  const size_t b = hdr.find("// IEM-TILE-REGION-END");
+  if (b == std::string::npos) throw std::runtime_error("internal: device header without tile-region markers");
+  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#define IEM_TILE 256\n") +
+         hdr.substr(0, b) + "#endif  // IEM_DEVICE_H (its kernels are not part of this code object)\n\n" + kBarrierSource;
+}
+BarrierArgsH barrier_args(const iem_barrier *b) {
+  BarrierArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.red = b->d_red; A.tab = b->d_tab;
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int barrier_launch(const iem_barrier *b, int which, BarrierArgsH &A) { return kkt_launch_raw(b->m, b->m->kbar_fn[which], &A, sizeof A, b->n_wg, 256); }
+// the state vectors a call needs: x with variables, y and the slack side with rows (the slack side only with inequality rows)
+bool barrier_state_missing(const iem_barrier *b, const double *x, const double *s, const double *y, const double *zL, const double *zU, const double *vL, const double *vU) {
+  return (b->nvar && (!x || !zL || !zU)) || (b->ncon && !y) || (b->n_ineq && (!s || !vL || !vU));
+}
+// the host analysis of iem_barrier_create: relaxed bounds xl | xu | rl | ru | ceq, flags fx | fc, counts — and its refusals
+int barrier_analyse(int64_t nvar, int64_t ncon, const double *const src[4], double relax, double *bounds, unsigned char *flags, iem_barrier *hb) {
+  if (!(relax >= 0.0) || !std::isfinite(relax)) return fail(IEM_E_ARG, "iem_barrier_create: relax must be finite and not negative");
+  const double inf = std::numeric_limits<double>::infinity();
+  auto lo = [&](double v) { return std::isfinite(v) ? v - relax * std::max(1.0, std::fabs(v)) : -inf; };
+  auto hi = [&](double v) { return std::isfinite(v) ? v + relax * std::max(1.0, std::fabs(v)) : inf; };
+  hb->nvar = nvar; hb->ncon = ncon;
+  hb->n_eq = hb->n_ineq = hb->n_xl = hb->n_xu = hb->n_sl = hb->n_su = 0;
+  double *xl = bounds, *xu = xl + nvar, *rl = xu + nvar, *ru = rl + ncon, *ceq = ru + ncon;
+  for (int64_t i = 0; i < nvar; ++i) {
+    const double l = src[0][i], u = src[1][i];
+    if (l != l || u != u || l > u || l == inf || u == -inf) return fail(IEM_E_ARG, "iem_barrier_create: variable " + std::to_string(i) + " has lvar > uvar (or a NaN / an infinite bound of the wrong sign)");
+    if (l == u && relax == 0.0) return fail(IEM_E_ARG, "iem_barrier_create: variable " + std::to_string(i) + " is fixed (lvar == uvar) and relax is 0: it has no interior");
+    xl[i] = lo(l); xu[i] = hi(u);
+    flags[(size_t)i] = (unsigned char)((std::isfinite(l) ? 1 : 0) | (std::isfinite(u) ? 2 : 0));
+    hb->n_xl += std::isfinite(l); hb->n_xu += std::isfinite(u);
+  }
+  for (int64_t j = 0; j < ncon; ++j) {
+    const double l = src[2][j], u = src[3][j];
+    if (l != l || u != u || l > u || l == inf || u == -inf) return fail(IEM_E_ARG, "iem_barrier_create: row " + std::to_string(j) + " has lcon > ucon (or a NaN / an infinite bound of the wrong sign)");
+    if (!std::isfinite(l) && !std::isfinite(u)) return fail(IEM_E_ARG, "iem_barrier_create: row " + std::to_string(j) + " has neither bound (a free row has no slack to eliminate)");
+    if (l == u) {
+      rl[j] = -inf; ru[j] = inf; ceq[j] = l;
+      flags[(size_t)(nvar + j)] = 4;
+      ++hb->n_eq;
+    } else {
+      rl[j] = lo(l); ru[j] = hi(u); ceq[j] = 0.0;
+      flags[(size_t)(nvar + j)] = (unsigned char)((std::isfinite(l) ? 1 : 0) | (std::isfinite(u) ? 2 : 0));
+      hb->n_sl += std::isfinite(l); hb->n_su += std::isfinite(u);
+      ++hb->n_ineq;
+    }
+  }
+  hb->n_wg = std::max<long long>(kkt_stream_grid(nvar + ncon), 1);
+  return IEM_OK;
+}
+int barrier_info_out(const iem_barrier *b, iem_barrier_info_t *out) {
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_barrier_info: set struct_size to sizeof(iem_barrier_info_t) before the call");
+  iem_barrier_info_t v;
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  v.nvar = b->nvar; v.ncon = b->ncon; v.n_eq = b->n_eq; v.n_ineq = b->n_ineq;
+  v.n_xl = b->n_xl; v.n_xu = b->n_xu; v.n_sl = b->n_sl; v.n_su = b->n_su;
+  v.nz = b->n_xl + b->n_xu + b->n_sl + b->n_su;
+  v.workgroups = b->n_wg;
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_barrier_analyse(int64_t nvar, int64_t ncon, const double *h_lvar, const double *h_uvar, const double *h_lcon, const double *h_ucon, double relax,
+                        double *h_bounds, uint8_t *h_flags, iem_barrier_info_t *info) {
+  if (nvar < 0 || ncon < 0 || (nvar && (!h_lvar || !h_uvar)) || (ncon && (!h_lcon || !h_ucon)) || !h_bounds || !h_flags || !info) return fail(IEM_E_ARG, "null argument");
+  const double *src[4] = {h_lvar, h_uvar, h_lcon, h_ucon};
+  iem_barrier hb;
+  int rc = barrier_analyse(nvar, ncon, src, relax, h_bounds, h_flags, &hb);
+  return rc ? rc : barrier_info_out(&hb, info);
+}
+
+int iem_barrier_source(char **out_src, uint64_t *out_key) {
+  try {
+    const std::string s = barrier_source();
+    if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
+    if (out_key) *out_key = iem::fnv1a64(s);
+  } catch (const std::exception &e) { return fail(IEM_E_COMPILE, e.what()); }
+  return IEM_OK;
+}
+
+int iem_barrier_destroy(iem_barrier *b) {
+  if (!b) return IEM_OK;
+  DevGuard dg_(b->m->device);
+  for (void *p : {(void *)b->d_bounds, (void *)b->d_flags, (void *)b->d_red, (void *)b->d_tab, (void *)b->d_ones})
+    if (p) hipFree(p);
+  delete b;
+  return IEM_OK;
+}
+
+int iem_barrier_create(iem_model *m, const double *h_lvar, const double *h_uvar, const double *h_lcon, const double *h_ucon, double relax, iem_barrier **out) {
+  if (!m || !out) return fail(IEM_E_ARG, "null argument");
+  if (m->sharded) return fail(IEM_E_ARG, "iem_barrier_create: a sharded handle holds one rank's window; the step lengths and error terms want the whole model");
+  const int64_t nvar = m->model.nvar, ncon = m->model.ncon, n = nvar + ncon;
+  std::vector<double> own[4];
+  const double *src[4] = {h_lvar, h_uvar, h_lcon, h_ucon};
+  static const int which[4] = {IEM_LVAR, IEM_UVAR, IEM_LCON, IEM_UCON};
+  for (int a = 0; a < 4; ++a)
+    if (!src[a]) {      // the handle's own host mirror
+      own[a].resize((size_t)std::max<int64_t>(a < 2 ? nvar : ncon, 1));
+      int rc = iem_get_host(m, which[a], own[a].data());
+      if (rc) return rc;
+      src[a] = own[a].data();
+    }
+  std::vector<double> bounds((size_t)std::max<int64_t>(2 * nvar + 3 * ncon, 1), 0.0);
+  std::vector<unsigned char> flags((size_t)std::max<int64_t>(n, 1), 0);
+  std::unique_ptr<iem_barrier> hb(new iem_barrier);
+  hb->m = m;
+  {
+    int rc = barrier_analyse(nvar, ncon, src, relax, bounds.data(), flags.data(), hb.get());
+    if (rc) return rc;
+  }
+  DevGuard dg_(m->device);
+  if (!m->kbar_mod) {
+    std::string src_txt;
+    try { src_txt = barrier_source(); } catch (const std::exception &e) { return fail(IEM_E_COMPILE, e.what()); }
+    int rc = load_source(m, src_txt, &m->kbar_mod);
+    if (rc) return rc;
+    static const char *names[6] = {"barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"};
+    for (int i = 0; i < 6; ++i) HIP_TRY(hipModuleGetFunction(&m->kbar_fn[i], m->kbar_mod, names[i]));
+  }
+  struct Drop { void operator()(iem_barrier *p) const { iem_barrier_destroy(p); } };      // (a failed create frees what it had uploaded)
+  std::unique_ptr<iem_barrier, Drop> b(hb.release());
+  const int64_t n_red = 4 * b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&b->d_bounds, bounds.size() * 8));
+  HIP_TRY(hipMalloc((void **)&b->d_flags, flags.size()));
+  HIP_TRY(hipMalloc((void **)&b->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMalloc((void **)&b->d_tab, 12 * 8));
+  HIP_TRY(hipMalloc((void **)&b->d_ones, 16));
+  long long tab[12];
+  for (int s = 0; s < 4; ++s) { tab[s] = s * (long long)b->n_wg; tab[4 + s] = 0; tab[8 + s] = (long long)b->n_wg; }
+  const double ones[2] = {1.0, 1.0};
+  HIP_TRY(hipMemcpy(b->d_bounds, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_flags, flags.data(), flags.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(b->d_red, 0, (size_t)n_red * 8));
+  HIP_TRY(hipMemcpy(b->d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b->d_ones, ones, sizeof ones, hipMemcpyHostToDevice));
+  *out = b.release();
+  return IEM_OK;
+}
+
+int iem_barrier_info(const iem_barrier *b, iem_barrier_info_t *out) {
+  if (!b || !out) return fail(IEM_E_ARG, "null argument");
+  return barrier_info_out(b, out);
+}
+
+int iem_barrier_start(iem_barrier *b, double *d_x, const double *d_c, double *d_s, double *d_zL, double *d_zU, double *d_vL, double *d_vU, double bound_push,
+                      double bound_frac) {
+  if (!(bound_push > 0.0) || !(bound_frac > 0.0) || !(bound_frac <= 0.5) || !std::isfinite(bound_push))
+    return fail(IEM_E_ARG, "iem_barrier_start: bound_push must be positive and bound_frac in (0, 0.5]");
+  if (!b || barrier_state_missing(b, d_x, d_s, d_c, d_zL, d_zU, d_vL, d_vU) || (b->n_ineq && !d_c)) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = d_x; A.c = d_c; A.s = d_s; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU; A.push = bound_push; A.frac = bound_frac;
+  return barrier_launch(b, BAR_START, A);
+}
+
+int iem_barrier_terms(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                      const double *d_vU, const double *d_r, const double *d_c, double mu, double *d_sigma, double *d_dcon, double *d_rhs) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_terms: mu must not be negative");
+  if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->nvar && (!d_r || !d_sigma)) || (b->ncon && (!d_c || !d_dcon)) || !d_rhs)
+    return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.y = (double *)d_y; A.zL = (double *)d_zL; A.zU = (double *)d_zU; A.vL = (double *)d_vL; A.vU = (double *)d_vU;
+  A.r = d_r; A.c = d_c; A.mu = mu; A.sigma = d_sigma; A.dcon = d_dcon; A.rhs = d_rhs;
+  return barrier_launch(b, BAR_TERMS, A);
+}
+
+int iem_barrier_step(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                     const double *d_vU, const double *d_sol, double mu, double tau, double *d_ds, double *d_dzL, double *d_dzU, double *d_dvL, double *d_dvU,
+                     double *d_alpha) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_step: mu must not be negative");
+  if (!(tau > 0.0 && tau <= 1.0)) return fail(IEM_E_ARG, "iem_barrier_step: tau must lie in (0, 1]");
+  if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
+      (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.y = (double *)d_y; A.zL = (double *)d_zL; A.zU = (double *)d_zU; A.vL = (double *)d_vL; A.vU = (double *)d_vU;
+  A.sol = d_sol; A.mu = mu; A.tau = tau; A.ds = d_ds; A.dzL = d_dzL; A.dzU = d_dzU; A.dvL = d_dvL; A.dvU = d_dvU; A.alpha = (unsigned long long *)d_alpha;
+  // the seed: the bits of 1.0 (a memset cannot write that pattern; a device-to-device copy is a capturable node)
+  HIP_TRY(hipMemcpyAsync(d_alpha, b->d_ones, 16, hipMemcpyDeviceToDevice, m->stream));
+  return barrier_launch(b, BAR_STEP, A);
+}
+
+int iem_barrier_update(iem_barrier *b, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
+                       const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha, double mu,
+                       double kappa_sigma) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_update: mu must not be negative");
+  if (!(kappa_sigma >= 1.0)) return fail(IEM_E_ARG, "iem_barrier_update: kappa_sigma must be at least 1");
+  if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
+      (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
+    return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  A.sol = d_sol; A.ds = (double *)d_ds; A.dzL = (double *)d_dzL; A.dzU = (double *)d_dzU; A.dvL = (double *)d_dvL; A.dvU = (double *)d_dvU;
+  A.alpha = (unsigned long long *)d_alpha; A.mu = mu; A.kappa = kappa_sigma;
+  return barrier_launch(b, BAR_UPDATE, A);
+}
+
+int iem_barrier_error(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                      const double *d_vU, const double *d_r, const double *d_c, double mu, double *d_out) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_error: mu must not be negative");
+  if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.y = (double *)d_y; A.zL = (double *)d_zL; A.zU = (double *)d_zU; A.vL = (double *)d_vL; A.vU = (double *)d_vU;
+  A.r = d_r; A.c = d_c; A.mu = mu; A.out = d_out;
+  HIP_TRY(hipMemsetAsync(d_out, 0, 4 * 8, m->stream));      // the four maxima start from +0.0
+  return barrier_launch(b, BAR_ERROR, A);
+}
+
+int iem_barrier_merit(iem_barrier *b, const double *d_x, const double *d_s, const double *d_c, double *d_out) {
+  if (!b || (b->nvar && !d_x) || (b->n_ineq && !d_s) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  BarrierArgsH A = barrier_args(b);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.c = d_c; A.out = d_out;
+  return barrier_launch(b, BAR_MERIT, A);
 }
 
 int iem_tuner_choice(iem_model *m, int kind, const double *d_vals, int *out_choice) {

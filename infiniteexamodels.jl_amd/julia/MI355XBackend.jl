@@ -464,6 +464,66 @@ border_solve!(m::MI355XModel, S, ne, n_border, nrhs, F, piv::ROCVector{Int32}, r
 is_inertia(::ChainKKTSolver) = true
 inertia(s::ChainKKTSolver) = (s.inertia[1], s.inertia[3], s.inertia[2])      # (positive, zero, negative)
 
+# ---- the interior-point barrier layer (include/iem.h: iem_barrier_*) --------------------------------------------------------
+# What MadNLP's set_aug_diagonal! / set_aug_rhs! / get_alpha_max / finish_aug_solve! and Ipopt's PDSystemSolver right-hand side and
+# IpoptCalculatedQuantities error terms compute between the evaluation calls and the linear solver, one launch each and every
+# scalar on the device.  Vectors are full length (s, vL, vU, ds, dvL, dvU have ncon entries; those on equality rows are never
+# touched).  A state is the tuple (x, s, y, zL, zU, vL, vU), directions are (ds, dzL, dzU, dvL, dvU).  UNEXECUTED, like the rest.
+struct IemBarrierInfo      # iem_barrier_info_t
+    struct_size::UInt64
+    nvar::Int64; ncon::Int64; n_eq::Int64; n_ineq::Int64; n_xl::Int64; n_xu::Int64; n_sl::Int64; n_su::Int64; nz::Int64; workgroups::Int64
+end
+mutable struct BarrierLayer
+    b::Ptr{Cvoid}
+    info::IemBarrierInfo
+end
+hptr(v) = v === nothing ? Ptr{Float64}(C_NULL) : pointer(v)
+# bounds: host vectors, or nothing for the handle's own (a scaled solver passes its scaled lcon / ucon)
+function BarrierLayer(m::MI355XModel; relax = 1e-8, lvar = nothing, uvar = nothing, lcon = nothing, ucon = nothing)
+    b = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_barrier_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Ptr{Cvoid}}),
+                m.handle, hptr(lvar), hptr(uvar), hptr(lcon), hptr(ucon), relax, b))
+    info = Ref(IemBarrierInfo(sizeof(IemBarrierInfo), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    check(ccall((:iem_barrier_info, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemBarrierInfo}), b[], info))
+    layer = BarrierLayer(b[], info[])
+    finalizer(l -> (l.b == C_NULL || ccall((:iem_barrier_destroy, LIBIEM), Cint, (Ptr{Cvoid},), l.b); l.b = C_NULL), layer)
+    return layer
+end
+# x is projected in place; s, zL, zU, vL, vU are written
+function barrier_start!(l::BarrierLayer, x, c, s, zL, zU, vL, vU; bound_push = 1e-2, bound_frac = 1e-2)
+    check(ccall((:iem_barrier_start, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                l.b, dptr(x), spptr(c), spptr(s), dptr(zL), dptr(zU), spptr(vL), spptr(vU), bound_push, bound_frac))
+    return x, s, zL, zU, vL, vU
+end
+# sigma, dcon, rhs: the inputs of factorize_diag! / solve_refined_diag!
+function barrier_terms!(l::BarrierLayer, state, r, c, mu, sigma, dcon, rhs)
+    check(ccall((:iem_barrier_terms, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                l.b, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(r), spptr(c), mu, dptr(sigma), spptr(dcon), dptr(rhs)))
+    return sigma, dcon, rhs
+end
+# the directions from sol = [dx; dy] and alpha = (alpha_primal, alpha_dual) on the device; +0.0: the state or direction was unusable
+function barrier_step!(l::BarrierLayer, state, sol, mu, tau, dirs, alpha)
+    check(ccall((:iem_barrier_step, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                l.b, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(sol), mu, tau, spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha)))
+    return dirs, alpha
+end
+function barrier_update!(l::BarrierLayer, state, sol, dirs, alpha, mu; kappa_sigma = 1e10)
+    check(ccall((:iem_barrier_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                l.b, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(sol), spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha), mu, kappa_sigma))
+    return state
+end
+# out: eight doubles on the device (include/iem.h lists them); r === nothing: out[1] is NaN
+function barrier_error!(l::BarrierLayer, state, r, c, mu, out)
+    check(ccall((:iem_barrier_error, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+                l.b, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), spptr(r), spptr(c), mu, dptr(out)))
+    return out
+end
+# out = (theta, sum log gap) at a trial (x, s, c): the bits barrier_error! writes to out[7], out[8]
+function barrier_merit!(l::BarrierLayer, x, s, c, out)
+    check(ccall((:iem_barrier_merit, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), l.b, dptr(x), spptr(s), spptr(c), dptr(out)))
+    return out
+end
+
 # ---- blob writer ----------------------------------------------------------------------------
 # Serialises a host ExaCore into the wire format of include/iem_blob.h.  [EXT]: the field and
 # type names of ExaModels' internal structs (Objective/Constraint linked lists, SIMDFunction,

@@ -75,6 +75,11 @@ class KktInfo(C.Structure):
                 ("lanes", C.c_int64), ("hub_ld", C.c_int64), ("hubs", C.c_int32), ("hub_rows", C.c_int32), ("hubs_per_block", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class BarrierInfo(C.Structure):
+    """``iem_barrier_info_t``: ``struct_size`` is set by the caller; the library writes at most that many bytes."""
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_int64) for n in ("nvar", "ncon", "n_eq", "n_ineq", "n_xl", "n_xu", "n_sl", "n_su", "nz", "workgroups")]
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("kind", C.c_int32), ("jit", C.c_int32), ("grid", C.c_int64 * 3),
                 ("lds_bytes", C.c_int64), ("alg_bytes_read", C.c_int64), ("alg_bytes_written", C.c_int64)]
@@ -86,7 +91,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_residual_source", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_residual_source", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -222,6 +227,17 @@ def lib():
     L.iem_kkt_border_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_kkt_set_border.argtypes = [vp, i32]
     L.iem_kkt_factor_async.argtypes = [vp, vp]
+    L.iem_barrier_create.argtypes = [vp, vp, vp, vp, vp, dbl, C.POINTER(vp)]
+    L.iem_barrier_analyse.argtypes = [i64, i64, vp, vp, vp, vp, dbl, vp, vp, C.POINTER(BarrierInfo)]
+    L.iem_barrier_destroy.argtypes = [vp]
+    L.iem_barrier_info.argtypes = [vp, C.POINTER(BarrierInfo)]
+    L.iem_barrier_start.argtypes = [vp] + [vp] * 7 + [dbl, dbl]
+    L.iem_barrier_terms.argtypes = [vp] + [vp] * 9 + [dbl, vp, vp, vp]
+    L.iem_barrier_step.argtypes = [vp] + [vp] * 8 + [dbl, dbl] + [vp] * 6
+    L.iem_barrier_update.argtypes = [vp] + [vp] * 14 + [dbl, dbl]
+    L.iem_barrier_error.argtypes = [vp] + [vp] * 9 + [dbl, vp]
+    L.iem_barrier_merit.argtypes = [vp, vp, vp, vp, vp]
+    L.iem_barrier_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_free.argtypes = [vp]
@@ -367,6 +383,36 @@ def kkt_border_source():
     finally:
         L.iem_free(p)
     return src, int(key.value)
+
+
+def barrier_source():
+    """HIP source of the interior-point barrier layer's kernels (``barrier_start`` / ``_terms`` / ``_step`` / ``_update`` / ``_error`` /
+    ``_merit``: the ``iem_barrier_*`` calls) and its cache key."""
+    L = lib()
+    p, key = C.c_void_p(), C.c_uint64()
+    check(L.iem_barrier_source(C.byref(p), C.byref(key)))
+    try:
+        src = C.string_at(p).decode()
+    finally:
+        L.iem_free(p)
+    return src, int(key.value)
+
+
+def barrier_analyse(lvar, uvar, lcon, ucon, relax: float = 1e-8):
+    """The host analysis of ``iem_barrier_create`` (no device): ``(dict(xl, xu, rl, ru, ceq), fx, fc, info dict)`` as numpy arrays —
+    relaxed bounds, presence flags (bit 0 lower, bit 1 upper, bit 2 equality row) and the counts of ``iem_barrier_info``."""
+    import numpy as np
+    lvar, uvar, lcon, ucon = (np.ascontiguousarray(a, dtype=np.float64) for a in (lvar, uvar, lcon, ucon))
+    n, m = len(lvar), len(lcon)
+    if len(uvar) != n or len(ucon) != m:
+        raise ValueError("lvar / uvar and lcon / ucon must have equal lengths")
+    bounds, flags = np.zeros(max(2 * n + 3 * m, 1)), np.zeros(max(n + m, 1), dtype=np.uint8)
+    info = BarrierInfo()
+    info.struct_size = C.sizeof(BarrierInfo)
+    check(lib().iem_barrier_analyse(n, m, lvar.ctypes.data, uvar.ctypes.data, lcon.ctypes.data, ucon.ctypes.data, float(relax), bounds.ctypes.data,
+                                    flags.ctypes.data, C.byref(info)))
+    parts = dict(xl=bounds[:n], xu=bounds[n:2 * n], rl=bounds[2 * n:2 * n + m], ru=bounds[2 * n + m:2 * n + 2 * m], ceq=bounds[2 * n + 2 * m:2 * n + 3 * m])
+    return parts, flags[:n], flags[n:n + m], {k: int(getattr(info, k)) for k, _ in BarrierInfo._fields_ if k != "struct_size"}
 
 
 def kkt_many_width(nb: int, ne: int, nc: int = 12) -> int:
