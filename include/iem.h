@@ -780,6 +780,12 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache
  * miss).  These two calls expose the generator so a build step can pre-compile. */
 int iem_emit_source(const void *blob, size_t nbytes, char **out_src, uint64_t *out_key);
+/* The hand-written code objects whose source depends on no model and no shape, as a list — what iem_kkt_residual_source,
+ * iem_kkt_diag_source, iem_kkt_border_source and iem_barrier_source return one by one: index 0, 1, .. gives the object's name
+ * (*out_name: a static string, not to be freed — "kkt_residual", "kkt_diag", "kkt_border", "barrier"), its HIP source (malloc'ed)
+ * and its cache key.  IEM_E_ARG for an index below 0 or past the last object, with nothing written: an offline build loops until
+ * then and needs no edit when the library gains an object.  Any output pointer may be NULL. */
+int iem_fixed_source(int index, const char **out_name, char **out_src, uint64_t *out_key);
 /* text description of the launches (kernel name, grid, argument tables) — for tooling/tests */
 int iem_emit_launch_plan(const void *blob, size_t nbytes, char **out_txt);
 /* Hessian structure of a blob under the current options, computed on the host (tooling/tests;

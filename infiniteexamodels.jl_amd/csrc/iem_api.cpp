@@ -87,12 +87,14 @@ int g_opt_poll_obj = 1;   // iem_set_option("poll_obj", 0): iem_obj always synch
 
 std::string contract_flag(const iem::Options &o) { return o.fp_contract ? "-ffp-contract=fast" : "-ffp-contract=off"; }
 
-// first line carries the compile flags so that an offline build (lib.precompile) and the
-// hiprtc path compile the same key with the same options
+// The head of every source: the first line carries the compile flags (`contract`: off / fast) so that an offline build
+// (lib.precompile_source) and the hiprtc path compile the same key with the same options
+std::string source_prelude(const std::string &contract) {
+  return "// iem-flags: -O3 -ffp-contract=" + contract + " -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n";
+}
+
 std::string full_source(const iem::Program &p, const iem::Options &o) {
-  std::string s;
-  s += "// iem-flags: -O3 " + contract_flag(o) + " -std=c++17\n";
-  s += "#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n";
+  std::string s = source_prelude(o.fp_contract ? "fast" : "off");
   s += std::string("#define IEM_NT ") + (o.nt_stores ? "1" : "0") + "\n";
   s += "#define IEM_TILE " + std::to_string(p.block) + "\n";
   s += std::string("#define IEM_WIDE_STORES ") + (o.wide_stores ? "1" : "0") + "\n";
@@ -122,6 +124,50 @@ std::string full_source(const iem::Program &p, const iem::Options &o) {
   s += "\n";
   s += p.source;
   return s;
+}
+
+// The hand-written code objects whose source does not depend on a shape: one row of kFixed each — the name iem_fixed_source
+// lists it under, the embedded text, whether the text sits behind the device header's helpers (everything in front of the
+// header's own kernels), and its kernels in slot order (the enum beside the row names the slots).  A handle loads one at the
+// first call that needs it (fixed_object); build() compiles every row offline.
+enum Fixed { F_KRES, F_KDIAG, F_KBORDER, F_BARRIER, F_COUNT };
+constexpr int kFixedSlots = 6;
+enum { KRES_RESIDUAL, KRES_AXPY };
+enum { KDIAG_GATHER, KDIAG_RESIDUAL, KDIAG_AXPY };
+enum { KBORDER_LDL, KBORDER_SOLVE, KBORDER_COLSUM, KBORDER_INERTIA };
+enum { BAR_START, BAR_TERMS, BAR_STEP, BAR_UPDATE, BAR_ERROR, BAR_MERIT };
+const struct FixedRow { const char *name, *text; bool behind_helpers; const char *kernels[kFixedSlots]; } kFixed[F_COUNT] = {
+    {"kkt_residual", kKktResidualSource, false, {"kkt_residual", "kkt_axpy1"}},      // iem_kkt_residual / iem_kkt_solve_refined
+    {"kkt_diag", kKktDiagSource, false, {"kkt_gather_d", "kkt_residual_dm", "kkt_axpy_m"}},      // iem_kkt_*_diag
+    {"kkt_border", kKktBorderSource, false, {"kkt_border_ldl", "kkt_border_solve", "kkt_border_colsum", "kkt_border_inertia"}},      // iem_kkt_border_* / iem_kkt_set_border
+    {"barrier", kBarrierSource, true, {"barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"}},      // iem_barrier_*
+};
+
+int fixed_source(Fixed f, std::string &s) {
+  s = source_prelude("off");
+  if (kFixed[f].behind_helpers) {
+    const std::string hdr(kDeviceHeader);
+    const size_t b = hdr.find("// IEM-TILE-REGION-END");
+    if (b == std::string::npos) return fail(IEM_E_COMPILE, "internal: device header without tile-region markers");
+    s += "#define IEM_TILE 256\n" + hdr.substr(0, b) + "#endif  // IEM_DEVICE_H (its kernels are not part of this code object)\n\n";
+  }
+  s += kFixed[f].text;
+  return IEM_OK;
+}
+
+// what every *_source entry point returns: a malloc'ed copy of the text and its cache key
+int emit_out(const std::string &s, char **out_src, uint64_t *out_key) {
+  if (out_src) {
+    *out_src = (char *)std::malloc(s.size() + 1);
+    std::memcpy(*out_src, s.c_str(), s.size() + 1);
+  }
+  if (out_key) *out_key = iem::fnv1a64(s);
+  return IEM_OK;
+}
+int fixed_source_out(Fixed f, char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = fixed_source(f, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
 }
 
 std::string lib_dir() {
@@ -266,23 +312,12 @@ struct iem_model {
   // iem_eval_trial_scaled, cleared by every arm)
   bool obj_scaled = false;
   double obj_factor = 1.0;
-  // `kres_*`: the finishing kernels of iem_kkt_residual (loaded by its first call)
-  hipModule_t kres_mod = nullptr;
-  hipFunction_t kres_fn = nullptr, kres_axpy = nullptr;
-  // the kernels of iem_kkt_assemble_diag / iem_kkt_residual_diag / iem_kkt_solve_refined_diag (csrc/iem_kkt_diag_device.h; loaded
-  // by the first of those calls)
-  hipModule_t kdg_mod = nullptr;
-  hipFunction_t kdg_gather = nullptr, kdg_res = nullptr, kdg_axpy = nullptr;
-  // the dense border on the device (csrc/iem_kkt_border_device.h; loaded by the first call that needs it).  `kb_part`: the column
-  // sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
-  hipModule_t kb_mod = nullptr;
-  hipFunction_t kb_ldl = nullptr, kb_solve = nullptr, kb_colsum = nullptr, kb_inertia = nullptr;
+  // the hand-written code objects of kFixed, each loaded by the first call that needs it (fixed_object): `mod` set = loaded, every
+  // kernel of its row resolved
+  struct FixedObject { hipModule_t mod = nullptr; hipFunction_t fn[kFixedSlots] = {}; } fixed[F_COUNT];
+  // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
-  // the kernels of the iem_barrier object (csrc/iem_barrier_device.h; loaded by the first iem_barrier_create of the handle), in the
-  // order start, terms, step, update, error, merit
-  hipModule_t kbar_mod = nullptr;
-  hipFunction_t kbar_fn[6] = {};
   // the explicit blocks in COO (iem_jacp_coord / iem_hessp_coord).  `pc_view`: the parameter view with the blocks' layout
   // (param_coord_layout), built by the first structure / nnz / evaluation call; it points into `model`.  `d_pc_spare`: where a
   // block the caller passed NULL for is written when it is not empty (allocated by the first such call)
@@ -377,6 +412,39 @@ int load_source(iem_model *m, const std::string &src, hipModule_t *mod) {
   return IEM_OK;
 }
 
+// A hand-written code object: the module of `src` and the kernels its `n` slots name.  *mod and the slots' functions are written
+// only once every name is resolved; any failure unloads the module and leaves them as they were (never loaded).
+struct KernelSlot { const char *name; hipFunction_t *fn; };
+int load_object(iem_model *m, const std::string &src, const KernelSlot *slots, int n, hipModule_t *mod) {
+  hipModule_t loaded = nullptr;
+  int rc = load_source(m, src, &loaded);
+  if (rc) return rc;
+  std::vector<hipFunction_t> fns((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const hipError_t e = hipModuleGetFunction(&fns[i], loaded, slots[i].name);
+    if (e != hipSuccess) {
+      hipModuleUnload(loaded);
+      return fail(IEM_E_HIP, std::string("hipModuleGetFunction(") + slots[i].name + "): " + hipGetErrorString(e));
+    }
+  }
+  for (int i = 0; i < n; ++i) *slots[i].fn = fns[i];
+  *mod = loaded;
+  return IEM_OK;
+}
+
+// row `f` of kFixed on the handle: loaded by the first call
+int fixed_object(iem_model *m, Fixed f) {
+  iem_model::FixedObject &o = m->fixed[f];
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = fixed_source(f, src);
+  if (rc) return rc;
+  KernelSlot slots[kFixedSlots];
+  int n = 0;
+  for (; n < kFixedSlots && kFixed[f].kernels[n]; ++n) slots[n] = KernelSlot{kFixed[f].kernels[n], &o.fn[n]};
+  return load_object(m, src, slots, n, &o.mod);
+}
+
 // code object of `co.prog` (generated with `opt`) and its kernel functions
 int load_program(iem_model *m, CodeObject &co, const iem::Options &opt) {
   int rc = load_source(m, full_source(co.prog, opt), &co.mod);
@@ -411,6 +479,13 @@ int compile_or_load(iem_model *m) {
   HIP_TRY(hipModuleGetFunction(&m->fn_halo, m->code.mod, m->opt.two_sided ? "iem_halo2_kernel" : "iem_halo_kernel"));
   HIP_TRY(hipModuleGetFunction(&m->fn_fold, m->code.mod, m->opt.two_sided ? "iem_halo2_fold_kernel" : "iem_halo_fold_kernel"));
   HIP_TRY(hipModuleGetFunction(&m->fn_reduce, m->code.mod, "iem_allreduce_kernel"));
+  return IEM_OK;
+}
+
+// One launch of a kernel that takes its arguments as ONE block of `sz` bytes (every hand-written kernel and every generated one does)
+int launch_args(hipFunction_t fn, void *args, size_t sz, unsigned gx, unsigned gy, unsigned block, unsigned lds, hipStream_t stream, unsigned gz = 1) {
+  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+  HIP_TRY(hipModuleLaunchKernel(fn, gx, gy, gz, block, 1, 1, lds, stream, nullptr, cfg));
   return IEM_OK;
 }
 
@@ -513,10 +588,7 @@ HaloArgsH halo_args(iem_model *m, double *d_x) {
 }
 int halo_launch(iem_model *m, double *d_x, hipStream_t stream) {
   HaloArgsH A = halo_args(m, d_x);
-  size_t sz = m->opt.two_sided ? sizeof A : kHaloArgs1;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(m->fn_halo, 1, 1, 1, 256, 1, 1, 0, stream, nullptr, cfg));
-  return IEM_OK;
+  return launch_args(m->fn_halo, &A, m->opt.two_sided ? sizeof A : kHaloArgs1, 1, 1, 256, 0, stream);
 }
 int halo_flush(iem_model *m) {
   if (!m->halo_deferred) return IEM_OK;
@@ -610,15 +682,11 @@ int partials_buffer(LoadedProgram &P, const hipStream_t *on_stream = nullptr) {
 // kernel k of `co` with the head `h` (h.comm set: the launch carries the deferred halo exchange — one extra leading workgroup column, iem_halo_wg)
 int launch_one(iem_model *m, CodeObject &co, int k, const LaunchHead &h) {
   const iem::KernelDesc &kd = co.prog.kernels[k];
-  const hipFunction_t fn = co.fns[k];
   const bool carry = h.comm != nullptr;
   std::vector<uint64_t> &buf = co.argbuf[k];
   std::memcpy(buf.data(), &h, sizeof h);
-  size_t sz = buf.size() * 8;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, buf.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)kd.grid[0] + (carry ? 1u : 0u), (unsigned)kd.grid[1], (unsigned)kd.grid[2], (unsigned)kd.block, 1, 1, 0,
-                                m->stream, nullptr, cfg));
-  return IEM_OK;
+  return launch_args(co.fns[k], buf.data(), buf.size() * 8, (unsigned)kd.grid[0] + (carry ? 1u : 0u), (unsigned)kd.grid[1], (unsigned)kd.block, 0, m->stream,
+                     (unsigned)kd.grid[2]);
 }
 
 // One evaluation call: the launchable kernels of `kind` in `P` with the head `h` (th and comm filled in here), ordered
@@ -1027,16 +1095,17 @@ int iem_emit_source(const void *blob, size_t nbytes, char **out_src, uint64_t *o
     iem::Model model;
     iem::parse_blob(blob, nbytes, model);
     iem::Program p = iem::generate(model, g_opt);
-    std::string s = full_source(p, g_opt);
-    if (out_src) {
-      *out_src = (char *)std::malloc(s.size() + 1);
-      std::memcpy(*out_src, s.c_str(), s.size() + 1);
-    }
-    if (out_key) *out_key = iem::fnv1a64(s);
-    return IEM_OK;
+    return emit_out(full_source(p, g_opt), out_src, out_key);
   } catch (const std::exception &e) {
     return fail(IEM_E_BLOB, e.what());
   }
+}
+
+int iem_fixed_source(int index, const char **out_name, char **out_src, uint64_t *out_key) {
+  if (index < 0 || index >= F_COUNT) return fail(IEM_E_ARG, "iem_fixed_source: no such code object");
+  const int rc = fixed_source_out((Fixed)index, out_src, out_key);
+  if (rc == IEM_OK && out_name) *out_name = kFixed[index].name;
+  return rc;
 }
 
 int iem_emit_launch_plan(const void *blob, size_t nbytes, char **out_txt) {
@@ -1287,10 +1356,7 @@ int iem_destroy(iem_model *m) {
   release_program(m->alt);
   for (LoadedProgram &P : m->derived) release_program(P);
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
-  if (m->kres_mod) hipModuleUnload(m->kres_mod);
-  if (m->kdg_mod) hipModuleUnload(m->kdg_mod);
-  if (m->kb_mod) hipModuleUnload(m->kb_mod);
-  if (m->kbar_mod) hipModuleUnload(m->kbar_mod);
+  for (auto &o : m->fixed) if (o.mod) hipModuleUnload(o.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -2484,10 +2550,7 @@ int iem_halo_fold(iem_model *m, double *d_vec) {
       m->d_halo_src, m->d_halo_dst, (long long)si.halo_doubles, (long long)si.world, (long long)reduce_chunks(1 + m->n_shared),
       (long long)(1 + m->n_shared), m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL,
       m->d_halo_src_l, m->d_halo_dst_r, (long long)si.halo_doubles_right, (long long)mailbox_b2(si.world, si.halo_doubles, 1 + m->n_shared)};
-  size_t sz = m->opt.two_sided ? sizeof A : 12 * 8;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(m->fn_fold, 1, 1, 1, 256, 1, 1, 0, m->stream, nullptr, cfg));
-  return IEM_OK;
+  return launch_args(m->fn_fold, &A, m->opt.two_sided ? sizeof A : 12 * 8, 1, 1, 256, 0, m->stream);
 }
 
 int iem_allreduce_obj_grad(iem_model *m, double *d_obj, double *d_g) {
@@ -2504,10 +2567,7 @@ int iem_allreduce_obj_grad(iem_model *m, double *d_obj, double *d_g) {
   struct { double *obj, *g; const long long *shared; unsigned long long *const *peers; long long NR, NH, W, rank, G; unsigned long long *hstatus; long long ticks; } A = {
       d_obj, d_g, m->d_shared, m->d_peers, (long long)(1 + m->n_shared), (long long)si.halo_doubles, (long long)si.world, (long long)si.rank, G,
       m->d_hstatus, (long long)m->opt.comm_timeout_ms * 100000LL};
-  size_t sz = sizeof A;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(m->fn_reduce, (unsigned)G, 1, 1, 256, 1, 1, 0, m->stream, nullptr, cfg));
-  return IEM_OK;
+  return launch_args(m->fn_reduce, &A, sizeof A, (unsigned)G, 1, 256, 0, m->stream);
 }
 
 int iem_comm_status(iem_model *m, int64_t *out_status) {
@@ -2597,7 +2657,7 @@ std::string kkt_source(int nb, int ne, int nc) {
   // quadrotor supports, 3.22 against 3.54 for the bordered OPF blocks, solves 9 % slower — the panel steps wait on their
   // dependency chain, not on issue slots.  IEM_KKT_CONTRACT=fast switches them on; profiles/r03_kkt_shape_ab.txt)
   static const KktKnobs knobs = kkt_knobs();
-  std::string s = std::string("// iem-flags: -O3 -ffp-contract=") + knobs.contract + " -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n";
+  std::string s = source_prelude(knobs.contract);
   s += "#define KKT_NB " + std::to_string(nb) + "\n#define KKT_NE " + std::to_string(std::max(ne, 0)) + "\n#define KKT_NC " + std::to_string(nc) + "\n";
   int wmax, wpe;
   kkt_shape(nb, ne, &wmax, &wpe);
@@ -2617,46 +2677,36 @@ bool kkt_fits(int nb, int ne, int nc) {
   const long long upd = 56LL * nc * (nc + 1) + 1024;
   return elim <= 160 * 1024 && upd <= 160 * 1024;
 }
+// The kernels of a chain KKT code object and where kkt_module keeps them.  `lane_rows_only`: the lane-per-row solves (csrc/iem_kkt_device.h:
+// kkt_fz / kkt_fs / kkt_bw, and their multi-column forms), resolved only for the shapes whose eliminate is lane-per-row too and nb <= 32:
+// at 40 x 40 they lose 12 % to the 64-thread kernels (two launches per level, 40 of 64 lanes), at 20 x 20 they win 30 %
+typedef iem_model::KktMod KM;
+const struct KktSlot { const char *name; hipFunction_t KM::*fn; bool lane_rows_only; } kKktSlots[] = {
+    {"kkt_eliminate", &KM::elim, false}, {"kkt_update", &KM::upd, false}, {"kkt_forward", &KM::fwd, false}, {"kkt_backward", &KM::bwd, false},
+    {"kkt_gather", &KM::gather, false}, {"kkt_move", &KM::move, false}, {"kkt_colsum", &KM::colsum, false},
+    {"kkt_hub_z", &KM::hub_z, false}, {"kkt_hub_widen", &KM::hub_widen, false}, {"kkt_hub_mask", &KM::hub_mask, false}, {"kkt_hub_ety", &KM::hub_ety, false},
+    {"kkt_hub_ex", &KM::hub_ex, false}, {"kkt_hub_leaf", &KM::hub_leaf, false}, {"kkt_hub_diagmax", &KM::hub_diagmax, false},
+    {"kkt_fz", &KM::fz, true}, {"kkt_fs", &KM::fs, true}, {"kkt_bw", &KM::bw, true}, {"kkt_fz_m", &KM::fz_m, true}, {"kkt_fs_m", &KM::fs_m, true}, {"kkt_bw_m", &KM::bw_m, true},
+    {"kkt_forward_m", &KM::fwd_m, false}, {"kkt_backward_m", &KM::bwd_m, false}, {"kkt_move_m", &KM::move_m, false}, {"kkt_colsum_m", &KM::colsum_m, false},
+};
 int kkt_module(iem_model *m, int nb, int ne, int nc, iem_model::KktMod **out) {
   if (nb < 4 || nb > 96 || nb % 4 || ne < -1 || ne > 128 || (ne > 0 && ne % 4) || nc < 4 || nc > 48 || nc % 4 || nc > nb || !kkt_fits(nb, ne, nc))
     return fail(IEM_E_ARG, "chain KKT: block size must be a multiple of 4 in 4..96, border size a multiple of 4 in 0..128, coupling width a multiple of 4 in 4..48 (and <= the block size), tiles within the LDS of a CU");
   auto it = m->kkt_mods.find({nb, ne * 64 + nc});
   if (it == m->kkt_mods.end()) {
     iem_model::KktMod km;
-    int rc = load_source(m, kkt_source(nb, ne, nc), &km.mod);
+    const bool lane_rows = kkt_rowwise(nb, ne) && nb <= 32;
+    KernelSlot slots[sizeof kKktSlots / sizeof *kKktSlots];
+    int n = 0;
+    for (const KktSlot &ks : kKktSlots)
+      if (lane_rows || !ks.lane_rows_only) slots[n++] = KernelSlot{ks.name, &(km.*ks.fn)};
+    int rc = load_object(m, kkt_source(nb, ne, nc), slots, n, &km.mod);
     if (rc) return rc;
-    HIP_TRY(hipModuleGetFunction(&km.elim, km.mod, "kkt_eliminate"));
     int wmax, wpe_;
     kkt_shape(nb, ne, &wmax, &wpe_);
     km.elim_wg = 64u * (unsigned)std::min((nb + 15) / 16, wmax);   // KKT_T of csrc/iem_kkt_device.h
     if (kkt_rowwise(nb, ne)) { km.elim_wg = 64u * (unsigned)kkt_row_wpg(nb, ne); km.elim_bpw = (int)km.elim_wg / (nb / kkt_rowwise(nb, ne)); }
-    HIP_TRY(hipModuleGetFunction(&km.upd, km.mod, "kkt_update"));
-    HIP_TRY(hipModuleGetFunction(&km.fwd, km.mod, "kkt_forward"));
-    HIP_TRY(hipModuleGetFunction(&km.bwd, km.mod, "kkt_backward"));
-    HIP_TRY(hipModuleGetFunction(&km.gather, km.mod, "kkt_gather"));
-    HIP_TRY(hipModuleGetFunction(&km.move, km.mod, "kkt_move"));
-    HIP_TRY(hipModuleGetFunction(&km.colsum, km.mod, "kkt_colsum"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_z, km.mod, "kkt_hub_z"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_widen, km.mod, "kkt_hub_widen"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_mask, km.mod, "kkt_hub_mask"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_ety, km.mod, "kkt_hub_ety"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_ex, km.mod, "kkt_hub_ex"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_leaf, km.mod, "kkt_hub_leaf"));
-    HIP_TRY(hipModuleGetFunction(&km.hub_diagmax, km.mod, "kkt_hub_diagmax"));
-    if (kkt_rowwise(nb, ne) && nb <= 32) {      // the lane-per-row solves (csrc/iem_kkt_device.h: kkt_fz / kkt_fs / kkt_bw) for the shapes whose eliminate is lane-per-row too:
-                                    // at 40 x 40 they lose 12 % to the 64-thread kernels (two launches per level, 40 of 64 lanes), at 20 x 20 they win 30 %
-      HIP_TRY(hipModuleGetFunction(&km.fz, km.mod, "kkt_fz"));
-      HIP_TRY(hipModuleGetFunction(&km.fs, km.mod, "kkt_fs"));
-      HIP_TRY(hipModuleGetFunction(&km.bw, km.mod, "kkt_bw"));
-      km.solve_bpw = 64 / nb;
-      HIP_TRY(hipModuleGetFunction(&km.fz_m, km.mod, "kkt_fz_m"));
-      HIP_TRY(hipModuleGetFunction(&km.fs_m, km.mod, "kkt_fs_m"));
-      HIP_TRY(hipModuleGetFunction(&km.bw_m, km.mod, "kkt_bw_m"));
-    }
-    HIP_TRY(hipModuleGetFunction(&km.fwd_m, km.mod, "kkt_forward_m"));
-    HIP_TRY(hipModuleGetFunction(&km.bwd_m, km.mod, "kkt_backward_m"));
-    HIP_TRY(hipModuleGetFunction(&km.move_m, km.mod, "kkt_move_m"));
-    HIP_TRY(hipModuleGetFunction(&km.colsum_m, km.mod, "kkt_colsum_m"));
+    if (lane_rows) km.solve_bpw = 64 / nb;
     km.many_r = kkt_many_width(nb, ne, nc);
     it = m->kkt_mods.emplace(std::make_pair(nb, ne * 64 + nc), km).first;
   }
@@ -2665,11 +2715,10 @@ int kkt_module(iem_model *m, int nb, int ne, int nc, iem_model::KktMod **out) {
 }
 struct KktArgsH { double *D, *Bt, *BR, *E, *Z, *Gp; const int *rows, *cols; long long *info; long long S, s; int final_block; double tiny; long long T = 0; };
 struct KktSolveArgsH { const double *D, *Bt, *BR, *Z; const int *rows, *cols; double *r, *z, *rBp; const double *xB; long long S, s; int final_block; long long T = 0; };
-int kkt_launch_raw(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, unsigned block) {
-  if (grid <= 0) return IEM_OK;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, 0, m->stream, nullptr, cfg));
-  return IEM_OK;
+// (an empty grid launches nothing; `cols`: the grid's second extent)
+int kkt_launch_raw(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, unsigned block, int cols = 1) {
+  if (grid <= 0 || cols <= 0) return IEM_OK;
+  return launch_args(fn, args, sz, (unsigned)grid, (unsigned)cols, block, 0, m->stream);
 }
 int kkt_launch(iem_model *m, hipFunction_t fn, KktArgsH a, long long grid, unsigned block) { return kkt_launch_raw(m, fn, &a, sizeof a, grid, block); }
 int kkt_launch_solve(iem_model *m, hipFunction_t fn, KktSolveArgsH a, long long grid, unsigned block) { return kkt_launch_raw(m, fn, &a, sizeof a, grid, block); }
@@ -2689,12 +2738,7 @@ int kkt_launch_elim(iem_model *m, const iem_model::KktMod *km, KktArgsH a, long 
 }
 }  // namespace
 
-int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key) {
-  const std::string s = kkt_source(nb, ne, nc);
-  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
-  if (out_key) *out_key = iem::fnv1a64(s);
-  return IEM_OK;
-}
+int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key) { return emit_out(kkt_source(nb, ne, nc), out_src, out_key); }
 
 int iem_kkt_chain_factor(iem_model *m, int64_t S, int nb, int ne, int nc, double *d_D, double *d_Bt, double *d_BR, const int32_t *d_rows,
                          const int32_t *d_cols, double *d_E, double *d_Z, double *d_Gp, int64_t *d_info, double tiny) {
@@ -2885,29 +2929,12 @@ int iem_kkt_chain_solve_many(iem_model *m, int64_t S, int64_t lane_len, int nb, 
 
 /* ---- the dense border on the device (csrc/iem_kkt_border_device.h) ------------------------------------------------------------ */
 namespace {
-std::string kkt_border_source() {
-  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktBorderSource;
-}
-// the code object: the synchronous part of the first call
-int kkt_border_setup(iem_model *m) {
-  if (m->kb_ldl) return IEM_OK;
-  int rc = load_source(m, kkt_border_source(), &m->kb_mod);
-  if (rc) return rc;
-  HIP_TRY(hipModuleGetFunction(&m->kb_solve, m->kb_mod, "kkt_border_solve"));
-  HIP_TRY(hipModuleGetFunction(&m->kb_colsum, m->kb_mod, "kkt_border_colsum"));
-  HIP_TRY(hipModuleGetFunction(&m->kb_inertia, m->kb_mod, "kkt_border_inertia"));
-  HIP_TRY(hipModuleGetFunction(&m->kb_ldl, m->kb_mod, "kkt_border_ldl"));
-  return IEM_OK;
-}
+// the code object (the synchronous part of the first call)
+int kkt_border_setup(iem_model *m) { return fixed_object(m, F_KBORDER); }
 bool kkt_border_shape_ok(int64_t S, int ne, int n_border) { return S >= 1 && ne >= 4 && ne <= 128 && ne % 4 == 0 && n_border >= 0 && n_border <= ne; }
 // LDS of kkt_border_ldl / kkt_border_solve (the layout at the head of csrc/iem_kkt_border_device.h)
 unsigned kkt_border_lds(int ne) { return (unsigned)(8 * (ne * (ne + 1) + 2 * ne + 16) + 4 * (2 * ne + 16)); }
 unsigned kkt_border_wg(int ne) { return ne <= 32 ? 64u : 256u; }
-int kkt_launch_lds(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, unsigned block, unsigned lds) {
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, block, 1, 1, lds, m->stream, nullptr, cfg));
-  return IEM_OK;
-}
 // kkt_colsum's pair of launches for nr matrices of rows x w (matrix u at in + u in_ld) through `fn` (kkt_colsum_m of a chain module
 // or its twin kkt_border_colsum): partial rows at part + u part_ld, the sums at part + u part_ld + res_off
 int kkt_border_sums(iem_model *m, hipFunction_t fn, const double *in, long long in_ld, int64_t rows, int64_t w, int nr, double *part, long long part_ld, long long res_off) {
@@ -2926,12 +2953,12 @@ int kkt_border_factor_run(iem_model *m, hipFunction_t colsum, int64_t S, int ne,
   int rc = kkt_border_sums(m, colsum, d_Gp, w * S, S, w, 1, part, 0, res_off);
   if (rc) return rc;
   struct { const double *G, *gsum; double *F; int *piv; long long *info; int ne, n_border; double rel; } A{d_G, part + res_off, d_F, d_piv, (long long *)d_info, ne, n_border, rel};
-  return kkt_launch_lds(m, m->kb_ldl, &A, sizeof A, 1, kkt_border_wg(ne), kkt_border_lds(ne));
+  return launch_args(m->fixed[F_KBORDER].fn[KBORDER_LDL], &A, sizeof A, 1, 1, kkt_border_wg(ne), kkt_border_lds(ne), m->stream);
 }
 struct KktBorderSolveArgsH { const double *F; const int *piv; const double *rhs; const long long *src, *dst; const double *sum; double *xB; long long ld_rhs, ld_sum, ld_x; int ne, n_border; };
 int kkt_border_solve_run(iem_model *m, const KktBorderSolveArgsH &a, int nrhs) {
   KktBorderSolveArgsH A = a;
-  return kkt_launch_lds(m, m->kb_solve, &A, sizeof A, nrhs, kkt_border_wg(a.ne), kkt_border_lds(a.ne));
+  return launch_args(m->fixed[F_KBORDER].fn[KBORDER_SOLVE], &A, sizeof A, (unsigned)nrhs, 1, kkt_border_wg(a.ne), kkt_border_lds(a.ne), m->stream);
 }
 int kkt_border_workspace(iem_model *m, int64_t doubles) {
   if (m->kb_part_n >= doubles) return IEM_OK;
@@ -2942,12 +2969,7 @@ int kkt_border_workspace(iem_model *m, int64_t doubles) {
 }
 }  // namespace
 
-int iem_kkt_border_source(char **out_src, uint64_t *out_key) {
-  const std::string s = kkt_border_source();
-  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
-  if (out_key) *out_key = iem::fnv1a64(s);
-  return IEM_OK;
-}
+int iem_kkt_border_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_KBORDER, out_src, out_key); }
 
 int iem_kkt_border_factor(iem_model *m, int64_t S, int ne, int n_border, const double *d_G, const double *d_Gp, double *d_F, int32_t *d_piv, int64_t *d_info,
                           double rel) {
@@ -2959,7 +2981,7 @@ int iem_kkt_border_factor(iem_model *m, int64_t S, int ne, int n_border, const d
   if (rc) return rc;
   const int64_t w = (int64_t)ne * ne, nrc = std::min<int64_t>(S, 512);      // (at most 512 partial rows, then the result)
   if ((rc = kkt_border_workspace(m, (nrc + 1) * w))) return rc;
-  return kkt_border_factor_run(m, m->kb_colsum, S, ne, n_border, d_G, d_Gp, d_F, d_piv, d_info, rel, m->kb_part, nrc * w);
+  return kkt_border_factor_run(m, m->fixed[F_KBORDER].fn[KBORDER_COLSUM], S, ne, n_border, d_G, d_Gp, d_F, d_piv, d_info, rel, m->kb_part, nrc * w);
 }
 
 int iem_kkt_border_solve(iem_model *m, int64_t S, int ne, int n_border, int nrhs, const double *d_F, const int32_t *d_piv, const double *d_rBp, const double *d_rB,
@@ -2972,7 +2994,7 @@ int iem_kkt_border_solve(iem_model *m, int64_t S, int ne, int n_border, int nrhs
   if (rc) return rc;
   const int64_t nrc = std::min<int64_t>(S, 512), wp = (nrc + 1) * ne;
   if ((rc = kkt_border_workspace(m, (int64_t)nrhs * wp))) return rc;
-  if ((rc = kkt_border_sums(m, m->kb_colsum, d_rBp, (long long)(S * ne), S, ne, nrhs, m->kb_part, (long long)wp, (long long)(nrc * ne)))) return rc;
+  if ((rc = kkt_border_sums(m, m->fixed[F_KBORDER].fn[KBORDER_COLSUM], d_rBp, (long long)(S * ne), S, ne, nrhs, m->kb_part, (long long)wp, (long long)(nrc * ne)))) return rc;
   return kkt_border_solve_run(m, KktBorderSolveArgsH{d_F, d_piv, d_rB, nullptr, nullptr, m->kb_part + nrc * ne, d_xB, (long long)ne, (long long)wp, (long long)ne, ne, n_border}, nrhs);
 }
 
@@ -3496,7 +3518,7 @@ int iem_kkt_factor_async(iem_kkt *k, int64_t *d_inertia) {
   int rc = kkt_border_setup(m);
   if (rc || (rc = kkt_factor_launch(k))) return rc;
   struct { const long long *info; long long *out; long long n; } A{k->d_info, (long long *)d_inertia, (long long)(L.nvar + L.ncon)};
-  if ((rc = kkt_launch_raw(m, m->kb_inertia, &A, sizeof A, 1, 64))) return rc;
+  if ((rc = kkt_launch_raw(m, m->fixed[F_KBORDER].fn[KBORDER_INERTIA], &A, sizeof A, 1, 64))) return rc;
   k->factored = true;
   return IEM_OK;
 }
@@ -3589,30 +3611,17 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
 
 /* ---- the residual of a KKT solve, matrix-free, and iterative refinement with it ---------------------------------------------- */
 namespace {
-std::string kkt_residual_source() {
-  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktResidualSource;
-}
 // the finishing kernels and the workspace {p, r, dsol}: the synchronous part of the first call
 int kkt_refine_setup(iem_kkt *k) {
-  iem_model *m = k->m;
-  if (!m->kres_fn) {
-    int rc = load_source(m, kkt_residual_source(), &m->kres_mod);
-    if (rc) return rc;
-    HIP_TRY(hipModuleGetFunction(&m->kres_axpy, m->kres_mod, "kkt_axpy1"));
-    HIP_TRY(hipModuleGetFunction(&m->kres_fn, m->kres_mod, "kkt_residual"));
-  }
+  int rc = fixed_object(k->m, F_KRES);
+  if (rc) return rc;
   if (!k->w_ref) HIP_TRY(hipMalloc((void **)&k->w_ref, (size_t)std::max<int64_t>(3 * (k->L.nvar + k->L.ncon), 1) * 8));
   return IEM_OK;
 }
 long long kkt_stream_grid(int64_t n) { return (long long)std::min<int64_t>((n + 255) / 256, 4096); }
 }  // namespace
 
-int iem_kkt_residual_source(char **out_src, uint64_t *out_key) {
-  const std::string s = kkt_residual_source();
-  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
-  if (out_key) *out_key = iem::fnv1a64(s);
-  return IEM_OK;
-}
+int iem_kkt_residual_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_KRES, out_src, out_key); }
 
 int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
                      const double *d_rhs, const double *d_sol, double *d_r, double *d_norm) {
@@ -3630,7 +3639,7 @@ int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double ob
   if (d_norm) HIP_TRY(hipMemsetAsync(d_norm, 0, 8, m->stream));
   struct { const double *p, *rhs, *sol, *sigma; double *r; unsigned long long *norm; double dw, dc; long long nvar, n; } A{
       p, d_rhs, d_sol, d_sigma, d_r, (unsigned long long *)d_norm, delta_w, delta_c, (long long)nvar, (long long)n};
-  return kkt_launch_raw(m, m->kres_fn, &A, sizeof A, kkt_stream_grid(n), 256);
+  return kkt_launch_raw(m, m->fixed[F_KRES].fn[KRES_RESIDUAL], &A, sizeof A, kkt_stream_grid(n), 256);
 }
 
 int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
@@ -3651,7 +3660,7 @@ int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, doub
     if ((rc = iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms ? d_norms + i : nullptr))) return rc;
     if ((rc = iem_kkt_solve(k, r, dsol))) return rc;
     struct { double *sol; const double *d; long long n; } A{d_sol, dsol, (long long)n};
-    if ((rc = kkt_launch_raw(m, m->kres_axpy, &A, sizeof A, kkt_stream_grid(n), 256))) return rc;
+    if ((rc = kkt_launch_raw(m, m->fixed[F_KRES].fn[KRES_AXPY], &A, sizeof A, kkt_stream_grid(n), 256))) return rc;
   }
   if (d_norms) return iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms + steps);
   return IEM_OK;
@@ -3744,26 +3753,11 @@ int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs
  * K = [W + diag(sigma) + delta_w I, J'; J, -diag(dcon + delta_c)]  (csrc/iem_kkt_diag_device.h) */
 namespace {
 constexpr int KKT_DIAG_SLAB = 8;      // columns per pass: a multiple of every chunk width of the multi-column kernels (kkt_many_width: 2 or 4)
-std::string kkt_diag_source() {
-  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n") + kKktDiagSource;
-}
 // the code object and — `workspace` — the planes {p, r, dsol} of one slab: the synchronous part of the first call
 int kkt_diag_setup(iem_kkt *k, bool workspace) {
-  iem_model *m = k->m;
-  if (!m->kdg_res) {
-    int rc = load_source(m, kkt_diag_source(), &m->kdg_mod);
-    if (rc) return rc;
-    HIP_TRY(hipModuleGetFunction(&m->kdg_gather, m->kdg_mod, "kkt_gather_d"));
-    HIP_TRY(hipModuleGetFunction(&m->kdg_axpy, m->kdg_mod, "kkt_axpy_m"));
-    HIP_TRY(hipModuleGetFunction(&m->kdg_res, m->kdg_mod, "kkt_residual_dm"));
-  }
+  int rc = fixed_object(k->m, F_KDIAG);
+  if (rc) return rc;
   if (workspace && !k->w_diag) HIP_TRY(hipMalloc((void **)&k->w_diag, (size_t)std::max<int64_t>(3 * KKT_DIAG_SLAB * (k->L.nvar + k->L.ncon), 1) * 8));
-  return IEM_OK;
-}
-int kkt_launch_cols(iem_model *m, hipFunction_t fn, void *args, size_t sz, long long grid, int cols) {
-  if (grid <= 0 || cols <= 0) return IEM_OK;
-  void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-  HIP_TRY(hipModuleLaunchKernel(fn, (unsigned)grid, (unsigned)cols, 1, 256, 1, 1, 0, m->stream, nullptr, cfg));
   return IEM_OK;
 }
 // the whole extent [d, d + (nrhs - 1) ld + n) of a set of columns
@@ -3784,16 +3778,11 @@ int kkt_residual_slab(iem_kkt *k, const double *d_x, const double *d_y, double o
   struct { const double *p, *rhs, *sol, *sigma, *dcon; double *r; unsigned long long *norms; double dw, dc; long long nvar, n, ld_p, ld_rhs, ld_sol, ld_r; } A{
       p, d_rhs, d_sol, d_sigma, ncon ? d_dcon : nullptr, d_r, (unsigned long long *)d_norms, delta_w, delta_c, (long long)nvar, (long long)n, (long long)n,
       (long long)ld_rhs, (long long)ld_sol, (long long)ld_r};
-  return kkt_launch_cols(m, m->kdg_res, &A, sizeof A, kkt_stream_grid(n), nr);
+  return kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_RESIDUAL], &A, sizeof A, kkt_stream_grid(n), 256, nr);
 }
 }  // namespace
 
-int iem_kkt_diag_source(char **out_src, uint64_t *out_key) {
-  const std::string s = kkt_diag_source();
-  if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
-  if (out_key) *out_key = iem::fnv1a64(s);
-  return IEM_OK;
-}
+int iem_kkt_diag_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_KDIAG, out_src, out_key); }
 
 int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c) {
   if (!k || (!d_hess && k->n_h) || (!d_jac && k->n_j)) return fail(IEM_E_ARG, "null argument");
@@ -3808,7 +3797,7 @@ int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac,
       k->d_flat, k->d_dest, k->d_seg, k->d_perm, d_hess, d_jac, d_sigma, d_dcon, delta_w, delta_c, (long long)k->n_dest, (long long)k->n_h, (long long)k->n_j,
       (long long)L.nvar, (long long)L.ncon};
   k->factored = false;
-  return kkt_launch_raw(m, m->kdg_gather, &A, sizeof A, (k->n_dest + 255) / 256, 256);
+  return kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_GATHER], &A, sizeof A, (k->n_dest + 255) / 256, 256);
 }
 
 int iem_kkt_residual_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w,
@@ -3863,7 +3852,7 @@ int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y,
       if ((rc = residual(i))) return rc;
       if ((rc = iem_kkt_solve_many(k, nr, r, n, dsol, n))) return rc;
       struct { double *sol; const double *d; long long n, ld_s, ld_d; } A{sol, dsol, (long long)n, (long long)ld_sol, (long long)n};
-      if ((rc = kkt_launch_cols(m, m->kdg_axpy, &A, sizeof A, kkt_stream_grid(n), nr))) return rc;
+      if ((rc = kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_AXPY], &A, sizeof A, kkt_stream_grid(n), 256, nr))) return rc;
     }
     if (d_norms && (rc = residual(steps))) return rc;
   }
@@ -3897,15 +3886,6 @@ struct BarrierArgsH {
   double mu, tau, kappa, push, frac;
   long long nvar, n, n_wg;
 };
-enum { BAR_START, BAR_TERMS, BAR_STEP, BAR_UPDATE, BAR_ERROR, BAR_MERIT };
-
-std::string barrier_source() {
-  const std::string hdr(kDeviceHeader);
-  const size_t b = hdr.find("// IEM-TILE-REGION-END");
-  if (b == std::string::npos) throw std::runtime_error("internal: device header without tile-region markers");
-  return std::string("// iem-flags: -O3 -ffp-contract=off -std=c++17\n#ifndef __HIPCC_RTC__\n#include <hip/hip_runtime.h>\n#endif\n#define IEM_TILE 256\n") +
-         hdr.substr(0, b) + "#endif  // IEM_DEVICE_H (its kernels are not part of this code object)\n\n" + kBarrierSource;
-}
 BarrierArgsH barrier_args(const iem_barrier *b) {
   BarrierArgsH A;
   std::memset(&A, 0, sizeof A);
@@ -3915,7 +3895,7 @@ BarrierArgsH barrier_args(const iem_barrier *b) {
   A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
   return A;
 }
-int barrier_launch(const iem_barrier *b, int which, BarrierArgsH &A) { return kkt_launch_raw(b->m, b->m->kbar_fn[which], &A, sizeof A, b->n_wg, 256); }
+int barrier_launch(const iem_barrier *b, int which, BarrierArgsH &A) { return kkt_launch_raw(b->m, b->m->fixed[F_BARRIER].fn[which], &A, sizeof A, b->n_wg, 256); }
 // the state vectors a call needs: x with variables, y and the slack side with rows (the slack side only with inequality rows)
 bool barrier_state_missing(const iem_barrier *b, const double *x, const double *s, const double *y, const double *zL, const double *zU, const double *vL, const double *vU) {
   return (b->nvar && (!x || !zL || !zU)) || (b->ncon && !y) || (b->n_ineq && (!s || !vL || !vU));
@@ -3977,14 +3957,7 @@ int iem_barrier_analyse(int64_t nvar, int64_t ncon, const double *h_lvar, const 
   return rc ? rc : barrier_info_out(&hb, info);
 }
 
-int iem_barrier_source(char **out_src, uint64_t *out_key) {
-  try {
-    const std::string s = barrier_source();
-    if (out_src) { *out_src = (char *)std::malloc(s.size() + 1); std::memcpy(*out_src, s.c_str(), s.size() + 1); }
-    if (out_key) *out_key = iem::fnv1a64(s);
-  } catch (const std::exception &e) { return fail(IEM_E_COMPILE, e.what()); }
-  return IEM_OK;
-}
+int iem_barrier_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_BARRIER, out_src, out_key); }
 
 int iem_barrier_destroy(iem_barrier *b) {
   if (!b) return IEM_OK;
@@ -4018,13 +3991,9 @@ int iem_barrier_create(iem_model *m, const double *h_lvar, const double *h_uvar,
     if (rc) return rc;
   }
   DevGuard dg_(m->device);
-  if (!m->kbar_mod) {
-    std::string src_txt;
-    try { src_txt = barrier_source(); } catch (const std::exception &e) { return fail(IEM_E_COMPILE, e.what()); }
-    int rc = load_source(m, src_txt, &m->kbar_mod);
+  {
+    int rc = fixed_object(m, F_BARRIER);
     if (rc) return rc;
-    static const char *names[6] = {"barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"};
-    for (int i = 0; i < 6; ++i) HIP_TRY(hipModuleGetFunction(&m->kbar_fn[i], m->kbar_mod, names[i]));
   }
   struct Drop { void operator()(iem_barrier *p) const { iem_barrier_destroy(p); } };      // (a failed create frees what it had uploaded)
   std::unique_ptr<iem_barrier, Drop> b(hb.release());

@@ -22,6 +22,9 @@ class IemError(RuntimeError):
     pass
 
 
+IEM_E_ARG = -4      # (include/iem.h)
+
+
 class Meta(C.Structure):
     _fields_ = [("nvar", C.c_int64), ("ncon", C.c_int64), ("npar", C.c_int64), ("nnzj", C.c_int64),
                 ("nnzh", C.c_int64), ("n_templates", C.c_int64), ("minimize", C.c_int32),
@@ -91,7 +94,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_residual_source", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_residual_source", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -238,8 +241,9 @@ def lib():
     L.iem_barrier_error.argtypes = [vp] + [vp] * 9 + [dbl, vp]
     L.iem_barrier_merit.argtypes = [vp, vp, vp, vp, vp]
     L.iem_barrier_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
-    L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64)]
+    L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
+    L.iem_fixed_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_free.argtypes = [vp]
     L.iem_set_option.argtypes = [C.c_char_p, i64]
     L.iem_time_kernels.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(dbl), C.POINTER(dbl)]
@@ -300,18 +304,19 @@ class options:
         return False
 
 
+def _source(fn, *args):
+    """``(text, key)`` of a source entry point: ``fn(*args, &text, &key)``, the text decoded and freed."""
+    p, key = C.c_void_p(), C.c_uint64()
+    check(fn(*args, C.byref(p), C.byref(key)))
+    try:
+        return C.string_at(p).decode(), int(key.value)
+    finally:
+        lib().iem_free(p)
+
+
 def emit_source(blob: bytes):
     """Generated HIP source of a model and its cache key (no device needed)."""
-    L = lib()
-    L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
-    p = C.c_void_p()
-    key = C.c_uint64()
-    check(L.iem_emit_source(blob, len(blob), C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_emit_source, blob, len(blob))
 
 
 def kkt_analyse_blob(blob: bytes, group: int = 0):
@@ -338,64 +343,39 @@ def kkt_analyse_blob(blob: bytes, group: int = 0):
 def kkt_source(nb: int, ne: int, nc: int = 12):
     """HIP source of the chain KKT solver's kernels for block size ``nb`` / border size ``ne`` / coupling width ``nc`` and its
     cache key."""
-    L = lib()
-    p, key = C.c_void_p(), C.c_uint64()
-    check(L.iem_kkt_source(int(nb), int(ne), int(nc), C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_kkt_source, int(nb), int(ne), int(nc))
 
 
 def kkt_residual_source():
     """HIP source of the finishing kernels of ``iem_kkt_residual`` / ``iem_kkt_solve_refined`` and its cache key."""
-    L = lib()
-    p, key = C.c_void_p(), C.c_uint64()
-    check(L.iem_kkt_residual_source(C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_kkt_residual_source)
 
 
 def kkt_diag_source():
     """HIP source of the per-row diagonal's kernels (``kkt_gather_d`` / ``kkt_residual_dm`` / ``kkt_axpy_m``: ``iem_kkt_assemble_diag``,
     ``iem_kkt_residual_diag``, ``iem_kkt_solve_refined_diag``) and its cache key."""
-    L = lib()
-    p, key = C.c_void_p(), C.c_uint64()
-    check(L.iem_kkt_diag_source(C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_kkt_diag_source)
 
 
 def kkt_border_source():
     """HIP source of the dense border's kernels (``kkt_border_ldl`` / ``kkt_border_solve``) and its cache key."""
-    L = lib()
-    p, key = C.c_void_p(), C.c_uint64()
-    check(L.iem_kkt_border_source(C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_kkt_border_source)
 
 
 def barrier_source():
     """HIP source of the interior-point barrier layer's kernels (``barrier_start`` / ``_terms`` / ``_step`` / ``_update`` / ``_error`` /
     ``_merit``: the ``iem_barrier_*`` calls) and its cache key."""
-    L = lib()
-    p, key = C.c_void_p(), C.c_uint64()
-    check(L.iem_barrier_source(C.byref(p), C.byref(key)))
-    try:
-        src = C.string_at(p).decode()
-    finally:
-        L.iem_free(p)
-    return src, int(key.value)
+    return _source(lib().iem_barrier_source)
+
+
+def fixed_sources():
+    """``(name, src, key)`` of every hand-written code object whose source depends on no model and no shape (``iem_fixed_source``):
+    the four above, and whatever the library gains."""
+    L, i, name = lib(), 0, C.c_char_p()
+    while L.iem_fixed_source(i, None, None, None) != IEM_E_ARG:      # (IEM_E_ARG: past the end; any other failure is raised below)
+        src, key = _source(L.iem_fixed_source, i, C.byref(name))
+        yield name.value.decode(), src, key
+        i += 1
 
 
 def barrier_analyse(lvar, uvar, lcon, ucon, relax: float = 1e-8):
@@ -421,16 +401,20 @@ def kkt_many_width(nb: int, ne: int, nc: int = 12) -> int:
     return int(re.search(r"^#define KKT_MR (\d+)$", kkt_source(nb, ne, nc)[0], re.M).group(1))
 
 
-def precompile_source(src: str, key: int, arch: str = "gfx950", defer: list = None) -> str:
-    """Offline-compile a complete HIP source (first line ``// iem-flags: ...``) into the in-tree code-object cache."""
+def precompile_source(src: str, key: int, arch: str = "gfx950", defer: list = None, force: bool = False) -> str:
+    """Offline-compile a complete HIP source (first line ``// iem-flags: ...``) into the in-tree code-object cache
+    (``hipcc --genco --offload-arch=gfx950``); returns the ``.hsaco`` path.  With ``defer`` (a list) the hipcc command
+    is appended to the list instead of being run: ``run_deferred`` compiles them in parallel."""
+    first = src.split("\n", 1)[0]
+    assert first.startswith("// iem-flags:"), first
     os.makedirs(KERNEL_DIR, exist_ok=True)
     out = os.path.join(KERNEL_DIR, f"iem_{key:016x}.hsaco")
-    if os.path.exists(out):
+    if os.path.exists(out) and not force:
         return out
     hip = os.path.join(KERNEL_DIR, f"iem_{key:016x}.hip")
     with open(hip, "w") as f:
         f.write(src)
-    flags = src.split("\n", 1)[0][len("// iem-flags:"):].split()
+    flags = first[len("// iem-flags:"):].split()
     cmd = [os.path.join(ROCM, "bin", "hipcc"), "--genco", f"--offload-arch={arch}", *flags, "-o", out + ".tmp", hip]
     if defer is not None:
         if not any(c[1] == out for c in defer):
@@ -545,29 +529,8 @@ def shard_blob(blob: bytes, group: int, rank: int, world: int):
 
 
 def precompile(blob: bytes, arch: str = "gfx950", force: bool = False, defer: list = None) -> str:
-    """Offline-compile a model's kernels into the in-tree code-object cache
-    (``hipcc --genco --offload-arch=gfx950``); returns the ``.hsaco`` path.  With ``defer`` (a
-    list) the source is generated now — under the CURRENT generator options — and the hipcc command
-    is appended to the list instead of being run: ``run_deferred`` compiles them in parallel."""
-    src, key = emit_source(blob)
-    os.makedirs(KERNEL_DIR, exist_ok=True)
-    out = os.path.join(KERNEL_DIR, f"iem_{key:016x}.hsaco")
-    if os.path.exists(out) and not force:
-        return out
-    hip = os.path.join(KERNEL_DIR, f"iem_{key:016x}.hip")
-    with open(hip, "w") as f:
-        f.write(src)
-    first = src.split("\n", 1)[0]
-    assert first.startswith("// iem-flags:"), first
-    flags = first[len("// iem-flags:"):].split()
-    cmd = [os.path.join(ROCM, "bin", "hipcc"), "--genco", f"--offload-arch={arch}", *flags, "-o", out + ".tmp", hip]
-    if defer is not None:
-        if not any(c[1] == out for c in defer):
-            defer.append((cmd, out))
-        return out
-    subprocess.check_call(cmd)
-    os.replace(out + ".tmp", out)
-    return out
+    """``precompile_source`` of a model's kernels: the source is generated now — under the CURRENT generator options."""
+    return precompile_source(*emit_source(blob), arch=arch, defer=defer, force=force)
 
 
 def run_deferred(jobs: list, workers: int = 0) -> None:
