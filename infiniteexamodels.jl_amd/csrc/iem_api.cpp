@@ -1233,10 +1233,7 @@ static int create_impl(const void *blob, size_t nbytes, int device, const iem_op
   if (device < 0 || device >= ndev) return fail(IEM_E_ARG, "device ordinal out of range");
   iem_model *m = new iem_model();
   m->device = device;
-  hopt.param_kinds = 0;   // (the handle's own program; a derived program sets the one field of its row in kDerived)
-  hopt.scaled_kinds = 0;
-  hopt.kkt_kinds = 0;
-  hopt.scaled_phase_kinds = 0;
+  iem::select_program(hopt, iem::PG_MODEL);   // (the handle's own program; a derived program is selected by its row in kDerived)
   m->opt = hopt;
   m->poll_obj = hpoll;
   try {
@@ -1573,13 +1570,12 @@ int iem_hprod(iem_model *m, const double *d_x, const double *d_y, const double *
 }
 
 // ---- the derived programs ---------------------------------------------------------------------------------------------------
-// One row per program of iem_model::derived, in the order of `Derived`.  `field` = `value`: the one generator option that
-// selects the program (the other three stay 0, as in the handle's own options).  `sharded`: why its entry points refuse a
-// sharded handle.  `partials`: it has objective kernels, so it owns partials and ticket words.  To add a program: a row
-// here (and a name in `Derived`), its entry points, and a row in build().
+// One row per program of iem_model::derived, in the order of `Derived`.  `program`: the generator's program (iem_codegen.cpp:
+// kPrograms), selected on top of the handle's own options.  `sharded`: why its entry points refuse a
+// sharded handle.  `partials`: it has objective kernels, so it owns partials and ticket words.  To add a program: its row in
+// kPrograms, a row here (and a name in `Derived`), its entry points, and a row in build().
 struct DerivedRow {
-  int iem::Options::*field;
-  int value;
+  iem::ProgramId program;
   const char *sharded;
   bool partials;
 };
@@ -1587,29 +1583,29 @@ static const char kShardedTheta[] = "θ is replicated on every rank, so the prod
                                     "sharded parameter products are out of scope";
 static const DerivedRow kDerived[D_COUNT] = {
     // D_PAR: the three parameter kinds (iem_jpprod / iem_jptprod / iem_hpprod), shaped like jprod / jtprod / hprod
-    {&iem::Options::param_kinds, 1, kShardedTheta, false},
+    {iem::PG_THETA, kShardedTheta, false},
     // D_ADJ: the adjoint parameter kind (iem_hptprod) on KK_HPROD's table slot
-    {&iem::Options::param_kinds, 2, kShardedTheta, false},
+    {iem::PG_ADJOINT, kShardedTheta, false},
     // D_TH2: the θθ kind (iem_hppprod) on KK_HPROD's table slot
-    {&iem::Options::param_kinds, 3, kShardedTheta, false},
+    {iem::PG_THETA2, kShardedTheta, false},
     // D_PC: the explicit θ blocks in COO (iem_jacp_coord on KK_JAC's table slot, iem_hessp_coord on KK_HESS's); no scatter kind
-    {&iem::Options::param_kinds, 4, kShardedTheta, false},
+    {iem::PG_COORD, kShardedTheta, false},
     // D_LAG: the residual program (iem_lagrad / iem_eval_residual): lagrad on KK_JTPROD's table slot, the model's own cons and
     // obj, KK_TRIAL with lagrad as third member
-    {&iem::Options::param_kinds, 5,
+    {iem::PG_LAGRAD,
      "the gradient of the Lagrangian would need the halo fold and the all-reduce of grad! and jtprod!; a sharded residual is out of scope", true},
     // D_SCL: the scaled program (iem_jac_rowmax / iem_cons_scaled / iem_jac_coord_scaled): rowmax on KK_JPROD's table slot,
     // cons_scaled on KK_CONS's, jac_scaled on KK_JAC's; s = the head's v.  No scatter kind: no follow-up, no memset
-    {&iem::Options::scaled_kinds, 1,
+    {iem::PG_SCALED,
      "the values need no communication, but the deferred halo exchange (carrier workgroup, flush in front of a launch that reads a halo entry) "
      "is not taught this program; scaled kernels on a sharded handle are out of scope", false},
     // D_KKT: the KKT operator (iem_kktprod): kktx on KK_HPROD's table slot, kkty on KK_JPROD's, KK_TRIAL with both as members;
     // u = the head's v, the dual direction = the head's last word
-    {&iem::Options::kkt_kinds, 1,
+    {iem::PG_KKT,
      "the x-part would need the halo fold and the all-reduce of hprod! and jtprod!; a sharded KKT operator is out of scope", false},
     // D_SPH: the scaled solver phases (iem_eval_trial_scaled / iem_eval_accepted_scaled and their members): sp_cons / sp_jac /
     // sp_hess / sp_obj / sp_grad on the model's own table slots, KK_TRIAL and KK_ACCEPTED over them; s = the head's v, y = the head's y
-    {&iem::Options::scaled_phase_kinds, 1,
+    {iem::PG_SPHASE,
      "the scaled gradient would need the halo fold and the all-reduce of grad!, and the deferred halo exchange is not taught this program; "
      "scaled solver phases on a sharded handle are out of scope", true},
 };
@@ -1627,7 +1623,7 @@ static int derived_program(iem_model *m, Derived d) {
   LoadedProgram &P = m->derived[d];
   if (P.tried) return P.rc ? fail(P.rc, P.err) : IEM_OK;
   iem::Options po = m->opt;
-  po.*kDerived[d].field = kDerived[d].value;
+  iem::select_program(po, kDerived[d].program);
   int rc = IEM_OK;
   try {
     P.prog = iem::generate(m->model, po);

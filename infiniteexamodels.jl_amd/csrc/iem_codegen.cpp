@@ -197,13 +197,13 @@ struct Output {
   int fold = 0;
   int64_t pin_J = 0, pin_K = -1, pin_de = 0;
   std::vector<int> grad_tidx;   // scatter kinds: template index-expression id behind each destination
-  bool to_aux = false;          // the explicit θ blocks (Options::param_kinds = 4): this COO stream goes to the kernel's second buffer
+  bool to_aux = false;          // the explicit θ blocks (PG_COORD): this COO stream goes to the kernel's second buffer
 };
 
 class KernelBuilder {
  public:
-  KernelBuilder(const Model &m, const Group &g, int kind, const Options &opt, const std::string &name)
-      : m_(m), g_(g), kind_(kind), opt_(opt), name_(name) {}
+  KernelBuilder(const Model &m, const Group &g, int kind, ProgramId pg, const Options &opt, const std::string &name)
+      : m_(m), g_(g), kind_(kind), pg_(pg), opt_(opt), name_(name) {}
 
   // ---- parameters ---------------------------------------------------------
   std::string ip(int64_t v, int space = 0) {
@@ -768,21 +768,15 @@ class KernelBuilder {
   }
 
   // ---- build the kernel's outputs ---------------------------------------------
-  // parameter kinds (Options::param_kinds; m_ is the parameter view): slots of θ
-  bool theta_kinds() const { return opt_.param_kinds >= 1 && opt_.param_kinds <= 4; }
-  // param_kinds = 5: the residual program over the PLAIN model — lagrad (σ ∇f + J' y) on the table slot of jtprod, next to the
-  // model's own cons and obj
-  bool lagrangian() const { return opt_.param_kinds == 5; }
-  // scaled_kinds = 1: the scaled program over the PLAIN model — rowmax on the table slot of jprod, cons_scaled on that of cons!,
-  // jac_scaled on that of jac_coord!; the factors s are A.v, indexed by the row
-  bool scaled() const { return opt_.scaled_kinds != 0; }
-  // kkt_kinds = 1: the KKT operator over the PLAIN model — kktx (W u + J' dv) on the table slot of hprod, kkty (J u) on that of
-  // jprod with the model's own builder; u = A.v, the dual direction dv = A.p6, read at row indices like y
-  bool kkt() const { return opt_.kkt_kinds != 0; }
-  // scaled_phase_kinds = 1: the scaled solver phases over the PLAIN model — the model's five kinds on their own table slots with
-  // the row factors s = A.v inside (sp_cons, sp_jac as the scaled program's; sp_hess seeded with fl(y[row] * s[row])) and the
-  // gradient seeded with A.w (sp_grad); sp_obj is the model's own objective
-  bool sphase() const { return opt_.scaled_phase_kinds != 0; }
+  // which program the kernel belongs to (kPrograms says what each is)
+  bool theta_kinds() const { return pg_ >= PG_THETA && pg_ <= PG_COORD; }   // m_ is the parameter view: slots of θ
+  bool theta_adjoint() const { return pg_ == PG_ADJOINT; }
+  bool theta_second() const { return pg_ == PG_THETA2; }
+  bool theta_coord() const { return pg_ == PG_COORD; }
+  bool lagrangian() const { return pg_ == PG_LAGRAD; }
+  bool scaled() const { return pg_ == PG_SCALED; }
+  bool kkt() const { return pg_ == PG_KKT; }
+  bool sphase() const { return pg_ == PG_SPHASE; }
   // s[row] of a constraint template's item: one load per row, where jtprod loads its seed
   int scale_of_row(const Template &t, const TGeo &G) {
     IdxVal rv; rv.aff = klin_aff(t, G, 1, t.o0); rv.aff.space = 4;   // a row index (into s), not an output position
@@ -790,12 +784,6 @@ class KernelBuilder {
   }
   // ONE rounded multiply of a finished value — never folded away (a slot that is the constant 1 or -0.0 still gives fl(s * slot))
   int scaled_by(int val, int s) { return mk(VBIN, IEM_OP_MUL, s, val < 0 ? C(0.0) : val, -1, 0); }
-  // param_kinds = 2: the adjoint program, hptprod alone on the table slot of hprod — tangents on the slots of x, outputs on the slots of θ
-  bool theta_adjoint() const { return opt_.param_kinds == 2; }
-  // param_kinds = 3: the θθ program, hppprod alone on the same table slot — tangents AND outputs on the slots of θ
-  bool theta_second() const { return opt_.param_kinds == 3; }
-  // param_kinds = 4: the explicit blocks in COO — jacp on the table slot of jac_coord!, hessp (two streams) on that of hess_coord!
-  bool theta_coord() const { return opt_.param_kinds == 4; }
   static bool has_theta_slot1(const Template &t) {
     for (int id : t.slot1_idx) if (t.is_theta_idx(id)) return true;
     return false;
@@ -808,44 +796,36 @@ class KernelBuilder {
     for (size_t s = 0; s < t.slot2_i.size(); ++s) if (t.is_theta_idx(t.slot2_i[s]) && t.is_theta_idx(t.slot2_j[s])) return true;
     return false;
   }
+  // The templates a kernel of kind_ is built from (asked only for the kinds the program has, kPrograms): those of the model's
+  // own kind on the same table slot, unless the program says otherwise
   bool relevant(const Template &t) const {
-    if (theta_coord()) return kind_ == KK_JAC ? !t.pc1.empty() : kind_ == KK_HESS && (!t.pcx.empty() || !t.pcp.empty());
-    if (theta_second()) return kind_ == KK_HPROD && has_theta_slot2(t);
-    if (theta_adjoint()) return kind_ == KK_HPROD && has_cross_slot2(t);
-    if (scaled()) switch (kind_) {
-      case KK_CONS: return t.kind == IEM_T_CON;
-      case KK_JAC: return t.kind == IEM_T_CON && t.o1step > 0;
-      case KK_JPROD: return t.kind == IEM_T_CON;           // rowmax: every row is written, 0.0 for a row without a slot
-      default: return false;
-    }
-    if (kkt()) switch (kind_) {
-      case KK_JPROD: return t.kind == IEM_T_CON;
-      // every template with a second-order slot, and every constraint template with a first-order one (an objective template
-      // contributes no first-order term: without a second-order slot it has nothing to add)
-      case KK_HPROD: return t.o2step > 0 || (t.kind == IEM_T_CON && t.o1step > 0);
-      default: return false;
-    }
-    if (sphase() && kind_ >= KK_JPROD) return false;   // the model's five evaluation kinds below, no product kind
-    if (lagrangian()) switch (kind_) {
-      case KK_CONS: return t.kind == IEM_T_CON;
-      case KK_OBJ: return t.kind == IEM_T_OBJ;
-      case KK_JTPROD: return t.o1step > 0;                 // constraints (seed y) and objective terms (seed σ): every first-order slot
-      default: return false;
-    }
-    if (theta_kinds()) switch (kind_) {
-      case KK_JPROD: return t.kind == IEM_T_CON;           // every row is written: zero where c does not depend on θ
-      case KK_JTPROD: return has_theta_slot1(t);           // constraints (seed y) and objective terms (seed σ)
-      case KK_HPROD: return has_cross_slot2(t);
-      default: return false;
+    const bool con = t.kind == IEM_T_CON, obj = t.kind == IEM_T_OBJ;
+    switch (pg_) {
+      case PG_THETA:
+        if (kind_ == KK_JTPROD) return has_theta_slot1(t);   // constraints (seed y) and objective terms (seed σ)
+        if (kind_ == KK_HPROD) return has_cross_slot2(t);
+        break;                                               // jpprod: every row is written, zero where c does not depend on θ
+      case PG_ADJOINT: return has_cross_slot2(t);
+      case PG_THETA2: return has_theta_slot2(t);
+      case PG_COORD: return kind_ == KK_JAC ? !t.pc1.empty() : !t.pcx.empty() || !t.pcp.empty();
+      case PG_LAGRAD:
+        if (kind_ == KK_JTPROD) return t.o1step > 0;         // constraints (seed y) and objective terms (seed σ): every first-order slot
+        break;
+      case PG_KKT:
+        // kktx: every template with a second-order slot, and every constraint template with a first-order one (an objective
+        // template contributes no first-order term: without a second-order slot it has nothing to add)
+        if (kind_ == KK_HPROD) return t.o2step > 0 || (con && t.o1step > 0);
+        break;
+      default: break;   // PG_MODEL; PG_SCALED (rowmax: every row is written, 0.0 for a row without a slot); PG_SPHASE
     }
     switch (kind_) {
-      case KK_CONS: return t.kind == IEM_T_CON;
-      case KK_JAC: return t.kind == IEM_T_CON && t.o1step > 0;
+      case KK_CONS: return con;
+      case KK_JAC: return con && t.o1step > 0;
       case KK_HESS: return t.o2step > 0;
-      case KK_OBJ: return t.kind == IEM_T_OBJ;
-      case KK_GRAD: return t.kind == IEM_T_OBJ && t.o1step > 0;
-      case KK_JPROD: return t.kind == IEM_T_CON;
-      case KK_JTPROD: return t.kind == IEM_T_CON && t.o1step > 0;
+      case KK_OBJ: return obj;
+      case KK_GRAD: return obj && t.o1step > 0;
+      case KK_JPROD: return con;
+      case KK_JTPROD: return con && t.o1step > 0;
       case KK_HPROD: return t.o2step > 0;
     }
     return false;
@@ -2183,6 +2163,7 @@ class KernelBuilder {
   const Model &m_;
   const Group &g_;
   int kind_;
+  ProgramId pg_;   // the program this kernel belongs to (kPrograms)
   Options opt_;
   std::string name_;
   std::vector<VNode> v_;
@@ -2610,17 +2591,100 @@ static void emit_dispatch_chain(std::ostream &src, size_t nb, size_t dec, size_t
   }
 }
 
-static const char *const kname[] = {"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"};
-// the parameter kinds (Options::param_kinds) ride on the table slots of the kinds they are shaped like
-static const char *const kname_theta[] = {"", "", "", "", "", "jpprod", "jptprod", "hpprod"};
-static const char *const kname_theta2[] = {"", "", "", "", "", "", "", "hptprod"};   // param_kinds = 2: the adjoint program
-static const char *const kname_theta3[] = {"", "", "", "", "", "", "", "hppprod"};   // param_kinds = 3: the θθ program
-static const char *const kname_theta4[] = {"", "jacp", "hessp", "", "", "", "", ""};     // param_kinds = 4: the explicit blocks in COO
-static const char *const kname_lag[] = {"cons", "", "", "obj", "", "", "lagrad", ""};   // param_kinds = 5: the residual program (plain model)
-static const char *const kname_scaled[] = {"cons_scaled", "jac_scaled", "", "", "", "rowmax", "", ""};   // scaled_kinds = 1: the scaled program (plain model)
-static const char *const kname_kkt[] = {"", "", "", "", "", "kkty", "", "kktx"};   // kkt_kinds = 1: the KKT operator (plain model)
-static const char *const kname_sphase[] = {"sp_cons", "sp_jac", "sp_hess", "sp_obj", "sp_grad", "", "", ""};   // scaled_phase_kinds = 1: the scaled solver phases (plain model)
-static const char *const *kind_names(const Options &o) { return o.scaled_phase_kinds ? kname_sphase : o.kkt_kinds ? kname_kkt : o.scaled_kinds ? kname_scaled : o.param_kinds == 5 ? kname_lag : o.param_kinds == 4 ? kname_theta4 : o.param_kinds == 3 ? kname_theta3 : o.param_kinds == 2 ? kname_theta2 : o.param_kinds ? kname_theta : kname; }
+// ---- the nine programs ---------------------------------------------------------------------------------------------------
+// A model has its own program and eight derived ones, each generated on its own by the same machinery; a row of kPrograms
+// holds what differs between them, KernelBuilder (relevant(), build()) the arithmetic of their kinds.  To add a program: a
+// ProgramId, a row here, its cases in KernelBuilder — and in the runtime a row in kDerived (iem_api.cpp) and one in build().
+enum ModelView { MV_PLAIN,        // the model as parsed
+                 MV_THETA,        // parameter_view: θ nodes are variables of the extended vector [x; θ]
+                 MV_THETA_COO };  // ... with param_coord_layout: the COO positions of the explicit θ blocks
+// options a program overrides whatever the caller set
+enum : unsigned { NO_HESS_MERGE = 1, NO_PAIR = 2, NO_PHASES = 4,
+                  MODEL_TILE = 8,          // the model's tile on every grid, no large-grid shape (big_batch_jac = big_batch_hess = 0)
+                  ONE_BODY_PER_GRID = 16 };   // fold_colloc = 0, jac_split = 0
+// One launch per solver phase: member kinds behind one workgroup-id dispatcher (emit_phases).  out / aux: the phase's buffers
+// for the member; w: passed to the member's bodies in place of A.w
+struct Member { int kind; const char *out, *aux; const char *w = nullptr; };
+struct Phase { int id; const char *name; std::vector<Member> mem; };
+struct ProgramSpec {
+  const char *kname[KK_COUNT];   // kernel name per KernelKind — the table slot, pointers and follow-ups the kernel takes; "": no such kind
+  ModelView view;
+  unsigned overrides;
+  unsigned npar_out;             // bit per scatter kind whose output has npar entries (an entry per θ), not nvar
+  bool two_addend;               // entries with at most two addends may stay f64 atomics (a + b = b + a); false: no float atomic at all
+  bool dv;                       // the bodies take the dual direction (the head's p6) behind v
+  bool sp_word;                  // the source starts with iem_sp_word
+  std::vector<Phase> phases;
+  bool has(int kind) const { return kname[kind][0] != 0; }
+  bool in_a_phase(int kind) const {
+    for (const Phase &ph : phases) for (const Member &mb : ph.mem) if (mb.kind == kind) return true;
+    return false;
+  }
+};
+static const ProgramSpec kPrograms[PG_COUNT] = {
+    // PG_MODEL: the model's own program, the kinds of NLPModels.  Phases — trial: out = c, aux = the objective scalar, p2 = its
+    // partials; accepted: out = jac values, aux = hess values, p2 = g, p3 = grad!'s reduction buffer; and all five evaluations
+    // of one point in ONE launch (iem_eval_all: the solver's first trial point is usually accepted): p4 = c, p5 = the
+    // objective's partials, p6 = its scalar
+    {{"cons", "jac", "hess", "obj", "grad", "jprod", "jtprod", "hprod"}, MV_PLAIN, 0, 0, true, false, false,
+     {{KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
+      {KK_ACCEPTED, "iem_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}}},
+      {KK_ALL, "iem_point_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_CONS, "A.p4", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}, {KK_OBJ, "A.p5", "A.p6"}}}}},
+    // PG_THETA: the parameter kinds — jpprod (dc/dθ) w, jptprod σ df/dθ + (dc/dθ)' y (npar entries, A.w = σ), hpprod
+    // (d2L/dx dθ) w — shaped like jprod / jtprod / hprod: differentiated over [x; θ], the builders keep the slots the kind asks
+    // for and drop the rest before anything is emitted; the same deterministic scatter machinery
+    {{"", "", "", "", "", "jpprod", "jptprod", "hpprod"}, MV_THETA, 0, 1u << KK_JTPROD, true, false, false, {}},
+    // PG_ADJOINT: hptprod (d2L/dθ dx) u alone, the transpose of hpprod — the same second-order sweep with the tangent u on the
+    // slots of x and the θ slots of the mixed entries kept; npar entries, scattered like jptprod's
+    {{"", "", "", "", "", "", "", "hptprod"}, MV_THETA, 0, 1u << KK_HPROD, false, false, false, {}},
+    // PG_THETA2: hppprod (d2L/dθ2) w alone — the second-order slots with BOTH entries in θ, hprod's arithmetic on them (the
+    // symmetric addend behind the same select), tangent and output over θ
+    {{"", "", "", "", "", "", "", "hppprod"}, MV_THETA, 0, 1u << KK_HPROD, false, false, false, {}},
+    // PG_COORD: the explicit blocks in COO — jacp: dc/dθ, the θ slots of the constraint templates' first-order slots; hessp:
+    // d2L/dx dθ (out) and d2L/dθ2 (aux), the second-order slots with one / with two entries in θ, from ONE sweep.  One lane per
+    // item, every slot stored once through the staged store path of jac_coord! / hess_coord!, layout by param_coord_layout.
+    // Item-owned stores need none of the scatter machinery (no folded collocation boxes), and the blocks are small next to the
+    // model's own COO outputs: one body per grid and kind, the model's tile; no scatter kind, no atomic
+    {{"", "jacp", "hessp", "", "", "", "", ""}, MV_THETA_COO, NO_HESS_MERGE | NO_PAIR | NO_PHASES | MODEL_TILE | ONE_BODY_PER_GRID, 0, false, false, false, {}},
+    // PG_LAGRAD: the residual program over the PLAIN model — lagrad: σ ∇f + J' y, the gradient of  σ f + y . c: objective
+    // templates seeded with σ (A.w), constraint templates with y[row] (A.v), every first-order slot kept, ONE deterministic
+    // scatter over both — next to the model's own cons and obj (same builders, same bodies).  ONE phase, the convergence check
+    // (iem_eval_residual): c, f and the dual residual in one launch — p3 = lagrad's output, p4 = its reduction buffer; its
+    // follow-ups stay with the runtime like grad!'s
+    {{"cons", "", "", "obj", "", "", "lagrad", ""}, MV_PLAIN, 0, 0, false, false, false,
+     {{KK_TRIAL, "iem_residual_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}, {KK_JTPROD, "A.p3", "A.p4"}}}}},
+    // PG_SCALED: the row scaling of a solver (Ipopt's gradient-based scaling, MadNLP's scale_constraints!) inside the kernels,
+    // over the PLAIN model.  s = A.v (ncon factors):
+    //   rowmax      (ncon out, no tangent loaded): max over the first-order slots of the row of |slot|, NaN-propagating, 0.0
+    //               for a row without a slot — a per-lane reduction, one exclusive store per row
+    //   cons_scaled s[row] * c_row(x), ONE rounded multiply of the value cons! computes
+    //   jac_scaled  s[row] * slot, ONE rounded multiply of every finished slot value (the reverse sweep is NOT seeded with s:
+    //               the linear rows' partials are item data), at the positions of jac_structure
+    // Same groups, folds, halves (jac_split) and store path as the model's own kinds.  No atomics
+    {{"cons_scaled", "jac_scaled", "", "", "", "rowmax", "", ""}, MV_PLAIN, NO_HESS_MERGE | NO_PAIR | NO_PHASES | MODEL_TILE, 0, false, false, false, {}},
+    // PG_KKT: the KKT operator over the PLAIN model.  u = A.v (nvar), the dual direction dv = the head's p6 (ncon, read at row
+    // indices like y), σ = A.w:
+    //   kktx (nvar out): W u + J' dv, W = σ ∇²f + Σ y_r ∇²c_r — hprod's contributions of every template with a second-order
+    //        slot, and for every constraint template with a first-order slot the first-order sweep seeded with dv[row], both
+    //        through ONE contribute map and ONE deterministic scatter; an entry no template touches comes out as 0
+    //   kkty (ncon out): J u, the model's own jprod builder and kind options
+    // ONE phase on the free slot KK_TRIAL, the whole operator in one launch (iem_kktprod_all): kkty's out = p2, kktx's out /
+    // aux as in its own launch; kktx's follow-ups stay with the runtime
+    {{"", "", "", "", "", "kkty", "", "kktx"}, MV_PLAIN, NO_HESS_MERGE | NO_PAIR | MODEL_TILE, 0, false, true, false,
+     {{KK_TRIAL, "iem_kktprod_all", {{KK_JPROD, "A.p2", "nullptr"}, {KK_HPROD, "A.out", "A.aux"}}}}},
+    // PG_SPHASE: the five evaluations of a solver that scales its NLP, over the PLAIN model.  s = A.v (ncon row factors), y = A.y:
+    //   sp_cons s[row] * c_row(x), as cons_scaled                         sp_jac s[row] * slot, as jac_scaled
+    //   sp_obj  the model's own objective bodies (the factor s_f meets the 8-byte scalar on the host)
+    //   sp_hess hess_coord! with a constraint template seeded by fl(y[row] * s[row]) — ONE rounded multiply, never folded,
+    //           s[row] loaded where scale_of_row loads it; an objective template's seed stays A.w
+    //   sp_grad grad! with the reverse sweep seeded by A.w (= s_f) instead of 1.0, through the same deterministic scatter
+    // and the two solver phases over them.  The accepted phase has TWO scalars: A.w is the Hessian's objective weight, the
+    // gradient's seed travels as the bits of a double in the head's word p4 (iem_sp_word).  No KK_ALL (iem_point_all uses
+    // p4 .. p6 itself)
+    {{"sp_cons", "sp_jac", "sp_hess", "sp_obj", "sp_grad", "", "", ""}, MV_PLAIN, NO_HESS_MERGE | NO_PAIR | MODEL_TILE, 0, false, false, true,
+     {{KK_TRIAL, "iem_sp_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
+      {KK_ACCEPTED, "iem_sp_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3", "iem_sp_word(A.p4)"}}}}},
+};
 static bool is_scatter(int kind) { return kind == KK_GRAD || kind == KK_JTPROD || kind == KK_HPROD; }
 
 // ---- launches of several bodies ------------------------------------------------------------------------------------------
@@ -2800,6 +2864,7 @@ struct Emitter {
   const std::vector<Options> &kopts;   // the options each builder was made with (kind_options)
   const Options &opt;
   Program &P;
+  ProgramId pg;
   // Kernels of more than one workgroup size in one program (the large-grid shape of jac_coord! / hess_coord!): every kernel
   // then sits in the namespace iem_t<size> that holds the tile-dependent device primitives compiled for its size, with
   // IEM_TILE redefined in front of it (csrc/iem_api.cpp: full_source).  A program of one size is emitted as it always was.
@@ -2815,6 +2880,7 @@ struct Emitter {
   void ns_end(int tile) {
     if (mixed) src << "}  // namespace iem_t" << tile << "\n#undef IEM_TILE\n#define IEM_TILE " << opt.block << "\n\n";
   }
+  const ProgramSpec &row() const { return kPrograms[pg]; }
   bool phases_on() const { return opt.phase_kernels && !opt.no_fuse && opt.fuse_groups && !opt.hess_merge; }
 };
 
@@ -2859,7 +2925,7 @@ static void emit_kinds(Emitter &E) {
     for (size_t k = 0; k < E.descs.size(); ++k) if (E.descs[k].kind == kind) ks.push_back(k);
     if (ks.empty()) continue;
     const int ktile = E.descs[ks[0]].block;   // one workgroup size per kind (kind_options)
-    const bool in_a_phase = E.phases_on() && (kind == KK_CONS || kind == KK_GRAD || kind == KK_JAC || kind == KK_HESS || (opt.param_kinds == 5 && kind == KK_JTPROD) || (opt.kkt_kinds && (kind == KK_JPROD || kind == KK_HPROD)));
+    const bool in_a_phase = E.phases_on() && E.row().in_a_phase(kind);
     const bool unfused = !opt.fuse_groups || (opt.no_fuse && opt.fuse_groups < 2);   // fuse_groups = 2: experiments (one launch of per-template bodies)
     if (kind != KK_OBJ && (unfused || (ks.size() == 1 && !in_a_phase))) {
       for (size_t k : ks) { E.ns_begin(ktile); E.src << E.builders[k]->emit(E.descs[k]); E.ns_end(ktile); E.P.kernels.push_back(E.descs[k]); }
@@ -2867,9 +2933,9 @@ static void emit_kinds(Emitter &E) {
     }
     std::stable_sort(ks.begin(), ks.end(), [&](size_t a, size_t b) { return E.descs[a].n_blocks > E.descs[b].n_blocks; });
     Launch &L = E.emitted[kind];
-    L.kind = kind; L.tile = ktile; L.dv = opt.kkt_kinds != 0;
+    L.kind = kind; L.tile = ktile; L.dv = E.row().dv;
     for (size_t k : ks) L.bodies.push_back(Body{E.builders[k].get(), &E.descs[k], "A.out", "A.aux", E.kopts[k].xcd_remap != 0});
-    if (!emit_launch(E, L, std::string("iem_") + kind_names(opt)[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
+    if (!emit_launch(E, L, std::string("iem_") + E.row().kname[kind] + "_all" + E.name_tag)) throw std::runtime_error("support grids too large for one launch");
     if (kind == KK_OBJ) E.P.n_partials = L.F.grid[0];
   }
 }
@@ -2880,33 +2946,11 @@ static void emit_kinds(Emitter &E) {
 // code at its own table base; bytes identical to the separate calls (same bodies).  Pointers: trial  out = c, aux = the
 // objective scalar, p2 = the objective's partials;  accepted  out = jac values, aux = hess values, p2 = g, p3 = grad!'s
 // reduction buffer.  Follow-ups of grad! (axis sums, plan-driven gather, runtime memsets) stay with the runtime.
-// The residual program (Options::param_kinds = 5) has ONE phase, the convergence check (iem_eval_residual): KK_TRIAL with a
-// third member, lagrad on KK_JTPROD's table slot — p3 = its output, p4 = its reduction buffer, A.v = y, A.w = σ; its
-// follow-ups stay with the runtime like grad!'s.
+// Which phases a program has, and their members, stands at its row of kPrograms.
 static void emit_phases(Emitter &E) {
   if (!E.phases_on()) return;
   std::ostringstream &src = E.src;
-  struct Member { int kind; const char *out, *aux; const char *w = nullptr; };   // w: passed to the member's bodies in place of A.w
-  struct Phase { int id; const char *name; std::vector<Member> mem; };
-  // The KKT operator (Options::kkt_kinds = 1) has ONE phase too, on the free slot KK_TRIAL: kkty (out = p2) and kktx (out, aux =
-  // its reduction buffer), u = A.v, the dual direction = p6; kktx's follow-ups stay with the runtime.
-  const std::vector<Phase> phases = E.opt.kkt_kinds ? std::vector<Phase>{
-    {KK_TRIAL, "iem_kktprod_all", {{KK_JPROD, "A.p2", "nullptr"}, {KK_HPROD, "A.out", "A.aux"}}},
-  } : E.opt.scaled_phase_kinds ? std::vector<Phase>{
-    // the scaled solver phases (Options::scaled_phase_kinds = 1): the two phases below with this program's members; A.w is
-    // the Hessian's objective weight, sp_grad's seed s_f the double whose bits the head's word p4 holds.  No KK_ALL.
-    {KK_TRIAL, "iem_sp_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
-    {KK_ACCEPTED, "iem_sp_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3", "iem_sp_word(A.p4)"}}},
-  } : E.opt.param_kinds == 5 ? std::vector<Phase>{
-    {KK_TRIAL, "iem_residual_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}, {KK_JTPROD, "A.p3", "A.p4"}}},
-  } : std::vector<Phase>{
-    {KK_TRIAL, "iem_trial_all", {{KK_CONS, "A.out", "nullptr"}, {KK_OBJ, "A.p2", "A.aux"}}},
-    {KK_ACCEPTED, "iem_accepted_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}}},
-    // all five evaluations of one point in ONE launch (iem_eval_all: the solver's first trial point is usually accepted —
-    // obj, cons!, grad!, jac_coord!, hess_coord! at the same x): p4 = c, p5 = the objective's partials, p6 = its scalar
-    {KK_ALL, "iem_point_all", {{KK_JAC, "A.out", "nullptr"}, {KK_HESS, "A.aux", "nullptr"}, {KK_CONS, "A.p4", "nullptr"}, {KK_GRAD, "A.p2", "A.p3"}, {KK_OBJ, "A.p5", "A.p6"}}},
-  };
-  for (const Phase &ph : phases) {
+  for (const Phase &ph : E.row().phases) {
     bool ok = true;
     int tile = 0;
     std::vector<Member> present;   // (a linear program has no hess_coord! kernel: the accepted point is grad! + jac_coord!)
@@ -3008,7 +3052,7 @@ static void emit_pair(Emitter &E, const Model &m, const std::map<size_t, std::pa
     kd.name = (rejoin ? whole->second.second : d.name) + "_p"; kd.kind = d.kind; kd.block = d.block; kd.lds_slots = d.lds_slots; kd.inter = rejoin ? -1 : d.inter;
     for (int a = 0; a < 3; ++a) kd.grid[a] = d.grid[a];
     kd.n_blocks = d.n_blocks;
-    auto kb = std::make_unique<KernelBuilder>(m, rejoin ? *whole->second.first : E.builders[k]->group(), kd.kind, E.kopts[k], kd.name);
+    auto kb = std::make_unique<KernelBuilder>(m, rejoin ? *whole->second.first : E.builders[k]->group(), kd.kind, E.pg, E.kopts[k], kd.name);
     if (!kb->build(nullptr)) throw std::runtime_error("internal: pair body without outputs");
     if (kd.kind == KK_HESS && opt.hess_merge) kb->merge_hess(nnz_again, classes_again);
     L.bodies.push_back(Body{kb.get(), &kd, kd.kind == KK_JAC ? "A.out" : "A.aux", "nullptr", E.kopts[k].xcd_remap != 0});
@@ -3018,69 +3062,56 @@ static void emit_pair(Emitter &E, const Model &m, const std::map<size_t, std::pa
   emit_launch(E, L, std::string("iem_pair_all") + E.name_tag);   // (too large for one launch: the two calls stay separate launches)
 }
 
-static Program generate_kinds(const Model &m, const Options &opt_in);
+ProgramId program_of(const Options &o) {
+  auto two = [](const char *a, const char *b) { return std::runtime_error(std::string(a) + " and " + b + " name different programs: set one of them"); };
+  if (o.scaled_phase_kinds) {
+    if (o.param_kinds) throw two("scaled_phase_kinds", "param_kinds");
+    if (o.scaled_kinds) throw two("scaled_phase_kinds", "scaled_kinds");
+    if (o.kkt_kinds) throw two("scaled_phase_kinds", "kkt_kinds");
+    return PG_SPHASE;
+  }
+  if (o.scaled_kinds) {
+    if (o.param_kinds) throw two("scaled_kinds", "param_kinds");
+    if (o.kkt_kinds) throw two("scaled_kinds", "kkt_kinds");
+    return PG_SCALED;
+  }
+  if (o.kkt_kinds) {
+    if (o.param_kinds) throw two("kkt_kinds", "param_kinds");
+    return PG_KKT;
+  }
+  return o.param_kinds >= 2 && o.param_kinds <= 5 ? ProgramId(PG_THETA + o.param_kinds - 1) : o.param_kinds ? PG_THETA : PG_MODEL;   // (as iem_set_option reads the value)
+}
+
+void select_program(Options &o, ProgramId pg) {
+  o.param_kinds = pg >= PG_THETA && pg <= PG_LAGRAD ? pg - PG_THETA + 1 : 0;
+  o.scaled_kinds = pg == PG_SCALED;
+  o.kkt_kinds = pg == PG_KKT;
+  o.scaled_phase_kinds = pg == PG_SPHASE;
+}
+
+static Program generate_kinds(const Model &m, const Options &opt_in, ProgramId pg);
 
 Program generate(const Model &m, const Options &opt_in) {
   validate_indices(m);
-  if (opt_in.scaled_phase_kinds) {
-    // the scaled solver phases: the model's five kinds with the row factors inside and the gradient seeded with A.w, over the
-    // PLAIN model; the model's tile on every grid (as the scaled program), no pair, its phase kernels are TRIAL and ACCEPTED
-    if (opt_in.param_kinds) throw std::runtime_error("scaled_phase_kinds and param_kinds name different programs: set one of them");
-    if (opt_in.scaled_kinds) throw std::runtime_error("scaled_phase_kinds and scaled_kinds name different programs: set one of them");
-    if (opt_in.kkt_kinds) throw std::runtime_error("scaled_phase_kinds and kkt_kinds name different programs: set one of them");
-    Options o = opt_in;
-    o.hess_merge = 0; o.pair_kernel = 0;
-    o.big_batch_jac = o.big_batch_hess = 0;
-    return generate_kinds(m, o);
-  }
-  if (opt_in.scaled_kinds) {
-    // the scaled program: rowmax, cons_scaled and jac_scaled over the PLAIN model, through the store path of the model's own
-    // kinds; the model's tile on every grid (as the explicit θ blocks), no pair, no phase kernel
-    if (opt_in.param_kinds) throw std::runtime_error("scaled_kinds and param_kinds name different programs: set one of them");
-    if (opt_in.kkt_kinds) throw std::runtime_error("scaled_kinds and kkt_kinds name different programs: set one of them");
-    Options o = opt_in;
-    o.hess_merge = 0; o.phase_kernels = 0; o.pair_kernel = 0;
-    o.big_batch_jac = o.big_batch_hess = 0;
-    return generate_kinds(m, o);
-  }
-  if (opt_in.kkt_kinds) {
-    // the KKT operator: kktx and kkty over the PLAIN model, the model's tile on every grid (no large-grid shape), no pair; its
-    // one phase kernel is the whole operator in one launch
-    if (opt_in.param_kinds) throw std::runtime_error("kkt_kinds and param_kinds name different programs: set one of them");
-    Options o = opt_in;
-    o.hess_merge = 0; o.pair_kernel = 0;
-    o.big_batch_jac = o.big_batch_hess = 0;
-    return generate_kinds(m, o);
-  }
-  if (!opt_in.param_kinds) return generate_kinds(m, opt_in);
-  // the residual program: lagrad next to the model's own cons and obj, over the PLAIN model — no slot of θ is differentiated
-  if (opt_in.param_kinds == 5) return generate_kinds(m, opt_in);
-  // the kinds d/dθ: the same machinery over the parameter view of the model (θ nodes are variables of the extended
-  // vector [x; θ]); the builders keep the slots the kind asks for and drop the rest before anything is emitted
+  const ProgramId pg = program_of(opt_in);
+  const ProgramSpec &row = kPrograms[pg];
+  Options o = opt_in;
+  if (row.overrides & NO_HESS_MERGE) o.hess_merge = 0;
+  if (row.overrides & NO_PAIR) o.pair_kernel = 0;
+  if (row.overrides & NO_PHASES) o.phase_kernels = 0;
+  if (row.overrides & MODEL_TILE) o.big_batch_jac = o.big_batch_hess = 0;
+  if (row.overrides & ONE_BODY_PER_GRID) o.fold_colloc = o.jac_split = 0;
+  if (row.view == MV_PLAIN) return generate_kinds(m, o, pg);
   Model view = parameter_view(m);
-  if (opt_in.param_kinds == 4) {
-    // the explicit blocks dc/dθ, d2L/dx dθ, d2L/dθ2 in COO: row-owned stores through the staged store path of jac_coord! /
-    // hess_coord!, one lane per item.  Item-owned stores need none of the scatter machinery (no folded collocation boxes),
-    // and the blocks are small next to the model's own COO outputs: one body per grid and kind, the model's tile.
-    param_coord_layout(view);
-    Options o = opt_in;
-    o.fold_colloc = 0; o.jac_split = 0; o.hess_merge = 0; o.phase_kernels = 0; o.pair_kernel = 0;
-    o.big_batch_jac = o.big_batch_hess = 0;
-    return generate_kinds(view, o);
-  }
-  return generate_kinds(view, opt_in);
+  if (row.view == MV_THETA_COO) param_coord_layout(view);
+  return generate_kinds(view, o, pg);
 }
 
-static Program generate_kinds(const Model &m, const Options &opt_in) {
+static Program generate_kinds(const Model &m, const Options &opt_in, ProgramId pg) {
   Options opt = opt_in;
-  const bool kkt = opt.kkt_kinds != 0;                                     // kkt: the KKT operator — kktx and kkty of the plain model
-  const bool sph = opt.scaled_phase_kinds != 0;                            // sph: the scaled solver phases — the model's five kinds, scaled, and their two phases
-  const bool scl = opt.scaled_kinds != 0;                                  // scl: the scaled program — cons_scaled, jac_scaled and rowmax of the plain model
-  const bool lag = opt.param_kinds == 5;                                   // lag: the residual program — cons, obj and lagrad of the plain model
-  const bool theta = opt.param_kinds != 0 && !lag, coord = opt.param_kinds == 4;   // coord: no scatter kind at all
-  const bool theta_hi = theta && opt.param_kinds >= 2;                     // the θ programs that hold ONE kind of their own
-  // length of a scatter kind's output vector: nvar, except the parameter kinds jptprod, hptprod and hppprod (an entry per θ)
-  auto nout = [&](int kind) { return (theta && kind == KK_JTPROD) || (theta_hi && kind == KK_HPROD) ? m.npar : m.nvar; };
+  const ProgramSpec &row = kPrograms[pg];
+  // length of a scatter kind's output vector
+  auto nout = [&](int kind) { return row.npar_out >> kind & 1 ? m.npar : m.nvar; };
   if (opt.block == 0) opt.block = choose_block(m, opt);
   Program P;
   P.block = opt.block;
@@ -3115,7 +3146,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
   }
   std::ostringstream src;
   src << "// generated by libiem_hip (iem_codegen.cpp) — do not edit\n";
-  if (sph)   // device code of this program alone (the device header is part of every model's source and stays as it is)
+  if (row.sp_word)   // device code of this program alone (the device header is part of every model's source and stays as it is)
     src << "// the second scalar of the scaled accepted phase: sp_grad's seed, carried as the bits of a double in a pointer word of the head\n"
         << "__device__ __forceinline__ double iem_sp_word(const double* p) { double d; __builtin_memcpy(&d, &p, 8); return d; }\n";
 
@@ -3140,15 +3171,10 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       throw std::runtime_error("support grid too large in dims 2/3 (limit 65535 per dimension for 3-D grids)");
     for (int kind = 0; kind < KK_COUNT; ++kind) {
       if (split && is_scatter(kind) != (pass == 1)) continue;   // pass 1: the scatter kinds on the fused groups
-      if (coord ? kind != KK_JAC && kind != KK_HESS : theta && kind != KK_JPROD && kind != KK_JTPROD && kind != KK_HPROD) continue;
-      if (!coord && theta_hi && kind != KK_HPROD) continue;
-      if (lag && kind != KK_CONS && kind != KK_OBJ && kind != KK_JTPROD) continue;
-      if (scl && kind != KK_CONS && kind != KK_JAC && kind != KK_JPROD) continue;
-      if (kkt && kind != KK_JPROD && kind != KK_HPROD) continue;
-      if (sph && kind >= KK_JPROD) continue;
-      std::string name = std::string("iem_") + kind_names(opt)[kind] + "_g" + std::to_string(gi) + name_tag;
+      if (!row.has(kind)) continue;
+      std::string name = std::string("iem_") + row.kname[kind] + "_g" + std::to_string(gi) + name_tag;
       const Options ko = kind_options(opt, pass ? groups_fused : groups, kind);
-      auto kb = std::make_unique<KernelBuilder>(m, g, kind, ko, name);
+      auto kb = std::make_unique<KernelBuilder>(m, g, kind, pg, ko, name);
       if (!kb->build(nullptr)) continue;
       if (kind == KK_JAC && opt.jac_split > 0 && !opt.no_fuse && ko.store_mode == 2 && g.grid_id > 0) {
         // a large grid: the templates whose partials are item data get a body of their own (Options::jac_split)
@@ -3163,7 +3189,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
             for (int ti : g.tpls) if ((data.count(ti) != 0) == (half == 0)) sg.tpls.push_back(ti);
             for (int ti : g.scalars) if ((data.count(ti) != 0 || !kb->relevant(m.tpl[ti])) == (half == 0)) sg.scalars.push_back(ti);
             const std::string hname = name + (half ? "b" : "a");
-            auto hb = std::make_unique<KernelBuilder>(m, sg, kind, ko, hname);
+            auto hb = std::make_unique<KernelBuilder>(m, sg, kind, pg, ko, hname);
             if (!hb->build(nullptr)) throw std::runtime_error("internal: empty half of a split jac_coord! body");
             KernelDesc hd;
             hd.name = hname; hd.kind = kind; hd.block = ko.block; hd.lds_slots = ko.lds_slots; hd.inter = (int)gi;
@@ -3374,9 +3400,9 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
           }
       return o.scalar ? (int64_t)1 : g.ext[0] * g.ext[1] * g.ext[2];
     };
-    // (not the adjoint parameter kind, nor the θθ kind: its output must be written without any float atomic — and the atomics would need a
-    //  memset launch in front of the kernel where the gather needs its launch behind it)
-    if (park_atomics && opt.det_scatter < 2 && opt.param_kinds < 2 && !kkt && !sph) {
+    // (not where the output must be written without any float atomic — the atomics would also need a memset launch in front of
+    //  the kernel where the gather needs its launch behind it)
+    if (park_atomics && opt.det_scatter < 2 && row.two_addend) {
       // at most TWO addends per entry: a + b = b + a, those atomics are already order-independent — and cheaper than
       // a second launch
       std::vector<int64_t> d0;
@@ -3444,12 +3470,7 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
       if (c.first > pos) holes.emplace_back(pos, c.first);
       pos = std::max(pos, c.second + 1);
     }
-    if (theta && kind == KK_GRAD) continue;
-    if (coord || (theta_hi && kind != KK_HPROD)) continue;
-    if (lag && kind != KK_JTPROD) continue;
-    if (scl) continue;
-    if (kkt && kind != KK_HPROD) continue;
-    if (sph && kind != KK_GRAD) continue;
+    if (!row.has(kind)) continue;
     if (pos < nout(kind)) holes.emplace_back(pos, nout(kind));
     int best = -1;
     for (size_t k = 0; k < descs.size(); ++k)
@@ -3519,14 +3540,12 @@ static Program generate_kinds(const Model &m, const Options &opt_in) {
     P.aux_doubles[kind] = base;
   }
   // the launches: one per NLPModels call, one per solver phase, and jac_coord! + hess_coord! in one
-  Emitter E{src, descs, builders, kopts, opt, P};
+  Emitter E{src, descs, builders, kopts, opt, P, pg};
   for (const KernelDesc &d : descs) E.mixed = E.mixed || d.block != opt.block;
   E.name_tag = name_tag;
   emit_kinds(E);
-  if (!theta) {
-    emit_phases(E);
-    if (!lag && !scl && !kkt && !sph) emit_pair(E, m, whole_of, second_half);
-  }
+  emit_phases(E);
+  emit_pair(E, m, whole_of, second_half);   // (a program with both jac and hess kernels that does not clear pair_kernel: the model's own)
   P.source = src.str();
   P.key = fnv1a64(P.source);
   return P;

@@ -127,62 +127,14 @@ struct Options {
   int digit_fields = 1;    // fields the parse-time digit pass recognised (iem_model.hpp: recover_digits, folded runs only) are decoded
                            // from the item coordinate in registers; 0: they stay gathers from their short columns
   int cons_direct_2d = 1;  // cons! of a model whose largest grid is 2-D: plain coalesced stores instead of the LDS re-cut (kind_options)
-  // 1: generate() emits the PARAMETER kinds instead — a program of its own, the model's usual program is untouched:
-  // jpprod (dc/dθ) w, jptprod σ df/dθ + (dc/dθ)' y, hpprod (d2L/dx dθ) w.  They take the table slots, pointers and follow-ups
-  // of the kinds they are shaped like (KK_JPROD / KK_JTPROD / KK_HPROD; jptprod's output has npar entries, A.w = σ), differentiate
-  // over the extended vector [x; θ] (iem_model.hpp: parameter_view) and go through the same deterministic scatter machinery.
-  // 2: the ADJOINT parameter program, again one of its own (the source of 1 does not move): hptprod (d2L/dθ dx) u alone, the
-  // transpose of hpprod — the same second-order sweep with the tangent u on the slots of x and the θ slots of the mixed entries
-  // kept; it takes KK_HPROD's table slot with an output of npar entries, scattered like jptprod's.
-  // 3: the θθ program, one more of its own (the sources of 1 and 2 do not move): hppprod (d2L/dθ2) w alone — the second-order
-  // slots with BOTH entries in θ, hprod's arithmetic on them (the symmetric addend behind the same select), tangent and
-  // output over θ; KK_HPROD's table slot again, npar entries out, scattered like hptprod's (no float atomic).
-  // 4: the explicit blocks in COO, a fifth program (the sources of 0 - 3 do not move): jacp — dc/dθ, the θ slots of the
-  // constraint templates' first-order slots — on KK_JAC's table slot, and hessp — d2L/dx dθ (out) and d2L/dθ2 (aux), the
-  // second-order slots with one / with two entries in θ, from ONE sweep — on KK_HESS's.  One lane per item, every slot
-  // stored once through the staged COO store path, layout by param_coord_layout (iem_model.hpp); no scatter kind, no atomic.
-  // 5: the residual program, a sixth one (the sources of 0 - 4 do not move), over the PLAIN model: lagrad — σ ∇f + J' y, the
-  // gradient of  σ f + y . c: objective templates seeded with σ (A.w), constraint templates with y[row] (A.v), every first-order
-  // slot kept, ONE deterministic scatter over both — on KK_JTPROD's table slot (nvar entries out), next to the model's own
-  // cons and obj (same builders, same bodies), and KK_TRIAL with lagrad as third member (p3 = its output, p4 = its reduction
-  // buffer): c, f and the dual residual of a convergence check in one launch (iem_eval_residual).
-  int param_kinds = 0;
-  // 1: generate() emits the SCALED program instead — a seventh one over the PLAIN model (param_kinds must be 0; with 0 here
-  // the sources, keys and launch plans of every other program are what they were): the row scaling of a solver
-  // (Ipopt's gradient-based scaling, MadNLP's scale_constraints!) inside the kernels.  s = A.v (ncon factors):
-  //   rowmax      on KK_JPROD's table slot (ncon out, no tangent loaded): max over the first-order slots of the row of |slot|,
-  //               NaN-propagating, 0.0 for a row without a slot — a per-lane reduction, one exclusive store per row
-  //   cons_scaled on KK_CONS's: s[row] * c_row(x), ONE rounded multiply of the value cons! computes
-  //   jac_scaled  on KK_JAC's: s[row] * slot, ONE rounded multiply of every finished slot value (the reverse sweep is NOT
-  //               seeded with s: the linear rows' partials are item data), at the positions of jac_structure
-  // Same groups, folds, halves (jac_split) and store path as the model's own kinds; like the explicit θ blocks the program
-  // keeps the model's tile on every grid (no large-grid shape), and it has no pair and no phase kernel.  No atomics.
-  int scaled_kinds = 0;
-  // 1: generate() emits the KKT OPERATOR instead — an eighth program over the PLAIN model (param_kinds and scaled_kinds must be
-  // 0; with 0 here the sources, keys and launch plans of every other program are what they were).  u = A.v (nvar), the dual
-  // direction dv = the head's p6 (ncon, read at row indices like y), σ = A.w:
-  //   kktx on KK_HPROD's table slot (nvar out): W u + J' dv, W = σ ∇²f + Σ y_r ∇²c_r — hprod's contributions of every template
-  //        with a second-order slot, and for every constraint template with a first-order slot the first-order sweep seeded
-  //        with dv[row], both through ONE contribute map and ONE deterministic scatter (no float atomic, the two-addend
-  //        shortcut off); an entry no template touches comes out as 0
-  //   kkty on KK_JPROD's (ncon out): J u, the model's own jprod builder and kind options
-  // and KK_TRIAL, free in this program, holds both behind one dispatcher (iem_kktprod_all: kkty's out = p2, kktx's out / aux as
-  // in its own launch); kktx's follow-ups stay with the runtime.  The model's tile on every grid, no pair.
-  int kkt_kinds = 0;
-  // 1: generate() emits the SCALED SOLVER PHASES instead — a ninth program over the PLAIN model (param_kinds, scaled_kinds and
-  // kkt_kinds must be 0; with 0 here the sources, keys and launch plans of every other program are what they were): the five
-  // evaluations of a solver that scales its NLP, on the model's own table slots.  s = A.v (ncon row factors), y = A.y:
-  //   sp_cons on KK_CONS's: s[row] * c_row(x), as cons_scaled           sp_jac on KK_JAC's: s[row] * slot, as jac_scaled
-  //   sp_obj  on KK_OBJ's:  the model's own objective bodies (the factor s_f meets the 8-byte scalar on the host)
-  //   sp_hess on KK_HESS's: hess_coord! with a constraint template seeded by fl(y[row] * s[row]) — ONE rounded multiply, never
-  //           folded, s[row] loaded where scale_of_row loads it; an objective template's seed stays A.w
-  //   sp_grad on KK_GRAD's: grad! with the reverse sweep seeded by A.w (= s_f) instead of 1.0, through the same deterministic
-  //           scatter (no float atomic, the two-addend shortcut off)
-  // and the two solver phases over them: KK_TRIAL {sp_cons -> out, sp_obj -> p2 / aux}, KK_ACCEPTED {sp_jac -> out, sp_hess ->
-  // aux, sp_grad -> p2 / p3}.  The accepted phase has TWO scalars: A.w is the Hessian's objective weight, the gradient's seed
-  // travels as the bits of a double in the head's word p4 (iem_sp_word, emitted with this program's source only).  The
-  // model's tile on every grid, no pair, no KK_ALL (iem_point_all uses p4 .. p6 itself).
-  int scaled_phase_kinds = 0;
+  // WHICH PROGRAM generate() emits: the model's own (all four 0) or one of the eight derived ones, each a program of its own
+  // that leaves the sources, keys and launch plans of the others alone.  The four fields are the public spelling (iem_set_option);
+  // program_of() resolves them to a ProgramId — two programs at once are refused, not guessed — and nothing else reads them.
+  // What each program is stands at its row of kPrograms (iem_codegen.cpp).
+  int param_kinds = 0;          // 1 .. 5: selects PG_THETA, PG_ADJOINT, PG_THETA2, PG_COORD, PG_LAGRAD, see kPrograms
+  int scaled_kinds = 0;         // 1: selects PG_SCALED, see kPrograms
+  int kkt_kinds = 0;            // 1: selects PG_KKT, see kPrograms
+  int scaled_phase_kinds = 0;   // 1: selects PG_SPHASE, see kPrograms
   // runtime only (the generator ignores them)
   int comm_timeout_ms = 5000;   // bound of every mailbox wait (halo exchange / fold / all-reduce kernels)
 };
@@ -223,6 +175,11 @@ struct Program {
   Gather gather[KK_COUNT];
   int64_t aux_doubles[KK_COUNT] = {};   // whole aux buffer of the kind: shared-entry part (values*wgs + ticket words), then the axis rows
 };
+
+// The nine programs the generator emits per model, in the order they were added; one row each in kPrograms (iem_codegen.cpp).
+enum ProgramId { PG_MODEL, PG_THETA, PG_ADJOINT, PG_THETA2, PG_COORD, PG_LAGRAD, PG_SCALED, PG_KKT, PG_SPHASE, PG_COUNT };
+ProgramId program_of(const Options &opt);          // the program the four fields name; throws when they name two
+void select_program(Options &opt, ProgramId pg);   // the four fields set for `pg`
 
 Program generate(const Model &m, const Options &opt);
 uint64_t fnv1a64(const std::string &s);

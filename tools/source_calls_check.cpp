@@ -1,5 +1,7 @@
 // source_calls_check.cpp — sanitizer harness for the source entry points (host only, no device): iem_fixed_source over the
-// indices -1 .. 4, the five named *_source calls and iem_emit_source on one blob, everything they return freed.  Build with
+// indices -1 .. 4, the five named *_source calls and iem_emit_source on one blob — for each of the generator's nine programs,
+// selected through iem_set_option and reset afterwards, and for the six pairs of two program options at once, each refused with
+// its message — everything they return freed.  Build with
 //   g++ -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
 //       -Iinclude tools/source_calls_check.cpp infiniteexamodels.jl_amd/csrc/iem_api.cpp \
 //       infiniteexamodels.jl_amd/csrc/iem_codegen.cpp -L/opt/rocm/lib -lamdhip64 -lhiprtc -ldl -Wl,-rpath,/opt/rocm/lib -o /tmp/source_calls_check
@@ -61,10 +63,35 @@ int main(int argc, char **argv) {
   if (argc > 1) {
     std::ifstream f(argv[1], std::ios::binary);
     std::vector<char> b((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-    char *src = nullptr;
-    uint64_t key = 0;
-    const int rc = iem_emit_source(b.data(), b.size(), &src, &key);
-    report("iem_emit_source(blob)", rc, src, key);
+    struct Opt { const char *name; int value; };
+    const Opt programs[9] = {{"param_kinds", 0}, {"param_kinds", 1}, {"param_kinds", 2}, {"param_kinds", 3}, {"param_kinds", 4}, {"param_kinds", 5},
+                             {"scaled_kinds", 1}, {"kkt_kinds", 1}, {"scaled_phase_kinds", 1}};
+    std::vector<uint64_t> keys;
+    for (const Opt &pg : programs) {
+      char *src = nullptr;
+      uint64_t key = 0;
+      if (iem_set_option(pg.name, pg.value) != IEM_OK) ++bad;
+      const int rc = iem_emit_source(b.data(), b.size(), &src, &key);
+      if (iem_set_option(pg.name, 0) != IEM_OK) ++bad;
+      for (uint64_t k : keys) if (k == key) { std::printf("%s=%d: the key of another program\n", pg.name, pg.value); ++bad; }
+      keys.push_back(key);
+      report((std::string("iem_emit_source ") + pg.name + "=" + std::to_string(pg.value)).c_str(), rc, src, key);
+    }
+    // two program options at once: refused with the message that names both, in the generator's order of precedence
+    const char *pairs[6][2] = {{"scaled_phase_kinds", "param_kinds"}, {"scaled_phase_kinds", "scaled_kinds"}, {"scaled_phase_kinds", "kkt_kinds"},
+                               {"scaled_kinds", "param_kinds"}, {"scaled_kinds", "kkt_kinds"}, {"kkt_kinds", "param_kinds"}};
+    for (const auto &pr : pairs) {
+      char *src = nullptr;
+      uint64_t key = 0;
+      if (iem_set_option(pr[0], 1) != IEM_OK || iem_set_option(pr[1], 1) != IEM_OK) ++bad;
+      const int rc = iem_emit_source(b.data(), b.size(), &src, &key);
+      const std::string want = std::string(pr[0]) + " and " + pr[1] + " name different programs: set one of them", got = iem_last_error();
+      if (iem_set_option(pr[0], 0) != IEM_OK || iem_set_option(pr[1], 0) != IEM_OK) ++bad;
+      const bool ok = rc != IEM_OK && !src && got == want;
+      std::printf("%-18s + %-12s rc %d  %s\n", pr[0], pr[1], rc, ok ? "refused with its message" : ("BAD: " + got).c_str());
+      if (!ok) ++bad;
+      if (src) iem_free(src);
+    }
   } else {
     std::printf("no blob given: iem_emit_source not called\n");
     ++bad;
