@@ -578,7 +578,8 @@ int iem_kkt_border_source(char **out_src, uint64_t *out_key);
  *                                     doubtful} pivots of K (a correctly regularised system has ncon negative ones); synchronises
  *   iem_kkt_solve(k, d_rhs, d_sol)    K sol = rhs (nvar + ncon doubles each; one pass through the factors — the residual
  *                                     rhs − K sol and iterative refinement: iem_kkt_residual / iem_kkt_solve_refined below)
- * d_rhs and d_sol may be the same array.  The object borrows the model handle (its stream, device and kernel cache): destroy
+ * d_rhs and d_sol may be the same array; a PARTIAL overlap of the two is IEM_E_ARG (iem_kkt_solve is iem_kkt_solve_many with one
+ * column and takes its rule — such a call used to be undefined, it is refused now).  The object borrows the model handle (its stream, device and kernel cache): destroy
  * it before iem_destroy(m).  Models whose blocks / border / coupling exceed the solver's limits (96 / 64 / 48) are refused by
  * iem_kkt_create. */
 typedef struct iem_kkt iem_kkt;
@@ -621,9 +622,12 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol);
  * residuals, predictor + corrector): column u is d_rhs + u ld_rhs / d_sol + u ld_sol, nvar + ncon doubles; ld >= nvar + ncon, the
  * entries between are neither read nor written.  d_sol == d_rhs with ld_sol == ld_rhs solves in place; any other overlap is
  * IEM_E_ARG — judged on the whole extents [d, d + (nrhs - 1) ld + n), so columns of d_sol interleaved with those of d_rhs
- * (disjoint, but inside each other's extent) are refused as well.  Any nrhs: the columns are processed in chunks (see iem_kkt_chain_solve_many) through a workspace of ONE chunk that
- * the first call allocates and iem_kkt_destroy frees — memory does not grow with nrhs.  Column u carries the bits
- * iem_kkt_solve gives for it.  In mode 0 the border system is solved on the host once per column, with one read-back and one upload per
+ * (disjoint, but inside each other's extent) are refused as well.  Any nrhs: the columns are processed in chunks (see iem_kkt_chain_solve_many) through the object's workspace of ONE chunk —
+ * one column wide from iem_kkt_create on (a one-column solve allocates nothing), grown once to the chunk width by the first call with
+ * nrhs > 1, freed by iem_kkt_destroy: memory does not grow with nrhs.  THE GROWTH FREES the one-column buffers: a graph captured
+ * from iem_kkt_solve / iem_kkt_solve_refined before it points at freed memory afterwards — an application that uses both kinds of
+ * call makes one multi-column call before it captures, or captures again after the first one.  iem_kkt_solve is this call with one column: column u carries
+ * the bits iem_kkt_solve gives for it.  In mode 0 the border system is solved on the host once per column, with one read-back and one upload per
  * chunk; in mode 1 (iem_kkt_set_border) on the device, one launch per chunk.  Hub mode (info.hubs != 0) is accepted as a loop of single solves: the hubs' side stays matrix-vector work per column
  * (sharing its factors across columns — GEMM for GEMV — is not done). */
 int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol);
@@ -648,8 +652,6 @@ int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double ob
  * the object (a dense border is solved on the host in mode 0 only: iem_kkt_set_border).  d_sol may not overlap d_rhs.  Workspace: 3 (nvar + ncon) doubles, as above. */
 int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w,
                           double delta_c, const double *d_rhs, double *d_sol, int steps, double *d_norms /* steps + 1 or NULL */);
-/* HIP source of the two finishing kernels and its cache key — for offline builds (no device needed; malloc'ed) */
-int iem_kkt_residual_source(char **out_src, uint64_t *out_key);
 
 /* A PER-ROW diagonal in the constraint block — what an interior-point method with eliminated slacks assembles (Sigma_s^-1 on its
  * inequality rows, another value per row at every iterate) — and the residual / refinement over several columns:
@@ -673,8 +675,12 @@ int iem_kkt_residual_source(char **out_src, uint64_t *out_key);
  * the one behind the last step (with d_norms == NULL that last residual is not formed).  steps >= 0.  No read-back of a norm and
  * no early exit: as asynchronous and capturable as iem_kkt_solve_many is for the object's mode, after a first call.  d_sol may
  * not overlap d_rhs (nor d_norms either).  With nrhs = 1 and d_dcon == NULL: the bits of iem_kkt_solve_refined.
- * Workspace: 3 (nvar + ncon) doubles per column of ONE slab (8 columns — a multiple of every chunk width of iem_kkt_solve_many),
- * owned by the object: allocated by the first call, freed by iem_kkt_destroy; it does not grow with nrhs. */
+ * iem_kkt_assemble, iem_kkt_residual and iem_kkt_solve_refined ARE these calls with nrhs = 1, ld = nvar + ncon and d_dcon == NULL.
+ * Workspace: 3 (nvar + ncon) doubles per column, owned by the object and shared by the residual and refined calls: one column from
+ * the first such call on, ONE slab (8 columns — a multiple of every chunk width of iem_kkt_solve_many) from the first call with
+ * nrhs > 1 on (the growth waits for the stream once and frees the one-column planes: a graph captured from iem_kkt_residual /
+ * iem_kkt_solve_refined before it has to be captured again, as for iem_kkt_solve_many); freed by iem_kkt_destroy; it does not grow
+ * with nrhs. */
 int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma /* nvar | NULL */,
                           const double *d_dcon /* ncon | NULL */, double delta_w, double delta_c);
 int iem_kkt_residual_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma,
@@ -780,9 +786,9 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache
  * miss).  These two calls expose the generator so a build step can pre-compile. */
 int iem_emit_source(const void *blob, size_t nbytes, char **out_src, uint64_t *out_key);
-/* The hand-written code objects whose source depends on no model and no shape, as a list — what iem_kkt_residual_source,
- * iem_kkt_diag_source, iem_kkt_border_source and iem_barrier_source return one by one: index 0, 1, .. gives the object's name
- * (*out_name: a static string, not to be freed — "kkt_residual", "kkt_diag", "kkt_border", "barrier"), its HIP source (malloc'ed)
+/* The hand-written code objects whose source depends on no model and no shape, as a list — what iem_kkt_diag_source,
+ * iem_kkt_border_source and iem_barrier_source return one by one: index 0, 1, .. gives the object's name
+ * (*out_name: a static string, not to be freed — "kkt_diag", "kkt_border", "barrier"), its HIP source (malloc'ed)
  * and its cache key.  IEM_E_ARG for an index below 0 or past the last object, with nothing written: an offline build loops until
  * then and needs no edit when the library gains an object.  Any output pointer may be NULL. */
 int iem_fixed_source(int index, const char **out_name, char **out_src, uint64_t *out_key);

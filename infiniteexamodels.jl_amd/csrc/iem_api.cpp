@@ -43,10 +43,7 @@ static const char *kKktSource =
 static const char *kKktManySource =   // the multi-column solve kernels, behind the single-column ones in every chain KKT code object
 #include "iem_kkt_many_device_h.inc"
     ;
-static const char *kKktResidualSource =   // the finishing kernels of iem_kkt_residual / iem_kkt_solve_refined: a code object of their own
-#include "iem_kkt_residual_device_h.inc"
-    ;
-static const char *kKktDiagSource =       // the per-row diagonal's gather and the multi-column residual / add (iem_kkt_*_diag): a code object of its own
+static const char *kKktDiagSource =       // the KKT object's gather, residual and add over one or several columns: a code object of its own
 #include "iem_kkt_diag_device_h.inc"
     ;
 static const char *kKktBorderSource =     // the dense border on the device (kkt_border_ldl / kkt_border_solve): a code object of its own
@@ -130,15 +127,13 @@ std::string full_source(const iem::Program &p, const iem::Options &o) {
 // lists it under, the embedded text, whether the text sits behind the device header's helpers (everything in front of the
 // header's own kernels), and its kernels in slot order (the enum beside the row names the slots).  A handle loads one at the
 // first call that needs it (fixed_object); build() compiles every row offline.
-enum Fixed { F_KRES, F_KDIAG, F_KBORDER, F_BARRIER, F_COUNT };
+enum Fixed { F_KDIAG, F_KBORDER, F_BARRIER, F_COUNT };
 constexpr int kFixedSlots = 6;
-enum { KRES_RESIDUAL, KRES_AXPY };
 enum { KDIAG_GATHER, KDIAG_RESIDUAL, KDIAG_AXPY };
 enum { KBORDER_LDL, KBORDER_SOLVE, KBORDER_COLSUM, KBORDER_INERTIA };
 enum { BAR_START, BAR_TERMS, BAR_STEP, BAR_UPDATE, BAR_ERROR, BAR_MERIT };
 const struct FixedRow { const char *name, *text; bool behind_helpers; const char *kernels[kFixedSlots]; } kFixed[F_COUNT] = {
-    {"kkt_residual", kKktResidualSource, false, {"kkt_residual", "kkt_axpy1"}},      // iem_kkt_residual / iem_kkt_solve_refined
-    {"kkt_diag", kKktDiagSource, false, {"kkt_gather_d", "kkt_residual_dm", "kkt_axpy_m"}},      // iem_kkt_*_diag
+    {"kkt_diag", kKktDiagSource, false, {"kkt_gather_d", "kkt_residual_dm", "kkt_axpy_m"}},      // iem_kkt_assemble* / iem_kkt_residual* / iem_kkt_solve_refined*
     {"kkt_border", kKktBorderSource, false, {"kkt_border_ldl", "kkt_border_solve", "kkt_border_colsum", "kkt_border_inertia"}},      // iem_kkt_border_* / iem_kkt_set_border
     {"barrier", kBarrierSource, true, {"barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"}},      // iem_barrier_*
 };
@@ -296,7 +291,7 @@ struct iem_model {
   bool reads_halo_x[iem::KK_LAST + 1] = {}, reads_halo_v[iem::KK_LAST + 1] = {}, carrier[iem::KK_LAST + 1] = {};
   uint64_t nonce = 0;
   // chain KKT solver (iem_kkt_chain_*): one code object per (block size, border size)
-  struct KktMod { unsigned elim_wg = 64; int elim_bpw = 1; hipModule_t mod = nullptr; hipFunction_t elim = nullptr, upd = nullptr, fwd = nullptr, bwd = nullptr, gather = nullptr, move = nullptr, colsum = nullptr, hub_z = nullptr, hub_widen = nullptr, hub_mask = nullptr, hub_ety = nullptr, hub_ex = nullptr, hub_leaf = nullptr, hub_diagmax = nullptr, fz = nullptr, fs = nullptr, bw = nullptr; int solve_bpw = 0;
+  struct KktMod { unsigned elim_wg = 64; int elim_bpw = 1; hipModule_t mod = nullptr; hipFunction_t elim = nullptr, upd = nullptr, fwd = nullptr, bwd = nullptr, hub_z = nullptr, hub_widen = nullptr, hub_mask = nullptr, hub_ety = nullptr, hub_ex = nullptr, hub_leaf = nullptr, hub_diagmax = nullptr, fz = nullptr, fs = nullptr, bw = nullptr; int solve_bpw = 0;
                   // the multi-column solves (csrc/iem_kkt_many_device.h): many_r columns per chunk (KKT_MR of the module's source)
                   hipFunction_t fwd_m = nullptr, bwd_m = nullptr, fz_m = nullptr, fs_m = nullptr, bw_m = nullptr, move_m = nullptr, colsum_m = nullptr; int many_r = 1; };
   std::map<std::pair<int, int>, KktMod> kkt_mods;
@@ -2679,7 +2674,6 @@ bool kkt_fits(int nb, int ne, int nc) {
 typedef iem_model::KktMod KM;
 const struct KktSlot { const char *name; hipFunction_t KM::*fn; bool lane_rows_only; } kKktSlots[] = {
     {"kkt_eliminate", &KM::elim, false}, {"kkt_update", &KM::upd, false}, {"kkt_forward", &KM::fwd, false}, {"kkt_backward", &KM::bwd, false},
-    {"kkt_gather", &KM::gather, false}, {"kkt_move", &KM::move, false}, {"kkt_colsum", &KM::colsum, false},
     {"kkt_hub_z", &KM::hub_z, false}, {"kkt_hub_widen", &KM::hub_widen, false}, {"kkt_hub_mask", &KM::hub_mask, false}, {"kkt_hub_ety", &KM::hub_ety, false},
     {"kkt_hub_ex", &KM::hub_ex, false}, {"kkt_hub_leaf", &KM::hub_leaf, false}, {"kkt_hub_diagmax", &KM::hub_diagmax, false},
     {"kkt_fz", &KM::fz, true}, {"kkt_fs", &KM::fs, true}, {"kkt_bw", &KM::bw, true}, {"kkt_fz_m", &KM::fz_m, true}, {"kkt_fs_m", &KM::fs_m, true}, {"kkt_bw_m", &KM::bw_m, true},
@@ -2931,7 +2925,7 @@ bool kkt_border_shape_ok(int64_t S, int ne, int n_border) { return S >= 1 && ne 
 // LDS of kkt_border_ldl / kkt_border_solve (the layout at the head of csrc/iem_kkt_border_device.h)
 unsigned kkt_border_lds(int ne) { return (unsigned)(8 * (ne * (ne + 1) + 2 * ne + 16) + 4 * (2 * ne + 16)); }
 unsigned kkt_border_wg(int ne) { return ne <= 32 ? 64u : 256u; }
-// kkt_colsum's pair of launches for nr matrices of rows x w (matrix u at in + u in_ld) through `fn` (kkt_colsum_m of a chain module
+// the column sums' pair of launches for nr matrices of rows x w (matrix u at in + u in_ld) through `fn` (kkt_colsum_m of a chain module
 // or its twin kkt_border_colsum): partial rows at part + u part_ld, the sums at part + u part_ld + res_off
 int kkt_border_sums(iem_model *m, hipFunction_t fn, const double *in, long long in_ld, int64_t rows, int64_t w, int nr, double *part, long long part_ld, long long res_off) {
   struct Sum { const double *in; double *out; long long rows, w, rows_per_wg, in_ld, out_ld, wgs; };
@@ -2999,15 +2993,23 @@ struct iem_kkt {
   iem_model *m = nullptr;
   iem::KktLayout L;
   iem_model::KktMod *km = nullptr;
-  double *d_flat = nullptr, *d_BR = nullptr, *d_Z = nullptr, *d_Gp = nullptr, *d_r = nullptr, *d_z = nullptr, *d_rBp = nullptr, *d_xB = nullptr, *d_part = nullptr;
+  double *d_flat = nullptr, *d_BR = nullptr, *d_Z = nullptr, *d_Gp = nullptr, *d_part = nullptr;
   int32_t *d_rows = nullptr, *d_cols = nullptr;
   long long *d_dest = nullptr, *d_on = nullptr, *d_pos = nullptr, *d_border = nullptr, *d_bloc = nullptr, *d_info = nullptr;
   unsigned *d_seg = nullptr, *d_perm = nullptr;
   int64_t n_dest = 0, n_on = 0, n_h = 0, n_j = 0;
-  double *m_r = nullptr, *m_z = nullptr, *m_rBp = nullptr, *m_xB = nullptr, *m_part = nullptr;      // iem_kkt_solve_many: ONE chunk of columns, allocated by its first call
+  // The solves' workspace: the block-ordered planes r, z, rBp, xB of ONE chunk of `chunk_cols` columns — one column from
+  // iem_kkt_create on, the shape's chunk width from the first multi-column solve on (kkt_chunk_workspace).  Hub mode uses column 0.
+  // An allocation per plane, grown together: as planes of one allocation r and z cost the one-column refined solve 1 % at 1e5
+  // quadrotor supports (the kernels' own time is the same in a trace; profiles/kkt_single_path_ab.json).
+  // (The column sums' partials sit in d_part: 513 ne doubles per column, and a chunk has at most four columns, ne at least four.)
+  double *w_r = nullptr, *w_z = nullptr, *w_rBp = nullptr, *w_xB = nullptr;
+  int chunk_cols = 0;
   std::vector<double> Gs;        // the border's Schur complement (host), set by iem_kkt_factor
-  double *w_ref = nullptr;       // iem_kkt_residual / iem_kkt_solve_refined: p, r, dsol (3 (nvar + ncon) doubles), allocated by the first call
-  double *w_diag = nullptr;      // iem_kkt_residual_diag / iem_kkt_solve_refined_diag: p | r | dsol for ONE slab of columns, allocated by the first call
+  // The residuals' and the refinement's workspace: the planes p | r | dsol of `ref_cols` columns of nvar + ncon doubles — one column
+  // from the first residual or refined call on, one slab from the first such call with several columns on (kkt_refine_workspace)
+  double *w_ref = nullptr;
+  int ref_cols = 0;
   int border_mode = 0;           // iem_kkt_set_border: 0 the border on the host, 1 on the device (d_F, d_piv: its factors)
   double *d_F = nullptr;
   int32_t *d_piv = nullptr;
@@ -3044,22 +3046,28 @@ int kkt_upload_bytes(void **d, const void *h, size_t bytes) {
   return IEM_OK;
 }
 #define kkt_upload(dptr, vec) kkt_upload_bytes((void **)(dptr), (vec).data(), (vec).size() * sizeof((vec)[0]))
-// column sums of a device S x w matrix, to the host
+// column sums of a device S x w matrix, to the host: kkt_border_sums' two launches (up to 512 row chunks x column chunks of 256 —
+// every CU busy: the border terms of 1e4 OPF scenarios are 216 MB), then w doubles come home
 int kkt_colsum_host(iem_kkt *k, const double *d_in, int64_t rows, int64_t w, std::vector<double> &out) {
-  // two launches: up to 512 row chunks x column chunks of 256 (every CU busy: the border terms of 1e4 OPF scenarios are 216 MB),
-  // then the partials into one row; w doubles come home
   iem_model *m = k->m;
-  const int64_t ncc = (w + 255) / 256, per = (rows + 511) / 512, nrc = (rows + per - 1) / per;
-  struct Sum { const double *in; double *out; long long rows, w, rows_per_wg; };
-  Sum A{d_in, k->d_part, (long long)rows, (long long)w, (long long)per};
-  int rc = kkt_launch_raw(m, k->km->colsum, &A, sizeof A, nrc * ncc, 256);
+  int rc = kkt_border_sums(m, k->km->colsum_m, d_in, 0, rows, w, 1, k->d_part, 0, (long long)(512 * w));
   if (rc) return rc;
-  double *d_row = k->d_part + 512 * w;
-  Sum B{k->d_part, d_row, (long long)nrc, (long long)w, (long long)nrc};
-  if ((rc = kkt_launch_raw(m, k->km->colsum, &B, sizeof B, ncc, 256))) return rc;
   out.assign((size_t)w, 0.0);
   HIP_TRY(hipStreamSynchronize(m->stream));
-  HIP_TRY(hipMemcpy(out.data(), d_row, (size_t)w * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out.data(), k->d_part + 512 * w, (size_t)w * 8, hipMemcpyDeviceToHost));
+  return IEM_OK;
+}
+// the solves' workspace for `cols` columns (grown, never shrunk: a growth waits for the stream, frees and allocates)
+int kkt_chunk_workspace(iem_kkt *k, int cols) {
+  if (k->chunk_cols >= cols) return IEM_OK;
+  if (k->chunk_cols) HIP_TRY(hipStreamSynchronize(k->m->stream));
+  const iem::KktLayout &L = k->L;
+  const int64_t ne = std::max<int64_t>(L.ne, 0), doubles[4] = {L.S * L.nb, L.S * L.nb, L.S * ne, ne};
+  double **plane[4] = {&k->w_r, &k->w_z, &k->w_rBp, &k->w_xB};
+  for (double **p : plane) { if (*p) hipFree(*p); *p = nullptr; }
+  k->chunk_cols = 0;
+  for (int i = 0; i < 4; ++i) HIP_TRY(hipMalloc((void **)plane[i], (size_t)std::max<int64_t>(cols * doubles[i], 1) * 8));
+  k->chunk_cols = cols;
   return IEM_OK;
 }
 }  // namespace
@@ -3322,29 +3330,32 @@ int hub_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
   int rc;
   if ((rc = hub_blas_load(k))) return rc;
   const double *Dinv = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB(), *E0 = k->d_flat + L.oE();
-  struct Mv { double *dst; const double *src; const long long *di, *si; long long n; };
   struct Vec { const double *E0, *v; double *out; const int *q; long long T, lanes; int nb, nq, hw; };
+  auto move = [&](double *dst, const double *src, const long long *di, const long long *si, int64_t cnt) {      // kkt_move_m on one column
+    struct { double *dst; const double *src; const long long *di, *si; long long n, ldd, lds; int nr; } A{dst, src, di, si, (long long)cnt, 0, 0, 1};
+    return kkt_launch_raw(m, k->km->move_m, &A, sizeof A, (cnt + 255) / 256, 256);
+  };
+  double *d_r = k->w_r, *d_z = k->w_z;      // column 0 of the solves' workspace
   const size_t rbytes = (size_t)(L.S * L.nb) * 8;
   auto chain = [&](double *r) {
-    int e = iem_kkt_chain_solve_lanes(m, L.S, L.Tp, L.nb, 0, L.nc, Dinv, Bt, k->d_BR, k->d_rows, k->d_cols, nullptr, r, k->d_z, nullptr, nullptr, 0);
-    return e ? e : iem_kkt_chain_solve_lanes(m, L.S, L.Tp, L.nb, 0, L.nc, Dinv, Bt, k->d_BR, k->d_rows, k->d_cols, nullptr, r, k->d_z, nullptr, nullptr, 1);
+    int e = iem_kkt_chain_solve_lanes(m, L.S, L.Tp, L.nb, 0, L.nc, Dinv, Bt, k->d_BR, k->d_rows, k->d_cols, nullptr, r, d_z, nullptr, nullptr, 0);
+    return e ? e : iem_kkt_chain_solve_lanes(m, L.S, L.Tp, L.nb, 0, L.nc, Dinv, Bt, k->d_BR, k->d_rows, k->d_cols, nullptr, r, d_z, nullptr, nullptr, 1);
   };
   HIP_TRY(hipMemsetAsync(h->r2, 0, rbytes, m->stream));
-  { Mv A{h->r2, d_rhs, k->d_pos, k->d_on, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
-  HIP_TRY(hipMemcpyAsync(k->d_r, h->r2, rbytes, hipMemcpyDeviceToDevice, m->stream));
-  if ((rc = chain(k->d_r))) return rc;                                       // y = K_c^-1 r_c
+  if ((rc = move(h->r2, d_rhs, k->d_pos, k->d_on, k->n_on))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_r, h->r2, rbytes, hipMemcpyDeviceToDevice, m->stream));
+  if ((rc = chain(d_r))) return rc;                                          // y = K_c^-1 r_c
   // r_B - E' y on the hubs, the dense solve, then x_c = K_c^-1 (r_c - E x_B)
   HIP_TRY(hipMemsetAsync(h->x, 0, (size_t)std::max<int64_t>(h->steps * HUB_LEAF, L.Tp * L.hw) * 8, m->stream));
-  { Mv A{h->x, d_rhs, k->d_bloc, k->d_border, (long long)L.n_border}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc; }
-  { Vec A{E0, k->d_r, h->x, h->d_q, (long long)L.Tp, (long long)L.lanes, L.nb, L.nq, (int)L.hw}; if ((rc = kkt_launch_raw(m, k->km->hub_ety, &A, sizeof A, L.Tp, 64))) return rc; }
+  if ((rc = move(h->x, d_rhs, k->d_bloc, k->d_border, L.n_border))) return rc;
+  { Vec A{E0, d_r, h->x, h->d_q, (long long)L.Tp, (long long)L.lanes, L.nb, L.nq, (int)L.hw}; if ((rc = kkt_launch_raw(m, k->km->hub_ety, &A, sizeof A, L.Tp, 64))) return rc; }
   if ((rc = hub_dense_solve(k, h->x))) return rc;
   if (L.Tp * L.hw > L.H) HIP_TRY(hipMemsetAsync(h->x + L.H, 0, (size_t)(L.Tp * L.hw - L.H) * 8, m->stream));
   { Vec A{E0, h->x, h->r2, h->d_q, (long long)L.Tp, (long long)L.lanes, L.nb, L.nq, (int)L.hw};
     if ((rc = kkt_launch_raw(m, k->km->hub_ex, &A, sizeof A, (L.Tp * L.lanes * L.nq + 255) / 256, 256))) return rc; }
   if ((rc = chain(h->r2))) return rc;
-  { Mv A{d_sol, h->r2, k->d_on, k->d_pos, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
-  { Mv A{d_sol, h->x, k->d_border, k->d_bloc, (long long)L.n_border}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc; }
-  return IEM_OK;
+  if ((rc = move(d_sol, h->r2, k->d_on, k->d_pos, k->n_on))) return rc;
+  return move(d_sol, h->x, k->d_border, k->d_bloc, L.n_border);
 }
 }  // namespace
 
@@ -3402,6 +3413,7 @@ int iem_kkt_create(iem_model *m, int group, iem_kkt **out) {
     int rc = kkt_module(m, k->L.nb, k->L.ne, k->L.nc, &k->km);
     if (rc) return rc;
     const iem::KktLayout &L = k->L;
+    if (L.ne > 0 && k->km->many_r > L.ne) return fail(IEM_E_ARG, "iem_kkt_create: internal — a chunk of columns is wider than the border");      // (d_part holds a chunk's column sums)
     std::vector<long long> dest(P.dest.begin(), P.dest.end()), on, pos, border, bloc;
     for (int64_t u = 0; u < L.nvar + L.ncon; ++u) {
       if (L.blk[(size_t)u] >= 0) { on.push_back(u); pos.push_back(L.blk[(size_t)u] * L.nb + L.loc[(size_t)u]); }
@@ -3417,15 +3429,15 @@ int iem_kkt_create(iem_model *m, int group, iem_kkt **out) {
     HIP_TRY(hipMalloc((void **)&k->d_BR, (size_t)std::max<int64_t>(S * nc * nc, 1) * 8));
     HIP_TRY(hipMalloc((void **)&k->d_Z, (size_t)std::max<int64_t>(S * nb * ne, 1) * 8));
     HIP_TRY(hipMalloc((void **)&k->d_Gp, (size_t)std::max<int64_t>(S * ne * ne, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&k->d_r, (size_t)(S * nb) * 8));
-    HIP_TRY(hipMalloc((void **)&k->d_z, (size_t)(S * nb) * 8));
-    HIP_TRY(hipMalloc((void **)&k->d_rBp, (size_t)std::max<int64_t>(S * ne, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&k->d_xB, (size_t)std::max<int64_t>(ne, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&k->d_part, (size_t)(513 * std::max<int64_t>(ne * ne, 1)) * 8));      // kkt_colsum_host: 512 partial rows + the result
+    if ((rc = kkt_chunk_workspace(k.get(), 1))) return rc;      // (here, not in the first solve: a one-column solve can be captured without a warm-up call)
+    HIP_TRY(hipMalloc((void **)&k->d_part, (size_t)(513 * std::max<int64_t>(ne * ne, 1)) * 8));      // kkt_border_sums: 512 partial rows + the result of Gp's sum (ne^2 wide) — and, in a solve, of rBp's per column of a chunk (ne wide, at most ne columns)
     HIP_TRY(hipMalloc((void **)&k->d_info, 32));
     HIP_TRY(hipMalloc((void **)&k->d_F, (size_t)std::max<int64_t>(ne * ne, 1) * 8));
     HIP_TRY(hipMalloc((void **)&k->d_piv, (size_t)std::max<int64_t>(ne, 1) * 4));
     if (L.hubs && (rc = hub_alloc(k.get()))) return rc;
+    // the gather / residual / add of the object itself: loaded here, so that iem_kkt_assemble stays launch-only — and behind the
+    // allocations, where the lazy load of the former per-row calls sat
+    if ((rc = fixed_object(m, F_KDIAG))) return rc;
   } catch (const std::exception &e) {
     return fail(IEM_E_ARG, e.what());
   }
@@ -3437,8 +3449,7 @@ int iem_kkt_destroy(iem_kkt *k) {
   if (!k) return IEM_OK;
   DevGuard dg_(k->m->device);
   hub_free(k);
-  for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_r, (void *)k->d_z, (void *)k->d_rBp, (void *)k->d_xB, (void *)k->d_part,
-                  (void *)k->m_r, (void *)k->m_z, (void *)k->m_rBp, (void *)k->m_xB, (void *)k->m_part, (void *)k->w_ref, (void *)k->w_diag, (void *)k->d_F, (void *)k->d_piv,
+  for (void *p : {(void *)k->d_flat, (void *)k->d_BR, (void *)k->d_Z, (void *)k->d_Gp, (void *)k->d_part, (void *)k->w_r, (void *)k->w_z, (void *)k->w_rBp, (void *)k->w_xB, (void *)k->w_ref, (void *)k->d_F, (void *)k->d_piv,
                   (void *)k->d_rows, (void *)k->d_cols, (void *)k->d_dest, (void *)k->d_on, (void *)k->d_pos, (void *)k->d_border, (void *)k->d_bloc, (void *)k->d_info,
                   (void *)k->d_seg, (void *)k->d_perm})
     if (p) hipFree(p);
@@ -3464,16 +3475,7 @@ int iem_kkt_layout(const iem_kkt *k, int64_t *h_blk, int64_t *h_loc, int32_t *h_
 }
 
 int iem_kkt_assemble(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, double delta_w, double delta_c) {
-  if (!k || (!d_hess && k->n_h) || (!d_jac && k->n_j)) return fail(IEM_E_ARG, "null argument");
-  iem_model *m = k->m;
-  DevGuard dg_(m->device);
-  const iem::KktLayout &L = k->L;
-  HIP_TRY(hipMemsetAsync(k->d_flat, 0, (size_t)L.total() * 8, m->stream));
-  struct { double *flat; const long long *dest; const unsigned *seg, *perm; const double *hess, *jac, *sigma; double dw, dc; long long n_dest, n_h, n_j, n_var, n_con; } A{
-      k->d_flat, k->d_dest, k->d_seg, k->d_perm, d_hess, d_jac, d_sigma, delta_w, delta_c, (long long)k->n_dest, (long long)k->n_h, (long long)k->n_j,
-      (long long)L.nvar, (long long)L.ncon};
-  k->factored = false;
-  return kkt_launch_raw(m, k->km->gather, &A, sizeof A, (k->n_dest + 255) / 256, 256);
+  return iem_kkt_assemble_diag(k, d_hess, d_jac, d_sigma, nullptr, delta_w, delta_c);
 }
 
 namespace {
@@ -3561,120 +3563,39 @@ int iem_kkt_factor(iem_kkt *k, int64_t *out_inertia) {
   return IEM_OK;
 }
 
-int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
-  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
-  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
-  iem_model *m = k->m;
-  DevGuard dg_(m->device);
-  const iem::KktLayout &L = k->L;
-  if (L.hubs) return hub_solve(k, d_rhs, d_sol);
-  const bool chained = L.reach > 0;
-  const double *Dinv = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB();
-  HIP_TRY(hipMemsetAsync(k->d_r, 0, (size_t)(L.S * L.nb) * 8, m->stream));
-  struct Mv { double *dst; const double *src; const long long *di, *si; long long n; };
-  int rc;
-  { Mv A{k->d_r, d_rhs, k->d_pos, k->d_on, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
-  if ((rc = iem_kkt_chain_solve(m, L.S, L.nb, L.ne, L.nc, Dinv, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
-                                chained ? k->d_cols : nullptr, k->d_Z, k->d_r, chained ? k->d_z : nullptr, k->d_rBp, nullptr, 0)))
-    return rc;
-  if (L.ne > 0 && k->border_mode == 1) {      // border system on the device: the column sum of rBp, then ONE workgroup
-    if ((rc = kkt_border_sums(m, k->km->colsum_m, k->d_rBp, 0, L.S, L.ne, 1, k->d_part, 0, 512LL * L.ne))) return rc;
-    if ((rc = kkt_border_solve_run(m, KktBorderSolveArgsH{k->d_F, k->d_piv, d_rhs, k->d_border, k->d_bloc, k->d_part + 512 * L.ne, k->d_xB, 0, 0, 0, L.ne, (int)L.n_border}, 1)))
-      return rc;
-  } else if (L.ne > 0) {      // border system on the host: Gs xB = rB - sum_k rBp[k]
-    std::vector<double> rbp, rB((size_t)L.ne, 0.0);
-    if ((rc = kkt_colsum_host(k, k->d_rBp, L.S, L.ne, rbp))) return rc;
-    std::vector<double> rhs_b((size_t)L.n_border);
-    std::vector<long long> border((size_t)L.n_border);
-    if (L.n_border) {   // (a handful of entries: gathered through a staging vector on the device)
-      Mv A{k->d_xB, d_rhs, k->d_bloc, k->d_border, (long long)L.n_border};
-      if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc;
-      HIP_TRY(hipStreamSynchronize(m->stream));
-      HIP_TRY(hipMemcpy(rB.data(), k->d_xB, (size_t)L.n_border * 8, hipMemcpyDeviceToHost));
-    }
-    for (int i = 0; i < L.ne; ++i) rB[(size_t)i] = (i < L.n_border ? rB[(size_t)i] : 0.0) - rbp[(size_t)i];
-    if (!iem::dense_solve(k->Gs, L.ne, rB)) return fail(IEM_E_ARG, "iem_kkt_solve: the border's Schur complement is singular");
-    HIP_TRY(hipMemcpyAsync(k->d_xB, rB.data(), (size_t)L.ne * 8, hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));      // (rB is a host temporary)
-  }
-  if ((rc = iem_kkt_chain_solve(m, L.S, L.nb, L.ne, L.nc, Dinv, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
-                                chained ? k->d_cols : nullptr, k->d_Z, k->d_r, chained ? k->d_z : nullptr, k->d_rBp, L.ne > 0 ? k->d_xB : nullptr, 1)))
-    return rc;
-  { Mv A{d_sol, k->d_r, k->d_on, k->d_pos, (long long)k->n_on}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (k->n_on + 255) / 256, 256))) return rc; }
-  if (L.n_border) { Mv A{d_sol, k->d_xB, k->d_border, k->d_bloc, (long long)L.n_border}; if ((rc = kkt_launch_raw(m, k->km->move, &A, sizeof A, (L.n_border + 255) / 256, 256))) return rc; }
-  return IEM_OK;
-}
-
-/* ---- the residual of a KKT solve, matrix-free, and iterative refinement with it ---------------------------------------------- */
+/* ---- solve, residual and refined solve of the object: ONE implementation each, over nrhs columns (nrhs = 1, ld = nvar + ncon, no
+ * per-row diagonal: the single-column entry points).  An entry point makes its refusals in its own name (`who`), then calls the
+ * implementation.  K = [W + diag(sigma) + delta_w I, J'; J, -diag(dcon + delta_c)]  (csrc/iem_kkt_diag_device.h) ---------------------- */
 namespace {
-// the finishing kernels and the workspace {p, r, dsol}: the synchronous part of the first call
-int kkt_refine_setup(iem_kkt *k) {
-  int rc = fixed_object(k->m, F_KRES);
-  if (rc) return rc;
-  if (!k->w_ref) HIP_TRY(hipMalloc((void **)&k->w_ref, (size_t)std::max<int64_t>(3 * (k->L.nvar + k->L.ncon), 1) * 8));
-  return IEM_OK;
-}
+constexpr int KKT_DIAG_SLAB = 8;      // columns per pass of a residual / a refined solve: a multiple of every chunk width of the multi-column kernels (kkt_many_width: 2 or 4)
 long long kkt_stream_grid(int64_t n) { return (long long)std::min<int64_t>((n + 255) / 256, 4096); }
-}  // namespace
-
-int iem_kkt_residual_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_KRES, out_src, out_key); }
-
-int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
-                     const double *d_rhs, const double *d_sol, double *d_r, double *d_norm) {
-  if (!k || !d_rhs || !d_sol || !d_r) return fail(IEM_E_ARG, "null argument");
-  iem_model *m = k->m;
-  const int64_t nvar = k->L.nvar, ncon = k->L.ncon, n = nvar + ncon;
-  if (kkt_overlap(d_r, n, d_sol, n) || (d_r != d_rhs && kkt_overlap(d_r, n, d_rhs, n)) || kkt_overlap(d_r, n, d_norm, 1) || kkt_overlap(d_norm, 1, d_sol, n) ||
-      kkt_overlap(d_norm, 1, d_rhs, n))
-    return fail(IEM_E_ARG, "iem_kkt_residual: d_r overlaps d_sol or part of d_rhs, or d_norm lies inside a vector");
-  DevGuard dg_(m->device);
-  int rc = kkt_refine_setup(k);
-  if (rc) return rc;
-  double *p = k->w_ref;
-  if ((rc = iem_kktprod(m, d_x, d_y, obj_weight, d_sol, ncon ? d_sol + nvar : nullptr, p, ncon ? p + nvar : nullptr))) return rc;
-  if (d_norm) HIP_TRY(hipMemsetAsync(d_norm, 0, 8, m->stream));
-  struct { const double *p, *rhs, *sol, *sigma; double *r; unsigned long long *norm; double dw, dc; long long nvar, n; } A{
-      p, d_rhs, d_sol, d_sigma, d_r, (unsigned long long *)d_norm, delta_w, delta_c, (long long)nvar, (long long)n};
-  return kkt_launch_raw(m, m->fixed[F_KRES].fn[KRES_RESIDUAL], &A, sizeof A, kkt_stream_grid(n), 256);
-}
-
-int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
-                          const double *d_rhs, double *d_sol, int steps, double *d_norms) {
-  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
-  if (steps < 0) return fail(IEM_E_ARG, "iem_kkt_solve_refined: steps must not be negative");
-  const int64_t n = k->L.nvar + k->L.ncon;
-  if (kkt_overlap(d_sol, n, d_rhs, n) || kkt_overlap(d_norms, steps + 1, d_sol, n) || kkt_overlap(d_norms, steps + 1, d_rhs, n))
-    return fail(IEM_E_ARG, "iem_kkt_solve_refined: d_sol, d_rhs and d_norms may not overlap");
-  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
-  iem_model *m = k->m;
-  DevGuard dg_(m->device);
-  int rc = kkt_refine_setup(k);
-  if (rc) return rc;
-  double *r = k->w_ref + n, *dsol = k->w_ref + 2 * n;
-  if ((rc = iem_kkt_solve(k, d_rhs, d_sol))) return rc;
-  for (int i = 0; i < steps; ++i) {
-    if ((rc = iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms ? d_norms + i : nullptr))) return rc;
-    if ((rc = iem_kkt_solve(k, r, dsol))) return rc;
-    struct { double *sol; const double *d; long long n; } A{d_sol, dsol, (long long)n};
-    if ((rc = kkt_launch_raw(m, m->fixed[F_KRES].fn[KRES_AXPY], &A, sizeof A, kkt_stream_grid(n), 256))) return rc;
-  }
-  if (d_norms) return iem_kkt_residual(k, d_x, d_y, obj_weight, d_sigma, delta_w, delta_c, d_rhs, d_sol, r, d_norms + steps);
+// the whole extent [d, d + (nrhs - 1) ld + n) of a set of columns
+int64_t kkt_extent(int nrhs, int64_t ld, int64_t n) { return (int64_t)(nrhs - 1) * ld + n; }
+int kkt_refuse(const char *who, const char *what) { return fail(IEM_E_ARG, std::string(who) + ": " + what); }
+// what every call over columns refuses first (nrhs before the object is looked at)
+int kkt_columns_refusals(const char *who, const iem_kkt *k, int nrhs, std::initializer_list<const void *> vectors, std::initializer_list<int64_t> lds) {
+  if (!k) return kkt_refuse(who, "null argument");
+  for (const void *v : vectors) if (!v) return kkt_refuse(who, "null argument");
+  if (nrhs < 1) return kkt_refuse(who, "nrhs must be at least 1");
+  for (int64_t ld : lds) if (ld < k->L.nvar + k->L.ncon) return kkt_refuse(who, "a leading dimension is shorter than nvar + ncon");
   return IEM_OK;
 }
+const char *kNoFactorisation = "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)";      // (one sentence, whoever refuses)
 
-int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol) {
-  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
-  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_solve_many: nrhs must be at least 1");
+int kkt_solve_refusals(const char *who, const iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol) {
+  int rc = kkt_columns_refusals(who, k, nrhs, {d_rhs, d_sol}, {ld_rhs, ld_sol});
+  if (rc) return rc;
+  const int64_t n = k->L.nvar + k->L.ncon;
+  // in place column for column, or apart.  (Address ranges as integers: the two may be unrelated allocations.  Whole extents are
+  // compared — columns of one array interleaved with columns of the other are refused too)
+  if (!(d_sol == d_rhs && ld_sol == ld_rhs) && kkt_overlap(d_rhs, kkt_extent(nrhs, ld_rhs, n), d_sol, kkt_extent(nrhs, ld_sol, n)))
+    return kkt_refuse(who, "d_rhs and d_sol overlap (allowed: the same array with the same leading dimension)");
+  if (!k->factored) return fail(IEM_E_ARG, kNoFactorisation);
+  return IEM_OK;
+}
+// the solve behind those refusals: chunks of the shape's width (a chunk of ONE column runs the single-column kernels of the chain)
+int kkt_solve_columns(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol) {
   const iem::KktLayout &L = k->L;
-  const int64_t n = L.nvar + L.ncon;
-  if (ld_rhs < n || ld_sol < n) return fail(IEM_E_ARG, "iem_kkt_solve_many: a leading dimension is shorter than nvar + ncon");
-  if (!(d_sol == d_rhs && ld_sol == ld_rhs)) {      // in place column for column, or apart
-    // (address ranges as integers: the two may be unrelated allocations.  Whole extents are compared — columns of one array
-    // interleaved with columns of the other are refused too)
-    const uintptr_t r0 = (uintptr_t)d_rhs, r1 = r0 + (uintptr_t)(((int64_t)(nrhs - 1) * ld_rhs + n) * 8), s0 = (uintptr_t)d_sol, s1 = s0 + (uintptr_t)(((int64_t)(nrhs - 1) * ld_sol + n) * 8);
-    if (r0 < s1 && s0 < r1) return fail(IEM_E_ARG, "iem_kkt_solve_many: d_rhs and d_sol overlap (allowed: the same array with the same leading dimension)");
-  }
-  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
   iem_model *m = k->m;
   DevGuard dg_(m->device);
   int rc;
@@ -3684,86 +3605,73 @@ int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs
     return IEM_OK;
   }
   const int R = k->km->many_r;
-  const int64_t pl = L.S * L.nb, ne = L.ne, wp = 513 * std::max<int64_t>(ne, 1);
-  if (!k->m_r) {
-    HIP_TRY(hipMalloc((void **)&k->m_r, (size_t)(R * pl) * 8));
-    HIP_TRY(hipMalloc((void **)&k->m_z, (size_t)(R * pl) * 8));
-    HIP_TRY(hipMalloc((void **)&k->m_rBp, (size_t)std::max<int64_t>(R * L.S * ne, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&k->m_xB, (size_t)std::max<int64_t>(R * ne, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&k->m_part, (size_t)(R * wp) * 8));      // per column: 512 partial rows + the result (kkt_colsum_host)
-  }
+  const int64_t pl = L.S * L.nb, ne = L.ne, wp = 513 * std::max<int64_t>(ne, 1);      // wp: per column 512 partial rows of the column sums + the result, in d_part
+  if ((rc = kkt_chunk_workspace(k, nrhs > 1 ? R : 1))) return rc;      // (one column: what iem_kkt_create allocated)
+  double *w_r = k->w_r, *w_z = k->w_z, *w_rBp = k->w_rBp, *w_xB = k->w_xB;
   const bool chained = L.reach > 0;
   const double *Dinv = k->d_flat + L.oD(), *Bt = k->d_flat + L.oB();
   struct Mv { double *dst; const double *src; const long long *di, *si; long long n, ldd, lds; int nr; };
-  struct Sum { const double *in; double *out; long long rows, w, rows_per_wg, in_ld, out_ld, wgs; };
   auto move = [&](Mv A, int64_t cnt) { A.n = (long long)cnt; return kkt_launch_raw(m, k->km->move_m, &A, sizeof A, (cnt + 255) / 256, 256); };
   auto chain = [&](int nr, int phase) {
     return iem_kkt_chain_solve_many(m, L.S, L.S, L.nb, L.ne, L.nc, Dinv, chained ? Bt : nullptr, chained ? k->d_BR : nullptr, chained ? k->d_rows : nullptr,
-                                    chained ? k->d_cols : nullptr, k->d_Z, k->m_r, chained ? k->m_z : nullptr, k->m_rBp, (phase && ne > 0) ? k->m_xB : nullptr, nr, phase);
+                                    chained ? k->d_cols : nullptr, k->d_Z, w_r, chained ? w_z : nullptr, w_rBp, (phase && ne > 0) ? w_xB : nullptr, nr, phase);
   };
   std::vector<double> rB, col;
   for (int c0 = 0; c0 < nrhs; c0 += R) {
     const int nr = std::min(R, nrhs - c0);
     const double *rhs = d_rhs + (int64_t)c0 * ld_rhs;
     double *sol = d_sol + (int64_t)c0 * ld_sol;
-    HIP_TRY(hipMemsetAsync(k->m_r, 0, (size_t)(nr * pl) * 8, m->stream));
-    if ((rc = move(Mv{k->m_r, rhs, k->d_pos, k->d_on, 0, (long long)pl, (long long)ld_rhs, nr}, k->n_on))) return rc;
+    HIP_TRY(hipMemsetAsync(w_r, 0, (size_t)(nr * pl) * 8, m->stream));
+    if ((rc = move(Mv{w_r, rhs, k->d_pos, k->d_on, 0, (long long)pl, (long long)ld_rhs, nr}, k->n_on))) return rc;
     if ((rc = chain(nr, 0))) return rc;
     if (ne > 0 && k->border_mode == 1) {      // the border systems on the device: ONE launch, a workgroup per column
-      if ((rc = kkt_border_sums(m, k->km->colsum_m, k->m_rBp, (long long)(L.S * ne), L.S, ne, nr, k->m_part, (long long)wp, 512LL * ne))) return rc;
-      if ((rc = kkt_border_solve_run(m, KktBorderSolveArgsH{k->d_F, k->d_piv, rhs, k->d_border, k->d_bloc, k->m_part + 512 * ne, k->m_xB, (long long)ld_rhs, (long long)wp,
+      if ((rc = kkt_border_sums(m, k->km->colsum_m, w_rBp, (long long)(L.S * ne), L.S, ne, nr, k->d_part, (long long)wp, 512LL * ne))) return rc;
+      if ((rc = kkt_border_solve_run(m, KktBorderSolveArgsH{k->d_F, k->d_piv, rhs, k->d_border, k->d_bloc, k->d_part + 512 * ne, w_xB, (long long)ld_rhs, (long long)wp,
                                                             (long long)ne, (int)ne, (int)L.n_border}, nr)))
         return rc;
     } else if (ne > 0) {      // the border systems on the host: Gs xB = rB - sum_k rBp[k] per column — ONE read-back and ONE upload per chunk
-      const int64_t ncc = (ne + 255) / 256, per = (L.S + 511) / 512, nrc = (L.S + per - 1) / per;      // kkt_colsum_host's two launches, for every column
-      Sum A{k->m_rBp, k->m_part, (long long)L.S, (long long)ne, (long long)per, (long long)(L.S * ne), (long long)wp, (long long)(nrc * ncc)};
-      if ((rc = kkt_launch_raw(m, k->km->colsum_m, &A, sizeof A, nr * nrc * ncc, 256))) return rc;
-      Sum B{k->m_part, k->m_part + 512 * ne, (long long)nrc, (long long)ne, (long long)nrc, (long long)wp, (long long)wp, (long long)ncc};
-      if ((rc = kkt_launch_raw(m, k->km->colsum_m, &B, sizeof B, nr * ncc, 256))) return rc;
+      if ((rc = kkt_border_sums(m, k->km->colsum_m, w_rBp, (long long)(L.S * ne), L.S, ne, nr, k->d_part, (long long)wp, 512LL * ne))) return rc;
       if (L.n_border) {
-        HIP_TRY(hipMemsetAsync(k->m_xB, 0, (size_t)(nr * ne) * 8, m->stream));
-        if ((rc = move(Mv{k->m_xB, rhs, k->d_bloc, k->d_border, 0, (long long)ne, (long long)ld_rhs, nr}, L.n_border))) return rc;
+        HIP_TRY(hipMemsetAsync(w_xB, 0, (size_t)(nr * ne) * 8, m->stream));
+        if ((rc = move(Mv{w_xB, rhs, k->d_bloc, k->d_border, 0, (long long)ne, (long long)ld_rhs, nr}, L.n_border))) return rc;
       }
       rB.assign((size_t)(nr * ne), 0.0);
       std::vector<double> rbp((size_t)(nr * ne));
       HIP_TRY(hipStreamSynchronize(m->stream));
-      HIP_TRY(hipMemcpy2D(rbp.data(), (size_t)ne * 8, k->m_part + 512 * ne, (size_t)wp * 8, (size_t)ne * 8, (size_t)nr, hipMemcpyDeviceToHost));
-      if (L.n_border) HIP_TRY(hipMemcpy(rB.data(), k->m_xB, (size_t)(nr * ne) * 8, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy2D(rbp.data(), (size_t)ne * 8, k->d_part + 512 * ne, (size_t)wp * 8, (size_t)ne * 8, (size_t)nr, hipMemcpyDeviceToHost));
+      if (L.n_border) HIP_TRY(hipMemcpy(rB.data(), w_xB, (size_t)(nr * ne) * 8, hipMemcpyDeviceToHost));
       for (int u = 0; u < nr; ++u) {
         col.assign((size_t)ne, 0.0);
         for (int i = 0; i < ne; ++i) col[(size_t)i] = (i < L.n_border ? rB[(size_t)(u * ne + i)] : 0.0) - rbp[(size_t)(u * ne + i)];
         if (!iem::dense_solve(k->Gs, L.ne, col)) return fail(IEM_E_ARG, "iem_kkt_solve: the border's Schur complement is singular");
         std::copy(col.begin(), col.end(), rB.begin() + (size_t)u * (size_t)ne);
       }
-      HIP_TRY(hipMemcpyAsync(k->m_xB, rB.data(), (size_t)(nr * ne) * 8, hipMemcpyHostToDevice, m->stream));
+      HIP_TRY(hipMemcpyAsync(w_xB, rB.data(), (size_t)(nr * ne) * 8, hipMemcpyHostToDevice, m->stream));
       HIP_TRY(hipStreamSynchronize(m->stream));      // (rB is a host temporary)
     }
     if ((rc = chain(nr, 1))) return rc;
-    if ((rc = move(Mv{sol, k->m_r, k->d_on, k->d_pos, 0, (long long)ld_sol, (long long)pl, nr}, k->n_on))) return rc;
-    if (L.n_border && (rc = move(Mv{sol, k->m_xB, k->d_border, k->d_bloc, 0, (long long)ld_sol, (long long)ne, nr}, L.n_border))) return rc;
+    if ((rc = move(Mv{sol, w_r, k->d_on, k->d_pos, 0, (long long)ld_sol, (long long)pl, nr}, k->n_on))) return rc;
+    if (L.n_border && (rc = move(Mv{sol, w_xB, k->d_border, k->d_bloc, 0, (long long)ld_sol, (long long)ne, nr}, L.n_border))) return rc;
   }
   return IEM_OK;
 }
 
-/* ---- a per-row diagonal in the constraint block, and the residual / refinement over several columns ----------------------------
- * K = [W + diag(sigma) + delta_w I, J'; J, -diag(dcon + delta_c)]  (csrc/iem_kkt_diag_device.h) */
-namespace {
-constexpr int KKT_DIAG_SLAB = 8;      // columns per pass: a multiple of every chunk width of the multi-column kernels (kkt_many_width: 2 or 4)
-// the code object and — `workspace` — the planes {p, r, dsol} of one slab: the synchronous part of the first call
-int kkt_diag_setup(iem_kkt *k, bool workspace) {
-  int rc = fixed_object(k->m, F_KDIAG);
-  if (rc) return rc;
-  if (workspace && !k->w_diag) HIP_TRY(hipMalloc((void **)&k->w_diag, (size_t)std::max<int64_t>(3 * KKT_DIAG_SLAB * (k->L.nvar + k->L.ncon), 1) * 8));
+// the planes p | r | dsol for `nrhs` columns (one column, or one slab): the synchronous part of the first residual or refined call,
+// grown like the solves' workspace
+int kkt_refine_workspace(iem_kkt *k, int nrhs) {
+  const int cols = nrhs > 1 ? KKT_DIAG_SLAB : 1;
+  if (k->ref_cols >= cols) return IEM_OK;
+  if (k->w_ref) { HIP_TRY(hipStreamSynchronize(k->m->stream)); hipFree(k->w_ref); k->w_ref = nullptr; k->ref_cols = 0; }
+  HIP_TRY(hipMalloc((void **)&k->w_ref, (size_t)std::max<int64_t>(3 * cols * (k->L.nvar + k->L.ncon), 1) * 8));
+  k->ref_cols = cols;
   return IEM_OK;
 }
-// the whole extent [d, d + (nrhs - 1) ld + n) of a set of columns
-int64_t kkt_extent(int nrhs, int64_t ld, int64_t n) { return (int64_t)(nrhs - 1) * ld + n; }
-// the residuals of nr <= KKT_DIAG_SLAB columns: one iem_kktprod per column into the slab's p planes, then ONE launch
+// the residuals of nr <= ref_cols columns: one iem_kktprod per column into the p planes, then ONE launch
 int kkt_residual_slab(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c,
                       int nr, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, double *d_r, int64_t ld_r, double *d_norms) {
   iem_model *m = k->m;
   const int64_t nvar = k->L.nvar, ncon = k->L.ncon, n = nvar + ncon;
-  double *p = k->w_diag;
+  double *p = k->w_ref;
   int rc;
   for (int u = 0; u < nr; ++u) {
     const double *s = d_sol + (int64_t)u * ld_sol;
@@ -3776,17 +3684,103 @@ int kkt_residual_slab(iem_kkt *k, const double *d_x, const double *d_y, double o
       (long long)ld_rhs, (long long)ld_sol, (long long)ld_r};
   return kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_RESIDUAL], &A, sizeof A, kkt_stream_grid(n), 256, nr);
 }
+
+int kkt_residual_refusals(const char *who, const iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, const double *d_r,
+                          int64_t ld_r, const double *d_norms) {
+  int rc = kkt_columns_refusals(who, k, nrhs, {d_rhs, d_sol, d_r}, {ld_rhs, ld_sol, ld_r});
+  if (rc) return rc;
+  const int64_t n = k->L.nvar + k->L.ncon, er = kkt_extent(nrhs, ld_r, n), eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n);
+  if (kkt_overlap(d_r, er, d_sol, es) || (!(d_r == d_rhs && ld_r == ld_rhs) && kkt_overlap(d_r, er, d_rhs, eb)) || kkt_overlap(d_r, er, d_norms, nrhs) ||
+      kkt_overlap(d_norms, nrhs, d_sol, es) || kkt_overlap(d_norms, nrhs, d_rhs, eb))
+    return kkt_refuse(who, "overlap — d_r overlaps d_sol or d_rhs (allowed: d_r == d_rhs with the same leading dimension), or d_norms lies inside the vectors");
+  return IEM_OK;
+}
+int kkt_residual_columns(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c,
+                         int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, double *d_r, int64_t ld_r, double *d_norms) {
+  DevGuard dg_(k->m->device);
+  int rc = kkt_refine_workspace(k, nrhs);
+  if (rc) return rc;
+  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
+    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
+    if ((rc = kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, d_rhs + (int64_t)c0 * ld_rhs, ld_rhs, d_sol + (int64_t)c0 * ld_sol, ld_sol,
+                                d_r + (int64_t)c0 * ld_r, ld_r, d_norms ? d_norms + c0 : nullptr)))
+      return rc;
+  }
+  return IEM_OK;
+}
+
+int kkt_refined_refusals(const char *who, const iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, int steps,
+                         const double *d_norms) {
+  int rc = kkt_columns_refusals(who, k, nrhs, {d_rhs, d_sol}, {ld_rhs, ld_sol});
+  if (rc) return rc;
+  if (steps < 0) return kkt_refuse(who, "steps must not be negative");
+  const int64_t n = k->L.nvar + k->L.ncon, eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n), en = (int64_t)(steps + 1) * nrhs;
+  if (kkt_overlap(d_sol, es, d_rhs, eb) || kkt_overlap(d_norms, en, d_sol, es) || kkt_overlap(d_norms, en, d_rhs, eb))
+    return kkt_refuse(who, "overlap — d_sol, d_rhs and d_norms may not overlap");
+  if (!k->factored) return fail(IEM_E_ARG, kNoFactorisation);
+  return IEM_OK;
+}
+// solve, then `steps` times residual, solve of it, add; the norms in front of every step and behind the last
+int kkt_refined_columns(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c,
+                        int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol, int steps, double *d_norms) {
+  iem_model *m = k->m;
+  DevGuard dg_(m->device);
+  int rc = kkt_refine_workspace(k, nrhs);
+  if (rc) return rc;
+  const int64_t n = k->L.nvar + k->L.ncon;
+  double *r = k->w_ref + (int64_t)k->ref_cols * n, *dsol = k->w_ref + 2 * (int64_t)k->ref_cols * n;
+  // slab by slab (the columns do not interact, and the chunks of the solve inside a slab are those of the whole set)
+  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
+    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
+    const double *rhs = d_rhs + (int64_t)c0 * ld_rhs;
+    double *sol = d_sol + (int64_t)c0 * ld_sol;
+    auto residual = [&](int i) {
+      return kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, rhs, ld_rhs, sol, ld_sol, r, n, d_norms ? d_norms + (int64_t)i * nrhs + c0 : nullptr);
+    };
+    if ((rc = kkt_solve_columns(k, nr, rhs, ld_rhs, sol, ld_sol))) return rc;
+    for (int i = 0; i < steps; ++i) {
+      if ((rc = residual(i))) return rc;
+      if ((rc = kkt_solve_columns(k, nr, r, n, dsol, n))) return rc;
+      struct { double *sol; const double *d; long long n, ld_s, ld_d; } A{sol, dsol, (long long)n, (long long)ld_sol, (long long)n};
+      if ((rc = kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_AXPY], &A, sizeof A, kkt_stream_grid(n), 256, nr))) return rc;
+    }
+    if (d_norms && (rc = residual(steps))) return rc;
+  }
+  return IEM_OK;
+}
 }  // namespace
 
 int iem_kkt_diag_source(char **out_src, uint64_t *out_key) { return fixed_source_out(F_KDIAG, out_src, out_key); }
 
+int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol) {
+  const int64_t n = k ? k->L.nvar + k->L.ncon : 0;
+  int rc = kkt_solve_refusals("iem_kkt_solve", k, 1, d_rhs, n, d_sol, n);
+  return rc ? rc : kkt_solve_columns(k, 1, d_rhs, n, d_sol, n);
+}
+
+int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol) {
+  int rc = kkt_solve_refusals("iem_kkt_solve_many", k, nrhs, d_rhs, ld_rhs, d_sol, ld_sol);
+  return rc ? rc : kkt_solve_columns(k, nrhs, d_rhs, ld_rhs, d_sol, ld_sol);
+}
+
+int iem_kkt_residual(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
+                     const double *d_rhs, const double *d_sol, double *d_r, double *d_norm) {
+  const int64_t n = k ? k->L.nvar + k->L.ncon : 0;
+  int rc = kkt_residual_refusals("iem_kkt_residual", k, 1, d_rhs, n, d_sol, n, d_r, n, d_norm);
+  return rc ? rc : kkt_residual_columns(k, d_x, d_y, obj_weight, d_sigma, nullptr, delta_w, delta_c, 1, d_rhs, n, d_sol, n, d_r, n, d_norm);
+}
+
+int iem_kkt_solve_refined(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, double delta_w, double delta_c,
+                          const double *d_rhs, double *d_sol, int steps, double *d_norms) {
+  const int64_t n = k ? k->L.nvar + k->L.ncon : 0;
+  int rc = kkt_refined_refusals("iem_kkt_solve_refined", k, 1, d_rhs, n, d_sol, n, steps, d_norms);
+  return rc ? rc : kkt_refined_columns(k, d_x, d_y, obj_weight, d_sigma, nullptr, delta_w, delta_c, 1, d_rhs, n, d_sol, n, steps, d_norms);
+}
+
 int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac, const double *d_sigma, const double *d_dcon, double delta_w, double delta_c) {
   if (!k || (!d_hess && k->n_h) || (!d_jac && k->n_j)) return fail(IEM_E_ARG, "null argument");
-  if (!d_dcon || k->L.ncon == 0) return iem_kkt_assemble(k, d_hess, d_jac, d_sigma, delta_w, delta_c);      // no per-row part: kkt_gather as it is
   iem_model *m = k->m;
   DevGuard dg_(m->device);
-  int rc = kkt_diag_setup(k, false);
-  if (rc) return rc;
   const iem::KktLayout &L = k->L;
   HIP_TRY(hipMemsetAsync(k->d_flat, 0, (size_t)L.total() * 8, m->stream));
   struct { double *flat; const long long *dest; const unsigned *seg, *perm; const double *hess, *jac, *sigma, *dcon; double dw, dc; long long n_dest, n_h, n_j, n_var, n_con; } A{
@@ -3798,61 +3792,14 @@ int iem_kkt_assemble_diag(iem_kkt *k, const double *d_hess, const double *d_jac,
 
 int iem_kkt_residual_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w,
                           double delta_c, int nrhs, const double *d_rhs, int64_t ld_rhs, const double *d_sol, int64_t ld_sol, double *d_r, int64_t ld_r, double *d_norms) {
-  if (!k || !d_rhs || !d_sol || !d_r) return fail(IEM_E_ARG, "null argument");
-  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_residual_diag: nrhs must be at least 1");
-  iem_model *m = k->m;
-  const int64_t n = k->L.nvar + k->L.ncon;
-  if (ld_rhs < n || ld_sol < n || ld_r < n) return fail(IEM_E_ARG, "iem_kkt_residual_diag: a leading dimension is shorter than nvar + ncon");
-  const int64_t er = kkt_extent(nrhs, ld_r, n), eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n);
-  if (kkt_overlap(d_r, er, d_sol, es) || (!(d_r == d_rhs && ld_r == ld_rhs) && kkt_overlap(d_r, er, d_rhs, eb)) || kkt_overlap(d_r, er, d_norms, nrhs) ||
-      kkt_overlap(d_norms, nrhs, d_sol, es) || kkt_overlap(d_norms, nrhs, d_rhs, eb))
-    return fail(IEM_E_ARG, "iem_kkt_residual_diag: overlap — d_r overlaps d_sol or d_rhs (allowed: d_r == d_rhs with ld_r == ld_rhs), or d_norms lies inside the vectors");
-  DevGuard dg_(m->device);
-  int rc = kkt_diag_setup(k, true);
-  if (rc) return rc;
-  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
-    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
-    if ((rc = kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, d_rhs + (int64_t)c0 * ld_rhs, ld_rhs, d_sol + (int64_t)c0 * ld_sol, ld_sol,
-                                d_r + (int64_t)c0 * ld_r, ld_r, d_norms ? d_norms + c0 : nullptr)))
-      return rc;
-  }
-  return IEM_OK;
+  int rc = kkt_residual_refusals("iem_kkt_residual_diag", k, nrhs, d_rhs, ld_rhs, d_sol, ld_sol, d_r, ld_r, d_norms);
+  return rc ? rc : kkt_residual_columns(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nrhs, d_rhs, ld_rhs, d_sol, ld_sol, d_r, ld_r, d_norms);
 }
 
 int iem_kkt_solve_refined_diag(iem_kkt *k, const double *d_x, const double *d_y, double obj_weight, const double *d_sigma, const double *d_dcon, double delta_w,
                                double delta_c, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol, int steps, double *d_norms) {
-  if (!k || !d_rhs || !d_sol) return fail(IEM_E_ARG, "null argument");
-  if (nrhs < 1) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: nrhs must be at least 1");
-  if (steps < 0) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: steps must not be negative");
-  const int64_t n = k->L.nvar + k->L.ncon;
-  if (ld_rhs < n || ld_sol < n) return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: a leading dimension is shorter than nvar + ncon");
-  const int64_t eb = kkt_extent(nrhs, ld_rhs, n), es = kkt_extent(nrhs, ld_sol, n), en = (int64_t)(steps + 1) * nrhs;
-  if (kkt_overlap(d_sol, es, d_rhs, eb) || kkt_overlap(d_norms, en, d_sol, es) || kkt_overlap(d_norms, en, d_rhs, eb))
-    return fail(IEM_E_ARG, "iem_kkt_solve_refined_diag: overlap — d_sol, d_rhs and d_norms may not overlap");
-  if (!k->factored) return fail(IEM_E_ARG, "iem_kkt_solve: no factorisation (iem_kkt_assemble + iem_kkt_factor first)");
-  iem_model *m = k->m;
-  DevGuard dg_(m->device);
-  int rc = kkt_diag_setup(k, true);
-  if (rc) return rc;
-  double *r = k->w_diag + (int64_t)KKT_DIAG_SLAB * n, *dsol = k->w_diag + 2 * (int64_t)KKT_DIAG_SLAB * n;
-  // slab by slab (the columns do not interact, and the chunks of iem_kkt_solve_many inside a slab are those of the whole set)
-  for (int c0 = 0; c0 < nrhs; c0 += KKT_DIAG_SLAB) {
-    const int nr = std::min(KKT_DIAG_SLAB, nrhs - c0);
-    const double *rhs = d_rhs + (int64_t)c0 * ld_rhs;
-    double *sol = d_sol + (int64_t)c0 * ld_sol;
-    auto residual = [&](int i) {
-      return kkt_residual_slab(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nr, rhs, ld_rhs, sol, ld_sol, r, n, d_norms ? d_norms + (int64_t)i * nrhs + c0 : nullptr);
-    };
-    if ((rc = iem_kkt_solve_many(k, nr, rhs, ld_rhs, sol, ld_sol))) return rc;
-    for (int i = 0; i < steps; ++i) {
-      if ((rc = residual(i))) return rc;
-      if ((rc = iem_kkt_solve_many(k, nr, r, n, dsol, n))) return rc;
-      struct { double *sol; const double *d; long long n, ld_s, ld_d; } A{sol, dsol, (long long)n, (long long)ld_sol, (long long)n};
-      if ((rc = kkt_launch_raw(m, m->fixed[F_KDIAG].fn[KDIAG_AXPY], &A, sizeof A, kkt_stream_grid(n), 256, nr))) return rc;
-    }
-    if (d_norms && (rc = residual(steps))) return rc;
-  }
-  return IEM_OK;
+  int rc = kkt_refined_refusals("iem_kkt_solve_refined_diag", k, nrhs, d_rhs, ld_rhs, d_sol, ld_sol, steps, d_norms);
+  return rc ? rc : kkt_refined_columns(k, d_x, d_y, obj_weight, d_sigma, d_dcon, delta_w, delta_c, nrhs, d_rhs, ld_rhs, d_sol, ld_sol, steps, d_norms);
 }
 
 /* ---- the interior-point barrier layer: what sits between the evaluation calls and the KKT object (csrc/iem_barrier_device.h) ---- */

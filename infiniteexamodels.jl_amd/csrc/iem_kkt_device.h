@@ -648,7 +648,7 @@ __device__ __forceinline__ double kkt_tdot(const double *__restrict__ M, const d
 }
 // forward, level l:   eliminated  z_i = D_i^-1 r_i,  rBp_i = Z_i' r_i ;
 //                     survivors   r_j[R] -= BR_p (D_p^-1 r_p)[C] ,  r_j[C] -= Bt_q' (D_q^-1 r_q)[R]      (64 threads per block)
-// TWINS: kkt_forward_m / kkt_backward_m (and kkt_fz_m / kkt_fs_m / kkt_bw_m, kkt_move_m, kkt_colsum_m) in csrc/iem_kkt_many_device.h repeat
+// TWINS: kkt_forward_m / kkt_backward_m (and kkt_fz_m / kkt_fs_m / kkt_bw_m) in csrc/iem_kkt_many_device.h repeat
 // these kernels' operations per column IN THE SAME ORDER — a column of iem_kkt_solve_many is bit for bit iem_kkt_solve of it
 // (tests/test_gpu_kkt_solve_many.py).  Any change to the arithmetic or its order here has to be made there as well.
 extern "C" __global__ __launch_bounds__(64) void kkt_forward(const KktSolveArgs A) {
@@ -862,52 +862,6 @@ extern "C" __global__ __launch_bounds__(64) void kkt_bw(const KktSolveArgs A) {
   A.r[i * KKT_NB + li] = acc;
 }
 #endif
-
-// ---- the solver-facing entry points (iem_kkt_assemble / _solve): blocks from the COO values, right-hand sides in and out ----
-// flat[dest[i]] = sum over k in [seg[i], seg[i + 1]) of the source perm[k] — an index into the virtual array
-//   hess values | jac values | (sigma + delta_w) per variable | -delta_c per row | 1.0 (the padding's unit diagonal)
-struct KktGatherArgs {
-  double *flat;
-  const long long *dest;
-  const unsigned *seg, *perm;
-  const double *hess, *jac, *sigma;
-  double dw, dc;
-  long long n_dest, n_h, n_j, n_var, n_con;
-};
-extern "C" __global__ __launch_bounds__(256) void kkt_gather(const KktGatherArgs A) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= A.n_dest) return;
-  double acc = 0.0;
-  for (unsigned k = A.seg[i]; k < A.seg[i + 1]; ++k) {
-    long long s = A.perm[k];
-    double v;
-    if (s < A.n_h) v = A.hess[s];
-    else if ((s -= A.n_h) < A.n_j) v = A.jac[s];
-    else if ((s -= A.n_j) < A.n_var) v = (A.sigma ? A.sigma[s] : 0.0) + A.dw;
-    else if ((s -= A.n_var) < A.n_con) v = -A.dc;
-    else v = 1.0;
-    acc += v;
-  }
-  A.flat[A.dest[i]] = acc;
-}
-// r[pos[i]] = rhs[idx[i]]  (into the chain / the border)   and back:  sol[idx[i]] = r[pos[i]]
-struct KktMoveArgs { double *dst; const double *src; const long long *di, *si; long long n; };
-extern "C" __global__ __launch_bounds__(256) void kkt_move(const KktMoveArgs A) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i < A.n) A.dst[A.di[i]] = A.src[A.si[i]];
-}
-// column sums of a rows x w matrix (per-block border terms): workgroup b sums the rows of chunk b / ncc for the 256 columns of
-// chunk b % ncc (ncc = ceil(w / 256)) into out[chunk][column]; a second launch over the partials leaves one row
-struct KktSumArgs { const double *in; double *out; long long rows, w, rows_per_wg; };
-extern "C" __global__ __launch_bounds__(256) void kkt_colsum(const KktSumArgs A) {
-  const long long ncc = (A.w + 255) / 256, rc = (long long)blockIdx.x / ncc, cc = (long long)blockIdx.x % ncc;
-  const long long c = cc * 256 + threadIdx.x;
-  if (c >= A.w) return;
-  const long long r0 = rc * A.rows_per_wg, r1 = r0 + A.rows_per_wg < A.rows ? r0 + A.rows_per_wg : A.rows;
-  double acc = 0.0;
-  for (long long r = r0; r < r1; ++r) acc += A.in[r * A.w + c];
-  A.out[rc * A.w + c] = acc;
-}
 
 // ---- span-sparse border columns of a laned chain (kkt_chain.HubChainKKT; pandemic 5 000 x 100: u(t) as 5 000 hubs) --------------
 // A block alive at level s (time t = a s, a = its index among the blocks alive) carries border columns for the hubs

@@ -1,17 +1,21 @@
-// iem_kkt_diag_device.h — the kernels of iem_kkt_assemble_diag / iem_kkt_residual_diag / iem_kkt_solve_refined_diag: the KKT
-// object with a PER-ROW diagonal in the constraint block,  K = [W + diag(sigma) + delta_w I, J'; J, −diag(dcon + delta_c)],  and
-// its residual / refinement over several columns.  A code object of its own (no other source key knows of it), compiled with
-// -ffp-contract=off: every line below is the order of operations of the contract in include/iem.h.
+// iem_kkt_diag_device.h — the finishing kernels of the KKT object (iem_kkt_assemble* / iem_kkt_residual* / iem_kkt_solve_refined*):
+// K = [W + diag(sigma) + delta_w I, J'; J, −diag(dcon + delta_c)]  with an optional PER-ROW diagonal dcon in the constraint block,
+// its residual and its refinement over one or several columns.  A code object of its own (no other source key knows of it), compiled
+// with -ffp-contract=off: every line below is the order of operations of the contract in include/iem.h.
 //
-//   kkt_gather_d:    kkt_gather (csrc/iem_kkt_device.h) with ONE change: the per-row source is −(dcon[row] + delta_c) — one
-//                    rounded add, then the negation.  The segment loop, its order and every other source are kkt_gather's.
+//   kkt_gather_d:    the dense blocks from the COO values.  flat[dest[i]] = sum over k in [seg[i], seg[i + 1]) of the source perm[k]
+//                    — an index into the virtual array
+//                      hess values | jac values | (sigma + delta_w) per variable | per constraint row | 1.0 (the padding's unit diagonal)
+//                    summed from 0.0 in the order of the segment.  The per-row source is −delta_c without dcon and
+//                    −(dcon[row] + delta_c) with it — one rounded add, then the negation, so that dcon ≡ d, delta_c = 0 gives the
+//                    bits of delta_c = d.
 //   kkt_residual_dm: entries x columns (blockIdx.y = column u, at base + u·ld).  p = K0·sol from iem_kktprod, then per entry
 //                      i <  nvar:  r = rhs − (p + ((sigma ? sigma[i] : 0) + delta_w)·sol)
 //                      i >= nvar:  d = dcon ? dcon[i − nvar] + delta_c : delta_c,   r = rhs − (p − d·sol)
 //                    and, where asked for, max |r| of the column into norms[u]: the bit pattern of a non-negative double orders as
 //                    an unsigned 64-bit integer (a NaN's lies above every finite one), so the maximum is taken on the patterns —
-//                    per lane, across the wave by shuffles, across waves by ONE integer atomicMax per wave (the scheme of
-//                    kkt_residual).  No float atomic, no order dependence; norms is zeroed by the runtime in front of the launch.
+//                    per lane, across the wave by shuffles, across waves by ONE integer atomicMax per wave.  No float atomic, no order
+//                    dependence: the result is bitwise reproducible.  norms is zeroed by the runtime in front of the launch.
 //   kkt_axpy_m:      sol[u·ld_s + i] = sol[u·ld_s + i] + d[u·ld_d + i]  (one rounded add per entry)
 //
 // One thread takes the entries i, i + stride, ... of its column: plain vector loads and stores.
@@ -20,7 +24,7 @@ struct KktGatherDArgs {
   double *flat;
   const long long *dest;
   const unsigned *seg, *perm;
-  const double *hess, *jac, *sigma, *dcon;   // sigma: nvar entries or null;  dcon: ncon entries (never null here)
+  const double *hess, *jac, *sigma, *dcon;   // sigma: nvar entries or null;  dcon: ncon entries or null
   double dw, dc;
   long long n_dest, n_h, n_j, n_var, n_con;
 };
@@ -35,7 +39,7 @@ extern "C" __global__ __launch_bounds__(256) void kkt_gather_d(const KktGatherDA
     if (s < A.n_h) v = A.hess[s];
     else if ((s -= A.n_h) < A.n_j) v = A.jac[s];
     else if ((s -= A.n_j) < A.n_var) v = (A.sigma ? A.sigma[s] : 0.0) + A.dw;
-    else if ((s -= A.n_var) < A.n_con) v = -(A.dcon[s] + A.dc);
+    else if ((s -= A.n_var) < A.n_con) v = A.dcon ? -(A.dcon[s] + A.dc) : -A.dc;
     else v = 1.0;
     acc += v;
   }

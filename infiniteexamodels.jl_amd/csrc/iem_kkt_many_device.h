@@ -428,7 +428,8 @@ extern "C" __global__ __launch_bounds__(64) void kkt_bw_m(const KktSolveManyArgs
 #endif
 
 // ---- right-hand sides in and out, border terms ---------------------------------------------------------------------------------
-// dst[di[i] + u ldd] = src[si[i] + u lds]  for the nr columns of a chunk (kkt_move per column; the index pair loaded once)
+// Right-hand sides into the chain's block order (and the border's) and the solutions back:  dst[di[i] + u ldd] = src[si[i] + u lds]
+// for the nr columns of a chunk — a thread per index pair, loaded once for all columns
 struct KktMoveManyArgs { double *dst; const double *src; const long long *di, *si; long long n, ldd, lds; int nr; };
 extern "C" __global__ __launch_bounds__(256) void kkt_move_m(const KktMoveManyArgs A) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -436,8 +437,11 @@ extern "C" __global__ __launch_bounds__(256) void kkt_move_m(const KktMoveManyAr
   const long long d = A.di[i], s = A.si[i];
   for (int u = 0; u < A.nr; ++u) A.dst[d + u * A.ldd] = A.src[s + u * A.lds];
 }
-// kkt_colsum for every column of a chunk in one launch: workgroups [u wgs, (u + 1) wgs) do what kkt_colsum's grid does, on the
-// matrix in + u in_ld into out + u out_ld (the same partial sums in the same order)
+// Column sums of `rows x w` matrices (the per-block border terms), one matrix per column of a chunk: matrix u sits at in + u in_ld
+// and is served by the workgroups [u wgs, (u + 1) wgs).  Workgroup b of a matrix sums the rows of chunk b / ncc (rows_per_wg rows,
+// from 0.0 in row order) for the 256 columns of chunk b % ncc (ncc = ceil(w / 256)) into out[u out_ld + chunk w + column]; a second
+// launch over the partials leaves one row (kkt_border_sums in csrc/iem_api.cpp).  The order of the additions is fixed: the sums are
+// bitwise reproducible, and kkt_border_colsum (csrc/iem_kkt_border_device.h) forms the same ones.
 struct KktSumManyArgs { const double *in; double *out; long long rows, w, rows_per_wg, in_ld, out_ld, wgs; };
 extern "C" __global__ __launch_bounds__(256) void kkt_colsum_m(const KktSumManyArgs A) {
   const long long u = (long long)blockIdx.x / A.wgs, bx = (long long)blockIdx.x - u * A.wgs;

@@ -499,9 +499,6 @@ class ChainKKT:
         self._rows, self._cols = torch.as_tensor(rt, device=dev), torch.as_tensor(ct, device=dev)
         self.Z, self.Gp = torch.empty(max(S * nb * ne, 1), **f64), torch.empty(max(S * ne * ne, 1), **f64)
         self.info = torch.zeros(3, dtype=torch.int64, device=dev)
-        self._r = torch.zeros(S * nb, **f64)
-        self._z = torch.empty(S * nb if L.reach > 0 else 1, **f64)
-        self._rBp = torch.empty(max(S * ne, 1), **f64)
         on, pos, border = L.positions()
         self._on, self._pos, self._border = (torch.as_tensor(a, device=dev) for a in (on, pos, border))
         self._glu = None
@@ -556,23 +553,11 @@ class ChainKKT:
         ``rhs`` may also be 2-D, ``(nvar + ncon, K)`` with columns of any stride: the K columns go through the levels
         together (``iem_kkt_chain_solve_many``: the factors are read once per chunk of columns, not once per column) and
         the result has the same shape.  Refinement is per column — with ``"auto"`` a column stops when ITS residual is
-        under ITS bound — and column ``j`` carries the bits ``solve(rhs[:, j])`` gives."""
+        under ITS bound — and column ``j`` carries the bits ``solve(rhs[:, j])`` gives: a 1-D ``rhs`` IS the one-column case."""
         mv = self._matvec if operator is None else operator.matvec
         if rhs.dim() == 2:
             return self._solve_many(rhs, refine, rtol, mv)
-        x = self._solve_once(rhs)
-        if refine == "auto":
-            bound = rtol * max(1.0, float(rhs.abs().max().item()))
-            for _ in range(2):
-                res = rhs - mv(x)
-                if float(res.abs().max().item()) <= bound:
-                    break
-                x = x + self._solve_once(res)
-            return x
-        for _ in range(int(refine)):
-            res = rhs - mv(x)
-            x = x + self._solve_once(res)
-        return x
+        return self._solve_many(rhs.unsqueeze(1), refine, rtol, mv)[:, 0]
 
     def _solve_many(self, rhs, refine, rtol, mv=None):
         t = self._torch
@@ -599,8 +584,9 @@ class ChainKKT:
     _MANY_SLAB = 8      # columns per pass of _solve_once_many (a multiple of every chunk width of the kernels)
 
     def _solve_once_many(self, B):
-        """``_solve_once`` for the rows of ``B`` (K, n); row for row the same arithmetic.  The rows go through in slabs of
-        ``_MANY_SLAB``: the block-ordered workspace (r, z, rBp) is at most that many columns, however large K is."""
+        """One pass through the factors for the rows of ``B`` (K, n): right-hand sides into block order, the levels forward, the
+        border system, the levels backward, solutions back — a row's bits do not depend on the other rows.  The rows go through
+        in slabs of ``_MANY_SLAB``: the block-ordered workspace (r, z, rBp) is at most that many columns, however large K is."""
         if B.shape[0] > self._MANY_SLAB:
             return self._torch.cat([self._solve_once_many(B[c0:c0 + self._MANY_SLAB]) for c0 in range(0, B.shape[0], self._MANY_SLAB)])
         t, L, m = self._torch, self.layout, self.model
@@ -624,7 +610,7 @@ class ChainKKT:
             _lib.check(m._L.iem_kkt_border_solve(m._h, L.S, L.ne, L.n_border, K, p(self._F), p(self._piv), p(rBp), p(rB), p(xB)))
         elif L.ne:
             xB = t.empty(K, L.ne, **f64)
-            for j in range(K):                         # (the border system per column, with the expressions of _solve_once: the same bits)
+            for j in range(K):                         # (the border system per column: a column's bits do not depend on K)
                 rB = t.zeros(L.ne, **f64)
                 rB[:L.n_border] = B[j][self._border]
                 rB = rB - rBp[j][:L.S * L.ne].view(L.S, L.ne).sum(0)
@@ -647,34 +633,6 @@ class ChainKKT:
         nl = int(self._long_rows.numel())
         _lib.check(m._L.iem_csr_spmv(m._h, k.n, p(k.rowptr), p(k.colind), p(k.vals), p(x), p(y), nl, p(self._long_rows) if nl else None))
         return y
-
-    def _solve_once(self, rhs):
-        t, L, m = self._torch, self.layout, self.model
-        r = self._r
-        r.zero_()
-        r[self._pos] = rhs[self._on]
-        m._sync_stream()
-        p = lambda a: C.c_void_p(a.data_ptr())
-        chained = L.reach > 0
-        args = (m._h, L.S, L.nb, L.ne, L.nc, p(self.D), p(self.B) if chained else None, p(self.BR) if chained else None,
-                p(self._rows) if chained else None, p(self._cols) if chained else None, p(self.Z), p(r), p(self._z) if chained else None, p(self._rBp))
-        xB = None
-        _lib.check(m._L.iem_kkt_chain_solve(*args, None, 0))
-        if L.ne and self.border == "device":
-            xB, rB = t.empty(L.ne, dtype=t.float64, device=r.device), t.zeros(L.ne, dtype=t.float64, device=r.device)
-            rB[:L.n_border] = rhs[self._border]
-            _lib.check(m._L.iem_kkt_border_solve(m._h, L.S, L.ne, L.n_border, 1, p(self._F), p(self._piv), p(self._rBp), p(rB), p(xB)))
-        elif L.ne:
-            rB = t.zeros(L.ne, dtype=t.float64, device=r.device)
-            rB[:L.n_border] = rhs[self._border]
-            rB = rB - self._rBp[:L.S * L.ne].view(L.S, L.ne).sum(0)
-            xB = t.linalg.lu_solve(*self._glu, rB.unsqueeze(1)).squeeze(1).contiguous()
-        _lib.check(m._L.iem_kkt_chain_solve(*args, p(xB) if xB is not None else None, 1))
-        out = t.empty_like(rhs)
-        out[self._on] = r[self._pos]
-        if L.ne:
-            out[self._border] = xB[:L.n_border]
-        return out
 
 
 class HubChainKKT:

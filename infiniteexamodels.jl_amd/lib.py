@@ -94,7 +94,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_residual_source", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -220,7 +220,6 @@ def lib():
     L.iem_kkt_solve_many.argtypes = [vp, i32, vp, i64, vp, i64]
     L.iem_kkt_residual.argtypes = [vp, vp, vp, dbl, vp, dbl, dbl, vp, vp, vp, vp]
     L.iem_kkt_solve_refined.argtypes = [vp, vp, vp, dbl, vp, dbl, dbl, vp, vp, i32, vp]
-    L.iem_kkt_residual_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_kkt_assemble_diag.argtypes = [vp, vp, vp, vp, vp, dbl, dbl]
     L.iem_kkt_residual_diag.argtypes = [vp, vp, vp, dbl, vp, vp, dbl, dbl, i32, vp, i64, vp, i64, vp, i64, vp]
     L.iem_kkt_solve_refined_diag.argtypes = [vp, vp, vp, dbl, vp, vp, dbl, dbl, i32, vp, i64, vp, i64, i32, vp]
@@ -346,14 +345,9 @@ def kkt_source(nb: int, ne: int, nc: int = 12):
     return _source(lib().iem_kkt_source, int(nb), int(ne), int(nc))
 
 
-def kkt_residual_source():
-    """HIP source of the finishing kernels of ``iem_kkt_residual`` / ``iem_kkt_solve_refined`` and its cache key."""
-    return _source(lib().iem_kkt_residual_source)
-
-
 def kkt_diag_source():
-    """HIP source of the per-row diagonal's kernels (``kkt_gather_d`` / ``kkt_residual_dm`` / ``kkt_axpy_m``: ``iem_kkt_assemble_diag``,
-    ``iem_kkt_residual_diag``, ``iem_kkt_solve_refined_diag``) and its cache key."""
+    """HIP source of the KKT object's own kernels (``kkt_gather_d`` / ``kkt_residual_dm`` / ``kkt_axpy_m``: ``iem_kkt_assemble*``,
+    ``iem_kkt_residual*``, ``iem_kkt_solve_refined*``) and its cache key."""
     return _source(lib().iem_kkt_diag_source)
 
 

@@ -10,7 +10,7 @@ REL = 1e-14
 
 
 def colsum(a):
-    """Column sums of a (rows, w) array as ``kkt_colsum`` forms them: up to 512 chunks of rows, each summed from 0.0 in row
+    """Column sums of a (rows, w) array as ``kkt_colsum_m`` / ``kkt_border_colsum`` form them: up to 512 chunks of rows, each summed from 0.0 in row
     order, then the partial rows summed from 0.0 in chunk order."""
     a = np.asarray(a, dtype=np.float64)
     rows, w = a.shape

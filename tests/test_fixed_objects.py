@@ -7,7 +7,6 @@ import pytest
 
 # the kernels the per-object source tests look for (test_kktprod.py, test_kkt_diag.py, test_kkt_border.py, test_barrier.py)
 KERNELS = {
-    "kkt_residual": ("kkt_residual", "kkt_axpy1"),
     "kkt_diag": ("kkt_gather_d", "kkt_residual_dm", "kkt_axpy_m"),
     "kkt_border": ("kkt_border_ldl", "kkt_border_solve", "kkt_border_colsum", "kkt_border_inertia"),
     "barrier": ("barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"),
@@ -21,12 +20,11 @@ def fnv1a64(text: str) -> int:
     return h
 
 
-def test_the_list_is_the_four_named_sources(built):
+def test_the_list_is_the_three_named_sources(built):
     from infiniteexamodels.jl_amd import lib as iemlib
     listed = list(iemlib.fixed_sources())
     assert [name for name, _, _ in listed] == list(KERNELS)
-    named = dict(kkt_residual=iemlib.kkt_residual_source, kkt_diag=iemlib.kkt_diag_source, kkt_border=iemlib.kkt_border_source,
-                 barrier=iemlib.barrier_source)
+    named = dict(kkt_diag=iemlib.kkt_diag_source, kkt_border=iemlib.kkt_border_source, barrier=iemlib.barrier_source)
     for name, src, key in listed:
         assert (src, key) == named[name](), name
         assert key == fnv1a64(src), name
@@ -38,7 +36,7 @@ def test_the_list_is_the_four_named_sources(built):
     assert key == fnv1a64(src)
 
 
-@pytest.mark.parametrize("index", [-1, 4])
+@pytest.mark.parametrize("index", [-1, 3])
 def test_past_the_end_is_refused_and_writes_nothing(index, built):
     from infiniteexamodels.jl_amd import lib as iemlib
     L = iemlib.lib()
@@ -65,7 +63,7 @@ def test_precompile_source_wants_the_flag_line(built, tmp_path, monkeypatch):
     assert not (tmp_path / "kernels").exists()      # refused before anything is written
     # a source with the line is taken: its hipcc command carries the line's flags
     jobs = []
-    src, key = iemlib.kkt_residual_source()
+    src, key = iemlib.kkt_diag_source()
     out = iemlib.precompile_source(src, key, defer=jobs)
     assert out == str(tmp_path / "kernels" / f"iem_{key:016x}.hsaco") and len(jobs) == 1
     assert "-ffp-contract=off" in jobs[0][0] and "--offload-arch=gfx950" in jobs[0][0]

@@ -37,7 +37,7 @@ def nan(*shape):
 
 
 # ---- the low-level pair against the restatement ---------------------------------------------------------------------------------
-SHAPES = [(4, 3, 1), (12, 10, 3), (64, 61, 700), (68, 66, 3), (128, 125, 1)]      # (ne, n_border, S); 700 blocks: beyond kkt_colsum's 512 row chunks
+SHAPES = [(4, 3, 1), (12, 10, 3), (64, 61, 700), (68, 66, 3), (128, 125, 1)]      # (ne, n_border, S); 700 blocks: beyond the column sum's 512 row chunks
 
 
 def family(which, ne, nb_):

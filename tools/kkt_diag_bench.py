@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """What the per-row diagonal costs at assembly, and what the multi-column refined solve costs per column, on one KKT object.
 
-  a0  iem_kkt_assemble                                      scalar delta_c (kkt_gather)
-  a1  iem_kkt_assemble_diag with a vector dcon              kkt_gather_d: 8·ncon bytes more to read
+  a0  iem_kkt_assemble                                      scalar delta_c (kkt_gather_d without dcon)
+  a1  iem_kkt_assemble_diag with a vector dcon              the same kernel: 8·ncon bytes more to read
   b0  16 x iem_kkt_solve_refined(steps = 1)                 per column: solve, operator, finishing kernel, solve, add
   b1  iem_kkt_solve_refined_diag(nrhs = 16, steps = 1)      iem_kkt_solve_many for the solves, the same operator launches, one
                                                             finishing launch and one add per slab of 8 columns

@@ -1,5 +1,5 @@
 // source_calls_check.cpp — sanitizer harness for the source entry points (host only, no device): iem_fixed_source over the
-// indices -1 .. 4, the five named *_source calls and iem_emit_source on one blob — for each of the generator's nine programs,
+// indices -1 .. 3, the four named *_source calls and iem_emit_source on one blob — for each of the generator's nine programs,
 // selected through iem_set_option and reset afterwards, and for the six pairs of two program options at once, each refused with
 // its message — everything they return freed.  Build with
 //   g++ -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -std=c++17 -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
@@ -29,12 +29,12 @@ int main(int argc, char **argv) {
     if (src) iem_free(src);
   };
   std::vector<std::string> listed;
-  for (int i = -1; i <= 4; ++i) {
+  for (int i = -1; i <= 3; ++i) {
     const char *name = "(untouched)";
     char *src = nullptr;
     uint64_t key = 0;
     const int rc = iem_fixed_source(i, &name, &src, &key);
-    if (i < 0 || i >= 4) {
+    if (i < 0 || i >= 3) {
       const bool ok = rc == IEM_E_ARG && !src && key == 0 && std::strcmp(name, "(untouched)") == 0;
       std::printf("iem_fixed_source(%d)         rc %d  %s\n", i, rc, ok ? "refused, nothing written" : "BAD");
       if (!ok) ++bad;
@@ -45,13 +45,13 @@ int main(int argc, char **argv) {
     if (iem_fixed_source(i, nullptr, nullptr, nullptr) != IEM_OK) ++bad;      // every output is optional
   }
   typedef int (*named_t)(char **, uint64_t *);
-  const named_t named[4] = {iem_kkt_residual_source, iem_kkt_diag_source, iem_kkt_border_source, iem_barrier_source};
-  const char *names[4] = {"iem_kkt_residual_source", "iem_kkt_diag_source", "iem_kkt_border_source", "iem_barrier_source"};
-  for (int i = 0; i < 4; ++i) {
+  const named_t named[3] = {iem_kkt_diag_source, iem_kkt_border_source, iem_barrier_source};
+  const char *names[3] = {"iem_kkt_diag_source", "iem_kkt_border_source", "iem_barrier_source"};
+  for (int i = 0; i < 3; ++i) {
     char *src = nullptr;
     uint64_t key = 0;
     const int rc = named[i](&src, &key);
-    if (!src || listed.size() != 4 || listed[i] != src) { std::printf("%s differs from the listed source\n", names[i]); ++bad; }
+    if (!src || listed.size() != 3 || listed[i] != src) { std::printf("%s differs from the listed source\n", names[i]); ++bad; }
     report(names[i], rc, src, key);
   }
   {
