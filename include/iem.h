@@ -508,7 +508,9 @@ int iem_csr_spmv(iem_model *m, int64_t n, const int32_t *d_rowptr, const int32_t
  * d_Bt == NULL (and d_BR == d_rows == d_cols == d_z == NULL): the blocks couple to the border only (scenario blocks of a
  * two-stage problem) — one launch instead of the levels (ne = -1: no border and a kernel shape for ONE block per launch — the pivot
  * blocks of a dense block factorisation, S = 1).  nb: multiple of 4 in 4..96, ne: multiple of 4 in 0..128, nc: multiple
- * of 4 in 4..48, nc <= nb.  Asynchronous on the handle's stream. */
+ * of 4 in 4..48, nc <= nb — and, with a border, the LDS kkt_eliminate declares within the 163 840 bytes of a CU:
+ * 8 (2 16R 5 + 2 4 (16R + 1) + 64) + 8 + 8 nb (nb + 1) + 16 nb (ne + 1) with R = ceil(nb / 16) (ne up to 128 for nb <= 60, 64 at
+ * nb = 84, 44 at nb = 96); anything else is IEM_E_ARG, from iem_kkt_source as from every call here.  Asynchronous on the handle's stream. */
 int iem_kkt_chain_factor(iem_model *m, int64_t S, int nb, int ne, int nc, double *d_D, double *d_Bt, double *d_BR, const int32_t *d_rows,
                          const int32_t *d_cols, double *d_E, double *d_Z, double *d_Gp, int64_t *d_info, double tiny);
 /* ONE step of that reduction (no border), for a caller that interleaves work of its own between the levels — the span-sparse
@@ -632,7 +634,8 @@ int iem_kkt_solve(iem_kkt *k, const double *d_rhs, double *d_sol);
  * (sharing its factors across columns — GEMM for GEMV — is not done). */
 int iem_kkt_solve_many(iem_kkt *k, int nrhs, const double *d_rhs, int64_t ld_rhs, double *d_sol, int64_t ld_sol);
 
-/* HIP source of the solver's kernels for one (nb, ne, nc) and its cache key — for offline builds (no device needed; malloc'ed) */
+/* HIP source of the solver's kernels for one (nb, ne, nc) and its cache key — for offline builds (no device needed; malloc'ed).
+ * A shape iem_kkt_chain_factor refuses is refused here with the same IEM_E_ARG and the same message. */
 int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key);
 
 /* r = rhs − K sol  with  K = [W + diag(sigma) + delta_w I, J'; J, −delta_c I]  at (x, y, obj_weight) — matrix-free: iem_kktprod

@@ -2661,12 +2661,25 @@ std::string kkt_source(int nb, int ne, int nc) {
   s += kKktManySource;
   return s;
 }
-// LDS of kkt_eliminate: the panel buffers of the inverse, and with a border one NB x NB and two NB x NE tiles; of kkt_update:
-// seven NC x NC tiles
+// LDS the kernels of a shape DECLARE, from the quantities of csrc/iem_kkt_device.h.  kkt_eliminate, lane-per-row form: two pivot-row
+// buffers of KKT_BPW blocks and the two counters; panel form: the column and row panels of the inverse (two of each, 16 R rows of stride
+// KKT_LC = 5 and 4 rows of stride KKT_LP = 16 R + 1, R = ceil(nb / 16) tile rows — NOT nb: the rim is part of the buffers), the 2 x 32
+// doubles of the pivot blocks and the two counters, and with a border one NB x NB and two NB x NE tiles (strides nb + 1, ne + 1).
+// kkt_update: seven NC x NC tiles (and the two index tables, within the allowance).
+long long kkt_lds_eliminate(int nb, int ne) {
+  if (const int rpl = kkt_rowwise(nb, ne)) return 16LL * ((64 * kkt_row_wpg(nb, ne)) / (nb / rpl)) * nb + 8;
+  const long long R = (nb + 15) / 16;
+  return 8LL * (2 * 16 * R * 5 + 2 * 4 * (16 * R + 1) + 64) + 8 + (ne > 0 ? 8LL * nb * (nb + 1) + 16LL * nb * (ne + 1) : 0);
+}
 bool kkt_fits(int nb, int ne, int nc) {
-  const long long elim = 8LL * (10 * nb + 8 * (nb + 1)) + (ne > 0 ? 8LL * nb * (nb + 1) + 16LL * nb * (ne + 1) : 0) + 1024;
   const long long upd = 56LL * nc * (nc + 1) + 1024;
-  return elim <= 160 * 1024 && upd <= 160 * 1024;
+  return kkt_lds_eliminate(nb, ne) <= 160 * 1024 && upd <= 160 * 1024;
+}
+// The shapes a chain KKT code object exists for: what iem_kkt_source emits and kkt_module loads — one rule, one message
+int kkt_admit(int nb, int ne, int nc) {
+  if (nb < 4 || nb > 96 || nb % 4 || ne < -1 || ne > 128 || (ne > 0 && ne % 4) || nc < 4 || nc > 48 || nc % 4 || nc > nb || !kkt_fits(nb, ne, nc))
+    return fail(IEM_E_ARG, "chain KKT: block size must be a multiple of 4 in 4..96, border size a multiple of 4 in 0..128, coupling width a multiple of 4 in 4..48 (and <= the block size), tiles within the LDS of a CU");
+  return IEM_OK;
 }
 // The kernels of a chain KKT code object and where kkt_module keeps them.  `lane_rows_only`: the lane-per-row solves (csrc/iem_kkt_device.h:
 // kkt_fz / kkt_fs / kkt_bw, and their multi-column forms), resolved only for the shapes whose eliminate is lane-per-row too and nb <= 32:
@@ -2680,8 +2693,7 @@ const struct KktSlot { const char *name; hipFunction_t KM::*fn; bool lane_rows_o
     {"kkt_forward_m", &KM::fwd_m, false}, {"kkt_backward_m", &KM::bwd_m, false}, {"kkt_move_m", &KM::move_m, false}, {"kkt_colsum_m", &KM::colsum_m, false},
 };
 int kkt_module(iem_model *m, int nb, int ne, int nc, iem_model::KktMod **out) {
-  if (nb < 4 || nb > 96 || nb % 4 || ne < -1 || ne > 128 || (ne > 0 && ne % 4) || nc < 4 || nc > 48 || nc % 4 || nc > nb || !kkt_fits(nb, ne, nc))
-    return fail(IEM_E_ARG, "chain KKT: block size must be a multiple of 4 in 4..96, border size a multiple of 4 in 0..128, coupling width a multiple of 4 in 4..48 (and <= the block size), tiles within the LDS of a CU");
+  if (int rc = kkt_admit(nb, ne, nc)) return rc;
   auto it = m->kkt_mods.find({nb, ne * 64 + nc});
   if (it == m->kkt_mods.end()) {
     iem_model::KktMod km;
@@ -2728,7 +2740,10 @@ int kkt_launch_elim(iem_model *m, const iem_model::KktMod *km, KktArgsH a, long 
 }
 }  // namespace
 
-int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key) { return emit_out(kkt_source(nb, ne, nc), out_src, out_key); }
+int iem_kkt_source(int nb, int ne, int nc, char **out_src, uint64_t *out_key) {
+  if (int rc = kkt_admit(nb, ne, nc)) return rc;      // (what no handle would load has no source either: the CPU can sweep admission)
+  return emit_out(kkt_source(nb, ne, nc), out_src, out_key);
+}
 
 int iem_kkt_chain_factor(iem_model *m, int64_t S, int nb, int ne, int nc, double *d_D, double *d_Bt, double *d_BR, const int32_t *d_rows,
                          const int32_t *d_cols, double *d_E, double *d_Z, double *d_Gp, int64_t *d_info, double tiny) {

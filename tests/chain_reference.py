@@ -21,8 +21,9 @@ def fill_blocks(layout, rows, cols, vals):
     return (flat[oD:oB].reshape(S, nb, nb).copy(), B, flat[oE:oG].reshape(S, nb, ne).copy(), flat[oG:total].reshape(ne, ne).copy())
 
 
-def factor(D, B, E):
-    """In place on copies: returns (Dinv, X, Y, Z, Gp, negative pivots)."""
+def factor(D, B, E, pre=None):
+    """In place on copies: returns (Dinv, X, Y, Z, Gp, negative pivots).  `pre` (a dict): filled with every block as it stood when
+    it was inverted."""
     S, nb, _ = D.shape
     ne = E.shape[2]
     D, B, E = D.copy(), B.copy(), E.copy()
@@ -33,6 +34,8 @@ def factor(D, B, E):
         nonlocal neg
         # pivots of the un-pivoted elimination = those of LDL': count the negative ones
         M = D[i].copy()
+        if pre is not None:
+            pre[i] = M.copy()
         for k in range(nb):
             neg += M[k, k] < 0
             M[k + 1:, k + 1:] -= np.outer(M[k + 1:, k], M[k, k + 1:]) / M[k, k]

@@ -101,7 +101,10 @@ def test_keys_of_the_other_kkt_code_objects_did_not_move(built):
     """every KKT code object and the barrier object keep the key pinned in tests/golden/kkt_source_keys.json"""
     from infiniteexamodels.jl_amd import lib as iemlib
     want = json.load(open(GOLDEN))
-    assert set(want["iem_kkt_source"]) == {"40,0,12", "20,0,8", "20,112,4", "20,4,0", "96,-1,4"}
+    # (20,0,4 — the hub lanes' chains — stood here as "20,4,0": nb 20, ne 4, nc 0, a shape no handle loads; iem_kkt_source refuses it now)
+    assert set(want["iem_kkt_source"]) == {"40,0,12", "20,0,8", "20,112,4", "20,0,4", "96,-1,4"}
+    with pytest.raises(iemlib.IemError):
+        iemlib.kkt_source(20, 4, 0)
     for shape, key in want["iem_kkt_source"].items():
         assert f"{iemlib.kkt_source(*map(int, shape.split(',')))[1]:016x}" == key, shape
     assert set(want) == {"iem_kkt_source", "iem_kkt_border_source", "iem_kkt_diag_source", "iem_barrier_source"}
