@@ -784,6 +784,76 @@ int iem_barrier_merit(iem_barrier *b, const double *d_x, const double *d_s, cons
 /* HIP source of the six kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_barrier_source(char **out_src, uint64_t *out_key);
 
+/* ---- the filter line search ------------------------------------------------------------------------------------------------------
+ * The decision of an interior-point iteration on the device (csrc/iem_search_device.h), as an object beside iem_barrier: the slope of
+ * the barrier objective phi_mu = obj_weight·f − mu·sum log gap along the direction, the trial point, and the acceptance test of
+ * Waechter and Biegler 2006, Algorithm A, with its filter.  A ladder of K rungs
+ *     iem_search_begin;  K × { iem_search_trial, iem_obj_device, iem_cons, iem_barrier_merit, iem_search_accept };  iem_barrier_update
+ * needs no host decision and is graph-capturable: once a rung accepts, the later rungs recompute the same trial point and their
+ * accept call returns at its first test; iem_barrier_update moves nothing for alpha = +0.0, which is what a search without a step
+ * leaves in d_alpha[0].  The host reads one status word (iem_search_state, or its own copy of the block) when it likes.
+ *
+ * THE CONTROL BLOCK: sixteen 8-byte words on the device (iem_search_device gives the pointer; a host may write word 0 or word 9):
+ *     0 alpha (double)          1 alpha_max: the d_alpha[0] that begin saw      2 phi0 = obj_weight·f − mu·sum log gap      3 theta0
+ *     4 slope                   5 theta_min      6 theta_max                    7 phi of the last trial   8 theta of the last trial
+ *     9 status (int64): 0 SEARCHING, 1 accepted f-type, 2 accepted h-type, 3 FAILED, 4 UNUSABLE           10 trials (int64)
+ *     11 filter count (int64)   12 flags (int64): bit 0 = theta_min / theta_max are set, bit 1 = filter overflow        13–15 zero
+ * The filter: filter_capacity pairs (theta, phi) on the device, the first `filter count` of them in use.
+ *
+ * iem_search_begin: slope = sum of  t_i = (obj_weight·g_i + gb_i)·dx_i  over the variables and  t_j = gs_j·ds_j  over the inequality
+ *     rows (gb_i, gs_j of the barrier contract above: the same gaps, the same branches for absent bounds, the same rounding order;
+ *     equality rows are skipped, their ds entries never read); d_grad = grad f as iem_grad / iem_eval_accepted write it.  A lane adds its entries
+ *     in index order, the workgroups' totals are summed in the fixed order of the barrier sums: bitwise reproducible, no float
+ *     atomic.  The workgroup that arrives last fills words 0–4, 7–10 and 13–15: alpha = alpha_max = d_alpha[0], phi0 from d_obj[0] and
+ *     d_err[7], theta0 = d_err[6], trials = 0, words 7 and 8 NaN, status SEARCHING — or UNUSABLE with alpha = +0.0 when d_alpha[0] is not
+ *     > 0 (+0.0: the barrier layer's "unusable") or the slope is NaN.  While flag bit 0 is clear it sets theta_min = 1e-4·max(1, theta0),
+ *     theta_max = 1e4·max(1, theta0) and the bit.  The filter, its count and flag bit 1 stay.
+ * iem_search_trial:  xt = x + alpha·dx,  st = s + alpha·ds on inequality rows (equality rows' entries never written), alpha read from
+ *     the block; with status FAILED or UNUSABLE nothing is stored.
+ * iem_search_accept: ONE workgroup of 64 threads.  With a status other than SEARCHING it writes only d_alpha[0] — the accepted alpha,
+ *     or +0.0 for FAILED / UNUSABLE.  Otherwise, each operation rounded once:  theta_t = d_merit[0],  phi_t = obj_weight·ft − mu·d_merit[1];
+ *         admissible:  phi_t and theta_t finite, theta_t <= theta_max, and no filter entry (Ft, Fp) with theta_t >= Ft and phi_t >= Fp
+ *         switching:   slope < 0 and theta0 <= theta_min and alpha·pow(−slope, s_phi) > delta·pow(theta0, s_theta)
+ *         Armijo:      phi_t <= (phi0 + (eta_phi·alpha)·slope) + (10·2⁻⁵²)·|phi0|
+ *         sufficient:  theta_t <= (1 − gamma_theta)·theta0  or  phi_t <= phi0 − gamma_phi·theta0
+ *     admissible, switching, Armijo: accepted, status 1;  admissible, not switching, sufficient: accepted, status 2 — and then the filter
+ *     gains ((1 − gamma_theta)·theta0, phi0 − gamma_phi·theta0): the entries it dominates (both coordinates >=) leave first, the others
+ *     keep their order, the new entry is appended; a full filter sets flag bit 1 and appends nothing, the step still stands (entries
+ *     behind the count are not defined).  Accepted: d_alpha[0] = alpha.  Rejected: trials += 1, alpha = 0.5·alpha, d_alpha[0] = +0.0; if trials ==
+ *     max_trials or the new alpha < alpha_floor the status becomes FAILED and alpha +0.0.  Words 7, 8 take phi_t, theta_t either way.
+ *     d_alpha[1] (the dual step length) is never touched.
+ * iem_search_reset: a new barrier problem (mu changed): filter emptied, flags cleared — one asynchronous 16-byte memset.
+ * Every call runs on the handle's stream; begin, trial and accept are one launch each; nothing allocates after create, nothing
+ * synchronises and nothing is copied to the host, except by iem_search_state.  IEM_E_ARG before any device work: null required
+ * pointers (s, ds, st may be NULL without inequality rows), mu < 0, options out of range (gamma_theta, gamma_phi, eta_phi in (0, 1),
+ * delta > 0, s_theta > 1, s_phi >= 1, alpha_floor >= 0, max_trials >= 1, 1 <= filter_capacity <= 1024).  The object borrows the barrier object (bounds,
+ * flags, grid) and through it the model handle: destroy it before them.  Not here: the mu update, inertia correction, the second-order
+ * correction, Ipopt's alpha_min formula, restoration, sharded handles (iem_barrier_create refuses them). */
+typedef struct iem_search iem_search;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_search_opts_t) */
+  double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor;
+  int64_t max_trials, filter_capacity;
+} iem_search_opts_t;                    /* NULL = Ipopt's defaults: 1e-5, 1e-8, 1e-8, 1.0, 1.1, 2.3, 1e-16, 30, 64 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_search_state_t): at most that many bytes are written */
+  double alpha, alpha_max, phi0, theta0, slope, theta_min, theta_max, phi_trial, theta_trial;      /* words 0–8 of the block */
+  int64_t status, trials, filter_count, flags;                                                     /* words 9–12 */
+} iem_search_state_t;
+enum { IEM_SEARCH_SEARCHING = 0, IEM_SEARCH_F_TYPE = 1, IEM_SEARCH_H_TYPE = 2, IEM_SEARCH_FAILED = 3, IEM_SEARCH_UNUSABLE = 4 };
+int iem_search_create(iem_barrier *b, const iem_search_opts_t *opts, iem_search **out);
+int iem_search_destroy(iem_search *s);
+int iem_search_reset(iem_search *s);
+int iem_search_begin(iem_search *s, const double *d_x, const double *d_s, const double *d_grad, const double *d_sol, const double *d_ds,
+                     const double *d_obj, const double *d_err /* 8, of iem_barrier_error at this point */, const double *d_alpha /* 2 */,
+                     double mu, double obj_weight);
+int iem_search_trial(iem_search *s, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, double *d_xt, double *d_st);
+int iem_search_accept(iem_search *s, const double *d_ft, const double *d_merit /* 2 */, double mu, double obj_weight, double *d_alpha);
+int iem_search_device(const iem_search *s, void **d_control, double **d_filter /* filter_capacity pairs (theta, phi) */);
+int iem_search_state(iem_search *s, iem_search_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the three kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_search_source(char **out_src, uint64_t *out_key);
+
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache

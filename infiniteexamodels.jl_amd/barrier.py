@@ -187,3 +187,110 @@ class BarrierLayer:
                 self.close()
         except Exception:
             pass
+
+
+class FilterSearch:
+    """``FilterSearch(layer, **opts)``: the filter line search of the C-ABI (``iem_search_*``, ``csrc/iem_search_device.h``) beside a
+    :class:`BarrierLayer` — the filter and a control block of sixteen words on the device, three one-launch calls, no read-back but
+    :meth:`state`.  ``opts``: ``gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor, max_trials, filter_capacity``
+    (Ipopt's defaults).  One rung of the ladder, with ``xt, st, ct, ft, m`` buffers of the caller:
+
+        fs.begin(state, g, sol, dirs[0], obj, err, alpha, mu)          # obj: device tensor of one, err: bar.error(...) at this point
+        fs.trial(state, sol, dirs[0], xt, st)
+        model.obj_device(xt, out=ft); model.cons(xt, out=ct); bar.merit(xt, st, ct, out=m)
+        fs.accept(ft, m, mu, alpha)                                    # alpha[0]: the accepted step length, or +0.0
+        bar.update(state, sol, dirs, alpha, mu)
+
+    Once a rung accepts, later rungs recompute the same trial point and change nothing; a search without a step leaves ``alpha[0] =
+    +0.0``, for which ``update`` moves nothing.  ``reset()`` whenever ``mu`` changes."""
+
+    def __init__(self, layer: BarrierLayer, **opts):
+        self.layer = layer
+        self._s = None
+        o = _lib.SearchOpts.defaults(**opts)
+        self.opts = {name: getattr(o, name) for name, _ in _lib.SearchOpts._fields_ if name != "struct_size"}
+        L, b = layer._handle()
+        s = C.c_void_p()
+        _lib.check(L.iem_search_create(b, C.byref(o), C.byref(s)))
+        self._s = s
+
+    def _handle(self):
+        if self._s is None:
+            raise _lib.IemError("FilterSearch: closed")
+        L, _ = self.layer._handle()
+        return L, self._s
+
+    def begin(self, state, grad, sol, ds, obj, err, alpha, mu: float, obj_weight: float = 1.0):
+        """The slope of the barrier objective along ``sol = [dx; dy]``, ``ds`` and the control block of a new search
+        (``iem_search_begin``): ``obj`` a device tensor of one (``f``), ``err`` the eight numbers of ``BarrierLayer.error`` at this
+        point, ``alpha`` the device tensor of ``BarrierLayer.step``."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(grad, bar.nvar, "grad"), bar._vec(sol, bar.n, "sol"),
+                bar._vec(ds, bar.ncon, "ds", optional=slack), bar._vec(obj, 1, "obj"), bar._vec(err, 8, "err"), bar._vec(alpha, 2, "alpha"))
+        L, s = self._handle()
+        _lib.check(L.iem_search_begin(s, *args, float(mu), float(obj_weight)))
+
+    def trial(self, state, sol, ds, xt=None, st=None):
+        """``(xt, st) = (x + α·dx, s + α·ds)`` with the block's ``α`` (``iem_search_trial``); entries of ``st`` on equality rows keep
+        what the buffer held; nothing is stored once the search has failed."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        xt = xt if xt is not None else bar._new(bar.nvar)
+        st = st if st is not None else bar._new(bar.ncon)
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(sol, bar.n, "sol"),
+                bar._vec(ds, bar.ncon, "ds", optional=slack), bar._vec(xt, bar.nvar, "xt"), bar._vec(st, bar.ncon, "st", optional=slack))
+        L, s = self._handle()
+        _lib.check(L.iem_search_trial(s, *args))
+        return xt, st
+
+    def accept(self, ft, merit, mu: float, alpha, obj_weight: float = 1.0):
+        """The decision (``iem_search_accept``): ``ft`` a device tensor of one (``f`` at the trial point), ``merit`` the two numbers of
+        ``BarrierLayer.merit`` there; ``alpha[0]`` becomes the accepted step length or ``+0.0``.  Returns ``alpha``."""
+        bar = self.layer
+        args = (bar._vec(ft, 1, "ft"), bar._vec(merit, 2, "merit"), float(mu), float(obj_weight), bar._vec(alpha, 2, "alpha"))
+        L, s = self._handle()
+        _lib.check(L.iem_search_accept(s, *args))
+        return alpha
+
+    def reset(self):
+        """A new barrier problem (``mu`` changed): the filter emptied, the flags cleared (``iem_search_reset``)."""
+        L, s = self._handle()
+        _lib.check(L.iem_search_reset(s))
+
+    def state(self):
+        """THE read-back (``iem_search_state``, synchronises): the control block as a dict, ``status`` also by name."""
+        L, s = self._handle()
+        v = _lib.SearchState()
+        v.struct_size = C.sizeof(_lib.SearchState)
+        _lib.check(L.iem_search_state(s, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.SearchState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.SEARCH_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.SEARCH_STATUS) else "?"
+        return out
+
+    def device(self):
+        """``(control, filter)``: the addresses of the control block (16 words) and of the filter (``filter_capacity`` pairs) on the
+        device (``iem_search_device``)."""
+        L, s = self._handle()
+        ctl, flt = C.c_void_p(), C.c_void_p()
+        _lib.check(L.iem_search_device(s, C.byref(ctl), C.byref(flt)))
+        return ctl.value, flt.value
+
+    def close(self):
+        if self._s is not None:
+            _lib.check(self.layer.model._L.iem_search_destroy(self._s))
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass

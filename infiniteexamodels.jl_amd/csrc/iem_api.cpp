@@ -52,6 +52,9 @@ static const char *kKktBorderSource =     // the dense border on the device (kkt
 static const char *kBarrierSource =       // the interior-point barrier layer (iem_barrier_*): a code object of its own, behind the helpers of the device header (everything in front of its own kernels)
 #include "iem_barrier_device_h.inc"
     ;
+static const char *kSearchSource =        // the filter line search (iem_search_*): a code object of its own, behind the same helpers — not a row of kFixed
+#include "iem_search_device_h.inc"
+    ;
 
 namespace {
 
@@ -138,17 +141,19 @@ const struct FixedRow { const char *name, *text; bool behind_helpers; const char
     {"barrier", kBarrierSource, true, {"barrier_start", "barrier_terms", "barrier_step", "barrier_update", "barrier_error", "barrier_merit"}},      // iem_barrier_*
 };
 
-int fixed_source(Fixed f, std::string &s) {
+// the source of a hand-written code object: the prelude, the helpers of the device header where the text sits behind them, the text
+int object_source(const char *text, bool behind_helpers, std::string &s) {
   s = source_prelude("off");
-  if (kFixed[f].behind_helpers) {
+  if (behind_helpers) {
     const std::string hdr(kDeviceHeader);
     const size_t b = hdr.find("// IEM-TILE-REGION-END");
     if (b == std::string::npos) return fail(IEM_E_COMPILE, "internal: device header without tile-region markers");
     s += "#define IEM_TILE 256\n" + hdr.substr(0, b) + "#endif  // IEM_DEVICE_H (its kernels are not part of this code object)\n\n";
   }
-  s += kFixed[f].text;
+  s += text;
   return IEM_OK;
 }
+int fixed_source(Fixed f, std::string &s) { return object_source(kFixed[f].text, kFixed[f].behind_helpers, s); }
 
 // what every *_source entry point returns: a malloc'ed copy of the text and its cache key
 int emit_out(const std::string &s, char **out_src, uint64_t *out_key) {
@@ -310,6 +315,8 @@ struct iem_model {
   // the hand-written code objects of kFixed, each loaded by the first call that needs it (fixed_object): `mod` set = loaded, every
   // kernel of its row resolved
   struct FixedObject { hipModule_t mod = nullptr; hipFunction_t fn[kFixedSlots] = {}; } fixed[F_COUNT];
+  // the code object of the filter line search (iem_search_*): loaded by the first iem_search_create of the handle
+  struct SearchObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, trial = nullptr, accept = nullptr; } search;
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1349,6 +1356,7 @@ int iem_destroy(iem_model *m) {
   for (LoadedProgram &P : m->derived) release_program(P);
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
   for (auto &o : m->fixed) if (o.mod) hipModuleUnload(o.mod);
+  if (m->search.mod) hipModuleUnload(m->search.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -4054,6 +4062,192 @@ int iem_barrier_merit(iem_barrier *b, const double *d_x, const double *d_s, cons
   BarrierArgsH A = barrier_args(b);
   A.x = (double *)d_x; A.s = (double *)d_s; A.c = d_c; A.out = d_out;
   return barrier_launch(b, BAR_MERIT, A);
+}
+
+/* ---- the filter line search: slope, trial point, acceptance (csrc/iem_search_device.h) ---- */
+struct iem_search {
+  iem_barrier *b = nullptr;
+  iem_search_opts_t opt;
+  double *d_ctl = nullptr;             // the control block: 16 words
+  double *d_filter = nullptr;          // filter_capacity pairs (theta, phi)
+  double *d_red = nullptr;             // n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  long long *d_tab = nullptr;          // offs | first | count of iem_shared_totals
+};
+
+namespace {
+// SearchArgs of csrc/iem_search_device.h
+struct SearchArgsH {
+  const double *xl, *xu, *rl, *ru;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *g, *sol, *ds;
+  const double *obj, *err, *alpha_in;
+  double *xt, *st;
+  const double *ft, *merit;
+  double *alpha_out;
+  double *ctl, *filter;
+  double *red;
+  const long long *tab;
+  double mu, sigma;
+  double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor;
+  long long max_trials, capacity;
+  long long nvar, n, n_wg;
+};
+SearchArgsH search_args(const iem_search *s) {
+  const iem_barrier *b = s->b;
+  SearchArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.ctl = s->d_ctl; A.filter = s->d_filter; A.red = s->d_red; A.tab = s->d_tab;
+  A.gamma_theta = s->opt.gamma_theta; A.gamma_phi = s->opt.gamma_phi; A.eta_phi = s->opt.eta_phi; A.delta = s->opt.delta;
+  A.s_theta = s->opt.s_theta; A.s_phi = s->opt.s_phi; A.alpha_floor = s->opt.alpha_floor;
+  A.max_trials = (long long)s->opt.max_trials; A.capacity = (long long)s->opt.filter_capacity;
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+const struct SearchSlot { const char *name; hipFunction_t iem_model::SearchObject::*fn; } kSearchSlots[] = {
+    {"search_begin", &iem_model::SearchObject::begin},
+    {"search_trial", &iem_model::SearchObject::trial},
+    {"search_accept", &iem_model::SearchObject::accept},
+};
+int search_object(iem_model *m) {
+  iem_model::SearchObject &o = m->search;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kSearchSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[sizeof kSearchSlots / sizeof *kSearchSlots];
+  int n = 0;
+  for (const SearchSlot &ss : kSearchSlots) slots[n++] = KernelSlot{ss.name, &(o.*ss.fn)};
+  return load_object(m, src, slots, n, &o.mod);
+}
+int search_opts(const iem_search_opts_t *in, iem_search_opts_t *out) {
+  iem_search_opts_t v = {sizeof v, 1e-5, 1e-8, 1e-8, 1.0, 1.1, 2.3, 1e-16, 30, 64};      // Ipopt's
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_search_create: set struct_size to sizeof(iem_search_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  auto unit = [](double g) { return g > 0.0 && g < 1.0; };
+  if (!unit(v.gamma_theta) || !unit(v.gamma_phi) || !unit(v.eta_phi)) return fail(IEM_E_ARG, "iem_search_create: gamma_theta, gamma_phi and eta_phi must lie in (0, 1)");
+  if (!(v.delta > 0.0) || !std::isfinite(v.delta)) return fail(IEM_E_ARG, "iem_search_create: delta must be positive");
+  if (!(v.s_theta > 1.0) || !std::isfinite(v.s_theta)) return fail(IEM_E_ARG, "iem_search_create: s_theta must be greater than 1");
+  if (!(v.s_phi >= 1.0) || !std::isfinite(v.s_phi)) return fail(IEM_E_ARG, "iem_search_create: s_phi must be at least 1");
+  if (!(v.alpha_floor >= 0.0) || !std::isfinite(v.alpha_floor)) return fail(IEM_E_ARG, "iem_search_create: alpha_floor must be finite and not negative");
+  if (v.max_trials < 1) return fail(IEM_E_ARG, "iem_search_create: max_trials must be at least 1");
+  if (v.filter_capacity < 1 || v.filter_capacity > 1024) return fail(IEM_E_ARG, "iem_search_create: filter_capacity must lie in [1, 1024]");
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_search_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kSearchSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_search_destroy(iem_search *s) {
+  if (!s) return IEM_OK;
+  DevGuard dg_(s->b->m->device);
+  for (void *p : {(void *)s->d_ctl, (void *)s->d_filter, (void *)s->d_red, (void *)s->d_tab})
+    if (p) hipFree(p);
+  delete s;
+  return IEM_OK;
+}
+
+int iem_search_create(iem_barrier *b, const iem_search_opts_t *opts, iem_search **out) {
+  if (!b || !out) return fail(IEM_E_ARG, "null argument");
+  iem_search_opts_t opt;
+  {
+    int rc = search_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = search_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_search *p) const { iem_search_destroy(p); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_search, Drop> s(new iem_search);
+  s->b = b;
+  s->opt = opt;
+  const int64_t n_red = b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&s->d_ctl, 16 * 8));
+  HIP_TRY(hipMalloc((void **)&s->d_filter, (size_t)opt.filter_capacity * 16));
+  HIP_TRY(hipMalloc((void **)&s->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMalloc((void **)&s->d_tab, 3 * 8));
+  const long long tab[3] = {0, 0, (long long)b->n_wg};
+  int64_t ctl[16] = {};
+  ctl[9] = IEM_SEARCH_UNUSABLE;      // no begin yet: trial stores nothing, accept writes alpha = +0.0
+  HIP_TRY(hipMemcpy(s->d_ctl, ctl, sizeof ctl, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(s->d_filter, 0, (size_t)opt.filter_capacity * 16));
+  HIP_TRY(hipMemset(s->d_red, 0, (size_t)n_red * 8));
+  HIP_TRY(hipMemcpy(s->d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  *out = s.release();
+  return IEM_OK;
+}
+
+int iem_search_reset(iem_search *s) {
+  if (!s) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  HIP_TRY(hipMemsetAsync(s->d_ctl + 11, 0, 2 * 8, m->stream));      // the filter count and the flags
+  return IEM_OK;
+}
+
+int iem_search_begin(iem_search *s, const double *d_x, const double *d_s, const double *d_grad, const double *d_sol, const double *d_ds, const double *d_obj,
+                     const double *d_err, const double *d_alpha, double mu, double obj_weight) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_begin: mu must not be negative");
+  if (!s || (s->b->nvar && (!d_x || !d_grad)) || (s->b->n_ineq && (!d_s || !d_ds)) || !d_sol || !d_obj || !d_err || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  SearchArgsH A = search_args(s);
+  A.x = d_x; A.s = d_s; A.g = d_grad; A.sol = d_sol; A.ds = d_ds; A.obj = d_obj; A.err = d_err; A.alpha_in = d_alpha; A.mu = mu; A.sigma = obj_weight;
+  return kkt_launch_raw(m, m->search.begin, &A, sizeof A, s->b->n_wg, 256);
+}
+
+int iem_search_trial(iem_search *s, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, double *d_xt, double *d_st) {
+  if (!s || (s->b->nvar && (!d_x || !d_xt)) || (s->b->n_ineq && (!d_s || !d_ds || !d_st)) || !d_sol) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  SearchArgsH A = search_args(s);
+  A.x = d_x; A.s = d_s; A.sol = d_sol; A.ds = d_ds; A.xt = d_xt; A.st = d_st;
+  return kkt_launch_raw(m, m->search.trial, &A, sizeof A, s->b->n_wg, 256);
+}
+
+int iem_search_accept(iem_search *s, const double *d_ft, const double *d_merit, double mu, double obj_weight, double *d_alpha) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_accept: mu must not be negative");
+  if (!s || !d_ft || !d_merit || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  SearchArgsH A = search_args(s);
+  A.ft = d_ft; A.merit = d_merit; A.alpha_out = d_alpha; A.mu = mu; A.sigma = obj_weight;
+  return kkt_launch_raw(m, m->search.accept, &A, sizeof A, 1, 64);
+}
+
+int iem_search_device(const iem_search *s, void **d_control, double **d_filter) {
+  if (!s) return fail(IEM_E_ARG, "null argument");
+  if (d_control) *d_control = s->d_ctl;
+  if (d_filter) *d_filter = s->d_filter;
+  return IEM_OK;
+}
+
+int iem_search_state(iem_search *s, iem_search_state_t *out) {
+  if (!s || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_search_state: set struct_size to sizeof(iem_search_state_t) before the call");
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[16];
+  HIP_TRY(hipMemcpyAsync(w, s->d_ctl, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_search_state_t v;
+  static_assert(sizeof v == 14 * 8, "iem_search_state_t: struct_size, then words 0-12 of the block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.alpha, w, 13 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
 }
 
 int iem_tuner_choice(iem_model *m, int kind, const double *d_vals, int *out_choice) {

@@ -524,6 +524,64 @@ function barrier_merit!(l::BarrierLayer, x, s, c, out)
     return out
 end
 
+# ---- the filter line search (include/iem.h: iem_search_*) ---------------------------------------------------------------------
+# The decision of the iteration on the device: the slope of the barrier objective and the control block (search_begin!), the trial point
+# (search_trial!), the acceptance test of Waechter and Biegler 2006, Algorithm A, with its filter (search_accept!).  One launch each, no
+# read-back but search_state.  A ladder of K rungs (search_trial!, obj, cons, barrier_merit!, search_accept!) needs no host decision:
+# alpha[1] ends as the accepted step length or +0.0, for which barrier_update! moves nothing.  UNEXECUTED, like the rest.
+struct IemSearchOpts       # iem_search_opts_t
+    struct_size::UInt64
+    gamma_theta::Float64; gamma_phi::Float64; eta_phi::Float64; delta::Float64; s_theta::Float64; s_phi::Float64; alpha_floor::Float64
+    max_trials::Int64; filter_capacity::Int64
+end
+struct IemSearchState      # iem_search_state_t: words 0-12 of the control block
+    struct_size::UInt64
+    alpha::Float64; alpha_max::Float64; phi0::Float64; theta0::Float64; slope::Float64; theta_min::Float64; theta_max::Float64; phi_trial::Float64; theta_trial::Float64
+    status::Int64; trials::Int64; filter_count::Int64; flags::Int64      # status: 0 searching, 1 accepted f-type, 2 accepted h-type, 3 failed, 4 unusable
+end
+mutable struct FilterSearch
+    s::Ptr{Cvoid}
+    layer::BarrierLayer      # borrowed: kept alive
+end
+function FilterSearch(l::BarrierLayer; gamma_theta = 1e-5, gamma_phi = 1e-8, eta_phi = 1e-8, delta = 1.0, s_theta = 1.1, s_phi = 2.3, alpha_floor = 1e-16,
+                      max_trials = 30, filter_capacity = 64)
+    opts = Ref(IemSearchOpts(sizeof(IemSearchOpts), gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor, max_trials, filter_capacity))
+    s = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_search_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemSearchOpts}, Ptr{Ptr{Cvoid}}), l.b, opts, s))
+    fs = FilterSearch(s[], l)
+    finalizer(f -> (f.s == C_NULL || ccall((:iem_search_destroy, LIBIEM), Cint, (Ptr{Cvoid},), f.s); f.s = C_NULL), fs)
+    return fs
+end
+# a new barrier problem (mu changed): the filter emptied, the flags cleared
+search_reset!(f::FilterSearch) = check(ccall((:iem_search_reset, LIBIEM), Cint, (Ptr{Cvoid},), f.s))
+# obj: one double on the device (f), err: the eight of barrier_error! at this point, alpha: the two of barrier_step!
+function search_begin!(f::FilterSearch, state, grad, sol, ds, obj, err, alpha, mu; obj_weight = 1.0)
+    check(ccall((:iem_search_begin, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                f.s, spptr(state[1]), spptr(state[2]), spptr(grad), dptr(sol), spptr(ds), dptr(obj), dptr(err), dptr(alpha), mu, obj_weight))
+end
+function search_trial!(f::FilterSearch, state, sol, ds, xt, st)
+    check(ccall((:iem_search_trial, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                f.s, spptr(state[1]), spptr(state[2]), dptr(sol), spptr(ds), spptr(xt), spptr(st)))
+    return xt, st
+end
+# ft: one double on the device (f at the trial point), merit: the two of barrier_merit! there; alpha[1] becomes the accepted step length or +0.0
+function search_accept!(f::FilterSearch, ft, merit, mu, alpha; obj_weight = 1.0)
+    check(ccall((:iem_search_accept, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}), f.s, dptr(ft), dptr(merit), mu, obj_weight, dptr(alpha)))
+    return alpha
+end
+# the one read-back (synchronises the stream)
+function search_state(f::FilterSearch)
+    st = Ref(IemSearchState(sizeof(IemSearchState), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    check(ccall((:iem_search_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemSearchState}), f.s, st))
+    return st[]
+end
+# (control block: 16 words of 8 bytes, filter: filter_capacity pairs (theta, phi)) as device addresses
+function search_device(f::FilterSearch)
+    ctl, flt = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_search_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Float64}}), f.s, ctl, flt))
+    return ctl[], flt[]
+end
+
 # ---- blob writer ----------------------------------------------------------------------------
 # Serialises a host ExaCore into the wire format of include/iem_blob.h.  [EXT]: the field and
 # type names of ExaModels' internal structs (Objective/Constraint linked lists, SIMDFunction,

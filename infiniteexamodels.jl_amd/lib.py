@@ -83,6 +83,32 @@ class BarrierInfo(C.Structure):
     _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_int64) for n in ("nvar", "ncon", "n_eq", "n_ineq", "n_xl", "n_xu", "n_sl", "n_su", "nz", "workgroups")]
 
 
+class SearchOpts(C.Structure):
+    """``iem_search_opts_t``: ``struct_size`` is set by the caller; ``SearchOpts.defaults()`` has Ipopt's values."""
+    _fields_ = ([("struct_size", C.c_uint64)] + [(n, C.c_double) for n in ("gamma_theta", "gamma_phi", "eta_phi", "delta", "s_theta", "s_phi", "alpha_floor")] +
+                [(n, C.c_int64) for n in ("max_trials", "filter_capacity")])
+    DEFAULTS = dict(gamma_theta=1e-5, gamma_phi=1e-8, eta_phi=1e-8, delta=1.0, s_theta=1.1, s_phi=2.3, alpha_floor=1e-16, max_trials=30, filter_capacity=64)
+
+    @classmethod
+    def defaults(cls, **over):
+        unknown = set(over) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown search option(s): {sorted(unknown)}")
+        o = cls(**{**cls.DEFAULTS, **over})
+        o.struct_size = C.sizeof(cls)
+        return o
+
+
+class SearchState(C.Structure):
+    """``iem_search_state_t``: ``struct_size`` (set by the caller), then words 0-12 of the control block."""
+    _fields_ = ([("struct_size", C.c_uint64)] +
+                [(n, C.c_double) for n in ("alpha", "alpha_max", "phi0", "theta0", "slope", "theta_min", "theta_max", "phi_trial", "theta_trial")] +
+                [(n, C.c_int64) for n in ("status", "trials", "filter_count", "flags")])
+
+
+SEARCH_STATUS = ("searching", "accepted_f", "accepted_h", "failed", "unusable")
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("kind", C.c_int32), ("jit", C.c_int32), ("grid", C.c_int64 * 3),
                 ("lds_bytes", C.c_int64), ("alg_bytes_read", C.c_int64), ("alg_bytes_written", C.c_int64)]
@@ -94,7 +120,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -240,6 +266,15 @@ def lib():
     L.iem_barrier_error.argtypes = [vp] + [vp] * 9 + [dbl, vp]
     L.iem_barrier_merit.argtypes = [vp, vp, vp, vp, vp]
     L.iem_barrier_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.iem_search_create.argtypes = [vp, C.POINTER(SearchOpts), C.POINTER(vp)]
+    L.iem_search_destroy.argtypes = [vp]
+    L.iem_search_reset.argtypes = [vp]
+    L.iem_search_begin.argtypes = [vp] + [vp] * 8 + [dbl, dbl]
+    L.iem_search_trial.argtypes = [vp] + [vp] * 6
+    L.iem_search_accept.argtypes = [vp, vp, vp, dbl, dbl, vp]
+    L.iem_search_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.iem_search_state.argtypes = [vp, C.POINTER(SearchState)]
+    L.iem_search_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_fixed_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -360,6 +395,12 @@ def barrier_source():
     """HIP source of the interior-point barrier layer's kernels (``barrier_start`` / ``_terms`` / ``_step`` / ``_update`` / ``_error`` /
     ``_merit``: the ``iem_barrier_*`` calls) and its cache key."""
     return _source(lib().iem_barrier_source)
+
+
+def search_source():
+    """HIP source of the filter line search's kernels (``search_begin`` / ``search_trial`` / ``search_accept``: the ``iem_search_*``
+    calls) and its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
+    return _source(lib().iem_search_source)
 
 
 def fixed_sources():
