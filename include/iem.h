@@ -797,7 +797,7 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  *     0 alpha (double)          1 alpha_max: the d_alpha[0] that begin saw      2 phi0 = obj_weight·f − mu·sum log gap      3 theta0
  *     4 slope                   5 theta_min      6 theta_max                    7 phi of the last trial   8 theta of the last trial
  *     9 status (int64): 0 SEARCHING, 1 accepted f-type, 2 accepted h-type, 3 FAILED, 4 UNUSABLE           10 trials (int64)
- *     11 filter count (int64)   12 flags (int64): bit 0 = theta_min / theta_max are set, bit 1 = filter overflow        13–15 zero
+ *     11 filter count (int64)   12 flags (int64): bit 0 = theta_min / theta_max are set, bit 1 = filter overflow        13–15 zero (begin) — the iem_soc object's
  * The filter: filter_capacity pairs (theta, phi) on the device, the first `filter count` of them in use.
  *
  * iem_search_begin: slope = sum of  t_i = (obj_weight·g_i + gb_i)·dx_i  over the variables and  t_j = gs_j·ds_j  over the inequality
@@ -827,8 +827,9 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * synchronises and nothing is copied to the host, except by iem_search_state.  IEM_E_ARG before any device work: null required
  * pointers (s, ds, st may be NULL without inequality rows), mu < 0, options out of range (gamma_theta, gamma_phi, eta_phi in (0, 1),
  * delta > 0, s_theta > 1, s_phi >= 1, alpha_floor >= 0, max_trials >= 1, 1 <= filter_capacity <= 1024).  The object borrows the barrier object (bounds,
- * flags, grid) and through it the model handle: destroy it before them.  Not here: the mu update, inertia correction, the second-order
- * correction, Ipopt's alpha_min formula, restoration, sharded handles (iem_barrier_create refuses them). */
+ * flags, grid) and through it the model handle: destroy it before them.  Not here: the mu update, inertia correction,
+ * Ipopt's alpha_min formula, restoration, sharded handles (iem_barrier_create refuses them).  The second-order correction is the
+ * iem_soc object below; words 13–15 of the block are its. */
 typedef struct iem_search iem_search;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_search_opts_t) */
@@ -853,6 +854,85 @@ int iem_search_device(const iem_search *s, void **d_control, double **d_filter /
 int iem_search_state(iem_search *s, iem_search_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the three kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_search_source(char **out_src, uint64_t *out_key);
+
+/* ---- the second-order correction of the filter line search -----------------------------------------------------------------------
+ * Waechter and Biegler 2006, Algorithm A, steps A-5.5 to A-5.9 (Ipopt's TrySecondOrderCorrection, max_soc = 4, kappa_soc = 0.99) on the
+ * device (csrc/iem_soc_device.h), as an object beside iem_search: between the first rejected trial and the first halving of alpha, the
+ * constraint residual of the rejected trial point is added to the right-hand side and the corrected step is tested at full length.
+ * Every call is ONE launch and is gated ON THE DEVICE by words 13–15 of the search object's control block, so the same sequence serves a
+ * host that reads the status word after the first rung and runs the rounds only when wanted, and a captured ladder that holds P rounds
+ * unconditionally — a call that does not apply returns before its first store:
+ *     iem_search_begin;  rung;  iem_soc_open;
+ *     P × { iem_soc_rhs, iem_kkt_solve_refined_diag(1 column: rhs_soc -> sol_soc), iem_barrier_step(sol_soc -> ds_soc, dzL_soc, dzU_soc,
+ *           dvL_soc, dvU_soc, alpha_soc), iem_soc_trial, iem_obj_device, iem_cons, iem_barrier_merit, iem_soc_accept };
+ *     iem_soc_select;  (K − 1) × rung;  iem_barrier_update
+ * (rung = { iem_search_trial, iem_obj_device, iem_cons, iem_barrier_merit, iem_search_accept }).  The solve and the step run on this
+ * iteration's factors and are unchanged; while the correction is not ACTIVE they compute on buffers nobody reads.
+ *
+ * THE CONTROL BLOCK, words 13–15 (iem_search_begin zeroes them for every search):
+ *     13 state (int64): 0 NONE, 1 ACTIVE, 2 ACCEPTED, 3 CLOSED      14 rounds finished (int64)      15 alpha_prev (double)
+ *
+ * iem_soc_open: one workgroup; behind the first rung's iem_search_accept.  With state NONE: ACTIVE when status == SEARCHING, trials == 1
+ *     and theta of the last trial (word 8) is finite and >= theta0 (word 3) (a NaN compares false) — then rounds = 0 and alpha_prev =
+ *     alpha_max (word 1); otherwise CLOSED.  With any other state it writes nothing (idempotent: a replayed graph finds it decided).
+ *     A search with max_trials = 1 has FAILED at its first rejection, before a correction can open.
+ * iem_soc_rhs: with state ACTIVE, per row j (inf_t_j = ct_j − ceq_j on an equality row, ct_j − st_j on an inequality row: the
+ *     infeasibility of iem_barrier_merit at the latest trial point; each operation rounded once, in the order written):
+ *         rounds == 0:  prev_j = c_j − ceq_j  resp.  c_j − s_j          rounds > 0:  prev_j = csoc_j
+ *         csoc_j = alpha_prev·prev_j + inf_t_j                          (a product, then a sum; csoc is stored in the object)
+ *         equality row:    rhs_soc_y_j = −csoc_j
+ *         inequality row:  rhs_soc_y_j = −(csoc_j + rs_j·inv_j)         rs_j, inv_j of the barrier contract above from (s, y, vL, vU, mu)
+ *     and rhs_soc_i = rhs_i for i < nvar (the bits copied).  Only the linearised constraint J·dx − ds = −(c − s) changes: ds = (dy − rs)/sigs
+ *     and every multiplier direction keep their formulas, so iem_barrier_step is the step of the corrected direction.  Not ACTIVE:
+ *     nothing is stored, csoc stays.
+ * iem_soc_trial: with state ACTIVE and alpha_soc[0] > 0:  xt = x + alpha_soc[0]·dx_soc,  st = s + alpha_soc[0]·ds_soc on inequality rows
+ *     (equality rows' entries never written); otherwise nothing is stored.
+ * iem_soc_accept: ONE workgroup of 64 threads.  Not ACTIVE: writes nothing at all.  ACTIVE with alpha_soc[0] not > 0 (the barrier
+ *     layer's "unusable"): state CLOSED, rounds += 1, nothing else.  Otherwise the test of iem_search_accept word for word — theta_t,
+ *     phi_t, admissible, switching, Armijo, sufficient, in that rounding order — with alpha := alpha_max (word 1) in the switching
+ *     condition and in Armijo (Ipopt tests a corrected step with the full step's alpha).  Words 7, 8 take phi_t, theta_t and rounds += 1
+ *     either way.  Accepted: status 1 (f-type) or 2 (h-type: the filter gains its entry exactly as in iem_search_accept, overflow flag
+ *     included), word 0 = alpha_soc[0], d_alpha[0] = alpha_soc[0], d_alpha[1] = alpha_soc[1], state ACCEPTED.  Rejected: with p = the new
+ *     rounds, the correction goes on iff p < max_soc and theta_t is finite and theta_t <= kappa_soc·theta_prev (theta_prev = word 8 before
+ *     this call: the previous trial's theta; one product) — then alpha_prev = alpha_soc[0]; otherwise state CLOSED, and backtracking
+ *     continues from alpha_max/2, which the rejecting iem_search_accept left in word 0.  A rejection touches neither status, trials,
+ *     word 0 nor d_alpha.
+ * iem_soc_select: iff state ACCEPTED it copies the corrected direction over the first-order one — sol: nvar + ncon entries, dzL, dzU:
+ *     nvar, ds, dvL, dvU: inequality rows only; otherwise nothing.  The later rungs' iem_search_trial then recomputes x + alpha_soc·dx_soc
+ *     from the expression of iem_soc_trial (the same bits), and iem_barrier_update takes the corrected step with no host decision.
+ * Every call runs on the handle's stream, one launch, asynchronous, capturable; nothing allocates after create, nothing synchronises
+ * and nothing is copied to the host, except by iem_soc_state.  IEM_E_ARG before any device work: null required pointers (s, y, vL, vU,
+ * st, ds*, dvL*, dvU* may be NULL without inequality rows), mu < 0, max_soc outside [1, 16], kappa_soc outside (0, 1].  The object
+ * borrows the search object (block, filter, options) and through it the barrier object: destroy it before them.  Not here: the mu
+ * update, inertia correction, restoration, sharded handles. */
+typedef struct iem_soc iem_soc;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_soc_opts_t) */
+  int64_t max_soc;
+  double kappa_soc;
+} iem_soc_opts_t;                       /* NULL = Ipopt's defaults: 4, 0.99 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_soc_state_t): at most that many bytes are written */
+  int64_t status;                       /* word 9 of the block */
+  int64_t state, rounds;                /* words 13, 14 */
+  double alpha_prev;                    /* word 15 */
+} iem_soc_state_t;
+enum { IEM_SOC_NONE = 0, IEM_SOC_ACTIVE = 1, IEM_SOC_ACCEPTED = 2, IEM_SOC_CLOSED = 3 };
+int iem_soc_create(iem_search *s, const iem_soc_opts_t *opts, iem_soc **out);      /* allocates csoc (ncon doubles, zeroed) */
+int iem_soc_destroy(iem_soc *q);
+int iem_soc_open(iem_soc *q);
+int iem_soc_rhs(iem_soc *q, const double *d_s, const double *d_y, const double *d_vL, const double *d_vU, const double *d_c, const double *d_ct,
+                const double *d_st, const double *d_rhs, double mu, double *d_rhs_soc);
+int iem_soc_trial(iem_soc *q, const double *d_x, const double *d_s, const double *d_sol_soc, const double *d_ds_soc, const double *d_alpha_soc /* 2 */,
+                  double *d_xt, double *d_st);
+int iem_soc_accept(iem_soc *q, const double *d_ft, const double *d_merit /* 2 */, const double *d_alpha_soc /* 2 */, double mu, double obj_weight,
+                   double *d_alpha /* 2 */);
+int iem_soc_select(iem_soc *q, const double *d_sol_soc, const double *d_ds_soc, const double *d_dzL_soc, const double *d_dzU_soc, const double *d_dvL_soc,
+                   const double *d_dvU_soc, double *d_sol, double *d_ds, double *d_dzL, double *d_dzU, double *d_dvL, double *d_dvU);
+int iem_soc_device(const iem_soc *q, double **d_csoc /* ncon: the accumulated residual */);
+int iem_soc_state(iem_soc *q, iem_soc_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the five kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_soc_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

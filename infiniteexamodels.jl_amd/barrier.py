@@ -294,3 +294,126 @@ class FilterSearch:
                 self.close()
         except Exception:
             pass
+
+
+class SecondOrderCorrection:
+    """``SecondOrderCorrection(search, max_soc=4, kappa_soc=0.99)``: the second-order correction of the C-ABI (``iem_soc_*``,
+    ``csrc/iem_soc_device.h``) beside a :class:`FilterSearch` — five one-launch calls gated on the device by words 13–15 of the
+    search's control block, no read-back but :meth:`state`.  Between the first rung and the later ones, with buffers of the caller
+    (``kkt``: the ``KKTObject`` holding this iteration's factors):
+
+        soc.open()                                                     # behind the first rung's fs.accept
+        for _ in range(P):                                             # P <= max_soc rounds; a round that does not apply stores nothing
+            soc.rhs(state, c, ct, st, rhs, mu, out=rhs_soc)
+            kkt.solve(rhs_soc, refine=1, out=sol_soc)
+            bar.step(state, sol_soc, mu, tau, out=dirs_soc, alpha=alpha_soc)
+            soc.trial(state, sol_soc, dirs_soc[0], alpha_soc, xt, st)
+            model.obj_device(xt, out=ft); model.cons(xt, out=ct); bar.merit(xt, st, ct, out=m)
+            soc.accept(ft, m, alpha_soc, mu, alpha)
+        soc.select(sol_soc, dirs_soc, sol, dirs)                       # an accepted correction replaces the first-order direction
+
+    The later rungs and ``bar.update(state, sol, dirs, alpha, mu)`` then take the corrected step with no host decision."""
+
+    def __init__(self, search: FilterSearch, **opts):
+        self.search = search
+        self.layer = search.layer
+        self._q = None
+        o = _lib.SocOpts.defaults(**opts)
+        self.opts = {name: getattr(o, name) for name, _ in _lib.SocOpts._fields_ if name != "struct_size"}
+        L, s = search._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_soc_create(s, C.byref(o), C.byref(q)))
+        self._q = q
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("SecondOrderCorrection: closed")
+        L, _ = self.search._handle()
+        return L, self._q
+
+    def open(self):
+        """The gate (``iem_soc_open``), behind the first rung's ``accept``: the correction becomes active iff that trial was rejected
+        with a finite ``θ`` not below ``θ0``; a second call changes nothing."""
+        L, q = self._handle()
+        _lib.check(L.iem_soc_open(q))
+
+    def rhs(self, state, c, ct, st, rhs, mu: float, out=None):
+        """The accumulated constraint residual and the corrected right-hand side (``iem_soc_rhs``): ``c`` at the current point, ``ct`` /
+        ``st`` at the latest trial point, ``rhs`` of ``BarrierLayer.terms``.  Returns ``out`` (``nvar + ncon``)."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        out = out if out is not None else bar._new(bar.n)
+        args = (bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(state[2], bar.ncon, "y", optional=slack), bar._vec(state[5], bar.ncon, "vL", optional=slack),
+                bar._vec(state[6], bar.ncon, "vU", optional=slack), bar._vec(c, bar.ncon, "c"), bar._vec(ct, bar.ncon, "ct"), bar._vec(st, bar.ncon, "st", optional=slack),
+                bar._vec(rhs, bar.n, "rhs"), float(mu), bar._vec(out, bar.n, "rhs_soc"))
+        L, q = self._handle()
+        _lib.check(L.iem_soc_rhs(q, *args))
+        return out
+
+    def trial(self, state, sol_soc, ds_soc, alpha_soc, xt, st):
+        """``(xt, st) = (x + α_soc·dx_soc, s + α_soc·ds_soc)`` with ``α_soc = alpha_soc[0]`` read on the device (``iem_soc_trial``);
+        nothing is stored unless the correction is active and ``α_soc > 0``."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(sol_soc, bar.n, "sol_soc"),
+                bar._vec(ds_soc, bar.ncon, "ds_soc", optional=slack), bar._vec(alpha_soc, 2, "alpha_soc"), bar._vec(xt, bar.nvar, "xt"),
+                bar._vec(st, bar.ncon, "st", optional=slack))
+        L, q = self._handle()
+        _lib.check(L.iem_soc_trial(q, *args))
+        return xt, st
+
+    def accept(self, ft, merit, alpha_soc, mu: float, alpha, obj_weight: float = 1.0):
+        """The decision on a corrected trial point (``iem_soc_accept``): accepted, ``alpha`` takes both step lengths of ``alpha_soc``;
+        rejected, neither ``alpha`` nor the search's status, trials and step length change.  Returns ``alpha``."""
+        bar = self.layer
+        args = (bar._vec(ft, 1, "ft"), bar._vec(merit, 2, "merit"), bar._vec(alpha_soc, 2, "alpha_soc"), float(mu), float(obj_weight), bar._vec(alpha, 2, "alpha"))
+        L, q = self._handle()
+        _lib.check(L.iem_soc_accept(q, *args))
+        return alpha
+
+    def select(self, sol_soc, dirs_soc, sol, dirs):
+        """Iff the correction was accepted, ``sol_soc`` and ``dirs_soc = (ds, dzL, dzU, dvL, dvU)`` are copied over ``sol`` and
+        ``dirs`` (``iem_soc_select``)."""
+        bar = self.layer
+        src, dst = bar._dirs(dirs_soc), bar._dirs(dirs)
+        ps, pd = bar._vec(sol_soc, bar.n, "sol_soc"), bar._vec(sol, bar.n, "sol")
+        L, q = self._handle()
+        _lib.check(L.iem_soc_select(q, ps, *src, pd, *dst))
+        return sol, dirs
+
+    def state(self):
+        """THE read-back (``iem_soc_state``, synchronises): the search's status word and words 13–15 of the block, ``state`` also by
+        name."""
+        L, q = self._handle()
+        v = _lib.SocState()
+        v.struct_size = C.sizeof(_lib.SocState)
+        _lib.check(L.iem_soc_state(q, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.SocState._fields_ if name != "struct_size"}
+        out["state_name"] = _lib.SOC_STATE[out["state"]] if 0 <= out["state"] < len(_lib.SOC_STATE) else "?"
+        return out
+
+    def device(self):
+        """The address of the accumulated residual ``csoc`` (``ncon`` doubles) on the device (``iem_soc_device``)."""
+        L, q = self._handle()
+        p = C.c_void_p()
+        _lib.check(L.iem_soc_device(q, C.byref(p)))
+        return p.value
+
+    def close(self):
+        if self._q is not None:
+            _lib.check(self.layer.model._L.iem_soc_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.search._s is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass

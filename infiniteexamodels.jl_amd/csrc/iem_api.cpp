@@ -55,6 +55,9 @@ static const char *kBarrierSource =       // the interior-point barrier layer (i
 static const char *kSearchSource =        // the filter line search (iem_search_*): a code object of its own, behind the same helpers — not a row of kFixed
 #include "iem_search_device_h.inc"
     ;
+static const char *kSocSource =           // the second-order correction of the search (iem_soc_*): a code object of its own, behind no helpers — not a row of kFixed
+#include "iem_soc_device_h.inc"
+    ;
 
 namespace {
 
@@ -317,6 +320,8 @@ struct iem_model {
   struct FixedObject { hipModule_t mod = nullptr; hipFunction_t fn[kFixedSlots] = {}; } fixed[F_COUNT];
   // the code object of the filter line search (iem_search_*): loaded by the first iem_search_create of the handle
   struct SearchObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, trial = nullptr, accept = nullptr; } search;
+  // the code object of the second-order correction (iem_soc_*): loaded by the first iem_soc_create of the handle
+  struct SocObject { hipModule_t mod = nullptr; hipFunction_t open = nullptr, rhs = nullptr, trial = nullptr, accept = nullptr, select = nullptr; } soc;
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1357,6 +1362,7 @@ int iem_destroy(iem_model *m) {
   if (m->d_kkt_zero) hipFree(m->d_kkt_zero);
   for (auto &o : m->fixed) if (o.mod) hipModuleUnload(o.mod);
   if (m->search.mod) hipModuleUnload(m->search.mod);
+  if (m->soc.mod) hipModuleUnload(m->soc.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -4246,6 +4252,194 @@ int iem_search_state(iem_search *s, iem_search_state_t *out) {
   static_assert(sizeof v == 14 * 8, "iem_search_state_t: struct_size, then words 0-12 of the block");
   v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
   std::memcpy(&v.alpha, w, 13 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+/* ---- the second-order correction of the search: gate, corrected right-hand side, trial point, acceptance, selection (csrc/iem_soc_device.h) ---- */
+struct iem_soc {
+  iem_search *s = nullptr;
+  iem_soc_opts_t opt;
+  double *d_csoc = nullptr;            // the accumulated constraint residual: ncon
+};
+
+namespace {
+// SocArgs of csrc/iem_soc_device.h
+struct SocArgsH {
+  const double *rl, *ru, *ceq;
+  const unsigned char *fc;
+  const double *x, *s, *y, *vL, *vU;
+  const double *c, *ct, *st_in, *rhs;
+  double *rhs_soc, *csoc;
+  const double *sol, *ds, *dzL, *dzU, *dvL, *dvU;
+  const double *alpha_soc;
+  double *xt, *st;
+  const double *ft, *merit;
+  double *alpha_out;
+  double *o_sol, *o_ds, *o_dzL, *o_dzU, *o_dvL, *o_dvU;
+  double *ctl, *filter;
+  double mu, sigma;
+  double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, kappa_soc;
+  long long max_soc, capacity;
+  long long nvar, n;
+};
+SocArgsH soc_args(const iem_soc *q) {
+  const iem_search *s = q->s;
+  const iem_barrier *b = s->b;
+  SocArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.rl = b->d_bounds + 2 * b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fc = b->d_flags + b->nvar;
+  A.csoc = q->d_csoc; A.ctl = s->d_ctl; A.filter = s->d_filter;
+  A.gamma_theta = s->opt.gamma_theta; A.gamma_phi = s->opt.gamma_phi; A.eta_phi = s->opt.eta_phi; A.delta = s->opt.delta;
+  A.s_theta = s->opt.s_theta; A.s_phi = s->opt.s_phi; A.kappa_soc = q->opt.kappa_soc;
+  A.max_soc = (long long)q->opt.max_soc; A.capacity = (long long)s->opt.filter_capacity;
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon);
+  return A;
+}
+const struct SocSlot { const char *name; hipFunction_t iem_model::SocObject::*fn; } kSocSlots[] = {
+    {"soc_open", &iem_model::SocObject::open},     {"soc_rhs", &iem_model::SocObject::rhs},       {"soc_trial", &iem_model::SocObject::trial},
+    {"soc_accept", &iem_model::SocObject::accept}, {"soc_select", &iem_model::SocObject::select},
+};
+int soc_object(iem_model *m) {
+  iem_model::SocObject &o = m->soc;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kSocSource, false, src);
+  if (rc) return rc;
+  KernelSlot slots[sizeof kSocSlots / sizeof *kSocSlots];
+  int n = 0;
+  for (const SocSlot &ss : kSocSlots) slots[n++] = KernelSlot{ss.name, &(o.*ss.fn)};
+  return load_object(m, src, slots, n, &o.mod);
+}
+int soc_opts(const iem_soc_opts_t *in, iem_soc_opts_t *out) {
+  iem_soc_opts_t v = {sizeof v, 4, 0.99};      // Ipopt's max_soc, kappa_soc
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_soc_create: set struct_size to sizeof(iem_soc_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  if (v.max_soc < 1 || v.max_soc > 16) return fail(IEM_E_ARG, "iem_soc_create: max_soc must lie in [1, 16]");
+  if (!(v.kappa_soc > 0.0) || !(v.kappa_soc <= 1.0)) return fail(IEM_E_ARG, "iem_soc_create: kappa_soc must lie in (0, 1]");
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_soc_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kSocSource, false, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_soc_destroy(iem_soc *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->s->b->m->device);
+  if (q->d_csoc) hipFree(q->d_csoc);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_soc_create(iem_search *s, const iem_soc_opts_t *opts, iem_soc **out) {
+  if (!s || !out) return fail(IEM_E_ARG, "null argument");
+  iem_soc_opts_t opt;
+  {
+    int rc = soc_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_model *m = s->b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = soc_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_soc *p) const { iem_soc_destroy(p); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_soc, Drop> q(new iem_soc);
+  q->s = s;
+  q->opt = opt;
+  const size_t bytes = (size_t)std::max<int64_t>(s->b->ncon, 1) * 8;
+  HIP_TRY(hipMalloc((void **)&q->d_csoc, bytes));
+  HIP_TRY(hipMemset(q->d_csoc, 0, bytes));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_soc_open(iem_soc *q) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->s->b->m;
+  DevGuard dg_(m->device);
+  SocArgsH A = soc_args(q);
+  return kkt_launch_raw(m, m->soc.open, &A, sizeof A, 1, 64);
+}
+
+int iem_soc_rhs(iem_soc *q, const double *d_s, const double *d_y, const double *d_vL, const double *d_vU, const double *d_c, const double *d_ct, const double *d_st,
+                const double *d_rhs, double mu, double *d_rhs_soc) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_rhs: mu must not be negative");
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->ncon && (!d_c || !d_ct)) || (b->n_ineq && (!d_s || !d_y || !d_vL || !d_vU || !d_st)) || !d_rhs || !d_rhs_soc) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  SocArgsH A = soc_args(q);
+  A.s = d_s; A.y = d_y; A.vL = d_vL; A.vU = d_vU; A.c = d_c; A.ct = d_ct; A.st_in = d_st; A.rhs = d_rhs; A.rhs_soc = d_rhs_soc; A.mu = mu;
+  return kkt_launch_raw(m, m->soc.rhs, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_soc_trial(iem_soc *q, const double *d_x, const double *d_s, const double *d_sol_soc, const double *d_ds_soc, const double *d_alpha_soc, double *d_xt, double *d_st) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->nvar && (!d_x || !d_xt)) || (b->n_ineq && (!d_s || !d_ds_soc || !d_st)) || !d_sol_soc || !d_alpha_soc) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  SocArgsH A = soc_args(q);
+  A.x = d_x; A.s = d_s; A.sol = d_sol_soc; A.ds = d_ds_soc; A.alpha_soc = d_alpha_soc; A.xt = d_xt; A.st = d_st;
+  return kkt_launch_raw(m, m->soc.trial, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_soc_accept(iem_soc *q, const double *d_ft, const double *d_merit, const double *d_alpha_soc, double mu, double obj_weight, double *d_alpha) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_accept: mu must not be negative");
+  if (!q || !d_ft || !d_merit || !d_alpha_soc || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->s->b->m;
+  DevGuard dg_(m->device);
+  SocArgsH A = soc_args(q);
+  A.ft = d_ft; A.merit = d_merit; A.alpha_soc = d_alpha_soc; A.alpha_out = d_alpha; A.mu = mu; A.sigma = obj_weight;
+  return kkt_launch_raw(m, m->soc.accept, &A, sizeof A, 1, 64);
+}
+
+int iem_soc_select(iem_soc *q, const double *d_sol_soc, const double *d_ds_soc, const double *d_dzL_soc, const double *d_dzU_soc, const double *d_dvL_soc,
+                   const double *d_dvU_soc, double *d_sol, double *d_ds, double *d_dzL, double *d_dzU, double *d_dvL, double *d_dvU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if (!d_sol_soc || !d_sol || (b->nvar && (!d_dzL_soc || !d_dzU_soc || !d_dzL || !d_dzU)) ||
+      (b->n_ineq && (!d_ds_soc || !d_dvL_soc || !d_dvU_soc || !d_ds || !d_dvL || !d_dvU)))
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  SocArgsH A = soc_args(q);
+  A.sol = d_sol_soc; A.ds = d_ds_soc; A.dzL = d_dzL_soc; A.dzU = d_dzU_soc; A.dvL = d_dvL_soc; A.dvU = d_dvU_soc;
+  A.o_sol = d_sol; A.o_ds = d_ds; A.o_dzL = d_dzL; A.o_dzU = d_dzU; A.o_dvL = d_dvL; A.o_dvU = d_dvU;
+  return kkt_launch_raw(m, m->soc.select, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_soc_device(const iem_soc *q, double **d_csoc) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (d_csoc) *d_csoc = q->d_csoc;
+  return IEM_OK;
+}
+
+int iem_soc_state(iem_soc *q, iem_soc_state_t *out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_soc_state: set struct_size to sizeof(iem_soc_state_t) before the call");
+  iem_model *m = q->s->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[16];
+  HIP_TRY(hipMemcpyAsync(w, q->s->d_ctl, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_soc_state_t v;
+  static_assert(sizeof v == 5 * 8, "iem_soc_state_t: struct_size, the status word, then words 13-15 of the block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.status, w + 9, 8);
+  std::memcpy(&v.state, w + 13, 3 * 8);
   std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
   return IEM_OK;
 }

@@ -582,6 +582,72 @@ function search_device(f::FilterSearch)
     return ctl[], flt[]
 end
 
+# ---- the second-order correction of the search (include/iem.h: iem_soc_*) -------------------------------------------------------------
+# Between the first rejected trial and the first halving of alpha (Ipopt's TrySecondOrderCorrection): soc_open! behind the first rung, then
+# per round soc_rhs!, solve_refined! (one column: rhs_soc -> sol_soc), barrier_step! on sol_soc, soc_trial!, obj, cons, barrier_merit!,
+# soc_accept!; soc_select! copies an accepted correction over the first-order direction.  Every call is one launch, gated on the device
+# by words 13-15 of the search's control block: a call that does not apply stores nothing.  UNEXECUTED, like the rest.
+struct IemSocOpts          # iem_soc_opts_t
+    struct_size::UInt64
+    max_soc::Int64
+    kappa_soc::Float64
+end
+struct IemSocState         # iem_soc_state_t: the status word, then words 13-15 of the control block
+    struct_size::UInt64
+    status::Int64
+    state::Int64; rounds::Int64      # state: 0 none, 1 active, 2 accepted, 3 closed
+    alpha_prev::Float64
+end
+mutable struct SecondOrderCorrection
+    q::Ptr{Cvoid}
+    search::FilterSearch      # borrowed: kept alive
+end
+function SecondOrderCorrection(f::FilterSearch; max_soc = 4, kappa_soc = 0.99)
+    opts = Ref(IemSocOpts(sizeof(IemSocOpts), max_soc, kappa_soc))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_soc_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemSocOpts}, Ptr{Ptr{Cvoid}}), f.s, opts, q))
+    soc = SecondOrderCorrection(q[], f)
+    finalizer(c -> (c.q == C_NULL || ccall((:iem_soc_destroy, LIBIEM), Cint, (Ptr{Cvoid},), c.q); c.q = C_NULL), soc)
+    return soc
+end
+soc_open!(c::SecondOrderCorrection) = check(ccall((:iem_soc_open, LIBIEM), Cint, (Ptr{Cvoid},), c.q))
+# cons: c at the current point, ct / st: at the latest trial point, rhs: of barrier_terms!
+function soc_rhs!(c::SecondOrderCorrection, state, cons, ct, st, rhs, mu, rhs_soc)
+    check(ccall((:iem_soc_rhs, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}),
+                c.q, spptr(state[2]), spptr(state[3]), spptr(state[6]), spptr(state[7]), spptr(cons), spptr(ct), spptr(st), dptr(rhs), mu, dptr(rhs_soc)))
+    return rhs_soc
+end
+function soc_trial!(c::SecondOrderCorrection, state, sol_soc, ds_soc, alpha_soc, xt, st)
+    check(ccall((:iem_soc_trial, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                c.q, spptr(state[1]), spptr(state[2]), dptr(sol_soc), spptr(ds_soc), dptr(alpha_soc), spptr(xt), spptr(st)))
+    return xt, st
+end
+# accepted: alpha takes both step lengths of alpha_soc; rejected: alpha and the search's status, trials and step length stay
+function soc_accept!(c::SecondOrderCorrection, ft, merit, alpha_soc, mu, alpha; obj_weight = 1.0)
+    check(ccall((:iem_soc_accept, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}),
+                c.q, dptr(ft), dptr(merit), dptr(alpha_soc), mu, obj_weight, dptr(alpha)))
+    return alpha
+end
+# dirs = (ds, dzL, dzU, dvL, dvU)
+function soc_select!(c::SecondOrderCorrection, sol_soc, dirs_soc, sol, dirs)
+    check(ccall((:iem_soc_select, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 12)...),
+                c.q, dptr(sol_soc), spptr(dirs_soc[1]), spptr(dirs_soc[2]), spptr(dirs_soc[3]), spptr(dirs_soc[4]), spptr(dirs_soc[5]),
+                dptr(sol), spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5])))
+    return sol, dirs
+end
+# the one read-back (synchronises the stream)
+function soc_state(c::SecondOrderCorrection)
+    st = Ref(IemSocState(sizeof(IemSocState), 0, 0, 0, 0))
+    check(ccall((:iem_soc_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemSocState}), c.q, st))
+    return st[]
+end
+# the accumulated residual csoc (ncon doubles) as a device address
+function soc_device(c::SecondOrderCorrection)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_soc_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), c.q, p))
+    return p[]
+end
+
 # ---- blob writer ----------------------------------------------------------------------------
 # Serialises a host ExaCore into the wire format of include/iem_blob.h.  [EXT]: the field and
 # type names of ExaModels' internal structs (Objective/Constraint linked lists, SIMDFunction,
