@@ -828,7 +828,7 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * pointers (s, ds, st may be NULL without inequality rows), mu < 0, options out of range (gamma_theta, gamma_phi, eta_phi in (0, 1),
  * delta > 0, s_theta > 1, s_phi >= 1, alpha_floor >= 0, max_trials >= 1, 1 <= filter_capacity <= 1024).  The object borrows the barrier object (bounds,
  * flags, grid) and through it the model handle: destroy it before them.  Not here: the mu update, inertia correction,
- * Ipopt's alpha_min formula, restoration, sharded handles (iem_barrier_create refuses them).  The second-order correction is the
+ * Ipopt's alpha_min formula, sharded handles (iem_barrier_create refuses them); restoration is the iem_resto object below.  The second-order correction is the
  * iem_soc object below; words 13–15 of the block are its. */
 typedef struct iem_search iem_search;
 typedef struct {
@@ -904,7 +904,7 @@ int iem_search_source(char **out_src, uint64_t *out_key);
  * and nothing is copied to the host, except by iem_soc_state.  IEM_E_ARG before any device work: null required pointers (s, y, vL, vU,
  * st, ds*, dvL*, dvU* may be NULL without inequality rows), mu < 0, max_soc outside [1, 16], kappa_soc outside (0, 1].  The object
  * borrows the search object (block, filter, options) and through it the barrier object: destroy it before them.  Not here: the mu
- * update, inertia correction, restoration, sharded handles. */
+ * update, inertia correction, sharded handles (restoration: the iem_resto object below). */
 typedef struct iem_soc iem_soc;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_soc_opts_t) */
@@ -933,6 +933,105 @@ int iem_soc_device(const iem_soc *q, double **d_csoc /* ncon: the accumulated re
 int iem_soc_state(iem_soc *q, iem_soc_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the five kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_soc_source(char **out_src, uint64_t *out_key);
+
+/* ---- the feasibility restoration phase ---------------------------------------------------------------------------------------------
+ * Step A-9 of Waechter and Biegler 2006 (Ipopt's section 3.3) on the device (csrc/iem_resto_device.h), as an object beside
+ * iem_search: when the filter search of the ORIGINAL problem ends FAILED, the host enters the phase, iterates on the restoration
+ * problem
+ *     min  rho·sum(p + n) + zeta/2·|D_R (x − x_R)|²   s.t.  c(x) − s − p + n = 0 (inequality rows; c(x) − ceq − p + n = 0 on equality
+ *     rows),  p, n >= 0,  the bounds of x and s
+ * until the return test holds, and leaves.  With p, n eliminated the Newton system is the one iem_kkt_assemble_diag /
+ * iem_kkt_solve_refined_diag solve: W is iem_jac_hess_coord with obj_weight = 0, r is iem_eval_residual with obj_weight = 0.  One
+ * restoration iteration:
+ *     iem_eval_residual(0);  iem_resto_error;  iem_jac_hess_coord(0);  iem_resto_terms;  iem_kkt_assemble_diag(dcon);  factor;
+ *     iem_kkt_solve_refined_diag;  iem_resto_step;  iem_resto_merit(0);  iem_resto_begin;
+ *     K × { iem_resto_trial, iem_cons, iem_resto_merit(1), iem_search_accept(inner, out, out + 1, mu, 1.0, alpha) };
+ *     iem_resto_update;  iem_obj_device;  iem_cons;  iem_barrier_merit;  iem_resto_check
+ * The host keeps the mu rule (iem_search_reset(inner) when mu changes), the delta_w retry and one status read (iem_resto_state).
+ * Notation: gaps, flags, sl, su, ml, mu_u and the row-side sigs, gs are those of the barrier contract above;  inf_j = c_j − ceq_j on
+ * an equality row, c_j − s_j on an inequality row;  rho is an option;  zeta is a host double of the caller (eta·sqrt(mu), eta = 1).
+ * Every operation is rounded once, in the order written.  The object owns p, n, zp, zn, dp, dn, dzp, dzn, pt, nt, sR, ws (ncon each)
+ * and xR, wx (nvar each) — ONE allocation in this order, zeroed at create — a block of 8 words (0 state (int64)  1 theta_start
+ * 2 theta, 3 phi of the last check  4 the maximum of iem_resto_leave  5–7 zero) and an INNER iem_search on the same barrier object
+ * with the options of the original one (iem_resto_search).
+ * iem_resto_enter (two launches; the caller passes mu = max(mu, max |inf|), out[2] of iem_barrier_error):  xR = x,  wx_i = m·m with
+ *     m = min(1, 1/|x_i|);  sR, ws likewise on inequality rows;  per row  h = (mu − rho·inf)/(2 rho),  n = h + sqrt(h·h +
+ *     (mu·inf)/(2 rho)),  p = inf + n,  zp = mu/p,  zn = mu/n,  y_j = 0;  every present bound multiplier z = min(rho, z).  Then one
+ *     workgroup of 64 adds ((1 − gamma_theta)·theta0, phi0 − gamma_phi·theta0) from words 3 and 2 of the ORIGINAL block to the
+ *     ORIGINAL filter by the rule of iem_search_accept (dominated entries leave first, order kept, a full filter sets flag bit 1) and
+ *     writes theta_start = theta0, NaN into words 2, 3 and state ACTIVE into the object's block.
+ * iem_resto_terms:  variable:  zw = zeta·wx,  sigma = (sl + su) + zw,  gx = (mu_u − ml) + zw·(x − xR),  rhs = −(r + gx).  Row:
+ *     rc = (inf − p) + n,  Dp = p/zp,  Dn = n/zn,  ep = (mu − p·(rho − y))/zp,  en = (mu − n·(rho + y))/zn,  t = (rc − ep) + en,
+ *     D = Dp + Dn.  Equality row: dcon = D, rhs_y = −t.  Inequality row:  zs = zeta·ws,  sigs' = sigs + zs,  gsr = gs + zs·(s − sR),
+ *     rs' = gsr − y,  inv = 1/sigs',  dcon = inv + D,  rhs_y = −(t + rs'·inv).
+ * iem_resto_step:  ds = (dy − rs')/sigs';  dz*, dv* by the formulas of iem_barrier_step;  into the object  dp = ep + Dp·dy,
+ *     dn = en − Dn·dy,  dzp = ((rho − y) − zp) − dy,  dzn = ((rho + y) − zn) + dy.  Step lengths as in iem_barrier_step (seed 1.0,
+ *     integer minimum on bit patterns, a NaN direction or a candidate not > 0 gives +0.0), with the further candidates
+ *     ((−tau)·p)/dp where dp < 0, ((−tau)·n)/dn where dn < 0 for alpha_primal and ((−tau)·zp)/dzp where dzp < 0, ((−tau)·zn)/dzn
+ *     where dzn < 0 for alpha_dual.
+ * iem_resto_merit(which): at (x, s, c) with (p, n) (which = 0), or at the trial point the caller passes with (pt, nt) (which = 1):
+ *     S0 = sum_j (p + n),  S1 = sum_i wx·((x − xR)·(x − xR)) + sum_ineq ws·((s − sR)·(s − sR)),  theta_R = sum_j |(inf − p) + n|,
+ *     L = sum log gap + sum_j log p + sum_j log n;  out[0] = rho·S0 + (0.5·zeta)·S1,  out[1] = theta_R,  out[2] = L.  A lane adds its
+ *     entries in index order (per row: the slack's gaps, then p, then n); the totals are summed in the fixed order of the barrier
+ *     sums.  iem_search_accept(inner, out, out + 1, mu, 1.0, alpha) IS the restoration's acceptance test.
+ * iem_resto_begin: the slope  sum_i gx·dx + sum_ineq gsr·ds + sum_j ((rho − mu/p)·dp + (rho − mu/n)·dn)  and the INNER block word
+ *     for word as iem_search_begin leaves it, with phi0 = merit0[0] − mu·merit0[2], theta0 = merit0[1], alpha_max = alpha[0].
+ * iem_resto_trial: with the inner block's alpha  xt, st as iem_search_trial and  pt = p + alpha·dp,  nt = n + alpha·dn;  under FAILED
+ *     / UNUSABLE it stores nothing.
+ * iem_resto_update: the rules of iem_barrier_update (either step length +0.0: nothing moves), and  p += alpha_p·dp,
+ *     n += alpha_p·dn,  zp, zn stepped by alpha_d and guarded against the new p, n.
+ * iem_resto_error: the layout of iem_barrier_error:  [0] max |(r + zw·(x − xR)) − zL + zU| (NaN without r)  [1] max over rows of
+ *     |(rho − y) − zp|, |(rho + y) − zn| and on inequality rows |(zs·(s − sR) − y) − vL + vU|  [2] max |rc|  [3] max |gap·z − mu|
+ *     including p·zp, n·zn  [4] sum |y|  [5] sum of the multipliers including zp, zn  [6] theta_R  [7] L (the bits of
+ *     iem_resto_merit(0)'s out[1], out[2]).  The scaled error applies with the counts (ncon, nz + 2 ncon).
+ * iem_resto_check (one workgroup; d_f from iem_obj_device, d_merit from iem_barrier_merit at the new iterate, mu the ORIGINAL
+ *     problem's):  theta = d_merit[0],  phi = d_f − mu·d_merit[1].  With state ACTIVE: both are stored in words 2, 3, and the state
+ *     becomes RETURN iff theta, phi are finite, theta <= kappa_resto·theta_start, theta <= theta_max (word 6 of the ORIGINAL block)
+ *     and no ORIGINAL filter entry dominates (theta, phi).  With any other state nothing is written.
+ * iem_resto_leave (two launches): the integer maximum of the present bound multipliers; then y = 0, every present bound multiplier
+ *     becomes 1.0 iff that maximum exceeds bound_mult_reset_threshold (or is a NaN), and state NONE.
+ * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create, nothing synchronises and nothing
+ * is copied to the host, except by iem_resto_state.  IEM_E_ARG before any device work: null required pointers (the slack side may
+ * be NULL without inequality rows), rho <= 0, kappa_resto outside (0, 1), mu < 0, zeta < 0, tau outside (0, 1], which outside
+ * {0, 1}.  The object borrows the search object and through it the barrier object: destroy it before them.  Not here: Ipopt's
+ * alpha_min rule as the trigger (the host enters on FAILED), a second-order correction of the restoration, a nested restoration,
+ * sharded handles. */
+typedef struct iem_resto iem_resto;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_resto_opts_t) */
+  double rho, kappa_resto, bound_mult_reset_threshold;
+} iem_resto_opts_t;                     /* NULL = Ipopt's defaults: 1000, 0.9, 1000 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_resto_state_t): at most that many bytes are written */
+  int64_t state;                        /* word 0 of the block */
+  double theta_start, theta, phi;       /* words 1–3 */
+} iem_resto_state_t;
+enum { IEM_RESTO_NONE = 0, IEM_RESTO_ACTIVE = 1, IEM_RESTO_RETURN = 2 };
+int iem_resto_create(iem_search *fs, const iem_resto_opts_t *opts, iem_resto **out);
+int iem_resto_destroy(iem_resto *q);
+int iem_resto_search(const iem_resto *q, iem_search **out_inner);      /* the inner search: owned by the object, never to be destroyed */
+int iem_resto_enter(iem_resto *q, const double *d_x, const double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU,
+                    const double *d_c, double mu);
+int iem_resto_terms(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                    const double *d_vU, const double *d_r, const double *d_c, double mu, double zeta, double *d_sigma, double *d_dcon, double *d_rhs);
+int iem_resto_step(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                   const double *d_vU, const double *d_sol, double mu, double tau, double zeta, double *d_ds, double *d_dzL, double *d_dzU,
+                   double *d_dvL, double *d_dvU, double *d_alpha /* 2 */);
+int iem_resto_merit(iem_resto *q, int which, const double *d_x, const double *d_s, const double *d_c, double zeta, double *d_out /* 3 */);
+int iem_resto_begin(iem_resto *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, const double *d_merit0 /* 3 */,
+                    const double *d_alpha /* 2 */, double mu, double zeta);
+int iem_resto_trial(iem_resto *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, double *d_xt, double *d_st);
+int iem_resto_update(iem_resto *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
+                     const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha /* 2 */,
+                     double mu, double kappa_sigma);
+int iem_resto_error(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                    const double *d_vU, const double *d_r /* may be NULL */, const double *d_c, double mu, double zeta, double *d_out /* 8 */);
+int iem_resto_check(iem_resto *q, const double *d_f, const double *d_merit /* 2 */, double mu);
+int iem_resto_leave(iem_resto *q, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU);
+int iem_resto_device(const iem_resto *q, double **d_p, double **d_n, double **d_zp, double **d_zn, void **d_block);      /* any may be NULL */
+int iem_resto_state(iem_resto *q, iem_resto_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the twelve kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_resto_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

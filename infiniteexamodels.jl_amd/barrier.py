@@ -417,3 +417,198 @@ class SecondOrderCorrection:
                 self.close()
         except Exception:
             pass
+
+
+class Restoration:
+    """``Restoration(search, rho=1000, kappa_resto=0.9, bound_mult_reset_threshold=1000)``: the feasibility restoration phase of the
+    C-ABI (``iem_resto_*``, ``csrc/iem_resto_device.h``) beside the :class:`FilterSearch` of the ORIGINAL problem — the elastic
+    variables ``p, n``, their multipliers and directions, the reference point and an INNER :class:`FilterSearch`-like object
+    (:attr:`inner`) live on the device; no read-back but :meth:`state`.  When ``search.state()`` says ``failed``:
+
+        resto.enter(state, c, max(mu, max|inf|))                       # err[2] of bar.error is max|inf|
+        while resto.state()["state_name"] == "active":                 # one status read per iteration
+            model.eval_residual(x, y, 0.0, c=c, out=r)                 # r = J'y
+            resto.error(state, r, c, mu_R, zeta)                       # the restoration's own mu rule (inner.reset() on change)
+            model.jac_hess_coord(x, y, jv, hv, obj_weight=0.0)
+            sigma, dcon, rhs = resto.terms(state, r, c, mu_R, zeta)
+            kkt.assemble(hv, jv, sigma, dw, dc, dcon=dcon); kkt.factor(); sol = kkt.solve(rhs, refine=1)
+            dirs, alpha = resto.step(state, sol, mu_R, tau, zeta)
+            m0 = resto.merit(0, x, s, c, zeta); resto.begin(state, sol, dirs[0], m0, alpha, mu_R, zeta)
+            for _ in range(K):
+                resto.trial(state, sol, dirs[0], xt, st); model.cons(xt, ct); mt = resto.merit(1, xt, st, ct, zeta)
+                resto.inner.accept(mt[0:1], mt[1:3], mu_R, alpha)
+            resto.update(state, sol, dirs, alpha, mu_R)
+            model.obj_device(x, out=f); model.cons(x, c); bar.merit(x, s, c, out=m2); resto.check(f, m2, mu)
+        resto.leave(state)
+
+    ``zeta = sqrt(mu_R)``."""
+
+    def __init__(self, search: FilterSearch, **opts):
+        self.search = search
+        self.layer = search.layer
+        self._q = None
+        self.inner = None
+        o = _lib.RestoOpts.defaults(**opts)
+        self.opts = {name: getattr(o, name) for name, _ in _lib.RestoOpts._fields_ if name != "struct_size"}
+        L, s = search._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_resto_create(s, C.byref(o), C.byref(q)))
+        self._q = q
+        inner = C.c_void_p()
+        _lib.check(L.iem_resto_search(q, C.byref(inner)))
+        self.inner = _BorrowedSearch(self.layer, inner, search.opts)
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("Restoration: closed")
+        L, _ = self.search._handle()
+        return L, self._q
+
+    def enter(self, state, c, mu: float):
+        """The elastic start, the reference point, ``y = 0``, the bound multipliers clipped at ``rho`` IN PLACE, and the current point
+        into the ORIGINAL filter (``iem_resto_enter``); ``mu``: ``max(mu, max|inf|)``.  State ``active``."""
+        bar = self.layer
+        p = bar._state(state)
+        pc = bar._vec(c, bar.ncon, "c")
+        L, q = self._handle()
+        _lib.check(L.iem_resto_enter(q, *p, pc, float(mu)))
+        return state
+
+    def terms(self, state, r, c, mu: float, zeta: float, out=None):
+        """``(sigma, dcon, rhs)`` of the restoration's Newton system (``iem_resto_terms``); ``r = Jᵀy`` (``obj_weight = 0``)."""
+        bar = self.layer
+        sigma, dcon, rhs = out if out is not None else (bar._new(bar.nvar), bar._new(bar.ncon), bar._new(bar.n))
+        p = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(c, bar.ncon, "c"), float(mu), float(zeta), bar._vec(sigma, bar.nvar, "sigma"), bar._vec(dcon, bar.ncon, "dcon"),
+                bar._vec(rhs, bar.n, "rhs"))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_terms(q, *p, *args))
+        return sigma, dcon, rhs
+
+    def step(self, state, sol, mu: float, tau: float, zeta: float, out=None, alpha=None):
+        """``((ds, dzL, dzU, dvL, dvU), alpha)``; ``dp, dn, dzp, dzn`` stay in the object (``iem_resto_step``)."""
+        bar = self.layer
+        dirs = out if out is not None else (bar._new(bar.ncon), bar._new(bar.nvar), bar._new(bar.nvar), bar._new(bar.ncon), bar._new(bar.ncon))
+        alpha = alpha if alpha is not None else bar._new(2)
+        p, d = bar._state(state), bar._dirs(dirs)
+        ps, pa = bar._vec(sol, bar.n, "sol"), bar._vec(alpha, 2, "alpha")
+        L, q = self._handle()
+        _lib.check(L.iem_resto_step(q, *p, ps, float(mu), float(tau), float(zeta), *d, pa))
+        return dirs, alpha
+
+    def merit(self, which: int, x, s, c, zeta: float, out=None):
+        """``(rho·Σ(p + n) + zeta/2·proximity, θ_R, Σ log)`` as a device tensor (``iem_resto_merit``): at the state with ``(p, n)``
+        (``which = 0``) or at a trial point with ``(pt, nt)`` (``which = 1``)."""
+        bar = self.layer
+        out = out if out is not None else bar._new(3)
+        args = (bar._vec(x, bar.nvar, "x"), bar._vec(s, bar.ncon, "s", optional=bar.info["n_ineq"] == 0), bar._vec(c, bar.ncon, "c"), float(zeta), bar._vec(out, 3, "out"))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_merit(q, int(which), *args))
+        return out
+
+    def begin(self, state, sol, ds, merit0, alpha, mu: float, zeta: float):
+        """The slope of the restoration's barrier objective and the INNER block of a new search (``iem_resto_begin``)."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(sol, bar.n, "sol"),
+                bar._vec(ds, bar.ncon, "ds", optional=slack), bar._vec(merit0, 3, "merit0"), bar._vec(alpha, 2, "alpha"))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_begin(q, *args, float(mu), float(zeta)))
+
+    def trial(self, state, sol, ds, xt=None, st=None):
+        """``(xt, st)`` with the inner block's ``α``; ``pt, nt`` stay in the object (``iem_resto_trial``)."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        xt = xt if xt is not None else bar._new(bar.nvar)
+        st = st if st is not None else bar._new(bar.ncon)
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(sol, bar.n, "sol"),
+                bar._vec(ds, bar.ncon, "ds", optional=slack), bar._vec(xt, bar.nvar, "xt"), bar._vec(st, bar.ncon, "st", optional=slack))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_trial(q, *args))
+        return xt, st
+
+    def update(self, state, sol, dirs, alpha, mu: float, kappa_sigma: float = 1e10):
+        """The accepted step IN PLACE, ``p, n, zp, zn`` included (``iem_resto_update``).  Returns ``state``."""
+        bar = self.layer
+        p, d = bar._state(state), bar._dirs(dirs)
+        ps, pa = bar._vec(sol, bar.n, "sol"), bar._vec(alpha, 2, "alpha")
+        L, q = self._handle()
+        _lib.check(L.iem_resto_update(q, *p, ps, *d, pa, float(mu), float(kappa_sigma)))
+        return state
+
+    def error(self, state, r, c, mu: float, zeta: float, out=None):
+        """The eight numbers of ``iem_resto_error`` (the layout of ``BarrierLayer.error``) as a device tensor;
+        ``BarrierLayer.optimality_error`` applies with the counts ``(ncon, nz + 2·ncon)``."""
+        bar = self.layer
+        out = out if out is not None else bar._new(8)
+        p = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r", optional=True), bar._vec(c, bar.ncon, "c"), float(mu), float(zeta), bar._vec(out, 8, "out"))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_error(q, *p, *args))
+        return out
+
+    def check(self, f, merit, mu: float):
+        """The return test against the ORIGINAL filter (``iem_resto_check``): ``f`` a device tensor of one, ``merit`` the two numbers of
+        ``BarrierLayer.merit`` at the new iterate, ``mu`` the ORIGINAL problem's."""
+        bar = self.layer
+        args = (bar._vec(f, 1, "f"), bar._vec(merit, 2, "merit"), float(mu))
+        L, q = self._handle()
+        _lib.check(L.iem_resto_check(q, *args))
+
+    def leave(self, state):
+        """``y = 0``, the bound multipliers reset to 1 iff their maximum exceeds the threshold, state ``none`` (``iem_resto_leave``)."""
+        p = self.layer._state(state)
+        L, q = self._handle()
+        _lib.check(L.iem_resto_leave(q, p[2], p[3], p[4], p[5], p[6]))
+        return state
+
+    def state(self):
+        """THE read-back (``iem_resto_state``, synchronises): words 0–3 of the object's block, ``state`` also by name."""
+        L, q = self._handle()
+        v = _lib.RestoState()
+        v.struct_size = C.sizeof(_lib.RestoState)
+        _lib.check(L.iem_resto_state(q, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.RestoState._fields_ if name != "struct_size"}
+        out["state_name"] = _lib.RESTO_STATE[out["state"]] if 0 <= out["state"] < len(_lib.RESTO_STATE) else "?"
+        return out
+
+    def device(self):
+        """``dict(p, n, zp, zn, block)``: addresses on the device (``iem_resto_device``); the object's vectors are ONE allocation in
+        the order of ``include/iem.h``, ``p`` first."""
+        L, q = self._handle()
+        ptr = [C.c_void_p() for _ in range(5)]
+        _lib.check(L.iem_resto_device(q, *[C.byref(a) for a in ptr]))
+        return dict(zip(("p", "n", "zp", "zn", "block"), (a.value for a in ptr)))
+
+    def close(self):
+        if self._q is not None:
+            if self.inner is not None:
+                self.inner._s = None      # owned by the object: destroyed with it
+            _lib.check(self.layer.model._L.iem_resto_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.search._s is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
+class _BorrowedSearch(FilterSearch):
+    """the inner search of a :class:`Restoration`: every call of :class:`FilterSearch` on a handle the restoration object owns"""
+
+    def __init__(self, layer: BarrierLayer, handle, opts):
+        self.layer = layer
+        self._s = handle
+        self.opts = dict(opts)
+
+    def close(self):
+        self._s = None

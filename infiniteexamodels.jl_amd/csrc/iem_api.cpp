@@ -58,6 +58,9 @@ static const char *kSearchSource =        // the filter line search (iem_search_
 static const char *kSocSource =           // the second-order correction of the search (iem_soc_*): a code object of its own, behind no helpers — not a row of kFixed
 #include "iem_soc_device_h.inc"
     ;
+static const char *kRestoSource =         // the feasibility restoration phase (iem_resto_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_resto_device_h.inc"
+    ;
 
 namespace {
 
@@ -322,6 +325,8 @@ struct iem_model {
   struct SearchObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, trial = nullptr, accept = nullptr; } search;
   // the code object of the second-order correction (iem_soc_*): loaded by the first iem_soc_create of the handle
   struct SocObject { hipModule_t mod = nullptr; hipFunction_t open = nullptr, rhs = nullptr, trial = nullptr, accept = nullptr, select = nullptr; } soc;
+  // the code object of the feasibility restoration phase (iem_resto_*): loaded by the first iem_resto_create of the handle
+  struct RestoObject { hipModule_t mod = nullptr; hipFunction_t fn[12] = {}; } resto;
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1363,6 +1368,7 @@ int iem_destroy(iem_model *m) {
   for (auto &o : m->fixed) if (o.mod) hipModuleUnload(o.mod);
   if (m->search.mod) hipModuleUnload(m->search.mod);
   if (m->soc.mod) hipModuleUnload(m->soc.mod);
+  if (m->resto.mod) hipModuleUnload(m->resto.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -4440,6 +4446,324 @@ int iem_soc_state(iem_soc *q, iem_soc_state_t *out) {
   v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
   std::memcpy(&v.status, w + 9, 8);
   std::memcpy(&v.state, w + 13, 3 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+/* ---- the feasibility restoration phase: elastic start, terms, step, merit, inner search, return test (csrc/iem_resto_device.h) ---- */
+struct iem_resto {
+  iem_search *s = nullptr;             // the ORIGINAL problem's search (borrowed): its filter and control block
+  iem_search *inner = nullptr;         // the restoration problem's own search (owned), on the same barrier object
+  iem_resto_opts_t opt;
+  double *d_vec = nullptr;             // p | n | zp | zn | dp | dn | dzp | dzn | pt | nt | sR | ws (ncon each) | xR | wx (nvar each)
+  double *d_blk = nullptr;             // the block: 8 words
+  double *d_red = nullptr;             // 4 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+};
+
+namespace {
+// RestoArgs of csrc/iem_resto_device.h
+struct RestoArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c, *sol;
+  double *ds, *dzL, *dzU, *dvL, *dvU;
+  double *sigma, *dcon, *rhs;
+  unsigned long long *alpha;
+  double *out;
+  double *xt, *st;
+  const double *merit0, *f, *merit;
+  double *p, *n_, *zp, *zn, *dp, *dn, *dzp, *dzn, *pt, *nt, *sR, *ws, *xR, *wx;
+  double *blk;
+  double *octl, *ofilter;
+  double *ictl;
+  double *red;
+  const long long *tab;
+  double mu, tau, kappa, zeta, rho, kappa_resto, threshold, gamma_theta, gamma_phi;
+  long long capacity, which;
+  long long nvar, n, n_wg;
+};
+enum { RES_ENTER, RES_ENTER_FILTER, RES_TERMS, RES_STEP, RES_MERIT, RES_BEGIN, RES_TRIAL, RES_UPDATE, RES_ERROR, RES_CHECK, RES_LEAVE_MAX, RES_LEAVE, RES_KERNELS };
+const char *const kRestoKernels[RES_KERNELS] = {"resto_enter", "resto_enter_filter", "resto_terms", "resto_step", "resto_merit", "resto_begin",
+                                                "resto_trial", "resto_update", "resto_error", "resto_check", "resto_leave_max", "resto_leave"};
+RestoArgsH resto_args(const iem_resto *q) {
+  const iem_search *s = q->s;
+  const iem_barrier *b = s->b;
+  RestoArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  double *v = q->d_vec;
+  const int64_t m = b->ncon;
+  A.p = v; A.n_ = v + m; A.zp = v + 2 * m; A.zn = v + 3 * m; A.dp = v + 4 * m; A.dn = v + 5 * m; A.dzp = v + 6 * m; A.dzn = v + 7 * m;
+  A.pt = v + 8 * m; A.nt = v + 9 * m; A.sR = v + 10 * m; A.ws = v + 11 * m; A.xR = v + 12 * m; A.wx = A.xR + b->nvar;
+  A.blk = q->d_blk; A.octl = s->d_ctl; A.ofilter = s->d_filter; A.ictl = q->inner->d_ctl;
+  A.red = q->d_red; A.tab = b->d_tab;
+  A.rho = q->opt.rho; A.kappa_resto = q->opt.kappa_resto; A.threshold = q->opt.bound_mult_reset_threshold;
+  A.gamma_theta = s->opt.gamma_theta; A.gamma_phi = s->opt.gamma_phi; A.capacity = (long long)s->opt.filter_capacity;
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int resto_object(iem_model *m) {
+  iem_model::RestoObject &o = m->resto;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kRestoSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[RES_KERNELS];
+  for (int k = 0; k < RES_KERNELS; ++k) slots[k] = KernelSlot{kRestoKernels[k], &o.fn[k]};
+  return load_object(m, src, slots, RES_KERNELS, &o.mod);
+}
+int resto_launch(const iem_resto *q, int which, RestoArgsH &A, bool one_wave = false) {
+  iem_model *m = q->s->b->m;
+  return kkt_launch_raw(m, m->resto.fn[which], &A, sizeof A, one_wave ? 1 : q->s->b->n_wg, one_wave ? 64 : 256);
+}
+int resto_opts(const iem_resto_opts_t *in, iem_resto_opts_t *out) {
+  iem_resto_opts_t v = {sizeof v, 1000.0, 0.9, 1000.0};      // Ipopt's rho, required_infeasibility_reduction, bound_mult_reset_threshold
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_resto_create: set struct_size to sizeof(iem_resto_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  if (!(v.rho > 0.0) || !std::isfinite(v.rho)) return fail(IEM_E_ARG, "iem_resto_create: rho must be positive");
+  if (!(v.kappa_resto > 0.0) || !(v.kappa_resto < 1.0)) return fail(IEM_E_ARG, "iem_resto_create: kappa_resto must lie in (0, 1)");
+  if (!(v.bound_mult_reset_threshold >= 0.0)) return fail(IEM_E_ARG, "iem_resto_create: bound_mult_reset_threshold must not be negative");
+  *out = v;
+  return IEM_OK;
+}
+// mu, zeta, tau as every call checks them
+int resto_scalars(const char *call, double mu, double zeta, double tau = 1.0) {
+  if (!(mu >= 0.0)) return fail(IEM_E_ARG, std::string(call) + ": mu must not be negative");
+  if (!(zeta >= 0.0)) return fail(IEM_E_ARG, std::string(call) + ": zeta must not be negative");
+  if (!(tau > 0.0 && tau <= 1.0)) return fail(IEM_E_ARG, std::string(call) + ": tau must lie in (0, 1]");
+  return IEM_OK;
+}
+void resto_set_state(RestoArgsH &A, const double *x, const double *s, const double *y, const double *zL, const double *zU, const double *vL, const double *vU) {
+  A.x = (double *)x; A.s = (double *)s; A.y = (double *)y; A.zL = (double *)zL; A.zU = (double *)zU; A.vL = (double *)vL; A.vU = (double *)vU;
+}
+}  // namespace
+
+int iem_resto_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kRestoSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_resto_destroy(iem_resto *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->s->b->m->device);
+  if (q->inner) iem_search_destroy(q->inner);
+  for (void *p : {(void *)q->d_vec, (void *)q->d_blk, (void *)q->d_red})
+    if (p) hipFree(p);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_resto_create(iem_search *fs, const iem_resto_opts_t *opts, iem_resto **out) {
+  if (!fs || !out) return fail(IEM_E_ARG, "null argument");
+  iem_resto_opts_t opt;
+  {
+    int rc = resto_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_barrier *b = fs->b;
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = resto_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_resto *p) const { iem_resto_destroy(p); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_resto, Drop> q(new iem_resto);
+  q->s = fs;
+  q->opt = opt;
+  {
+    int rc = iem_search_create(b, &fs->opt, &q->inner);      // the restoration problem's own filter, with the options of the original search
+    if (rc) return rc;
+  }
+  const size_t n_vec = (size_t)std::max<int64_t>(12 * b->ncon + 2 * b->nvar, 1);
+  const int64_t n_red = 4 * b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&q->d_vec, n_vec * 8));
+  HIP_TRY(hipMalloc((void **)&q->d_blk, 8 * 8));
+  HIP_TRY(hipMalloc((void **)&q->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMemset(q->d_vec, 0, n_vec * 8));
+  HIP_TRY(hipMemset(q->d_blk, 0, 8 * 8));
+  HIP_TRY(hipMemset(q->d_red, 0, (size_t)n_red * 8));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_resto_search(const iem_resto *q, iem_search **out_inner) {
+  if (!q || !out_inner) return fail(IEM_E_ARG, "null argument");
+  *out_inner = q->inner;
+  return IEM_OK;
+}
+
+int iem_resto_enter(iem_resto *q, const double *d_x, const double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_c,
+                    double mu) {
+  int rc = resto_scalars("iem_resto_enter", mu, 0.0);
+  if (rc) return rc;
+  if (!q || barrier_state_missing(q->s->b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (q->s->b->ncon && !d_c)) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(q->s->b->m->device);
+  RestoArgsH A = resto_args(q);
+  resto_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  A.c = d_c; A.mu = mu;
+  if ((rc = resto_launch(q, RES_ENTER, A))) return rc;
+  return resto_launch(q, RES_ENTER_FILTER, A, true);
+}
+
+int iem_resto_terms(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                    const double *d_vU, const double *d_r, const double *d_c, double mu, double zeta, double *d_sigma, double *d_dcon, double *d_rhs) {
+  int rc = resto_scalars("iem_resto_terms", mu, zeta);
+  if (rc) return rc;
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->nvar && (!d_r || !d_sigma)) || (b->ncon && (!d_c || !d_dcon)) || !d_rhs)
+    return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  RestoArgsH A = resto_args(q);
+  resto_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  A.r = d_r; A.c = d_c; A.mu = mu; A.zeta = zeta; A.sigma = d_sigma; A.dcon = d_dcon; A.rhs = d_rhs;
+  return resto_launch(q, RES_TERMS, A);
+}
+
+int iem_resto_step(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                   const double *d_vU, const double *d_sol, double mu, double tau, double zeta, double *d_ds, double *d_dzL, double *d_dzU,
+                   double *d_dvL, double *d_dvU, double *d_alpha) {
+  int rc = resto_scalars("iem_resto_step", mu, zeta, tau);
+  if (rc) return rc;
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
+      (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  RestoArgsH A = resto_args(q);
+  resto_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  A.sol = d_sol; A.mu = mu; A.tau = tau; A.zeta = zeta; A.ds = d_ds; A.dzL = d_dzL; A.dzU = d_dzU; A.dvL = d_dvL; A.dvU = d_dvU;
+  A.alpha = (unsigned long long *)d_alpha;
+  HIP_TRY(hipMemcpyAsync(d_alpha, b->d_ones, 16, hipMemcpyDeviceToDevice, m->stream));      // the seed: the bits of 1.0
+  return resto_launch(q, RES_STEP, A);
+}
+
+int iem_resto_merit(iem_resto *q, int which, const double *d_x, const double *d_s, const double *d_c, double zeta, double *d_out) {
+  int rc = resto_scalars("iem_resto_merit", 0.0, zeta);
+  if (rc) return rc;
+  if (which != 0 && which != 1) return fail(IEM_E_ARG, "iem_resto_merit: which must be 0 (the state) or 1 (the trial point)");
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->nvar && !d_x) || (b->n_ineq && !d_s) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  RestoArgsH A = resto_args(q);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.c = d_c; A.zeta = zeta; A.out = d_out; A.which = which;
+  return resto_launch(q, RES_MERIT, A);
+}
+
+int iem_resto_begin(iem_resto *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, const double *d_merit0, const double *d_alpha,
+                    double mu, double zeta) {
+  int rc = resto_scalars("iem_resto_begin", mu, zeta);
+  if (rc) return rc;
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->nvar && !d_x) || (b->n_ineq && (!d_s || !d_ds)) || !d_sol || !d_merit0 || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  RestoArgsH A = resto_args(q);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.sol = d_sol; A.ds = (double *)d_ds; A.merit0 = d_merit0; A.alpha = (unsigned long long *)d_alpha; A.mu = mu; A.zeta = zeta;
+  return resto_launch(q, RES_BEGIN, A);
+}
+
+int iem_resto_trial(iem_resto *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, double *d_xt, double *d_st) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->nvar && (!d_x || !d_xt)) || (b->n_ineq && (!d_s || !d_ds || !d_st)) || !d_sol) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  RestoArgsH A = resto_args(q);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.sol = d_sol; A.ds = (double *)d_ds; A.xt = d_xt; A.st = d_st;
+  return resto_launch(q, RES_TRIAL, A);
+}
+
+int iem_resto_update(iem_resto *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
+                     const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha, double mu,
+                     double kappa_sigma) {
+  int rc = resto_scalars("iem_resto_update", mu, 0.0);
+  if (rc) return rc;
+  if (!(kappa_sigma >= 1.0)) return fail(IEM_E_ARG, "iem_resto_update: kappa_sigma must be at least 1");
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
+      (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
+    return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(b->m->device);
+  RestoArgsH A = resto_args(q);
+  resto_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  A.sol = d_sol; A.ds = (double *)d_ds; A.dzL = (double *)d_dzL; A.dzU = (double *)d_dzU; A.dvL = (double *)d_dvL; A.dvU = (double *)d_dvU;
+  A.alpha = (unsigned long long *)d_alpha; A.mu = mu; A.kappa = kappa_sigma;
+  return resto_launch(q, RES_UPDATE, A);
+}
+
+int iem_resto_error(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                    const double *d_vU, const double *d_r, const double *d_c, double mu, double zeta, double *d_out) {
+  int rc = resto_scalars("iem_resto_error", mu, zeta);
+  if (rc) return rc;
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  RestoArgsH A = resto_args(q);
+  resto_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  A.r = d_r; A.c = d_c; A.mu = mu; A.zeta = zeta; A.out = d_out;
+  HIP_TRY(hipMemsetAsync(d_out, 0, 4 * 8, m->stream));      // the four maxima start from +0.0
+  return resto_launch(q, RES_ERROR, A);
+}
+
+int iem_resto_check(iem_resto *q, const double *d_f, const double *d_merit, double mu) {
+  int rc = resto_scalars("iem_resto_check", mu, 0.0);
+  if (rc) return rc;
+  if (!q || !d_f || !d_merit) return fail(IEM_E_ARG, "null argument");
+  DevGuard dg_(q->s->b->m->device);
+  RestoArgsH A = resto_args(q);
+  A.f = d_f; A.merit = d_merit; A.mu = mu;
+  return resto_launch(q, RES_CHECK, A, true);
+}
+
+int iem_resto_leave(iem_resto *q, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->s->b;
+  if ((b->nvar && (!d_zL || !d_zU)) || (b->ncon && !d_y) || (b->n_ineq && (!d_vL || !d_vU))) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  RestoArgsH A = resto_args(q);
+  A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  HIP_TRY(hipMemsetAsync(q->d_blk + 4, 0, 8, m->stream));      // the maximum starts from +0.0
+  int rc = resto_launch(q, RES_LEAVE_MAX, A);
+  return rc ? rc : resto_launch(q, RES_LEAVE, A);
+}
+
+int iem_resto_device(const iem_resto *q, double **d_p, double **d_n, double **d_zp, double **d_zn, void **d_block) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const int64_t m = q->s->b->ncon;
+  if (d_p) *d_p = q->d_vec;
+  if (d_n) *d_n = q->d_vec + m;
+  if (d_zp) *d_zp = q->d_vec + 2 * m;
+  if (d_zn) *d_zn = q->d_vec + 3 * m;
+  if (d_block) *d_block = q->d_blk;
+  return IEM_OK;
+}
+
+int iem_resto_state(iem_resto *q, iem_resto_state_t *out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_resto_state: set struct_size to sizeof(iem_resto_state_t) before the call");
+  iem_model *m = q->s->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[8];
+  HIP_TRY(hipMemcpyAsync(w, q->d_blk, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_resto_state_t v;
+  static_assert(sizeof v == 5 * 8, "iem_resto_state_t: struct_size, then words 0-3 of the block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.state, w, 4 * 8);
   std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
   return IEM_OK;
 }

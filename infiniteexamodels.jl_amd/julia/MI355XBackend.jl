@@ -648,6 +648,93 @@ function soc_device(c::SecondOrderCorrection)
     return p[]
 end
 
+# ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
+# Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
+# per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
+# resto_step!, resto_merit!(0), resto_begin!, K x (resto_trial!, cons, resto_merit!(1), search_accept! on resto.inner),
+# resto_update!, obj, cons, barrier_merit!, resto_check!; resto_leave! once resto_state says RETURN.  zeta = sqrt(mu).  UNEXECUTED, like the rest.
+struct IemRestoOpts        # iem_resto_opts_t
+    struct_size::UInt64
+    rho::Float64; kappa_resto::Float64; bound_mult_reset_threshold::Float64
+end
+struct IemRestoState       # iem_resto_state_t: words 0-3 of the object's block
+    struct_size::UInt64
+    state::Int64      # 0 none, 1 active, 2 return
+    theta_start::Float64; theta::Float64; phi::Float64
+end
+mutable struct Restoration
+    q::Ptr{Cvoid}
+    search::FilterSearch      # the ORIGINAL problem's, borrowed: kept alive
+    inner::Ptr{Cvoid}         # the restoration problem's own search: owned by the object
+end
+function Restoration(f::FilterSearch; rho = 1000.0, kappa_resto = 0.9, bound_mult_reset_threshold = 1000.0)
+    opts = Ref(IemRestoOpts(sizeof(IemRestoOpts), rho, kappa_resto, bound_mult_reset_threshold))
+    q, inner = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_resto_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemRestoOpts}, Ptr{Ptr{Cvoid}}), f.s, opts, q))
+    check(ccall((:iem_resto_search, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), q[], inner))
+    r = Restoration(q[], f, inner[])
+    finalizer(c -> (c.q == C_NULL || ccall((:iem_resto_destroy, LIBIEM), Cint, (Ptr{Cvoid},), c.q); c.q = C_NULL), r)
+    return r
+end
+# mu: max(mu, max |inf|) — out[3] of barrier_error!
+resto_enter!(r::Restoration, state, cons, mu) =
+    check(ccall((:iem_resto_enter, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble), r.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), spptr(cons), mu))
+function resto_terms!(r::Restoration, state, res, cons, mu, zeta, sigma, dcon, rhs)
+    check(ccall((:iem_resto_terms, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                r.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), spptr(res), spptr(cons), mu, zeta, spptr(sigma), spptr(dcon), dptr(rhs)))
+    return sigma, dcon, rhs
+end
+function resto_step!(r::Restoration, state, sol, mu, tau, zeta, dirs, alpha)
+    check(ccall((:iem_resto_step, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                r.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(sol), mu, tau, zeta, spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha)))
+    return dirs, alpha
+end
+# which = 0: at the state with (p, n); 1: at the trial point with (pt, nt).  out: three doubles
+function resto_merit!(r::Restoration, which, x, s, cons, zeta, out)
+    check(ccall((:iem_resto_merit, LIBIEM), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Ptr{Float64}), r.q, which, spptr(x), spptr(s), spptr(cons), zeta, dptr(out)))
+    return out
+end
+resto_begin!(r::Restoration, state, sol, ds, merit0, alpha, mu, zeta) =
+    check(ccall((:iem_resto_begin, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                r.q, spptr(state[1]), spptr(state[2]), dptr(sol), spptr(ds), dptr(merit0), dptr(alpha), mu, zeta))
+function resto_trial!(r::Restoration, state, sol, ds, xt, st)
+    check(ccall((:iem_resto_trial, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                r.q, spptr(state[1]), spptr(state[2]), dptr(sol), spptr(ds), spptr(xt), spptr(st)))
+    return xt, st
+end
+# the restoration's acceptance test: iem_search_accept on the inner search, with merit = the three of resto_merit!(1)
+resto_accept!(r::Restoration, merit, mu, alpha) =
+    check(ccall((:iem_search_accept, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}), r.inner, dptr(merit), dptr(merit) + 8, mu, 1.0, dptr(alpha)))
+resto_reset!(r::Restoration) = check(ccall((:iem_search_reset, LIBIEM), Cint, (Ptr{Cvoid},), r.inner))
+function resto_update!(r::Restoration, state, sol, dirs, alpha, mu; kappa_sigma = 1e10)
+    check(ccall((:iem_resto_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble),
+                r.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(sol), spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha), mu, kappa_sigma))
+    return state
+end
+# res may be nothing (out[1] is NaN then); out: eight doubles in the layout of barrier_error!
+function resto_error!(r::Restoration, state, res, cons, mu, zeta, out)
+    check(ccall((:iem_resto_error, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cdouble, Cdouble, Ptr{Float64}),
+                r.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), spptr(res), spptr(cons), mu, zeta, dptr(out)))
+    return out
+end
+# f: one double on the device, merit: the two of barrier_merit! at the new iterate, mu: the ORIGINAL problem's
+resto_check!(r::Restoration, f, merit, mu) = check(ccall((:iem_resto_check, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cdouble), r.q, dptr(f), dptr(merit), mu))
+resto_leave!(r::Restoration, state) =
+    check(ccall((:iem_resto_leave, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), r.q, spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7])))
+# the one read-back (synchronises the stream)
+function resto_state(r::Restoration)
+    st = Ref(IemRestoState(sizeof(IemRestoState), 0, 0, 0, 0))
+    check(ccall((:iem_resto_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemRestoState}), r.q, st))
+    return st[]
+end
+# (p, n, zp, zn, block) as device addresses; the object's vectors are one allocation in the order of include/iem.h
+function resto_device(r::Restoration)
+    p = [Ref{Ptr{Float64}}(C_NULL) for _ in 1:4]
+    blk = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_resto_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Float64}}, Ptr{Ptr{Cvoid}}), r.q, p[1], p[2], p[3], p[4], blk))
+    return p[1][], p[2][], p[3][], p[4][], blk[]
+end
+
 # ---- blob writer ----------------------------------------------------------------------------
 # Serialises a host ExaCore into the wire format of include/iem_blob.h.  [EXT]: the field and
 # type names of ExaModels' internal structs (Objective/Constraint linked lists, SIMDFunction,

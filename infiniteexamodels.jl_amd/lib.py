@@ -132,6 +132,29 @@ class SocState(C.Structure):
 SOC_STATE = ("none", "active", "accepted", "closed")
 
 
+class RestoOpts(C.Structure):
+    """``iem_resto_opts_t``: ``struct_size`` is set by the caller; ``RestoOpts.defaults()`` has Ipopt's values."""
+    _fields_ = [("struct_size", C.c_uint64), ("rho", C.c_double), ("kappa_resto", C.c_double), ("bound_mult_reset_threshold", C.c_double)]
+    DEFAULTS = dict(rho=1000.0, kappa_resto=0.9, bound_mult_reset_threshold=1000.0)
+
+    @classmethod
+    def defaults(cls, **over):
+        unknown = set(over) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown restoration option(s): {sorted(unknown)}")
+        o = cls(**{**cls.DEFAULTS, **over})
+        o.struct_size = C.sizeof(cls)
+        return o
+
+
+class RestoState(C.Structure):
+    """``iem_resto_state_t``: ``struct_size`` (set by the caller), then words 0-3 of the object's block."""
+    _fields_ = [("struct_size", C.c_uint64), ("state", C.c_int64), ("theta_start", C.c_double), ("theta", C.c_double), ("phi", C.c_double)]
+
+
+RESTO_STATE = ("none", "active", "return")
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("kind", C.c_int32), ("jit", C.c_int32), ("grid", C.c_int64 * 3),
                 ("lds_bytes", C.c_int64), ("alg_bytes_read", C.c_int64), ("alg_bytes_written", C.c_int64)]
@@ -143,7 +166,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_resto_create", "iem_resto_destroy", "iem_resto_search", "iem_resto_enter", "iem_resto_terms", "iem_resto_step", "iem_resto_merit", "iem_resto_begin", "iem_resto_trial", "iem_resto_update", "iem_resto_error", "iem_resto_check", "iem_resto_leave", "iem_resto_device", "iem_resto_state", "iem_resto_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -308,6 +331,22 @@ def lib():
     L.iem_soc_device.argtypes = [vp, C.POINTER(vp)]
     L.iem_soc_state.argtypes = [vp, C.POINTER(SocState)]
     L.iem_soc_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.iem_resto_create.argtypes = [vp, C.POINTER(RestoOpts), C.POINTER(vp)]
+    L.iem_resto_destroy.argtypes = [vp]
+    L.iem_resto_search.argtypes = [vp, C.POINTER(vp)]
+    L.iem_resto_enter.argtypes = [vp] + [vp] * 8 + [dbl]
+    L.iem_resto_terms.argtypes = [vp] + [vp] * 9 + [dbl, dbl] + [vp] * 3
+    L.iem_resto_step.argtypes = [vp] + [vp] * 8 + [dbl, dbl, dbl] + [vp] * 6
+    L.iem_resto_merit.argtypes = [vp, i32, vp, vp, vp, dbl, vp]
+    L.iem_resto_begin.argtypes = [vp] + [vp] * 6 + [dbl, dbl]
+    L.iem_resto_trial.argtypes = [vp] + [vp] * 6
+    L.iem_resto_update.argtypes = [vp] + [vp] * 14 + [dbl, dbl]
+    L.iem_resto_error.argtypes = [vp] + [vp] * 9 + [dbl, dbl, vp]
+    L.iem_resto_check.argtypes = [vp, vp, vp, dbl]
+    L.iem_resto_leave.argtypes = [vp] + [vp] * 5
+    L.iem_resto_device.argtypes = [vp] + [C.POINTER(vp)] * 5
+    L.iem_resto_state.argtypes = [vp, C.POINTER(RestoState)]
+    L.iem_resto_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_fixed_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -440,6 +479,12 @@ def soc_source():
     """HIP source of the second-order correction's kernels (``soc_open`` / ``soc_rhs`` / ``soc_trial`` / ``soc_accept`` /
     ``soc_select``: the ``iem_soc_*`` calls) and its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
     return _source(lib().iem_soc_source)
+
+
+def resto_source():
+    """HIP source of the feasibility restoration phase's kernels (``resto_enter`` ... ``resto_leave``: the ``iem_resto_*`` calls) and
+    its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
+    return _source(lib().iem_resto_source)
 
 
 def fixed_sources():
