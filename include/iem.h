@@ -827,7 +827,7 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * synchronises and nothing is copied to the host, except by iem_search_state.  IEM_E_ARG before any device work: null required
  * pointers (s, ds, st may be NULL without inequality rows), mu < 0, options out of range (gamma_theta, gamma_phi, eta_phi in (0, 1),
  * delta > 0, s_theta > 1, s_phi >= 1, alpha_floor >= 0, max_trials >= 1, 1 <= filter_capacity <= 1024).  The object borrows the barrier object (bounds,
- * flags, grid) and through it the model handle: destroy it before them.  Not here: the mu update, inertia correction,
+ * flags, grid) and through it the model handle: destroy it before them.  Not here: inertia correction (the mu update is the iem_mu object below),
  * Ipopt's alpha_min formula, sharded handles (iem_barrier_create refuses them); restoration is the iem_resto object below.  The second-order correction is the
  * iem_soc object below; words 13–15 of the block are its. */
 typedef struct iem_search iem_search;
@@ -947,7 +947,8 @@ int iem_soc_source(char **out_src, uint64_t *out_key);
  *     iem_kkt_solve_refined_diag;  iem_resto_step;  iem_resto_merit(0);  iem_resto_begin;
  *     K × { iem_resto_trial, iem_cons, iem_resto_merit(1), iem_search_accept(inner, out, out + 1, mu, 1.0, alpha) };
  *     iem_resto_update;  iem_obj_device;  iem_cons;  iem_barrier_merit;  iem_resto_check
- * The host keeps the mu rule (iem_search_reset(inner) when mu changes), the delta_w retry and one status read (iem_resto_state).
+ * The host keeps the restoration problem's mu rule (iem_search_reset(inner) when mu changes; the iem_mu object below serves the original
+ * problem only and iem_resto_* never reads its block), the delta_w retry and one status read (iem_resto_state).
  * Notation: gaps, flags, sl, su, ml, mu_u and the row-side sigs, gs are those of the barrier contract above;  inf_j = c_j − ceq_j on
  * an equality row, c_j − s_j on an inequality row;  rho is an option;  zeta is a host double of the caller (eta·sqrt(mu), eta = 1).
  * Every operation is rounded once, in the order written.  The object owns p, n, zp, zn, dp, dn, dzp, dzn, pt, nt, sR, ws (ncon each)
@@ -1032,6 +1033,80 @@ int iem_resto_device(const iem_resto *q, double **d_p, double **d_n, double **d_
 int iem_resto_state(iem_resto *q, iem_resto_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the twelve kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_resto_source(char **out_src, uint64_t *out_key);
+
+/* ---- the barrier parameter ---------------------------------------------------------------------------------------------------------
+ * mu, tau and the stopping test of a monotone (Fiacco–McCormick) interior-point method on the device (csrc/iem_mu_device.h), as an
+ * object beside iem_barrier: the error terms with what the rule needs of the complementarity products (iem_mu_error), and the rule
+ * (iem_mu_update).  The values live in a block on the device that the kernels of iem_barrier, iem_search and iem_soc read once their
+ * object is BOUND to it (iem_*_bind_mu below), so one captured iteration
+ *     iem_eval_residual;  iem_mu_error;  iem_mu_update(fs);  iem_barrier_terms;  ...;  iem_search_begin;  rungs;  iem_barrier_update
+ * replays across a change of mu, and the host reads one struct per iteration (iem_mu_state).
+ *
+ * THE BLOCK: sixteen 8-byte words on the device (iem_mu_device gives the pointer):
+ *     0 mu      1 tau = max(tau_min, 1 − mu)      2 zeta = sqrt(mu) (kept for a later restoration binding)      3 E(0)
+ *     4 E(mu) at the mu the call leaves behind      5 e_d      6 e_p      7 e_c(0)
+ *     8 status (int64): 0 ITERATING, 1 CONVERGED, 2 UNUSABLE      9 flags (int64): bit 0 = mu changed in the last update
+ *     10 decreases so far (int64)      11 updates so far (int64)      12–15 zero
+ * iem_mu_create writes words 0–2 from mu_init and zeroes the rest.  iem_mu_reset (one launch of one workgroup, asynchronous) writes
+ *     words 0–2 from mu0 and zeroes words 8–11; words 3–7 stay.
+ * iem_mu_error: ONE launch on the barrier object's grid behind one 96-byte device-to-device copy (the seed of the extremes), twelve
+ *     words.  [0]–[7] are bit for bit what iem_barrier_error(mu = 0) writes on the same inputs (the same per-lane order, the same
+ *     fixed-order totals; the partial sums are the object's own).  With p = gap·z over the present bounds, each product rounded once:
+ *     [8] the minimum of the p that are >= +0.0 (an integer minimum on bit patterns seeded with +inf; a negative product, −0.0 or a
+ *     NaN does not enter)  [9] the sum of all p, the lane's entries in index order, the totals in the fixed order of the barrier
+ *     sums  [10] the count of the p that did not enter [8], as a double (exact)  [11] +0.0.  d_r is required: no NaN form.
+ * iem_mu_update: ONE workgroup of 64 threads, one thread decides, each operation rounded once, every max / min propagating a NaN.
+ *     With w the twelve words, m = ncon and nz of iem_barrier_info:
+ *         sd = max(s_max, (w4 + w5)/max(1, m + nz))/s_max      sc = max(s_max, w5/max(1, nz))/s_max
+ *         e_d = max(w0, w1)/sd      e_p = m ? w2 : 0      e_c(mu) = nz ? max(w3 − mu, mu − w8)/sc : 0      E(mu) = max(max(e_d, e_p), e_c(mu))
+ *     (rounding is monotone, so max(w3 − mu, mu − w8) carries the bits of max |p − mu|: word 3 of iem_barrier_error at that mu).
+ *     w10 != 0 or E(0) a NaN: status UNUSABLE, mu, tau, zeta stay.  Else E(0) <= tol: CONVERGED, mu stays.  Else ITERATING and
+ *         k = 0;  while mu > mu_floor and E(mu) <= kappa_eps·mu and k < 64:  mu = max(mu_floor, min(kappa_mu·mu, mu·sqrt(mu)));  k += 1
+ *     (sqrt correctly rounded; the exponent 1.5 is Ipopt's mu_superlinear_decrease_power and not an option).  k > 0: words 0–2 are
+ *     rewritten, flag bit 0 is set, word 10 grows by k, and words 11 and 12 of fs's control block are zeroed when fs is given —
+ *     the 16 bytes of iem_search_reset.  k = 0: flag bit 0 is cleared, fs is untouched.  Word 11 grows by 1 and words 3–7 are
+ *     stored either way.
+ * BINDING: iem_barrier_bind_mu / iem_search_bind_mu / iem_soc_bind_mu (p = NULL unbinds; no launch — the first iem_barrier_bind_mu of a handle
+ *     loads the bound variant of the barrier code object, so bind outside a capture).  While an
+ *     object is bound, barrier_terms / step / update / error, search_begin / accept and soc_rhs / accept read mu from word 0 (and
+ *     barrier_step tau from word 1) where they read their argument before, once, at the same place: the host's mu and tau arguments
+ *     and their range checks are ignored.  Unbound, every call writes the bits it wrote before.  Binding is per object: the inner
+ *     search of an iem_resto borrows the same barrier object and keeps the restoration problem's own mu — bind the barrier object
+ *     only while the original problem iterates.  iem_resto_* never reads the block.
+ * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create, nothing synchronises and nothing
+ * is copied to the host, except by iem_mu_state.  IEM_E_ARG before any device work: null required pointers (the slack side may be
+ * NULL without inequality rows), mu_init <= 0, kappa_mu or tau_min outside (0, 1), kappa_eps <= 0, tol <= 0, mu_floor < 0,
+ * s_max <= 0, any option not finite, mu0 <= 0 or not finite, an fs or a bind across two barrier objects.  The object borrows the
+ * barrier object; a bound object borrows the block: unbind (or destroy the bound objects) before iem_mu_destroy.  Not here: the
+ * delta_w / inertia retry, adaptive (Mehrotra, quality-function) rules — words 8 and 9 of iem_mu_error are what they need —
+ * a binding for iem_resto, sharded handles. */
+typedef struct iem_mu iem_mu;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mu_opts_t) */
+  double mu_init, kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max;
+} iem_mu_opts_t;                        /* NULL = Ipopt's defaults: 0.1, 10, 0.2, 0.99, 1e-8, 0 (= max(1e-11, tol/10)), 100 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mu_state_t): at most that many bytes are written */
+  double mu, tau, zeta, e0, e_mu, e_d, e_p, e_c0;      /* words 0–7 of the block */
+  int64_t status, flags, decreases, updates;           /* words 8–11 */
+} iem_mu_state_t;
+enum { IEM_MU_ITERATING = 0, IEM_MU_CONVERGED = 1, IEM_MU_UNUSABLE = 2 };
+int iem_mu_create(iem_barrier *b, const iem_mu_opts_t *opts, iem_mu **out);
+int iem_mu_destroy(iem_mu *p);
+int iem_mu_reset(iem_mu *p, double mu0);
+int iem_mu_error(iem_mu *p, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                 const double *d_vU, const double *d_r, const double *d_c, double *d_out /* 12 */);
+int iem_mu_update(iem_mu *p, const double *d_out12, iem_search *fs /* may be NULL */);
+int iem_mu_device(const iem_mu *p, double **d_block);
+int iem_mu_state(iem_mu *p, iem_mu_state_t *out);      /* synchronises the stream: the one read-back */
+int iem_barrier_bind_mu(iem_barrier *b, const iem_mu *p /* NULL unbinds */);
+int iem_search_bind_mu(iem_search *fs, const iem_mu *p /* NULL unbinds */);
+int iem_soc_bind_mu(iem_soc *q, const iem_mu *p /* NULL unbinds */);
+/* HIP source of the three kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_mu_source(char **out_src, uint64_t *out_key);
+/* ... and of the BOUND variant of the barrier code object: the text of iem_barrier_source with BarrierArgs one pointer longer and the
+ * reads of mu and tau taken from the block; iem_barrier_bind_mu loads it.  iem_barrier_source, its key and the unbound calls are unchanged */
+int iem_barrier_mu_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

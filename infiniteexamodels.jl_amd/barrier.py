@@ -152,6 +152,13 @@ class BarrierLayer:
         _lib.check(L.iem_barrier_merit(b, *args))
         return out
 
+    def bind_mu(self, param=None):
+        """While bound to a :class:`BarrierParameter` (``iem_barrier_bind_mu``), :meth:`terms`, :meth:`step`, :meth:`update` and
+        :meth:`error` read ``mu`` (and ``step`` its ``tau``) from the parameter's block on the device; their ``mu`` / ``tau``
+        arguments are ignored.  ``None`` unbinds."""
+        L, b = self._handle()
+        _lib.check(L.iem_barrier_bind_mu(b, param._handle()[1] if param is not None else None))
+
     # ---- the one read-back -------------------------------------------------------------------------------------
     @staticmethod
     def optimality_error(out, mu_counts):
@@ -257,6 +264,12 @@ class FilterSearch:
         """A new barrier problem (``mu`` changed): the filter emptied, the flags cleared (``iem_search_reset``)."""
         L, s = self._handle()
         _lib.check(L.iem_search_reset(s))
+
+    def bind_mu(self, param=None):
+        """While bound to a :class:`BarrierParameter` (``iem_search_bind_mu``), :meth:`begin` and :meth:`accept` read ``mu`` from the
+        parameter's block on the device; their ``mu`` argument is ignored.  ``None`` unbinds."""
+        L, s = self._handle()
+        _lib.check(L.iem_search_bind_mu(s, param._handle()[1] if param is not None else None))
 
     def state(self):
         """THE read-back (``iem_search_state``, synchronises): the control block as a dict, ``status`` also by name."""
@@ -371,6 +384,12 @@ class SecondOrderCorrection:
         _lib.check(L.iem_soc_accept(q, *args))
         return alpha
 
+    def bind_mu(self, param=None):
+        """While bound to a :class:`BarrierParameter` (``iem_soc_bind_mu``), :meth:`rhs` and :meth:`accept` read ``mu`` from the
+        parameter's block on the device; their ``mu`` argument is ignored.  ``None`` unbinds."""
+        L, q = self._handle()
+        _lib.check(L.iem_soc_bind_mu(q, param._handle()[1] if param is not None else None))
+
     def select(self, sol_soc, dirs_soc, sol, dirs):
         """Iff the correction was accepted, ``sol_soc`` and ``dirs_soc = (ds, dzL, dzU, dvL, dvU)`` are copied over ``sol`` and
         ``dirs`` (``iem_soc_select``)."""
@@ -414,6 +433,104 @@ class SecondOrderCorrection:
     def __del__(self):
         try:
             if self.search._s is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
+class BarrierParameter:
+    """``BarrierParameter(layer, **opts)``: the barrier parameter of the C-ABI (``iem_mu_*``, ``csrc/iem_mu_device.h``) beside a
+    :class:`BarrierLayer` — ``mu``, ``tau`` and the stopping test in a block of sixteen words on the device, two one-launch calls, no
+    read-back but :meth:`state`.  ``opts``: ``mu_init, kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max`` (Ipopt's defaults;
+    ``mu_floor = 0`` means ``max(1e-11, tol/10)``).  Per iteration, with the three objects bound (``bar.bind_mu(par)``,
+    ``fs.bind_mu(par)``, ``soc.bind_mu(par)`` — their ``mu`` / ``tau`` arguments are then ignored):
+
+        _, c, r = model.eval_residual(state[0], state[2])
+        w = par.error(state, r, c, out=w)                              # twelve words; w[:8] is bar.error(state, r, c, 0.0)
+        par.update(w, search=fs)                                       # the stopping test and the monotone rule; empties fs's filter iff mu moved
+        ...                                                            # terms, solve, step, begin, rungs, update: one graph for every mu
+        st = par.state()                                               # THE read-back: status, mu, the error terms"""
+
+    def __init__(self, layer: BarrierLayer, **opts):
+        self.layer = layer
+        self._p = None
+        o = _lib.MuOpts.defaults(**opts)
+        L, b = layer._handle()
+        p = C.c_void_p()
+        _lib.check(L.iem_mu_create(b, C.byref(o), C.byref(p)))
+        self._p = p
+        self.opts = {name: getattr(o, name) for name, _ in _lib.MuOpts._fields_ if name != "struct_size"}
+        if self.opts["mu_floor"] == 0.0:
+            self.opts["mu_floor"] = max(1e-11, self.opts["tol"] / 10.0)
+
+    def _handle(self):
+        if self._p is None:
+            raise _lib.IemError("BarrierParameter: closed")
+        L, _ = self.layer._handle()
+        return L, self._p
+
+    def reset(self, mu0: float = None):
+        """A new solve (``iem_mu_reset``, asynchronous): ``mu = mu0`` (default ``mu_init``), ``tau``, ``zeta`` from it, status
+        iterating, flags and counters zero."""
+        L, p = self._handle()
+        _lib.check(L.iem_mu_reset(p, float(self.opts["mu_init"] if mu0 is None else mu0)))
+
+    def error(self, state, r, c, out=None):
+        """The twelve words of ``iem_mu_error`` as a device tensor: the eight numbers of ``BarrierLayer.error(state, r, c, 0.0)`` bit
+        for bit, then the minimum of the complementarity products ``gap·z`` that are ``>= +0.0``, their sum, the count of the
+        products that are not, and ``+0.0``.  ``r`` is required."""
+        bar = self.layer
+        out = out if out is not None else bar._new(12)
+        ps = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(c, bar.ncon, "c"), bar._vec(out, 12, "out"))
+        L, p = self._handle()
+        _lib.check(L.iem_mu_error(p, *ps, *args))
+        return out
+
+    def update(self, out12, search: FilterSearch = None):
+        """The stopping test and the monotone rule on the device (``iem_mu_update``) from the twelve words of :meth:`error`; a
+        ``search`` has its filter emptied and its flags cleared exactly when ``mu`` moved."""
+        bar = self.layer
+        pw = bar._vec(out12, 12, "out12")
+        ps = search._handle()[1] if search is not None else None
+        L, p = self._handle()
+        _lib.check(L.iem_mu_update(p, pw, ps))
+
+    def state(self):
+        """THE read-back (``iem_mu_state``, synchronises): words 0–11 of the block as a dict, ``status`` also by name, ``changed`` =
+        flag bit 0."""
+        L, p = self._handle()
+        v = _lib.MuState()
+        v.struct_size = C.sizeof(_lib.MuState)
+        _lib.check(L.iem_mu_state(p, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.MuState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.MU_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.MU_STATUS) else "?"
+        out["changed"] = bool(out["flags"] & 1)
+        return out
+
+    def device(self):
+        """The address of the block (16 words) on the device (``iem_mu_device``)."""
+        L, p = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_mu_device(p, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        """Unbind (or close) the objects bound to this parameter first: they borrow its block."""
+        if self._p is not None:
+            _lib.check(self.layer.model._L.iem_mu_destroy(self._p))
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.layer._b is not None and getattr(self.layer.model, "_h", None):
                 self.close()
         except Exception:
             pass

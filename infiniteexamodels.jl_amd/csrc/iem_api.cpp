@@ -61,6 +61,9 @@ static const char *kSocSource =           // the second-order correction of the 
 static const char *kRestoSource =         // the feasibility restoration phase (iem_resto_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_resto_device_h.inc"
     ;
+static const char *kMuSource =            // the barrier parameter (iem_mu_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_mu_device_h.inc"
+    ;
 
 namespace {
 
@@ -327,6 +330,8 @@ struct iem_model {
   struct SocObject { hipModule_t mod = nullptr; hipFunction_t open = nullptr, rhs = nullptr, trial = nullptr, accept = nullptr, select = nullptr; } soc;
   // the code object of the feasibility restoration phase (iem_resto_*): loaded by the first iem_resto_create of the handle
   struct RestoObject { hipModule_t mod = nullptr; hipFunction_t fn[12] = {}; } resto;
+  FixedObject barrier_mu;      // the barrier kernels that read mu and tau from an iem_mu block (barrier_mu_source): loaded by the first bind
+  struct MuObject { hipModule_t mod = nullptr; hipFunction_t error = nullptr, update = nullptr, reset = nullptr; } mu;
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1369,6 +1374,8 @@ int iem_destroy(iem_model *m) {
   if (m->search.mod) hipModuleUnload(m->search.mod);
   if (m->soc.mod) hipModuleUnload(m->soc.mod);
   if (m->resto.mod) hipModuleUnload(m->resto.mod);
+  if (m->mu.mod) hipModuleUnload(m->mu.mod);
+  if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
   for (auto &S : m->tune) for (auto &T : S.slot) if (T.have_events) for (auto &e : T.ev) for (auto &q : e) hipEventDestroy(q);
@@ -3846,6 +3853,7 @@ struct iem_barrier {
   double *d_red = nullptr;             // 4 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
   long long *d_tab = nullptr;          // offs[4] | first[4] | count[4] of iem_shared_totals
   unsigned long long *d_ones = nullptr;   // the bits of {1.0, 1.0}: what the step lengths are seeded with (device-to-device copy)
+  const double *mu_blk = nullptr;      // iem_barrier_bind_mu: the block of an iem_mu object (borrowed), or null
 };
 
 namespace {
@@ -3863,6 +3871,7 @@ struct BarrierArgsH {
   const long long *tab;
   double mu, tau, kappa, push, frac;
   long long nvar, n, n_wg;
+  const double *mu_blk;
 };
 BarrierArgsH barrier_args(const iem_barrier *b) {
   BarrierArgsH A;
@@ -3871,9 +3880,48 @@ BarrierArgsH barrier_args(const iem_barrier *b) {
   A.fx = b->d_flags; A.fc = A.fx + b->nvar;
   A.red = b->d_red; A.tab = b->d_tab;
   A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  A.mu_blk = b->mu_blk;
   return A;
 }
-int barrier_launch(const iem_barrier *b, int which, BarrierArgsH &A) { return kkt_launch_raw(b->m, b->m->fixed[F_BARRIER].fn[which], &A, sizeof A, b->n_wg, 256); }
+// unbound: the barrier object as it always was (its BarrierArgs ends in front of mu_blk); bound: the variant below, which reads the block
+int barrier_launch(const iem_barrier *b, int which, BarrierArgsH &A) {
+  if (A.mu_blk) return kkt_launch_raw(b->m, b->m->barrier_mu.fn[which], &A, sizeof A, b->n_wg, 256);
+  return kkt_launch_raw(b->m, b->m->fixed[F_BARRIER].fn[which], &A, offsetof(BarrierArgsH, mu_blk), b->n_wg, 256);
+}
+// The BOUND variant of the barrier code object: the text of csrc/iem_barrier_device.h with BarrierArgs one pointer longer and the single
+// read of mu (barrier_step: and of tau) in barrier_terms / step / update / error taken from the block — derived from the one text, so
+// that the unbound object keeps its source, its key and its bits, and the two cannot drift apart.  Every pattern must match exactly as
+// often as listed: an edit of the header that breaks one is an error here, not a silently unbound kernel.
+int barrier_mu_source(std::string &s) {
+  static const struct { const char *from, *to; int times; } kEdits[] = {
+      {"  long long nvar, n, n_wg;\n};", "  long long nvar, n, n_wg;\n  const double *mu_blk;      // the iem_mu block {mu, tau, ...}\n};", 1},
+      {"  const double mu = A.mu;\n", "  const double mu = A.mu_blk[0];\n", 2},      // barrier_terms, barrier_error
+      {"  const double mu = A.mu, tau = A.tau, ntau = -A.tau;\n", "  const double mu = A.mu_blk[0], tau = A.mu_blk[1], ntau = -tau;\n", 1},      // barrier_step
+      {"  const double mu = A.mu, kappa = A.kappa;\n", "  const double mu = A.mu_blk[0], kappa = A.kappa;\n", 1},      // barrier_update
+  };
+  std::string text(kBarrierSource);
+  for (const auto &e : kEdits) {
+    const std::string from(e.from), to(e.to);
+    int seen = 0;
+    for (size_t at = text.find(from); at != std::string::npos; at = text.find(from, at + to.size())) {
+      text.replace(at, from.size(), to);
+      ++seen;
+    }
+    if (seen != e.times) return fail(IEM_E_COMPILE, std::string("internal: the barrier kernels do not read mu where the bound variant expects it: ") + e.from);
+  }
+  return object_source(text.c_str(), true, s);
+}
+int barrier_mu_object(iem_model *m) {
+  iem_model::FixedObject &o = m->barrier_mu;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = barrier_mu_source(src);
+  if (rc) return rc;
+  KernelSlot slots[kFixedSlots];
+  int n = 0;
+  for (; n < kFixedSlots && kFixed[F_BARRIER].kernels[n]; ++n) slots[n] = KernelSlot{kFixed[F_BARRIER].kernels[n], &o.fn[n]};
+  return load_object(m, src, slots, n, &o.mod);
+}
 // the state vectors a call needs: x with variables, y and the slack side with rows (the slack side only with inequality rows)
 bool barrier_state_missing(const iem_barrier *b, const double *x, const double *s, const double *y, const double *zL, const double *zU, const double *vL, const double *vU) {
   return (b->nvar && (!x || !zL || !zU)) || (b->ncon && !y) || (b->n_ineq && (!s || !vL || !vU));
@@ -4011,7 +4059,7 @@ int iem_barrier_start(iem_barrier *b, double *d_x, const double *d_c, double *d_
 
 int iem_barrier_terms(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                       const double *d_vU, const double *d_r, const double *d_c, double mu, double *d_sigma, double *d_dcon, double *d_rhs) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_terms: mu must not be negative");
+  if (!(b && b->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_terms: mu must not be negative");
   if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->nvar && (!d_r || !d_sigma)) || (b->ncon && (!d_c || !d_dcon)) || !d_rhs)
     return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(b->m->device);
@@ -4024,8 +4072,8 @@ int iem_barrier_terms(iem_barrier *b, const double *d_x, const double *d_s, cons
 int iem_barrier_step(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                      const double *d_vU, const double *d_sol, double mu, double tau, double *d_ds, double *d_dzL, double *d_dzU, double *d_dvL, double *d_dvU,
                      double *d_alpha) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_step: mu must not be negative");
-  if (!(tau > 0.0 && tau <= 1.0)) return fail(IEM_E_ARG, "iem_barrier_step: tau must lie in (0, 1]");
+  if (!(b && b->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_step: mu must not be negative");
+  if (!(b && b->mu_blk) && !(tau > 0.0 && tau <= 1.0)) return fail(IEM_E_ARG, "iem_barrier_step: tau must lie in (0, 1]");
   if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
       (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
     return fail(IEM_E_ARG, "null argument");
@@ -4042,7 +4090,7 @@ int iem_barrier_step(iem_barrier *b, const double *d_x, const double *d_s, const
 int iem_barrier_update(iem_barrier *b, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
                        const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha, double mu,
                        double kappa_sigma) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_update: mu must not be negative");
+  if (!(b && b->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_update: mu must not be negative");
   if (!(kappa_sigma >= 1.0)) return fail(IEM_E_ARG, "iem_barrier_update: kappa_sigma must be at least 1");
   if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol || !d_alpha || (b->nvar && (!d_dzL || !d_dzU)) ||
       (b->n_ineq && (!d_ds || !d_dvL || !d_dvU)))
@@ -4057,7 +4105,7 @@ int iem_barrier_update(iem_barrier *b, double *d_x, double *d_s, double *d_y, do
 
 int iem_barrier_error(iem_barrier *b, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                       const double *d_vU, const double *d_r, const double *d_c, double mu, double *d_out) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_error: mu must not be negative");
+  if (!(b && b->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_barrier_error: mu must not be negative");
   if (!b || barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
   iem_model *m = b->m;
   DevGuard dg_(m->device);
@@ -4084,6 +4132,7 @@ struct iem_search {
   double *d_filter = nullptr;          // filter_capacity pairs (theta, phi)
   double *d_red = nullptr;             // n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
   long long *d_tab = nullptr;          // offs | first | count of iem_shared_totals
+  const double *mu_blk = nullptr;      // iem_search_bind_mu: the block of an iem_mu object (borrowed), or null
 };
 
 namespace {
@@ -4103,6 +4152,7 @@ struct SearchArgsH {
   double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor;
   long long max_trials, capacity;
   long long nvar, n, n_wg;
+  const double *mu_blk;
 };
 SearchArgsH search_args(const iem_search *s) {
   const iem_barrier *b = s->b;
@@ -4115,6 +4165,7 @@ SearchArgsH search_args(const iem_search *s) {
   A.s_theta = s->opt.s_theta; A.s_phi = s->opt.s_phi; A.alpha_floor = s->opt.alpha_floor;
   A.max_trials = (long long)s->opt.max_trials; A.capacity = (long long)s->opt.filter_capacity;
   A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  A.mu_blk = s->mu_blk;
   return A;
 }
 const struct SearchSlot { const char *name; hipFunction_t iem_model::SearchObject::*fn; } kSearchSlots[] = {
@@ -4211,7 +4262,7 @@ int iem_search_reset(iem_search *s) {
 
 int iem_search_begin(iem_search *s, const double *d_x, const double *d_s, const double *d_grad, const double *d_sol, const double *d_ds, const double *d_obj,
                      const double *d_err, const double *d_alpha, double mu, double obj_weight) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_begin: mu must not be negative");
+  if (!(s && s->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_begin: mu must not be negative");
   if (!s || (s->b->nvar && (!d_x || !d_grad)) || (s->b->n_ineq && (!d_s || !d_ds)) || !d_sol || !d_obj || !d_err || !d_alpha) return fail(IEM_E_ARG, "null argument");
   iem_model *m = s->b->m;
   DevGuard dg_(m->device);
@@ -4230,7 +4281,7 @@ int iem_search_trial(iem_search *s, const double *d_x, const double *d_s, const 
 }
 
 int iem_search_accept(iem_search *s, const double *d_ft, const double *d_merit, double mu, double obj_weight, double *d_alpha) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_accept: mu must not be negative");
+  if (!(s && s->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_search_accept: mu must not be negative");
   if (!s || !d_ft || !d_merit || !d_alpha) return fail(IEM_E_ARG, "null argument");
   iem_model *m = s->b->m;
   DevGuard dg_(m->device);
@@ -4267,6 +4318,7 @@ struct iem_soc {
   iem_search *s = nullptr;
   iem_soc_opts_t opt;
   double *d_csoc = nullptr;            // the accumulated constraint residual: ncon
+  const double *mu_blk = nullptr;      // iem_soc_bind_mu: the block of an iem_mu object (borrowed), or null
 };
 
 namespace {
@@ -4288,6 +4340,7 @@ struct SocArgsH {
   double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, kappa_soc;
   long long max_soc, capacity;
   long long nvar, n;
+  const double *mu_blk;
 };
 SocArgsH soc_args(const iem_soc *q) {
   const iem_search *s = q->s;
@@ -4301,6 +4354,7 @@ SocArgsH soc_args(const iem_soc *q) {
   A.s_theta = s->opt.s_theta; A.s_phi = s->opt.s_phi; A.kappa_soc = q->opt.kappa_soc;
   A.max_soc = (long long)q->opt.max_soc; A.capacity = (long long)s->opt.filter_capacity;
   A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon);
+  A.mu_blk = q->mu_blk;
   return A;
 }
 const struct SocSlot { const char *name; hipFunction_t iem_model::SocObject::*fn; } kSocSlots[] = {
@@ -4380,7 +4434,7 @@ int iem_soc_open(iem_soc *q) {
 
 int iem_soc_rhs(iem_soc *q, const double *d_s, const double *d_y, const double *d_vL, const double *d_vU, const double *d_c, const double *d_ct, const double *d_st,
                 const double *d_rhs, double mu, double *d_rhs_soc) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_rhs: mu must not be negative");
+  if (!(q && q->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_rhs: mu must not be negative");
   if (!q) return fail(IEM_E_ARG, "null argument");
   const iem_barrier *b = q->s->b;
   if ((b->ncon && (!d_c || !d_ct)) || (b->n_ineq && (!d_s || !d_y || !d_vL || !d_vU || !d_st)) || !d_rhs || !d_rhs_soc) return fail(IEM_E_ARG, "null argument");
@@ -4403,7 +4457,7 @@ int iem_soc_trial(iem_soc *q, const double *d_x, const double *d_s, const double
 }
 
 int iem_soc_accept(iem_soc *q, const double *d_ft, const double *d_merit, const double *d_alpha_soc, double mu, double obj_weight, double *d_alpha) {
-  if (!(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_accept: mu must not be negative");
+  if (!(q && q->mu_blk) && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_soc_accept: mu must not be negative");
   if (!q || !d_ft || !d_merit || !d_alpha_soc || !d_alpha) return fail(IEM_E_ARG, "null argument");
   iem_model *m = q->s->b->m;
   DevGuard dg_(m->device);
@@ -4765,6 +4819,217 @@ int iem_resto_state(iem_resto *q, iem_resto_state_t *out) {
   v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
   std::memcpy(&v.state, w, 4 * 8);
   std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+/* ---- the barrier parameter on the device: error terms, the monotone rule, the block the other objects read (csrc/iem_mu_device.h) ---- */
+struct iem_mu {
+  iem_barrier *b = nullptr;
+  iem_mu_opts_t opt;                   // mu_floor resolved
+  double *d_blk = nullptr;             // the block: 16 words
+  double *d_red = nullptr;             // 6 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  long long *d_tab = nullptr;          // offs[6] | first[6] | count[6] of iem_shared_totals
+  double *d_seed = nullptr;            // what the twelve words of iem_mu_error start from: +0.0, and the bits of +inf in word 8
+};
+
+namespace {
+// MuArgs of csrc/iem_mu_device.h
+struct MuArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c;
+  double *out;
+  const double *w;
+  double *blk;
+  double *sctl;
+  double *red;
+  const long long *tab;
+  double kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max, mu0;
+  long long ncon, nz;
+  long long nvar, n, n_wg;
+};
+MuArgsH mu_args(const iem_mu *p) {
+  const iem_barrier *b = p->b;
+  MuArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.blk = p->d_blk; A.red = p->d_red; A.tab = p->d_tab;
+  A.kappa_eps = p->opt.kappa_eps; A.kappa_mu = p->opt.kappa_mu; A.tau_min = p->opt.tau_min; A.tol = p->opt.tol; A.mu_floor = p->opt.mu_floor; A.s_max = p->opt.s_max;
+  A.ncon = (long long)b->ncon; A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int mu_object(iem_model *m) {
+  iem_model::MuObject &o = m->mu;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kMuSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[3] = {KernelSlot{"mu_error", &o.error}, KernelSlot{"mu_update", &o.update}, KernelSlot{"mu_reset", &o.reset}};
+  return load_object(m, src, slots, 3, &o.mod);
+}
+int mu_opts(const iem_mu_opts_t *in, iem_mu_opts_t *out) {
+  iem_mu_opts_t v = {sizeof v, 0.1, 10.0, 0.2, 0.99, 1e-8, 0.0, 100.0};      // Ipopt's mu_init, barrier_tol_factor, mu_linear_decrease_factor, tau_min, tol; s_max
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_mu_create: set struct_size to sizeof(iem_mu_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  for (double f : {v.mu_init, v.kappa_eps, v.kappa_mu, v.tau_min, v.tol, v.mu_floor, v.s_max})
+    if (!std::isfinite(f)) return fail(IEM_E_ARG, "iem_mu_create: every option must be finite");
+  auto unit = [](double g) { return g > 0.0 && g < 1.0; };
+  if (!(v.mu_init > 0.0)) return fail(IEM_E_ARG, "iem_mu_create: mu_init must be positive");
+  if (!unit(v.kappa_mu) || !unit(v.tau_min)) return fail(IEM_E_ARG, "iem_mu_create: kappa_mu and tau_min must lie in (0, 1)");
+  if (!(v.kappa_eps > 0.0)) return fail(IEM_E_ARG, "iem_mu_create: kappa_eps must be positive");
+  if (!(v.tol > 0.0)) return fail(IEM_E_ARG, "iem_mu_create: tol must be positive");
+  if (!(v.mu_floor >= 0.0)) return fail(IEM_E_ARG, "iem_mu_create: mu_floor must not be negative");
+  if (!(v.s_max > 0.0)) return fail(IEM_E_ARG, "iem_mu_create: s_max must be positive");
+  if (v.mu_floor == 0.0) v.mu_floor = std::max(1e-11, v.tol / 10.0);
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_barrier_mu_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = barrier_mu_source(s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_mu_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kMuSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_mu_destroy(iem_mu *p) {
+  if (!p) return IEM_OK;
+  DevGuard dg_(p->b->m->device);
+  for (void *q : {(void *)p->d_blk, (void *)p->d_red, (void *)p->d_tab, (void *)p->d_seed})
+    if (q) hipFree(q);
+  delete p;
+  return IEM_OK;
+}
+
+int iem_mu_create(iem_barrier *b, const iem_mu_opts_t *opts, iem_mu **out) {
+  if (!b || !out) return fail(IEM_E_ARG, "null argument");
+  iem_mu_opts_t opt;
+  {
+    int rc = mu_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = mu_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_mu *p) const { iem_mu_destroy(p); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_mu, Drop> p(new iem_mu);
+  p->b = b;
+  p->opt = opt;
+  const int64_t n_red = 6 * b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&p->d_blk, 16 * 8));
+  HIP_TRY(hipMalloc((void **)&p->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMalloc((void **)&p->d_tab, 18 * 8));
+  HIP_TRY(hipMalloc((void **)&p->d_seed, 12 * 8));
+  long long tab[18];
+  for (int s = 0; s < 6; ++s) { tab[s] = s * (long long)b->n_wg; tab[6 + s] = 0; tab[12 + s] = (long long)b->n_wg; }
+  double seed[12] = {};
+  seed[8] = std::numeric_limits<double>::infinity();
+  double blk[16] = {};      // status ITERATING, no flag, counters 0
+  blk[0] = opt.mu_init;
+  blk[1] = std::max(opt.tau_min, 1.0 - opt.mu_init);
+  blk[2] = std::sqrt(opt.mu_init);
+  HIP_TRY(hipMemcpy(p->d_blk, blk, sizeof blk, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(p->d_red, 0, (size_t)n_red * 8));
+  HIP_TRY(hipMemcpy(p->d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(p->d_seed, seed, sizeof seed, hipMemcpyHostToDevice));
+  *out = p.release();
+  return IEM_OK;
+}
+
+int iem_mu_reset(iem_mu *p, double mu0) {
+  if (!p) return fail(IEM_E_ARG, "null argument");
+  if (!(mu0 > 0.0) || !std::isfinite(mu0)) return fail(IEM_E_ARG, "iem_mu_reset: mu0 must be positive and finite");
+  iem_model *m = p->b->m;
+  DevGuard dg_(m->device);
+  MuArgsH A = mu_args(p);
+  A.mu0 = mu0;
+  return kkt_launch_raw(m, m->mu.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_mu_error(iem_mu *p, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_r, const double *d_c, double *d_out) {
+  if (!p || barrier_state_missing(p->b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (p->b->nvar && !d_r) || (p->b->ncon && !d_c) || !d_out)
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = p->b->m;
+  DevGuard dg_(m->device);
+  MuArgsH A = mu_args(p);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU; A.r = d_r; A.c = d_c; A.out = d_out;
+  // the seed: the maxima start from +0.0, the minimum from the bits of +inf (a device-to-device copy is a capturable node)
+  HIP_TRY(hipMemcpyAsync(d_out, p->d_seed, 12 * 8, hipMemcpyDeviceToDevice, m->stream));
+  return kkt_launch_raw(m, m->mu.error, &A, sizeof A, p->b->n_wg, 256);
+}
+
+int iem_mu_update(iem_mu *p, const double *d_out12, iem_search *fs) {
+  if (!p || !d_out12) return fail(IEM_E_ARG, "null argument");
+  if (fs && fs->b != p->b) return fail(IEM_E_ARG, "iem_mu_update: the search belongs to another barrier object");
+  iem_model *m = p->b->m;
+  DevGuard dg_(m->device);
+  MuArgsH A = mu_args(p);
+  A.w = d_out12;
+  A.sctl = fs ? fs->d_ctl : nullptr;
+  return kkt_launch_raw(m, m->mu.update, &A, sizeof A, 1, 64);
+}
+
+int iem_mu_device(const iem_mu *p, double **d_block) {
+  if (!p) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = p->d_blk;
+  return IEM_OK;
+}
+
+int iem_mu_state(iem_mu *p, iem_mu_state_t *out) {
+  if (!p || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_mu_state: set struct_size to sizeof(iem_mu_state_t) before the call");
+  iem_model *m = p->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[16];
+  HIP_TRY(hipMemcpyAsync(w, p->d_blk, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_mu_state_t v;
+  static_assert(sizeof v == 13 * 8, "iem_mu_state_t: struct_size, then words 0-11 of the block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.mu, w, 12 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+int iem_barrier_bind_mu(iem_barrier *b, const iem_mu *p) {
+  if (!b) return fail(IEM_E_ARG, "null argument");
+  if (p && p->b != b) return fail(IEM_E_ARG, "iem_barrier_bind_mu: the iem_mu object was created on another barrier object");
+  if (p) {
+    DevGuard dg_(b->m->device);
+    int rc = barrier_mu_object(b->m);
+    if (rc) return rc;
+  }
+  b->mu_blk = p ? p->d_blk : nullptr;
+  return IEM_OK;
+}
+
+int iem_search_bind_mu(iem_search *fs, const iem_mu *p) {
+  if (!fs) return fail(IEM_E_ARG, "null argument");
+  if (p && p->b != fs->b) return fail(IEM_E_ARG, "iem_search_bind_mu: the iem_mu object was created on another barrier object");
+  fs->mu_blk = p ? p->d_blk : nullptr;
+  return IEM_OK;
+}
+
+int iem_soc_bind_mu(iem_soc *q, const iem_mu *p) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (p && p->b != q->s->b) return fail(IEM_E_ARG, "iem_soc_bind_mu: the iem_mu object was created on another barrier object");
+  q->mu_blk = p ? p->d_blk : nullptr;
   return IEM_OK;
 }
 

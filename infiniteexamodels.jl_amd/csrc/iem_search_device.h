@@ -41,6 +41,7 @@ struct SearchArgs {
   double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, alpha_floor;
   long long max_trials, capacity;
   long long nvar, n, n_wg;
+  const double *mu_blk;                           // iem_search_bind_mu: the iem_mu block {mu, ...}, or null — then A.mu rules
 };
 
 __device__ __forceinline__ long long search_word(const double *ctl, int w) { return __double_as_longlong(ctl[w]); }
@@ -51,7 +52,7 @@ __device__ __forceinline__ bool search_finite(double a) { return (__double_as_lo
 extern "C" __global__ __launch_bounds__(256) void search_begin(const SearchArgs A) {
   __shared__ double lds[8];
   const long long stride = (long long)gridDim.x * 256;
-  const double mu = A.mu, sigma = A.sigma;
+  const double mu = A.mu_blk ? A.mu_blk[0] : A.mu, sigma = A.sigma;
   double v[1] = {0.0};      // the slope: the terms of this lane in index order
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < A.n; i += stride) {
     if (i < A.nvar) {
@@ -131,7 +132,7 @@ extern "C" __global__ __launch_bounds__(64) void search_accept(const SearchArgs 
   long long count = search_word(ctl, SW_COUNT);      // (a host may write the block: a count outside the filter reads and writes nothing outside it)
   count = count < 0 ? 0 : count > A.capacity ? A.capacity : count;
   const double theta_t = A.merit[0];
-  const double phi_t = A.sigma * A.ft[0] - A.mu * A.merit[1];
+  const double phi_t = A.sigma * A.ft[0] - (A.mu_blk ? A.mu_blk[0] : A.mu) * A.merit[1];
   // admissible: finite, theta below its ceiling, not dominated by a filter entry (the scan: lane l takes the entries l, l + 64, ...)
   bool hit = false;
   for (long long k = lane; k < count; k += 64) hit = hit || (theta_t >= A.filter[2 * k] && phi_t >= A.filter[2 * k + 1]);

@@ -46,6 +46,7 @@ struct SocArgs {
   double gamma_theta, gamma_phi, eta_phi, delta, s_theta, s_phi, kappa_soc;
   long long max_soc, capacity;
   long long nvar, n;
+  const double *mu_blk;                           // iem_soc_bind_mu: the iem_mu block {mu, ...}, or null — then A.mu rules
 };
 
 __device__ __forceinline__ long long soc_word(const double *ctl, int w) { return __double_as_longlong(ctl[w]); }
@@ -69,7 +70,7 @@ extern "C" __global__ __launch_bounds__(64) void soc_open(const SocArgs A) {
 extern "C" __global__ __launch_bounds__(256) void soc_rhs(const SocArgs A) {
   if (soc_word(A.ctl, CW_SOC_STATE) != SOC_ACTIVE) return;      // nothing is stored, csoc stays
   const bool first = soc_word(A.ctl, CW_SOC_ROUNDS) == 0;
-  const double alpha_prev = A.ctl[CW_SOC_ALPHA_PREV], mu = A.mu;
+  const double alpha_prev = A.ctl[CW_SOC_ALPHA_PREV], mu = A.mu_blk ? A.mu_blk[0] : A.mu;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < A.n; i += stride) {
     if (i < A.nvar) {
@@ -132,7 +133,7 @@ extern "C" __global__ __launch_bounds__(64) void soc_accept(const SocArgs A) {
   long long count = soc_word(ctl, CW_COUNT);
   count = count < 0 ? 0 : count > A.capacity ? A.capacity : count;
   const double theta_t = A.merit[0];
-  const double phi_t = A.sigma * A.ft[0] - A.mu * A.merit[1];
+  const double phi_t = A.sigma * A.ft[0] - (A.mu_blk ? A.mu_blk[0] : A.mu) * A.merit[1];
   bool hit = false;
   for (long long k = lane; k < count; k += 64) hit = hit || (theta_t >= A.filter[2 * k] && phi_t >= A.filter[2 * k + 1]);
   const bool dominated = __ballot(hit) != 0ull;

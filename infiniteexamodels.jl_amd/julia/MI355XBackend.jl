@@ -648,6 +648,64 @@ function soc_device(c::SecondOrderCorrection)
     return p[]
 end
 
+# ---- the barrier parameter (include/iem.h: iem_mu_*) ---------------------------------------------------------------------------------
+# mu, tau and the stopping test in a block of sixteen words on the device beside the BarrierLayer: mu_error! (twelve words: the eight of
+# barrier_error! at mu = 0 bit for bit, then the minimum, the sum and the count of unusable values of the products gap·z) and mu_update!
+# (the stopping test and the monotone rule; a search given to it has its filter emptied iff mu moved).  bind_mu! makes the kernels of a
+# BarrierLayer, FilterSearch or SecondOrderCorrection read mu (and tau) from the block: their mu / tau arguments are then ignored and one
+# captured iteration serves every barrier problem.  bind_mu!(obj, nothing) unbinds; unbind before the parameter is finalized.  The inner
+# search of a Restoration keeps the restoration problem's own mu: never bind it.  UNEXECUTED, like the rest.
+struct IemMuOpts           # iem_mu_opts_t
+    struct_size::UInt64
+    mu_init::Float64; kappa_eps::Float64; kappa_mu::Float64; tau_min::Float64; tol::Float64; mu_floor::Float64; s_max::Float64
+end
+struct IemMuState          # iem_mu_state_t: words 0-11 of the block
+    struct_size::UInt64
+    mu::Float64; tau::Float64; zeta::Float64; e0::Float64; e_mu::Float64; e_d::Float64; e_p::Float64; e_c0::Float64
+    status::Int64; flags::Int64; decreases::Int64; updates::Int64      # status: 0 iterating, 1 converged, 2 unusable; flags bit 0: mu changed in the last update
+end
+mutable struct BarrierParameter
+    p::Ptr{Cvoid}
+    layer::BarrierLayer      # borrowed: kept alive
+end
+# mu_floor = 0: max(1e-11, tol/10)
+function BarrierParameter(l::BarrierLayer; mu_init = 0.1, kappa_eps = 10.0, kappa_mu = 0.2, tau_min = 0.99, tol = 1e-8, mu_floor = 0.0, s_max = 100.0)
+    opts = Ref(IemMuOpts(sizeof(IemMuOpts), mu_init, kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max))
+    p = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_mu_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMuOpts}, Ptr{Ptr{Cvoid}}), l.b, opts, p))
+    par = BarrierParameter(p[], l)
+    finalizer(q -> (q.p == C_NULL || ccall((:iem_mu_destroy, LIBIEM), Cint, (Ptr{Cvoid},), q.p); q.p = C_NULL), par)
+    return par
+end
+# a new solve: mu = mu0, tau and sqrt(mu) from it, status iterating, flags and counters zero (asynchronous)
+mu_reset!(q::BarrierParameter, mu0) = check(ccall((:iem_mu_reset, LIBIEM), Cint, (Ptr{Cvoid}, Cdouble), q.p, mu0))
+# out: twelve doubles on the device; r is required
+function mu_error!(q::BarrierParameter, state, r, c, out)
+    check(ccall((:iem_mu_error, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 10)...),
+                q.p, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(r), spptr(c), dptr(out)))
+    return out
+end
+# out12: the twelve of mu_error!; search: a FilterSearch on the same BarrierLayer, or nothing
+function mu_update!(q::BarrierParameter, out12; search = nothing)
+    check(ccall((:iem_mu_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), q.p, dptr(out12), search === nothing ? C_NULL : search.s))
+end
+# the one read-back (synchronises the stream)
+function mu_state(q::BarrierParameter)
+    st = Ref(IemMuState(sizeof(IemMuState), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    check(ccall((:iem_mu_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMuState}), q.p, st))
+    return st[]
+end
+# the block (16 words of 8 bytes) as a device address
+function mu_device(q::BarrierParameter)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_mu_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), q.p, p))
+    return p[]
+end
+_mu_handle(q) = q === nothing ? C_NULL : q.p
+bind_mu!(l::BarrierLayer, q) = check(ccall((:iem_barrier_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), l.b, _mu_handle(q)))
+bind_mu!(f::FilterSearch, q) = check(ccall((:iem_search_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), f.s, _mu_handle(q)))
+bind_mu!(c::SecondOrderCorrection, q) = check(ccall((:iem_soc_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.q, _mu_handle(q)))
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
