@@ -1078,8 +1078,8 @@ int iem_resto_source(char **out_src, uint64_t *out_key);
  * NULL without inequality rows), mu_init <= 0, kappa_mu or tau_min outside (0, 1), kappa_eps <= 0, tol <= 0, mu_floor < 0,
  * s_max <= 0, any option not finite, mu0 <= 0 or not finite, an fs or a bind across two barrier objects.  The object borrows the
  * barrier object; a bound object borrows the block: unbind (or destroy the bound objects) before iem_mu_destroy.  Not here: the
- * delta_w / inertia retry, adaptive (Mehrotra, quality-function) rules — words 8 and 9 of iem_mu_error are what they need —
- * a binding for iem_resto, sharded handles. */
+ * delta_w / inertia retry, a binding for iem_resto, sharded handles.  The adaptive rules that words 8 and 9 of iem_mu_error
+ * serve (probing, LOQO) are the iem_amu object below; Mehrotra's corrector and the quality-function oracle are not there either. */
 typedef struct iem_mu iem_mu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mu_opts_t) */
@@ -1107,6 +1107,90 @@ int iem_mu_source(char **out_src, uint64_t *out_key);
 /* ... and of the BOUND variant of the barrier code object: the text of iem_barrier_source with BarrierArgs one pointer longer and the
  * reads of mu and tau taken from the block; iem_barrier_bind_mu loads it.  iem_barrier_source, its key and the unbound calls are unchanged */
 int iem_barrier_mu_source(char **out_src, uint64_t *out_key);
+
+/* ---- the adaptive barrier parameter --------------------------------------------------------------------------------------------------
+ * Ipopt's `mu_strategy = adaptive` with the kkt-error globalisation on the device (csrc/iem_amu_device.h), as an object created ON an
+ * iem_mu: it drives that object's block, so every kernel bound through iem_*_bind_mu keeps reading word 0 (mu) and word 1 (tau) of the
+ * same block, and one captured iteration still replays across every change of mu.  Per iteration the host calls EITHER iem_mu_update
+ * OR iem_amu_update on the block.  kappa_eps, kappa_mu, tau_min, tol, mu_floor and s_max are those of the iem_mu object.
+ *
+ * THE OWN BLOCK: sixteen 8-byte words on the device (iem_amu_device gives the pointer; iem_amu_state_t mirrors words 0–13):
+ *     0 mode (int64): 0 FREE, 1 FIXED      1 mu_max (+0.0: unset)      2 reference count (int64)      3–6 references, oldest first
+ *     7 the oracle's mu before clamping      8 sigma      9 avg      10 m_aff (+0.0 for LOQO)
+ *     11 switches to FIXED (int64)      12 switches to FREE (int64)      13 oracle (int64): 0 probing, 1 LOQO      14–15 zero
+ * iem_amu_create zeroes it but for word 13.  iem_amu_reset (one launch of one workgroup, asynchronous) does the same: mode FREE, the
+ *     ring empty, mu_max unset, words 7–12 zero.  The iem_mu block has its own iem_mu_reset.
+ * iem_amu_probe: the complementarity that the affine-scaling step would leave behind.  ONE launch on the barrier object's grid, the
+ *     entry order and flags of iem_mu_error, no seed (the last workgroup writes all four words), no host memset, no synchronisation,
+ *     capturable.  With ap = alpha_aff[0], ad = alpha_aff[1] read once, d = dx (sol[i]) on variables and ds on rows, per PRESENT bound,
+ *     each operation rounded once, in this order:
+ *         t = ap·d      g = gap + t (lower bound; gap = x − xl or s − rl)      g = gap − t (upper bound; gap = xu − x or ru − s)
+ *         u = ad·dz      w = z + u      p = g·w
+ *     [0] the sum of all p — a lane adds its entries in index order (lower before upper), the workgroups park, the last arrival totals
+ *     in the fixed order of the barrier sums: with all directions +0.0 and alpha_aff = (1, 1) these are the bits of word 9 of
+ *     iem_mu_error on the same state  [1] the count of the p that are NaN, as a double (exact)  [2] ap  [3] ad.  Absent bounds and
+ *     equality rows are never read (neither state nor direction); y and dy are not read at all.
+ *     THE AFFINE DIRECTION comes from existing calls: sigma and dcon of iem_barrier_terms do not depend on mu, so
+ *         iem_barrier_terms(mu = 0) -> rhs_aff;  iem_kkt_solve_refined_diag on the iteration's factors;  iem_barrier_step(mu = 0, tau = 1)
+ *     with the barrier object UNBOUND around them (iem_barrier_bind_mu(b, NULL) ... iem_barrier_bind_mu(b, p): no launch after the
+ *     first bind; a capture bakes each node's variant and pointers).
+ * iem_amu_update: ONE workgroup of 64 threads, one thread decides, each operation rounded once, every max / min propagating a NaN.
+ *     With w the twelve words of iem_mu_error and q the four of iem_amu_probe (required for the probing oracle, NULL for LOQO), sd,
+ *     sc, e_d, e_p, e_c(mu), E(mu) are iem_mu_update's expressions.  Words 3–7, the status and updates += 1 of the iem_mu block are
+ *     stored as iem_mu_update stores them (word 4 at the mu the call leaves behind).
+ *     UNUSABLE: w10 != 0, E(0) a NaN, or (probing) q1 != 0, q2 or q3 the bits of +0.0 (an unusable affine step) — mu, tau, zeta and
+ *         the own block stay.  Else CONVERGED: E(0) <= tol — mu and the own block stay.  Else ITERATING:
+ *     nz == 0: mu = mu_min, nothing else.  Otherwise
+ *         avg = w9/nz (word 9);  mu_max = mu_max_fact·avg if word 1 is +0.0 (kept until iem_amu_reset)
+ *         progress = n < refs_max  ||  E(0) <= red_fact·max(references)          remember(E0): append; at refs_max drop the oldest first
+ *         mode FIXED:  progress ? (mode <- FREE, word 12 += 1, remember(E0))
+ *                               : the loop of iem_mu_update — the same condition, expression and cap of 64; decreases += k
+ *         mode FREE:   progress && !force_fixed ? remember(E0)
+ *                               : (mode <- FIXED, word 11 += 1, mu = min(max(init_factor·avg, mu_min), mu_max))
+ *         then, if the mode is FREE: the oracle, words 7, 8, 10, and mu = min(max(word 7, mu_min), mu_max)
+ *             probing:  m_aff = q0/nz;  r = m_aff/avg;  sigma = min((r·r)·r, sigma_max);  word 7 = sigma·avg
+ *             LOQO:     xi = w8/avg;  f = (0.05·(1 − xi))/xi;  c = min(f, 2.0);  sigma = 0.1·((c·c)·c);  word 7 = sigma·avg
+ *     (no pow: three multiplications).  If the BITS of mu changed: words 0–2 are rewritten (tau = max(tau_min, 1 − mu), zeta =
+ *     sqrt(mu) correctly rounded), flag bit 0 is set, and words 11 and 12 of fs's control block are zeroed when fs is given.
+ *     Otherwise flag bit 0 is cleared and fs is untouched.  force_fixed is the host's verdict on the last step (a failed search, a
+ *     tiny step): Ipopt's switch to the monotone mode.
+ * iem_amu_state: the one read-back — both blocks behind ONE synchronisation.
+ * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  IEM_E_ARG before any device
+ * work: null required pointers (the slack side may be NULL without inequality rows), a probing object updated without q, an fs of
+ * another barrier object, oracle not 0 or 1, sigma_max, mu_min, mu_max_fact or init_factor <= 0, red_fact outside (0, 1), refs_max
+ * outside 1..4, any option not finite.  The object borrows the iem_mu object: destroy it first.  Not here: Mehrotra's corrector,
+ * Ipopt's quality-function oracle, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w /
+ * inertia retry (the host's). */
+typedef struct iem_amu iem_amu;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_amu_opts_t) */
+  int64_t oracle;                       /* IEM_AMU_PROBING / IEM_AMU_LOQO */
+  double sigma_max, mu_min, mu_max_fact, init_factor, red_fact;
+  int64_t refs_max;                     /* 1..4 */
+} iem_amu_opts_t;                       /* NULL = probing, 100, 1e-11, 1e3, 0.8, 0.9999, 4 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_amu_state_t): at most that many bytes are written */
+  int64_t mode;                         /* word 0 */
+  double mu_max;                        /* word 1 */
+  int64_t refs_count;                   /* word 2 */
+  double refs[4];                       /* words 3–6 */
+  double mu_oracle, sigma, avg, m_aff;  /* words 7–10 */
+  int64_t to_fixed, to_free, oracle;    /* words 11–13 */
+} iem_amu_state_t;
+enum { IEM_AMU_FREE = 0, IEM_AMU_FIXED = 1 };
+enum { IEM_AMU_PROBING = 0, IEM_AMU_LOQO = 1 };
+int iem_amu_create(iem_mu *p, const iem_amu_opts_t *opts, iem_amu **out);
+int iem_amu_destroy(iem_amu *a);
+int iem_amu_reset(iem_amu *a);
+int iem_amu_probe(iem_amu *a, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                  const double *d_sol_aff, const double *d_ds_aff, const double *d_dzL_aff, const double *d_dzU_aff, const double *d_dvL_aff,
+                  const double *d_dvU_aff, const double *d_alpha_aff /* 2 */, double *d_out /* 4 */);
+int iem_amu_update(iem_amu *a, const double *d_out12 /* of iem_mu_error */, const double *d_probe4 /* NULL for LOQO */, int force_fixed,
+                   iem_search *fs /* may be NULL */);
+int iem_amu_device(const iem_amu *a, double **d_block);
+int iem_amu_state(iem_amu *a, iem_mu_state_t *mu_out, iem_amu_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the three kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_amu_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

@@ -18,6 +18,7 @@ every other row has an eliminated slack ``s``.  All vectors are full length: ``x
 Nothing above reads a value back; :meth:`BarrierLayer.optimality_error` is the only place that does."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -531,6 +532,127 @@ class BarrierParameter:
     def __del__(self):
         try:
             if self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
+class AdaptiveBarrierParameter:
+    """``AdaptiveBarrierParameter(par, **opts)``: the adaptive barrier parameter of the C-ABI (``iem_amu_*``,
+    ``csrc/iem_amu_device.h``) ON a :class:`BarrierParameter` — Ipopt's free / fixed modes with the kkt-error progress test, the
+    probing or the LOQO oracle, all in one launch that writes ``mu``, ``tau`` and the stopping test into ``par``'s block; the objects
+    bound to ``par`` follow.  ``opts``: ``oracle`` (``"probing"`` / ``"loqo"`` or 0 / 1), ``sigma_max, mu_min, mu_max_fact,
+    init_factor, red_fact, refs_max``.  Per iteration, in place of ``par.update``:
+
+        w = par.error(state, r, c, out=w)
+        with amu.affine(bar, fs):                                      # unbound inside: the calls take mu = 0, tau = 1
+            _, _, rhs_a = bar.terms(state, r, c, 0.0, out=(sigma, dcon, rhs_a))
+            sol_a = kkt.solve(rhs_a, refine=1)                         # one more back-solve on the iteration's factors
+            dirs_a, alpha_a = bar.step(state, sol_a, 0.0, 1.0)
+            q = amu.probe(state, sol_a, dirs_a, alpha_a, out=q)        # four words
+        amu.update(w, q, search=fs)                                    # LOQO: amu.update(w, search=fs), no affine solve at all
+        st = amu.state()                                               # THE read-back: both blocks"""
+
+    def __init__(self, par: BarrierParameter, **opts):
+        self.par = par
+        self.layer = par.layer
+        self._a = None
+        o = _lib.AmuOpts.defaults(**opts)
+        L, p = par._handle()
+        a = C.c_void_p()
+        _lib.check(L.iem_amu_create(p, C.byref(o), C.byref(a)))
+        self._a = a
+        self.opts = {name: getattr(o, name) for name, _ in _lib.AmuOpts._fields_ if name != "struct_size"}
+
+    def _handle(self):
+        if self._a is None:
+            raise _lib.IemError("AdaptiveBarrierParameter: closed")
+        L, _ = self.par._handle()
+        return L, self._a
+
+    def reset(self):
+        """A new solve (``iem_amu_reset``, asynchronous): mode free, the ring of references empty, ``mu_max`` unset, counters zero.
+        ``par.reset()`` is a call of its own."""
+        L, a = self._handle()
+        _lib.check(L.iem_amu_reset(a))
+
+    def probe(self, state, sol_aff, dirs_aff, alpha_aff, out=None):
+        """The four words of ``iem_amu_probe`` as a device tensor: the sum of the complementarity products after the affine step
+        ``(alpha_aff[0], alpha_aff[1])`` along ``sol_aff = [dx; dy]``, ``dirs_aff = (ds, dzL, dzU, dvL, dvU)``; the count of the
+        products that are NaN; the two step lengths.  ``y`` and ``dy`` are not read."""
+        bar = self.layer
+        out = out if out is not None else bar._new(4)
+        ps, pd = bar._state(state), bar._dirs(dirs_aff)
+        args = (bar._vec(sol_aff, bar.n, "sol_aff"), *pd, bar._vec(alpha_aff, 2, "alpha_aff"), bar._vec(out, 4, "out"))
+        L, a = self._handle()
+        _lib.check(L.iem_amu_probe(a, ps[0], ps[1], ps[3], ps[4], ps[5], ps[6], *args))
+        return out
+
+    def update(self, out12, probe4=None, force_fixed: bool = False, search: FilterSearch = None):
+        """The stopping test and the adaptive rule on the device (``iem_amu_update``) from the twelve words of
+        :meth:`BarrierParameter.error` and — probing oracle — the four of :meth:`probe`; a ``search`` has its filter emptied and its
+        flags cleared exactly when the bits of ``mu`` changed.  ``force_fixed``: the last step was poor, leave the free mode."""
+        bar = self.layer
+        pw = bar._vec(out12, 12, "out12")
+        pq = bar._vec(probe4, 4, "probe4", optional=True)
+        ps = search._handle()[1] if search is not None else None
+        L, a = self._handle()
+        _lib.check(L.iem_amu_update(a, pw, pq, int(bool(force_fixed)), ps))
+
+    def state(self):
+        """THE read-back (``iem_amu_state``, synchronises once): the dict of :meth:`BarrierParameter.state` and, under the
+        object's own names, ``mode`` / ``mode_name``, ``mu_max``, ``refs`` (oldest first), ``mu_oracle``, ``sigma``, ``avg``,
+        ``m_aff``, ``to_fixed``, ``to_free``, ``oracle`` / ``oracle_name``."""
+        L, a = self._handle()
+        v, u = _lib.MuState(), _lib.AmuState()
+        v.struct_size, u.struct_size = C.sizeof(_lib.MuState), C.sizeof(_lib.AmuState)
+        _lib.check(L.iem_amu_state(a, C.byref(v), C.byref(u)))
+        out = {name: getattr(v, name) for name, _ in _lib.MuState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.MU_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.MU_STATUS) else "?"
+        out["changed"] = bool(out["flags"] & 1)
+        out.update({name: getattr(u, name) for name, _ in _lib.AmuState._fields_ if name not in ("struct_size", "refs", "refs_count")})
+        out["refs"] = [float(u.refs[i]) for i in range(max(0, min(4, int(u.refs_count))))]
+        out["mode_name"] = _lib.AMU_MODE[out["mode"]] if 0 <= out["mode"] < len(_lib.AMU_MODE) else "?"
+        out["oracle_name"] = _lib.AMU_ORACLE[out["oracle"]] if 0 <= out["oracle"] < len(_lib.AMU_ORACLE) else "?"
+        return out
+
+    def device(self):
+        """The address of the object's own block (16 words) on the device (``iem_amu_device``); ``par.device()`` is the other."""
+        L, a = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_amu_device(a, C.byref(blk)))
+        return blk.value
+
+    @contextlib.contextmanager
+    def affine(self, layer: BarrierLayer, search: FilterSearch = None, soc: "SecondOrderCorrection" = None):
+        """The affine-scaling calls of one iteration: ``layer`` (and ``search``, ``soc`` if given) — objects BOUND to ``par`` — are
+        unbound inside the block, so ``terms`` / ``step`` take the host's ``mu = 0``, ``tau = 1``, and bound to ``par`` again
+        afterwards.  No launch either way (the bound variant was loaded by the first bind): inside a capture each node keeps the
+        variant it was captured with."""
+        objs = [o for o in (layer, search, soc) if o is not None]
+        for o in objs:
+            o.bind_mu(None)
+        try:
+            yield self
+        finally:
+            for o in objs:
+                o.bind_mu(self.par)
+
+    def close(self):
+        if self._a is not None:
+            _lib.check(self.layer.model._L.iem_amu_destroy(self._a))
+            self._a = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.par._p is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
                 self.close()
         except Exception:
             pass

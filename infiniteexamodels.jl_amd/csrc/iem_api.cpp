@@ -64,6 +64,9 @@ static const char *kRestoSource =         // the feasibility restoration phase (
 static const char *kMuSource =            // the barrier parameter (iem_mu_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_mu_device_h.inc"
     ;
+static const char *kAmuSource =           // the adaptive barrier parameter (iem_amu_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_amu_device_h.inc"
+    ;
 
 namespace {
 
@@ -332,6 +335,7 @@ struct iem_model {
   struct RestoObject { hipModule_t mod = nullptr; hipFunction_t fn[12] = {}; } resto;
   FixedObject barrier_mu;      // the barrier kernels that read mu and tau from an iem_mu block (barrier_mu_source): loaded by the first bind
   struct MuObject { hipModule_t mod = nullptr; hipFunction_t error = nullptr, update = nullptr, reset = nullptr; } mu;
+  struct AmuObject { hipModule_t mod = nullptr; hipFunction_t probe = nullptr, update = nullptr, reset = nullptr; } amu;      // the adaptive rule (iem_amu_*): loaded by the first iem_amu_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1375,6 +1379,7 @@ int iem_destroy(iem_model *m) {
   if (m->soc.mod) hipModuleUnload(m->soc.mod);
   if (m->resto.mod) hipModuleUnload(m->resto.mod);
   if (m->mu.mod) hipModuleUnload(m->mu.mod);
+  if (m->amu.mod) hipModuleUnload(m->amu.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -5030,6 +5035,195 @@ int iem_soc_bind_mu(iem_soc *q, const iem_mu *p) {
   if (!q) return fail(IEM_E_ARG, "null argument");
   if (p && p->b != q->s->b) return fail(IEM_E_ARG, "iem_soc_bind_mu: the iem_mu object was created on another barrier object");
   q->mu_blk = p ? p->d_blk : nullptr;
+  return IEM_OK;
+}
+
+/* ---- the adaptive barrier parameter: the probing oracle's look along the affine direction, the free / fixed rule on an iem_mu block (csrc/iem_amu_device.h) ---- */
+struct iem_amu {
+  iem_mu *p = nullptr;                 // the object whose block it drives (borrowed)
+  iem_amu_opts_t opt;
+  double *d_blk = nullptr;             // the own block: 16 words
+  double *d_red = nullptr;             // 2 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  long long *d_tab = nullptr;          // offs[2] | first[2] | count[2] of iem_shared_totals
+};
+
+namespace {
+// AmuArgs of csrc/iem_amu_device.h
+struct AmuArgsH {
+  const double *xl, *xu, *rl, *ru;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *zL, *zU, *vL, *vU;
+  const double *sol, *ds, *dzL, *dzU, *dvL, *dvU;
+  const double *alpha;
+  double *out;
+  const double *w;
+  const double *probe;
+  double *mblk;
+  double *ablk;
+  double *sctl;
+  double *red;
+  const long long *tab;
+  double kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max;
+  double sigma_max, mu_min, mu_max_fact, init_factor, red_fact;
+  long long refs_max, oracle, force_fixed;
+  long long ncon, nz;
+  long long nvar, n, n_wg;
+};
+AmuArgsH amu_args(const iem_amu *a) {
+  const iem_mu *p = a->p;
+  const iem_barrier *b = p->b;
+  AmuArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.mblk = p->d_blk; A.ablk = a->d_blk; A.red = a->d_red; A.tab = a->d_tab;
+  A.kappa_eps = p->opt.kappa_eps; A.kappa_mu = p->opt.kappa_mu; A.tau_min = p->opt.tau_min; A.tol = p->opt.tol; A.mu_floor = p->opt.mu_floor; A.s_max = p->opt.s_max;
+  A.sigma_max = a->opt.sigma_max; A.mu_min = a->opt.mu_min; A.mu_max_fact = a->opt.mu_max_fact; A.init_factor = a->opt.init_factor; A.red_fact = a->opt.red_fact;
+  A.refs_max = (long long)a->opt.refs_max; A.oracle = (long long)a->opt.oracle;
+  A.ncon = (long long)b->ncon; A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int amu_object(iem_model *m) {
+  iem_model::AmuObject &o = m->amu;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kAmuSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[3] = {KernelSlot{"amu_probe", &o.probe}, KernelSlot{"amu_update", &o.update}, KernelSlot{"amu_reset", &o.reset}};
+  return load_object(m, src, slots, 3, &o.mod);
+}
+int amu_opts(const iem_amu_opts_t *in, iem_amu_opts_t *out) {
+  iem_amu_opts_t v = {sizeof v, IEM_AMU_PROBING, 100.0, 1e-11, 1e3, 0.8, 0.9999, 4};      // Ipopt's sigma_max, mu_min, adaptive_mu_kkterror_red_fact / _red_iters, adaptive_mu_monotone_init_factor; mu_max_fact
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_amu_create: set struct_size to sizeof(iem_amu_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  for (double f : {v.sigma_max, v.mu_min, v.mu_max_fact, v.init_factor, v.red_fact})
+    if (!std::isfinite(f)) return fail(IEM_E_ARG, "iem_amu_create: every option must be finite");
+  if (v.oracle != IEM_AMU_PROBING && v.oracle != IEM_AMU_LOQO) return fail(IEM_E_ARG, "iem_amu_create: oracle must be 0 (probing) or 1 (LOQO)");
+  if (!(v.sigma_max > 0.0)) return fail(IEM_E_ARG, "iem_amu_create: sigma_max must be positive");
+  if (!(v.mu_min > 0.0)) return fail(IEM_E_ARG, "iem_amu_create: mu_min must be positive");
+  if (!(v.mu_max_fact > 0.0)) return fail(IEM_E_ARG, "iem_amu_create: mu_max_fact must be positive");
+  if (!(v.init_factor > 0.0)) return fail(IEM_E_ARG, "iem_amu_create: init_factor must be positive");
+  if (!(v.red_fact > 0.0 && v.red_fact < 1.0)) return fail(IEM_E_ARG, "iem_amu_create: red_fact must lie in (0, 1)");
+  if (v.refs_max < 1 || v.refs_max > 4) return fail(IEM_E_ARG, "iem_amu_create: refs_max must lie in 1..4");
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_amu_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kAmuSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_amu_destroy(iem_amu *a) {
+  if (!a) return IEM_OK;
+  DevGuard dg_(a->p->b->m->device);
+  for (void *q : {(void *)a->d_blk, (void *)a->d_red, (void *)a->d_tab})
+    if (q) hipFree(q);
+  delete a;
+  return IEM_OK;
+}
+
+int iem_amu_create(iem_mu *p, const iem_amu_opts_t *opts, iem_amu **out) {
+  if (!p || !out) return fail(IEM_E_ARG, "null argument");
+  iem_amu_opts_t opt;
+  {
+    int rc = amu_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  const iem_barrier *b = p->b;
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = amu_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_amu *a) const { iem_amu_destroy(a); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_amu, Drop> a(new iem_amu);
+  a->p = p;
+  a->opt = opt;
+  const int64_t n_red = 2 * b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&a->d_blk, 16 * 8));
+  HIP_TRY(hipMalloc((void **)&a->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMalloc((void **)&a->d_tab, 6 * 8));
+  long long tab[6];
+  for (int s = 0; s < 2; ++s) { tab[s] = s * (long long)b->n_wg; tab[2 + s] = 0; tab[4 + s] = (long long)b->n_wg; }
+  int64_t blk[16] = {};      // mode FREE, mu_max unset, the ring empty, counters 0
+  blk[13] = opt.oracle;
+  HIP_TRY(hipMemcpy(a->d_blk, blk, sizeof blk, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(a->d_red, 0, (size_t)n_red * 8));
+  HIP_TRY(hipMemcpy(a->d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  *out = a.release();
+  return IEM_OK;
+}
+
+int iem_amu_reset(iem_amu *a) {
+  if (!a) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = a->p->b->m;
+  DevGuard dg_(m->device);
+  AmuArgsH A = amu_args(a);
+  return kkt_launch_raw(m, m->amu.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_amu_probe(iem_amu *a, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                  const double *d_sol, const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU,
+                  const double *d_alpha, double *d_out) {
+  if (!a || !d_sol || !d_alpha || !d_out) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = a->p->b;
+  if ((b->nvar && (!d_x || !d_zL || !d_zU || !d_dzL || !d_dzU)) || (b->n_ineq && (!d_s || !d_vL || !d_vU || !d_ds || !d_dvL || !d_dvU))) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  AmuArgsH A = amu_args(a);
+  A.x = d_x; A.s = d_s; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  A.sol = d_sol; A.ds = d_ds; A.dzL = d_dzL; A.dzU = d_dzU; A.dvL = d_dvL; A.dvU = d_dvU;
+  A.alpha = d_alpha; A.out = d_out;
+  return kkt_launch_raw(m, m->amu.probe, &A, sizeof A, b->n_wg, 256);      // no seed: the last arrival writes all four words
+}
+
+int iem_amu_update(iem_amu *a, const double *d_out12, const double *d_probe4, int force_fixed, iem_search *fs) {
+  if (!a || !d_out12) return fail(IEM_E_ARG, "null argument");
+  if (a->opt.oracle == IEM_AMU_PROBING && !d_probe4) return fail(IEM_E_ARG, "iem_amu_update: the probing oracle needs the four words of iem_amu_probe");
+  if (fs && fs->b != a->p->b) return fail(IEM_E_ARG, "iem_amu_update: the search belongs to another barrier object");
+  iem_model *m = a->p->b->m;
+  DevGuard dg_(m->device);
+  AmuArgsH A = amu_args(a);
+  A.w = d_out12;
+  A.probe = a->opt.oracle == IEM_AMU_PROBING ? d_probe4 : nullptr;
+  A.force_fixed = force_fixed ? 1 : 0;
+  A.sctl = fs ? fs->d_ctl : nullptr;
+  return kkt_launch_raw(m, m->amu.update, &A, sizeof A, 1, 64);
+}
+
+int iem_amu_device(const iem_amu *a, double **d_block) {
+  if (!a) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = a->d_blk;
+  return IEM_OK;
+}
+
+int iem_amu_state(iem_amu *a, iem_mu_state_t *mu_out, iem_amu_state_t *out) {
+  if (!a || !mu_out || !out) return fail(IEM_E_ARG, "null argument");
+  if (mu_out->struct_size < sizeof(uint64_t) || out->struct_size < sizeof(uint64_t))
+    return fail(IEM_E_ARG, "iem_amu_state: set struct_size to sizeof(iem_mu_state_t) / sizeof(iem_amu_state_t) before the call");
+  iem_model *m = a->p->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[32];
+  HIP_TRY(hipMemcpyAsync(w, a->p->d_blk, 16 * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(w + 16, a->d_blk, 16 * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));      // ONE synchronisation for both blocks
+  iem_mu_state_t v;
+  v.struct_size = std::min<uint64_t>(mu_out->struct_size, sizeof v);
+  std::memcpy(&v.mu, w, 12 * 8);
+  std::memcpy(mu_out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  iem_amu_state_t u;
+  static_assert(sizeof u == 15 * 8, "iem_amu_state_t: struct_size, then words 0-13 of the own block");
+  u.struct_size = std::min<uint64_t>(out->struct_size, sizeof u);
+  std::memcpy(&u.mode, w + 16, 14 * 8);
+  std::memcpy(out, &u, (size_t)u.struct_size);
   return IEM_OK;
 }
 

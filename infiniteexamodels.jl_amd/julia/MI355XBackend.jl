@@ -706,6 +706,76 @@ bind_mu!(l::BarrierLayer, q) = check(ccall((:iem_barrier_bind_mu, LIBIEM), Cint,
 bind_mu!(f::FilterSearch, q) = check(ccall((:iem_search_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), f.s, _mu_handle(q)))
 bind_mu!(c::SecondOrderCorrection, q) = check(ccall((:iem_soc_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), c.q, _mu_handle(q)))
 
+# ---- the adaptive barrier parameter (include/iem.h: iem_amu_*) -----------------------------------------------------------------------
+# Ipopt's mu_strategy = adaptive (kkt-error globalisation; probing or LOQO oracle) ON a BarrierParameter, whose block it drives: the objects
+# bound to that parameter follow.  Per iteration, in the place of mu_update!: mu_error!; amu_affine(amu, layer, search) do ... end around
+# barrier_terms!(mu = 0), the back-solve of its rhs on the iteration's factors, barrier_step!(mu = 0, tau = 1) and amu_probe! (four words);
+# amu_update!(amu, out12, probe4; search); amu_state — the one read-back, both blocks.  LOQO needs no affine solve: amu_update!(amu, out12,
+# nothing).  Finalize (or let go of) the adaptive object before its BarrierParameter.  UNEXECUTED, like the rest.
+struct IemAmuOpts          # iem_amu_opts_t
+    struct_size::UInt64
+    oracle::Int64          # 0 probing, 1 LOQO
+    sigma_max::Float64; mu_min::Float64; mu_max_fact::Float64; init_factor::Float64; red_fact::Float64
+    refs_max::Int64        # 1..4
+end
+struct IemAmuState         # iem_amu_state_t: words 0-13 of the object's own block
+    struct_size::UInt64
+    mode::Int64            # 0 free, 1 fixed
+    mu_max::Float64
+    refs_count::Int64
+    refs::NTuple{4, Float64}      # oldest first
+    mu_oracle::Float64; sigma::Float64; avg::Float64; m_aff::Float64
+    to_fixed::Int64; to_free::Int64; oracle::Int64
+end
+mutable struct AdaptiveBarrierParameter
+    a::Ptr{Cvoid}
+    par::BarrierParameter      # borrowed: kept alive
+end
+function AdaptiveBarrierParameter(q::BarrierParameter; oracle = 0, sigma_max = 100.0, mu_min = 1e-11, mu_max_fact = 1e3, init_factor = 0.8, red_fact = 0.9999, refs_max = 4)
+    opts = Ref(IemAmuOpts(sizeof(IemAmuOpts), oracle, sigma_max, mu_min, mu_max_fact, init_factor, red_fact, refs_max))
+    a = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_amu_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemAmuOpts}, Ptr{Ptr{Cvoid}}), q.p, opts, a))
+    amu = AdaptiveBarrierParameter(a[], q)
+    finalizer(o -> (o.a == C_NULL || o.par.p == C_NULL || ccall((:iem_amu_destroy, LIBIEM), Cint, (Ptr{Cvoid},), o.a); o.a = C_NULL), amu)
+    return amu
+end
+# a new solve: mode free, the ring empty, mu_max unset, counters zero (asynchronous); mu_reset! on the parameter is a call of its own
+amu_reset!(o::AdaptiveBarrierParameter) = check(ccall((:iem_amu_reset, LIBIEM), Cint, (Ptr{Cvoid},), o.a))
+# out: four doubles on the device; sol = [dx; dy] and dirs = (ds, dzL, dzU, dvL, dvU) of the affine step, alpha its two step lengths on the device
+function amu_probe!(o::AdaptiveBarrierParameter, state, sol, dirs, alpha, out)
+    check(ccall((:iem_amu_probe, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 14)...),
+                o.a, spptr(state[1]), spptr(state[2]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]),
+                dptr(sol), spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha), dptr(out)))
+    return out
+end
+# out12: the twelve of mu_error!; probe4: the four of amu_probe!, or nothing (LOQO); search: a FilterSearch on the same BarrierLayer, or nothing
+function amu_update!(o::AdaptiveBarrierParameter, out12, probe4; force_fixed = false, search = nothing)
+    check(ccall((:iem_amu_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+                o.a, dptr(out12), probe4 === nothing ? Ptr{Float64}(C_NULL) : dptr(probe4), force_fixed ? 1 : 0, search === nothing ? C_NULL : search.s))
+end
+# the one read-back (synchronises the stream once): (IemMuState, IemAmuState)
+function amu_state(o::AdaptiveBarrierParameter)
+    st = Ref(IemMuState(sizeof(IemMuState), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    own = Ref(IemAmuState(sizeof(IemAmuState), 0, 0, 0, (0.0, 0.0, 0.0, 0.0), 0, 0, 0, 0, 0, 0, 0))
+    check(ccall((:iem_amu_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMuState}, Ptr{IemAmuState}), o.a, st, own))
+    return st[], own[]
+end
+# the own block (16 words of 8 bytes) as a device address
+function amu_device(o::AdaptiveBarrierParameter)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_amu_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.a, p))
+    return p[]
+end
+# the affine-scaling calls of one iteration: the objects (bound to the parameter) are unbound around f and bound again — no launch either way
+function amu_affine(f, o::AdaptiveBarrierParameter, objs...)
+    foreach(x -> bind_mu!(x, nothing), objs)
+    try
+        return f()
+    finally
+        foreach(x -> bind_mu!(x, o.par), objs)
+    end
+end
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,

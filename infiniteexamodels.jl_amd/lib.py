@@ -180,6 +180,38 @@ class MuState(C.Structure):
 MU_STATUS = ("iterating", "converged", "unusable")
 
 
+class AmuOpts(C.Structure):
+    """``iem_amu_opts_t``: ``struct_size`` is set by the caller; ``AmuOpts.defaults()`` has the library's values (``oracle``: 0 probing,
+    1 LOQO — or the names of ``AMU_ORACLE``)."""
+    _fields_ = ([("struct_size", C.c_uint64), ("oracle", C.c_int64)] +
+                [(n, C.c_double) for n in ("sigma_max", "mu_min", "mu_max_fact", "init_factor", "red_fact")] + [("refs_max", C.c_int64)])
+    DEFAULTS = dict(oracle=0, sigma_max=100.0, mu_min=1e-11, mu_max_fact=1e3, init_factor=0.8, red_fact=0.9999, refs_max=4)
+
+    @classmethod
+    def defaults(cls, **over):
+        unknown = set(over) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown adaptive barrier parameter option(s): {sorted(unknown)}")
+        if isinstance(over.get("oracle"), str):
+            if over["oracle"] not in AMU_ORACLE:
+                raise ValueError(f"oracle: one of {AMU_ORACLE} expected, got {over['oracle']!r}")
+            over["oracle"] = AMU_ORACLE.index(over["oracle"])
+        o = cls(**{**cls.DEFAULTS, **over})
+        o.struct_size = C.sizeof(cls)
+        return o
+
+
+class AmuState(C.Structure):
+    """``iem_amu_state_t``: ``struct_size`` (set by the caller), then words 0-13 of the object's own block."""
+    _fields_ = [("struct_size", C.c_uint64), ("mode", C.c_int64), ("mu_max", C.c_double), ("refs_count", C.c_int64), ("refs", C.c_double * 4),
+                ("mu_oracle", C.c_double), ("sigma", C.c_double), ("avg", C.c_double), ("m_aff", C.c_double),
+                ("to_fixed", C.c_int64), ("to_free", C.c_int64), ("oracle", C.c_int64)]
+
+
+AMU_MODE = ("free", "fixed")
+AMU_ORACLE = ("probing", "loqo")
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("kind", C.c_int32), ("jit", C.c_int32), ("grid", C.c_int64 * 3),
                 ("lds_bytes", C.c_int64), ("alg_bytes_read", C.c_int64), ("alg_bytes_written", C.c_int64)]
@@ -191,7 +223,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_resto_create", "iem_resto_destroy", "iem_resto_search", "iem_resto_enter", "iem_resto_terms", "iem_resto_step", "iem_resto_merit", "iem_resto_begin", "iem_resto_trial", "iem_resto_update", "iem_resto_error", "iem_resto_check", "iem_resto_leave", "iem_resto_device", "iem_resto_state", "iem_resto_source", "iem_mu_create", "iem_mu_destroy", "iem_mu_reset", "iem_mu_error", "iem_mu_update", "iem_mu_device", "iem_mu_state", "iem_barrier_bind_mu", "iem_search_bind_mu", "iem_soc_bind_mu", "iem_mu_source", "iem_barrier_mu_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_resto_create", "iem_resto_destroy", "iem_resto_search", "iem_resto_enter", "iem_resto_terms", "iem_resto_step", "iem_resto_merit", "iem_resto_begin", "iem_resto_trial", "iem_resto_update", "iem_resto_error", "iem_resto_check", "iem_resto_leave", "iem_resto_device", "iem_resto_state", "iem_resto_source", "iem_mu_create", "iem_mu_destroy", "iem_mu_reset", "iem_mu_error", "iem_mu_update", "iem_mu_device", "iem_mu_state", "iem_barrier_bind_mu", "iem_search_bind_mu", "iem_soc_bind_mu", "iem_mu_source", "iem_barrier_mu_source", "iem_amu_create", "iem_amu_destroy", "iem_amu_reset", "iem_amu_probe", "iem_amu_update", "iem_amu_device", "iem_amu_state", "iem_amu_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -384,6 +416,14 @@ def lib():
     L.iem_soc_bind_mu.argtypes = [vp, vp]
     L.iem_mu_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_barrier_mu_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.iem_amu_create.argtypes = [vp, C.POINTER(AmuOpts), C.POINTER(vp)]
+    L.iem_amu_destroy.argtypes = [vp]
+    L.iem_amu_reset.argtypes = [vp]
+    L.iem_amu_probe.argtypes = [vp] + [vp] * 6 + [vp] * 6 + [vp, vp]
+    L.iem_amu_update.argtypes = [vp, vp, vp, i32, vp]
+    L.iem_amu_device.argtypes = [vp, C.POINTER(vp)]
+    L.iem_amu_state.argtypes = [vp, C.POINTER(MuState), C.POINTER(AmuState)]
+    L.iem_amu_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_fixed_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -528,6 +568,12 @@ def mu_source():
     """HIP source of the barrier parameter's kernels (``mu_error`` / ``mu_update`` / ``mu_reset``: the ``iem_mu_*`` calls) and its cache
     key.  A code object of its own: not one of :func:`fixed_sources`."""
     return _source(lib().iem_mu_source)
+
+
+def amu_source():
+    """HIP source of the adaptive barrier parameter's kernels (``amu_probe`` / ``amu_update`` / ``amu_reset``: the ``iem_amu_*`` calls) and
+    its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
+    return _source(lib().iem_amu_source)
 
 
 def barrier_mu_source():
