@@ -1079,7 +1079,8 @@ int iem_resto_source(char **out_src, uint64_t *out_key);
  * s_max <= 0, any option not finite, mu0 <= 0 or not finite, an fs or a bind across two barrier objects.  The object borrows the
  * barrier object; a bound object borrows the block: unbind (or destroy the bound objects) before iem_mu_destroy.  Not here: the
  * delta_w / inertia retry, a binding for iem_resto, sharded handles.  The adaptive rules that words 8 and 9 of iem_mu_error
- * serve (probing, LOQO) are the iem_amu object below; Mehrotra's corrector and the quality-function oracle are not there either. */
+ * serve (probing, LOQO) are the iem_amu object below, the quality-function oracle the iem_qf object below it; Mehrotra's corrector is
+ * not there. */
 typedef struct iem_mu iem_mu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mu_opts_t) */
@@ -1158,9 +1159,9 @@ int iem_barrier_mu_source(char **out_src, uint64_t *out_key);
  * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  IEM_E_ARG before any device
  * work: null required pointers (the slack side may be NULL without inequality rows), a probing object updated without q, an fs of
  * another barrier object, oracle not 0 or 1, sigma_max, mu_min, mu_max_fact or init_factor <= 0, red_fact outside (0, 1), refs_max
- * outside 1..4, any option not finite.  The object borrows the iem_mu object: destroy it first.  Not here: Mehrotra's corrector,
- * Ipopt's quality-function oracle, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w /
- * inertia retry (the host's). */
+ * outside 1..4, any option not finite.  The object borrows the iem_mu object: destroy it first.  Ipopt's quality-function oracle
+ * (oracle = 2 here is refused) is the iem_qf object below.  Not here: Mehrotra's corrector, the obj-constr-filter globalisation, a
+ * binding for iem_resto, sharded handles, the delta_w / inertia retry (the host's). */
 typedef struct iem_amu iem_amu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_amu_opts_t) */
@@ -1191,6 +1192,116 @@ int iem_amu_device(const iem_amu *a, double **d_block);
 int iem_amu_state(iem_amu *a, iem_mu_state_t *mu_out, iem_amu_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the three kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_amu_source(char **out_src, uint64_t *out_key);
+
+/* ---- the quality-function oracle -------------------------------------------------------------------------------------------------------
+ * Ipopt's `mu_oracle = quality-function` (its default for mu_strategy = adaptive; QualityFunctionMuOracle with the 2-norm squared,
+ * no centrality and no balancing term; MadNLP's adaptive update has the same one) on the device (csrc/iem_qf_device.h), as an object
+ * created ON an iem_amu: it reads that object's block and the iem_mu block under it, and iem_qf_update goes in the place of
+ * iem_amu_update.  sigma_max defaults to the iem_amu object's; mu_min, mu_max_fact, init_factor, red_fact, refs_max are that
+ * object's, kappa_eps, kappa_mu, tau_min, tol, mu_floor and s_max those of the iem_mu object.  The iem_amu object's oracle option
+ * is not consulted.
+ *
+ * THE DIRECTION for a candidate sigma comes from existing calls.  The Newton direction is affine in mu for fixed factors, so with the
+ * barrier object UNBOUND (iem_barrier_bind_mu(b, NULL)):
+ *         iem_barrier_terms(mu = 0) and iem_barrier_terms(mu = mu_ref) -> two right-hand-side columns (sigma, dcon do not depend on mu);
+ *         one assemble + factor (the host's delta_w retry);  ONE iem_kkt_solve_refined_diag(nrhs = 2);
+ *         iem_barrier_step(mu = 0, tau = 1) -> d0,  iem_barrier_step(mu = mu_ref, tau = 1) -> d1 (their alphas are ignored)
+ *     and for every component the oracle reads (dx = sol[i], ds, dzL, dzU, dvL, dvU; never dy), each operation rounded once:
+ *         t = sigma·avg;  t = t/mu_ref          (once per thread)          e = d1 − d0;  u = t·e;  d = d0 + u
+ *     ONE device function forms d for both grid kernels.  With d1 = d0 the direction is d0 bit for bit (but −0.0 becomes +0.0).
+ *
+ * THE OWN BLOCK: thirty-two 8-byte words on the device (iem_qf_device gives the pointer; iem_qf_state_t mirrors words 0–26):
+ *     0 status (int64): 0 IDLE, 1 SECTION, 2 DONE, 3 UNUSABLE      1 phase (int64): which evaluation is next — 0 the first sigma,
+ *     1 the second, 2 / 3 the left / right interior point of the first bracket, 4 / 5 a new left / right interior point
+ *     2 section steps taken (int64)      3 evaluations (int64)      4 sigma: the trial the next alpha / value pair evaluates
+ *     5, 6 the alpha slots (alpha_primal, alpha_dual as bit patterns)      7 D2      8 P2      9 avg      10 lo      11 hi
+ *     12, 13 the bracket [a, b]      14, 15 its interior points c < d      16, 17 q(c), q(d)
+ *     18 the evaluated sigma of least q      19 that q      20 q at the first sigma
+ *     21–25 the last evaluation: q, C2, the count of NaN products, alpha_primal, alpha_dual      26 the first sigma      27–31 zero
+ * iem_qf_create zeroes it (IDLE); iem_qf_reset (one launch of one workgroup, asynchronous) does the same.
+ * iem_qf_begin: ONE launch on the barrier object's grid, the entry order and flags of iem_mu_error, no seed, capturable.  Two sums,
+ *     a lane adding its entries in index order, the workgroups parking, the last arrival totalling in the fixed order of the
+ *     barrier sums:   D2 = sum over variables of t·t, t = r − zL + zU, and over inequality rows of t·t, t = −y − vL + vU;
+ *     P2 = sum over rows of inf·inf, inf = c − ceq (equality) or c − s — the residual expressions of iem_barrier_error, in its
+ *     order (t = r; t = t − zL where the lower bound is present; t = t + zU where the upper one is).  The last arrival then zeroes
+ *     the block, stores D2 and P2 and, with w the twelve words of iem_mu_error and every max / min propagating a NaN,
+ *         nz == 0:  status DONE, nothing else.  Otherwise
+ *         avg = w9/nz;  mu_max = word 1 of the iem_amu block, or mu_max_fact·avg while that word is +0.0 (the word is not written)
+ *         lo = max(sigma_min, mu_min/avg);  hi = max(lo, min(sigma_max, mu_max/avg));  sigma = min(max(1, lo), hi)
+ *         the alpha slots = the bits of 1.0;  phase 0;  status SECTION.
+ * iem_qf_alpha: ONE launch on the same grid: the fraction-to-the-boundary step lengths of d(sigma) — the candidates
+ *     (−tau·gap)/d, (tau·gap)/d, (−tau·z)/dz and the unusable-value rules of iem_barrier_step (a candidate that is not > 0 counts
+ *     as +0.0; a NaN in dx or in the ds of an inequality row makes alpha_primal +0.0 whatever the bounds, a NaN in a multiplier's
+ *     direction at a present bound makes alpha_dual +0.0) — except that dy is not read and tau is word 1 of the iem_mu block.
+ *     Integer minima on the bit patterns into slots 5 and 6, at most one atomic per workgroup and slot.
+ * iem_qf_value: ONE launch on the same grid.  With ap, ad the two slots read once, per PRESENT bound in the operation order of
+ *     iem_amu_probe:   t = ap·d;  g = gap + t (lower) or gap − t (upper);  u = ad·dz;  w = z + u;  p = g·w;   the columns
+ *     C2 = sum of p·p and the count of the p that are NaN are parked and totalled as above.  The last arrival forms
+ *         q = +inf  if ap or ad carries the bits of +0.0 or a product was a NaN; otherwise
+ *         ud = 1 − ad;  up = 1 − ap;  td = ((ud·ud)·D2)/n_d;  tp = ((up·up)·P2)/n_p;  tc = C2/nz;  q = (td + tp) + tc
+ *     with n_d = nvar + inequality rows, n_p = ncon, a term whose count is 0 being +0.0, and a NaN q counting as +inf; then it
+ *     takes ONE step of the section below, writes the next trial sigma into word 4 and re-seeds the two slots with the bits of 1.0.
+ * THE SECTION, word for word (g = 0.6180339887498949, tol = section_sigma_tol, every comparison on q with NaN already +inf):
+ *     every evaluation:  evaluations += 1;  words 21–25;  if it is the first or q < word 19: words 18, 19 = sigma, q (the first of
+ *         equal values stays)
+ *     phase 0:  word 20 = q;  sigma <- max(lo, sigma·(1 − 1e-2));  phase 1
+ *     phase 1:  [a, b] = [lo, sigma] if q <= word 20, else [first sigma, hi];  w = b − a;  if w <= tol·b: FINISH;  else
+ *               gw = g·w;  c = b − gw;  d = a + gw;  sigma <- c;  phase 2
+ *     phase 2:  q(c) = q;  sigma <- d;  phase 3
+ *     phase 3 or 5:  q(d) = q;  STEP            phase 4:  q(c) = q;  STEP
+ *     STEP:  if steps == max_section_steps: FINISH;  else
+ *               q(c) <= q(d):  b = d;  d = c;  q(d) = q(c);  gw = g·(b − a);  c = b − gw;  sigma <- c;  phase 4
+ *               otherwise:     a = c;  c = d;  q(c) = q(d);  gw = g·(b − a);  d = a + gw;  sigma <- d;  phase 5
+ *            steps += 1;  if b − a <= tol·b: FINISH (the new point is not evaluated)
+ *     FINISH:  status = UNUSABLE if word 19 is +inf (every q was), else DONE;  word 4 stays.
+ *     So there is one new evaluation per step, at most max_section_steps + 4 evaluations in all, and lo == hi finishes after two.
+ *     With a status other than SECTION, iem_qf_alpha and iem_qf_value return before their first store: the host issues
+ *     max_section_steps + 4 alpha / value pairs with no decision in between, and a captured sequence is valid at every state.
+ * iem_qf_update: ONE workgroup of 64 threads, one thread decides: iem_amu_update's rule word for word on the same two blocks —
+ *     the stopping test, the ring of references, the free / fixed modes, the monotone loop, fs's filter emptied exactly when the
+ *     bits of mu changed.  Only the free-mode oracle differs: sigma (word 8 of the iem_amu block) = word 18, word 7 = sigma·avg,
+ *     word 10 = word 19; and UNUSABLE has one more condition: a section whose status is not DONE.
+ * iem_qf_state: the one read-back — the iem_mu block, the iem_amu block and the own block behind ONE synchronisation.
+ * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  No float atomic, no cooperative
+ * launch, no grid-wide wait: every dependence between workgroups is a launch boundary.  IEM_E_ARG before any device work: null
+ * required pointers (the slack side may be NULL without inequality rows), an fs of another barrier object, mu_ref, sigma_min or
+ * section_sigma_tol <= 0, sigma_max < 0 (0: the iem_amu object's), max_section_steps outside 1..16, any option not finite.  The
+ * object borrows the iem_amu object: destroy it first.  Not here: Ipopt's other norm types, the centrality and balancing terms,
+ * Mehrotra's corrector, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w / inertia retry. */
+typedef struct iem_qf iem_qf;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_qf_opts_t) */
+  double mu_ref, sigma_min, sigma_max, section_sigma_tol;
+  int64_t max_section_steps;            /* 1..16 */
+} iem_qf_opts_t;                        /* NULL = 1.0, 1e-6, 0 (= the iem_amu object's sigma_max), 1e-2, 8 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_qf_state_t): at most that many bytes are written */
+  int64_t status, phase, steps, evaluations;      /* words 0–3 */
+  double sigma_trial;                   /* word 4 */
+  double alpha_slots[2];                /* words 5, 6 */
+  double d2, p2, avg, lo, hi;           /* words 7–11 */
+  double a, b, c, d, qc, qd;            /* words 12–17 */
+  double sigma, q, q_first;             /* words 18–20: the result, its q, q at the first sigma */
+  double q_last, c2_last, nan_last, alpha_p_last, alpha_d_last;      /* words 21–25 */
+  double sigma_first;                   /* word 26 */
+} iem_qf_state_t;
+enum { IEM_QF_IDLE = 0, IEM_QF_SECTION = 1, IEM_QF_DONE = 2, IEM_QF_UNUSABLE = 3 };
+int iem_qf_create(iem_amu *a, const iem_qf_opts_t *opts, iem_qf **out);
+int iem_qf_destroy(iem_qf *q);
+int iem_qf_reset(iem_qf *q);
+int iem_qf_begin(iem_qf *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_r, const double *d_c, const double *d_out12 /* of iem_mu_error */);
+int iem_qf_alpha(iem_qf *q, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_sol0, const double *d_ds0, const double *d_dzL0, const double *d_dzU0, const double *d_dvL0, const double *d_dvU0,
+                 const double *d_sol1, const double *d_ds1, const double *d_dzL1, const double *d_dzU1, const double *d_dvL1, const double *d_dvU1);
+int iem_qf_value(iem_qf *q, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_sol0, const double *d_ds0, const double *d_dzL0, const double *d_dzU0, const double *d_dvL0, const double *d_dvU0,
+                 const double *d_sol1, const double *d_ds1, const double *d_dzL1, const double *d_dzU1, const double *d_dvL1, const double *d_dvU1);
+int iem_qf_update(iem_qf *q, const double *d_out12 /* of iem_mu_error */, int force_fixed, iem_search *fs /* may be NULL */);
+int iem_qf_device(const iem_qf *q, double **d_block);
+int iem_qf_state(iem_qf *q, iem_mu_state_t *mu_out, iem_amu_state_t *amu_out, iem_qf_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the five kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_qf_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

@@ -658,6 +658,152 @@ class AdaptiveBarrierParameter:
             pass
 
 
+class QualityFunction:
+    """``QualityFunction(amu, **opts)``: the quality-function oracle of the C-ABI (``iem_qf_*``, ``csrc/iem_qf_device.h``) ON an
+    :class:`AdaptiveBarrierParameter` — Ipopt's default ``mu_oracle`` for ``mu_strategy = adaptive``: a golden-section search over
+    ``sigma`` of the 2-norm-squared quality function, one launch for the step lengths and one for the value per candidate, the whole
+    state machine on the device, and the adaptive rule with its result in one launch.  ``opts``: ``mu_ref, sigma_min, sigma_max``
+    (0: ``amu``'s), ``section_sigma_tol, max_section_steps``.  Per iteration, in place of ``amu.update``:
+
+        w = par.error(state, r, c, out=w)
+        with amu.affine(bar, fs):                                      # unbound inside: the calls take the host's mu and tau = 1
+            _, _, rhs0 = bar.terms(state, r, c, 0.0, out=(sigma, dcon, rhs2[0]))
+            _, _, rhs1 = bar.terms(state, r, c, qf.opts["mu_ref"], out=(sigma, dcon, rhs2[1]))
+            sol2 = kkt.solve(rhs2.t(), refine=1).t()                   # rhs2: (2, n).  ONE pass over the iteration's factors for both columns
+            d0 = bar.step(state, sol2[0], 0.0, 1.0)[0]
+            d1 = bar.step(state, sol2[1], qf.opts["mu_ref"], 1.0)[0]
+        qf.begin(state, r, c, w)
+        qf.section(state, (sol2[0], *d0), (sol2[1], *d1))              # max_section_steps + 4 alpha / value pairs, no decision between
+        qf.update(w, search=fs)
+        st = qf.state()                                                # THE read-back: the three blocks"""
+
+    def __init__(self, amu: AdaptiveBarrierParameter, **opts):
+        self.amu = amu
+        self.par = amu.par
+        self.layer = amu.layer
+        self._q = None
+        o = _lib.QfOpts.defaults(**opts)
+        L, a = amu._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_qf_create(a, C.byref(o), C.byref(q)))
+        self._q = q
+        self.opts = {name: getattr(o, name) for name, _ in _lib.QfOpts._fields_ if name != "struct_size"}
+        if self.opts["sigma_max"] == 0.0:
+            self.opts["sigma_max"] = amu.opts["sigma_max"]
+        self.pairs = int(self.opts["max_section_steps"]) + 4
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("QualityFunction: closed")
+        L, _ = self.amu._handle()
+        return L, self._q
+
+    def reset(self):
+        """A new solve (``iem_qf_reset``, asynchronous): the section idle, the block zero.  ``amu.reset()`` and ``par.reset()`` are
+        calls of their own."""
+        L, q = self._handle()
+        _lib.check(L.iem_qf_reset(q))
+
+    def begin(self, state, r, c, out12):
+        """``iem_qf_begin``: the squared norms of the dual and the primal residual, and the section's first trial ``sigma`` from the
+        twelve words of :meth:`BarrierParameter.error` — all into the object's block."""
+        bar = self.layer
+        ps = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(c, bar.ncon, "c"), bar._vec(out12, 12, "out12"))
+        L, q = self._handle()
+        _lib.check(L.iem_qf_begin(q, *ps, *args))
+
+    def _pair_args(self, state, d0, d1):
+        bar = self.layer
+        ps = bar._state(state)
+        if len(d0) != 6 or len(d1) != 6:
+            raise ValueError("d0, d1: (sol, ds, dzL, dzU, dvL, dvU)")
+        cols = []
+        for d, tag in ((d0, "0"), (d1, "1")):
+            cols += [bar._vec(d[0], bar.n, "sol" + tag), *bar._dirs(d[1:])]
+        return (ps[0], ps[1], ps[3], ps[4], ps[5], ps[6], *cols)
+
+    def alpha(self, state, d0, d1):
+        """``iem_qf_alpha``: the fraction-to-the-boundary step lengths of the direction at the trial ``sigma`` into the block's two
+        slots; ``d0 = (sol, ds, dzL, dzU, dvL, dvU)`` at ``mu = 0``, ``d1`` at ``mu = mu_ref``.  Nothing unless a section is open."""
+        args = self._pair_args(state, d0, d1)
+        L, q = self._handle()
+        _lib.check(L.iem_qf_alpha(q, *args))
+
+    def value(self, state, d0, d1):
+        """``iem_qf_value``: the quality function at the trial ``sigma`` with the slots' step lengths, and one step of the section:
+        the next trial, or the result.  Nothing unless a section is open."""
+        args = self._pair_args(state, d0, d1)
+        L, q = self._handle()
+        _lib.check(L.iem_qf_value(q, *args))
+
+    def section(self, state, d0, d1, pairs: int = None):
+        """Every ``alpha`` / ``value`` pair of a section (``max_section_steps + 4``), with no decision in between: pairs behind the
+        one that finishes the section do nothing on the device.  A model without any bound (``nz == 0``: ``begin`` leaves the section
+        DONE) is issued no pair at all — a property of the model, not of the state."""
+        args = self._pair_args(state, d0, d1)
+        L, q = self._handle()
+        if self.layer.info["nz"] == 0 and pairs is None:
+            return
+        for _ in range(self.pairs if pairs is None else int(pairs)):
+            _lib.check(L.iem_qf_alpha(q, *args))
+            _lib.check(L.iem_qf_value(q, *args))
+
+    def update(self, out12, force_fixed: bool = False, search: FilterSearch = None):
+        """The stopping test and the adaptive rule on the device (``iem_qf_update``) with the section's result as the oracle; a
+        ``search`` has its filter emptied and its flags cleared exactly when the bits of ``mu`` changed."""
+        bar = self.layer
+        pw = bar._vec(out12, 12, "out12")
+        ps = search._handle()[1] if search is not None else None
+        L, q = self._handle()
+        _lib.check(L.iem_qf_update(q, pw, int(bool(force_fixed)), ps))
+
+    def state(self):
+        """THE read-back (``iem_qf_state``, synchronises once): the dict of :meth:`AdaptiveBarrierParameter.state` and ``section``:
+        the object's own words by the names of ``iem_qf_state_t`` (``status_name`` among them)."""
+        L, q = self._handle()
+        v, u, t = _lib.MuState(), _lib.AmuState(), _lib.QfState()
+        v.struct_size, u.struct_size, t.struct_size = C.sizeof(_lib.MuState), C.sizeof(_lib.AmuState), C.sizeof(_lib.QfState)
+        _lib.check(L.iem_qf_state(q, C.byref(v), C.byref(u), C.byref(t)))
+        out = {name: getattr(v, name) for name, _ in _lib.MuState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.MU_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.MU_STATUS) else "?"
+        out["changed"] = bool(out["flags"] & 1)
+        out.update({name: getattr(u, name) for name, _ in _lib.AmuState._fields_ if name not in ("struct_size", "refs", "refs_count")})
+        out["refs"] = [float(u.refs[i]) for i in range(max(0, min(4, int(u.refs_count))))]
+        out["mode_name"] = _lib.AMU_MODE[out["mode"]] if 0 <= out["mode"] < len(_lib.AMU_MODE) else "?"
+        sec = {name: getattr(t, name) for name, _ in _lib.QfState._fields_ if name not in ("struct_size", "alpha_slots")}
+        sec["alpha_slots"] = [float(t.alpha_slots[0]), float(t.alpha_slots[1])]
+        sec["status_name"] = _lib.QF_STATUS[sec["status"]] if 0 <= sec["status"] < len(_lib.QF_STATUS) else "?"
+        out["section"] = sec
+        return out
+
+    def device(self):
+        """The address of the object's own block (32 words) on the device (``iem_qf_device``)."""
+        L, q = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_qf_device(q, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        if self._q is not None:
+            _lib.check(self.layer.model._L.iem_qf_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.amu._a is not None and self.par._p is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
 class Restoration:
     """``Restoration(search, rho=1000, kappa_resto=0.9, bound_mult_reset_threshold=1000)``: the feasibility restoration phase of the
     C-ABI (``iem_resto_*``, ``csrc/iem_resto_device.h``) beside the :class:`FilterSearch` of the ORIGINAL problem — the elastic

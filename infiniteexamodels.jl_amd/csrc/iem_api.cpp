@@ -67,6 +67,9 @@ static const char *kMuSource =            // the barrier parameter (iem_mu_*): a
 static const char *kAmuSource =           // the adaptive barrier parameter (iem_amu_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_amu_device_h.inc"
     ;
+static const char *kQfSource =            // the quality-function oracle (iem_qf_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_qf_device_h.inc"
+    ;
 
 namespace {
 
@@ -336,6 +339,7 @@ struct iem_model {
   FixedObject barrier_mu;      // the barrier kernels that read mu and tau from an iem_mu block (barrier_mu_source): loaded by the first bind
   struct MuObject { hipModule_t mod = nullptr; hipFunction_t error = nullptr, update = nullptr, reset = nullptr; } mu;
   struct AmuObject { hipModule_t mod = nullptr; hipFunction_t probe = nullptr, update = nullptr, reset = nullptr; } amu;      // the adaptive rule (iem_amu_*): loaded by the first iem_amu_create
+  struct QfObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, alpha = nullptr, value = nullptr, update = nullptr, reset = nullptr; } qf;      // the quality-function oracle (iem_qf_*): loaded by the first iem_qf_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1380,6 +1384,7 @@ int iem_destroy(iem_model *m) {
   if (m->resto.mod) hipModuleUnload(m->resto.mod);
   if (m->mu.mod) hipModuleUnload(m->mu.mod);
   if (m->amu.mod) hipModuleUnload(m->amu.mod);
+  if (m->qf.mod) hipModuleUnload(m->qf.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -5224,6 +5229,232 @@ int iem_amu_state(iem_amu *a, iem_mu_state_t *mu_out, iem_amu_state_t *out) {
   u.struct_size = std::min<uint64_t>(out->struct_size, sizeof u);
   std::memcpy(&u.mode, w + 16, 14 * 8);
   std::memcpy(out, &u, (size_t)u.struct_size);
+  return IEM_OK;
+}
+
+/* ---- the quality-function oracle: residual norms, step lengths and the quality function at a candidate sigma, the section search, the rule (csrc/iem_qf_device.h) ---- */
+struct iem_qf {
+  iem_amu *a = nullptr;                // the object whose rule it completes (borrowed), on its iem_mu
+  iem_qf_opts_t opt;                   // sigma_max resolved: the iem_amu object's where the caller gave 0
+  double *d_blk = nullptr;             // the own block: 32 words
+  double *d_red = nullptr;             // 2 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  long long *d_tab = nullptr;          // offs[2] | first[2] | count[2] of iem_shared_totals
+};
+
+namespace {
+// QfArgs of csrc/iem_qf_device.h
+struct QfArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c;
+  const double *sol0, *ds0, *dzL0, *dzU0, *dvL0, *dvU0;
+  const double *sol1, *ds1, *dzL1, *dzU1, *dvL1, *dvU1;
+  const double *w;
+  double *mblk;
+  double *ablk;
+  double *qblk;
+  double *sctl;
+  double *red;
+  const long long *tab;
+  double kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max;
+  double mu_min, mu_max_fact, init_factor, red_fact;
+  double mu_ref, sigma_min, sigma_max, sigma_tol;
+  long long max_steps, refs_max, force_fixed;
+  long long n_d, n_p;
+  long long ncon, nz;
+  long long nvar, n, n_wg;
+};
+QfArgsH qf_args(const iem_qf *q) {
+  const iem_amu *a = q->a;
+  const iem_mu *p = a->p;
+  const iem_barrier *b = p->b;
+  QfArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.mblk = p->d_blk; A.ablk = a->d_blk; A.qblk = q->d_blk; A.red = q->d_red; A.tab = q->d_tab;
+  A.kappa_eps = p->opt.kappa_eps; A.kappa_mu = p->opt.kappa_mu; A.tau_min = p->opt.tau_min; A.tol = p->opt.tol; A.mu_floor = p->opt.mu_floor; A.s_max = p->opt.s_max;
+  A.mu_min = a->opt.mu_min; A.mu_max_fact = a->opt.mu_max_fact; A.init_factor = a->opt.init_factor; A.red_fact = a->opt.red_fact;
+  A.mu_ref = q->opt.mu_ref; A.sigma_min = q->opt.sigma_min; A.sigma_max = q->opt.sigma_max; A.sigma_tol = q->opt.section_sigma_tol;
+  A.max_steps = (long long)q->opt.max_section_steps; A.refs_max = (long long)a->opt.refs_max;
+  A.n_d = (long long)(b->nvar + b->n_ineq); A.n_p = (long long)b->ncon;
+  A.ncon = (long long)b->ncon; A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int qf_object(iem_model *m) {
+  iem_model::QfObject &o = m->qf;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kQfSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[5] = {KernelSlot{"qf_begin", &o.begin}, KernelSlot{"qf_alpha", &o.alpha}, KernelSlot{"qf_value", &o.value}, KernelSlot{"qf_update", &o.update},
+                         KernelSlot{"qf_reset", &o.reset}};
+  return load_object(m, src, slots, 5, &o.mod);
+}
+int qf_opts(const iem_qf_opts_t *in, double amu_sigma_max, iem_qf_opts_t *out) {
+  iem_qf_opts_t v = {sizeof v, 1.0, 1e-6, 0.0, 1e-2, 8};      // mu_ref; Ipopt's sigma_min; sigma_max (0: the iem_amu object's); quality_function_section_sigma_tol, quality_function_max_section_steps
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_qf_create: set struct_size to sizeof(iem_qf_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  for (double f : {v.mu_ref, v.sigma_min, v.sigma_max, v.section_sigma_tol})
+    if (!std::isfinite(f)) return fail(IEM_E_ARG, "iem_qf_create: every option must be finite");
+  if (!(v.mu_ref > 0.0)) return fail(IEM_E_ARG, "iem_qf_create: mu_ref must be positive");
+  if (!(v.sigma_min > 0.0)) return fail(IEM_E_ARG, "iem_qf_create: sigma_min must be positive");
+  if (v.sigma_max < 0.0) return fail(IEM_E_ARG, "iem_qf_create: sigma_max must be positive (or 0: the iem_amu object's)");
+  if (!(v.section_sigma_tol > 0.0)) return fail(IEM_E_ARG, "iem_qf_create: section_sigma_tol must be positive");
+  if (v.max_section_steps < 1 || v.max_section_steps > 16) return fail(IEM_E_ARG, "iem_qf_create: max_section_steps must lie in 1..16");
+  if (v.sigma_max == 0.0) v.sigma_max = amu_sigma_max;
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_qf_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kQfSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_qf_destroy(iem_qf *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->a->p->b->m->device);
+  for (void *v : {(void *)q->d_blk, (void *)q->d_red, (void *)q->d_tab})
+    if (v) hipFree(v);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_qf_create(iem_amu *a, const iem_qf_opts_t *opts, iem_qf **out) {
+  if (!a || !out) return fail(IEM_E_ARG, "null argument");
+  iem_qf_opts_t opt;
+  {
+    int rc = qf_opts(opts, a->opt.sigma_max, &opt);
+    if (rc) return rc;
+  }
+  const iem_barrier *b = a->p->b;
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = qf_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_qf *q) const { iem_qf_destroy(q); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_qf, Drop> q(new iem_qf);
+  q->a = a;
+  q->opt = opt;
+  const int64_t n_red = 2 * b->n_wg + 1 + (b->n_wg + 31) / 32;      // (IEM_TICKET_WORDS of csrc/iem_device.h)
+  HIP_TRY(hipMalloc((void **)&q->d_blk, 32 * 8));
+  HIP_TRY(hipMalloc((void **)&q->d_red, (size_t)n_red * 8));
+  HIP_TRY(hipMalloc((void **)&q->d_tab, 6 * 8));
+  long long tab[6];
+  for (int s = 0; s < 2; ++s) { tab[s] = s * (long long)b->n_wg; tab[2 + s] = 0; tab[4 + s] = (long long)b->n_wg; }
+  HIP_TRY(hipMemset(q->d_blk, 0, 32 * 8));      // status IDLE: alpha and value do nothing before the first begin
+  HIP_TRY(hipMemset(q->d_red, 0, (size_t)n_red * 8));
+  HIP_TRY(hipMemcpy(q->d_tab, tab, sizeof tab, hipMemcpyHostToDevice));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_qf_reset(iem_qf *q) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->a->p->b->m;
+  DevGuard dg_(m->device);
+  QfArgsH A = qf_args(q);
+  return kkt_launch_raw(m, m->qf.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_qf_begin(iem_qf *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_r, const double *d_c, const double *d_out12) {
+  if (!q || !d_out12) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->a->p->b;
+  if ((b->nvar && (!d_x || !d_zL || !d_zU || !d_r)) || (b->ncon && (!d_y || !d_c)) || (b->n_ineq && (!d_s || !d_vL || !d_vU))) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  QfArgsH A = qf_args(q);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  A.r = d_r; A.c = d_c; A.w = d_out12;
+  return kkt_launch_raw(m, m->qf.begin, &A, sizeof A, b->n_wg, 256);      // no seed: the last arrival writes the whole block
+}
+
+namespace {
+// the arguments iem_qf_alpha and iem_qf_value share
+int qf_pair(iem_qf *q, bool value, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+            const double *const *d0, const double *const *d1) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->a->p->b;
+  if ((b->nvar && (!d_x || !d_zL || !d_zU || !d0[0] || !d1[0] || !d0[2] || !d0[3] || !d1[2] || !d1[3])) ||
+      (b->n_ineq && (!d_s || !d_vL || !d_vU || !d0[1] || !d1[1] || !d0[4] || !d0[5] || !d1[4] || !d1[5])))
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  QfArgsH A = qf_args(q);
+  A.x = d_x; A.s = d_s; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  A.sol0 = d0[0]; A.ds0 = d0[1]; A.dzL0 = d0[2]; A.dzU0 = d0[3]; A.dvL0 = d0[4]; A.dvU0 = d0[5];
+  A.sol1 = d1[0]; A.ds1 = d1[1]; A.dzL1 = d1[2]; A.dzU1 = d1[3]; A.dvL1 = d1[4]; A.dvU1 = d1[5];
+  return kkt_launch_raw(m, value ? m->qf.value : m->qf.alpha, &A, sizeof A, b->n_wg, 256);
+}
+}  // namespace
+
+int iem_qf_alpha(iem_qf *q, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_sol0, const double *d_ds0, const double *d_dzL0, const double *d_dzU0, const double *d_dvL0, const double *d_dvU0,
+                 const double *d_sol1, const double *d_ds1, const double *d_dzL1, const double *d_dzU1, const double *d_dvL1, const double *d_dvU1) {
+  const double *d0[6] = {d_sol0, d_ds0, d_dzL0, d_dzU0, d_dvL0, d_dvU0}, *d1[6] = {d_sol1, d_ds1, d_dzL1, d_dzU1, d_dvL1, d_dvU1};
+  return qf_pair(q, false, d_x, d_s, d_zL, d_zU, d_vL, d_vU, d0, d1);
+}
+
+int iem_qf_value(iem_qf *q, const double *d_x, const double *d_s, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                 const double *d_sol0, const double *d_ds0, const double *d_dzL0, const double *d_dzU0, const double *d_dvL0, const double *d_dvU0,
+                 const double *d_sol1, const double *d_ds1, const double *d_dzL1, const double *d_dzU1, const double *d_dvL1, const double *d_dvU1) {
+  const double *d0[6] = {d_sol0, d_ds0, d_dzL0, d_dzU0, d_dvL0, d_dvU0}, *d1[6] = {d_sol1, d_ds1, d_dzL1, d_dzU1, d_dvL1, d_dvU1};
+  return qf_pair(q, true, d_x, d_s, d_zL, d_zU, d_vL, d_vU, d0, d1);
+}
+
+int iem_qf_update(iem_qf *q, const double *d_out12, int force_fixed, iem_search *fs) {
+  if (!q || !d_out12) return fail(IEM_E_ARG, "null argument");
+  if (fs && fs->b != q->a->p->b) return fail(IEM_E_ARG, "iem_qf_update: the search belongs to another barrier object");
+  iem_model *m = q->a->p->b->m;
+  DevGuard dg_(m->device);
+  QfArgsH A = qf_args(q);
+  A.w = d_out12;
+  A.force_fixed = force_fixed ? 1 : 0;
+  A.sctl = fs ? fs->d_ctl : nullptr;
+  return kkt_launch_raw(m, m->qf.update, &A, sizeof A, 1, 64);
+}
+
+int iem_qf_device(const iem_qf *q, double **d_block) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = q->d_blk;
+  return IEM_OK;
+}
+
+int iem_qf_state(iem_qf *q, iem_mu_state_t *mu_out, iem_amu_state_t *amu_out, iem_qf_state_t *out) {
+  if (!q || !mu_out || !amu_out || !out) return fail(IEM_E_ARG, "null argument");
+  if (mu_out->struct_size < sizeof(uint64_t) || amu_out->struct_size < sizeof(uint64_t) || out->struct_size < sizeof(uint64_t))
+    return fail(IEM_E_ARG, "iem_qf_state: set struct_size to sizeof(iem_mu_state_t) / sizeof(iem_amu_state_t) / sizeof(iem_qf_state_t) before the call");
+  iem_model *m = q->a->p->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[64];
+  HIP_TRY(hipMemcpyAsync(w, q->a->p->d_blk, 16 * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(w + 16, q->a->d_blk, 16 * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipMemcpyAsync(w + 32, q->d_blk, 32 * 8, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));      // ONE synchronisation for the three blocks
+  iem_mu_state_t v;
+  v.struct_size = std::min<uint64_t>(mu_out->struct_size, sizeof v);
+  std::memcpy(&v.mu, w, 12 * 8);
+  std::memcpy(mu_out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  iem_amu_state_t u;
+  u.struct_size = std::min<uint64_t>(amu_out->struct_size, sizeof u);
+  std::memcpy(&u.mode, w + 16, 14 * 8);
+  std::memcpy(amu_out, &u, (size_t)u.struct_size);
+  iem_qf_state_t t;
+  static_assert(sizeof t == 28 * 8, "iem_qf_state_t: struct_size, then words 0-26 of the own block");
+  t.struct_size = std::min<uint64_t>(out->struct_size, sizeof t);
+  std::memcpy(&t.status, w + 32, 27 * 8);
+  std::memcpy(out, &t, (size_t)t.struct_size);
   return IEM_OK;
 }
 

@@ -776,6 +776,84 @@ function amu_affine(f, o::AdaptiveBarrierParameter, objs...)
     end
 end
 
+# ---- the quality-function oracle (include/iem.h: iem_qf_*) ---------------------------------------------------------------------------
+# Ipopt's mu_oracle = quality-function (2-norm squared, no centrality or balancing term) ON an AdaptiveBarrierParameter: a golden-section
+# search over sigma whose state machine lives on the device.  Per iteration, in the place of amu_update!: mu_error!; amu_affine(...) do ...
+# end around barrier_terms!(mu = 0) and barrier_terms!(mu = mu_ref), ONE two-column back-solve on the iteration's factors,
+# barrier_step!(mu = 0, tau = 1) -> d0 and barrier_step!(mu = mu_ref, tau = 1) -> d1; qf_begin!; qf_section! (max_section_steps + 4
+# qf_alpha! / qf_value! pairs, no decision in between); qf_update!(qf, out12; search); qf_state — the one read-back, three blocks.
+# d0, d1 = (sol, ds, dzL, dzU, dvL, dvU).  Finalize (or let go of) the oracle before its AdaptiveBarrierParameter.  UNEXECUTED, like the rest.
+struct IemQfOpts           # iem_qf_opts_t
+    struct_size::UInt64
+    mu_ref::Float64; sigma_min::Float64; sigma_max::Float64; section_sigma_tol::Float64
+    max_section_steps::Int64      # 1..16
+end
+struct IemQfState          # iem_qf_state_t: words 0-26 of the object's own block
+    struct_size::UInt64
+    status::Int64; phase::Int64; steps::Int64; evaluations::Int64      # status: 0 idle, 1 section, 2 done, 3 unusable
+    sigma_trial::Float64
+    alpha_slots::NTuple{2, Float64}
+    d2::Float64; p2::Float64; avg::Float64; lo::Float64; hi::Float64
+    a::Float64; b::Float64; c::Float64; d::Float64; qc::Float64; qd::Float64
+    sigma::Float64; q::Float64; q_first::Float64
+    q_last::Float64; c2_last::Float64; nan_last::Float64; alpha_p_last::Float64; alpha_d_last::Float64
+    sigma_first::Float64
+end
+mutable struct QualityFunction
+    q::Ptr{Cvoid}
+    amu::AdaptiveBarrierParameter      # borrowed: kept alive
+    pairs::Int
+end
+function QualityFunction(o::AdaptiveBarrierParameter; mu_ref = 1.0, sigma_min = 1e-6, sigma_max = 0.0, section_sigma_tol = 1e-2, max_section_steps = 8)
+    opts = Ref(IemQfOpts(sizeof(IemQfOpts), mu_ref, sigma_min, sigma_max, section_sigma_tol, max_section_steps))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_qf_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemQfOpts}, Ptr{Ptr{Cvoid}}), o.a, opts, q))
+    qf = QualityFunction(q[], o, max_section_steps + 4)
+    finalizer(x -> (x.q == C_NULL || x.amu.a == C_NULL || ccall((:iem_qf_destroy, LIBIEM), Cint, (Ptr{Cvoid},), x.q); x.q = C_NULL), qf)
+    return qf
+end
+# a new solve: the section idle (asynchronous); amu_reset! and mu_reset! are calls of their own
+qf_reset!(o::QualityFunction) = check(ccall((:iem_qf_reset, LIBIEM), Cint, (Ptr{Cvoid},), o.q))
+# r = sigma grad f + J'y, c = c(x), out12: the twelve of mu_error!
+function qf_begin!(o::QualityFunction, state, r, c, out12)
+    check(ccall((:iem_qf_begin, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 10)...),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]),
+                dptr(r), spptr(c), dptr(out12)))
+end
+_qf_pair(state, d0, d1) = (spptr(state[1]), spptr(state[2]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]),
+                           dptr(d0[1]), spptr(d0[2]), spptr(d0[3]), spptr(d0[4]), spptr(d0[5]), spptr(d0[6]),
+                           dptr(d1[1]), spptr(d1[2]), spptr(d1[3]), spptr(d1[4]), spptr(d1[5]), spptr(d1[6]))
+qf_alpha!(o::QualityFunction, state, d0, d1) =
+    check(ccall((:iem_qf_alpha, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 18)...), o.q, _qf_pair(state, d0, d1)...))
+qf_value!(o::QualityFunction, state, d0, d1) =
+    check(ccall((:iem_qf_value, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 18)...), o.q, _qf_pair(state, d0, d1)...))
+# every pair of a section: the pairs behind the one that finishes it do nothing on the device
+function qf_section!(o::QualityFunction, state, d0, d1; pairs = o.pairs)
+    for _ in 1:pairs
+        qf_alpha!(o, state, d0, d1)
+        qf_value!(o, state, d0, d1)
+    end
+end
+# out12: the twelve of mu_error!; search: a FilterSearch on the same BarrierLayer, or nothing
+function qf_update!(o::QualityFunction, out12; force_fixed = false, search = nothing)
+    check(ccall((:iem_qf_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+                o.q, dptr(out12), force_fixed ? 1 : 0, search === nothing ? C_NULL : search.s))
+end
+# the one read-back (synchronises the stream once): (IemMuState, IemAmuState, IemQfState)
+function qf_state(o::QualityFunction)
+    st = Ref(IemMuState(sizeof(IemMuState), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    mid = Ref(IemAmuState(sizeof(IemAmuState), 0, 0, 0, (0.0, 0.0, 0.0, 0.0), 0, 0, 0, 0, 0, 0, 0))
+    own = Ref(IemQfState(sizeof(IemQfState), 0, 0, 0, 0, 0, (0.0, 0.0), ntuple(_ -> 0.0, 20)...))
+    check(ccall((:iem_qf_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMuState}, Ptr{IemAmuState}, Ptr{IemQfState}), o.q, st, mid, own))
+    return st[], mid[], own[]
+end
+# the own block (32 words of 8 bytes) as a device address
+function qf_device(o::QualityFunction)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_qf_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.q, p))
+    return p[]
+end
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
