@@ -58,6 +58,35 @@ def probe_words(B, st, sol, dirs, alpha):
     return p, float(np.isnan(p).sum()), float(alpha[0]), float(alpha[1])
 
 
+def probe_addends(B, st, sol, dirs, alpha):
+    """the products of amu_probe over [0, nvar + ncon) in the kernel's statement order: ``(pL, pU)`` — lower then upper on a variable
+    and on an inequality row, +0.0 where the bound is absent"""
+    x, s, y, zL, zU, vL, vU = st
+    ds, dzL, dzU, dvL, dvU = dirs
+    ap, ad = F(alpha[0]), F(alpha[1])
+    dx = np.asarray(sol)[:len(x)]
+    with np.errstate(all="ignore"):
+        tx, ts = ap * dx, ap * ds
+        pL = bref.full(B, B["hasL"], ((x - B["xl"]) + tx) * (zL + ad * dzL), B["gL"], ((s - B["rl"]) + ts) * (vL + ad * dvL))
+        pU = bref.full(B, B["hasU"], ((B["xu"] - x) - tx) * (zU + ad * dzU), B["gU"], ((B["ru"] - s) - ts) * (vU + ad * dvU))
+    return pL, pU
+
+
+def probe_sum(B, st, sol, dirs, alpha, n_wg):
+    """word 0 of amu_probe on a grid of `n_wg` workgroups: the device's bits"""
+    return bref.device_sum(list(probe_addends(B, st, sol, dirs, alpha)), n_wg)
+
+
+def directions(P, seed=7):
+    """a random sol = [dx; dy] and, from it, barrier_reference.step at tau = 1: ``(sol, dirs, alpha)`` on the host — NaN on equality rows"""
+    B, st = P["B"], P["state"]
+    n, m = len(st[0]), len(st[1])
+    rng = np.random.default_rng(seed)
+    sol = 0.1 * rng.standard_normal(n + m)
+    dirs, alpha = bref.step(B, st, sol, tuple(np.full(m, np.nan) for _ in range(3)), bref.MU, 1.0)
+    return sol, dirs, alpha
+
+
 def _ring(ab):
     return int(min(max(ints(ab)[NREFS], 0), 4))
 

@@ -3,6 +3,12 @@ barrier_merit, expression for expression (numpy rounds every operation and contr
 kernels) — and the state the tests of the barrier layer share.  TEST INFRASTRUCTURE: tests/test_barrier.py (CPU) and
 tests/test_gpu_barrier.py.
 
+THE SUMS are restated in the device's order (`device_sum`, shared by every restatement built on this one): a lane adds the addends of
+its entries i, i + 256·n_wg, ... one after the other from +0.0, the 64 lanes of a wave meet in the shuffle tree of iem_wave_sum, the
+four waves of a workgroup are added in order, and the last arrival totals the column — lane l takes the workgroups l, l + 64, ...,
+then the same tree.  `error_sums` / `merit_sums` are bitwise the kernels' for the grid they are given, but for sum log gap (numpy's
+log).  `big_point` is the shared state of the shapes at which the stride loop runs more than once (tests/test_device_order.py, CPU).
+
 Vectors are full length: x, zL, zU (nvar); s, vL, vU, ds, dvL, dvU (ncon, entries on equality rows never read or written).  Where
 the kernels branch on a presence flag the restatement computes on every entry and selects with np.where: the selected entries
 carry the same bits, the others (NaN / inf arithmetic on absent bounds) are discarded."""
@@ -176,6 +182,195 @@ def sum_bound(terms):
     numpy's log"""
     terms = np.asarray(terms, dtype=np.float64)
     return math.fsum(terms), (len(terms) + 2) * 2.0 ** -52 * math.fsum(np.abs(terms))
+
+
+def _tree(a):
+    """iem_wave_sum on the last axis (64 lanes): what lane 0 holds"""
+    a = a.copy()
+    for off in (32, 16, 8, 4, 2, 1):
+        a[..., :off] = a[..., :off] + a[..., off:2 * off]
+    return a[..., 0]
+
+
+def device_sum(addends, n_wg):
+    """One column of iem_shared_park / iem_shared_totals over a grid of `n_wg` workgroups of 256: `addends` is a list of arrays over
+    the entries [0, n) — what a lane adds for entry i, in that order (+0.0 where the kernel adds nothing: the accumulators start
+    from +0.0 and never hold −0.0, so the bits are the same).  A lane adds the addends of its entries i, i + 256·n_wg, ... one after
+    the other from +0.0, the 64 lanes of a wave meet in the shuffle tree of iem_wave_sum, the four waves of a workgroup are added in
+    order, and the last arrival totals the column — lane l takes the workgroups l, l + 64, ..., then the same tree."""
+    n_wg = int(n_wg)
+    T = 256 * n_wg
+    n = len(addends[0])
+    acc = np.zeros(T)
+    with np.errstate(all="ignore"):
+        for k in range(0, n, T):
+            for a in addends:
+                seg = a[k:k + T]
+                acc[:len(seg)] = acc[:len(seg)] + seg
+        waves = _tree(acc.reshape(n_wg, 4, 64))
+        parked = ((waves[:, 0] + waves[:, 1]) + waves[:, 2]) + waves[:, 3]
+        pad = np.zeros(-(-n_wg // 64) * 64)
+        pad[:n_wg] = parked
+        lanes = np.zeros(64)
+        for row in pad.reshape(-1, 64):
+            lanes = lanes + row
+        return np.float64(_tree(lanes))
+
+
+def full(B, on_x, vx, on_s, vs):
+    """addends over [0, nvar + ncon): vx where on_x, vs where on_s, +0.0 elsewhere (None: nothing on that side)"""
+    nvar, ncon = len(B["hasL"]), len(B["eq"])
+    with np.errstate(all="ignore"):
+        return np.concatenate([np.zeros(nvar) if on_x is None else np.where(on_x, vx, 0.0), np.zeros(ncon) if on_s is None else np.where(on_s, vs, 0.0)])
+
+
+def grid(n):
+    """kkt_stream_grid of csrc/iem_api.cpp: min(ceil(n / 256), 4096) workgroups"""
+    return min(-(-int(n) // 256), 4096)
+
+
+def trips(nvar, n, n_wg):
+    """``[(variables, rows), ...]``: how many entries of each branch the grid takes on each trip of the stride loop"""
+    T = 256 * int(n_wg)
+    return [(max(0, min(k + T, nvar) - k), min(k + T, n) - max(k, nvar) if k + T > nvar else 0) for k in range(0, int(n), T)]
+
+
+def log_addends(B, x, s):
+    """the column `sum log gap` of barrier_error / barrier_merit: lower then upper on a variable and on an inequality row — numpy's
+    log, which need not carry the last bit of the device's"""
+    with np.errstate(all="ignore"):
+        return [full(B, B["hasL"], np.log(x - B["xl"]), B["gL"], np.log(s - B["rl"])), full(B, B["hasU"], np.log(B["xu"] - x), B["gU"], np.log(B["ru"] - s))]
+
+
+def error_addends(B, st, c):
+    """The four parked columns of barrier_error (out[4..7]) as lists of addends over [0, nvar + ncon) in the kernel's statement order:
+    sum |y| (every row), the present multipliers (zL then zU on a variable, vL then vU on a row), theta (every row), sum log gap."""
+    x, s, y, zL, zU, vL, vU = st
+    every = np.ones(len(y), dtype=bool)
+    with np.errstate(all="ignore"):
+        inf = np.where(B["eq"], c - B["ceq"], c - s)
+        return ([full(B, None, None, every, np.abs(y))], [full(B, B["hasL"], zL, B["gL"], vL), full(B, B["hasU"], zU, B["gU"], vU)],
+                [full(B, None, None, every, np.abs(inf))], log_addends(B, x, s))
+
+
+def error_sums(B, st, c, n_wg):
+    """out[4..7] of barrier_error on a grid of `n_wg` workgroups: the first three carry the device's bits, the fourth is the device's
+    order over numpy's logs"""
+    return np.array([device_sum(col, n_wg) for col in error_addends(B, st, c)])
+
+
+def merit_sums(B, x, s, c, n_wg):
+    """the two of barrier_merit: the columns of out[6], out[7] of barrier_error"""
+    with np.errstate(all="ignore"):
+        inf = np.where(B["eq"], c - B["ceq"], c - s)
+    return np.array([device_sum([full(B, None, None, np.ones(len(c), dtype=bool), np.abs(inf))], n_wg), device_sum(log_addends(B, x, s), n_wg)])
+
+
+HEAVY = (36, 29)      # which candidate lane carries the weight and the seed of its multipliers (chosen so that tests/test_device_order.py passes)
+H57 = 2.0 ** 57
+
+
+def _heavy_lane(P, k, seed):
+    """THE SPREAD of the sizes above 27 000 (that one keeps its recipe).  Over 10⁶ addends of one magnitude a total's last bit is
+    10⁶ times coarser than a lane's, so no order of a lane's additions shows in it: the bits of a total discriminate only where one
+    lane outweighs all the others.  So one lane does — the entries i0, i0 + T, i0 + 2T (T = 4096·256: the same lane on three trips,
+    two variables and a row, each with both bounds; the k-th such lane).  Its six multipliers become 2⁵⁷·(1, 1, 2, 4, 8, 16)·U(1, 2)
+    in the kernel's order: every addition of the lane lands in another binade, so that the roundings depend on the order (under ONE
+    dominating addend the others round on its grid one by one, and their order cannot show).  Returns the three entries; `plant`
+    gives a direction (or any vector over the entries) weights there."""
+    B, st = P["B"], P["state"]
+    n, m = len(st[0]), len(st[2])
+    T = 4096 * 256
+    assert n > T and n + m > 2 * T
+    both_x, both_s = B["hasL"] & B["hasU"], B["gL"] & B["gU"]
+    cand = (i for i in range(1000, n - T) if both_x[i] and both_x[i + T] and both_s[i + 2 * T - n])
+    for _ in range(k + 1):
+        i0 = next(cand)
+    j = i0 + 2 * T - n
+    z = H57 * np.array([1.0, 1.0, 2.0, 4.0, 8.0, 16.0]) * np.random.default_rng(700 + seed).uniform(1.0, 2.0, 6)
+    st[3][i0], st[4][i0], st[3][i0 + T], st[4][i0 + T], st[5][j], st[6][j] = z
+    return (i0, i0 + T, i0 + 2 * T)
+
+
+def plant(P, v, scales, seed=0):
+    """a copy of `v` (over the entries, over the variables or over the rows) with scales[k]·U(1, 2) at the k-th of P's heavy entries;
+    P without them: `v` itself"""
+    if P["heavy"] is None:
+        return v
+    n, m = len(P["state"][0]), len(P["state"][2])
+    rng = np.random.default_rng(900 + seed)
+    v = v.copy()
+    for i, scale in zip(P["heavy"], scales):
+        j = i - n if len(v) == m else i
+        w = scale * rng.uniform(1.0, 2.0)
+        if 0 <= j < len(v):
+            v[j] = w
+    return v
+
+
+def cut(B, iv, ir):
+    """the bounds dictionary over the variables `iv` and the rows `ir` alone (index arrays): what an order-free word — a maximum, a
+    minimum, a step length — takes from those entries is the restatement's value on the cut, at the cost of a few entries"""
+    nvar = len(B["hasL"])
+    C = {k: (v[iv] if len(v) == nvar else v[ir]) for k, v in B.items() if k != "counts"}
+    C["counts"] = dict(nvar=len(iv), ncon=len(ir))
+    return C
+
+
+def cut_state(st, iv, ir):
+    return (st[0][iv], st[1][ir], st[2][ir], st[3][iv], st[4][iv], st[5][ir], st[6][ir])
+
+
+def seam_positions(nvar, n, n_wg):
+    """the entries at which a later trip, or the other branch, begins or ends: either side of the nvar seam, 2²⁰ − 1 and 2²⁰ (the last
+    entry of the first trip of 4096 workgroups and the first of the second), the first entry of the third trip where there is one,
+    and n − 1"""
+    T = 256 * int(n_wg)
+    pos = {"left of the seam": nvar - 1, "right of the seam": nvar, "2^20 - 1": 2 ** 20 - 1, "2^20": 2 ** 20, "n - 1": n - 1}
+    if n > 2 * T:
+        pos["first of trip three"] = 2 * T
+    assert T == 2 ** 20 and all(0 <= i < n for i in pos.values())
+    return pos
+
+
+def nearest(mask, i):
+    """the entry nearest to i at which `mask` (over the entries) holds"""
+    idx = np.flatnonzero(mask)
+    return int(idx[np.argmin(np.abs(idx - i))])
+
+
+_big = {}
+
+
+def big_point(supports=27_000):
+    """quadrotor(supports) with bounds and a state of the tests' own, built once per size and left unchanged: variables free / lower /
+    upper / both, rows equality / lower / upper / both in equal shares; gaps 10^U(−2, 1), multipliers 10^U(−2, 2), NaN where a bound is
+    absent and on equality rows of the slack side; r and c random.  27 000: nvar + ncon = 1 080 000 > 2²⁰ entries, the later trip of
+    the stride loop is rows only; 60 000: nvar = 1 320 000 > 2²⁰, three trips, the second crosses the nvar seam."""
+    supports = int(supports)
+    if supports in _big:
+        return _big[supports]
+    from infiniteexamodels.jl_amd import transcribe, workloads
+    core = transcribe.exa_core(workloads.quadrotor(supports))
+    n, m = int(core.nvar), int(core.ncon)
+    assert n + m > 2 ** 20
+    rng = np.random.default_rng(supports // 10)
+    gap = lambda k: 10.0 ** rng.uniform(-2.0, 1.0, k)
+    x, kx = rng.standard_normal(n), rng.integers(0, 4, n)
+    lvar, uvar = np.where(kx & 1, x - gap(n), -np.inf), np.where(kx & 2, x + gap(n), np.inf)
+    s0, kc = rng.standard_normal(m), rng.integers(0, 4, m)
+    eq = kc == 0
+    lcon, ucon = np.where(eq, s0, np.where(kc & 1, s0 - gap(m), -np.inf)), np.where(eq, s0, np.where(kc & 2, s0 + gap(m), np.inf))
+    B = relaxed_bounds(lvar, uvar, lcon, ucon, RELAX)
+    mult = lambda on: np.where(on, 10.0 ** rng.uniform(-2.0, 2.0, len(on)), NAN)
+    state = (x, np.where(eq, NAN, s0), rng.standard_normal(m), mult(B["hasL"]), mult(B["hasU"]), mult(B["gL"]), mult(B["gU"]))
+    P = dict(core=core, blob=None, B=B, lvar=lvar, uvar=uvar, lcon=lcon, ucon=ucon, state=state, r=rng.standard_normal(n), c=s0 + 0.1 * rng.standard_normal(m), mu=MU,
+             tau=TAU, relax=RELAX, heavy=None)
+    assert B["counts"]["nz"] > 10 ** 5 and B["counts"]["n_eq"] > 10 ** 4
+    if supports != 27_000:
+        P["heavy"] = _heavy_lane(P, *HEAVY)
+    _big[supports] = P
+    return P
 
 
 _points = {}

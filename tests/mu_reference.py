@@ -64,6 +64,24 @@ def error_words(B, st, r, c):
     return head, (ay, mult, theta, logs), w8, float((~ok).sum()), p
 
 
+def product_addends(B, st):
+    """the products over [0, nvar + ncon) in mu_error's statement order: ``(pL, pU)`` — lower then upper on a variable and on an
+    inequality row, +0.0 where the bound is absent — and the masks of the present bounds laid out the same way"""
+    x, s, y, zL, zU, vL, vU = st
+    with np.errstate(all="ignore"):
+        pL = bref.full(B, B["hasL"], (x - B["xl"]) * zL, B["gL"], (s - B["rl"]) * vL)
+        pU = bref.full(B, B["hasU"], (B["xu"] - x) * zU, B["gU"], (B["ru"] - s) * vU)
+    return (pL, pU), (np.concatenate([B["hasL"], B["gL"]]), np.concatenate([B["hasU"], B["gU"]]))
+
+
+def product_sums(B, st, n_wg):
+    """``(word 9, word 10)`` of mu_error on a grid of `n_wg` workgroups, in the device's order: the sum of the products and the count
+    of those that do not enter the minimum"""
+    (pL, pU), (onL, onU) = product_addends(B, st)
+    bad = [np.where(on, ~enters(np.ascontiguousarray(p)), False).astype(np.float64) for p, on in ((pL, onL), (pU, onU))]
+    return bref.device_sum([pL, pU], n_wg), bref.device_sum(bad, n_wg)
+
+
 def terms(w, counts, opts):
     """``(e_d, e_p, sc)`` of mu_update from the twelve words"""
     m, nz = int(counts[0]), int(counts[1])

@@ -42,41 +42,7 @@ def fresh_block():
     return np.zeros(WORDS)
 
 
-def _tree(a):
-    """iem_wave_sum on the last axis (64 lanes): what lane 0 holds"""
-    a = a.copy()
-    for off in (32, 16, 8, 4, 2, 1):
-        a[..., :off] = a[..., :off] + a[..., off:2 * off]
-    return a[..., 0]
-
-
-def device_sum(addends, n_wg):
-    """One column of iem_shared_park / iem_shared_totals over a grid of `n_wg` workgroups of 256: `addends` is a list of arrays over
-    the entries [0, n) — what a lane adds for entry i, in that order (+0.0 where the kernel adds nothing: the accumulators start
-    from +0.0 and never hold −0.0, so the bits are the same)."""
-    n_wg = int(n_wg)
-    T = 256 * n_wg
-    n = len(addends[0])
-    acc = np.zeros(T)
-    with np.errstate(all="ignore"):
-        for k in range(0, n, T):
-            for a in addends:
-                seg = a[k:k + T]
-                acc[:len(seg)] = acc[:len(seg)] + seg
-        waves = _tree(acc.reshape(n_wg, 4, 64))
-        parked = ((waves[:, 0] + waves[:, 1]) + waves[:, 2]) + waves[:, 3]
-        pad = np.zeros(-(-n_wg // 64) * 64)
-        pad[:n_wg] = parked
-        lanes = np.zeros(64)
-        for row in pad.reshape(-1, 64):
-            lanes = lanes + row
-        return F(_tree(lanes))
-
-
-def _full(B, on_x, vx, on_s, vs):
-    """addends over [0, nvar + ncon): vx where on_x, vs where on_s, +0.0 elsewhere"""
-    with np.errstate(all="ignore"):
-        return np.concatenate([np.where(on_x, vx, 0.0), np.where(on_s, vs, 0.0)])
+device_sum, _tree, _full = bref.device_sum, bref._tree, bref.full      # (the sums in the device's order live with the barrier layer's restatement)
 
 
 def begin(B, st, r, c, w, ab, aopts, qopts, n_wg):

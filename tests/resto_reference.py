@@ -190,6 +190,61 @@ def slope_terms(B, R, st, sol, ds, mu, zeta, opts=OPTS):
         return np.concatenate([q["gx"] * sol[:len(st[0])], (q["gsr"] * ds)[~B["eq"]], (rho - mu / R["p"]) * R["dp"] + (rho - mu / R["n"]) * R["dn"]])
 
 
+def merit_addends(B, R, which, x, s, c):
+    """The four parked columns of resto_merit over [0, nvar + ncon) in the kernel's statement order: S0 (p + n, every row), S1 (the
+    proximity term of a variable and of an inequality row), theta_R (every row), L (log gap lower then upper, then log p, log n on
+    every row — numpy's logs)."""
+    p, n = (R["pt"], R["nt"]) if which else (R["p"], R["n"])
+    ine = ~B["eq"]
+    every, allx = np.ones(len(c), dtype=bool), np.ones(len(x), dtype=bool)
+    with np.errstate(all="ignore"):
+        dxr, dsr = x - R["xR"], s - R["sR"]
+        rc = (infeasibility(B, c, s) - p) + n
+        logs = bref.log_addends(B, x, s) + [bref.full(B, None, None, every, np.log(p)), bref.full(B, None, None, every, np.log(n))]
+        return ([bref.full(B, None, None, every, p + n)], [bref.full(B, allx, R["wx"] * (dxr * dxr), ine, R["ws"] * (dsr * dsr))],
+                [bref.full(B, None, None, every, np.abs(rc))], logs)
+
+
+def merit_device(B, R, which, x, s, c, zeta, n_wg, opts=OPTS):
+    """resto_merit on a grid of `n_wg` workgroups: out[0] and out[1] carry the device's bits, out[2] is the device's order over
+    numpy's logs"""
+    return merit_out(*(bref.device_sum(col, n_wg) for col in merit_addends(B, R, which, x, s, c)), zeta, opts)
+
+
+def slope_addends(B, R, st, sol, ds, mu, zeta, opts=OPTS):
+    """the one parked column of resto_begin: gx·dx on a variable; on a row gsr·ds (inequality rows only), then
+    (rho − mu/p)·dp + (rho − mu/n)·dn"""
+    q = _side(B, R, st, mu, zeta, opts)
+    rho = opts["rho"]
+    nvar = len(st[0])
+    every = np.ones(len(st[2]), dtype=bool)
+    with np.errstate(all="ignore"):
+        return [bref.full(B, np.ones(nvar, dtype=bool), q["gx"] * sol[:nvar], ~B["eq"], q["gsr"] * ds),
+                bref.full(B, None, None, every, (rho - mu / R["p"]) * R["dp"] + (rho - mu / R["n"]) * R["dn"])]
+
+
+def slope(B, R, st, sol, ds, mu, zeta, n_wg, opts=OPTS):
+    """the slope resto_begin sums on a grid of `n_wg` workgroups: the device's bits"""
+    return bref.device_sum(slope_addends(B, R, st, sol, ds, mu, zeta, opts), n_wg)
+
+
+def error_addends(B, R, st, c):
+    """The four parked columns of resto_error (out[4..7]): sum |y|, the multipliers (lower then upper, then zp, zn on every row),
+    theta_R and L as resto_merit(0) adds them."""
+    x, s, y, zL, zU, vL, vU = st
+    every = np.ones(len(y), dtype=bool)
+    _, _, theta, logs = merit_addends(B, R, 0, x, s, c)
+    with np.errstate(all="ignore"):
+        return ([bref.full(B, None, None, every, np.abs(y))],
+                [bref.full(B, B["hasL"], zL, B["gL"], vL), bref.full(B, B["hasU"], zU, B["gU"], vU), bref.full(B, None, None, every, R["zp"]),
+                 bref.full(B, None, None, every, R["zn"])], theta, logs)
+
+
+def error_sums(B, R, st, c, n_wg):
+    """out[4..7] of resto_error on a grid of `n_wg` workgroups (the last: the device's order over numpy's logs)"""
+    return np.array([bref.device_sum(col, n_wg) for col in error_addends(B, R, st, c)])
+
+
 def begin(ctl, slope, merit0, alpha, mu):
     """the INNER block resto_begin's last workgroup leaves, given the slope it summed: search_reference.begin word for word"""
     return sref.begin(ctl, slope, float(merit0[0]), np.array([0, 0, 0, 0, 0, 0, float(merit0[1]), float(merit0[2])]), alpha, mu, 1.0)
@@ -382,6 +437,37 @@ def entered(P, mu=None, seed=0, opts=OPTS):
     R["sR"] = np.where(B["eq"], R["sR"], R["sR"] + 0.05 * rng.standard_normal(m))
     st = (st[0], st[1], P["state"][2].copy()) + st[3:]
     return R, st, mu
+
+
+_big = {}
+# barrier_reference.plant on the heavy lane of the sizes above 27 000 — weights and seeds (chosen so that tests/test_device_order.py
+# passes): the direction (the slope), xR and sR (S1)
+SPREAD_SOL, SPREAD_REF = (2.0 ** 30, 2.0 ** 31, 2.0 ** 50), (2.0 ** 10, 2.0 ** 10.5, 2.0 ** 11)
+SEED_SOL, SEED_REF = 15, 0
+
+
+def big_entered(supports):
+    """`entered` at barrier_reference.big_point(supports) and one resto_step from a random sol, built once per size and left
+    unchanged: dict(P, R (before the step), R_step (dp, dn, dzp, dzn filled), state, mu, zeta, sol, dirs, alpha).  On the heavy lane
+    of the sizes above 27 000: the two variables get their heavy multipliers back (resto_enter clipped them to rho: the row keeps its
+    clipped ones, a heavy row would leave no ds), and the direction and the reference point carry barrier_reference.plant's weights — so
+    that the sum of the multipliers, the slope and S1 discriminate."""
+    supports = int(supports)
+    if supports not in _big:
+        P = bref.big_point(supports)
+        R, st, mu = entered(P)
+        zeta = math.sqrt(mu)
+        n, m = len(st[0]), len(st[2])
+        sol = np.random.default_rng(4000 + supports // 10).standard_normal(n + m)
+        if P["heavy"] is not None:
+            iv = list(P["heavy"][:2])
+            st = tuple(a.copy() for a in st)
+            st[3][iv], st[4][iv] = P["state"][3][iv], P["state"][4][iv]
+            R["xR"], R["sR"] = bref.plant(P, R["xR"], SPREAD_REF, SEED_REF), bref.plant(P, R["sR"], SPREAD_REF, SEED_REF)
+            sol = bref.plant(P, sol, SPREAD_SOL, SEED_SOL)
+        dirs, alpha, R_step = step(P["B"], R, st, sol, tuple(np.full(m, NAN) for _ in range(3)), mu, bref.TAU, zeta)
+        _big[supports] = dict(P=P, R=R, R_step=R_step, state=st, mu=mu, zeta=zeta, sol=sol, dirs=dirs, alpha=alpha)
+    return _big[supports]
 
 
 # ---- the hand-built cases of the return test and of the filter append -----------------------------------------------------------------

@@ -8,11 +8,14 @@ import math
 
 import numpy as np
 
+import barrier_reference as bref
+
 SEARCHING, F_TYPE, H_TYPE, FAILED, UNUSABLE = 0, 1, 2, 3, 4
 ALPHA, ALPHA_MAX, PHI0, THETA0, SLOPE, THETA_MIN, THETA_MAX, PHI_T, THETA_T, STATUS, TRIALS, COUNT, FLAGS = range(13)
 OPTS = dict(gamma_theta=1e-5, gamma_phi=1e-8, eta_phi=1e-8, delta=1.0, s_theta=1.1, s_phi=2.3, alpha_floor=1e-16, max_trials=30, filter_capacity=64)
 ARMIJO_SLACK = 10.0 * 2.0 ** -52
 NAN = float("nan")
+SPREAD, SPREAD_SEED = (2.0 ** 20, 2.0 ** 21, 2.0 ** 22), 6      # barrier_reference.plant's weights on the heavy lane of a big shape's direction: the slope discriminates
 
 
 def word(ctl, w):
@@ -47,6 +50,37 @@ def slope_terms(B, x, s, g, sol, ds, mu, sigma=1.0):
         nl, nu = np.where(B["gL"], mu / (s - B["rl"]), 0.0), np.where(B["gU"], mu / (B["ru"] - s), 0.0)
         ts = ((nu - nl) * ds)[ine]
     return np.concatenate([tx, ts])
+
+
+def slope_addends(B, x, s, g, sol, ds, mu, sigma=1.0):
+    """the one parked column of search_begin over [0, nvar + ncon): (sigma·g_i + gb_i)·dx_i on a variable, gs_j·ds_j on an inequality
+    row, nothing (+0.0) on an equality row — one addend per entry"""
+    nvar = len(x)
+    with np.errstate(all="ignore"):
+        ml, mu_u = np.where(B["hasL"], mu / (x - B["xl"]), 0.0), np.where(B["hasU"], mu / (B["xu"] - x), 0.0)
+        nl, nu = np.where(B["gL"], mu / (s - B["rl"]), 0.0), np.where(B["gU"], mu / (B["ru"] - s), 0.0)
+        return [bref.full(B, np.ones(nvar, dtype=bool), (sigma * g + (mu_u - ml)) * sol[:nvar], ~B["eq"], (nu - nl) * ds)]
+
+
+def slope(B, x, s, g, sol, ds, mu, sigma, n_wg):
+    """the slope search_begin sums on a grid of `n_wg` workgroups: the device's bits (barrier_reference.device_sum)"""
+    return bref.device_sum(slope_addends(B, x, s, g, sol, ds, mu, sigma), n_wg)
+
+
+_big = {}
+
+
+def big_inputs(supports):
+    """host side of a search at barrier_reference.big_point(supports), built once per size: ``(g, sol, ds, f, alpha)`` — random, NaN
+    in ds on equality rows (never read), and barrier_reference.plant's weights on the heavy lane of the direction"""
+    if supports not in _big:
+        P = bref.big_point(supports)
+        B = P["B"]
+        n, m = len(P["state"][0]), len(P["state"][2])
+        rng = np.random.default_rng(77)
+        g, sol, ds = rng.standard_normal(n), rng.standard_normal(n + m), np.where(B["eq"], NAN, rng.standard_normal(m))
+        _big[supports] = (g, bref.plant(P, sol, SPREAD, SPREAD_SEED), bref.plant(P, ds, SPREAD, SPREAD_SEED), 1.25, np.array([0.75, 0.5]))
+    return _big[supports]
 
 
 def begin(ctl, slope, obj, err, alpha, mu, sigma=1.0):

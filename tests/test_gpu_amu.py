@@ -1,16 +1,19 @@
 """The adaptive barrier parameter object (iem_amu_*, csrc/iem_amu_device.h) on the MI355X.
 
 BITWISE against tests/amu_reference.py: words 1–3 of iem_amu_probe and both blocks (and a search's control block) after
-iem_amu_update on every entry of `branch_cases`, for both oracles.  Word 0 of the probe lies within barrier_reference.sum_bound of
-math.fsum of the restatement's terms, repeats bit for bit, and with zero directions and alpha = (1, 1) carries the bits of word 9 of
+iem_amu_update on every entry of `branch_cases`, for both oracles.  Word 0 of the probe carries the bits of
+amu_reference.probe_sum — the restatement in the DEVICE'S ORDER (barrier_reference.device_sum) on the object's own grid of
+info["workgroups"] workgroups — repeats bit for bit, and with zero directions and alpha = (1, 1) carries the bits of word 9 of
 iem_mu_error on the same state: the summation order is the existing kernel's.  One iteration — the affine solve, the probe and the
 adaptive update included — captured once replays at two states; tests/amu_loop.py converges with the rule on the device and with
 the restatement on the host through bitwise the same iterates.
 
 Shapes: those of tests/test_gpu_mu.py, whose helpers this file shares — opf_7 (two workgroups), quadrotor_100 (several workgroups:
-the last-arrival path; nz = 0), `maratos` (every row an equality) and quadrotor(27 000) with random bounds and state (nvar + ncon >
-2²⁰: the grid-stride loop runs)."""
+the last-arrival path; nz = 0), `maratos` (every row an equality) and the two big shapes of barrier_reference.big_point on 4096
+workgroups: quadrotor(27 000) (nvar + ncon > 2²⁰: the grid-stride loop runs a second trip, rows only) and quadrotor(60 000) (nvar >
+2²⁰: three trips, the second across the nvar seam — asserted and printed)."""
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
@@ -38,14 +41,7 @@ def probe(S, amu, sol, dirs, alpha, st=None):
     return h[:4]
 
 
-def directions(P, seed=7):
-    """a random sol = [dx; dy] and, from it, barrier_reference.step at tau = 1: ``(sol, dirs, alpha)`` on the host — NaN on equality rows"""
-    B, st = P["B"], P["state"]
-    n, m = len(st[0]), len(st[1])
-    rng = np.random.default_rng(seed)
-    sol = 0.1 * rng.standard_normal(n + m)
-    dirs, alpha = bref.step(B, st, sol, tuple(np.full(m, NAN) for _ in range(3)), bref.MU, 1.0)
-    return sol, dirs, alpha
+directions = aref.directions
 
 
 @pytest.mark.parametrize("name", tm.SHAPES)
@@ -58,11 +54,15 @@ def test_probe_words(name, built):
         sol, dirs, alpha = T(sol_h), tuple(T(d) for d in dirs_h), T(alpha_h)
         q = probe(S, amu, sol, dirs, alpha)
         p, nan, ap, ad = aref.probe_words(B, st_h, sol_h, dirs_h, alpha_h)
-        fs, bound = bref.sum_bound(p)
-        print(name, "workgroups", S.bar.info["workgroups"], "nz", S.counts[1], "alpha", alpha_h.tolist(), "q0", q[0], "fsum", fs, "bound", bound, "q1", q[1])
+        n_wg = S.bar.info["workgroups"]
+        assert n_wg == min(-(-S.n // 256), 4096)
+        if name in tm.BIG:
+            tm.big_facts(name, S)
+        q0 = aref.probe_sum(B, st_h, sol_h, dirs_h, alpha_h, n_wg)
+        print(name, "workgroups", n_wg, "nz", S.counts[1], "alpha", alpha_h.tolist(), "q0", repr(q[0]), "device order", repr(float(q0)), "fsum", math.fsum(p), "q1", q[1])
         assert len(p) == S.counts[1] and nan == 0.0
         assert same_bits(q[1:], [nan, ap, ad]), q
-        assert abs(q[0] - fs) <= bound
+        assert same_bits(q[0], q0), (q[0], q0)
         assert same_bits(probe(S, amu, sol, dirs, alpha), q)      # the same bits again: the sum has one order
         # zero directions, alpha = (1, 1): the sum of the complementarity products, in the order of iem_mu_error's word 9
         zero = tuple(T(np.zeros(len(d))) for d in dirs_h)

@@ -2,12 +2,24 @@
 
 BITWISE against tests/barrier_reference.py (the numpy restatement, no tolerance): sigma, dcon, rhs, the five directions, the updated
 state, the step lengths, the four maxima of the error block, the start projection — outputs into NaN-poisoned buffers with NaN
-padding behind every vector, equality-row entries of the slack-side vectors still NaN afterwards.  The four sums: identical bits over
-ten calls, merit's two the bits of error's [6], [7], and against math.fsum of the restated terms within (N + 2)·2⁻⁵²·Σ|term|.
+padding behind every vector, equality-row entries of the slack-side vectors still NaN afterwards — and the parked sums: sum |y|, the
+sum of the multipliers and theta carry the bits of barrier_reference.error_sums, the restatement in the DEVICE'S ORDER
+(barrier_reference.device_sum) on the object's own grid of info["workgroups"] workgroups, identical over ten calls, merit's two the
+bits of error's [6], [7].  ONE EXCEPTION: sum log gap.  The device's log and numpy's need not agree in the last bit, so that column
+is formed in the device's order from numpy's logs and compared within (N + 2)·2⁻⁵²·Σ|term| (barrier_reference.sum_bound), as against
+math.fsum before; merit's copy still carries the bits of error's.
 
 Models: opf_7 (every bound kind, fixed variables), farmer_5 (no equality rows, lower-only inequality rows), pandemic_20x3,
 quadrotor_100 (no bounds at all) and pandemic_100x7: 12 000 entries = 47 workgroups of 256, more than one ticket group of 32, so the
 sums cross a seam of iem_last_arrival (the grid is min(ceil(n / 256), 4096): no cap is in the way; the test prints it).
+
+THE BIG SHAPES (barrier_reference.big_point): quadrotor(27 000) — 1 080 000 entries on 4096 workgroups, two trips of the stride
+loop, the second rows only — and quadrotor(60 000) — 2 400 000 entries, nvar = 1 320 000 > 2²⁰, three trips, the second across the
+nvar seam, the third rows (asserted and printed, with the entries per trip and branch).  At both: start, terms, step, update, error
+and merit bit for bit as above; and every extreme slot (the two step lengths, the four maxima) with its deciding value planted at
+either side of the nvar seam, at 2²⁰ − 1, 2²⁰, the first entry of trip three and n − 1 in turn — an extreme is order-free, so only a
+deciding value ON a later trip shows a kernel that drops one; there too a NaN direction and a point exactly on its relaxed bound
+(alpha_p = +0.0, update moves nothing).
 
 THE TINY DIRECTION.  "The same direction ·1e-9 gives alpha = (1, 1) exactly" cannot hold at the shared state: ds = (dy − rs)/sigs and
 dz = (mu/gap − z) − (z/gap)·d have parts that do not scale with the direction (the reference gives, for d·1e-9 at the shared state,
@@ -29,6 +41,7 @@ from barrier_reference import KAPPA, MU, TAU
 
 pytestmark = pytest.mark.gpu
 MODELS = ["opf_7", "farmer_5", "pandemic_20x3", "quadrotor_100", "pandemic_100x7"]
+BIG = {"quadrotor_27000": 27_000, "quadrotor_60000": 60_000}
 PAD = 5
 DW, DC = 1e-2, 1e-6      # delta_w = 1e-2 gives the inertia (nvar, ncon, 0) on both models of the solver tests (eigenvalues, checked on the host)
 NAN = float("nan")
@@ -61,28 +74,48 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.int64), b.view(np.int64))
 
 
+def point(name, seed=0):
+    return bref.big_point(BIG[name]) if name in BIG else bref.barrier_point(name, seed)
+
+
 @contextlib.contextmanager
 def layer(name, seed=0):
-    """the model handle, the raw barrier object and the shared point"""
+    """the model handle, the raw barrier object and the shared point (a big shape: on the point's own bounds)"""
     from infiniteexamodels.jl_amd import lib as iemlib
     from infiniteexamodels.jl_amd.model import ExaModel
-    P = bref.barrier_point(name, seed)
-    gm = ExaModel(P["core"], device=0, blob=P["blob"])
+    P = point(name, seed)
+    gm = ExaModel(P["core"], device=0, blob=P["blob"]) if P["blob"] is not None else ExaModel(P["core"], device=0)
     b = C.c_void_p()
-    iemlib.check(gm._L.iem_barrier_create(gm._h, None, None, None, None, bref.RELAX, C.byref(b)))
+    bounds = [np.ascontiguousarray(P[k], dtype=np.float64) for k in ("lvar", "uvar", "lcon", "ucon")] if name in BIG else [None] * 4
+    iemlib.check(gm._L.iem_barrier_create(gm._h, *[a.ctypes.data if a is not None else None for a in bounds], bref.RELAX, C.byref(b)))
     try:
         info = iemlib.BarrierInfo()
         info.struct_size = C.sizeof(iemlib.BarrierInfo)
         iemlib.check(gm._L.iem_barrier_info(b, C.byref(info)))
-        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=P["om"].nvar, ncon=P["om"].ncon, n=P["om"].nvar + P["om"].ncon, check=iemlib.check,
+        cn = P["B"]["counts"]
+        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=cn["nvar"], ncon=cn["ncon"], n=cn["nvar"] + cn["ncon"], check=iemlib.check,
                                   info={k: int(getattr(info, k)) for k, _ in iemlib.BarrierInfo._fields_})
         S.sizes = (S.nvar, S.ncon, S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
         S.dsizes = (S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
+        assert S.nvar == int(gm.meta.nvar) and S.ncon == int(gm.meta.ncon)
         gm._sync_stream()
         yield S
     finally:
         iemlib.check(gm._L.iem_barrier_destroy(b))
         gm.close()
+
+
+def big_facts(name, S):
+    """what the big shapes are there for, asserted instead of trusted, and printed: the grid, the trips, the entries per trip and branch"""
+    trips = bref.trips(S.nvar, S.n, S.info["workgroups"])
+    print(f"{name}: n {S.n}, workgroups {S.info['workgroups']}, trips {len(trips)}, (variables, rows) per trip {trips}")
+    assert {k: S.info[k] for k in S.B["counts"]} == S.B["counts"] and S.info["workgroups"] == min(-(-S.n // 256), 4096) == 4096
+    if name == "quadrotor_60000":
+        assert (S.nvar, S.ncon, S.n) == (1_320_000, 1_080_000, 2_400_000) and S.nvar > 2 ** 20
+        assert len(trips) == 3 and trips[0][1] == 0 and trips[1][0] > 0 and trips[1][1] > 0 and trips[2][0] == 0 and trips[2][1] > 0
+    else:
+        assert S.n == 1_080_000 and S.nvar < 2 ** 20 < S.n and len(trips) == 2 and trips[1][0] == 0 and trips[1][1] > 0
+    return trips
 
 
 def terms(S, st, r, c, mu=MU):
@@ -232,10 +265,7 @@ def test_error_block_and_merit(name, built):
         for _ in range(10):
             assert same_bits(host(merit(S, st[0], st[1], c), 2), m)
         assert same_bits(host(error(S, st, r, c), 8), first)      # (merit shares the parked values and the tickets: they are as they were)
-        for k, t in zip((4, 5, 6, 7), sums):
-            want, bound = bref.sum_bound(t)
-            print(name, f"out[{k}] = {first[k]!r}, fsum {want!r}, |difference| {abs(first[k] - want):.3e}, bound {bound:.3e}, terms {len(t)}")
-            assert abs(first[k] - want) <= bound, k
+        check_sums(name, S, first, st_h, P["c"], sums[3])
         none = host(error(S, st, None, c), 8)
         assert math.isnan(none[0]) and same_bits(none[1:], first[1:])
         # a NaN in an input wins its maximum
@@ -243,6 +273,173 @@ def test_error_block_and_merit(name, built):
         assert math.isnan(host(error(S, st, r, dev(bad)), 8)[2])
         if B["counts"]["nz"] == 0:
             assert first[3] == 0.0 and first[5] == 0.0 and first[7] == 0.0 and first[1] == 0.0
+
+
+@pytest.mark.parametrize("name", list(BIG))
+def test_big_shapes_bitwise(name, built):
+    """every kernel of the layer at a shape whose stride loop runs more than once (module docstring), bit for bit"""
+    with layer(name) as S:
+        B, P = S.B, S.P
+        big_facts(name, S)
+        st_h = P["state"]
+        st = tuple(dev(a) for a in st_h)
+        r, c = dev(P["r"]), dev(P["c"])
+        poison = tuple(np.full(S.ncon, NAN) for _ in range(3))
+        for g, w, k, what in zip(terms(S, st, r, c), bref.terms(B, st_h, P["r"], P["c"]), (S.nvar, S.ncon, S.n), ("sigma", "dcon", "rhs")):
+            assert same_bits(host(g, k), w), what
+        sol_h = np.random.default_rng(21).standard_normal(S.n)
+        sol = dev(sol_h)
+        dirs, alpha = step(S, st, sol)
+        want_dirs, want_alpha = bref.step(B, st_h, sol_h, poison)
+        a = host(alpha, 2)
+        print(name, "alpha", a.tolist())
+        for g, w, k, nm in zip(dirs, want_dirs, S.dsizes, ("ds", "dzL", "dzU", "dvL", "dvU")):
+            assert same_bits(host(g, k), w), nm
+        for g in (dirs[0], dirs[3], dirs[4]):
+            assert bool(np.isnan(host(g, S.ncon)[B["eq"]]).all())
+        assert same_bits(a, want_alpha) and 0.0 < a[0] < 1.0 and 0.0 < a[1] < 1.0, (a, want_alpha)
+        # error and merit at the state, before it moves
+        first = host(error(S, st, r, c), 8)
+        head, *sums = bref.error(B, st_h, P["r"], P["c"])
+        assert same_bits(first[:4], head), (first[:4], head)
+        check_sums(name, S, first, st_h, P["c"], sums[3])
+        assert same_bits(host(error(S, st, r, c), 8), first)
+        assert same_bits(host(merit(S, st[0], st[1], c), 2), first[6:8])
+        update(S, st, sol, dirs, alpha)
+        new = bref.update(B, st_h, sol_h, want_dirs, want_alpha)
+        for g, w, nm in zip(state_host(S, st), new, ("x", "s", "y", "zL", "zU", "vL", "vU")):
+            assert same_bits(g, w), nm
+        assert not same_bits(new[0], st_h[0]) and np.isnan(new[1][B["eq"]]).all()
+        # start: points inside, on and far outside the bounds
+        rng = np.random.default_rng(2)
+        x0 = st_h[0] + rng.standard_normal(S.nvar) * 10.0 ** rng.uniform(-3, 3, S.nvar)
+        with np.errstate(invalid="ignore"):
+            x0 = np.where(rng.random(S.nvar) < 0.2, np.where(B["hasL"], B["xl"], x0), x0)
+            x0 = np.where(rng.random(S.nvar) < 0.2, np.where(B["hasU"], B["xu"], x0), x0)
+        c0 = P["c"] + rng.standard_normal(S.ncon) * 10.0 ** rng.uniform(-3, 3, S.ncon)
+        xs, cs = dev(x0), dev(c0)
+        outs = [nan(k) for k in (S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)]
+        S.check(S.L.iem_barrier_start(S.b, _p(xs), _p(cs), *map(_p, outs), bref.PUSH, bref.FRAC))
+        for g, w, k, nm in zip([xs] + outs, bref.start(B, x0, c0, poison), (S.nvar, S.ncon, S.nvar, S.nvar, S.ncon, S.ncon), ("x", "s", "zL", "zU", "vL", "vU")):
+            assert same_bits(host(g, k), w), ("start", nm)
+
+
+def planted(S, what):
+    """``[(label, entry)]``: for every seam position the nearest entry that can carry `what` — "variable", "row", "inequality row",
+    "bound" (an entry with a bound of its own), "lower", "upper" — asserted to be of that kind; a position whose nearest entry is
+    another position's is listed once"""
+    B = S.B
+    no_x, no_s = np.zeros(S.nvar, dtype=bool), np.zeros(S.ncon, dtype=bool)
+    mask = {"variable": np.concatenate([~no_x, no_s]), "row": np.concatenate([no_x, ~no_s]), "inequality row": np.concatenate([no_x, ~B["eq"]]),
+            "bound": np.concatenate([B["hasL"] | B["hasU"], B["gL"] | B["gU"]]), "lower": np.concatenate([B["hasL"], B["gL"]]),
+            "upper": np.concatenate([B["hasU"], B["gU"]])}[what]
+    out, seen = [], set()
+    for label, i in bref.seam_positions(S.nvar, S.n, S.info["workgroups"]).items():
+        k = bref.nearest(mask, i)
+        assert mask[k]
+        if k not in seen:
+            seen.add(k)
+            out.append((f"{label} -> {k}", k))
+    return out
+
+
+def cut_at(S, st_h, i):
+    """the one-entry cut of the bounds and of a host state at entry i, and the entry's place: (B1, st1, "x" or "s", index there)"""
+    iv, ir = (np.array([i]), np.array([], dtype=np.int64)) if i < S.nvar else (np.array([], dtype=np.int64), np.array([i - S.nvar]))
+    return bref.cut(S.B, iv, ir), bref.cut_state(st_h, iv, ir), iv, ir
+
+
+@pytest.mark.parametrize("name", list(BIG))
+def test_big_extremes_on_later_trips(name, built):
+    """the two step lengths and the four maxima with their deciding value planted at each seam position in turn (module docstring):
+    the slot carries the bits numpy gives for the planted entry, which beats the rest of the state"""
+    import torch
+    with layer(name) as S:
+        B, P = S.B, S.P
+        big_facts(name, S)
+        st_h = P["state"]
+        st = tuple(dev(a) for a in st_h)
+        r, c = dev(P["r"]), dev(P["c"])
+        poison = tuple(np.full(S.ncon, NAN) for _ in range(3))
+        sol_h = np.random.default_rng(21).standard_normal(S.n)
+        sol = dev(sol_h)
+        base_alpha = bref.step(B, st_h, sol_h, poison)[1]
+        keep = [t.clone() for t in st]
+
+        def alpha_at(i, value, x_value=None):
+            """barrier_step with sol[i] = value (and the point's entry i = x_value): the device's two step lengths, numpy's on the cut"""
+            B1, st1, iv, ir = cut_at(S, st_h, i)
+            st1 = [a.copy() for a in st1]
+            sol1 = np.array([value])
+            vec = 0 if i < S.nvar else 1
+            j = i if i < S.nvar else i - S.nvar
+            if x_value is not None:
+                st1[vec][0] = x_value
+                st[vec][j] = x_value
+            sol[i] = value
+            dirs, alpha = step(S, st, sol)
+            # on the cut of one row sol = [dy], of one variable sol = [dx]
+            got, one = host(alpha, 2), bref.step(B1, tuple(st1), sol1, tuple(np.full(len(ir), NAN) for _ in range(3)))[1]
+            return got, np.minimum(base_alpha, one), one, dirs, alpha
+
+        def restore(i):
+            sol[i] = float(sol_h[i])
+            for t, k in zip(st, keep):
+                t.copy_(k)
+
+        for slot, what in ((0, "alpha_primal"), (1, "alpha_dual")):
+            for label, i in planted(S, "lower"):
+                value = -1e9 if slot == 0 else 1e9      # towards a lower bound: the primal step; away from it: dz < 0, the dual step
+                got, want, one, _, _ = alpha_at(i, value)
+                print(f"{name} {what} planted at {label}: {got.tolist()}, the entry alone {one.tolist()}, the rest {base_alpha.tolist()}")
+                assert one[slot] < base_alpha[slot] and same_bits(got, want), (what, label, got, want)
+                restore(i)
+        for label, i in planted(S, "lower"):
+            # a NaN direction; a point exactly on its relaxed bound with a direction through it: alpha_p = +0.0, update moves nothing
+            j = i if i < S.nvar else i - S.nvar
+            bound = float((B["xl"] if i < S.nvar else B["rl"])[j])
+            for case, value, x_value in (("NaN direction", NAN, None), ("on its bound", -1.0 if i < S.nvar else -1e9, bound)):
+                got, want, one, dirs, alpha = alpha_at(i, value, x_value)
+                print(f"{name} {case} at {label}: alpha {got.tolist()}")
+                assert same_bits(got[:1], [0.0]) and same_bits(one[:1], [0.0]) and same_bits(got, want), (case, label, got, one)
+                before = [t.clone() for t in st]
+                update(S, st, sol, dirs, alpha)
+                assert all(torch.equal(a.view(torch.int64), b_.view(torch.int64)) for a, b_ in zip(st, before)), (case, label)
+                restore(i)
+        # the four maxima: r (a variable), y (an inequality row), c (a row), a multiplier (an entry with a lower bound)
+        base = bref.error(B, st_h, P["r"], P["c"])[0]
+        assert same_bits(host(error(S, st, r, c), 8)[:4], base)
+        r_h, c_h = P["r"], P["c"]
+        for slot, what, kind in ((0, "r", "variable"), (1, "y", "inequality row"), (2, "c", "row"), (3, "z", "lower")):
+            for label, i in planted(S, kind):
+                B1, st1, iv, ir = cut_at(S, st_h, i)
+                st1 = [a.copy() for a in st1]
+                r1, c1 = r_h[iv].copy(), c_h[ir].copy()
+                j = i if i < S.nvar else i - S.nvar
+                vec, host_vec = {"r": (r, r1), "y": (st[2], st1[2]), "c": (c, c1), "z": (st[3], st1[3]) if i < S.nvar else (st[5], st1[5])}[what]
+                old = float(vec[j])
+                vec[j] = 1e30
+                host_vec[0] = 1e30
+                got = host(error(S, st, r, c), 8)[:4]
+                one = bref.error(B1, tuple(st1), r1 if len(iv) else None, c1)[0]
+                want = np.maximum(base, np.where(np.isnan(one), 0.0, one))      # (a cut without variables has no out[0])
+                print(f"{name} out[{slot}] planted ({what}) at {label}: {got.tolist()}")
+                assert one[slot] > base[slot] and same_bits(got, want), (what, label, got, want)
+                vec[j] = old
+        assert same_bits(host(error(S, st, r, c), 8)[:4], base)
+
+
+def check_sums(name, S, out, st_h, c_h, logs):
+    """out[4..6] are the bits of the restatement in the device's order on the object's own grid; out[7] (the device's log) lies within
+    sum_bound of the same order over numpy's logs, and of math.fsum"""
+    n_wg = S.info["workgroups"]
+    assert n_wg == min(-(-S.n // 256), 4096)
+    want = bref.error_sums(S.B, st_h, c_h, n_wg)
+    print(name, "workgroups", n_wg, "out[4..7]", out[4:8].tolist(), "device order", want.tolist())
+    assert same_bits(out[4:7], want[:3]), (out[4:7], want[:3])
+    fs, bound = bref.sum_bound(logs)
+    print(name, f"out[7] = {out[7]!r}, device order over numpy's logs {want[3]!r}, fsum {fs!r}, bound {bound:.3e}, terms {len(logs)}")
+    assert abs(out[7] - want[3]) <= bound and abs(out[7] - fs) <= bound
 
 
 def _solver(S, mode):

@@ -2,14 +2,17 @@
 
 BITWISE against the device's own iem_barrier_error (words 0–7 of iem_mu_error), against numpy (the extremes, the count) and against
 tests/mu_reference.py (the whole block after iem_mu_update on every branch; a ladder of decreases from mu_init to the floor and 10⁴
-log-uniform mu: the check of the device's sqrt).  The sum of the products lies within barrier_reference.sum_bound of math.fsum and
-repeats bit for bit.  Bound calls given wrong host scalars write the bits of the unbound calls given the block's; one captured
-iteration replays across a change of mu.
+log-uniform mu: the check of the device's sqrt).  Word 9, the sum of the products, carries the bits of mu_reference.product_sums —
+the restatement in the DEVICE'S ORDER (barrier_reference.device_sum) on the object's own grid of info["workgroups"] workgroups; the
+count of word 10 goes through the same column — and repeats bit for bit.  Bound calls given wrong host scalars write the bits of the
+unbound calls given the block's; one captured iteration replays across a change of mu.
 
 Shapes: opf_7 (two workgroups), quadrotor_100 (several workgroups: the last-arrival path; no bound at all), `maratos` (nz = 0, every
-row an equality) and quadrotor(27 000) with random bounds and a random interior state (nvar + ncon = 1 080 000 > 2²⁰ = 4096
-workgroups of 256: the grid-stride loop runs; bounds of every kind on variables and rows, so all twelve words are exercised by many
-workgroups)."""
+row an equality) and the two big shapes of barrier_reference.big_point, random bounds of every kind and a random interior state on
+4096 workgroups of 256: quadrotor(27 000) (nvar + ncon = 1 080 000 > 2²⁰: the grid-stride loop runs a second trip, rows only) and
+quadrotor(60 000) (nvar = 1 320 000 > 2²⁰: three trips, the second across the nvar seam — asserted and printed).  At the big shapes
+every extreme slot of iem_mu_error (the four maxima, the minimum of word 8) is also planted at either side of the nvar seam, at
+2²⁰ − 1, 2²⁰, the first entry of trip three and n − 1 in turn, and the −0.0 multiplier is counted there."""
 import contextlib
 import ctypes as C
 import math
@@ -23,7 +26,8 @@ import mu_reference as mref
 import soc_reference
 
 pytestmark = pytest.mark.gpu
-SHAPES = ["opf_7", "quadrotor_100", "maratos", "quadrotor_27000"]
+BIG = {"quadrotor_27000": 27_000, "quadrotor_60000": 60_000}
+SHAPES = ["opf_7", "quadrotor_100", "maratos"] + list(BIG)
 NAN = float("nan")
 PAD = 5
 WRONG_MU, WRONG_TAU = 123.0, 0.5
@@ -72,37 +76,26 @@ def poke(ptr, a):
     assert hip().hipMemcpy(ptr, a.ctypes.data, a.nbytes, 1) == 0
 
 
-_big = []
-
-
-def big_point():
-    """quadrotor(27 000) with bounds and a state of this test's own, built once: variables free / lower / upper / both, rows equality /
-    lower / upper / both in equal shares; gaps 10^U(−2, 1), multipliers 10^U(−2, 2), NaN where a bound is absent and on equality rows
-    of the slack side; r and c random"""
-    if _big:
-        return _big[0]
-    from infiniteexamodels.jl_amd import transcribe, workloads
-    core = transcribe.exa_core(workloads.quadrotor(27_000))
-    n, m = int(core.nvar), int(core.ncon)
-    assert n + m > 2 ** 20
-    rng = np.random.default_rng(2700)
-    gap = lambda k: 10.0 ** rng.uniform(-2.0, 1.0, k)
-    x, kx = rng.standard_normal(n), rng.integers(0, 4, n)
-    lvar, uvar = np.where(kx & 1, x - gap(n), -np.inf), np.where(kx & 2, x + gap(n), np.inf)
-    s0, kc = rng.standard_normal(m), rng.integers(0, 4, m)
-    eq = kc == 0
-    lcon, ucon = np.where(eq, s0, np.where(kc & 1, s0 - gap(m), -np.inf)), np.where(eq, s0, np.where(kc & 2, s0 + gap(m), np.inf))
-    B = bref.relaxed_bounds(lvar, uvar, lcon, ucon, bref.RELAX)
-    mult = lambda on: np.where(on, 10.0 ** rng.uniform(-2.0, 2.0, len(on)), NAN)
-    state = (x, np.where(eq, NAN, s0), rng.standard_normal(m), mult(B["hasL"]), mult(B["hasU"]), mult(B["gL"]), mult(B["gU"]))
-    P = dict(core=core, blob=None, B=B, lvar=lvar, uvar=uvar, lcon=lcon, ucon=ucon, state=state, r=rng.standard_normal(n), c=s0 + 0.1 * rng.standard_normal(m))
-    assert B["counts"]["nz"] > 10 ** 5 and B["counts"]["n_eq"] > 10 ** 4
-    _big.append(P)
-    return P
+def big_point(supports=27_000):
+    """barrier_reference.big_point: quadrotor(supports) with bounds and a state of the tests' own, built once per size"""
+    return bref.big_point(supports)
 
 
 def point(name):
-    return big_point() if name == "quadrotor_27000" else soc_reference.point(name)
+    return big_point(BIG[name]) if name in BIG else soc_reference.point(name)
+
+
+def big_facts(name, S):
+    """the grid and the trips of a big shape, asserted instead of trusted, and printed"""
+    n_wg = S.bar.info["workgroups"]
+    trips = bref.trips(S.nvar, S.n, n_wg)
+    print(f"{name}: n {S.n}, workgroups {n_wg}, trips {len(trips)}, (variables, rows) per trip {trips}")
+    assert n_wg == min(-(-S.n // 256), 4096) == 4096
+    if name == "quadrotor_60000":
+        assert (S.nvar, S.ncon, S.n) == (1_320_000, 1_080_000, 2_400_000) and S.nvar > 2 ** 20
+        assert len(trips) == 3 and trips[0][1] == 0 and trips[1][0] > 0 and trips[1][1] > 0 and trips[2][0] == 0 and trips[2][1] > 0
+    else:
+        assert S.n == 1_080_000 and S.nvar < 2 ** 20 < S.n and len(trips) == 2 and trips[1][0] == 0 and trips[1][1] > 0
 
 
 @contextlib.contextmanager
@@ -143,10 +136,14 @@ def test_error_words(name, built):
         assert same_bits(w[:8], e8), (w[:8], e8)
         head, _, w8, w10, p = mref.error_words(B, st_h, P["r"], P["c"])
         assert same_bits(w[:4], head)
-        fs, bound = bref.sum_bound(p)
-        print(name, "workgroups", S.bar.info["workgroups"], "nz", S.counts[1], "w8", w[8], "w9", w[9], "fsum", fs, "bound", bound, "w10", w[10])
-        assert same_bits(w[8], w8) and same_bits(w[10], w10) and w10 == 0.0 and same_bits(w[11], 0.0)
-        assert abs(w[9] - fs) <= bound
+        n_wg = S.bar.info["workgroups"]
+        assert n_wg == min(-(-S.n // 256), 4096)
+        if name in BIG:
+            big_facts(name, S)
+        w9, c10 = mref.product_sums(B, st_h, n_wg)
+        print(name, "workgroups", n_wg, "nz", S.counts[1], "w8", w[8], "w9", repr(w[9]), "device order", repr(float(w9)), "fsum", math.fsum(p), "w10", w[10])
+        assert same_bits(w[8], w8) and same_bits(w[10], w10) and w10 == 0.0 and same_bits(w[11], 0.0) and same_bits(c10, w10)
+        assert same_bits(w[9], w9), (w[9], w9)
         assert same_bits(words(S), w)      # the same bits again: the sums have one order
         if S.counts[1] == 0:
             assert w[8] == np.inf and w[3] == 0.0 and same_bits(w[9], 0.0)
@@ -164,7 +161,9 @@ def test_error_words(name, built):
             wb = words(S, st=tuple(st))
             assert b10 == 1.0 and same_bits(wb[10], 1.0) and same_bits(wb[8], b8), (value, wb)
             assert np.isnan(wb[3]) if value != value else same_bits(wb[3], np.abs(bp).max())
-            assert abs(wb[9] - math.fsum(bp)) <= bref.sum_bound(bp)[1] if value == value else np.isnan(wb[9])
+            b9, c10 = mref.product_sums(B, tuple(bad), n_wg)
+            assert same_bits(wb[9], b9) if value == value else np.isnan(wb[9]) and np.isnan(b9)
+            assert same_bits(c10, 1.0)
         # −0.0 is not >= +0.0 on the bit patterns: a zero multiplier under a negative zero
         bad = [a.copy() for a in st_h]
         bad[k][i] = -0.0
@@ -172,6 +171,60 @@ def test_error_words(name, built):
         st[k] = T(bad[k])
         wb = words(S, st=tuple(st))
         assert same_bits(wb[10], 1.0)
+
+
+@pytest.mark.parametrize("name", list(BIG))
+def test_big_extremes_on_later_trips(name, built):
+    """the four maxima and the minimum of word 8 with their deciding value planted at each seam position in turn (module docstring):
+    the slot carries the bits numpy gives for the planted entry, which beats the rest of the state; and a −0.0 multiplier there is
+    counted in word 10"""
+    P = point(name)
+    with objects(P) as S:
+        B, st_h, r_h, c_h = S.B, P["state"], P["r"], P["c"]
+        big_facts(name, S)
+        n = S.nvar
+        no_x, no_s = np.zeros(S.nvar, dtype=bool), np.zeros(S.ncon, dtype=bool)
+        masks = {"variable": np.concatenate([~no_x, no_s]), "row": np.concatenate([no_x, ~no_s]), "inequality row": np.concatenate([no_x, ~B["eq"]]),
+                 "lower": np.concatenate([B["hasL"], B["gL"]])}
+
+        def planted(kind):
+            out, seen = [], set()
+            for label, i in bref.seam_positions(S.nvar, S.n, S.bar.info["workgroups"]).items():
+                k = bref.nearest(masks[kind], i)
+                assert masks[kind][k]
+                if k not in seen:
+                    seen.add(k)
+                    out.append((f"{label} -> {k}", k))
+            return out
+        base = words(S)
+        head, _, w8, w10, _ = mref.error_words(B, st_h, r_h, c_h)
+        assert same_bits(base[:4], head) and same_bits(base[8], w8) and w10 == 0.0
+        dev_vec = {"r": S.r, "y": S.st[2], "c": S.c}
+        for slot, what, kind, value in ((0, "r", "variable", 1e30), (1, "y", "inequality row", 1e30), (2, "c", "row", 1e30), (3, "z", "lower", 1e30), (8, "z", "lower", 1e-30),
+                                        (10, "z", "lower", -0.0)):
+            for label, i in planted(kind):
+                iv, ir = (np.array([i]), np.array([], dtype=np.int64)) if i < n else (np.array([], dtype=np.int64), np.array([i - n]))
+                B1, st1 = bref.cut(B, iv, ir), [a.copy() for a in bref.cut_state(st_h, iv, ir)]
+                r1, c1 = r_h[iv].copy(), c_h[ir].copy()
+                j = i if i < n else i - n
+                vec = dev_vec[what] if what != "z" else (S.st[3] if i < n else S.st[5])
+                host_vec = {"r": r1, "y": st1[2], "c": c1, "z": st1[3] if i < n else st1[5]}[what]
+                old = float(vec[j])
+                vec[j] = value
+                host_vec[0] = value
+                got = words(S)
+                h1, _, m1, bad1, _ = mref.error_words(B1, tuple(st1), r1 if len(iv) else np.zeros(0), c1)
+                want_head = np.maximum(base[:4], np.where(np.isnan(h1), 0.0, h1))
+                print(f"{name} word {slot} planted ({what} = {value}) at {label}: head {got[:4].tolist()}, w8 {got[8]}, w10 {got[10]}")
+                assert same_bits(got[:4], want_head) and same_bits(got[8], min(float(base[8]), m1)) and same_bits(got[10], bad1), (slot, label, got)
+                if slot < 4:
+                    assert h1[slot] > base[slot]
+                elif slot == 8:
+                    assert m1 < base[8]
+                else:
+                    assert bad1 == 1.0 and same_bits(got[8], base[8])      # −0.0 is not >= +0.0 on the bit patterns: counted, kept out of the minimum
+                vec[j] = old
+        assert same_bits(words(S), base)
 
 
 def pattern_search(S, fs):

@@ -3,13 +3,21 @@
 BITWISE against tests/resto_reference.py (the numpy restatement, no tolerance): every output vector of every kernel — the object's
 own vectors read back through hipMemcpy — the step lengths, the maxima, the blocks and the filters; entries that must NOT be written
 (the slack side on equality rows, everything under +0.0 step lengths or a FAILED / UNUSABLE inner search, the object under a check
-that does not apply) are NaN-poisoned on the way in and compared bit for bit.  The parked sums (merit, slope, error) are bitwise equal
-between two runs and within barrier_reference.sum_bound of math.fsum of the restated addends.  resto_enter's sqrt is compared bitwise
-as well: the device's f64 sqrt is correctly rounded, as numpy's is.
+that does not apply) are NaN-poisoned on the way in and compared bit for bit.  THE PARKED SUMS are bitwise too: resto_merit's
+rho·S0 + zeta/2·S1 and theta_R, the slope of resto_begin — so the WHOLE inner block, from the restatement's own slope — and sum |y|
+and the sum of the multipliers of resto_error carry the bits of resto_reference.merit_device / slope / error_sums, the restatement
+in the DEVICE'S ORDER (barrier_reference.device_sum) on the object's own grid of info["workgroups"] workgroups.  ONE EXCEPTION: L, the
+sum of logs — the device's log and numpy's need not agree in the last bit, so that column is formed in the device's order from
+numpy's logs and compared within barrier_reference.sum_bound, as against math.fsum before; resto_error's copy still carries the bits
+of resto_merit(0)'s.  resto_enter's sqrt is compared bitwise as well: the device's f64 sqrt is correctly rounded, as numpy's is.
 
-Models: opf_7, pandemic_20x3, quadrotor_100 (several workgroups, the nvar seam inside one) of tests/cases.py and the two
-Waechter-Biegler models of tests/resto_reference.py at three supports.  The tables of return-test and filter-append cases are those
-of tests/test_resto.py.  One restoration iteration is captured as ONE graph and replayed; tests/resto_loop.py reaches the optima of
+Models: opf_7, pandemic_20x3, quadrotor_100 (several workgroups, the nvar seam inside one), pandemic_100x7 (47 workgroups: one full
+ticket group of iem_last_arrival and one ragged one) of tests/cases.py and the two Waechter-Biegler models of
+tests/resto_reference.py at three supports; and THE BIG SHAPES of tests/test_gpu_barrier.py — quadrotor(27 000) and quadrotor(60 000)
+of barrier_reference.big_point at resto_reference.big_entered, 4096 workgroups, two and three trips of the stride loop (asserted and
+printed) — through every 256-thread kernel, with each extreme slot (resto_step's step lengths, resto_error's maxima, resto_leave_max)
+planted at the seam positions of the later trips.  The tables of return-test and filter-append cases are those of
+tests/test_resto.py.  One restoration iteration is captured as ONE graph and replayed; tests/resto_loop.py reaches the optima of
 the two Waechter-Biegler models, and ends FAILED with max_restorations = 0."""
 import contextlib
 import ctypes as C
@@ -23,10 +31,11 @@ import barrier_reference as bref
 import resto_reference as rref
 import search_reference as sref
 from barrier_reference import KAPPA, TAU
+from test_gpu_barrier import BIG, big_facts
 from test_gpu_search import NAN, Search, _p, dev, hip, host, nan, same_bits
 
 pytestmark = pytest.mark.gpu
-MODELS = ["opf_7", "pandemic_20x3", "quadrotor_100", "wb_eq", "wb_ineq"]
+MODELS = ["opf_7", "pandemic_20x3", "quadrotor_100", "pandemic_100x7", "wb_eq", "wb_ineq"]
 DELTA_C = 1e-10
 
 
@@ -86,13 +95,20 @@ def layer(name, seed=0):
     """tests/test_gpu_search.py's layer with the Waechter-Biegler models among the models"""
     from infiniteexamodels.jl_amd import lib as iemlib
     from infiniteexamodels.jl_amd.model import ExaModel
-    P = rref.point(name, seed)
-    gm = ExaModel(P["core"], device=0, blob=P["blob"])
+    P = bref.big_point(BIG[name]) if name in BIG else rref.point(name, seed)
+    gm = ExaModel(P["core"], device=0, blob=P["blob"]) if P["blob"] is not None else ExaModel(P["core"], device=0)
     b = C.c_void_p()
-    iemlib.check(gm._L.iem_barrier_create(gm._h, None, None, None, None, bref.RELAX, C.byref(b)))
+    bounds = [np.ascontiguousarray(P[k], dtype=np.float64) for k in ("lvar", "uvar", "lcon", "ucon")] if name in BIG else [None] * 4
+    iemlib.check(gm._L.iem_barrier_create(gm._h, *[a.ctypes.data if a is not None else None for a in bounds], bref.RELAX, C.byref(b)))
     made = []
     try:
-        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=P["om"].nvar, ncon=P["om"].ncon, n=P["om"].nvar + P["om"].ncon, check=iemlib.check)
+        info = iemlib.BarrierInfo()
+        info.struct_size = C.sizeof(iemlib.BarrierInfo)
+        iemlib.check(gm._L.iem_barrier_info(b, C.byref(info)))
+        cn = P["B"]["counts"]
+        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=cn["nvar"], ncon=cn["ncon"], n=cn["nvar"] + cn["ncon"], check=iemlib.check,
+                                  info={k: int(getattr(info, k)) for k, _ in iemlib.BarrierInfo._fields_})
+        assert S.nvar == int(gm.meta.nvar) and S.ncon == int(gm.meta.ncon) and S.info["workgroups"] == min(-(-S.n // 256), 4096)
         S.sizes = (S.nvar, S.ncon, S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
         S.dsizes = (S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
         S.search = lambda **opts: made.append(Search(S, **opts)) or made[-1]
@@ -112,17 +128,30 @@ def same_object(got, want, keys=rref.ROWS + rref.VARS + ("blk",)):
     return True
 
 
-def within(got, terms, what, extra=0.0):
-    want, bound = bref.sum_bound(terms)
-    print(f"    {what}: device {got!r}, fsum {want!r}, |difference| {abs(got - want):.3e}, bound {bound + extra:.3e}, terms {len(terms)}")
-    assert abs(got - want) <= bound + extra, what
+def logs_within(got, want, terms, what):
+    """a sum of logs: within sum_bound of the device's order over numpy's logs, and of math.fsum"""
+    fs, bound = bref.sum_bound(terms)
+    print(f"    {what}: device {got!r}, device order over numpy's logs {float(want)!r}, fsum {fs!r}, bound {bound:.3e}, terms {len(terms)}")
+    assert abs(got - float(want)) <= bound and abs(got - fs) <= bound, what
 
 
-@pytest.mark.parametrize("name", MODELS)
+def check_merit(S, R, which, x_h, s_h, c_h, zeta, got, what):
+    """resto_merit: out[0], out[1] carry the bits of the restatement in the device's order; out[2] is a sum of logs"""
+    want = rref.merit_device(S.B, R, which, x_h, s_h, c_h, zeta, S.info["workgroups"])
+    print(f"  {what}: device {got.tolist()}, device order {want.tolist()}, workgroups {S.info['workgroups']}")
+    assert same_bits(got[:2], want[:2]), (what, got, want)
+    logs_within(float(got[2]), want[2], rref.merit_terms(S.B, R, which, x_h, s_h, c_h)[3], "L")
+
+
+@pytest.mark.parametrize("name", MODELS + list(BIG))
 def test_every_kernel_bitwise(name, built):
     with layer(name) as S:
         P, B = S.P, S.B
         n, m = S.nvar, S.ncon
+        if name in BIG:
+            big_facts(name, S)
+        if name == "pandemic_100x7":
+            assert S.n == 12000 and S.info["workgroups"] == 47
         eqnan = lambda a: np.where(B["eq"], NAN, a)
         rng = np.random.default_rng(41)
         q = S.search()
@@ -149,12 +178,16 @@ def test_every_kernel_bitwise(name, built):
             assert same_bits(host(t, k), want)
         assert same_bits(q.block(), ctl1) and same_bits(q.filter(), filt1) and sref.word(ctl1, sref.COUNT) == 2      # (3, 11) left, the new entry came
         # ---- the middle of a phase: p, n, zp, zn off the central path, a multiplier y
-        R, st_h, mu = rref.entered(P)
+        if name in BIG:      # (the shared big case: the heavy lane of the 60 000 shape carries its weights)
+            E = rref.big_entered(BIG[name])
+            R, st_h, mu = {k: v.copy() for k, v in E["R"].items()}, E["state"], E["mu"]
+        else:
+            R, st_h, mu = rref.entered(P)
         zeta = math.sqrt(mu)
         R["blk"] = R1["blk"]
         z.upload(R)
         st = tuple(dev(a) for a in st_h)
-        r_h = P["om"].jtprod(st_h[0], st_h[2])
+        r_h = P["r"] if name in BIG else P["om"].jtprod(st_h[0], st_h[2])
         r = dev(r_h)
         # terms
         sigma, dcon, rhs = nan(n), nan(m), nan(S.n)
@@ -163,7 +196,7 @@ def test_every_kernel_bitwise(name, built):
         assert same_bits(host(sigma, n), want[0]) and same_bits(host(dcon, m), want[1]) and same_bits(host(rhs, S.n), want[2])
         assert same_object(z.object(), R)      # terms writes nothing into the object
         # step
-        sol_h = rng.standard_normal(S.n)
+        sol_h = E["sol"] if name in BIG else rng.standard_normal(S.n)
         sol = dev(sol_h)
         dirs, alpha = tuple(nan(k) for k in S.dsizes), nan(2)
         z.call("step", *map(_p, st), _p(sol), mu, TAU, zeta, *map(_p, dirs), _p(alpha))
@@ -192,12 +225,7 @@ def test_every_kernel_bitwise(name, built):
             again = nan(3)
             z.call("merit", 0, _p(st[0]), _p(st[1]), _p(c), zeta, _p(again))
             assert same_bits(host(again, 3), m0_h)
-        S0, S1, th, lg = rref.merit_terms(B, R, 0, st_h[0], st_h[1], c_h)
-        print(name, "merit(0)")
-        rho = rref.OPTS["rho"]
-        within(float(m0_h[0]), np.concatenate([rho * S0, (0.5 * zeta) * S1]), "rho·S0 + zeta/2·S1", extra=4 * 2.0 ** -52 * abs(float(m0_h[0])))
-        within(float(m0_h[1]), th, "theta_R")
-        within(float(m0_h[2]), lg, "L")
+        check_merit(S, R, 0, st_h[0], st_h[1], c_h, zeta, m0_h, f"{name} merit(0)")
         # begin: the slope and the inner block
         start = z.inner.block()
         assert sref.word(start, sref.STATUS) == sref.UNUSABLE
@@ -206,10 +234,10 @@ def test_every_kernel_bitwise(name, built):
         for _ in range(3):
             z.call("begin", _p(st[0]), _p(st[1]), _p(sol), _p(dirs[0]), _p(m0), _p(alpha), mu, zeta)
             assert same_bits(z.inner.block(), first)
-        print(name, "begin")
-        within(float(first[sref.SLOPE]), rref.slope_terms(B, R, st_h, sol_h, np.where(B["eq"], 0.0, dirs_h[0]), mu, zeta), "slope")
-        ref = rref.begin(start, float(first[sref.SLOPE]), m0_h, alpha_h, mu)
-        assert same_bits(first, ref) and sref.word(first, sref.STATUS) == sref.SEARCHING and first[sref.ALPHA] == alpha_h[0]
+        slope = rref.slope(B, R, st_h, sol_h, dirs_h[0], mu, zeta, S.info["workgroups"])      # the restatement's, in the device's order
+        print(name, f"begin: slope {float(first[sref.SLOPE])!r}, device order {float(slope)!r}")
+        ref = rref.begin(start, slope, m0_h, alpha_h, mu)
+        assert same_bits(first, ref) and sref.word(first, sref.STATUS) == sref.SEARCHING and first[sref.ALPHA] == alpha_h[0], (first, ref)
         assert same_bits(q.block(), ctl1)      # the ORIGINAL block is not the inner one
         # trial, merit at the trial point
         xt, s_t = nan(n), nan(m)
@@ -220,11 +248,7 @@ def test_every_kernel_bitwise(name, built):
         ct, m1 = dev(ct_h), nan(3)
         z.call("merit", 1, _p(xt), _p(s_t), _p(ct), zeta, _p(m1))
         m1_h = host(m1, 3)
-        S0, S1, th, lg = rref.merit_terms(B, R, 1, xt_h, s_t_h, ct_h)
-        print(name, "merit(1)")
-        within(float(m1_h[0]), np.concatenate([rho * S0, (0.5 * zeta) * S1]), "rho·S0 + zeta/2·S1", extra=4 * 2.0 ** -52 * abs(float(m1_h[0])))
-        within(float(m1_h[1]), th, "theta_R")
-        within(float(m1_h[2]), lg, "L")
+        check_merit(S, R, 1, xt_h, s_t_h, ct_h, zeta, m1_h, f"{name} merit(1)")
         # trial under FAILED and UNUSABLE: nothing is stored
         for status in (sref.FAILED, sref.UNUSABLE):
             blk = first.copy()
@@ -245,9 +269,10 @@ def test_every_kernel_bitwise(name, built):
         assert same_bits(host(again, 8), out_h)
         head, ay, mult, th, lg = rref.error(B, R, st_h, r_h, c_h, mu, zeta)
         assert same_bits(out_h[:4], head), (out_h[:4], head)
-        print(name, "error")
-        within(float(out_h[4]), ay, "sum |y|")
-        within(float(out_h[5]), mult, "sum of multipliers")
+        sums = rref.error_sums(B, R, st_h, c_h, S.info["workgroups"])
+        print(name, "error: out[4..7]", out_h[4:].tolist(), "device order", sums.tolist())
+        assert same_bits(out_h[4:7], sums[:3]), (out_h[4:7], sums[:3])
+        logs_within(float(out_h[7]), sums[3], lg, "L")
         assert same_bits(out_h[6:], m0_h[1:])      # theta_R and L: the bits of merit(0)
         z.call("error", *map(_p, st), None, _p(c), mu, zeta, _p(again))
         head_nr, *_ = rref.error(B, R, st_h, None, c_h, mu, zeta)
@@ -283,6 +308,122 @@ def test_every_kernel_bitwise(name, built):
             assert same_object(z.object(), dict(Ra, blk=want_blk))
             if bump and B["counts"]["nz"]:
                 assert want_blk[rref.R_ZMAX] == 1000.5
+
+
+@pytest.mark.parametrize("name", list(BIG))
+def test_big_extremes_on_later_trips(name, built):
+    """resto_step's two step lengths, resto_error's four maxima and resto_leave_max with their deciding value planted at each seam
+    position of tests/test_gpu_barrier.py in turn: the slot carries the bits numpy gives for the planted entry, which beats the rest"""
+    from test_gpu_barrier import cut_at, planted
+    with layer(name) as S:
+        P, B = S.P, S.B
+        n, m = S.nvar, S.ncon
+        big_facts(name, S)
+        E = rref.big_entered(BIG[name])
+        R, st_h, mu = E["R"], E["state"], E["mu"]
+        zeta = math.sqrt(mu)
+        q = S.search()
+        z = S.resto(q)
+        z.upload(R)
+        st = tuple(dev(a) for a in st_h)
+        r_h, c_h = P["r"], P["c"]
+        r, c = dev(r_h), dev(c_h)
+        sol_h = np.random.default_rng(43).standard_normal(S.n)      # (not the shared direction: its heavy lane leaves no room below its step lengths)
+        sol = dev(sol_h)
+        poison = tuple(np.full(m, NAN) for _ in range(3))
+        base_alpha = rref.step(B, R, st_h, sol_h, poison, mu, TAU, zeta)[1]
+        dirs, alpha = tuple(nan(k) for k in S.dsizes), nan(2)
+
+        def cut_R(iv, ir):
+            C1 = {k: R[k][ir] for k in rref.ROWS}
+            C1.update({k: R[k][iv] for k in rref.VARS})
+            C1["blk"] = R["blk"]
+            return C1
+        for slot, what in ((0, "alpha_primal"), (1, "alpha_dual")):
+            for label, i in planted(S, "lower"):
+                B1, st1, iv, ir = cut_at(S, st_h, i)
+                value = -1e9 if slot == 0 else 1e9
+                sol[i] = value
+                z.call("step", *map(_p, st), _p(sol), mu, TAU, zeta, *map(_p, dirs), _p(alpha))
+                got = host(alpha, 2)
+                one = rref.step(B1, cut_R(iv, ir), st1, np.array([value]), tuple(np.full(len(ir), NAN) for _ in range(3)), mu, TAU, zeta)[1]
+                print(f"{name} {what} planted at {label}: {got.tolist()}, the entry alone {one.tolist()}, the rest {base_alpha.tolist()}")
+                assert one[slot] < base_alpha[slot] and same_bits(got, np.minimum(base_alpha, one)), (what, label, got, one)
+                sol[i] = float(sol_h[i])
+        # a NaN direction; a point exactly on its relaxed bound with a direction through it: alpha_primal = +0.0, update moves nothing
+        import torch
+        four = np.concatenate([R[k] for k in ("p", "n", "zp", "zn")])
+        got_four = np.empty(4 * m)
+        for label, i in planted(S, "lower"):
+            j, vec = (i, 0) if i < n else (i - n, 1)
+            bound = float((B["xl"] if i < n else B["rl"])[j])
+            for case, value, x_value in (("NaN direction", NAN, None), ("on its bound", -1.0 if i < n else -1e9, bound)):
+                B1, st1, iv, ir = cut_at(S, st_h, i)
+                st1 = [a.copy() for a in st1]
+                old = float(st[vec][j])
+                if x_value is not None:
+                    st[vec][j] = x_value
+                    st1[vec][0] = x_value
+                sol[i] = value
+                z.call("step", *map(_p, st), _p(sol), mu, TAU, zeta, *map(_p, dirs), _p(alpha))
+                got = host(alpha, 2)
+                one = rref.step(B1, cut_R(iv, ir), tuple(st1), np.array([value]), tuple(np.full(len(ir), NAN) for _ in range(3)), mu, TAU, zeta)[1]
+                print(f"{name} {case} at {label}: alpha {got.tolist()}")
+                assert same_bits(got[:1], [0.0]) and same_bits(got, np.minimum(base_alpha, one)), (case, label, got, one)
+                before = [t.clone() for t in st]
+                z.call("update", *map(_p, st), _p(sol), *map(_p, dirs), _p(alpha), mu, KAPPA)
+                assert all(torch.equal(a.view(torch.int64), b_.view(torch.int64)) for a, b_ in zip(st, before)), (case, label)
+                z.q._copy(got_four.ctypes.data, z.d_vec, got_four.nbytes, 2)
+                assert same_bits(got_four, four), (case, label)
+                sol[i] = float(sol_h[i])
+                st[vec][j] = old
+        # the four maxima: r (a variable), y (a row), c (a row), a multiplier (an entry with a lower bound)
+        base = rref.error(B, R, st_h, r_h, c_h, mu, zeta)[0]
+        out = nan(8)
+
+        def error_head():
+            z.call("error", *map(_p, st), _p(r), _p(c), mu, zeta, _p(out))
+            return host(out, 8)[:4]
+        assert same_bits(error_head(), base)
+        for slot, what, kind in ((0, "r", "variable"), (1, "y", "row"), (2, "c", "row"), (3, "z", "lower")):
+            for label, i in planted(S, kind):
+                B1, st1, iv, ir = cut_at(S, st_h, i)
+                st1 = [a.copy() for a in st1]
+                r1, c1 = r_h[iv].copy(), c_h[ir].copy()
+                j = i if i < n else i - n
+                vec, host_vec = {"r": (r, r1), "y": (st[2], st1[2]), "c": (c, c1), "z": (st[3], st1[3]) if i < n else (st[5], st1[5])}[what]
+                old = float(vec[j])
+                vec[j] = 1e30
+                host_vec[0] = 1e30
+                got = error_head()
+                one = rref.error(B1, cut_R(iv, ir), tuple(st1), r1 if len(iv) else None, c1, mu, zeta)[0]
+                want = np.maximum(base, np.where(np.isnan(one), 0.0, one))      # (a cut without variables has no out[0])
+                print(f"{name} out[{slot}] planted ({what}) at {label}: {got.tolist()}")
+                assert one[slot] > base[slot] and same_bits(got, want), (what, label, got, want)
+                vec[j] = old
+        assert same_bits(error_head(), base)
+        # resto_leave_max: every present multiplier at most 50 but the planted one, below the reset threshold: nothing but y moves
+        with np.errstate(invalid="ignore"):
+            cur = [np.minimum(a, 50.0) if k >= 3 else a.copy() for k, a in enumerate(st_h)]
+        stl = tuple(dev(a) for a in cur)
+        active = R["blk"].copy()
+        active.view(np.int64)[0] = rref.RETURN
+        got_blk = np.empty(8)
+        for label, i in planted(S, "upper"):
+            j = i if i < n else i - n
+            vec = stl[4] if i < n else stl[6]
+            vec[j] = 777.25
+            z.q._copy(z.d_blk, active.ctypes.data, 64, 1)
+            z.call("leave", *map(_p, stl[2:]))
+            z.q._copy(got_blk.ctypes.data, z.d_blk, 64, 2)
+            print(f"{name} leave_max planted at {label}: {got_blk[rref.R_ZMAX]}")
+            assert same_bits(got_blk[rref.R_ZMAX], 777.25) and int(got_blk.view(np.int64)[0]) == rref.NONE, (label, got_blk)
+            assert float(vec[j]) == 777.25      # below the threshold: the multipliers stay
+            vec[j] = 50.0
+        z.q._copy(z.d_blk, active.ctypes.data, 64, 1)
+        z.call("leave", *map(_p, stl[2:]))
+        z.q._copy(got_blk.ctypes.data, z.d_blk, 64, 2)
+        assert same_bits(got_blk[rref.R_ZMAX], 50.0)
 
 
 def test_the_return_test_and_the_filter_append(built):

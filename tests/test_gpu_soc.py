@@ -6,8 +6,11 @@ left bit for bit; for every hand-built case of the correction table the block, t
 after every round.  Outputs go into NaN-poisoned buffers with NaN padding; entries of s, st, ds, dvL, dvU on equality rows are NaN
 on the way in and still NaN afterwards.
 
-Models: opf_7, pandemic_20x3, quadrotor_100 (several workgroups, the nvar seam inside one) of tests/cases.py, and `maratos` of
-tests/soc_reference.py (three supports: 6 variables, 3 equality rows, no bounds).
+Models: opf_7, pandemic_20x3, quadrotor_100 (several workgroups, the nvar seam inside one) and pandemic_100x7 (12 000 entries, 47
+workgroups) of tests/cases.py, and `maratos` of tests/soc_reference.py (three supports: 6 variables, 3 equality rows, no bounds).
+The grid calls (rhs, trial, select, with the gating words set so that they run, and under every other gate) also run at THE BIG
+SHAPES of tests/test_gpu_barrier.py — quadrotor(27 000) and quadrotor(60 000) of barrier_reference.big_point: 4096 workgroups, two
+and three trips of the stride loop, the nvar seam inside the second trip of the larger (asserted and printed) — bit for bit.
 
 THE LADDER on `maratos` from x = (cos 0.8, sin 0.8), y = −1.5·w:  begin; rung; open; 2 × round; select; 2 × rung; update; error — the
 full Newton step raises theta and phi (the Maratos effect) and is rejected, round 1 of the correction is accepted f-type, round 2 and
@@ -24,10 +27,11 @@ import barrier_reference as bref
 import search_reference as sref
 import soc_reference as cref
 from barrier_reference import KAPPA, MU, TAU
+from test_gpu_barrier import BIG, big_facts
 from test_gpu_search import DC, DW, LADDER, NAN, Search, _p, bref_names, dev, hip, host, nan, newton_direction, same_bits
 
 pytestmark = pytest.mark.gpu
-MODELS = ["opf_7", "pandemic_20x3", "quadrotor_100", "maratos"]
+MODELS = ["opf_7", "pandemic_20x3", "quadrotor_100", "pandemic_100x7", "maratos"]
 SIGMA = 1.0
 DELTA_C = 1e-10
 
@@ -82,13 +86,20 @@ def layer(name, seed=0):
     """tests/test_gpu_search.py's layer with `maratos` among the models: the handle, the raw barrier object, the shared point"""
     from infiniteexamodels.jl_amd import lib as iemlib
     from infiniteexamodels.jl_amd.model import ExaModel
-    P = cref.point(name, seed)
-    gm = ExaModel(P["core"], device=0, blob=P["blob"])
+    P = bref.big_point(BIG[name]) if name in BIG else cref.point(name, seed)
+    gm = ExaModel(P["core"], device=0, blob=P["blob"]) if P["blob"] is not None else ExaModel(P["core"], device=0)
     b = C.c_void_p()
-    iemlib.check(gm._L.iem_barrier_create(gm._h, None, None, None, None, bref.RELAX, C.byref(b)))
+    bounds = [np.ascontiguousarray(P[k], dtype=np.float64) for k in ("lvar", "uvar", "lcon", "ucon")] if name in BIG else [None] * 4
+    iemlib.check(gm._L.iem_barrier_create(gm._h, *[a.ctypes.data if a is not None else None for a in bounds], bref.RELAX, C.byref(b)))
     made = []
     try:
-        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=P["om"].nvar, ncon=P["om"].ncon, n=P["om"].nvar + P["om"].ncon, check=iemlib.check)
+        info = iemlib.BarrierInfo()
+        info.struct_size = C.sizeof(iemlib.BarrierInfo)
+        iemlib.check(gm._L.iem_barrier_info(b, C.byref(info)))
+        cn = P["B"]["counts"]
+        S = types.SimpleNamespace(gm=gm, L=gm._L, b=b, P=P, B=P["B"], nvar=cn["nvar"], ncon=cn["ncon"], n=cn["nvar"] + cn["ncon"], check=iemlib.check,
+                                  info={k: int(getattr(info, k)) for k, _ in iemlib.BarrierInfo._fields_})
+        assert S.nvar == int(gm.meta.nvar) and S.ncon == int(gm.meta.ncon) and S.info["workgroups"] == min(-(-S.n // 256), 4096)
         S.sizes = (S.nvar, S.ncon, S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
         S.dsizes = (S.ncon, S.nvar, S.nvar, S.ncon, S.ncon)
         S.search = lambda **opts: made.append(Search(S, **opts)) or made[-1]
@@ -109,12 +120,16 @@ def soc_block(state, rounds=0, alpha_prev=0.75, **kw):
     return ctl
 
 
-@pytest.mark.parametrize("name", MODELS)
+@pytest.mark.parametrize("name", MODELS + list(BIG))
 def test_grid_calls(name, built):
     """soc_rhs, soc_trial and soc_select against the restatement: rounds = 0 (csoc holds NaN: it is not read) and rounds = 1; and with
     the state word NONE, CLOSED, ACCEPTED (select: NONE, ACTIVE, CLOSED) every output and csoc keep their bits"""
     with layer(name) as S:
         P, B = S.P, S.B
+        if name in BIG:
+            big_facts(name, S)
+        if name == "pandemic_100x7":
+            assert S.n == 12000 and S.info["workgroups"] == 47
         st_h = P["state"]
         rng = np.random.default_rng(31)
         eqnan = lambda a: np.where(B["eq"], NAN, a)
