@@ -1079,8 +1079,8 @@ int iem_resto_source(char **out_src, uint64_t *out_key);
  * s_max <= 0, any option not finite, mu0 <= 0 or not finite, an fs or a bind across two barrier objects.  The object borrows the
  * barrier object; a bound object borrows the block: unbind (or destroy the bound objects) before iem_mu_destroy.  Not here: the
  * delta_w / inertia retry, a binding for iem_resto, sharded handles.  The adaptive rules that words 8 and 9 of iem_mu_error
- * serve (probing, LOQO) are the iem_amu object below, the quality-function oracle the iem_qf object below it; Mehrotra's corrector is
- * not there. */
+ * serve (probing, LOQO) are the iem_amu object below, the quality-function oracle the iem_qf object below it, Mehrotra's corrector
+ * the iem_mpc object below that. */
 typedef struct iem_mu iem_mu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mu_opts_t) */
@@ -1160,8 +1160,8 @@ int iem_barrier_mu_source(char **out_src, uint64_t *out_key);
  * work: null required pointers (the slack side may be NULL without inequality rows), a probing object updated without q, an fs of
  * another barrier object, oracle not 0 or 1, sigma_max, mu_min, mu_max_fact or init_factor <= 0, red_fact outside (0, 1), refs_max
  * outside 1..4, any option not finite.  The object borrows the iem_mu object: destroy it first.  Ipopt's quality-function oracle
- * (oracle = 2 here is refused) is the iem_qf object below.  Not here: Mehrotra's corrector, the obj-constr-filter globalisation, a
- * binding for iem_resto, sharded handles, the delta_w / inertia retry (the host's). */
+ * (oracle = 2 here is refused) is the iem_qf object below, Mehrotra's corrector the iem_mpc object below that.  Not here: the
+ * obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w / inertia retry (the host's). */
 typedef struct iem_amu iem_amu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_amu_opts_t) */
@@ -1266,8 +1266,9 @@ int iem_amu_source(char **out_src, uint64_t *out_key);
  * launch, no grid-wide wait: every dependence between workgroups is a launch boundary.  IEM_E_ARG before any device work: null
  * required pointers (the slack side may be NULL without inequality rows), an fs of another barrier object, mu_ref, sigma_min or
  * section_sigma_tol <= 0, sigma_max < 0 (0: the iem_amu object's), max_section_steps outside 1..16, any option not finite.  The
- * object borrows the iem_amu object: destroy it first.  Not here: Ipopt's other norm types, the centrality and balancing terms,
- * Mehrotra's corrector, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w / inertia retry. */
+ * object borrows the iem_amu object: destroy it first.  Mehrotra's corrector is the iem_mpc object below.  Not here: Ipopt's other
+ * norm types, the centrality and balancing terms, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the
+ * delta_w / inertia retry. */
 typedef struct iem_qf iem_qf;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_qf_opts_t) */
@@ -1302,6 +1303,90 @@ int iem_qf_device(const iem_qf *q, double **d_block);
 int iem_qf_state(iem_qf *q, iem_mu_state_t *mu_out, iem_amu_state_t *amu_out, iem_qf_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the five kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_qf_source(char **out_src, uint64_t *out_key);
+
+/* ---- Mehrotra's corrector --------------------------------------------------------------------------------------------------------------
+ * The second-order term of the complementarity equations on the right-hand side (Ipopt's `mehrotra_algorithm = yes`, every LP / QP
+ * interior-point code) on the device (csrc/iem_mpc_device.h), as an object created ON an iem_amu: it borrows that object, the iem_mu
+ * block under it and the barrier object's bounds, flags and grid.  The affine-scaling direction (sol_aff, ds_aff, dzL_aff, dzU_aff,
+ * dvL_aff, dvU_aff: what iem_amu_probe is handed; with iem_qf its d0) carries the term dgap_aff·dz_aff; the corrected direction solves
+ * the Newton system whose complementarity rows have the target mu − dgap_aff·dz_aff in the place of mu.  It costs one more column of
+ * the iteration's refined solve, no factorisation and no host decision.  The calls run AFTER the rule's update (iem_amu_update /
+ * iem_qf_update), at the new mu, with the objects bound again.
+ *
+ * Entry order, flags (fx / fc) and what is never read are those of iem_barrier_terms / iem_barrier_step: one thread takes the entries
+ * i, i + stride, ... of [0, nvar + ncon); nothing is read where no bound is present, nor on equality rows of the slack side; dy_aff
+ * (sol_aff past nvar) is never read.  Each operation is rounded once, in the order written here.  With d_aff = sol_aff[i] on variables
+ * and ds_aff[j] on inequality rows, per PRESENT bound:
+ *         lower bound:  e = d_aff·dz_aff;  m = mu − e          upper bound:  e = d_aff·dz_aff;  m = mu + e      (its gap moves by −d)
+ * iem_mpc_terms: ONE launch on the barrier object's grid.  Two columns, d_rhs2 + u·ld (ld >= nvar + ncon; the layout of
+ *     iem_kkt_solve_refined_diag).  Column 0 is bit for bit the rhs of iem_barrier_terms at that mu.  Column 1 is the same expressions
+ *     with m in the place of mu:   ml = m/gap (lower; else +0.0);  mu_u = m/gap (upper; else +0.0);  variables: gb = mu_u − ml;
+ *     rhs = −(r + gb);  inequality rows: sl = vL/gap, su = vU/gap, sigs = sl + su;  gs = mu_u − ml;  rs = gs − y;  inv = 1.0/sigs;
+ *     rhs = −((c − s) + rs·inv);  equality rows: −(c − ceq) in both columns.  sigma and dcon are NOT written: they do not depend on mu
+ *     and exist from the affine iem_barrier_terms call.
+ * iem_mpc_step: ONE launch on the same grid behind one 16-byte device-to-device copy (the step lengths' seed, the bits of 1.0), on
+ *     the CORRECTED solution (column 1 of the solve).  iem_barrier_step word for word with m in the place of mu:
+ *         variables:  dzL = (m/gap − zL) − (zL/gap)·dx;  dzU = (m/gap − zU) + (zU/gap)·dx      (absent bound: +0.0)
+ *         rows:  ml = m/gap, mu_u = m/gap;  gs = mu_u − ml;  rs = gs − y;  ds = (dy − rs)/sigs;  dvL = (ml − vL) − sl·ds;
+ *                dvU = (mu_u − vU) + su·ds
+ *     and its candidates (−tau·gap)/d, (tau·gap)/d, (−tau·z)/dz, its NaN rules (a NaN in dx, dy or the ds of an inequality row makes
+ *     alpha_primal +0.0 whatever the bounds, a NaN in a multiplier's direction at a present bound makes alpha_dual +0.0; a candidate
+ *     that is not > 0 counts as +0.0) and its integer minima on bit patterns, at most one atomic per workgroup and slot.  Column 0 of
+ *     the solve goes through iem_barrier_step, unchanged.
+ * THE SAFEGUARD'S MEASUREMENT is iem_amu_probe on the corrected direction at alpha_c: four words q_c.  A launch of its own because it
+ *     needs alpha_c: every dependence between workgroups is a launch boundary.
+ * iem_mpc_select: ONE launch on the same grid.  Every thread reads q_c, the two words of alpha_c and word 9 (avg) of the iem_amu block
+ *     — none of which the launch writes — and decides the same way.  With nz of iem_barrier_info:
+ *         predicted = nz ? q_c[0]/nz : +0.0;   bound = red_fact·avg
+ *         TAKEN  iff  nz != 0  and  q_c[1] == 0  and  neither word of alpha_c is the bits of +0.0  and  predicted <= bound
+ *     (a NaN compares false; red_fact = 1.0 is Ipopt's corrector_compl_avrg_red_fact).  Taken, the corrected direction is copied
+ *     over the first-order one, exactly the entries iem_soc_select copies — sol: nvar + ncon; dzL, dzU: nvar; ds, dvL, dvU:
+ *     inequality rows only — and d_alpha takes the two words of alpha_c.  Refused, the call returns before its first store to a
+ *     direction.  iem_search_begin, the rungs, iem_soc_* and iem_barrier_update then run on the first-order buffers as before.
+ * THE OWN BLOCK: sixteen 8-byte words on the device (iem_mpc_device gives the pointer; iem_mpc_state_t mirrors words 0–6), written by
+ *     one thread of workgroup 0 of iem_mpc_select:
+ *     0 the decision of this call (int64): 1 taken, 0 refused      1 correctors taken so far (int64)      2 refused so far (int64)
+ *     3 predicted      4 avg      5, 6 alpha_c (alpha_primal, alpha_dual)      7–15 zero
+ *     iem_mpc_create zeroes it; iem_mpc_reset (one launch of one workgroup, asynchronous) does the same.
+ * iem_mpc_bind_mu(q, p): bound, mpc_terms / mpc_step read mu and tau from words 0 and 1 of the iem_mu block and ignore their
+ *     arguments and the range checks; p = NULL unbinds: they take the host's mu >= 0 and tau in (0, 1].  No launch, one code object.
+ * iem_mpc_state: the one read-back (one synchronisation).
+ * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  No float atomic, no cooperative
+ * launch.  IEM_E_ARG before any device work: null required pointers (the slack side may be NULL without inequality rows),
+ * ld < nvar + ncon, red_fact not finite or <= 0, an iem_mu passed to iem_mpc_bind_mu that is not the object's own, unbound mu < 0 or
+ * tau outside (0, 1], d_alpha == d_alpha_c.  The object borrows the iem_amu object: destroy it first.  Not here: Ipopt's
+ * accept_every_trial_step and the other options mehrotra_algorithm implies, Gondzio's multiple centrality correctors, a corrector
+ * inside iem_resto, sharded handles, the delta_w / inertia retry.  iem_soc_rhs is unchanged: the second-order correction's own
+ * right-hand side keeps the target mu. */
+typedef struct iem_mpc iem_mpc;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mpc_opts_t) */
+  double red_fact;
+} iem_mpc_opts_t;                       /* NULL = 1.0 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_mpc_state_t): at most that many bytes are written */
+  int64_t taken, n_taken, n_refused;    /* words 0–2 */
+  double predicted, avg;                /* words 3, 4 */
+  double alpha_c[2];                    /* words 5, 6 */
+} iem_mpc_state_t;
+int iem_mpc_create(iem_amu *a, const iem_mpc_opts_t *opts, iem_mpc **out);
+int iem_mpc_destroy(iem_mpc *q);
+int iem_mpc_reset(iem_mpc *q);
+int iem_mpc_bind_mu(iem_mpc *q, const iem_mu *p /* NULL unbinds */);
+int iem_mpc_terms(iem_mpc *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                  const double *d_vU, const double *d_r, const double *d_c, const double *d_sol_aff, const double *d_ds_aff, const double *d_dzL_aff,
+                  const double *d_dzU_aff, const double *d_dvL_aff, const double *d_dvU_aff, double mu, double *d_rhs2, int64_t ld);
+int iem_mpc_step(iem_mpc *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                 const double *d_vU, const double *d_sol_aff, const double *d_ds_aff, const double *d_dzL_aff, const double *d_dzU_aff,
+                 const double *d_dvL_aff, const double *d_dvU_aff, const double *d_sol_c, double mu, double tau, double *d_ds_c, double *d_dzL_c,
+                 double *d_dzU_c, double *d_dvL_c, double *d_dvU_c, double *d_alpha_c /* 2 */);
+int iem_mpc_select(iem_mpc *q, const double *d_probe4 /* q_c */, const double *d_alpha_c /* 2 */, const double *d_sol_c, const double *d_ds_c,
+                   const double *d_dzL_c, const double *d_dzU_c, const double *d_dvL_c, const double *d_dvU_c, double *d_sol, double *d_ds, double *d_dzL,
+                   double *d_dzU, double *d_dvL, double *d_dvU, double *d_alpha /* 2 */);
+int iem_mpc_device(const iem_mpc *q, double **d_block);
+int iem_mpc_state(iem_mpc *q, iem_mpc_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the four kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_mpc_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

@@ -804,6 +804,132 @@ class QualityFunction:
             pass
 
 
+class MehrotraCorrector:
+    """``MehrotraCorrector(amu, red_fact=1.0)``: Mehrotra's corrector of the C-ABI (``iem_mpc_*``, ``csrc/iem_mpc_device.h``) ON an
+    :class:`AdaptiveBarrierParameter` — the second-order term ``Δgap_aff·Δz_aff`` of the complementarity equations on the right-hand
+    side, for one more column of the iteration's refined solve; the safeguard's decision and the copy over the first-order direction
+    on the device.  Per iteration, AFTER the rule's update, with the objects bound again (``mpc.bind_mu(par)`` once):
+
+        amu.update(w, q, search=fs)                                    # (or qf.update; the affine direction is then its d0)
+        rhs2 = mpc.terms(state, r, c, sol_a, dirs_a, out=rhs2)         # (2, n): column 0 is bar.terms(...)[2] at the new mu
+        sol2 = kkt.solve(rhs2.t(), refine=1).t()                       # ONE pass over the iteration's factors for both columns
+        dirs, alpha = bar.step(state, sol2[0], mu, tau)                # column 0: unchanged
+        dirs_c, alpha_c = mpc.step(state, sol_a, dirs_a, sol2[1])
+        q_c = amu.probe(state, sol2[1], dirs_c, alpha_c, out=q_c)      # the safeguard's measurement
+        mpc.select(q_c, alpha_c, sol2[1], dirs_c, sol2[0], dirs, alpha)   # taken: the corrected direction over the first-order one
+        ...                                                            # fs.begin, the rungs, soc, bar.update on (sol2[0], dirs, alpha)
+        st = mpc.state()                                               # THE read-back"""
+
+    def __init__(self, amu: AdaptiveBarrierParameter, **opts):
+        self.amu = amu
+        self.par = amu.par
+        self.layer = amu.layer
+        self._q = None
+        o = _lib.MpcOpts.defaults(**opts)
+        L, a = amu._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_mpc_create(a, C.byref(o), C.byref(q)))
+        self._q = q
+        self.opts = {name: getattr(o, name) for name, _ in _lib.MpcOpts._fields_ if name != "struct_size"}
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("MehrotraCorrector: closed")
+        L, _ = self.amu._handle()
+        return L, self._q
+
+    def _affine(self, sol_aff, dirs_aff):
+        bar = self.layer
+        return (bar._vec(sol_aff, bar.n, "sol_aff"), *bar._dirs(dirs_aff))
+
+    def reset(self):
+        """A new solve (``iem_mpc_reset``, asynchronous): the block zero."""
+        L, q = self._handle()
+        _lib.check(L.iem_mpc_reset(q))
+
+    def bind_mu(self, param=None):
+        """While bound to the :class:`BarrierParameter` under ``amu`` (``iem_mpc_bind_mu``), :meth:`terms` and :meth:`step` read
+        ``mu`` and ``tau`` from its block on the device; their ``mu`` / ``tau`` arguments are ignored.  ``None`` unbinds."""
+        L, q = self._handle()
+        _lib.check(L.iem_mpc_bind_mu(q, param._handle()[1] if param is not None else None))
+
+    def terms(self, state, r, c, sol_aff, dirs_aff, mu: float = 0.0, out=None):
+        """The two right-hand-side columns as one ``(2, n)`` device tensor (``iem_mpc_terms``): row 0 is ``BarrierLayer.terms``'s
+        ``rhs`` at that ``mu`` bit for bit, row 1 has ``mu − Δgap_aff·Δz_aff`` per bound in the place of ``mu``.  ``sigma`` and
+        ``dcon`` are not written: they are those of the affine ``terms`` call."""
+        bar = self.layer
+        out = out if out is not None else bar._torch.empty((2, bar.n), dtype=bar._torch.float64, device=bar.model.device)
+        if tuple(out.shape) != (2, bar.n) or out.stride(1) != 1 or out.stride(0) < bar.n or out.dtype != bar._torch.float64:
+            raise ValueError(f"out: a float64 tensor of shape (2, {bar.n}) with contiguous rows expected")
+        ps = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(c, bar.ncon, "c"), *self._affine(sol_aff, dirs_aff), float(mu), C.c_void_p(out.data_ptr()), int(out.stride(0)))
+        L, q = self._handle()
+        _lib.check(L.iem_mpc_terms(q, *ps, *args))
+        return out
+
+    def step(self, state, sol_aff, dirs_aff, sol_c, mu: float = 0.0, tau: float = 1.0, out=None, alpha=None):
+        """``((ds, dzL, dzU, dvL, dvU), alpha_c)`` of the corrected solution ``sol_c`` (``iem_mpc_step``): ``BarrierLayer.step`` with
+        the per-bound target in the place of ``mu``."""
+        bar = self.layer
+        dirs = out if out is not None else (bar._new(bar.ncon), bar._new(bar.nvar), bar._new(bar.nvar), bar._new(bar.ncon), bar._new(bar.ncon))
+        alpha = alpha if alpha is not None else bar._new(2)
+        ps, d = bar._state(state), bar._dirs(dirs)
+        args = (*self._affine(sol_aff, dirs_aff), bar._vec(sol_c, bar.n, "sol_c"), float(mu), float(tau), *d, bar._vec(alpha, 2, "alpha"))
+        L, q = self._handle()
+        _lib.check(L.iem_mpc_step(q, *ps, *args))
+        return dirs, alpha
+
+    def select(self, probe4, alpha_c, sol_c, dirs_c, sol, dirs, alpha):
+        """The safeguard's decision on the device (``iem_mpc_select``) from the four words of ``amu.probe`` on the corrected
+        direction: taken, ``sol_c``, ``dirs_c`` and ``alpha_c`` are copied over ``sol``, ``dirs`` and ``alpha``; refused, nothing
+        moves.  Returns ``(sol, dirs, alpha)``."""
+        bar = self.layer
+        src, dst = bar._dirs(dirs_c), bar._dirs(dirs)
+        args = (bar._vec(probe4, 4, "probe4"), bar._vec(alpha_c, 2, "alpha_c"), bar._vec(sol_c, bar.n, "sol_c"), *src, bar._vec(sol, bar.n, "sol"), *dst,
+                bar._vec(alpha, 2, "alpha"))
+        L, q = self._handle()
+        _lib.check(L.iem_mpc_select(q, *args))
+        return sol, dirs, alpha
+
+    def state(self):
+        """THE read-back (``iem_mpc_state``, synchronises once): ``taken`` (the last decision), ``n_taken``, ``n_refused``,
+        ``predicted``, ``avg``, ``alpha_c``."""
+        L, q = self._handle()
+        v = _lib.MpcState()
+        v.struct_size = C.sizeof(_lib.MpcState)
+        _lib.check(L.iem_mpc_state(q, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.MpcState._fields_ if name not in ("struct_size", "alpha_c")}
+        out["taken"] = bool(out["taken"])
+        out["alpha_c"] = [float(v.alpha_c[0]), float(v.alpha_c[1])]
+        return out
+
+    def device(self):
+        """The address of the object's own block (16 words) on the device (``iem_mpc_device``)."""
+        L, q = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_mpc_device(q, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        if self._q is not None:
+            _lib.check(self.layer.model._L.iem_mpc_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.amu._a is not None and self.par._p is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
 class Restoration:
     """``Restoration(search, rho=1000, kappa_resto=0.9, bound_mult_reset_threshold=1000)``: the feasibility restoration phase of the
     C-ABI (``iem_resto_*``, ``csrc/iem_resto_device.h``) beside the :class:`FilterSearch` of the ORIGINAL problem — the elastic

@@ -70,6 +70,9 @@ static const char *kAmuSource =           // the adaptive barrier parameter (iem
 static const char *kQfSource =            // the quality-function oracle (iem_qf_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_qf_device_h.inc"
     ;
+static const char *kMpcSource =           // Mehrotra's corrector (iem_mpc_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_mpc_device_h.inc"
+    ;
 
 namespace {
 
@@ -340,6 +343,7 @@ struct iem_model {
   struct MuObject { hipModule_t mod = nullptr; hipFunction_t error = nullptr, update = nullptr, reset = nullptr; } mu;
   struct AmuObject { hipModule_t mod = nullptr; hipFunction_t probe = nullptr, update = nullptr, reset = nullptr; } amu;      // the adaptive rule (iem_amu_*): loaded by the first iem_amu_create
   struct QfObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, alpha = nullptr, value = nullptr, update = nullptr, reset = nullptr; } qf;      // the quality-function oracle (iem_qf_*): loaded by the first iem_qf_create
+  struct MpcObject { hipModule_t mod = nullptr; hipFunction_t terms = nullptr, step = nullptr, select = nullptr, reset = nullptr; } mpc;      // Mehrotra's corrector (iem_mpc_*): loaded by the first iem_mpc_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1385,6 +1389,7 @@ int iem_destroy(iem_model *m) {
   if (m->mu.mod) hipModuleUnload(m->mu.mod);
   if (m->amu.mod) hipModuleUnload(m->amu.mod);
   if (m->qf.mod) hipModuleUnload(m->qf.mod);
+  if (m->mpc.mod) hipModuleUnload(m->mpc.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -5455,6 +5460,207 @@ int iem_qf_state(iem_qf *q, iem_mu_state_t *mu_out, iem_amu_state_t *amu_out, ie
   t.struct_size = std::min<uint64_t>(out->struct_size, sizeof t);
   std::memcpy(&t.status, w + 32, 27 * 8);
   std::memcpy(out, &t, (size_t)t.struct_size);
+  return IEM_OK;
+}
+
+/* ---- Mehrotra's corrector: the two-column right-hand side, the corrected directions and step lengths, the safeguard's decision (csrc/iem_mpc_device.h) ---- */
+struct iem_mpc {
+  iem_amu *a = nullptr;                // the object whose affine direction it completes (borrowed), on its iem_mu
+  iem_mpc_opts_t opt;
+  double *d_blk = nullptr;             // the own block: 16 words
+  const double *mu_blk = nullptr;      // iem_mpc_bind_mu: the block of the iem_mu object (borrowed), or null
+};
+
+namespace {
+// MpcArgs of csrc/iem_mpc_device.h
+struct MpcArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c;
+  const double *sol_a, *ds_a, *dzL_a, *dzU_a, *dvL_a, *dvU_a;
+  const double *sol;
+  double *ds, *dzL, *dzU, *dvL, *dvU;
+  double *rhs0, *rhs1;
+  unsigned long long *alpha;
+  const double *probe;
+  double *o_sol, *o_ds, *o_dzL, *o_dzU, *o_dvL, *o_dvU, *o_alpha;
+  const double *mblk;
+  const double *ablk;
+  double *blk;
+  double mu, tau, red_fact;
+  long long nz;
+  long long nvar, n;
+};
+MpcArgsH mpc_args(const iem_mpc *q) {
+  const iem_barrier *b = q->a->p->b;
+  MpcArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.mblk = q->mu_blk; A.ablk = q->a->d_blk; A.blk = q->d_blk;
+  A.red_fact = q->opt.red_fact;
+  A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon);
+  return A;
+}
+int mpc_object(iem_model *m) {
+  iem_model::MpcObject &o = m->mpc;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kMpcSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[4] = {KernelSlot{"mpc_terms", &o.terms}, KernelSlot{"mpc_step", &o.step}, KernelSlot{"mpc_select", &o.select}, KernelSlot{"mpc_reset", &o.reset}};
+  return load_object(m, src, slots, 4, &o.mod);
+}
+int mpc_opts(const iem_mpc_opts_t *in, iem_mpc_opts_t *out) {
+  iem_mpc_opts_t v = {sizeof v, 1.0};      // Ipopt's corrector_compl_avrg_red_fact
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_mpc_create: set struct_size to sizeof(iem_mpc_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  if (!std::isfinite(v.red_fact) || !(v.red_fact > 0.0)) return fail(IEM_E_ARG, "iem_mpc_create: red_fact must be positive and finite");
+  *out = v;
+  return IEM_OK;
+}
+// the affine direction a call needs: dx, dzL, dzU with variables, ds, dvL, dvU with inequality rows
+bool mpc_affine_missing(const iem_barrier *b, const double *sol, const double *ds, const double *dzL, const double *dzU, const double *dvL, const double *dvU) {
+  return !sol || (b->nvar && (!dzL || !dzU)) || (b->n_ineq && (!ds || !dvL || !dvU));
+}
+}  // namespace
+
+int iem_mpc_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kMpcSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_mpc_destroy(iem_mpc *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->a->p->b->m->device);
+  if (q->d_blk) hipFree(q->d_blk);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_mpc_create(iem_amu *a, const iem_mpc_opts_t *opts, iem_mpc **out) {
+  if (!a || !out) return fail(IEM_E_ARG, "null argument");
+  iem_mpc_opts_t opt;
+  {
+    int rc = mpc_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_model *m = a->p->b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = mpc_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_mpc *q) const { iem_mpc_destroy(q); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_mpc, Drop> q(new iem_mpc);
+  q->a = a;
+  q->opt = opt;
+  HIP_TRY(hipMalloc((void **)&q->d_blk, 16 * 8));
+  HIP_TRY(hipMemset(q->d_blk, 0, 16 * 8));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_mpc_reset(iem_mpc *q) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->a->p->b->m;
+  DevGuard dg_(m->device);
+  MpcArgsH A = mpc_args(q);
+  return kkt_launch_raw(m, m->mpc.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_mpc_bind_mu(iem_mpc *q, const iem_mu *p) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (p && p != q->a->p) return fail(IEM_E_ARG, "iem_mpc_bind_mu: not the iem_mu object this corrector was created on");
+  q->mu_blk = p ? p->d_blk : nullptr;
+  return IEM_OK;
+}
+
+int iem_mpc_terms(iem_mpc *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                  const double *d_vU, const double *d_r, const double *d_c, const double *d_sol_aff, const double *d_ds_aff, const double *d_dzL_aff,
+                  const double *d_dzU_aff, const double *d_dvL_aff, const double *d_dvU_aff, double mu, double *d_rhs2, int64_t ld) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (!q->mu_blk && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_mpc_terms: mu must not be negative");
+  const iem_barrier *b = q->a->p->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->nvar && !d_r) || (b->ncon && !d_c) || !d_rhs2 ||
+      mpc_affine_missing(b, d_sol_aff, d_ds_aff, d_dzL_aff, d_dzU_aff, d_dvL_aff, d_dvU_aff))
+    return fail(IEM_E_ARG, "null argument");
+  if (ld < b->nvar + b->ncon) return fail(IEM_E_ARG, "iem_mpc_terms: ld must be at least nvar + ncon");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  MpcArgsH A = mpc_args(q);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU; A.r = d_r; A.c = d_c;
+  A.sol_a = d_sol_aff; A.ds_a = d_ds_aff; A.dzL_a = d_dzL_aff; A.dzU_a = d_dzU_aff; A.dvL_a = d_dvL_aff; A.dvU_a = d_dvU_aff;
+  A.mu = mu; A.rhs0 = d_rhs2; A.rhs1 = d_rhs2 + ld;
+  return kkt_launch_raw(m, m->mpc.terms, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_mpc_step(iem_mpc *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                 const double *d_vU, const double *d_sol_aff, const double *d_ds_aff, const double *d_dzL_aff, const double *d_dzU_aff,
+                 const double *d_dvL_aff, const double *d_dvU_aff, const double *d_sol_c, double mu, double tau, double *d_ds_c, double *d_dzL_c,
+                 double *d_dzU_c, double *d_dvL_c, double *d_dvU_c, double *d_alpha_c) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (!q->mu_blk && !(mu >= 0.0)) return fail(IEM_E_ARG, "iem_mpc_step: mu must not be negative");
+  if (!q->mu_blk && !(tau > 0.0 && tau <= 1.0)) return fail(IEM_E_ARG, "iem_mpc_step: tau must lie in (0, 1]");
+  const iem_barrier *b = q->a->p->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || !d_sol_c || !d_alpha_c ||
+      mpc_affine_missing(b, d_sol_aff, d_ds_aff, d_dzL_aff, d_dzU_aff, d_dvL_aff, d_dvU_aff) ||
+      mpc_affine_missing(b, d_sol_c, d_ds_c, d_dzL_c, d_dzU_c, d_dvL_c, d_dvU_c))
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  MpcArgsH A = mpc_args(q);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  A.sol_a = d_sol_aff; A.ds_a = d_ds_aff; A.dzL_a = d_dzL_aff; A.dzU_a = d_dzU_aff; A.dvL_a = d_dvL_aff; A.dvU_a = d_dvU_aff;
+  A.sol = d_sol_c; A.mu = mu; A.tau = tau; A.ds = d_ds_c; A.dzL = d_dzL_c; A.dzU = d_dzU_c; A.dvL = d_dvL_c; A.dvU = d_dvU_c;
+  A.alpha = (unsigned long long *)d_alpha_c;
+  // the seed: the bits of 1.0 (the barrier object's; a device-to-device copy is a capturable node)
+  HIP_TRY(hipMemcpyAsync(d_alpha_c, b->d_ones, 16, hipMemcpyDeviceToDevice, m->stream));
+  return kkt_launch_raw(m, m->mpc.step, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_mpc_select(iem_mpc *q, const double *d_probe4, const double *d_alpha_c, const double *d_sol_c, const double *d_ds_c, const double *d_dzL_c,
+                   const double *d_dzU_c, const double *d_dvL_c, const double *d_dvU_c, double *d_sol, double *d_ds, double *d_dzL, double *d_dzU,
+                   double *d_dvL, double *d_dvU, double *d_alpha) {
+  if (!q || !d_probe4 || !d_alpha_c || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->a->p->b;
+  if (mpc_affine_missing(b, d_sol_c, d_ds_c, d_dzL_c, d_dzU_c, d_dvL_c, d_dvU_c) || mpc_affine_missing(b, d_sol, d_ds, d_dzL, d_dzU, d_dvL, d_dvU))
+    return fail(IEM_E_ARG, "null argument");
+  if (d_alpha == d_alpha_c) return fail(IEM_E_ARG, "iem_mpc_select: d_alpha and d_alpha_c must be two buffers (every thread reads the one while one thread writes the other)");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  MpcArgsH A = mpc_args(q);
+  A.probe = d_probe4; A.alpha = (unsigned long long *)d_alpha_c;
+  A.sol = d_sol_c; A.ds = (double *)d_ds_c; A.dzL = (double *)d_dzL_c; A.dzU = (double *)d_dzU_c; A.dvL = (double *)d_dvL_c; A.dvU = (double *)d_dvU_c;
+  A.o_sol = d_sol; A.o_ds = d_ds; A.o_dzL = d_dzL; A.o_dzU = d_dzU; A.o_dvL = d_dvL; A.o_dvU = d_dvU; A.o_alpha = d_alpha;
+  return kkt_launch_raw(m, m->mpc.select, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_mpc_device(const iem_mpc *q, double **d_block) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = q->d_blk;
+  return IEM_OK;
+}
+
+int iem_mpc_state(iem_mpc *q, iem_mpc_state_t *out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_mpc_state: set struct_size to sizeof(iem_mpc_state_t) before the call");
+  iem_model *m = q->a->p->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[16];
+  HIP_TRY(hipMemcpyAsync(w, q->d_blk, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_mpc_state_t v;
+  static_assert(sizeof v == 8 * 8, "iem_mpc_state_t: struct_size, then words 0-6 of the own block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.taken, w, 7 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
   return IEM_OK;
 }
 

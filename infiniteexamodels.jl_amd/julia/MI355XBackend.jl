@@ -854,6 +854,73 @@ function qf_device(o::QualityFunction)
     return p[]
 end
 
+# ---- Mehrotra's corrector (include/iem.h: iem_mpc_*) -----------------------------------------------------------------------------------
+# The second-order term of the complementarity equations on the right-hand side, ON an AdaptiveBarrierParameter.  Per iteration, BEHIND
+# amu_update! (or qf_update!), with the objects bound again: mpc_terms! (two columns: column 0 is barrier_terms!' rhs, column 1 carries
+# mu − dgap_aff·dz_aff per bound); ONE two-column back-solve on the iteration's factors; barrier_step! on column 0; mpc_step! on column 1;
+# amu_probe! on the corrected direction at alpha_c; mpc_select! — taken, the corrected direction is copied over the first-order one;
+# mpc_state — the one read-back.  aff = (sol, ds, dzL, dzU, dvL, dvU) of the affine step.  Finalize (or let go of) the corrector before its
+# AdaptiveBarrierParameter.  UNEXECUTED, like the rest.
+struct IemMpcOpts          # iem_mpc_opts_t
+    struct_size::UInt64
+    red_fact::Float64
+end
+struct IemMpcState         # iem_mpc_state_t: words 0-6 of the object's own block
+    struct_size::UInt64
+    taken::Int64; n_taken::Int64; n_refused::Int64
+    predicted::Float64; avg::Float64
+    alpha_c::NTuple{2, Float64}
+end
+mutable struct MehrotraCorrector
+    q::Ptr{Cvoid}
+    amu::AdaptiveBarrierParameter      # borrowed: kept alive
+end
+function MehrotraCorrector(o::AdaptiveBarrierParameter; red_fact = 1.0)
+    opts = Ref(IemMpcOpts(sizeof(IemMpcOpts), red_fact))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_mpc_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMpcOpts}, Ptr{Ptr{Cvoid}}), o.a, opts, q))
+    mpc = MehrotraCorrector(q[], o)
+    finalizer(x -> (x.q == C_NULL || x.amu.a == C_NULL || ccall((:iem_mpc_destroy, LIBIEM), Cint, (Ptr{Cvoid},), x.q); x.q = C_NULL), mpc)
+    return mpc
+end
+# a new solve: the block zero (asynchronous)
+mpc_reset!(o::MehrotraCorrector) = check(ccall((:iem_mpc_reset, LIBIEM), Cint, (Ptr{Cvoid},), o.q))
+# bound, mpc_terms! and mpc_step! read mu and tau from the parameter's block; nothing unbinds
+bind_mu!(o::MehrotraCorrector, q) = check(ccall((:iem_mpc_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), o.q, _mu_handle(q)))
+_mpc_aff(aff) = (dptr(aff[1]), spptr(aff[2]), spptr(aff[3]), spptr(aff[4]), spptr(aff[5]), spptr(aff[6]))
+# rhs2: 2·ld doubles on the device, column u at offset u·ld (ld >= nvar + ncon): the layout of solve_refined!
+function mpc_terms!(o::MehrotraCorrector, state, r, c, aff, rhs2, ld; mu = 0.0)
+    check(ccall((:iem_mpc_terms, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 15)..., Cdouble, Ptr{Float64}, Int64),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]),
+                dptr(r), spptr(c), _mpc_aff(aff)..., mu, dptr(rhs2), ld))
+    return rhs2
+end
+# sol_c: the corrected solution (column 1 of the solve); dirs_c = (ds, dzL, dzU, dvL, dvU) and alpha_c (two doubles) on the device
+function mpc_step!(o::MehrotraCorrector, state, aff, sol_c, dirs_c, alpha_c; mu = 0.0, tau = 1.0)
+    check(ccall((:iem_mpc_step, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 14)..., Cdouble, Cdouble, ntuple(_ -> Ptr{Float64}, 6)...),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]),
+                _mpc_aff(aff)..., dptr(sol_c), mu, tau, spptr(dirs_c[1]), spptr(dirs_c[2]), spptr(dirs_c[3]), spptr(dirs_c[4]), spptr(dirs_c[5]), dptr(alpha_c)))
+    return dirs_c, alpha_c
+end
+# probe4: the four of amu_probe! on the corrected direction; taken: (sol_c, dirs_c, alpha_c) over (sol, dirs, alpha)
+function mpc_select!(o::MehrotraCorrector, probe4, alpha_c, sol_c, dirs_c, sol, dirs, alpha)
+    check(ccall((:iem_mpc_select, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 15)...),
+                o.q, dptr(probe4), dptr(alpha_c), dptr(sol_c), spptr(dirs_c[1]), spptr(dirs_c[2]), spptr(dirs_c[3]), spptr(dirs_c[4]), spptr(dirs_c[5]),
+                dptr(sol), spptr(dirs[1]), spptr(dirs[2]), spptr(dirs[3]), spptr(dirs[4]), spptr(dirs[5]), dptr(alpha)))
+end
+# the one read-back (synchronises the stream once)
+function mpc_state(o::MehrotraCorrector)
+    own = Ref(IemMpcState(sizeof(IemMpcState), 0, 0, 0, 0.0, 0.0, (0.0, 0.0)))
+    check(ccall((:iem_mpc_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemMpcState}), o.q, own))
+    return own[]
+end
+# the own block (16 words of 8 bytes) as a device address
+function mpc_device(o::MehrotraCorrector)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_mpc_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.q, p))
+    return p[]
+end
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
