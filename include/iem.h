@@ -1388,6 +1388,88 @@ int iem_mpc_state(iem_mpc *q, iem_mpc_state_t *out);      /* synchronises the st
 /* HIP source of the four kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_mpc_source(char **out_src, uint64_t *out_key);
 
+/* ---- the starting point: least-squares multipliers and the warm start --------------------------------------------------------------------
+ * What stands in front of the first iteration (csrc/iem_init_device.h), as an object created ON an iem_barrier whose bounds, flags and
+ * grid it borrows: Ipopt's default initialiser of the row multipliers (DefaultIterateInitializer::least_square_mults with
+ * constr_mult_init_max) behind iem_barrier_start for a COLD start, and in the place of iem_barrier_start for a WARM start the
+ * projection of a given primal-dual point (Ipopt's WarmStartIterateInitializer: warm_start_bound_push, warm_start_bound_frac,
+ * warm_start_mult_bound_push, warm_start_mult_init_max) with a barrier parameter taken from that point's complementarity.
+ *
+ * Entry order and flags (fx / fc) are those of iem_barrier_terms: one thread takes the entries i, i + stride, ... of
+ * [0, nvar + ncon); nothing is read where no bound is present; entries of s, vL, vU on equality rows are neither read nor written.
+ * Each operation is rounded once, in the order written here.
+ *
+ * THE LEAST-SQUARES ESTIMATE.  With grad f + J'y − zL + zU = 0 and −y − vL + vU = 0 on inequality rows, y_new = y + delta minimises
+ *         ‖r + J'delta − zL + zU‖² + ‖−(y + delta) − vL + vU‖² (the second term over inequality rows),
+ *     r = obj_weight·grad f + J'y as iem_eval_residual writes it (at y = 0: the gradient).  Its normal equations are the existing K
+ *     with a ZERO Hessian value array, sigma = 1, dcon = 1 on inequality rows and 0 on equality rows, delta_w = 0:
+ *         [I, J'; J, −diag(dcon + delta_c)] [w; delta] = [−(r − zL + zU); t + y (inequality rows), 0 (equality rows)],
+ *         t = (lower ? vL : 0) − (upper ? vU : 0).
+ * iem_init_ls_terms: ONE launch on the barrier object's grid.  variables: sigma = 1.0;  a = r − zL (lower bound present);
+ *     a = a + zU (upper bound present);  rhs = −a.  equality rows: dcon = +0.0, rhs = +0.0.  inequality rows: dcon = 1.0,
+ *     t = (lower ? vL : +0.0) − (upper ? vU : +0.0);  rhs = y + t.  The caller assembles with a zeroed hess array
+ *     (iem_kkt_assemble_diag(k, zeros, jac, sigma, dcon, 0, delta_c)), factors and solves with the existing calls; the refined solve
+ *     stays matrix-free at (x, y = 0, obj_weight = 0), where the Hessian of the Lagrangian is zero.
+ * iem_init_ls_apply: an 8-byte device-to-device copy (the seed of the maximum, +0.0) and at most two launches on the same grid.  The norm:
+ *     yn = y + sol[nvar + j] over ALL rows, ynorm = max |yn| as an integer maximum on the bit patterns — order-independent, a NaN
+ *     wins, at most one atomic per workgroup; without rows it is +0.0 and this launch is left out.  The apply: every thread reads
+ *     ynorm; ACCEPTED iff ynorm <= y_max (a NaN compares false).  Accepted: y = yn.  Rejected with on_reject = 0: y = +0.0 (Ipopt's
+ *     initialiser); with on_reject = 1 the call returns before its first store to y (Ipopt's recalc_y use).  sol's x part is never
+ *     read.  One thread writes words 0–3 of the own block.
+ * iem_init_warm: ONE launch, in place.  x takes the projection of iem_barrier_start with (warm_push, warm_frac) in the place of
+ *     (bound_push, bound_frac) — with equal constants the bits of iem_barrier_start — and s on inequality rows the same projection
+ *     of THE GIVEN s (not of c).  Each present bound multiplier (zL, zU; vL, vU on inequality rows):
+ *         z = (z > warm_z_push) ? z : warm_z_push   (a NaN becomes the push);   z = (z < warm_z_max) ? z : warm_z_max;
+ *     each absent one becomes +0.0.  Every row's y:  y = NaN ? +0.0 : (y < −warm_y_max) ? −warm_y_max : (y > warm_y_max) ? warm_y_max : y.
+ * iem_init_mu(q, w12, p): ONE workgroup of 64 threads, one thread decides.  w12: the twelve words of iem_mu_error at the warm state;
+ *     nz of iem_barrier_info.  If nz == 0, or w[10] != 0, or avg = w[9]/nz is a NaN or not > 0:  mu0 = p's mu_init (word 5 = 1).
+ *     Otherwise t = mu_factor·avg;  mu0 = t (word 5 = 0);  t > cap: mu0 = cap (3);  then mu0 < mu_floor: mu0 = mu_floor (2) — cap =
+ *     mu_cap, or p's mu_init where mu_cap is 0; mu_floor that of p.  Words 0–2 and 8–11 of p's block are then written bit for bit as
+ *     iem_mu_reset(p, mu0) writes them (mu0, max(tau_min, 1 − mu0), sqrt(mu0); status ITERATING, flags and counters 0); words 3–7
+ *     stay.  The objects bound to p read the new mu with their next launch; iem_amu / iem_qf / iem_search keep their own resets.
+ * THE OWN BLOCK: sixteen 8-byte words on the device (iem_init_device gives the pointer; iem_init_state_t mirrors words 0–5):
+ *     0 ynorm of the last iem_init_ls_apply      1 its decision (int64): 1 accepted, 0 rejected      2 estimates accepted so far (int64)
+ *     3 rejected so far (int64)      4 the mu0 last written by iem_init_mu      5 how it was chosen (int64): 0 from the average,
+ *     1 fallback to mu_init, 2 clamped below, 3 clamped above      6–15 zero
+ *     iem_init_create zeroes it; iem_init_reset (one launch of one workgroup of 64 threads, asynchronous) does the same.
+ * iem_init_state: the one read-back (one synchronisation).
+ * Every other call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  No float atomic, no
+ * cooperative launch.  IEM_E_ARG before any device work: null required pointers (s, vL, vU may be NULL without inequality rows; y,
+ * dcon without rows), an option that is not finite or outside its range (below), an iem_mu of another barrier object.  The object
+ * borrows the iem_barrier object: destroy it first.  Not here: the delta_w / inertia retry, Ipopt's least_square_init_primal and
+ * least_square_init_duals, bound_mult_init_method = mu-based, warm_start_target_mu and warm_start_entire_iterate, a warm start of
+ * iem_resto, sharded handles.  iem_barrier_start is unchanged. */
+typedef struct iem_init iem_init;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_init_opts_t) */
+  double y_max;                         /* 1e3 (Ipopt's constr_mult_init_max); >= 0 */
+  int64_t on_reject;                    /* 0: a rejected estimate writes y = +0.0; 1: it keeps y */
+  double warm_push, warm_frac;          /* 1e-3, 1e-3; > 0, in (0, 0.5] */
+  double warm_z_push, warm_z_max;       /* 1e-3, 1e6; > 0, >= warm_z_push */
+  double warm_y_max;                    /* 1e6; > 0 */
+  double mu_factor;                     /* 1.0; > 0 */
+  double mu_cap;                        /* 0 = the mu_init of the iem_mu object handed to iem_init_mu; >= 0 */
+} iem_init_opts_t;                      /* NULL = the defaults */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_init_state_t): at most that many bytes are written */
+  double ynorm;                         /* word 0 */
+  int64_t accepted, n_accepted, n_rejected;      /* words 1–3 */
+  double mu0;                           /* word 4 */
+  int64_t how;                          /* word 5 */
+} iem_init_state_t;
+int iem_init_create(iem_barrier *b, const iem_init_opts_t *opts, iem_init **out);
+int iem_init_destroy(iem_init *q);
+int iem_init_reset(iem_init *q);
+int iem_init_ls_terms(iem_init *q, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU, const double *d_r,
+                      double *d_sigma, double *d_dcon, double *d_rhs);
+int iem_init_ls_apply(iem_init *q, const double *d_sol, double *d_y);
+int iem_init_warm(iem_init *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU);
+int iem_init_mu(iem_init *q, const double *d_out12 /* of iem_mu_error */, iem_mu *p);
+int iem_init_device(const iem_init *q, double **d_block);
+int iem_init_state(iem_init *q, iem_init_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the six kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_init_source(char **out_src, uint64_t *out_key);
+
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache

@@ -930,6 +930,123 @@ class MehrotraCorrector:
             pass
 
 
+class StartingPoint:
+    """``StartingPoint(layer, **opts)``: the starting point of the C-ABI (``iem_init_*``, ``csrc/iem_init_device.h``) ON a
+    :class:`BarrierLayer` — Ipopt's least-squares estimate of the row multipliers for a cold start, and for a warm start the
+    projection of a given primal-dual point with a barrier parameter taken from its complementarity.  ``opts``: ``y_max, on_reject,
+    warm_push, warm_frac, warm_z_push, warm_z_max, warm_y_max, mu_factor, mu_cap`` (``include/iem.h`` has ranges and defaults).
+
+    A cold start, behind ``state = bar.start(x, model.cons(x))``, with ``r`` of ``model.eval_residual(x, y, 1.0)``:
+
+        sigma, dcon, rhs = init.ls_terms(state, r)                     # sigma = 1; dcon = 1 on inequality rows
+        kkt.assemble(zeros_h, jv, sigma, 0.0, delta_c, dcon=dcon, at=(x, zeros_y, 0.0))      # a ZERO Hessian: W = 0 at (y = 0, obj_weight = 0)
+        kkt.factor(); sol = kkt.solve(rhs, refine=1)
+        init.ls_apply(sol, state[2])                                   # y += sol[nvar:] where max |y| <= y_max, else y = 0
+
+    A warm start from a previous solution (x, s, y, zL, zU, vL, vU), in the place of ``bar.start``:
+
+        init.warm(state)                                               # in place: the push, the clamps
+        w = par.error(state, r, c)                                     # r, c at the pushed point
+        init.mu(w, par)                                                # mu0 into par's block: every bound object reads it
+
+    Nothing above reads a value back; :meth:`state` is the only place that does."""
+
+    def __init__(self, layer: BarrierLayer, **opts):
+        self.layer = layer
+        self._q = None
+        o = _lib.InitOpts.defaults(**opts)
+        L, b = layer._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_init_create(b, C.byref(o), C.byref(q)))
+        self._q = q
+        self.opts = {name: getattr(o, name) for name, _ in _lib.InitOpts._fields_ if name != "struct_size"}
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("StartingPoint: closed")
+        L, _ = self.layer._handle()
+        return L, self._q
+
+    def reset(self):
+        """A new solve (``iem_init_reset``, asynchronous): the block zero.  Returns ``self``."""
+        L, q = self._handle()
+        _lib.check(L.iem_init_reset(q))
+        return self
+
+    def ls_terms(self, state, r, out=None):
+        """``(sigma, dcon, rhs)`` of the least-squares estimate at ``state`` (``iem_init_ls_terms``; ``x`` and ``s`` are not read):
+        exactly the inputs of ``KKTObject.assemble`` with a zeroed Hessian value array and of ``solve``."""
+        bar = self.layer
+        sigma, dcon, rhs = out if out is not None else (bar._new(bar.nvar), bar._new(bar.ncon), bar._new(bar.n))
+        p = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(sigma, bar.nvar, "sigma"), bar._vec(dcon, bar.ncon, "dcon"), bar._vec(rhs, bar.n, "rhs"))
+        L, q = self._handle()
+        _lib.check(L.iem_init_ls_terms(q, *p[2:], *args))
+        return sigma, dcon, rhs
+
+    def ls_apply(self, sol, y):
+        """``y += sol[nvar:]`` IN PLACE where ``max |y + sol[nvar:]| <= y_max``; otherwise ``y = 0`` (``on_reject = 0``) or ``y`` as it
+        was (``on_reject = 1``) — decided on the device (``iem_init_ls_apply``).  Returns ``y``."""
+        bar = self.layer
+        args = (bar._vec(sol, bar.n, "sol"), bar._vec(y, bar.ncon, "y"))
+        L, q = self._handle()
+        _lib.check(L.iem_init_ls_apply(q, *args))
+        return y
+
+    def warm(self, state):
+        """The warm-start projection of ``state = (x, s, y, zL, zU, vL, vU)`` IN PLACE (``iem_init_warm``).  Returns ``state``."""
+        p = self.layer._state(state)
+        L, q = self._handle()
+        _lib.check(L.iem_init_warm(q, *p))
+        return state
+
+    def mu(self, w12, par):
+        """The barrier parameter of a warm start into the block of the :class:`BarrierParameter` ``par`` (``iem_init_mu``), from the
+        twelve words ``w12 = par.error(state, r, c)`` at the warm state.  Returns ``self``."""
+        pw = self.layer._vec(w12, 12, "w12")
+        L, q = self._handle()
+        _lib.check(L.iem_init_mu(q, pw, par._handle()[1]))
+        return self
+
+    def state(self):
+        """THE read-back (``iem_init_state``, synchronises once): ``ynorm``, ``accepted`` (the last decision), ``n_accepted``,
+        ``n_rejected``, ``mu0``, ``how`` and ``how_name``."""
+        L, q = self._handle()
+        v = _lib.InitState()
+        v.struct_size = C.sizeof(_lib.InitState)
+        _lib.check(L.iem_init_state(q, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.InitState._fields_ if name != "struct_size"}
+        out["accepted"] = bool(out["accepted"])
+        out["how_name"] = _lib.INIT_HOW[out["how"]] if 0 <= out["how"] < len(_lib.INIT_HOW) else "?"
+        return out
+
+    def device(self):
+        """The address of the object's own block (16 words) on the device (``iem_init_device``)."""
+        L, q = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_init_device(q, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        if self._q is not None:
+            _lib.check(self.layer.model._L.iem_init_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
 class Restoration:
     """``Restoration(search, rho=1000, kappa_resto=0.9, bound_mult_reset_threshold=1000)``: the feasibility restoration phase of the
     C-ABI (``iem_resto_*``, ``csrc/iem_resto_device.h``) beside the :class:`FilterSearch` of the ORIGINAL problem — the elastic

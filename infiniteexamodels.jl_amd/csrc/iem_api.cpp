@@ -73,6 +73,9 @@ static const char *kQfSource =            // the quality-function oracle (iem_qf
 static const char *kMpcSource =           // Mehrotra's corrector (iem_mpc_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_mpc_device_h.inc"
     ;
+static const char *kInitSource =          // the starting point (iem_init_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_init_device_h.inc"
+    ;
 
 namespace {
 
@@ -344,6 +347,7 @@ struct iem_model {
   struct AmuObject { hipModule_t mod = nullptr; hipFunction_t probe = nullptr, update = nullptr, reset = nullptr; } amu;      // the adaptive rule (iem_amu_*): loaded by the first iem_amu_create
   struct QfObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, alpha = nullptr, value = nullptr, update = nullptr, reset = nullptr; } qf;      // the quality-function oracle (iem_qf_*): loaded by the first iem_qf_create
   struct MpcObject { hipModule_t mod = nullptr; hipFunction_t terms = nullptr, step = nullptr, select = nullptr, reset = nullptr; } mpc;      // Mehrotra's corrector (iem_mpc_*): loaded by the first iem_mpc_create
+  struct InitObject { hipModule_t mod = nullptr; hipFunction_t ls_terms = nullptr, ls_norm = nullptr, ls_apply = nullptr, warm = nullptr, mu = nullptr, reset = nullptr; } init;      // the starting point (iem_init_*): loaded by the first iem_init_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1390,6 +1394,7 @@ int iem_destroy(iem_model *m) {
   if (m->amu.mod) hipModuleUnload(m->amu.mod);
   if (m->qf.mod) hipModuleUnload(m->qf.mod);
   if (m->mpc.mod) hipModuleUnload(m->mpc.mod);
+  if (m->init.mod) hipModuleUnload(m->init.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -5660,6 +5665,200 @@ int iem_mpc_state(iem_mpc *q, iem_mpc_state_t *out) {
   static_assert(sizeof v == 8 * 8, "iem_mpc_state_t: struct_size, then words 0-6 of the own block");
   v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
   std::memcpy(&v.taken, w, 7 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+/* ---- the starting point: least-squares multipliers, the warm-start projection and its barrier parameter (csrc/iem_init_device.h) ---- */
+struct iem_init {
+  iem_barrier *b = nullptr;            // the object whose bounds, flags and grid it uses (borrowed)
+  iem_init_opts_t opt;
+  double *d_blk = nullptr;             // the own block: 16 words, then the slot of ynorm's bits and a word that stays +0.0 (the slot's seed)
+};
+
+namespace {
+// InitArgs of csrc/iem_init_device.h
+struct InitArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r;
+  const double *sol;
+  double *sigma, *dcon, *rhs;
+  unsigned long long *slot;
+  const double *w;
+  double *mblk;
+  double *blk;
+  double y_max, push, frac, z_push, z_max, y_clip, mu_factor, cap;
+  double mu_init, mu_floor, tau_min;
+  long long on_reject, nz;
+  long long nvar, n;
+};
+InitArgsH init_args(const iem_init *q) {
+  const iem_barrier *b = q->b;
+  InitArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  A.blk = q->d_blk; A.slot = (unsigned long long *)(q->d_blk + 16);
+  A.y_max = q->opt.y_max; A.on_reject = (long long)q->opt.on_reject;
+  A.push = q->opt.warm_push; A.frac = q->opt.warm_frac; A.z_push = q->opt.warm_z_push; A.z_max = q->opt.warm_z_max; A.y_clip = q->opt.warm_y_max;
+  A.mu_factor = q->opt.mu_factor; A.cap = q->opt.mu_cap;
+  A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon);
+  return A;
+}
+int init_object(iem_model *m) {
+  iem_model::InitObject &o = m->init;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kInitSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[6] = {KernelSlot{"init_ls_terms", &o.ls_terms}, KernelSlot{"init_ls_norm", &o.ls_norm}, KernelSlot{"init_ls_apply", &o.ls_apply},
+                         KernelSlot{"init_warm", &o.warm}, KernelSlot{"init_mu", &o.mu}, KernelSlot{"init_reset", &o.reset}};
+  return load_object(m, src, slots, 6, &o.mod);
+}
+int init_opts(const iem_init_opts_t *in, iem_init_opts_t *out) {
+  // Ipopt's constr_mult_init_max; its initialiser's y = 0 on rejection; warm_start_bound_push, _bound_frac, _mult_bound_push, _mult_init_max
+  iem_init_opts_t v = {sizeof v, 1e3, 0, 1e-3, 1e-3, 1e-3, 1e6, 1e6, 1.0, 0.0};
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_init_create: set struct_size to sizeof(iem_init_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  for (double f : {v.y_max, v.warm_push, v.warm_frac, v.warm_z_push, v.warm_z_max, v.warm_y_max, v.mu_factor, v.mu_cap})
+    if (!std::isfinite(f)) return fail(IEM_E_ARG, "iem_init_create: every option must be finite");
+  if (!(v.y_max >= 0.0)) return fail(IEM_E_ARG, "iem_init_create: y_max must not be negative");
+  if (v.on_reject != 0 && v.on_reject != 1) return fail(IEM_E_ARG, "iem_init_create: on_reject must be 0 (write +0.0) or 1 (keep y)");
+  if (!(v.warm_push > 0.0)) return fail(IEM_E_ARG, "iem_init_create: warm_push must be positive");
+  if (!(v.warm_frac > 0.0) || !(v.warm_frac <= 0.5)) return fail(IEM_E_ARG, "iem_init_create: warm_frac must lie in (0, 0.5]");
+  if (!(v.warm_z_push > 0.0)) return fail(IEM_E_ARG, "iem_init_create: warm_z_push must be positive");
+  if (!(v.warm_z_max >= v.warm_z_push)) return fail(IEM_E_ARG, "iem_init_create: warm_z_max must be at least warm_z_push");
+  if (!(v.warm_y_max > 0.0)) return fail(IEM_E_ARG, "iem_init_create: warm_y_max must be positive");
+  if (!(v.mu_factor > 0.0)) return fail(IEM_E_ARG, "iem_init_create: mu_factor must be positive");
+  if (!(v.mu_cap >= 0.0)) return fail(IEM_E_ARG, "iem_init_create: mu_cap must not be negative");
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_init_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kInitSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_init_destroy(iem_init *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->b->m->device);
+  if (q->d_blk) hipFree(q->d_blk);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_init_create(iem_barrier *b, const iem_init_opts_t *opts, iem_init **out) {
+  if (!b || !out) return fail(IEM_E_ARG, "null argument");
+  iem_init_opts_t opt;
+  {
+    int rc = init_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = init_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_init *q) const { iem_init_destroy(q); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_init, Drop> q(new iem_init);
+  q->b = b;
+  q->opt = opt;
+  HIP_TRY(hipMalloc((void **)&q->d_blk, 18 * 8));
+  HIP_TRY(hipMemset(q->d_blk, 0, 18 * 8));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_init_reset(iem_init *q) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->b->m;
+  DevGuard dg_(m->device);
+  InitArgsH A = init_args(q);
+  return kkt_launch_raw(m, m->init.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_init_ls_terms(iem_init *q, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU, const double *d_r,
+                      double *d_sigma, double *d_dcon, double *d_rhs) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->b;
+  if ((b->nvar && (!d_zL || !d_zU || !d_r || !d_sigma)) || (b->ncon && (!d_y || !d_dcon)) || (b->n_ineq && (!d_vL || !d_vU)) || !d_rhs)
+    return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  InitArgsH A = init_args(q);
+  A.y = (double *)d_y; A.zL = (double *)d_zL; A.zU = (double *)d_zU; A.vL = (double *)d_vL; A.vU = (double *)d_vU;
+  A.r = d_r; A.sigma = d_sigma; A.dcon = d_dcon; A.rhs = d_rhs;
+  return kkt_launch_raw(m, m->init.ls_terms, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_init_ls_apply(iem_init *q, const double *d_sol, double *d_y) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->b;
+  if (!d_sol || (b->ncon && !d_y)) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  InitArgsH A = init_args(q);
+  A.sol = d_sol; A.y = d_y;
+  // the seed: the maximum starts from the bits of +0.0 (a device-to-device copy is a capturable node, as in iem_barrier_step); without rows it stays there
+  HIP_TRY(hipMemcpyAsync(A.slot, q->d_blk + 17, 8, hipMemcpyDeviceToDevice, m->stream));
+  if (b->ncon) {
+    int rc = kkt_launch_raw(m, m->init.ls_norm, &A, sizeof A, b->n_wg, 256);
+    if (rc) return rc;
+  }
+  return kkt_launch_raw(m, m->init.ls_apply, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_init_warm(iem_init *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU)) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  InitArgsH A = init_args(q);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU;
+  return kkt_launch_raw(m, m->init.warm, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_init_mu(iem_init *q, const double *d_out12, iem_mu *p) {
+  if (!q || !d_out12 || !p) return fail(IEM_E_ARG, "null argument");
+  if (p->b != q->b) return fail(IEM_E_ARG, "iem_init_mu: the iem_mu object belongs to another barrier object");
+  iem_model *m = q->b->m;
+  DevGuard dg_(m->device);
+  InitArgsH A = init_args(q);
+  A.w = d_out12; A.mblk = p->d_blk;
+  A.mu_init = p->opt.mu_init; A.mu_floor = p->opt.mu_floor; A.tau_min = p->opt.tau_min;
+  if (A.cap == 0.0) A.cap = p->opt.mu_init;
+  return kkt_launch_raw(m, m->init.mu, &A, sizeof A, 1, 64);
+}
+
+int iem_init_device(const iem_init *q, double **d_block) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = q->d_blk;
+  return IEM_OK;
+}
+
+int iem_init_state(iem_init *q, iem_init_state_t *out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_init_state: set struct_size to sizeof(iem_init_state_t) before the call");
+  iem_model *m = q->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[16];
+  HIP_TRY(hipMemcpyAsync(w, q->d_blk, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_init_state_t v;
+  static_assert(sizeof v == 7 * 8, "iem_init_state_t: struct_size, then words 0-5 of the own block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.ynorm, w, 6 * 8);
   std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
   return IEM_OK;
 }

@@ -921,6 +921,74 @@ function mpc_device(o::MehrotraCorrector)
     return p[]
 end
 
+# ---- the starting point (include/iem.h: iem_init_*) -----------------------------------------------------------------------------------
+# What stands in front of the first iteration, ON a BarrierLayer.  COLD, behind barrier_start!: init_ls_terms! (sigma = 1, dcon = 1 on
+# inequality rows, the right-hand side of the least-squares multiplier estimate), assemble with a ZEROED Hessian value array, factor, one
+# (refined) solve, init_ls_apply! (y += dy where max |y + dy| <= y_max, else y = 0 or y kept).  WARM, in the place of barrier_start!:
+# init_warm! (the push of x and of the given s, the multipliers clamped, y clipped), the evaluation, mu_error!, init_mu! (mu0 from the
+# average complementarity into the BarrierParameter's block).  init_state — the one read-back.  Finalize (or let go of) the starting
+# point before its BarrierLayer.  UNEXECUTED, like the rest.
+struct IemInitOpts         # iem_init_opts_t
+    struct_size::UInt64
+    y_max::Float64
+    on_reject::Int64
+    warm_push::Float64; warm_frac::Float64; warm_z_push::Float64; warm_z_max::Float64; warm_y_max::Float64
+    mu_factor::Float64; mu_cap::Float64
+end
+struct IemInitState        # iem_init_state_t: words 0-5 of the object's own block
+    struct_size::UInt64
+    ynorm::Float64
+    accepted::Int64; n_accepted::Int64; n_rejected::Int64
+    mu0::Float64
+    how::Int64             # 0 from the average, 1 fallback to mu_init, 2 clamped below, 3 clamped above
+end
+mutable struct StartingPoint
+    q::Ptr{Cvoid}
+    layer::BarrierLayer      # borrowed: kept alive
+end
+function StartingPoint(l::BarrierLayer; y_max = 1e3, on_reject = 0, warm_push = 1e-3, warm_frac = 1e-3, warm_z_push = 1e-3, warm_z_max = 1e6, warm_y_max = 1e6,
+                       mu_factor = 1.0, mu_cap = 0.0)
+    opts = Ref(IemInitOpts(sizeof(IemInitOpts), y_max, on_reject, warm_push, warm_frac, warm_z_push, warm_z_max, warm_y_max, mu_factor, mu_cap))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_init_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemInitOpts}, Ptr{Ptr{Cvoid}}), l.b, opts, q))
+    sp = StartingPoint(q[], l)
+    finalizer(x -> (x.q == C_NULL || x.layer.b == C_NULL || ccall((:iem_init_destroy, LIBIEM), Cint, (Ptr{Cvoid},), x.q); x.q = C_NULL), sp)
+    return sp
+end
+# a new solve: the block zero (asynchronous)
+init_reset!(o::StartingPoint) = check(ccall((:iem_init_reset, LIBIEM), Cint, (Ptr{Cvoid},), o.q))
+# state = (x, s, y, zL, zU, vL, vU); x and s are not read.  sigma (nvar), dcon (ncon), rhs (nvar + ncon) on the device
+function init_ls_terms!(o::StartingPoint, state, r, sigma, dcon, rhs)
+    check(ccall((:iem_init_ls_terms, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 9)...),
+                o.q, spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), dptr(r), dptr(sigma), spptr(dcon), dptr(rhs)))
+    return sigma, dcon, rhs
+end
+# sol = [w; dy] of the solve; y in place
+function init_ls_apply!(o::StartingPoint, sol, y)
+    check(ccall((:iem_init_ls_apply, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), o.q, dptr(sol), spptr(y)))
+    return y
+end
+# the warm-start projection, in place
+function init_warm!(o::StartingPoint, state)
+    check(ccall((:iem_init_warm, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 7)...),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7])))
+    return state
+end
+# out12: the twelve of mu_error! at the warm state; par: a BarrierParameter on the same BarrierLayer
+init_mu!(o::StartingPoint, out12, par::BarrierParameter) = check(ccall((:iem_init_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Cvoid}), o.q, dptr(out12), par.p))
+# the one read-back (synchronises the stream once)
+function init_state(o::StartingPoint)
+    own = Ref(IemInitState(sizeof(IemInitState), 0.0, 0, 0, 0, 0.0, 0))
+    check(ccall((:iem_init_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemInitState}), o.q, own))
+    return own[]
+end
+# the own block (16 words of 8 bytes) as a device address
+function init_device(o::StartingPoint)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_init_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.q, p))
+    return p[]
+end
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
