@@ -1470,6 +1470,91 @@ int iem_init_state(iem_init *q, iem_init_state_t *out);      /* synchronises the
 /* HIP source of the six kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_init_source(char **out_src, uint64_t *out_key);
 
+/* ---- the stopping test and the kept iterate -----------------------------------------------------------------------------------------------
+ * What decides that a solve ends (csrc/iem_conv_device.h), as an object created ON an iem_mu whose barrier object, grid, tol, s_max and
+ * mu_floor it borrows and whose block it reads: Ipopt's OptimalityErrorConvergenceCheck — the scaled error E(0) beside the unscaled
+ * tolerances (dual_inf_tol, constr_viol_tol, compl_inf_tol), the ACCEPTABLE level (acceptable_tol and its companions, met
+ * acceptable_iter times in a row), max_iter, diverging_iterates_tol, the invalid number and the tiny step — and THE KEPT ITERATE: the
+ * best acceptable point, copied into the object's own buffers on the device's own decision, without a read-back, and handed back
+ * when the solve later stalls, diverges, runs out of iterations or fails in restoration.  iem_mu_update keeps its own test
+ * (E(0) <= tol) and its status word; this object neither reads nor writes them.
+ *
+ * Entry order and flags (fx / fc) are those of iem_barrier_terms: one thread takes the entries i, i + stride, ... of
+ * [0, nvar + ncon); nothing is read where no bound is present; entries of s, vL, vU, ds on equality rows are neither read nor
+ * written.  Each operation is rounded once, in the order written here.  The maxima are integer maxima on the bit patterns of
+ * non-negative doubles — order-independent, a NaN wins, at most one atomic per workgroup and slot.
+ *
+ * THE BLOCK: twenty-four 8-byte words on the device (iem_conv_device gives the pointer; iem_conv_state_t mirrors words 0–18).
+ *     int64:  0 status: 0 ITERATING, 1 CONVERGED, 2 ACCEPTABLE, 3 MAXITER, 4 DIVERGING, 5 INVALID, 6 TINY_STEP
+ *             1 checks so far      2 acceptable checks in a row      3 keep: the last check asks for a copy      4 kept: a point is held
+ *             5 the value of word 1 at the check that kept it      6 flags: bit 0 = acceptable now, bit 1 = this step tiny, bit 2 = tiny
+ *             with mu above its floor (the hint for force_fixed of iem_amu_update / iem_qf_update)      7 tiny steps in a row
+ *     double: 8 E(0)      9 d = max(w0, w1)      10 p = ncon ? w2 : 0      11 cpl = nz ? w3 : 0      12 f      13 the f of the previous
+ *             check (what the objective change was taken against)      14 xmax      15 E(0) of the kept point      16 its f      17 rel
+ *             18 dymax      19–23 zero
+ *     A status other than 0 is LATCHED: every later iem_conv_check writes keep = 0 and nothing else, every later iem_conv_step writes
+ *     nothing, until iem_conv_reset (one launch of one workgroup of 64 threads: the block zero; the kept buffers keep their bytes).
+ * iem_conv_check(q, w12, f, x): an 8-byte device-to-device copy (the seed of the maximum, +0.0) and two launches.  xmax = max_i |x_i|
+ *     over the variables.  Then one thread decides.  E(0) in the expressions of iem_mu_update at mu = +0.0 with that object's s_max:
+ *     word 8 is bit for bit word 3 of the iem_mu block after iem_mu_update on the same twelve words.  The first branch that applies:
+ *     1. w[10] != 0, or one of E(0), f, xmax a NaN, or E(0) or f infinite: INVALID (keep = 0, bit 0 clear).
+ *     2. E(0) <= tol && d <= dual_inf_tol && p <= constr_viol_tol && cpl <= compl_inf_tol: CONVERGED, keep = 1 (bit 0 clear: the
+ *        acceptable level is not evaluated, the count of word 2 stays).
+ *     3. acceptable = E(0) <= acceptable_tol && d <= acceptable_dual_inf_tol && p <= acceptable_constr_viol_tol && cpl <=
+ *        acceptable_compl_inf_tol && (word 1 == 0, the first check of a solve, or |f − f_prev| / max(1, |f|) <= acceptable_obj_change_tol,
+ *        f_prev the f of the previous check).  Bit 0 = acceptable; word 2 grows by one when acceptable and returns to 0 when not.
+ *        acceptable && (kept == 0 || E(0) <= word 15): keep = 1.  acceptable_iter > 0 && word 2 >= acceptable_iter: ACCEPTABLE.
+ *     4. otherwise word 1 >= max_iter: MAXITER (max_iter iterations pass; the check behind them stops).
+ *     5. otherwise xmax > diverging_iterates_tol: DIVERGING.
+ *     keep is written 0 or 1 by every check; with keep = 1, kept = 1 and words 15, 16, 5 take E(0), f and word 1.  Words 8–14 are
+ *     rewritten by every unlatched check; word 1 grows by one where the status stays 0.  Bits 1 and 2 of the flags stay.
+ * iem_conv_keep(q, state): ONE launch on the barrier grid.  Every thread reads keep, which the launch does not write; at 0 it
+ *     returns before its first store.  At 1 it copies into the object's own buffers (3 nvar + 4 ncon doubles, allocated and zeroed at
+ *     create): x; zL / zU where the bound is present, +0.0 where absent; every row's y; s, vL, vU of inequality rows the same way.
+ * iem_conv_restore(q, state): the same launch in the other direction on the word kept; at 0 it touches nothing; where it copies it
+ *     writes only the entries that iem_conv_keep reads.  iem_conv_kept hands out the seven device pointers (any may be NULL).
+ * iem_conv_step(q, x, s, sol, ds): after the direction is solved; a 16-byte seed copy and two launches.
+ *     rel = max(|sol_i| / (1.0 + |x_i|) over the variables, |ds_j| / (1.0 + |s_j|) over the inequality rows);  dymax = max_j |sol[nvar + j]|
+ *     over all rows.  tiny = rel < tiny_step_tol (a NaN compares false); word 7 grows when tiny, otherwise returns to 0; bit 1 = tiny;
+ *     bit 2 = tiny && mu > mu_floor, mu = word 0 of the iem_mu block; word 7 >= 2 && dymax < tiny_step_y_tol && mu <= mu_floor:
+ *     TINY_STEP.  Ipopt also skips its line search on a tiny step; this object only reports.
+ * iem_conv_state: the one read-back (one synchronisation).
+ * Every other call runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  No float atomic, no
+ * cooperative launch.  IEM_E_ARG before any device work: null required pointers (s, vL, vU, ds may be NULL without inequality rows, y
+ * without rows), a tolerance that is <= 0 or a NaN (+inf is allowed and switches that test off), a negative max_iter or
+ * acceptable_iter, a struct_size that is not the struct's.  The object borrows the iem_mu object: destroy it first.  Not here: the
+ * delta_w / inertia retry, Ipopt's skipping of the line search on a tiny step, max_cpu_time, a freeze of the other kernels behind the
+ * latch (a replay past a terminal status keeps iterating; iem_conv_restore is what hands back the point), a binding for iem_resto,
+ * scaled against unscaled problems (the tolerances apply in the scaling the caller evaluates in), sharded handles. */
+typedef struct iem_conv iem_conv;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_conv_opts_t) */
+  double dual_inf_tol, constr_viol_tol, compl_inf_tol;      /* 1, 1e-4, 1e-4; > 0, +inf allowed */
+  double acceptable_tol;                /* 1e-6 */
+  int64_t acceptable_iter;              /* 15; 0 switches the ACCEPTABLE stop off (points are still kept); >= 0 */
+  double acceptable_dual_inf_tol, acceptable_constr_viol_tol, acceptable_compl_inf_tol, acceptable_obj_change_tol;      /* 1e10, 1e-2, 1e-2, 1e20 */
+  int64_t max_iter;                     /* 3000; >= 0 */
+  double diverging_iterates_tol;        /* 1e20 */
+  double tiny_step_tol, tiny_step_y_tol;                    /* 10·2^-52, 1e-2 */
+} iem_conv_opts_t;                      /* NULL = the defaults */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_conv_state_t) */
+  int64_t status, checks, acceptable_count, keep, kept, kept_at, flags, tiny_count;      /* words 0–7 */
+  double e0, dual_inf, constr_viol, compl_inf, f, f_prev, xmax, kept_e0, kept_f, rel, dymax;      /* words 8–18 */
+} iem_conv_state_t;
+int iem_conv_create(iem_mu *p, const iem_conv_opts_t *opts, iem_conv **out);
+int iem_conv_destroy(iem_conv *q);
+int iem_conv_reset(iem_conv *q);
+int iem_conv_check(iem_conv *q, const double *d_out12 /* of iem_mu_error */, const double *d_f /* 1 */, const double *d_x);
+int iem_conv_keep(iem_conv *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU);
+int iem_conv_restore(iem_conv *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU);
+int iem_conv_step(iem_conv *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds);
+int iem_conv_kept(const iem_conv *q, double **d_x, double **d_s, double **d_y, double **d_zL, double **d_zU, double **d_vL, double **d_vU);
+int iem_conv_device(const iem_conv *q, double **d_block);
+int iem_conv_state(iem_conv *q, iem_conv_state_t *out);      /* synchronises the stream: the one read-back */
+/* HIP source of the seven kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_conv_source(char **out_src, uint64_t *out_key);
+
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates
  * and compiled for gfx950 (offline into a code-object cache, or by hiprtc on a cache

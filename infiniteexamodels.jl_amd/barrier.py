@@ -1047,6 +1047,145 @@ class StartingPoint:
             pass
 
 
+class ConvergenceCheck:
+    """``ConvergenceCheck(par, **opts)``: the stopping test and the kept iterate of the C-ABI (``iem_conv_*``,
+    ``csrc/iem_conv_device.h``) ON a :class:`BarrierParameter`, whose ``tol``, ``s_max``, ``mu_floor`` and block it reads — Ipopt's
+    scaled error beside the unscaled tolerances, the acceptable level met ``acceptable_iter`` times in a row, ``max_iter``, diverging
+    iterates, the invalid number, the tiny step; the best acceptable point is copied into the object's own buffers on the device's
+    own decision.  ``opts``: ``dual_inf_tol, constr_viol_tol, compl_inf_tol, acceptable_tol, acceptable_iter,
+    acceptable_dual_inf_tol, acceptable_constr_viol_tol, acceptable_compl_inf_tol, acceptable_obj_change_tol, max_iter,
+    diverging_iterates_tol, tiny_step_tol, tiny_step_y_tol`` (Ipopt's defaults; ``inf`` switches a tolerance off).  Per iteration:
+
+        w = par.error(state, r, c, out=w)
+        conv.check(w, f, state[0])                                     # the stopping test: status, keep
+        conv.keep(state)                                               # copies iff the check asked for it
+        par.update(w, search=fs)
+        st = conv.state()                                              # THE read-back; st["status"] != 0: conv.restore(state) where st["kept"]
+        ...                                                            # terms, assemble, factor, solve
+        dirs, alpha = bar.step(state, sol, mu, tau)
+        conv.step(state, sol, dirs[0])                                 # the tiny step: read with the next state()
+
+    A status other than 0 is latched until :meth:`reset`."""
+
+    def __init__(self, par: BarrierParameter, **opts):
+        self.par = par
+        self.layer = par.layer
+        self._q = None
+        o = _lib.ConvOpts.defaults(**opts)
+        L, p = par._handle()
+        q = C.c_void_p()
+        _lib.check(L.iem_conv_create(p, C.byref(o), C.byref(q)))
+        self._q = q
+        self.opts = {name: getattr(o, name) for name, _ in _lib.ConvOpts._fields_ if name != "struct_size"}
+
+    def _handle(self):
+        if self._q is None:
+            raise _lib.IemError("ConvergenceCheck: closed")
+        L, _ = self.par._handle()
+        return L, self._q
+
+    def reset(self):
+        """A new solve (``iem_conv_reset``, asynchronous): the block zero; the kept buffers keep their bytes.  Returns ``self``."""
+        L, q = self._handle()
+        _lib.check(L.iem_conv_reset(q))
+        return self
+
+    def check(self, w12, f, x):
+        """The stopping test on the device (``iem_conv_check``) from the twelve words of ``par.error``, the objective ``f`` (a device
+        tensor of one) and ``x``.  Returns ``self``."""
+        bar = self.layer
+        args = (bar._vec(w12, 12, "w12"), bar._vec(f, 1, "f"), bar._vec(x, bar.nvar, "x"))
+        L, q = self._handle()
+        _lib.check(L.iem_conv_check(q, *args))
+        return self
+
+    def keep(self, state):
+        """Copy ``state`` into the kept buffers iff the last :meth:`check` asked for it (``iem_conv_keep``).  Returns ``self``."""
+        p = self.layer._state(state)
+        L, q = self._handle()
+        _lib.check(L.iem_conv_keep(q, *p))
+        return self
+
+    def restore(self, state):
+        """The kept point into ``state`` IN PLACE iff one is held (``iem_conv_restore``): only the entries :meth:`keep` reads are
+        written.  Returns ``state``."""
+        p = self.layer._state(state)
+        L, q = self._handle()
+        _lib.check(L.iem_conv_restore(q, *p))
+        return state
+
+    def step(self, state, sol, ds):
+        """The tiny-step test on the device (``iem_conv_step``) from ``x, s`` of ``state``, ``sol = [dx; dy]`` and the slack direction
+        ``ds`` of ``BarrierLayer.step``.  Returns ``self``."""
+        bar = self.layer
+        slack = bar.info["n_ineq"] == 0
+        args = (bar._vec(state[0], bar.nvar, "x"), bar._vec(state[1], bar.ncon, "s", optional=slack), bar._vec(sol, bar.n, "sol"), bar._vec(ds, bar.ncon, "ds", optional=slack))
+        L, q = self._handle()
+        _lib.check(L.iem_conv_step(q, *args))
+        return self
+
+    def kept(self):
+        """The kept point ``(x, s, y, zL, zU, vL, vU)`` as device tensors that ALIAS the object's own buffers (``iem_conv_kept``):
+        valid until :meth:`close`; absent bounds hold ``+0.0``, equality rows of ``s, vL, vU`` what create left (zero)."""
+        import torch
+        bar = self.layer
+        L, q = self._handle()
+        ptrs = [C.c_void_p() for _ in range(7)]
+        _lib.check(L.iem_conv_kept(q, *[C.byref(p) for p in ptrs]))
+        sizes = (bar.nvar, bar.ncon, bar.ncon, bar.nvar, bar.nvar, bar.ncon, bar.ncon)
+        total = 3 * bar.nvar + 4 * bar.ncon
+
+        class _Span:      # the whole allocation through the CUDA array interface: the tensors below are views of it
+            __cuda_array_interface__ = dict(shape=(max(total, 1),), typestr="<f8", data=(ptrs[0].value, False), version=2)
+
+        whole = torch.as_tensor(_Span(), device=bar.model.device)
+        out, at = [], 0
+        for p, k in zip(ptrs, sizes):
+            assert (p.value or 0) == ptrs[0].value + 8 * at or k == 0
+            out.append(whole[at:at + k])
+            at += k
+        return tuple(out)
+
+    def state(self):
+        """THE read-back (``iem_conv_state``, synchronises once): words 0–18 of the block as a dict, ``status_name``, and the flag bits
+        as ``acceptable``, ``tiny``, ``tiny_above_floor``."""
+        L, q = self._handle()
+        v = _lib.ConvState()
+        v.struct_size = C.sizeof(_lib.ConvState)
+        _lib.check(L.iem_conv_state(q, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.ConvState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.CONV_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.CONV_STATUS) else "?"
+        out["keep"], out["kept"] = bool(out["keep"]), bool(out["kept"])
+        out.update(acceptable=bool(out["flags"] & 1), tiny=bool(out["flags"] & 2), tiny_above_floor=bool(out["flags"] & 4))
+        return out
+
+    def device(self):
+        """The address of the object's own block (24 words) on the device (``iem_conv_device``)."""
+        L, q = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_conv_device(q, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        if self._q is not None:
+            _lib.check(self.layer.model._L.iem_conv_destroy(self._q))
+            self._q = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.par._p is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass
+
+
 class Restoration:
     """``Restoration(search, rho=1000, kappa_resto=0.9, bound_mult_reset_threshold=1000)``: the feasibility restoration phase of the
     C-ABI (``iem_resto_*``, ``csrc/iem_resto_device.h``) beside the :class:`FilterSearch` of the ORIGINAL problem — the elastic

@@ -76,6 +76,9 @@ static const char *kMpcSource =           // Mehrotra's corrector (iem_mpc_*): a
 static const char *kInitSource =          // the starting point (iem_init_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_init_device_h.inc"
     ;
+static const char *kConvSource =          // the stopping test and the kept iterate (iem_conv_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_conv_device_h.inc"
+    ;
 
 namespace {
 
@@ -348,6 +351,7 @@ struct iem_model {
   struct QfObject { hipModule_t mod = nullptr; hipFunction_t begin = nullptr, alpha = nullptr, value = nullptr, update = nullptr, reset = nullptr; } qf;      // the quality-function oracle (iem_qf_*): loaded by the first iem_qf_create
   struct MpcObject { hipModule_t mod = nullptr; hipFunction_t terms = nullptr, step = nullptr, select = nullptr, reset = nullptr; } mpc;      // Mehrotra's corrector (iem_mpc_*): loaded by the first iem_mpc_create
   struct InitObject { hipModule_t mod = nullptr; hipFunction_t ls_terms = nullptr, ls_norm = nullptr, ls_apply = nullptr, warm = nullptr, mu = nullptr, reset = nullptr; } init;      // the starting point (iem_init_*): loaded by the first iem_init_create
+  struct ConvObject { hipModule_t mod = nullptr; hipFunction_t xmax = nullptr, decide = nullptr, stepmax = nullptr, step_decide = nullptr, keep = nullptr, restore = nullptr, reset = nullptr; } conv;      // the stopping test (iem_conv_*): loaded by the first iem_conv_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1395,6 +1399,7 @@ int iem_destroy(iem_model *m) {
   if (m->qf.mod) hipModuleUnload(m->qf.mod);
   if (m->mpc.mod) hipModuleUnload(m->mpc.mod);
   if (m->init.mod) hipModuleUnload(m->init.mod);
+  if (m->conv.mod) hipModuleUnload(m->conv.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -5860,6 +5865,227 @@ int iem_init_state(iem_init *q, iem_init_state_t *out) {
   v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
   std::memcpy(&v.ynorm, w, 6 * 8);
   std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
+  return IEM_OK;
+}
+
+/* ---- the stopping test and the kept iterate (csrc/iem_conv_device.h) ---- */
+struct iem_conv {
+  iem_mu *p = nullptr;                 // the object whose barrier object, grid, tol, s_max, mu_floor and block it uses (borrowed)
+  iem_conv_opts_t opt;
+  double *d_blk = nullptr;             // the own block: 24 words, then the slots of xmax, rel, dymax and two words that stay +0.0 (the slots' seed)
+  double *d_kept = nullptr;            // the kept point: x | s | y | zL | zU | vL | vU (3 nvar + 4 ncon doubles)
+};
+
+namespace {
+constexpr int kConvWords = 24, kConvAlloc = kConvWords + 5;
+// ConvArgs of csrc/iem_conv_device.h
+struct ConvArgsH {
+  const unsigned char *fx, *fc;
+  double *x, *s, *y, *zL, *zU, *vL, *vU;
+  double *kx, *ks, *ky, *kzL, *kzU, *kvL, *kvU;
+  const double *sol, *ds;
+  const double *w, *f;
+  const double *mblk;
+  double *blk;
+  unsigned long long *slot;
+  double tol, s_max, mu_floor;
+  double dual_inf_tol, constr_viol_tol, compl_inf_tol;
+  double acceptable_tol, acceptable_dual_inf_tol, acceptable_constr_viol_tol, acceptable_compl_inf_tol, acceptable_obj_change_tol;
+  double diverging_iterates_tol, tiny_step_tol, tiny_step_y_tol;
+  long long acceptable_iter, max_iter;
+  long long ncon, nz;
+  long long nvar, n;
+};
+void conv_kept(const iem_conv *q, double *out[7]) {
+  const iem_barrier *b = q->p->b;
+  const int64_t sizes[7] = {b->nvar, b->ncon, b->ncon, b->nvar, b->nvar, b->ncon, b->ncon};
+  double *at = q->d_kept;
+  for (int k = 0; k < 7; ++k) { out[k] = at; at += sizes[k]; }
+}
+ConvArgsH conv_args(const iem_conv *q) {
+  const iem_mu *p = q->p;
+  const iem_barrier *b = p->b;
+  const iem_conv_opts_t &o = q->opt;
+  ConvArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  double *k[7];
+  conv_kept(q, k);
+  A.kx = k[0]; A.ks = k[1]; A.ky = k[2]; A.kzL = k[3]; A.kzU = k[4]; A.kvL = k[5]; A.kvU = k[6];
+  A.mblk = p->d_blk;
+  A.blk = q->d_blk; A.slot = (unsigned long long *)(q->d_blk + kConvWords);
+  A.tol = p->opt.tol; A.s_max = p->opt.s_max; A.mu_floor = p->opt.mu_floor;
+  A.dual_inf_tol = o.dual_inf_tol; A.constr_viol_tol = o.constr_viol_tol; A.compl_inf_tol = o.compl_inf_tol;
+  A.acceptable_tol = o.acceptable_tol; A.acceptable_dual_inf_tol = o.acceptable_dual_inf_tol; A.acceptable_constr_viol_tol = o.acceptable_constr_viol_tol;
+  A.acceptable_compl_inf_tol = o.acceptable_compl_inf_tol; A.acceptable_obj_change_tol = o.acceptable_obj_change_tol;
+  A.diverging_iterates_tol = o.diverging_iterates_tol; A.tiny_step_tol = o.tiny_step_tol; A.tiny_step_y_tol = o.tiny_step_y_tol;
+  A.acceptable_iter = (long long)o.acceptable_iter; A.max_iter = (long long)o.max_iter;
+  A.ncon = (long long)b->ncon; A.nz = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon);
+  return A;
+}
+void conv_set_state(ConvArgsH &A, const double *x, const double *s, const double *y, const double *zL, const double *zU, const double *vL, const double *vU) {
+  A.x = (double *)x; A.s = (double *)s; A.y = (double *)y; A.zL = (double *)zL; A.zU = (double *)zU; A.vL = (double *)vL; A.vU = (double *)vU;
+}
+int conv_object(iem_model *m) {
+  iem_model::ConvObject &o = m->conv;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kConvSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[7] = {KernelSlot{"conv_xmax", &o.xmax}, KernelSlot{"conv_decide", &o.decide}, KernelSlot{"conv_stepmax", &o.stepmax}, KernelSlot{"conv_step_decide", &o.step_decide},
+                         KernelSlot{"conv_keep", &o.keep}, KernelSlot{"conv_restore", &o.restore}, KernelSlot{"conv_reset", &o.reset}};
+  return load_object(m, src, slots, 7, &o.mod);
+}
+int conv_opts(const iem_conv_opts_t *in, iem_conv_opts_t *out) {
+  // Ipopt's dual_inf_tol, constr_viol_tol, compl_inf_tol, acceptable_tol, acceptable_iter, acceptable_dual_inf_tol, acceptable_constr_viol_tol,
+  // acceptable_compl_inf_tol, acceptable_obj_change_tol, max_iter, diverging_iterates_tol, tiny_step_tol (10 machine epsilons), tiny_step_y_tol
+  iem_conv_opts_t v = {sizeof v, 1.0, 1e-4, 1e-4, 1e-6, 15, 1e10, 1e-2, 1e-2, 1e20, 3000, 1e20, 10.0 * std::numeric_limits<double>::epsilon(), 1e-2};
+  if (in) {
+    if (in->struct_size != sizeof v) return fail(IEM_E_ARG, "iem_conv_create: set struct_size to sizeof(iem_conv_opts_t) before the call");
+    v = *in;
+  }
+  const struct { const char *name; double value; } tols[] = {
+      {"dual_inf_tol", v.dual_inf_tol}, {"constr_viol_tol", v.constr_viol_tol}, {"compl_inf_tol", v.compl_inf_tol}, {"acceptable_tol", v.acceptable_tol},
+      {"acceptable_dual_inf_tol", v.acceptable_dual_inf_tol}, {"acceptable_constr_viol_tol", v.acceptable_constr_viol_tol},
+      {"acceptable_compl_inf_tol", v.acceptable_compl_inf_tol}, {"acceptable_obj_change_tol", v.acceptable_obj_change_tol},
+      {"diverging_iterates_tol", v.diverging_iterates_tol}, {"tiny_step_tol", v.tiny_step_tol}, {"tiny_step_y_tol", v.tiny_step_y_tol}};
+  for (const auto &t : tols)
+    if (!(t.value > 0.0)) return fail(IEM_E_ARG, std::string("iem_conv_create: ") + t.name + " must be positive (+inf switches the test off)");
+  if (v.acceptable_iter < 0) return fail(IEM_E_ARG, "iem_conv_create: acceptable_iter must not be negative");
+  if (v.max_iter < 0) return fail(IEM_E_ARG, "iem_conv_create: max_iter must not be negative");
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_conv_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kConvSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_conv_destroy(iem_conv *q) {
+  if (!q) return IEM_OK;
+  DevGuard dg_(q->p->b->m->device);
+  if (q->d_blk) hipFree(q->d_blk);
+  if (q->d_kept) hipFree(q->d_kept);
+  delete q;
+  return IEM_OK;
+}
+
+int iem_conv_create(iem_mu *p, const iem_conv_opts_t *opts, iem_conv **out) {
+  if (!p || !out) return fail(IEM_E_ARG, "null argument");
+  iem_conv_opts_t opt;
+  {
+    int rc = conv_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  const iem_barrier *b = p->b;
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = conv_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_conv *q) const { iem_conv_destroy(q); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_conv, Drop> q(new iem_conv);
+  q->p = p;
+  q->opt = opt;
+  const size_t n_kept = (size_t)std::max<int64_t>(1, 3 * b->nvar + 4 * b->ncon);
+  HIP_TRY(hipMalloc((void **)&q->d_blk, kConvAlloc * 8));
+  HIP_TRY(hipMemset(q->d_blk, 0, kConvAlloc * 8));
+  HIP_TRY(hipMalloc((void **)&q->d_kept, n_kept * 8));
+  HIP_TRY(hipMemset(q->d_kept, 0, n_kept * 8));
+  *out = q.release();
+  return IEM_OK;
+}
+
+int iem_conv_reset(iem_conv *q) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = q->p->b->m;
+  DevGuard dg_(m->device);
+  ConvArgsH A = conv_args(q);
+  return kkt_launch_raw(m, m->conv.reset, &A, sizeof A, 1, 64);
+}
+
+int iem_conv_check(iem_conv *q, const double *d_out12, const double *d_f, const double *d_x) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->p->b;
+  if (!d_out12 || !d_f || (b->nvar && !d_x)) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  ConvArgsH A = conv_args(q);
+  A.w = d_out12; A.f = d_f; A.x = (double *)d_x;
+  // the seed: the maximum starts from the bits of +0.0 (a device-to-device copy is a capturable node, as in iem_init_ls_apply)
+  HIP_TRY(hipMemcpyAsync(A.slot, q->d_blk + kConvWords + 3, 8, hipMemcpyDeviceToDevice, m->stream));
+  int rc = kkt_launch_raw(m, m->conv.xmax, &A, sizeof A, b->n_wg, 256);
+  if (rc) return rc;
+  return kkt_launch_raw(m, m->conv.decide, &A, sizeof A, 1, 64);
+}
+
+int iem_conv_keep(iem_conv *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->p->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU)) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  ConvArgsH A = conv_args(q);
+  conv_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  return kkt_launch_raw(m, m->conv.keep, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_conv_restore(iem_conv *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->p->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU)) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  ConvArgsH A = conv_args(q);
+  conv_set_state(A, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU);
+  return kkt_launch_raw(m, m->conv.restore, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_conv_step(iem_conv *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = q->p->b;
+  if (!d_sol || (b->nvar && !d_x) || (b->n_ineq && (!d_s || !d_ds))) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  ConvArgsH A = conv_args(q);
+  A.x = (double *)d_x; A.s = (double *)d_s; A.sol = d_sol; A.ds = d_ds;
+  HIP_TRY(hipMemcpyAsync(A.slot + 1, q->d_blk + kConvWords + 3, 16, hipMemcpyDeviceToDevice, m->stream));      // the seeds of rel and dymax
+  int rc = kkt_launch_raw(m, m->conv.stepmax, &A, sizeof A, b->n_wg, 256);
+  if (rc) return rc;
+  return kkt_launch_raw(m, m->conv.step_decide, &A, sizeof A, 1, 64);
+}
+
+int iem_conv_kept(const iem_conv *q, double **d_x, double **d_s, double **d_y, double **d_zL, double **d_zU, double **d_vL, double **d_vU) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  double *k[7];
+  conv_kept(q, k);
+  double **outs[7] = {d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU};
+  for (int i = 0; i < 7; ++i)
+    if (outs[i]) *outs[i] = k[i];
+  return IEM_OK;
+}
+
+int iem_conv_device(const iem_conv *q, double **d_block) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = q->d_blk;
+  return IEM_OK;
+}
+
+int iem_conv_state(iem_conv *q, iem_conv_state_t *out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size != sizeof(iem_conv_state_t)) return fail(IEM_E_ARG, "iem_conv_state: set struct_size to sizeof(iem_conv_state_t) before the call");
+  iem_model *m = q->p->b->m;
+  DevGuard dg_(m->device);
+  uint64_t w[kConvWords];
+  HIP_TRY(hipMemcpyAsync(w, q->d_blk, sizeof w, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  static_assert(sizeof(iem_conv_state_t) == 20 * 8, "iem_conv_state_t: struct_size, then words 0-18 of the own block");
+  std::memcpy(&out->status, w, 19 * 8);
   return IEM_OK;
 }
 

@@ -989,6 +989,81 @@ function init_device(o::StartingPoint)
     return p[]
 end
 
+# ---- the stopping test and the kept iterate (include/iem.h: iem_conv_*) ---------------------------------------------------------------
+# What decides that a solve ends, ON a BarrierParameter (its tol, s_max, mu_floor and block).  Per iteration: mu_error!, conv_check!
+# (status, keep), conv_keep! (copies iff the check asked for it), mu_update!, conv_state — the one read-back; behind barrier_step!
+# conv_step! (the tiny step).  A status other than 0 is latched until conv_reset!; conv_restore! hands the kept point back.  Finalize (or
+# let go of) the object before its BarrierParameter.  UNEXECUTED, like the rest.
+struct IemConvOpts         # iem_conv_opts_t
+    struct_size::UInt64
+    dual_inf_tol::Float64; constr_viol_tol::Float64; compl_inf_tol::Float64
+    acceptable_tol::Float64
+    acceptable_iter::Int64
+    acceptable_dual_inf_tol::Float64; acceptable_constr_viol_tol::Float64; acceptable_compl_inf_tol::Float64; acceptable_obj_change_tol::Float64
+    max_iter::Int64
+    diverging_iterates_tol::Float64
+    tiny_step_tol::Float64; tiny_step_y_tol::Float64
+end
+struct IemConvState        # iem_conv_state_t: words 0-18 of the object's own block
+    struct_size::UInt64
+    status::Int64          # 0 iterating, 1 converged, 2 acceptable, 3 maxiter, 4 diverging, 5 invalid, 6 tiny step
+    checks::Int64; acceptable_count::Int64; keep::Int64; kept::Int64; kept_at::Int64
+    flags::Int64           # bit 0 acceptable now, bit 1 this step tiny, bit 2 tiny with mu above its floor
+    tiny_count::Int64
+    e0::Float64; dual_inf::Float64; constr_viol::Float64; compl_inf::Float64; f::Float64; f_prev::Float64; xmax::Float64
+    kept_e0::Float64; kept_f::Float64; rel::Float64; dymax::Float64
+end
+mutable struct ConvergenceCheck
+    q::Ptr{Cvoid}
+    par::BarrierParameter      # borrowed: kept alive
+end
+function ConvergenceCheck(par::BarrierParameter; dual_inf_tol = 1.0, constr_viol_tol = 1e-4, compl_inf_tol = 1e-4, acceptable_tol = 1e-6, acceptable_iter = 15,
+                          acceptable_dual_inf_tol = 1e10, acceptable_constr_viol_tol = 1e-2, acceptable_compl_inf_tol = 1e-2, acceptable_obj_change_tol = 1e20,
+                          max_iter = 3000, diverging_iterates_tol = 1e20, tiny_step_tol = 10.0 * eps(Float64), tiny_step_y_tol = 1e-2)
+    opts = Ref(IemConvOpts(sizeof(IemConvOpts), dual_inf_tol, constr_viol_tol, compl_inf_tol, acceptable_tol, acceptable_iter, acceptable_dual_inf_tol,
+                           acceptable_constr_viol_tol, acceptable_compl_inf_tol, acceptable_obj_change_tol, max_iter, diverging_iterates_tol, tiny_step_tol, tiny_step_y_tol))
+    q = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_conv_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemConvOpts}, Ptr{Ptr{Cvoid}}), par.p, opts, q))
+    cc = ConvergenceCheck(q[], par)
+    finalizer(x -> (x.q == C_NULL || x.par.p == C_NULL || ccall((:iem_conv_destroy, LIBIEM), Cint, (Ptr{Cvoid},), x.q); x.q = C_NULL), cc)
+    return cc
+end
+# a new solve: the block zero, the kept buffers keep their bytes (asynchronous)
+conv_reset!(o::ConvergenceCheck) = check(ccall((:iem_conv_reset, LIBIEM), Cint, (Ptr{Cvoid},), o.q))
+# out12: the twelve of mu_error!; f: the objective, one double on the device; x: the variables
+conv_check!(o::ConvergenceCheck, out12, f, x) = check(ccall((:iem_conv_check, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), o.q, dptr(out12), dptr(f), spptr(x)))
+# state = (x, s, y, zL, zU, vL, vU): copied into the object's buffers iff the last conv_check! asked for it
+function conv_keep!(o::ConvergenceCheck, state)
+    check(ccall((:iem_conv_keep, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 7)...),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7])))
+end
+# the kept point into state, in place, iff one is held: only the entries conv_keep! reads are written
+function conv_restore!(o::ConvergenceCheck, state)
+    check(ccall((:iem_conv_restore, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 7)...),
+                o.q, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7])))
+    return state
+end
+# behind the solve of the direction: sol = [dx; dy], ds the slack direction of barrier_step!
+conv_step!(o::ConvergenceCheck, x, s, sol, ds) = check(ccall((:iem_conv_step, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 4)...), o.q, spptr(x), spptr(s), dptr(sol), spptr(ds)))
+# the kept point (x, s, y, zL, zU, vL, vU) as device addresses into the object's own buffers
+function conv_kept(o::ConvergenceCheck)
+    p = ntuple(_ -> Ref{Ptr{Float64}}(C_NULL), 7)
+    check(ccall((:iem_conv_kept, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Ptr{Float64}}, 7)...), o.q, p...))
+    return map(r -> r[], p)
+end
+# the one read-back (synchronises the stream once)
+function conv_state(o::ConvergenceCheck)
+    own = Ref(IemConvState(sizeof(IemConvState), 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0))
+    check(ccall((:iem_conv_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemConvState}), o.q, own))
+    return own[]
+end
+# the own block (24 words of 8 bytes) as a device address
+function conv_device(o::ConvergenceCheck)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_conv_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.q, p))
+    return p[]
+end
+
 # ---- the feasibility restoration phase (include/iem.h: iem_resto_*) ------------------------------------------------------------------
 # Step A-9 of Waechter and Biegler 2006 beside the FilterSearch of the ORIGINAL problem: resto_enter! when its search ended FAILED, then
 # per iteration eval_residual (obj_weight 0), resto_error!, jac_hess_coord (0), resto_terms!, assemble / factor / solve_refined!,
