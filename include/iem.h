@@ -828,7 +828,7 @@ int iem_barrier_source(char **out_src, uint64_t *out_key);
  * pointers (s, ds, st may be NULL without inequality rows), mu < 0, options out of range (gamma_theta, gamma_phi, eta_phi in (0, 1),
  * delta > 0, s_theta > 1, s_phi >= 1, alpha_floor >= 0, max_trials >= 1, 1 <= filter_capacity <= 1024).  The object borrows the barrier object (bounds,
  * flags, grid) and through it the model handle: destroy it before them.  Not here: inertia correction (the mu update is the iem_mu object below),
- * Ipopt's alpha_min formula, sharded handles (iem_barrier_create refuses them); restoration is the iem_resto object below.  The second-order correction is the
+ * sharded handles (iem_barrier_create refuses them); restoration is the iem_resto object below, Ipopt's alpha_min rule iem_rmu_trigger.  The second-order correction is the
  * iem_soc object below; words 13–15 of the block are its. */
 typedef struct iem_search iem_search;
 typedef struct {
@@ -947,8 +947,8 @@ int iem_soc_source(char **out_src, uint64_t *out_key);
  *     iem_kkt_solve_refined_diag;  iem_resto_step;  iem_resto_merit(0);  iem_resto_begin;
  *     K × { iem_resto_trial, iem_cons, iem_resto_merit(1), iem_search_accept(inner, out, out + 1, mu, 1.0, alpha) };
  *     iem_resto_update;  iem_obj_device;  iem_cons;  iem_barrier_merit;  iem_resto_check
- * The host keeps the restoration problem's mu rule (iem_search_reset(inner) when mu changes; the iem_mu object below serves the original
- * problem only and iem_resto_* never reads its block), the delta_w retry and one status read (iem_resto_state).
+ * The host keeps the restoration problem's mu rule (iem_search_reset(inner) when mu changes) — or hands it to the iem_rmu object below,
+ * which also binds these calls to a block on the device (iem_resto_bind_mu) —, the delta_w retry and one status read (iem_resto_state).
  * Notation: gaps, flags, sl, su, ml, mu_u and the row-side sigs, gs are those of the barrier contract above;  inf_j = c_j − ceq_j on
  * an equality row, c_j − s_j on an inequality row;  rho is an option;  zeta is a host double of the caller (eta·sqrt(mu), eta = 1).
  * Every operation is rounded once, in the order written.  The object owns p, n, zp, zn, dp, dn, dzp, dzn, pt, nt, sR, ws (ncon each)
@@ -994,8 +994,8 @@ int iem_soc_source(char **out_src, uint64_t *out_key);
  * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create, nothing synchronises and nothing
  * is copied to the host, except by iem_resto_state.  IEM_E_ARG before any device work: null required pointers (the slack side may
  * be NULL without inequality rows), rho <= 0, kappa_resto outside (0, 1), mu < 0, zeta < 0, tau outside (0, 1], which outside
- * {0, 1}.  The object borrows the search object and through it the barrier object: destroy it before them.  Not here: Ipopt's
- * alpha_min rule as the trigger (the host enters on FAILED), a second-order correction of the restoration, a nested restoration,
+ * {0, 1}.  The object borrows the search object and through it the barrier object: destroy it before them.  Not here (Ipopt's alpha_min rule as
+ * the trigger and the restoration's own mu on the device are the iem_rmu object below): a second-order correction of the restoration, a nested restoration,
  * sharded handles. */
 typedef struct iem_resto iem_resto;
 typedef struct {
@@ -1043,7 +1043,7 @@ int iem_resto_source(char **out_src, uint64_t *out_key);
  * replays across a change of mu, and the host reads one struct per iteration (iem_mu_state).
  *
  * THE BLOCK: sixteen 8-byte words on the device (iem_mu_device gives the pointer):
- *     0 mu      1 tau = max(tau_min, 1 − mu)      2 zeta = sqrt(mu) (kept for a later restoration binding)      3 E(0)
+ *     0 mu      1 tau = max(tau_min, 1 − mu)      2 zeta = sqrt(mu) (what a bound iem_resto reads: iem_resto_bind_mu)      3 E(0)
  *     4 E(mu) at the mu the call leaves behind      5 e_d      6 e_p      7 e_c(0)
  *     8 status (int64): 0 ITERATING, 1 CONVERGED, 2 UNUSABLE      9 flags (int64): bit 0 = mu changed in the last update
  *     10 decreases so far (int64)      11 updates so far (int64)      12–15 zero
@@ -1072,13 +1072,13 @@ int iem_resto_source(char **out_src, uint64_t *out_key);
  *     barrier_step tau from word 1) where they read their argument before, once, at the same place: the host's mu and tau arguments
  *     and their range checks are ignored.  Unbound, every call writes the bits it wrote before.  Binding is per object: the inner
  *     search of an iem_resto borrows the same barrier object and keeps the restoration problem's own mu — bind the barrier object
- *     only while the original problem iterates.  iem_resto_* never reads the block.
+ *     only while the original problem iterates.  iem_resto_* reads a block only once bound to an iem_rmu (iem_resto_bind_mu).
  * Every call runs on the handle's stream, asynchronous, capturable; nothing allocates after create, nothing synchronises and nothing
  * is copied to the host, except by iem_mu_state.  IEM_E_ARG before any device work: null required pointers (the slack side may be
  * NULL without inequality rows), mu_init <= 0, kappa_mu or tau_min outside (0, 1), kappa_eps <= 0, tol <= 0, mu_floor < 0,
  * s_max <= 0, any option not finite, mu0 <= 0 or not finite, an fs or a bind across two barrier objects.  The object borrows the
  * barrier object; a bound object borrows the block: unbind (or destroy the bound objects) before iem_mu_destroy.  Not here: the
- * delta_w / inertia retry, a binding for iem_resto, sharded handles.  The adaptive rules that words 8 and 9 of iem_mu_error
+ * delta_w / inertia retry, sharded handles.  The adaptive rules that words 8 and 9 of iem_mu_error
  * serve (probing, LOQO) are the iem_amu object below, the quality-function oracle the iem_qf object below it, Mehrotra's corrector
  * the iem_mpc object below that. */
 typedef struct iem_mu iem_mu;
@@ -1161,7 +1161,7 @@ int iem_barrier_mu_source(char **out_src, uint64_t *out_key);
  * another barrier object, oracle not 0 or 1, sigma_max, mu_min, mu_max_fact or init_factor <= 0, red_fact outside (0, 1), refs_max
  * outside 1..4, any option not finite.  The object borrows the iem_mu object: destroy it first.  Ipopt's quality-function oracle
  * (oracle = 2 here is refused) is the iem_qf object below, Mehrotra's corrector the iem_mpc object below that.  Not here: the
- * obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the delta_w / inertia retry (the host's). */
+ * obj-constr-filter globalisation, sharded handles, the delta_w / inertia retry (the host's). */
 typedef struct iem_amu iem_amu;
 typedef struct {
   uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_amu_opts_t) */
@@ -1267,7 +1267,7 @@ int iem_amu_source(char **out_src, uint64_t *out_key);
  * required pointers (the slack side may be NULL without inequality rows), an fs of another barrier object, mu_ref, sigma_min or
  * section_sigma_tol <= 0, sigma_max < 0 (0: the iem_amu object's), max_section_steps outside 1..16, any option not finite.  The
  * object borrows the iem_amu object: destroy it first.  Mehrotra's corrector is the iem_mpc object below.  Not here: Ipopt's other
- * norm types, the centrality and balancing terms, the obj-constr-filter globalisation, a binding for iem_resto, sharded handles, the
+ * norm types, the centrality and balancing terms, the obj-constr-filter globalisation, sharded handles, the
  * delta_w / inertia retry. */
 typedef struct iem_qf iem_qf;
 typedef struct {
@@ -1524,7 +1524,7 @@ int iem_init_source(char **out_src, uint64_t *out_key);
  * without rows), a tolerance that is <= 0 or a NaN (+inf is allowed and switches that test off), a negative max_iter or
  * acceptable_iter, a struct_size that is not the struct's.  The object borrows the iem_mu object: destroy it first.  Not here: the
  * delta_w / inertia retry, Ipopt's skipping of the line search on a tiny step, max_cpu_time, a freeze of the other kernels behind the
- * latch (a replay past a terminal status keeps iterating; iem_conv_restore is what hands back the point), a binding for iem_resto,
+ * latch (a replay past a terminal status keeps iterating; iem_conv_restore is what hands back the point),
  * scaled against unscaled problems (the tolerances apply in the scaling the caller evaluates in), sharded handles. */
 typedef struct iem_conv iem_conv;
 typedef struct {
@@ -1554,6 +1554,109 @@ int iem_conv_device(const iem_conv *q, double **d_block);
 int iem_conv_state(iem_conv *q, iem_conv_state_t *out);      /* synchronises the stream: the one read-back */
 /* HIP source of the seven kernels and its cache key — for offline builds (no device needed; malloc'ed) */
 int iem_conv_source(char **out_src, uint64_t *out_key);
+
+/* ---- the restoration phase's barrier parameter ---------------------------------------------------------------------------------------
+ * The restoration problem's own mu on the device (csrc/iem_rmu_device.h), as an object created ON an iem_resto: Ipopt's monotone rule
+ * for the restoration problem, the exit "converged to a point of local infeasibility" (STATIONARY), the start of a phase
+ * (mu_R = max(mu, max |inf|)), Ipopt's alpha_min rule behind an iem_search_accept, and the BOUND variant of the restoration code
+ * object, whose kernels read mu, tau and zeta from a block instead of host doubles.  One captured restoration iteration
+ *     iem_eval_residual(0);  iem_rmu_error;  iem_rmu_update;  iem_jac_hess_coord(0);  iem_resto_terms;  assemble;  factor;  refined solve;
+ *     iem_resto_step;  iem_resto_merit(0);  iem_resto_begin;  K x { iem_resto_trial, iem_cons, iem_resto_merit(1), iem_search_accept(inner),
+ *     iem_rmu_trigger(1) };  iem_resto_update;  iem_obj_device;  iem_cons;  iem_barrier_merit;  iem_resto_check
+ * then replays across a change of the restoration's mu, and the host reads one struct per iteration (iem_rmu_state).
+ *
+ * The object owns a genuine iem_mu object on the same barrier object — the RESTORATION BLOCK, the sixteen words of the iem_mu block,
+ * built by iem_mu_create with the options below; iem_rmu_mu returns it (never to be destroyed by the caller; iem_mu_device,
+ * iem_mu_state and iem_search_bind_mu(inner, ...) apply to it) — and its OWN BLOCK of sixteen 8-byte words (iem_rmu_device):
+ *     0 status (int64): 0 ITERATING, 1 STATIONARY, 2 UNUSABLE      1 flags (int64): bit 0 = mu changed in the last update, bit 1 = the
+ *     ladder of the last update was truncated      2 decreases in the last update (int64)      3 decreases since enter (int64)
+ *     4 E_R(0)      5 E_R(mu) at the mu the update leaves      6 mu at enter      7 max |inf| at enter
+ *     8 alpha_min of the last trigger call that evaluated it      9 triggers fired on the original search (int64)
+ *     10 triggers fired on the inner search (int64)      11-15 zero
+ * IEM_RMU_K = 6 candidates is a compile-time constant: one update decreases mu at most IEM_RMU_K − 1 = 5 times.
+ * iem_rmu_enter(d_err: the 8 words of iem_barrier_error or the first 8 of iem_mu_error at this point; mu_host): one workgroup, one
+ *     thread decides.  mu_orig = word 0 of the original block when par_orig was given, otherwise mu_host;  mu_R = max(mu_orig, d_err[2])
+ *     (a NaN propagates).  mu_R a NaN or not > 0: status UNUSABLE and nothing else moves.  Otherwise the restoration block is written bit
+ *     for bit as iem_mu_reset(p, mu_R) writes it, the own block is zeroed except word 6 = mu_R and word 7 = d_err[2], and words 11, 12
+ *     of the inner search's control block are zeroed (the 16 bytes of iem_search_reset).  Issue it in front of iem_resto_enter: bound,
+ *     that call takes mu_R from the block.  The trigger counters (words 9, 10) start from zero with the phase: a caller who counts over a
+ *     whole solve reads them (iem_rmu_state) in front of the next iem_rmu_enter and carries them over.
+ * iem_rmu_error: ONE launch on the barrier object's grid behind one 256-byte device-to-device copy (the seed), 32 words.  The
+ *     candidates  mu_0 = word 0, zeta_0 = word 2 of the restoration block,  mu_{k+1} = max(mu_floor, min(kappa_mu·mu_k,
+ *     mu_k·sqrt(mu_k))),  zeta_{k+1} = sqrt(mu_{k+1})  are formed once per thread.  With E the output of iem_resto_error:
+ *     [0]-[7] bit for bit iem_resto_error(mu = 0, zeta = zeta_0) on the same inputs (same per-lane order, same fixed-order totals; the
+ *     partial sums are the restoration block's own)  [8] the minimum, [9] the sum, [10] the count of unusable values of the
+ *     complementarity products exactly as iem_mu_error defines its words 8-10, taken over the present bounds AND p·zp, n·zn on every
+ *     row (a lane's entries in index order; per row the slack's bounds, then p·zp, then n·zn)  [11] +0.0
+ *     [12 + 3k] mu_k, [13 + 3k] E[0] at zeta_k, [14 + 3k] E[1] at zeta_k for k = 0..5 (integer maxima on bit patterns: a NaN gives a NaN)
+ *     [30], [31] +0.0.  d_r is required: no NaN form.
+ * iem_rmu_update(d_out32): one workgroup, one thread decides, each operation rounded once, every max / min propagating a NaN.  With w
+ *     the 32 words, m = ncon and nzr = nz + 2·ncon:
+ *         sd = max(s_max, (w4 + w5)/max(1, m + nzr))/s_max      sc = max(s_max, w5/max(1, nzr))/s_max
+ *         E_k(mu) = max(max(max(w[13+3k], w[14+3k])/sd, m ? w2 : 0), nzr ? max(w3 − mu, mu − w8)/sc : 0)
+ *     w10 != 0 or E_0(0) a NaN: UNUSABLE.  Else E_0(0) <= tol: STATIONARY.  In both the restoration block and the filter stay (j = 0).
+ *     Else ITERATING and  j = 0;  while j < 5 and mu_j > mu_floor and E_j(mu_j) <= kappa_eps·mu_j:  j += 1  (mu_j = w[12+3j]); when
+ *     the condition still holds at j = 5, flag bit 1 is set (otherwise cleared) and the next update goes on from there.  j > 0: words
+ *     0-2 of the restoration block become mu_j, max(tau_min, 1 − mu_j), sqrt(mu_j), flag bit 0 is set, word 2 = j, word 3 grows by j,
+ *     and the inner filter is emptied.  j = 0: flag bit 0 is cleared, word 2 = 0, block and filter stay untouched.  Status, word 4 =
+ *     E_0(0) and word 5 = E_j(mu_j) are stored either way.  The status is not latched: the next update decides again.
+ * iem_rmu_trigger(which: 0 the original search of the iem_resto, 1 its inner search; d_alpha: that search's step lengths): one
+ *     workgroup of 64 behind an iem_search_accept.  With a status other than SEARCHING it writes nothing.  Otherwise, with that
+ *     search's options and words 0 (alpha), 3 (theta0), 4 (slope), 5 (theta_min) of its control block:  a = gamma_theta;  slope < 0:
+ *     a = min(a, (gamma_phi·theta0)/(−slope));  slope < 0 and theta0 <= theta_min:  a = min(a, (delta·pow(theta0, s_theta))/pow(−slope,
+ *     s_phi));  alpha_min = gamma_alpha·a  into word 8.  alpha < alpha_min (a NaN compares false): that search's status FAILED, its
+ *     word 0 = +0.0, d_alpha[0] = +0.0, counter 9 + which grows.  Idempotent.  Issued behind every accept it is Ipopt's rule exactly;
+ *     issued once per captured ladder of `rungs` accepts it lets at most rungs − 1 further halvings through.  No kernel of iem_search
+ *     changes.
+ * iem_rmu_state: the one read-back — one gather launch, ONE copy, one synchronisation: the own block, the restoration block and
+ *     the block of the iem_resto.
+ * iem_resto_bind_mu(q, rp; NULL unbinds): no launch; the first bind of a handle loads the bound variant of the restoration code
+ *     object (iem_resto_mu_source: the ONE text of iem_resto_source with RestoArgs two pointers longer and the reads edited), so bind
+ *     outside a capture.  While bound, resto_enter / _terms / _step / _begin / _update / _error read mu from word 0 of the restoration
+ *     block, resto_step tau from word 1, and every kernel that takes zeta (terms, step, merit, begin, error) reads it from word 2 —
+ *     once, where the kernel read its argument before; resto_check reads the ORIGINAL problem's mu from word 0 of par_orig's block when
+ *     iem_rmu_create was given one and keeps its host argument otherwise.  The host's mu / tau / zeta arguments and their range checks
+ *     are ignored.  Unbound, every iem_resto_* call writes the bits it wrote before; iem_resto_source and its key are unchanged.  The
+ *     inner search is bound with iem_search_bind_mu(inner, the object iem_rmu_mu returns).
+ * Every call but iem_rmu_state runs on the handle's stream, asynchronous, capturable; nothing allocates after create.  No float atomic,
+ * no cooperative launch.  IEM_E_ARG before any device work: null required pointers, an option that is not finite, not positive, or
+ * (kappa_mu, tau_min, gamma_alpha) not below 1, a par_orig or a bind across two objects, which outside {0, 1}.  The object borrows the
+ * iem_resto (destroy it first); iem_rmu_destroy unbinds that iem_resto and its inner search where they still read the block.  Not
+ * here: adaptive rules for the restoration, the restoration's own second-order correction, a nested restoration, the delta_w /
+ * inertia retry, a warm start of iem_resto, sharded handles. */
+#define IEM_RMU_K 6
+typedef struct iem_rmu iem_rmu;
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_rmu_opts_t) */
+  double kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max, gamma_alpha;
+} iem_rmu_opts_t;                       /* NULL = 10, 0.2, 0.99, 1e-8, 1e-11, 100, 0.05 */
+typedef struct {
+  uint64_t struct_size;                 /* set by the CALLER to sizeof(iem_rmu_state_t): at most that many bytes are written */
+  int64_t status, flags, decreases_last, decreases;        /* words 0–3 of the own block */
+  double e0, e_mu, mu_enter, inf_enter, alpha_min;         /* words 4–8 */
+  int64_t triggers_orig, triggers_inner;                   /* words 9, 10 */
+  double mu, tau, zeta, mu_e0, mu_e_mu, mu_e_d, mu_e_p, mu_e_c0;      /* words 0–7 of the restoration block */
+  int64_t mu_status, mu_flags, mu_decreases, mu_updates;   /* words 8–11 of the restoration block */
+  int64_t resto_state;                  /* word 0 of the iem_resto block */
+  double theta_start, theta, phi;       /* words 1–3 of the iem_resto block */
+} iem_rmu_state_t;
+enum { IEM_RMU_ITERATING = 0, IEM_RMU_STATIONARY = 1, IEM_RMU_UNUSABLE = 2 };
+int iem_rmu_create(iem_resto *q, const iem_mu *par_orig /* may be NULL */, const iem_rmu_opts_t *opts, iem_rmu **out);
+int iem_rmu_destroy(iem_rmu *rp);
+int iem_rmu_mu(const iem_rmu *rp, const iem_mu **out_par);      /* the restoration block's object: owned by rp, never to be destroyed */
+int iem_rmu_enter(iem_rmu *rp, const double *d_err /* 8 */, double mu_host);
+int iem_rmu_error(iem_rmu *rp, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
+                  const double *d_vU, const double *d_r, const double *d_c, double *d_out /* 32 */);
+int iem_rmu_update(iem_rmu *rp, const double *d_out32);
+int iem_rmu_trigger(iem_rmu *rp, int which, double *d_alpha /* 2 */);
+int iem_rmu_device(const iem_rmu *rp, double **d_block);
+int iem_rmu_state(iem_rmu *rp, iem_rmu_state_t *out);      /* synchronises the stream: the one read-back */
+int iem_resto_bind_mu(iem_resto *q, const iem_rmu *rp /* NULL unbinds */);
+/* HIP source of the five kernels and its cache key — for offline builds (no device needed; malloc'ed) */
+int iem_rmu_source(char **out_src, uint64_t *out_key);
+/* ... and of the BOUND variant of the restoration code object; iem_resto_bind_mu loads it.  iem_resto_source, its key and the unbound
+ * calls are unchanged */
+int iem_resto_mu_source(char **out_src, uint64_t *out_key);
 
 /* ---- kernel generation (no device needed) ---------------------------------------
  * The evaluator of a model is specialised HIP source generated from its templates

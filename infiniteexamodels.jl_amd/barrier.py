@@ -1322,6 +1322,14 @@ class Restoration:
         L, q = self._handle()
         _lib.check(L.iem_resto_check(q, *args))
 
+    def bind_mu(self, param=None):
+        """While bound to a :class:`RestorationParameter` created on this object (``iem_resto_bind_mu``), every call above reads
+        ``mu``, ``tau`` and ``zeta`` from the restoration block on the device — and :meth:`check` the ORIGINAL problem's ``mu`` from
+        the original block where the parameter was given one; the host arguments are ignored.  ``None`` unbinds.  The first bind of
+        a model loads a code object: bind outside a capture."""
+        L, q = self._handle()
+        _lib.check(L.iem_resto_bind_mu(q, param._handle()[1] if param is not None else None))
+
     def leave(self, state):
         """``y = 0``, the bound multipliers reset to 1 iff their maximum exceeds the threshold, state ``none`` (``iem_resto_leave``)."""
         p = self.layer._state(state)
@@ -1379,3 +1387,135 @@ class _BorrowedSearch(FilterSearch):
 
     def close(self):
         self._s = None
+
+
+class _BorrowedParameter(BarrierParameter):
+    """the restoration block of a :class:`RestorationParameter`: :meth:`state`, :meth:`device` and ``FilterSearch.bind_mu`` of
+    :class:`BarrierParameter` on a handle the restoration parameter owns"""
+
+    def __init__(self, layer: BarrierLayer, handle, opts):
+        self.layer = layer
+        self._p = handle
+        self.opts = dict(opts)
+
+    def close(self):
+        self._p = None
+
+
+class RestorationParameter:
+    """``RestorationParameter(resto, par_orig=None, **opts)``: the restoration problem's own barrier parameter of the C-ABI
+    (``iem_rmu_*``, ``csrc/iem_rmu_device.h``) ON a :class:`Restoration` — the monotone rule over ``lib.RMU_K`` fixed candidates,
+    the exit at a stationary point of the infeasibility, the start of a phase and Ipopt's ``alpha_min`` rule, every decision on the
+    device.  ``par_orig``: the ORIGINAL problem's :class:`BarrierParameter`, whose ``mu`` :meth:`enter` and a bound
+    ``Restoration.check`` then read from its block.  ``opts``: ``kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max, gamma_alpha``.
+    With ``resto.bind_mu(rp)`` and ``resto.inner.bind_mu(rp.inner_mu)`` the restoration iteration of :class:`Restoration` becomes
+
+        rp.enter(err, mu); resto.enter(state, c, 0.0)                  # mu_R = max(mu, err[2]) on the device
+        while True:
+            model.eval_residual(x, y, 0.0, c=c, out=r)
+            w = rp.error(state, r, c, out=w); rp.update(w)             # the rule; empties the inner filter iff mu moved
+            ...                                                        # terms, solve, step, merit, begin: the scalars are ignored
+            for _ in range(K):
+                resto.trial(...); model.cons(xt, ct); mt = resto.merit(1, xt, st, ct, 0.0)
+                resto.inner.accept(mt[0:1], mt[1:3], 0.0, alpha); rp.trigger(1, alpha)
+            resto.update(...); ...; resto.check(f, m2, mu)
+            st = rp.state()                                            # THE read-back: the rule, the block, the phase's state
+
+    — one graph for every ``mu`` of the phase."""
+
+    def __init__(self, resto: Restoration, par_orig: BarrierParameter = None, **opts):
+        self.resto = resto
+        self.layer = resto.layer
+        self.par_orig = par_orig
+        self._r = None
+        self.inner_mu = None
+        o = _lib.RmuOpts.defaults(**opts)
+        self.opts = {name: getattr(o, name) for name, _ in _lib.RmuOpts._fields_ if name != "struct_size"}
+        L, q = resto._handle()
+        rp = C.c_void_p()
+        _lib.check(L.iem_rmu_create(q, par_orig._handle()[1] if par_orig is not None else None, C.byref(o), C.byref(rp)))
+        self._r = rp
+        par = C.c_void_p()
+        _lib.check(L.iem_rmu_mu(rp, C.byref(par)))
+        self.inner_mu = _BorrowedParameter(self.layer, par, dict(self.opts, mu_init=0.1))
+
+    def _handle(self):
+        if self._r is None:
+            raise _lib.IemError("RestorationParameter: closed")
+        L, _ = self.resto._handle()
+        return L, self._r
+
+    def enter(self, err, mu: float = 0.0):
+        """The start of a phase (``iem_rmu_enter``): ``mu_R = max(mu, err[2])`` into the restoration block, the own block zeroed, the
+        inner filter emptied; ``err``: the eight words of ``BarrierLayer.error`` (or the first of ``BarrierParameter.error``) at this
+        point; ``mu`` is ignored where a ``par_orig`` was given.  Issue it in front of ``Restoration.enter``."""
+        bar = self.layer
+        pe = bar._vec(err[:8], 8, "err")
+        L, rp = self._handle()
+        _lib.check(L.iem_rmu_enter(rp, pe, float(mu)))
+
+    def error(self, state, r, c, out=None):
+        """The 32 words of ``iem_rmu_error`` as a device tensor: ``Restoration.error(state, r, c, 0, zeta_0)`` bit for bit, the
+        minimum, sum and unusable count of the complementarity products, then ``(mu_k, E[0], E[1])`` of each candidate."""
+        bar = self.layer
+        out = out if out is not None else bar._new(32)
+        ps = bar._state(state)
+        args = (bar._vec(r, bar.nvar, "r"), bar._vec(c, bar.ncon, "c"), bar._vec(out, 32, "out"))
+        L, rp = self._handle()
+        _lib.check(L.iem_rmu_error(rp, *ps, *args))
+        return out
+
+    def update(self, out32):
+        """The rule on the device (``iem_rmu_update``) from the 32 words of :meth:`error`."""
+        pw = self.layer._vec(out32, 32, "out32")
+        L, rp = self._handle()
+        _lib.check(L.iem_rmu_update(rp, pw))
+
+    def trigger(self, which: int, alpha):
+        """Ipopt's ``alpha_min`` rule (``iem_rmu_trigger``) behind an ``accept`` of the original search of the restoration
+        (``which = 0``) or of its inner search (``which = 1``); ``alpha``: that search's step lengths."""
+        pa = self.layer._vec(alpha, 2, "alpha")
+        L, rp = self._handle()
+        _lib.check(L.iem_rmu_trigger(rp, int(which), pa))
+
+    def state(self):
+        """THE read-back (``iem_rmu_state``, one copy, synchronises once): the own block, the restoration block (``mu, tau, zeta``,
+        ``mu_*``) and the restoration's state, ``status`` and ``resto_state`` also by name, ``changed`` / ``truncated`` = flag bits."""
+        L, rp = self._handle()
+        v = _lib.RmuState()
+        v.struct_size = C.sizeof(_lib.RmuState)
+        _lib.check(L.iem_rmu_state(rp, C.byref(v)))
+        out = {name: getattr(v, name) for name, _ in _lib.RmuState._fields_ if name != "struct_size"}
+        out["status_name"] = _lib.RMU_STATUS[out["status"]] if 0 <= out["status"] < len(_lib.RMU_STATUS) else "?"
+        out["resto_state_name"] = _lib.RESTO_STATE[out["resto_state"]] if 0 <= out["resto_state"] < len(_lib.RESTO_STATE) else "?"
+        out.update(changed=bool(out["flags"] & 1), truncated=bool(out["flags"] & 2))
+        return out
+
+    def device(self):
+        """The address of the object's own block (16 words) on the device (``iem_rmu_device``)."""
+        L, rp = self._handle()
+        blk = C.c_void_p()
+        _lib.check(L.iem_rmu_device(rp, C.byref(blk)))
+        return blk.value
+
+    def close(self):
+        """Unbinds the restoration object and its inner search where they still read the block."""
+        if self._r is not None:
+            if self.inner_mu is not None:
+                self.inner_mu._p = None      # owned by the object: destroyed with it
+            _lib.check(self.layer.model._L.iem_rmu_destroy(self._r))
+            self._r = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            if self.resto._q is not None and self.resto.search._s is not None and self.layer._b is not None and getattr(self.layer.model, "_h", None):
+                self.close()
+        except Exception:
+            pass

@@ -79,6 +79,9 @@ static const char *kInitSource =          // the starting point (iem_init_*): a 
 static const char *kConvSource =          // the stopping test and the kept iterate (iem_conv_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
 #include "iem_conv_device_h.inc"
     ;
+static const char *kRmuSource =           // the restoration phase's barrier parameter (iem_rmu_*): a code object of its own, behind the helpers of the device header — not a row of kFixed
+#include "iem_rmu_device_h.inc"
+    ;
 
 namespace {
 
@@ -352,6 +355,8 @@ struct iem_model {
   struct MpcObject { hipModule_t mod = nullptr; hipFunction_t terms = nullptr, step = nullptr, select = nullptr, reset = nullptr; } mpc;      // Mehrotra's corrector (iem_mpc_*): loaded by the first iem_mpc_create
   struct InitObject { hipModule_t mod = nullptr; hipFunction_t ls_terms = nullptr, ls_norm = nullptr, ls_apply = nullptr, warm = nullptr, mu = nullptr, reset = nullptr; } init;      // the starting point (iem_init_*): loaded by the first iem_init_create
   struct ConvObject { hipModule_t mod = nullptr; hipFunction_t xmax = nullptr, decide = nullptr, stepmax = nullptr, step_decide = nullptr, keep = nullptr, restore = nullptr, reset = nullptr; } conv;      // the stopping test (iem_conv_*): loaded by the first iem_conv_create
+  RestoObject resto_mu;      // the restoration kernels that read mu, tau and zeta from an iem_mu block (resto_mu_source): loaded by the first iem_resto_bind_mu
+  struct RmuObject { hipModule_t mod = nullptr; hipFunction_t error = nullptr, enter = nullptr, update = nullptr, trigger = nullptr, gather = nullptr; } rmu;      // the restoration's barrier parameter (iem_rmu_*): loaded by the first iem_rmu_create
   // `kb_part`: the column sums' workspace of the raw calls iem_kkt_border_factor / _solve (grown on demand)
   double *kb_part = nullptr;
   int64_t kb_part_n = 0;
@@ -1400,6 +1405,8 @@ int iem_destroy(iem_model *m) {
   if (m->mpc.mod) hipModuleUnload(m->mpc.mod);
   if (m->init.mod) hipModuleUnload(m->init.mod);
   if (m->conv.mod) hipModuleUnload(m->conv.mod);
+  if (m->resto_mu.mod) hipModuleUnload(m->resto_mu.mod);
+  if (m->rmu.mod) hipModuleUnload(m->rmu.mod);
   if (m->barrier_mu.mod) hipModuleUnload(m->barrier_mu.mod);
   if (m->kb_part) hipFree(m->kb_part);
   for (double *r : m->d_pc_spare) if (r) hipFree(r);
@@ -4537,6 +4544,8 @@ struct iem_resto {
   double *d_vec = nullptr;             // p | n | zp | zn | dp | dn | dzp | dzn | pt | nt | sR | ws (ncon each) | xR | wx (nvar each)
   double *d_blk = nullptr;             // the block: 8 words
   double *d_red = nullptr;             // 4 n_wg parked values + the ticket words (zeroed once; the tickets reset themselves)
+  const double *mu_blk = nullptr;      // iem_resto_bind_mu: the restoration block of an iem_rmu object (borrowed), or null
+  const double *mu_orig_blk = nullptr; // ... and the ORIGINAL problem's iem_mu block that object was given, or null
 };
 
 namespace {
@@ -4561,6 +4570,7 @@ struct RestoArgsH {
   double mu, tau, kappa, zeta, rho, kappa_resto, threshold, gamma_theta, gamma_phi;
   long long capacity, which;
   long long nvar, n, n_wg;
+  const double *mu_blk, *mu_orig_blk;
 };
 enum { RES_ENTER, RES_ENTER_FILTER, RES_TERMS, RES_STEP, RES_MERIT, RES_BEGIN, RES_TRIAL, RES_UPDATE, RES_ERROR, RES_CHECK, RES_LEAVE_MAX, RES_LEAVE, RES_KERNELS };
 const char *const kRestoKernels[RES_KERNELS] = {"resto_enter", "resto_enter_filter", "resto_terms", "resto_step", "resto_merit", "resto_begin",
@@ -4581,6 +4591,7 @@ RestoArgsH resto_args(const iem_resto *q) {
   A.rho = q->opt.rho; A.kappa_resto = q->opt.kappa_resto; A.threshold = q->opt.bound_mult_reset_threshold;
   A.gamma_theta = s->opt.gamma_theta; A.gamma_phi = s->opt.gamma_phi; A.capacity = (long long)s->opt.filter_capacity;
   A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  A.mu_blk = q->mu_blk; A.mu_orig_blk = q->mu_orig_blk;
   return A;
 }
 int resto_object(iem_model *m) {
@@ -4593,9 +4604,54 @@ int resto_object(iem_model *m) {
   for (int k = 0; k < RES_KERNELS; ++k) slots[k] = KernelSlot{kRestoKernels[k], &o.fn[k]};
   return load_object(m, src, slots, RES_KERNELS, &o.mod);
 }
+// unbound: the restoration object as it always was (its RestoArgs ends in front of mu_blk); bound: the variant below, which reads the block
 int resto_launch(const iem_resto *q, int which, RestoArgsH &A, bool one_wave = false) {
   iem_model *m = q->s->b->m;
-  return kkt_launch_raw(m, m->resto.fn[which], &A, sizeof A, one_wave ? 1 : q->s->b->n_wg, one_wave ? 64 : 256);
+  const long long grid = one_wave ? 1 : q->s->b->n_wg;
+  if (A.mu_blk) return kkt_launch_raw(m, m->resto_mu.fn[which], &A, sizeof A, grid, one_wave ? 64 : 256);
+  return kkt_launch_raw(m, m->resto.fn[which], &A, offsetof(RestoArgsH, mu_blk), grid, one_wave ? 64 : 256);
+}
+// The BOUND variant of the restoration code object: the text of csrc/iem_resto_device.h with RestoArgs two pointers longer and the
+// single read of mu, tau and zeta in every kernel that takes one taken from the restoration block {mu, tau, zeta, ...}; resto_check
+// takes the ORIGINAL problem's mu from word 0 of the original block where there is one — derived from the one text, so that the
+// unbound object keeps its source, its key and its bits, and the two cannot drift apart.  Every pattern must match exactly as often
+// as listed: an edit of the header that breaks one is an error here, not a silently unbound kernel.
+int resto_mu_source(std::string &s) {
+  static const struct { const char *from, *to; int times; } kEdits[] = {
+      {"  long long nvar, n, n_wg;\n};",
+       "  long long nvar, n, n_wg;\n  const double *mu_blk, *mu_orig_blk;      // the restoration block {mu, tau, zeta, ...}; the ORIGINAL iem_mu block or null\n};", 1},
+      {"  const double mu = A.mu, rho = A.rho, rho2 = 2.0 * A.rho;\n", "  const double mu = A.mu_blk[0], rho = A.rho, rho2 = 2.0 * A.rho;\n", 1},      // resto_enter
+      {"  const double mu = A.mu, zeta = A.zeta;\n", "  const double mu = A.mu_blk[0], zeta = A.mu_blk[2];\n", 1},      // resto_terms
+      {"  const double mu = A.mu, tau = A.tau, ntau = -A.tau, zeta = A.zeta;\n",
+       "  const double mu = A.mu_blk[0], tau = A.mu_blk[1], ntau = -tau, zeta = A.mu_blk[2];\n", 1},      // resto_step
+      {"(0.5 * A.zeta) * lds[1]", "(0.5 * A.mu_blk[2]) * lds[1]", 1},      // resto_merit
+      {"  const double mu = A.mu, zeta = A.zeta, rho = A.rho;\n", "  const double mu = A.mu_blk[0], zeta = A.mu_blk[2], rho = A.rho;\n", 2},      // resto_begin, resto_error
+      {"  const double mu = A.mu, kappa = A.kappa;\n", "  const double mu = A.mu_blk[0], kappa = A.kappa;\n", 1},      // resto_update
+      {"A.f[0] - A.mu * A.merit[1]", "A.f[0] - (A.mu_orig_blk ? A.mu_orig_blk[0] : A.mu) * A.merit[1]", 1},      // resto_check
+  };
+  std::string text(kRestoSource);
+  for (const auto &e : kEdits) {
+    const std::string from(e.from), to(e.to);
+    int seen = 0;
+    for (size_t at = text.find(from); at != std::string::npos; at = text.find(from, at + to.size())) {
+      text.replace(at, from.size(), to);
+      ++seen;
+    }
+    if (seen != e.times) return fail(IEM_E_COMPILE, std::string("internal: the restoration kernels do not read mu where the bound variant expects it: ") + e.from);
+  }
+  if (text.find("A.mu,") != std::string::npos || text.find("A.tau") != std::string::npos || text.find("A.zeta") != std::string::npos)
+    return fail(IEM_E_COMPILE, "internal: the bound variant of the restoration kernels still reads a host scalar");
+  return object_source(text.c_str(), true, s);
+}
+int resto_mu_object(iem_model *m) {
+  iem_model::RestoObject &o = m->resto_mu;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = resto_mu_source(src);
+  if (rc) return rc;
+  KernelSlot slots[RES_KERNELS];
+  for (int k = 0; k < RES_KERNELS; ++k) slots[k] = KernelSlot{kRestoKernels[k], &o.fn[k]};
+  return load_object(m, src, slots, RES_KERNELS, &o.mod);
 }
 int resto_opts(const iem_resto_opts_t *in, iem_resto_opts_t *out) {
   iem_resto_opts_t v = {sizeof v, 1000.0, 0.9, 1000.0};      // Ipopt's rho, required_infeasibility_reduction, bound_mult_reset_threshold
@@ -4680,7 +4736,7 @@ int iem_resto_search(const iem_resto *q, iem_search **out_inner) {
 
 int iem_resto_enter(iem_resto *q, const double *d_x, const double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_c,
                     double mu) {
-  int rc = resto_scalars("iem_resto_enter", mu, 0.0);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_enter", mu, 0.0);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!q || barrier_state_missing(q->s->b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (q->s->b->ncon && !d_c)) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(q->s->b->m->device);
@@ -4693,7 +4749,7 @@ int iem_resto_enter(iem_resto *q, const double *d_x, const double *d_s, double *
 
 int iem_resto_terms(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                     const double *d_vU, const double *d_r, const double *d_c, double mu, double zeta, double *d_sigma, double *d_dcon, double *d_rhs) {
-  int rc = resto_scalars("iem_resto_terms", mu, zeta);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_terms", mu, zeta);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!q) return fail(IEM_E_ARG, "null argument");
   const iem_barrier *b = q->s->b;
@@ -4709,7 +4765,7 @@ int iem_resto_terms(iem_resto *q, const double *d_x, const double *d_s, const do
 int iem_resto_step(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                    const double *d_vU, const double *d_sol, double mu, double tau, double zeta, double *d_ds, double *d_dzL, double *d_dzU,
                    double *d_dvL, double *d_dvU, double *d_alpha) {
-  int rc = resto_scalars("iem_resto_step", mu, zeta, tau);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_step", mu, zeta, tau);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!q) return fail(IEM_E_ARG, "null argument");
   const iem_barrier *b = q->s->b;
@@ -4727,7 +4783,7 @@ int iem_resto_step(iem_resto *q, const double *d_x, const double *d_s, const dou
 }
 
 int iem_resto_merit(iem_resto *q, int which, const double *d_x, const double *d_s, const double *d_c, double zeta, double *d_out) {
-  int rc = resto_scalars("iem_resto_merit", 0.0, zeta);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_merit", 0.0, zeta);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (which != 0 && which != 1) return fail(IEM_E_ARG, "iem_resto_merit: which must be 0 (the state) or 1 (the trial point)");
   if (!q) return fail(IEM_E_ARG, "null argument");
@@ -4741,7 +4797,7 @@ int iem_resto_merit(iem_resto *q, int which, const double *d_x, const double *d_
 
 int iem_resto_begin(iem_resto *q, const double *d_x, const double *d_s, const double *d_sol, const double *d_ds, const double *d_merit0, const double *d_alpha,
                     double mu, double zeta) {
-  int rc = resto_scalars("iem_resto_begin", mu, zeta);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_begin", mu, zeta);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!q) return fail(IEM_E_ARG, "null argument");
   const iem_barrier *b = q->s->b;
@@ -4765,7 +4821,7 @@ int iem_resto_trial(iem_resto *q, const double *d_x, const double *d_s, const do
 int iem_resto_update(iem_resto *q, double *d_x, double *d_s, double *d_y, double *d_zL, double *d_zU, double *d_vL, double *d_vU, const double *d_sol,
                      const double *d_ds, const double *d_dzL, const double *d_dzU, const double *d_dvL, const double *d_dvU, const double *d_alpha, double mu,
                      double kappa_sigma) {
-  int rc = resto_scalars("iem_resto_update", mu, 0.0);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_update", mu, 0.0);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!(kappa_sigma >= 1.0)) return fail(IEM_E_ARG, "iem_resto_update: kappa_sigma must be at least 1");
   if (!q) return fail(IEM_E_ARG, "null argument");
@@ -4783,7 +4839,7 @@ int iem_resto_update(iem_resto *q, double *d_x, double *d_s, double *d_y, double
 
 int iem_resto_error(iem_resto *q, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL,
                     const double *d_vU, const double *d_r, const double *d_c, double mu, double zeta, double *d_out) {
-  int rc = resto_scalars("iem_resto_error", mu, zeta);
+  int rc = q && q->mu_blk ? IEM_OK : resto_scalars("iem_resto_error", mu, zeta);      // (bound: the block rules, the host scalars are ignored)
   if (rc) return rc;
   if (!q) return fail(IEM_E_ARG, "null argument");
   const iem_barrier *b = q->s->b;
@@ -4798,7 +4854,7 @@ int iem_resto_error(iem_resto *q, const double *d_x, const double *d_s, const do
 }
 
 int iem_resto_check(iem_resto *q, const double *d_f, const double *d_merit, double mu) {
-  int rc = resto_scalars("iem_resto_check", mu, 0.0);
+  int rc = q && q->mu_orig_blk ? IEM_OK : resto_scalars("iem_resto_check", mu, 0.0);      // (bound with an original block: that block rules)
   if (rc) return rc;
   if (!q || !d_f || !d_merit) return fail(IEM_E_ARG, "null argument");
   DevGuard dg_(q->s->b->m->device);
@@ -6086,6 +6142,243 @@ int iem_conv_state(iem_conv *q, iem_conv_state_t *out) {
   HIP_TRY(hipStreamSynchronize(m->stream));
   static_assert(sizeof(iem_conv_state_t) == 20 * 8, "iem_conv_state_t: struct_size, then words 0-18 of the own block");
   std::memcpy(&out->status, w, 19 * 8);
+  return IEM_OK;
+}
+
+/* ---- the restoration phase's barrier parameter: candidates' error, the rule, enter, the alpha_min trigger, the bound restoration (csrc/iem_rmu_device.h) ---- */
+struct iem_rmu {
+  iem_resto *q = nullptr;              // the restoration object it was created on (borrowed)
+  iem_mu *par = nullptr;               // the restoration block: a genuine iem_mu object on the same barrier object (owned)
+  const iem_mu *orig = nullptr;        // the ORIGINAL problem's iem_mu object (borrowed), or null
+  iem_rmu_opts_t opt;
+  double *d_blk = nullptr;             // the own block: 16 words | the read-back's staging: 40 words | the seed of iem_rmu_error: 32 words
+};
+
+namespace {
+constexpr int kRmuWords = 16, kRmuStage = 40, kRmuOut = 32, kRmuAlloc = kRmuWords + kRmuStage + kRmuOut;
+static_assert(IEM_RMU_K == 6, "csrc/iem_rmu_device.h: RMU_K");
+// RmuArgs of csrc/iem_rmu_device.h
+struct RmuArgsH {
+  const double *xl, *xu, *rl, *ru, *ceq;
+  const unsigned char *fx, *fc;
+  const double *x, *s, *y, *zL, *zU, *vL, *vU;
+  const double *r, *c;
+  const double *p, *n_, *zp, *zn, *sR, *ws, *xR, *wx;
+  double *out;
+  const double *w;
+  double *blk;
+  double *mblk;
+  const double *oblk;
+  const double *rblk;
+  double *ctl;
+  double *ictl;
+  double *alpha;
+  double *red;
+  const long long *tab;
+  double kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max, gamma_alpha;
+  double rho, mu_host;
+  double gamma_theta, gamma_phi, delta, s_theta, s_phi;
+  long long which;
+  long long ncon, nzr;
+  long long nvar, n, n_wg;
+};
+RmuArgsH rmu_args(const iem_rmu *rp) {
+  const iem_resto *q = rp->q;
+  const iem_barrier *b = q->s->b;
+  const iem_rmu_opts_t &o = rp->opt;
+  RmuArgsH A;
+  std::memset(&A, 0, sizeof A);
+  A.xl = b->d_bounds; A.xu = A.xl + b->nvar; A.rl = A.xu + b->nvar; A.ru = A.rl + b->ncon; A.ceq = A.ru + b->ncon;
+  A.fx = b->d_flags; A.fc = A.fx + b->nvar;
+  const double *v = q->d_vec;
+  const int64_t m = b->ncon;
+  A.p = v; A.n_ = v + m; A.zp = v + 2 * m; A.zn = v + 3 * m; A.sR = v + 10 * m; A.ws = v + 11 * m; A.xR = v + 12 * m; A.wx = A.xR + b->nvar;
+  A.blk = rp->d_blk; A.mblk = rp->par->d_blk; A.oblk = rp->orig ? rp->orig->d_blk : nullptr; A.rblk = q->d_blk;
+  A.ictl = q->inner->d_ctl;
+  A.red = rp->par->d_red; A.tab = rp->par->d_tab;      // the restoration block's own partial sums: six columns, as iem_mu_error's
+  A.kappa_eps = o.kappa_eps; A.kappa_mu = o.kappa_mu; A.tau_min = o.tau_min; A.tol = o.tol; A.mu_floor = o.mu_floor; A.s_max = o.s_max; A.gamma_alpha = o.gamma_alpha;
+  A.rho = q->opt.rho;
+  A.ncon = (long long)b->ncon; A.nzr = (long long)(b->n_xl + b->n_xu + b->n_sl + b->n_su + 2 * b->ncon);
+  A.nvar = (long long)b->nvar; A.n = (long long)(b->nvar + b->ncon); A.n_wg = (long long)b->n_wg;
+  return A;
+}
+int rmu_object(iem_model *m) {
+  iem_model::RmuObject &o = m->rmu;
+  if (o.mod) return IEM_OK;
+  std::string src;
+  int rc = object_source(kRmuSource, true, src);
+  if (rc) return rc;
+  KernelSlot slots[5] = {KernelSlot{"rmu_error", &o.error}, KernelSlot{"rmu_enter", &o.enter}, KernelSlot{"rmu_update", &o.update}, KernelSlot{"rmu_trigger", &o.trigger},
+                         KernelSlot{"rmu_gather", &o.gather}};
+  return load_object(m, src, slots, 5, &o.mod);
+}
+int rmu_opts(const iem_rmu_opts_t *in, iem_rmu_opts_t *out) {
+  iem_rmu_opts_t v = {sizeof v, 10.0, 0.2, 0.99, 1e-8, 1e-11, 100.0, 0.05};      // Ipopt's barrier_tol_factor, mu_linear_decrease_factor, tau_min, tol; the floor; s_max; alpha_min_frac
+  if (in) {
+    if (in->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_rmu_create: set struct_size to sizeof(iem_rmu_opts_t) before the call");
+    std::memcpy(&v, in, (size_t)std::min<uint64_t>(in->struct_size, sizeof v));      // (fields a shorter struct does not have keep their defaults)
+    v.struct_size = sizeof v;
+  }
+  const struct { const char *name; double value; bool unit; } rows[] = {
+      {"kappa_eps", v.kappa_eps, false}, {"kappa_mu", v.kappa_mu, true}, {"tau_min", v.tau_min, true}, {"tol", v.tol, false},
+      {"mu_floor", v.mu_floor, false}, {"s_max", v.s_max, false}, {"gamma_alpha", v.gamma_alpha, true}};
+  for (const auto &r : rows) {
+    if (!std::isfinite(r.value) || !(r.value > 0.0)) return fail(IEM_E_ARG, std::string("iem_rmu_create: ") + r.name + " must be positive and finite");
+    if (r.unit && !(r.value < 1.0)) return fail(IEM_E_ARG, std::string("iem_rmu_create: ") + r.name + " must lie in (0, 1)");
+  }
+  *out = v;
+  return IEM_OK;
+}
+}  // namespace
+
+int iem_rmu_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = object_source(kRmuSource, true, s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_resto_mu_source(char **out_src, uint64_t *out_key) {
+  std::string s;
+  const int rc = resto_mu_source(s);
+  return rc ? rc : emit_out(s, out_src, out_key);
+}
+
+int iem_rmu_destroy(iem_rmu *rp) {
+  if (!rp) return IEM_OK;
+  iem_resto *q = rp->q;
+  DevGuard dg_(q->s->b->m->device);
+  if (rp->par) {
+    // whoever still reads the restoration block lets go of it: the iem_resto object and its inner search
+    if (q->mu_blk == rp->par->d_blk) { q->mu_blk = nullptr; q->mu_orig_blk = nullptr; }
+    if (q->inner->mu_blk == rp->par->d_blk) q->inner->mu_blk = nullptr;
+    iem_mu_destroy(rp->par);
+  }
+  if (rp->d_blk) hipFree(rp->d_blk);
+  delete rp;
+  return IEM_OK;
+}
+
+int iem_rmu_create(iem_resto *q, const iem_mu *par_orig, const iem_rmu_opts_t *opts, iem_rmu **out) {
+  if (!q || !out) return fail(IEM_E_ARG, "null argument");
+  iem_rmu_opts_t opt;
+  {
+    int rc = rmu_opts(opts, &opt);
+    if (rc) return rc;
+  }
+  iem_barrier *b = q->s->b;
+  if (par_orig && par_orig->b != b) return fail(IEM_E_ARG, "iem_rmu_create: the original iem_mu object was created on another barrier object");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  {
+    int rc = rmu_object(m);
+    if (rc) return rc;
+  }
+  struct Drop { void operator()(iem_rmu *p) const { iem_rmu_destroy(p); } };      // (a failed create frees what it had allocated)
+  std::unique_ptr<iem_rmu, Drop> rp(new iem_rmu);
+  rp->q = q;
+  rp->orig = par_orig;
+  rp->opt = opt;
+  {
+    iem_mu_opts_t mo = {sizeof mo, 0.1, opt.kappa_eps, opt.kappa_mu, opt.tau_min, opt.tol, opt.mu_floor, opt.s_max};      // (mu_init: iem_rmu_enter writes the block before it is read)
+    int rc = iem_mu_create(b, &mo, &rp->par);
+    if (rc) return rc;
+  }
+  HIP_TRY(hipMalloc((void **)&rp->d_blk, kRmuAlloc * 8));
+  double h[kRmuAlloc] = {};
+  h[kRmuWords + kRmuStage + 8] = std::numeric_limits<double>::infinity();      // the seed: the minimum starts from +inf, everything else from +0.0
+  HIP_TRY(hipMemcpy(rp->d_blk, h, sizeof h, hipMemcpyHostToDevice));
+  *out = rp.release();
+  return IEM_OK;
+}
+
+int iem_rmu_mu(const iem_rmu *rp, const iem_mu **out_par) {
+  if (!rp || !out_par) return fail(IEM_E_ARG, "null argument");
+  *out_par = rp->par;
+  return IEM_OK;
+}
+
+int iem_resto_bind_mu(iem_resto *q, const iem_rmu *rp) {
+  if (!q) return fail(IEM_E_ARG, "null argument");
+  if (rp && rp->q != q) return fail(IEM_E_ARG, "iem_resto_bind_mu: the iem_rmu object was created on another iem_resto object");
+  if (rp) {
+    DevGuard dg_(q->s->b->m->device);
+    int rc = resto_mu_object(q->s->b->m);
+    if (rc) return rc;
+  }
+  q->mu_blk = rp ? rp->par->d_blk : nullptr;
+  q->mu_orig_blk = rp && rp->orig ? rp->orig->d_blk : nullptr;
+  return IEM_OK;
+}
+
+int iem_rmu_enter(iem_rmu *rp, const double *d_err, double mu_host) {
+  if (!rp || !d_err) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = rp->q->s->b->m;
+  DevGuard dg_(m->device);
+  RmuArgsH A = rmu_args(rp);
+  A.w = d_err; A.mu_host = mu_host;
+  return kkt_launch_raw(m, m->rmu.enter, &A, sizeof A, 1, 64);
+}
+
+int iem_rmu_error(iem_rmu *rp, const double *d_x, const double *d_s, const double *d_y, const double *d_zL, const double *d_zU, const double *d_vL, const double *d_vU,
+                  const double *d_r, const double *d_c, double *d_out) {
+  if (!rp) return fail(IEM_E_ARG, "null argument");
+  const iem_barrier *b = rp->q->s->b;
+  if (barrier_state_missing(b, d_x, d_s, d_y, d_zL, d_zU, d_vL, d_vU) || (b->nvar && !d_r) || (b->ncon && !d_c) || !d_out) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = b->m;
+  DevGuard dg_(m->device);
+  RmuArgsH A = rmu_args(rp);
+  A.x = d_x; A.s = d_s; A.y = d_y; A.zL = d_zL; A.zU = d_zU; A.vL = d_vL; A.vU = d_vU; A.r = d_r; A.c = d_c; A.out = d_out;
+  // the seed: the maxima start from +0.0, the minimum from the bits of +inf (a device-to-device copy is a capturable node)
+  HIP_TRY(hipMemcpyAsync(d_out, rp->d_blk + kRmuWords + kRmuStage, kRmuOut * 8, hipMemcpyDeviceToDevice, m->stream));
+  return kkt_launch_raw(m, m->rmu.error, &A, sizeof A, b->n_wg, 256);
+}
+
+int iem_rmu_update(iem_rmu *rp, const double *d_out32) {
+  if (!rp || !d_out32) return fail(IEM_E_ARG, "null argument");
+  iem_model *m = rp->q->s->b->m;
+  DevGuard dg_(m->device);
+  RmuArgsH A = rmu_args(rp);
+  A.w = d_out32;
+  return kkt_launch_raw(m, m->rmu.update, &A, sizeof A, 1, 64);
+}
+
+int iem_rmu_trigger(iem_rmu *rp, int which, double *d_alpha) {
+  if (which != 0 && which != 1) return fail(IEM_E_ARG, "iem_rmu_trigger: which must be 0 (the original search) or 1 (the inner search)");
+  if (!rp || !d_alpha) return fail(IEM_E_ARG, "null argument");
+  const iem_search *fs = which ? rp->q->inner : rp->q->s;
+  iem_model *m = fs->b->m;
+  DevGuard dg_(m->device);
+  RmuArgsH A = rmu_args(rp);
+  A.ctl = fs->d_ctl; A.alpha = d_alpha; A.which = which;
+  A.gamma_theta = fs->opt.gamma_theta; A.gamma_phi = fs->opt.gamma_phi; A.delta = fs->opt.delta; A.s_theta = fs->opt.s_theta; A.s_phi = fs->opt.s_phi;
+  return kkt_launch_raw(m, m->rmu.trigger, &A, sizeof A, 1, 64);
+}
+
+int iem_rmu_device(const iem_rmu *rp, double **d_block) {
+  if (!rp) return fail(IEM_E_ARG, "null argument");
+  if (d_block) *d_block = rp->d_blk;
+  return IEM_OK;
+}
+
+int iem_rmu_state(iem_rmu *rp, iem_rmu_state_t *out) {
+  if (!rp || !out) return fail(IEM_E_ARG, "null argument");
+  if (out->struct_size < sizeof(uint64_t)) return fail(IEM_E_ARG, "iem_rmu_state: set struct_size to sizeof(iem_rmu_state_t) before the call");
+  iem_model *m = rp->q->s->b->m;
+  DevGuard dg_(m->device);
+  RmuArgsH A = rmu_args(rp);
+  A.out = rp->d_blk + kRmuWords;
+  int rc = kkt_launch_raw(m, m->rmu.gather, &A, sizeof A, 1, 64);
+  if (rc) return rc;
+  uint64_t w[kRmuStage];
+  HIP_TRY(hipMemcpyAsync(w, rp->d_blk + kRmuWords, sizeof w, hipMemcpyDeviceToHost, m->stream));      // the ONE copy: three blocks
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  iem_rmu_state_t v;
+  static_assert(sizeof v == 28 * 8, "iem_rmu_state_t: struct_size, words 0-10 of the own block, 0-11 of the restoration block, 0-3 of the iem_resto block");
+  v.struct_size = std::min<uint64_t>(out->struct_size, sizeof v);
+  std::memcpy(&v.status, w, 11 * 8);
+  std::memcpy(&v.mu, w + 16, 12 * 8);
+  std::memcpy(&v.resto_state, w + 32, 4 * 8);
+  std::memcpy(out, &v, (size_t)v.struct_size);      // never more than the caller's struct holds
   return IEM_OK;
 }
 

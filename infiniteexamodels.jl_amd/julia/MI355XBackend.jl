@@ -1151,6 +1151,76 @@ function resto_device(r::Restoration)
     return p[1][], p[2][], p[3][], p[4][], blk[]
 end
 
+# ---- the restoration phase's barrier parameter (include/iem.h: iem_rmu_*, iem_resto_bind_mu) -----------------------------------------
+# The restoration problem's own mu ON a Restoration: rmu_enter! in front of resto_enter! (mu_R = max(mu, max |inf|) on the device), per
+# iteration rmu_error! (32 words: resto_error! at mu = 0, the products' extremes, six candidates) and rmu_update! (the monotone rule,
+# STATIONARY, the inner filter emptied iff mu moved), rmu_trigger! behind every accept (Ipopt's alpha_min), rmu_state — the one
+# read-back.  bind_mu!(r, rp) makes every resto_*! call read mu, tau and zeta from the restoration block (their scalar arguments are
+# then ignored); rmu_bind_inner! binds the inner search to the same block.  Finalize (or let go of) the object before its Restoration.
+# UNEXECUTED, like the rest.
+struct IemRmuOpts          # iem_rmu_opts_t
+    struct_size::UInt64
+    kappa_eps::Float64; kappa_mu::Float64; tau_min::Float64; tol::Float64; mu_floor::Float64; s_max::Float64; gamma_alpha::Float64
+end
+struct IemRmuState         # iem_rmu_state_t: the own block, the restoration block, the block of the Restoration
+    struct_size::UInt64
+    status::Int64          # 0 iterating, 1 stationary, 2 unusable
+    flags::Int64           # bit 0 mu changed in the last update, bit 1 its ladder was truncated
+    decreases_last::Int64; decreases::Int64
+    e0::Float64; e_mu::Float64; mu_enter::Float64; inf_enter::Float64; alpha_min::Float64
+    triggers_orig::Int64; triggers_inner::Int64
+    mu::Float64; tau::Float64; zeta::Float64; mu_e0::Float64; mu_e_mu::Float64; mu_e_d::Float64; mu_e_p::Float64; mu_e_c0::Float64
+    mu_status::Int64; mu_flags::Int64; mu_decreases::Int64; mu_updates::Int64
+    resto_state::Int64     # 0 none, 1 active, 2 return
+    theta_start::Float64; theta::Float64; phi::Float64
+end
+const RMU_K = 6            # IEM_RMU_K: the candidates of one update
+mutable struct RestorationParameter
+    rp::Ptr{Cvoid}
+    resto::Restoration                       # borrowed: kept alive
+    orig::Union{Nothing, BarrierParameter}   # the ORIGINAL problem's parameter, borrowed: kept alive
+    inner_mu::Ptr{Cvoid}                     # the restoration block's iem_mu object: owned by the object
+end
+function RestorationParameter(r::Restoration, orig::Union{Nothing, BarrierParameter} = nothing; kappa_eps = 10.0, kappa_mu = 0.2, tau_min = 0.99, tol = 1e-8,
+                              mu_floor = 1e-11, s_max = 100.0, gamma_alpha = 0.05)
+    opts = Ref(IemRmuOpts(sizeof(IemRmuOpts), kappa_eps, kappa_mu, tau_min, tol, mu_floor, s_max, gamma_alpha))
+    rp, par = Ref{Ptr{Cvoid}}(C_NULL), Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:iem_rmu_create, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{IemRmuOpts}, Ptr{Ptr{Cvoid}}), r.q, orig === nothing ? C_NULL : orig.p, opts, rp))
+    check(ccall((:iem_rmu_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), rp[], par))
+    o = RestorationParameter(rp[], r, orig, par[])
+    finalizer(x -> (x.rp == C_NULL || x.resto.q == C_NULL || ccall((:iem_rmu_destroy, LIBIEM), Cint, (Ptr{Cvoid},), x.rp); x.rp = C_NULL), o)
+    return o
+end
+# err: the eight of barrier_error! (or the first eight of mu_error!) at this point; mu is ignored where an original parameter was given
+rmu_enter!(o::RestorationParameter, err, mu = 0.0) = check(ccall((:iem_rmu_enter, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cdouble), o.rp, dptr(err), mu))
+# out: 32 doubles; res is required
+function rmu_error!(o::RestorationParameter, state, res, cons, out)
+    check(ccall((:iem_rmu_error, LIBIEM), Cint, (Ptr{Cvoid}, ntuple(_ -> Ptr{Float64}, 10)...),
+                o.rp, spptr(state[1]), spptr(state[2]), spptr(state[3]), spptr(state[4]), spptr(state[5]), spptr(state[6]), spptr(state[7]), spptr(res), spptr(cons), dptr(out)))
+    return out
+end
+rmu_update!(o::RestorationParameter, out32) = check(ccall((:iem_rmu_update, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Float64}), o.rp, dptr(out32)))
+# which = 0: the original search of the Restoration, 1: its inner search; alpha: that search's step lengths
+rmu_trigger!(o::RestorationParameter, which, alpha) = check(ccall((:iem_rmu_trigger, LIBIEM), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}), o.rp, which, dptr(alpha)))
+# the one read-back (one copy, synchronises the stream once)
+function rmu_state(o::RestorationParameter)
+    st = Ref(IemRmuState(sizeof(IemRmuState), 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0))
+    check(ccall((:iem_rmu_state, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{IemRmuState}), o.rp, st))
+    return st[]
+end
+# the own block (16 words of 8 bytes) as a device address
+function rmu_device(o::RestorationParameter)
+    p = Ref{Ptr{Float64}}(C_NULL)
+    check(ccall((:iem_rmu_device, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Ptr{Float64}}), o.rp, p))
+    return p[]
+end
+# bind (or, with nothing, unbind) the Restoration: the first bind of a handle loads a code object, so bind outside a capture
+bind_mu!(r::Restoration, o::Union{Nothing, RestorationParameter}) =
+    check(ccall((:iem_resto_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), r.q, o === nothing ? C_NULL : o.rp))
+# ... and its inner search, to the restoration block (unbind = false) or to nothing
+rmu_bind_inner!(o::RestorationParameter; unbind = false) =
+    check(ccall((:iem_search_bind_mu, LIBIEM), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), o.resto.inner, unbind ? C_NULL : o.inner_mu))
+
 # ---- blob writer ----------------------------------------------------------------------------
 # Serialises a host ExaCore into the wire format of include/iem_blob.h.  [EXT]: the field and
 # type names of ExaModels' internal structs (Objective/Constraint linked lists, SIMDFunction,

@@ -320,6 +320,36 @@ class ConvState(C.Structure):
 CONV_STATUS = ("iterating", "converged", "acceptable", "maxiter", "diverging", "invalid", "tiny_step")
 
 
+class RmuOpts(C.Structure):
+    """``iem_rmu_opts_t``: ``struct_size`` is set by the caller; ``RmuOpts.defaults()`` has the library's values (Ipopt's
+    ``barrier_tol_factor``, ``mu_linear_decrease_factor``, ``tau_min``, ``tol``, the floor of mu, ``s_max``, ``alpha_min_frac``)."""
+    _fields_ = [("struct_size", C.c_uint64)] + [(n, C.c_double) for n in ("kappa_eps", "kappa_mu", "tau_min", "tol", "mu_floor", "s_max", "gamma_alpha")]
+    DEFAULTS = dict(kappa_eps=10.0, kappa_mu=0.2, tau_min=0.99, tol=1e-8, mu_floor=1e-11, s_max=100.0, gamma_alpha=0.05)
+
+    @classmethod
+    def defaults(cls, **over):
+        unknown = set(over) - set(cls.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown restoration parameter option(s): {sorted(unknown)}")
+        o = cls(**{**cls.DEFAULTS, **over})
+        o.struct_size = C.sizeof(cls)
+        return o
+
+
+class RmuState(C.Structure):
+    """``iem_rmu_state_t``: ``struct_size`` (set by the caller), then words 0-10 of the object's own block, words 0-11 of the
+    restoration ``iem_mu`` block and words 0-3 of the ``iem_resto`` block — one copy."""
+    _fields_ = ([("struct_size", C.c_uint64)] + [(n, C.c_int64) for n in ("status", "flags", "decreases_last", "decreases")] +
+                [(n, C.c_double) for n in ("e0", "e_mu", "mu_enter", "inf_enter", "alpha_min")] + [(n, C.c_int64) for n in ("triggers_orig", "triggers_inner")] +
+                [(n, C.c_double) for n in ("mu", "tau", "zeta", "mu_e0", "mu_e_mu", "mu_e_d", "mu_e_p", "mu_e_c0")] +
+                [(n, C.c_int64) for n in ("mu_status", "mu_flags", "mu_decreases", "mu_updates")] +
+                [("resto_state", C.c_int64)] + [(n, C.c_double) for n in ("theta_start", "theta", "phi")])
+
+
+RMU_STATUS = ("iterating", "stationary", "unusable")
+RMU_K = 6
+
+
 class KernelInfo(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("kind", C.c_int32), ("jit", C.c_int32), ("grid", C.c_int64 * 3),
                 ("lds_bytes", C.c_int64), ("alg_bytes_read", C.c_int64), ("alg_bytes_written", C.c_int64)]
@@ -331,7 +361,7 @@ SYMBOLS = ["iem_create", "iem_create_opts", "iem_create_sharded", "iem_shard_inf
            "iem_destroy", "iem_meta", "iem_template_info", "iem_kernel_info", "iem_get_host", "iem_set_stream",
            "iem_synchronize", "iem_set_parameter", "iem_obj", "iem_obj_device", "iem_obj_begin", "iem_obj_end", "iem_grad", "iem_cons",
            "iem_jac_coord", "iem_hess_coord", "iem_jac_hess_coord", "iem_eval_trial", "iem_eval_accepted", "iem_eval_all", "iem_lagrad_prepare", "iem_lagrad", "iem_eval_residual", "iem_scaled_prepare", "iem_jac_rowmax", "iem_cons_scaled", "iem_jac_coord_scaled", "iem_scaled_phase_prepare", "iem_grad_scaled", "iem_hess_coord_scaled", "iem_eval_trial_scaled", "iem_eval_accepted_scaled", "iem_kktprod_prepare", "iem_kktprod", "iem_jprod", "iem_jtprod", "iem_hprod", "iem_param_prepare", "iem_jpprod", "iem_jptprod", "iem_hpprod", "iem_hptprod", "iem_hppprod_prepare", "iem_hppprod", "iem_param_coord_prepare", "iem_kernel_count", "iem_param_coord_nnz", "iem_jacp_structure", "iem_hessxp_structure", "iem_hesspp_structure", "iem_jacp_coord", "iem_hessp_coord", "iem_jac_structure", "iem_hess_structure",
-           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_resto_create", "iem_resto_destroy", "iem_resto_search", "iem_resto_enter", "iem_resto_terms", "iem_resto_step", "iem_resto_merit", "iem_resto_begin", "iem_resto_trial", "iem_resto_update", "iem_resto_error", "iem_resto_check", "iem_resto_leave", "iem_resto_device", "iem_resto_state", "iem_resto_source", "iem_mu_create", "iem_mu_destroy", "iem_mu_reset", "iem_mu_error", "iem_mu_update", "iem_mu_device", "iem_mu_state", "iem_barrier_bind_mu", "iem_search_bind_mu", "iem_soc_bind_mu", "iem_mu_source", "iem_barrier_mu_source", "iem_amu_create", "iem_amu_destroy", "iem_amu_reset", "iem_amu_probe", "iem_amu_update", "iem_amu_device", "iem_amu_state", "iem_amu_source", "iem_qf_create", "iem_qf_destroy", "iem_qf_reset", "iem_qf_begin", "iem_qf_alpha", "iem_qf_value", "iem_qf_update", "iem_qf_device", "iem_qf_state", "iem_qf_source", "iem_mpc_create", "iem_mpc_destroy", "iem_mpc_reset", "iem_mpc_bind_mu", "iem_mpc_terms", "iem_mpc_step", "iem_mpc_select", "iem_mpc_device", "iem_mpc_state", "iem_mpc_source", "iem_init_create", "iem_init_destroy", "iem_init_reset", "iem_init_ls_terms", "iem_init_ls_apply", "iem_init_warm", "iem_init_mu", "iem_init_device", "iem_init_state", "iem_init_source", "iem_conv_create", "iem_conv_destroy", "iem_conv_reset", "iem_conv_check", "iem_conv_keep", "iem_conv_restore", "iem_conv_step", "iem_conv_kept", "iem_conv_device", "iem_conv_state", "iem_conv_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
+           "iem_jac_structure_device", "iem_hess_structure_device", "iem_csr_values", "iem_csr_values32", "iem_csr_spmv", "iem_kkt_chain_factor", "iem_kkt_chain_level", "iem_kkt_hub_level", "iem_kkt_chain_solve", "iem_kkt_chain_solve_lanes", "iem_kkt_chain_solve_many", "iem_kkt_source", "iem_kkt_create", "iem_kkt_destroy", "iem_kkt_info", "iem_kkt_layout", "iem_kkt_analyse_blob", "iem_kkt_assemble", "iem_kkt_factor", "iem_kkt_solve", "iem_kkt_solve_many", "iem_kkt_residual", "iem_kkt_solve_refined", "iem_kkt_assemble_diag", "iem_kkt_residual_diag", "iem_kkt_solve_refined_diag", "iem_kkt_diag_source", "iem_kkt_border_factor", "iem_kkt_border_solve", "iem_kkt_border_source", "iem_kkt_set_border", "iem_kkt_factor_async", "iem_barrier_create", "iem_barrier_analyse", "iem_barrier_destroy", "iem_barrier_info", "iem_barrier_start", "iem_barrier_terms", "iem_barrier_step", "iem_barrier_update", "iem_barrier_error", "iem_barrier_merit", "iem_barrier_source", "iem_search_create", "iem_search_destroy", "iem_search_reset", "iem_search_begin", "iem_search_trial", "iem_search_accept", "iem_search_device", "iem_search_state", "iem_search_source", "iem_soc_create", "iem_soc_destroy", "iem_soc_open", "iem_soc_rhs", "iem_soc_trial", "iem_soc_accept", "iem_soc_select", "iem_soc_device", "iem_soc_state", "iem_soc_source", "iem_resto_create", "iem_resto_destroy", "iem_resto_search", "iem_resto_enter", "iem_resto_terms", "iem_resto_step", "iem_resto_merit", "iem_resto_begin", "iem_resto_trial", "iem_resto_update", "iem_resto_error", "iem_resto_check", "iem_resto_leave", "iem_resto_device", "iem_resto_state", "iem_resto_source", "iem_mu_create", "iem_mu_destroy", "iem_mu_reset", "iem_mu_error", "iem_mu_update", "iem_mu_device", "iem_mu_state", "iem_barrier_bind_mu", "iem_search_bind_mu", "iem_soc_bind_mu", "iem_mu_source", "iem_barrier_mu_source", "iem_amu_create", "iem_amu_destroy", "iem_amu_reset", "iem_amu_probe", "iem_amu_update", "iem_amu_device", "iem_amu_state", "iem_amu_source", "iem_qf_create", "iem_qf_destroy", "iem_qf_reset", "iem_qf_begin", "iem_qf_alpha", "iem_qf_value", "iem_qf_update", "iem_qf_device", "iem_qf_state", "iem_qf_source", "iem_mpc_create", "iem_mpc_destroy", "iem_mpc_reset", "iem_mpc_bind_mu", "iem_mpc_terms", "iem_mpc_step", "iem_mpc_select", "iem_mpc_device", "iem_mpc_state", "iem_mpc_source", "iem_init_create", "iem_init_destroy", "iem_init_reset", "iem_init_ls_terms", "iem_init_ls_apply", "iem_init_warm", "iem_init_mu", "iem_init_device", "iem_init_state", "iem_init_source", "iem_conv_create", "iem_conv_destroy", "iem_conv_reset", "iem_conv_check", "iem_conv_keep", "iem_conv_restore", "iem_conv_step", "iem_conv_kept", "iem_conv_device", "iem_conv_state", "iem_conv_source", "iem_rmu_create", "iem_rmu_destroy", "iem_rmu_mu", "iem_rmu_enter", "iem_rmu_error", "iem_rmu_update", "iem_rmu_trigger", "iem_rmu_device", "iem_rmu_state", "iem_resto_bind_mu", "iem_rmu_source", "iem_resto_mu_source", "iem_emit_source", "iem_fixed_source", "iem_emit_launch_plan", "iem_blob_hess_structure", "iem_blob_param_coord_structure", "iem_blob_array", "iem_free",
            "iem_set_option", "iem_time_kernels", "iem_tuner_choice", "iem_tune", "iem_last_error", "iem_version"]
 
 
@@ -573,6 +603,18 @@ def lib():
     L.iem_conv_device.argtypes = [vp, C.POINTER(vp)]
     L.iem_conv_state.argtypes = [vp, C.POINTER(ConvState)]
     L.iem_conv_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.iem_rmu_create.argtypes = [vp, vp, C.POINTER(RmuOpts), C.POINTER(vp)]
+    L.iem_rmu_destroy.argtypes = [vp]
+    L.iem_rmu_mu.argtypes = [vp, C.POINTER(vp)]
+    L.iem_rmu_enter.argtypes = [vp, vp, dbl]
+    L.iem_rmu_error.argtypes = [vp] + [vp] * 9 + [vp]
+    L.iem_rmu_update.argtypes = [vp, vp]
+    L.iem_rmu_trigger.argtypes = [vp, i32, vp]
+    L.iem_rmu_device.argtypes = [vp, C.POINTER(vp)]
+    L.iem_rmu_state.argtypes = [vp, C.POINTER(RmuState)]
+    L.iem_resto_bind_mu.argtypes = [vp, vp]
+    L.iem_rmu_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.iem_resto_mu_source.argtypes = [C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.iem_emit_source.restype = i32
     L.iem_fixed_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(C.c_uint64)]
@@ -749,6 +791,18 @@ def conv_source():
     ``conv_keep`` / ``conv_restore`` / ``conv_reset``: the ``iem_conv_*`` calls) and its cache key.  A code object of its own: not
     one of :func:`fixed_sources`."""
     return _source(lib().iem_conv_source)
+
+
+def rmu_source():
+    """HIP source of the restoration parameter's kernels (``rmu_error`` / ``rmu_enter`` / ``rmu_update`` / ``rmu_trigger`` /
+    ``rmu_gather``: the ``iem_rmu_*`` calls) and its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
+    return _source(lib().iem_rmu_source)
+
+
+def resto_mu_source():
+    """HIP source of the BOUND variant of the restoration kernels (``iem_resto_bind_mu``: the text of :func:`resto_source` with ``mu``,
+    ``tau`` and ``zeta`` read from the restoration block) and its cache key.  A code object of its own: not one of :func:`fixed_sources`."""
+    return _source(lib().iem_resto_mu_source)
 
 
 def barrier_mu_source():
